@@ -434,6 +434,48 @@ def reduce_max(elapsed, dist):
     return float(t.item())
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, sm, wl):
+    """--dump-outputs: what a caller of plv_camera_frame holds after the last step of the main timed segment (the filter's mean and
+    covariance, the clone window, the calibration, the frame's tracked points and lines), one DIR/<name>.npy each in float32 / float64
+    (feature ids as float64: exact below 2^53; an empty array is left out), so that two builds run on the same stream can be compared output
+    for output."""
+    st, ctx = sm.state, sm.ctx       # (timed_segment has synchronised the context)
+    ts = sorted(st.clones)
+    out = {
+        "imu_state": np.frombuffer(st.imu, dtype=np.float64)[:16].copy(),      # q (JPL, 4), p, v, bg, ba
+        "state_time": np.array([st.time], dtype=np.float64),
+        "covariance": ctx.cov_download(st.n),
+        "clone_times": np.array(ts, dtype=np.float64),
+        "clone_q": np.array([st.clones[t].q for t in ts], dtype=np.float64).reshape(-1, 4),
+        "clone_p": np.array([st.clones[t].p for t in ts], dtype=np.float64).reshape(-1, 3),
+        "slam_ids": np.array(sorted(st.slam), dtype=np.float64),
+        "slam_p": np.array([st.slam[k].p for k in sorted(st.slam)], dtype=np.float64).reshape(-1, 3),
+    }
+    if st.cam_intr is not None:
+        out["cam_intrinsics"] = np.array(st.cam_intr.v, dtype=np.float64)
+        out["cam_extrinsics"] = np.concatenate([st.cam_ext.q, st.cam_ext.p]).astype(np.float64)
+        out["cam_dt"] = np.array(st.cam_dt.v, dtype=np.float64)
+    if st.wheel_intr is not None:
+        out["wheel_intrinsics"] = np.array(st.wheel_intr.v, dtype=np.float64)
+        out["wheel_extrinsics"] = np.concatenate([st.wheel_ext.q, st.wheel_ext.p]).astype(np.float64)
+        out["wheel_dt"] = np.array(st.wheel_dt.v, dtype=np.float64)
+    pts, ids = ctx.tracker_last()
+    out["tracked_points"], out["tracked_ids"] = pts.astype(np.float32), ids.astype(np.float64)
+    if wl["lines"]:
+        lines, lids = ctx.line_tracker_last()
+        out["tracked_lines"], out["tracked_line_ids"] = lines.astype(np.float32), lids.astype(np.float64)
+    out = {k: a for k, a in out.items() if a.size}      # (nothing held, nothing written: e.g. no SLAM landmarks under max_slam 0)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"bench: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -462,6 +504,8 @@ def main():
     ap.add_argument("--pin", choices=("none", "node", "ccx", "ccx2"), default=os.environ.get("PLV_BENCH_PIN", "ccx"),
                     help="CPU affinity of this process and the library's threads: the cores of the GPU's NUMA node, or one L3 complex of that "
                          "node (the least busy one; with several ranks, one complex per rank)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the main timed segment, write what its last step computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: exercises the multi-process plumbing only (tests/test_bench_dist.py)")
     args = ap.parse_args()
@@ -693,6 +737,8 @@ def main():
     pl.staged, pl.pinned = args.images == "resident", args.images == "pinned"
     seg = timed_segment(args.steps)                                   # (1) images resident in HBM -> `value`
     pl.staged, pl.pinned = True, False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sm, wl)
     if os.environ.get("PLV_BENCH_FINGERPRINT"):     # (determinism checks: the filter's state after the timed segment, to the last bit)
         print("[fingerprint] p = %r  q = %r  trace(P) = %r  routes = %r" % (tuple(float(x) for x in sm.state.imu.p), tuple(float(x) for x in sm.state.imu.q),
                                                                           float(np.trace(ctx.cov_download(sm.state.n))), pkg.route_counts()), file=sys.stderr)

@@ -48,7 +48,12 @@ def test_line_host_stage_under_sanitizers(maps, tmp_path, san):
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1", ASAN_OPTIONS="detect_leaks=0")
-    r = subprocess.run([exe, maps, "6"], capture_output=True, text=True, env=env, timeout=600)
+    run = [exe, maps, "6"]
+    if "thread" in san and shutil.which("setarch"):
+        # gcc 11's ThreadSanitizer knows the address layout of 28-bit mmap randomisation only; with more bits the program lands outside
+        # it ("unexpected memory mapping").  This one process runs without randomisation instead.
+        run = ["setarch", os.uname().machine, "-R"] + run
+    r = subprocess.run(run, capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0 and "ok:" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
     import re
     m = re.search(r"(\d+) kept by the assignment, (\d+) matched", r.stdout)
