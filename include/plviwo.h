@@ -708,7 +708,12 @@ int plv_state_boxplus(int n_var, const plv_state_var *vars, const double *dx, in
  * opt_lines is given, the join of an asynchronous line feed, plv_camera_update_lines on the updated state and its dx applied the
  * same way.  `st` must stay current under plv_state_boxplus: its clone arrays are the `val` / `out` arrays of the clone variables
  * and its calibration fields are their `mirror`s.  The point half's database hand-back (CamHelper::cleanup_features) is run while
- * the line update executes on the device.  Outputs as in the two calls; line_db_size = LineFeatureDatabase size after the feed. */
+ * the line update executes on the device.  Outputs as in the two calls; line_db_size = LineFeatureDatabase size after the feed.
+ * Failures: the arguments (null pointers, max_slam > 0, a variable of an unknown kind or with id + size beyond the covariance — the
+ * test of plv_state_boxplus) are checked before anything is enqueued, and a refused call (PLV_E_BADARG) leaves the covariance, the
+ * variables and the feature databases as they were.  On any other return than PLV_OK the covariance and the variables still describe
+ * one estimate: as they were before the call when the point half failed, with the point update applied to both when the line half
+ * failed after it. */
 typedef struct plv_try_update {
   const plv_update_options *opt_points;
   const plv_update_options *opt_lines;   /* NULL: points only */
@@ -731,7 +736,11 @@ int plv_camera_try_update(plv_ctx *ctx, const plv_state_view *st, plv_try_update
  * plv_camera_try_update.  The image comes from HBM slot `slot` (plv_image_stage; slot >= 0) or from the host (img, stride).
  * update == NULL: feed only (not initialised yet / fewer than intr_order + 1 clones, CamHelper.cpp:615-616); with lines on and
  * update->opt_lines == NULL the lines are tracked but not used.  `st` is the state at the time of the call (the extrinsics and
- * intrinsics the vanishing points are made from are st's).  line_db_size: LineFeatureDatabase size after the feed. */
+ * intrinsics the vanishing points are made from are st's).  line_db_size: LineFeatureDatabase size after the feed.
+ * Failures: update arguments plv_camera_try_update refuses are checked first; the frame is then fed as one without an update and
+ * the call returns PLV_E_BADARG.  On any return other than PLV_OK the covariance and the variables are as plv_camera_try_update
+ * leaves them (a refused or failing point half: as before the call — a point update already enqueued behind the flow is undone on
+ * the device), and the tracker and line databases hold the frame's feed. */
 typedef struct plv_camera_frame_io {
   double timestamp;
   int slot;                /* >= 0: staged image; < 0: img / stride */

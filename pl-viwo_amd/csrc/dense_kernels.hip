@@ -132,7 +132,8 @@ __global__ void __launch_bounds__(1024) ekf_commit_kernel(double *__restrict__ P
                                                          int mirror_words, const int *__restrict__ skip, double *__restrict__ dx,
                                                          const unsigned *__restrict__ mirror2_src, unsigned *__restrict__ mirror2_dst,
                                                          int mirror2_words, unsigned *done_word, unsigned done_val,
-                                                         int *__restrict__ applied_out, const int *__restrict__ cap_words, int cap) {
+                                                         int *__restrict__ applied_out, const int *__restrict__ cap_words, int cap,
+                                                         double *__restrict__ save, unsigned *__restrict__ save_word, unsigned save_seq) {
   // done_word (pinned, optional; the launch then has ONE workgroup): behind the mirrors AND the covariance commit the workgroup stores
   // done_val there, and the host, spinning on the word, knows both the results and the covariance to be final
   const bool skipped = skip && *skip == 0;  // (the gate accepted nothing: no correction, the covariance stays)
@@ -148,6 +149,9 @@ __global__ void __launch_bounds__(1024) ekf_commit_kernel(double *__restrict__ P
   // applied_out: "this update changed the state" — StateHelper::EKFUpdate reached its mean update (:156-168): read by a launch that is
   // enqueued behind the update before the host has seen its result and applies dx to its own copy of the state (the chained line launch)
   if (applied_out && blockIdx.x == 0 && threadIdx.x == 0) *applied_out = (skipped || capped || *flag != 0) ? 0 : 1;
+  // save (a speculative point batch, plv_ctx::cov_save): both halves of what the commit overwrites, and save_seq in save_word when it
+  // did — the host restores them when nobody uses the update (plv_points_spec_undo; (P - dC) + dC would not be P again)
+  if (save_word && blockIdx.x == 0 && threadIdx.x == 0) *save_word = (skipped || capped || *flag != 0) ? 0u : save_seq;
   if (blockIdx.x == 0) {
     if (skipped && dx) {
       for (int i = threadIdx.x; i < n; i += blockDim.x) dx[i] = 0.0;
@@ -162,7 +166,9 @@ __global__ void __launch_bounds__(1024) ekf_commit_kernel(double *__restrict__ P
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < n * n; idx += gridDim.x * blockDim.x) {
       int j = idx / n, i = idx - j * n;
       if (i <= j) {
-        double v = P[(size_t)j * ldp + i] - dC[(size_t)j * ldc + i];
+        const double u = P[(size_t)j * ldp + i];
+        if (save) save[(size_t)j * n + i] = u, save[(size_t)i * n + j] = P[(size_t)i * ldp + j];
+        double v = u - dC[(size_t)j * ldc + i];
         P[(size_t)j * ldp + i] = v;
         P[(size_t)i * ldp + j] = v;
       }
@@ -213,11 +219,24 @@ static int launch_ekf_commit(plv_ctx *ctx, double *d_P, int n, int ldp, const do
                        d_flag, (const unsigned *)mirror_src, (unsigned *)mirror_dst, (int)(mirror_bytes / 4), ctx->skip_word, d_dx,
                        (const unsigned *)(mirror_dst ? ctx->mirror2_src : nullptr), (unsigned *)(mirror_dst ? ctx->mirror2_dst : nullptr),
                        (int)((ctx->mirror2_bytes + 3) / 4), dw, ctx->update_seq, mirror_dst ? ctx->applied_word : nullptr,
-                       mirror_dst ? ctx->cap_words : nullptr, ctx->cap);
+                       mirror_dst ? ctx->cap_words : nullptr, ctx->cap, ctx->cov_save, ctx->cov_save_word, ctx->cov_save_seq);
     ctx->update_word_used = dw != nullptr;
     if (mirror_dst && ctx->applied_word) ctx->applied_used = true;
     if (mirror_dst && ctx->mirror2_dst) ctx->mirror2_taken = true;
   }
+  PLV_HIP_CHECK(hipGetLastError());
+  return PLV_OK;
+}
+
+// The covariance ekf_commit_kernel saved for a speculative point batch copied back (P: n x n, ld = n), when the save word says that the
+// batch's commit (seq) did overwrite it.
+__global__ void __launch_bounds__(256) cov_restore_kernel(double *__restrict__ P, const double *__restrict__ save, int nn,
+                                                          const unsigned *__restrict__ save_word, unsigned seq) {
+  if (*save_word != seq) return;
+  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < nn; idx += gridDim.x * blockDim.x) P[idx] = save[idx];
+}
+int launch_cov_restore(plv_ctx *ctx, double *d_P, int n, const double *save, const unsigned *save_word, unsigned seq) {
+  hipLaunchKernelGGL(cov_restore_kernel, dim3(std::min(64, cdiv(n * n, 256))), dim3(256), 0, ctx->stream, d_P, save, n * n, save_word, seq);
   PLV_HIP_CHECK(hipGetLastError());
   return PLV_OK;
 }

@@ -410,6 +410,12 @@ int plv_jacobian_columns(const plv_state_view *st, const plv_tracks *tr, int *co
 // in both cases.
 typedef plv_ctx_update_state::PointJob PointJob;
 static PointJob &point_job(plv_ctx *ctx) { return plv_update_state(ctx)->point_job; }
+// the commits of a speculative point batch (its launch, and a re-run inside the wait) save the covariance they overwrite
+static void spec_save_arm(plv_ctx *ctx, plv_ctx_update_state *us, bool on) {
+  ctx->cov_save = on ? us->spec_save.as<double>() : nullptr;
+  ctx->cov_save_word = on ? us->chain_words.as<unsigned>() + 1 : nullptr;
+  ctx->cov_save_seq = on ? us->spec_save_seq : 0;
+}
 static hipEvent_t g_ce[3] = {nullptr, nullptr, nullptr};
 
 int plv_points_update_submit(plv_ctx *ctx, const plv_state_view *st, const plv_tracks *all, const plv_tri_options *tri, const uint8_t *flags,
@@ -453,8 +459,17 @@ int plv_points_update_submit(plv_ctx *ctx, const plv_state_view *st, const plv_t
   us->applied_word = us->chain_words.as<int>();
   ctx->applied_word = us->applied_word, ctx->applied_used = false;
   ctx->cap_words = spec ? ft.d_words + 3 : nullptr, ctx->cap = max_sel;
+  us->spec_save_seq = 0;
+  if (spec) {  // (the commit saves what it overwrites: plv_points_spec_undo)
+    TRY(us->spec_save.reserve((size_t)ctx->cov_n * ctx->cov_n * 8));
+    if (++us->spec_save_count == 0) ++us->spec_save_count;  // (0: no batch)
+    us->spec_save_seq = us->spec_save_count;
+    us->spec_save_n = ctx->cov_n;
+    spec_save_arm(ctx, us, true);
+  }
   int rc = plv_msckf_update_resident_launch(ctx, sigma2, chi2_mult, res_norm_gate);
   ctx->cap_words = nullptr;
+  spec_save_arm(ctx, us, false);
   us->applied_armed = rc == PLV_OK && ctx->applied_used;
   ctx->applied_word = nullptr, ctx->applied_used = false;
   us->pt_tri_p = (const double *)(us->tri.as<char>() + ft.o_p), us->pt_tri_ok = (const unsigned char *)(us->tri.as<char>() + ft.o_ok), us->pt_tri_F = F;
@@ -500,7 +515,9 @@ int plv_points_update_collect(plv_ctx *ctx, double *p_out, uint8_t *ok_out, doub
   plv::frame_mark("@ host work inside the point wait done");
   plv::NsScope ns_pw(plv::counters().points_wait_ns);
   plv::HostPhase ph_d("points fused: wait");
+  if (J.spec && us->spec_save_seq) spec_save_arm(ctx, us, true);
   if (rc == PLV_OK) rc = plv_msckf_update_resident_wait(ctx, accepted, n_rows, dx);  // (ends at the update's last kernel)
+  spec_save_arm(ctx, us, false);
   if (rc != PLV_OK || !J.mirrored) PLV_HIP_CHECK(plv::stream_sync(ctx->stream));    // (the copy command enqueued behind it)
   ph_d.stop();
   plv::frame_mark("@ point update collected");
@@ -528,6 +545,29 @@ int plv_points_update_collect(plv_ctx *ctx, double *p_out, uint8_t *ok_out, doub
     if (spec_over) *spec_over = 0;
   }
   return rc;
+}
+
+extern "C" int plv_camera_lines_job_pending(plv_ctx *ctx);  // line_api.hip
+extern "C" void plv_camera_lines_job_abort(plv_ctx *ctx);
+// (internal, tracker_api.hip) the speculative point batch was collected and nobody will use its update: the covariance as the batch found
+// it.  The stream is waited for and a line launch chained behind the batch is aborted first (its commit sits on top of the batch's: the
+// saved covariance undoes both).  Nothing is restored when the batch committed nothing (rejected, capped, skipped, ended at the gate).
+int plv_points_spec_undo(plv_ctx *ctx) {
+  auto *us = plv_update_state(ctx);
+  const unsigned seq = us->spec_save_seq;
+  us->spec_save_seq = 0;
+  if (!seq) return PLV_OK;
+  PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
+  if (plv_camera_lines_job_pending(ctx)) plv_camera_lines_job_abort(ctx);
+  if (us->spec_save_n != ctx->cov_n) {
+    set_last_error("plv_points_spec_undo: the covariance changed size under a speculative point update");
+    return PLV_E_DEVICE;
+  }
+  TRY(launch_cov_restore(ctx, ctx->d_P.as<double>(), ctx->cov_n, us->spec_save.as<double>(), us->chain_words.as<unsigned>() + 1, seq));
+  PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
+  ++ctx->gather_stamp;
+  ctx->cov_host_synced = ctx->gather_stamp;
+  return PLV_OK;
 }
 
 int plv_points_update_fused(plv_ctx *ctx, const plv_state_view *st, const plv_tracks *all, const plv_tri_options *tri,

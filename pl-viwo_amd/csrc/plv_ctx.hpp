@@ -543,6 +543,11 @@ struct plv_ctx {
   // set by the caller of a speculative point update (plv_points_update_submit) around its launch: ekf_commit_kernel's cap test
   const int *cap_words = nullptr;
   int cap = 0;
+  // set around the launch of a speculative point update and its re-run (RedoW): ekf_commit_kernel saves the covariance it overwrites in
+  // cov_save (n x n) and stores cov_save_seq in cov_save_word — what plv_points_spec_undo restores when nobody uses the update
+  double *cov_save = nullptr;
+  unsigned *cov_save_word = nullptr;
+  unsigned cov_save_seq = 0;
   // Measurement knob PLV_KNOB_DONE_WORDS — completion words in pinned memory: the last kernel of the flow (word 0) and of an update
   // (word 16) stores the call's sequence number there behind its result block (system-scope release) and the host spins on the word
   // instead of waiting on an event.  Off by default (no gain in the frame, see the knob list).

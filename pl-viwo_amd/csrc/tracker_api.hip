@@ -899,10 +899,12 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
       rc_s = plv_points_update_collect(ctx, cp.data(), cok.data(), ce.data(), cacc.data(), &nrows, dx, start_detection_ahead, ctx, cmem.data(), &count, &over);
     }
     T->chain_ok = false;
+    // (an exit that does not use the batch's update: the covariance goes back to what the batch found, plv_points_spec_undo)
     auto fail = [&](const char *why) {
       plv::set_last_error("speculative point update: %s (host pool %d, device pool %d%s)", why, Fp0, count, over ? ", over the cap" : "");
       for (Cand &c : pool) give_back_all(c);
-      return finish(PLV_E_DEVICE);
+      const int rc_u = plv_points_spec_undo(ctx);
+      return finish(rc_u != PLV_OK ? rc_u : PLV_E_DEVICE);
     };
     if (!same) return fail("the batch was staged for another update than the one asked for");
     if (over || Fp0 > plv::spec_grid(opt->max_msckf)) {
@@ -917,6 +919,7 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
     } else {
       if (rc_s != PLV_OK && rc_s != PLV_E_NOT_PSD) {
         for (Cand &c : pool) give_back_all(c);
+        (void)plv_points_spec_undo(ctx);
         return finish(rc_s);
       }
       if (!known || count != Fp0) return fail("host and device disagree on the pool");
@@ -932,6 +935,7 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
       s_status = rc_s == PLV_E_NOT_PSD ? rc_s : PLV_OK;
       if (rc_s == PLV_E_NOT_PSD) std::fill(dx, dx + ctx->cov_n, 0.0);  // EKFUpdate returned false: nothing changed
       spec_done = true;
+      plv_update_state(ctx)->spec_save_seq = 0;  // (the batch's update is used: nothing to undo)
       ++plv::counters().speculated;
       if (Fp0 > opt->max_msckf) ++plv::counters().spec_over[0];
     }
@@ -1353,13 +1357,25 @@ void plv_tracker_run_deferred(void *arg) {
   f();
 }
 
-int plv_camera_try_update(plv_ctx *ctx, const plv_state_view *st, plv_try_update *io) {
+extern "C" int plv_state_vars_check(int n_var, const plv_state_var *vars, int n_dx);  // init_api.cpp
+// Every argument plv_camera_try_update can refuse, checked before anything is enqueued (plv_camera_frame: before its feed, and so before
+// the speculative point update): a refused call leaves the covariance and the variables as they were.
+static int try_update_args(plv_ctx *ctx, const plv_state_view *st, const plv_try_update *io) {
   if (!ctx || !st || !io || !io->opt_points || !io->dx_points || !io->res_points || (io->n_var > 0 && !io->vars)) return PLV_E_BADARG;
   if (io->opt_lines && (!io->dx_lines || !io->res_lines)) return PLV_E_BADARG;
   if (io->opt_points->max_slam > 0) {  // the in-state landmark updates sit between the two halves and are the caller's
     plv::set_last_error("plv_camera_try_update: max_slam > 0 needs the two-call form (plv_slam_update in between)");
     return PLV_E_BADARG;
   }
+  if (plv_state_vars_check(io->n_var, io->vars, ctx->cov_n) != PLV_OK) {  // (the test plv_state_boxplus makes when dx is applied)
+    plv::set_last_error("plv_camera_try_update: a variable of the list has an unknown kind, no values or an index beyond the covariance (%d)", ctx->cov_n);
+    return PLV_E_BADARG;
+  }
+  return PLV_OK;
+}
+
+int plv_camera_try_update(plv_ctx *ctx, const plv_state_view *st, plv_try_update *io) {
+  TRY(try_update_args(ctx, st, io));
   Tracker *T = trk(ctx);
   const int n = ctx->cov_n;
   auto apply = [&](const plv_update_result &r, const double *dx) {  // StateHelper::EKFUpdate's mean update (:156-168)
@@ -1427,9 +1443,10 @@ int plv_camera_try_update(plv_ctx *ctx, const plv_state_view *st, plv_try_update
   }
   // REF UpdaterCamera.cpp:148-152: get_line_features runs between get_features and msckf_update — the line pool is triangulated on
   // the state as it is before the point update's correction is applied (chained: its launch is already on the stream, staged from st)
-  if (rc == PLV_OK && io->opt_lines && !chained) rc = plv_camera_get_line_features(ctx, st);
+  const int rc_lf = rc == PLV_OK && io->opt_lines && !chained ? plv_camera_get_line_features(ctx, st) : PLV_OK;
   plv::frame_mark("@ update_points returned");
-  if (rc == PLV_OK) rc = apply(*io->res_points, io->dx_points);
+  if (rc == PLV_OK) rc = apply(*io->res_points, io->dx_points);  // (the covariance holds the point update: so does the state)
+  if (rc == PLV_OK) rc = rc_lf;
   if (rc == PLV_OK && io->opt_lines) {
     rc = plv_line_tracker_feed_wait(ctx);
     io->line_db_size = plv_line_db_size_after_feed(ctx);
@@ -1455,6 +1472,10 @@ int plv_camera_try_update(plv_ctx *ctx, const plv_state_view *st, plv_try_update
 // UpdaterCamera::feed_measurement followed by try_update (REF: UpdaterCamera.cpp:77-116, 139-195), one call per camera frame.
 int plv_camera_frame(plv_ctx *ctx, const plv_state_view *st, plv_camera_frame_io *io) {
   if (!ctx || !st || !io || (io->slot < 0 && !io->img)) return PLV_E_BADARG;
+  // update arguments plv_camera_try_update would refuse: the frame is fed as one without an update, and the call returns the refusal
+  // (nothing enqueued for an update that cannot be used)
+  const int rc_args = io->update ? try_update_args(ctx, st, io->update) : PLV_OK;
+  plv_try_update *const upd = rc_args == PLV_OK ? io->update : nullptr;
   plv::NsScope ns(plv::counters().frame_ns);
   struct RuScope {  // PLV_HOST_TIMING: page faults and system time of the caller's thread inside the frame
     struct rusage a;
@@ -1484,16 +1505,17 @@ int plv_camera_frame(plv_ctx *ctx, const plv_state_view *st, plv_camera_frame_io
     ~SpecGuard() {
       T->spec_st = nullptr, T->spec_opt = nullptr;
       if (!T->spec.active) return;
-      T->spec.active = false;  // (an early exit: the update ran, nobody reads it; the covariance on the device is what it left)
+      T->spec.active = false;  // (an early exit: the update ran, nobody reads it; the covariance goes back to what it found)
       const int F = T->spec.F, n = c->cov_n;
       std::vector<double> p(3 * (size_t)F), e(F), dx((size_t)std::max(n, 1));
       std::vector<uint8_t> ok(F), acc(F);
       int rows = 0;
       (void)plv_points_update_collect(c, p.data(), ok.data(), e.data(), acc.data(), &rows, dx.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+      (void)plv_points_spec_undo(c);
     }
   } spec_guard{ctx, Tf};
   Tf->spec.active = false;
-  if (io->update && io->update->opt_points && io->update->opt_points->max_slam == 0) Tf->spec_st = st, Tf->spec_opt = io->update->opt_points;
+  if (upd && upd->opt_points && upd->opt_points->max_slam == 0) Tf->spec_st = st, Tf->spec_opt = upd->opt_points;
   const bool lines = io->use_lines != 0;
   // with lines and an update to follow, the line tracker's host logic runs on the worker thread next to the point update (joined inside
   // plv_camera_try_update) and is posted by the point tracker's feed itself, the moment the frame's point list stands
@@ -1502,8 +1524,8 @@ int plv_camera_frame(plv_ctx *ctx, const plv_state_view *st, plv_camera_frame_io
   int line_feed_rc = PLV_OK;
   double vps[6] = {0, 0, 0, 0, 0, 0};
   if (lines) TRY(plv_vanishing_points(st->R_ItoC, st->intrinsics, vps));
-  if (lines && io->update && io->update->opt_lines) {
-    plv_line_feed_pool_args(ctx, st, io->update->opt_lines);  // (the worker forms the line update's pool at the end of the feed)
+  if (lines && upd && upd->opt_lines) {
+    plv_line_feed_pool_args(ctx, st, upd->opt_lines);  // (the worker forms the line update's pool at the end of the feed)
     Tf->points_ready = [&](int np, const float *pts, const uint64_t *pids) {
       line_feed_posted = true;
       line_feed_rc = plv_line_tracker_feed_async_points(ctx, io->timestamp, vps, np, pts, pids);
@@ -1518,23 +1540,23 @@ int plv_camera_frame(plv_ctx *ctx, const plv_state_view *st, plv_camera_frame_io
   Tf->spec_st = nullptr, Tf->spec_opt = nullptr;
   TRY(rc_feed);
   if (lines) {
-    if (io->update && io->update->opt_lines) {
+    if (upd && upd->opt_lines) {
       if (!line_feed_posted) TRY(plv_line_tracker_feed_async(ctx, io->timestamp, vps));  // (a feed that ended before its point list: first frame, nothing tracked)
       else TRY(line_feed_rc);
     }
     else
       TRY(plv_line_tracker_feed(ctx, io->timestamp, vps));
   }
-  if (!io->update) {
+  if (!upd) {
     io->line_db_size = lines ? plv_line_db_size(ctx) : 0;
-    return PLV_OK;
+    return rc_args;
   }
   rx_feed.stop();
   plv::frame_mark("@ feed done, try_update starts");
-  const int rc = plv_camera_try_update(ctx, st, io->update);
+  const int rc = plv_camera_try_update(ctx, st, upd);
   plv::frame_mark("@ try_update returned");
-  if (lines && !io->update->opt_lines) (void)plv_line_tracker_feed_wait(ctx);
-  io->line_db_size = io->update->opt_lines ? io->update->line_db_size : (lines ? plv_line_db_size(ctx) : 0);
+  if (lines && !upd->opt_lines) (void)plv_line_tracker_feed_wait(ctx);
+  io->line_db_size = upd->opt_lines ? upd->line_db_size : (lines ? plv_line_db_size(ctx) : 0);
   return rc;
 }
 

@@ -68,6 +68,8 @@ void launch_whiten_b(plv_ctx *ctx, const double *Lt, int k, const double *Gs, co
                      const double *d_P, int ldp, int n, const int *d_cols, double *Y0, double *GP, double *d0, const int *use_m);
 int launch_stack_compact(plv_ctx *ctx, const double *d_A, int lda, int nc, const int *d_acc_rows, int F, int mp_max, double *d_dst, int ldd, bool exact_rows = false,
                          int *d_total_out = nullptr /* device word: the rows gathered */);
+// the covariance ekf_commit_kernel saved for a speculative point batch (plv_ctx::cov_save) back into d_P, if that commit (seq) took place
+int launch_cov_restore(plv_ctx *ctx, double *d_P, int n, const double *save, const unsigned *save_word, unsigned seq);
 int launch_stack_zero_rejected(plv_ctx *ctx, double *d_A, int lda, int nc, const int *d_acc_rows, int F, int mp_max);
 int launch_prior_factor(plv_ctx *ctx, hipStream_t st, const double *d_P, int n, int ldp, const int *d_cols, int k);
 int launch_gram_information(plv_ctx *ctx, const double *d_A, int lda, int nc, const int *d_acc_rows, int F, int mp_max);

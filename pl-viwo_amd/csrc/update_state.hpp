@@ -89,7 +89,12 @@ struct plv_ctx_update_state {
   const double *pt_tri_p = nullptr;
   const unsigned char *pt_tri_ok = nullptr;
   int pt_tri_F = 0;
-  plv::DevBuf chain_words;      // home of applied_word
+  plv::DevBuf chain_words;      // home of applied_word [0] and of the speculative batch's save word [1]
+  // the covariance as the last speculative point batch found it (ekf_commit_kernel, plv_ctx::cov_save), valid when the save word holds
+  // spec_save_seq; spec_save_seq = 0: no batch is waiting to be used or undone
+  plv::DevBuf spec_save;
+  unsigned spec_save_seq = 0, spec_save_count = 0;
+  int spec_save_n = 0;
   int *applied_word = nullptr;  // device word ekf_commit_kernel sets to 1 when the point update changed the state (0: dx is not to be applied)
   bool applied_armed = false;   // ... and the last point launch ended in that kernel with the word as its argument
   hipStream_t spec_stream = nullptr;  // upload of a speculative batch (stage_inputs)
@@ -127,6 +132,8 @@ extern "C" int plv_points_update_submit(plv_ctx *ctx, const plv_state_view *st, 
                                         double chi2_mult, double res_norm_gate, const plv_points_spec *spec);
 extern "C" int plv_points_update_collect(plv_ctx *ctx, double *p_out, uint8_t *ok_out, double *err_out, uint8_t *accepted, int *n_rows, double *dx,
                                          void (*before_wait)(void *), void *before_wait_arg, uint8_t *member, int *spec_count, int *spec_over);
+// a collected speculative batch whose update nobody uses: the covariance as it found it (a chained line launch aborted first)
+extern "C" int plv_points_spec_undo(plv_ctx *ctx);
 extern "C" int plv_points_update_fused(plv_ctx *ctx, const plv_state_view *st, const plv_tracks *all, const plv_tri_options *tri,
                                        const uint8_t *flags, int max_sel, int k, const int *col_to_state, int ld, double sigma2,
                                        double chi2_mult, double res_norm_gate, double *p_out, uint8_t *ok_out, double *err_out,

@@ -1,5 +1,6 @@
 """plv_camera_try_update / plv_camera_frame on hand-made databases: the point half of the one-call form against
 plv_camera_update_points + a dx applied by the caller (same database, same covariance), and the state the library moved."""
+import copy
 import ctypes as C
 
 import numpy as np
@@ -86,3 +87,63 @@ def test_camera_frame_without_update_is_the_feed(pkg):
     pb, ib = b.tracker_last()
     assert len(ia) > 50 and np.array_equal(ia, ib) and np.array_equal(pa, pb)
     a.close(), b.close()
+
+
+def _scene_state(pkg, sc):
+    """A view of the scene and the variable list that keeps it current (clone positions, intrinsics + their mirror in the view).  The
+    view is made of copies: StateView keeps the scene's own arrays, which the variables move."""
+    st, _ = synth.scene_views(pkg, copy.deepcopy(sc))
+    K = np.array(st.c.intrinsics)
+    base = C.addressof(st.c)
+    ent = [("vec", int(st.ids[i]) + 3, st.p[i], None, None) for i in range(len(st.ids))]
+    ent.append(("vec", sc["intr_id"], K, None, base + pkg.PlvStateView.intrinsics.offset))
+    return st, K, pkg.BoxPlus(ent)
+
+
+def _state_of(st, K):
+    return st.p.copy(), K.copy(), np.array(st.c.intrinsics)
+
+
+@pytest.mark.parametrize("case", ["lines_without_outputs", "no_variable_list", "variable_out_of_range"])
+def test_try_update_with_invalid_arguments_leaves_the_filter_as_it_was(pkg, case):
+    """plv_camera_try_update with arguments it refuses (PLV_E_BADARG): the resident covariance bit for bit, the caller's state and the
+    feature database as they were.  A variable list with an index beyond the covariance is refused by plv_state_boxplus too, but that
+    check must come before the point update has committed P on the device.  The next valid call then is the call of an untouched
+    twin context."""
+    fo = oracle_lib.load_front()
+    sc = synth.vio_scene(F=60, M=15, noise_px=0.4, seed=11)
+    n, t = sc["n_state"], sc["t"]
+    kw = dict(t_prev_frame=t[-2], state_time=t[-1], window_full=True, **TRI)
+    b, twin = _filled_context(pkg, sc, fo), _filled_context(pkg, sc, fo)
+    st_b, K_b, plus_b = _scene_state(pkg, sc)
+    st_t, K_t, plus_t = _scene_state(pkg, sc)
+    P0, s0, db0 = b.cov_download(n), _state_of(st_b, K_b), b.db_size()
+    io, _ = b._try_update_io(plus_b, n, 40, 15, lines=case == "lines_without_outputs", **kw)
+    bad = (pkg.PlvStateVar * plus_b.n)()
+    C.memmove(bad, plus_b.vars, C.sizeof(bad))
+    bad[plus_b.n - 1].id = n                      # (the intrinsics: 8 values from index n)
+    saved = io.dx_lines, io.vars
+    if case == "lines_without_outputs":
+        io.dx_lines = None
+    elif case == "no_variable_list":
+        io.vars = None
+    else:
+        io.vars = C.addressof(bad)
+    try:
+        rc = b.lib.plv_camera_try_update(b.h, C.byref(st_b.c), C.byref(io))
+    finally:
+        io.dx_lines, io.vars = saved
+    assert rc == pkg.PLV_E_BADARG
+    assert np.array_equal(b.cov_download(n), P0)
+    for x, y in zip(_state_of(st_b, K_b), s0):
+        assert np.array_equal(x, y)
+    assert b.db_size() == db0
+    out, _, _ = b.camera_try_update(st_b, plus_b, n, 40, 15, lines=False, **kw)
+    ref, _, _ = twin.camera_try_update(st_t, plus_t, n, 40, 15, lines=False, **kw)
+    assert out["n_accepted"] == ref["n_accepted"] > 20 and out["status"] == ref["status"] == 0
+    for key in ("ids", "accepted", "dx", "p_FinG"):
+        assert np.array_equal(out[key], ref[key]), key
+    assert np.array_equal(b.cov_download(n), twin.cov_download(n)) and b.db_size() == twin.db_size()
+    for x, y in zip(_state_of(st_b, K_b), _state_of(st_t, K_t)):
+        assert np.array_equal(x, y)
+    b.close(), twin.close()

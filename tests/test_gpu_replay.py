@@ -1,6 +1,7 @@
 """SURVEY §8(f) rank 4 end to end: a rendered dataset on disk (images, IMU and wheel CSV, YAML configuration in the reference's
 layout) replayed through SystemManager on the GPU -- initialiser, propagation, cloning, tracker, MSCKF / line / wheel updates,
 marginalisation -- and scored with the ATE evaluator against the simulated truth."""
+import ctypes as C
 import importlib
 import os
 
@@ -580,3 +581,130 @@ def test_replay_window_options(pkg, dataset, tmp_path):
     assert stats["n_state"] <= 15 + 8 + 6 * 12 and stats["cam_accepted"] > 300 and stats["lines_tracked"] == 0
     r, n = _score(pkg, traj, os.path.join(dataset, "gt.txt"))
     assert r["pos"]["rmse"] < 0.10, r
+
+
+_FAIL_AT = 10     # the update-carrying frame that is given invalid arguments (lines are being updated by then)
+
+
+def _var_arrays(plus):
+    """The bytes of every array a variable list points at: values, rotation matrices, mirrors (state view fields)."""
+    out = []
+    for v in plus.vars[:plus.n]:
+        m = 9 if v.kind == 1 else v.size
+        for addr, cnt in ((v.val, 4 if v.kind == 1 else v.size), (v.out, 9), (v.mirror, m)):
+            if addr:
+                out.append(C.string_at(addr, 8 * cnt))
+    return out
+
+
+def _drive_with_a_failing_frame(pkg, dataset, tmp_path, monkeypatch, case, knobs, twin=None):
+    """The street drive through SystemManager's one-call path (plv_camera_frame) with update-carrying frame _FAIL_AT given invalid
+    arguments (case None: none), checked right after that call against what the drive `twin` saw at the frame.  Returns the
+    replay's result and what was seen at that frame."""
+    options, rp = importlib.import_module("plviwo_amd.options"), importlib.import_module("plviwo_amd.replay")
+    system = importlib.import_module("plviwo_amd.system")
+    orig, seen, rec = system.SystemManager.camera_run, [0], {}
+
+    def run(self, prep, sync=True):
+        fr = prep["frame"]
+        if fr is None or fr["io"] is None:
+            return orig(self, prep, sync)
+        seen[0] += 1
+        if seen[0] != _FAIL_AT:
+            return orig(self, prep, sync)
+        io, ctx, n = fr["io"], self.ctx, self.state.n
+        plus = fr["results"].keep[8][0]        # (the variable list of this call: Context._try_update_io)
+        assert plus is not None and C.addressof(plus.vars) == io.vars
+        rec["lines"] = bool(io.opt_lines)
+        if case is None:
+            orig(self, prep, sync)
+            pts, _, _ = fr["results"]()
+            rec.update(rc=fr["rc"], n_accepted=pts["n_accepted"], last=ctx.tracker_last(), line_db=fr["f"].line_db_size)
+            return
+        P0, a0 = ctx.cov_download(n), _var_arrays(plus)
+        bad = (pkg.PlvStateVar * plus.n)()
+        C.memmove(bad, plus.vars, C.sizeof(bad))
+        bad[plus.n - 1].id = n
+        saved = io.dx_lines, io.res_lines, io.vars   # (Context caches the structure per option set: restored at once)
+        if case == "lines_without_outputs":
+            io.dx_lines = None
+        elif case == "no_variable_list":
+            io.vars = None
+        else:
+            io.vars = C.addressof(bad)
+        try:
+            orig(self, prep, sync)
+        finally:
+            io.dx_lines, io.res_lines, io.vars = saved
+        rc, last = fr["rc"], ctx.tracker_last()
+        assert rc == pkg.PLV_E_BADARG, (knobs, rc)
+        assert np.array_equal(ctx.cov_download(n), P0), f"knobs {knobs}: the covariance changed"
+        assert _var_arrays(plus) == a0, f"knobs {knobs}: the state changed"
+        # the frame's feed took place: the tracker's points and the line database as after the twin's call
+        assert np.array_equal(last[1], twin["last"][1]) and np.array_equal(last[0], twin["last"][0]), knobs
+        assert fr["f"].line_db_size == ctx.line_db_size() == twin["line_db"], (knobs, fr["f"].line_db_size, ctx.line_db_size(), twin["line_db"])
+        rec["rc"] = rc
+        fr["rc"], fr["results"] = 0, None     # (the frame counts as one without an update; the drive goes on with valid arguments)
+
+    monkeypatch.setattr(system.SystemManager, "camera_run", run)
+    monkeypatch.setattr(system.SystemManager, "one_call_update", True)
+    monkeypatch.setattr(system.SystemManager, "one_call_frame", True)
+    name = f"{case}_{knobs}"
+    op = options.load_options(sd.write_config(str(tmp_path / "config"), dataset, str(tmp_path / f"traj_{name}.txt")))
+    op.est.cam.use_lines = True
+    prev = pkg.debug_knobs(knobs)
+    try:
+        out = rp.replay(op)
+    finally:
+        pkg.debug_knobs(prev)
+        monkeypatch.setattr(system.SystemManager, "camera_run", orig)
+    assert seen[0] > _FAIL_AT, seen
+    return out, rec
+
+
+_CASES = ["lines_without_outputs", "no_variable_list", "variable_out_of_range"]
+_ROUTES = {"speculative": 0, "after_the_flow": 1 << 24}
+_DRIVES = {}
+
+
+@pytest.fixture(scope="module")
+def street_twin(pkg, street_dataset, tmp_path_factory):
+    """The drive with valid arguments throughout: what it saw at frame _FAIL_AT"""
+    with pytest.MonkeyPatch.context() as mp:
+        (s, _, _), rec = _drive_with_a_failing_frame(pkg, street_dataset, tmp_path_factory.mktemp("twin"), mp, None, 0)
+    assert rec["rc"] == 0 and rec["lines"] and rec["n_accepted"] > 0, rec
+    assert s["line_updates"] >= 10 and s["cam_updates"] >= 40
+    return rec
+
+
+def _failing_drive(pkg, street_dataset, street_twin, tmp_path, monkeypatch, case, route):
+    if (case, route) not in _DRIVES:
+        _DRIVES[(case, route)] = _drive_with_a_failing_frame(pkg, street_dataset, tmp_path, monkeypatch, case, _ROUTES[route], twin=street_twin)[0]
+    return _DRIVES[(case, route)]
+
+
+@pytest.mark.parametrize("route", list(_ROUTES))
+@pytest.mark.parametrize("case", _CASES)
+def test_camera_frame_with_invalid_arguments_leaves_the_filter_as_it_was(pkg, street_dataset, street_twin, tmp_path, monkeypatch, case, route):
+    """plv_camera_frame whose update arguments are refused (PLV_E_BADARG) on a frame of the drive, with the point update enqueued
+    behind the flow (the default) and with it submitted after the flow's result (knob 1 << 24): the covariance on the device and every
+    array of the variable list bit for bit as before the call, and the frame's feed done (the tracker's points and the line database
+    as after the call of a twin drive that updated at that frame).  Checked inside the drive, right after the call."""
+    _DRIVES.pop((case, route), None)
+    _failing_drive(pkg, street_dataset, street_twin, tmp_path, monkeypatch, case, route)
+
+
+@pytest.mark.parametrize("case", _CASES)
+def test_drive_after_a_refused_frame_is_the_same_on_both_routes(pkg, street_dataset, street_twin, tmp_path, monkeypatch, case):
+    """... and the drive goes on with valid arguments: the speculative route and the route after the flow give the same filter, as
+    test_one_call_try_update_equals_the_two_calls asks of them (identical counts, trajectories equal to rounding)."""
+    s0, t0, p0 = _failing_drive(pkg, street_dataset, street_twin, tmp_path, monkeypatch, case, "after_the_flow")
+    s1, t1, p1 = _failing_drive(pkg, street_dataset, street_twin, tmp_path, monkeypatch, case, "speculative")
+    for key in s0:
+        if key.startswith("time"):
+            continue
+        if isinstance(s0[key], float):
+            assert abs(s1[key] - s0[key]) <= 1e-9 * max(1.0, abs(s0[key])), (key, s1[key], s0[key])
+        else:
+            assert s1[key] == s0[key], (key, s1[key], s0[key])
+    assert np.array_equal(t1, t0) and np.abs(p1 - p0).max() < 1e-9
