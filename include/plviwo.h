@@ -28,6 +28,11 @@
 extern "C" {
 #endif
 
+/* The shared library is built with hidden visibility and exports exactly what this header declares. */
+#if defined(__GNUC__)
+#pragma GCC visibility push(default)
+#endif
+
 #define PLV_ABI_VERSION 1
 
 /* ---------------------------------------------------------------- status codes */
@@ -967,6 +972,23 @@ typedef struct plv_stats { double min, max, median, mean, rmse, std, ninetynine;
  * ori_err[i] = |log_so3(R_aligned^T R_gt)| in degrees, pos_err[i] = |p_gt - p_aligned|.  Every output is nullable. */
 int plv_traj_ate(plv_ctx *ctx, int method, int n, const double *est_poses, const double *gt_poses, int n_aligned, double *R,
                  double *t, double *s, double *aligned, double *ori_err, double *pos_err, plv_stats *ori, plv_stats *pos);
+
+
+/* ---------------------------------------------------------------------------------------------
+ * Measurement aids: bench.py and the tests read and switch these; a product caller has no use for them.
+ * ------------------------------------------------------------------------------------------- */
+/* the mask of alternative placements (csrc/plv_ctx.hpp "Measurement knobs"); set < 0 only queries.  Returns the previous mask. */
+unsigned plv_debug_knobs(long long set);
+/* device / pinned (re)allocations since the library was loaded: a frame that grows a buffer pays a hipMalloc */
+unsigned long long plv_alloc_count(void);
+/* wall time (ns) inside the parts of plv_camera_frame since the library was loaded: [0] the wait for flow + RANSAC,
+ * [1] plv_camera_update_points, [2] of it the wait for the device, [3] plv_camera_update_lines, [4] the join of the line worker,
+ * [5..9] the line worker: post -> wake-up, wait for the edge maps, walk + fit, feed post -> start, the feed */
+void plv_phase_counters(unsigned long long *out10);
+
+#if defined(__GNUC__)
+#pragma GCC visibility pop
+#endif
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@
 #include "detect_kernels.hpp"
 #include "frontend_kernels.hpp"
 #include "line_kernels.hpp"
+#include "plv_internal.hpp"
 
 using namespace plv;
 
@@ -182,8 +183,7 @@ int upload_image(plv_ctx *ctx, FrontState *s, void *dst, const uint8_t *img, int
 
 }  // namespace
 
-extern "C" {
-
+namespace plv {
 void plv_frontend_destroy(plv_ctx *ctx) {
   auto *s = (FrontState *)ctx->fe_state;
   if (!s) return;
@@ -235,6 +235,8 @@ int plv_feed_image_enqueue(plv_ctx *ctx, const uint8_t *img, int stride) {
   // no copy command: the histogram kernel reads the pinned block over PCIe (16 bytes per lane) and leaves the image in s->raw
   return feed_device(ctx, s, s->raw.as<uint8_t>(), h_src);
 }
+}  // namespace plv
+extern "C" {
 
 // A pinned host block of the library for the caller to write the next image into (a camera driver's DMA target, cv_bridge's copy
 // target: `cv::Mat(h, w, CV_8UC1, ptr)`): plv_tracker_feed / plv_camera_frame recognise a pointer into it and skip their own host
@@ -735,13 +737,17 @@ void det_post(plv_ctx *ctx, const DetJob &J, float *pts, uint64_t *ids, int cap,
 // a detection that was started ahead of time and has not been collected: wait for it so that its buffers can be reused
 void det_drop_pending(FrontState *s);
 }  // namespace
+}  // extern "C"
+namespace plv {
 // plv_ctx_synchronize: the side stream's work belongs to the frame that started it — wait for it too (the job stays collectable)
-extern "C" int plv_front_quiesce(plv_ctx *ctx) {
+int plv_front_quiesce(plv_ctx *ctx) {
   if (!ctx || !ctx->fe_state) return PLV_OK;
   FrontState *s = (FrontState *)ctx->fe_state;
   if (s->det_pending.active && s->det_done) PLV_HIP_CHECK(plv::event_sync(s->det_done));
   return PLV_OK;
 }
+}  // namespace plv
+extern "C" {
 namespace {
 void det_drop_pending(FrontState *s) {
   if (s->det_pending.active) {
@@ -785,6 +791,10 @@ int plv_perform_detection(plv_ctx *ctx, int which, const uint8_t *mask, float *p
   return PLV_OK;
 }
 
+}  // extern "C"
+
+namespace plv {
+
 // The top-up detection of the NEXT frame, started now: on the current image (the next frame's last image) with the points this frame
 // ended with.  Runs on a side stream next to whatever the caller enqueues on the ctx stream (the updates); plv_perform_detection of
 // the next frame finds it finished (the per-kernel profiler follows it onto the side stream: Profiler::collect).
@@ -818,4 +828,4 @@ int plv_perform_detection_ahead(plv_ctx *ctx, const uint8_t *mask, const float *
   return PLV_OK;
 }
 
-}  // extern "C"
+}  // namespace plv

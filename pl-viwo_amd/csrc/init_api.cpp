@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/plviwo.h"
+#include "plv_internal.hpp"
 
 namespace {
 
@@ -348,6 +349,8 @@ void plv_jpl_left_update(int n, double *q, const double *dth, double *R) {
 // Type::update(dx.block(id, 0, size, 1)) per variable: Vec adds, JPLQuat composes on the left, PoseJPL is one of each).
 // `out` of a quaternion receives its rotation matrix; `mirror` (nullable) a second copy of what the variable now holds (the value of
 // a vector, the rotation matrix of a quaternion) — e.g. the field of a plv_state_view the caller keeps current.
+}  // extern "C"
+namespace plv {
 // (internal; plv_camera_try_update / plv_camera_frame check the list with it before they enqueue anything)
 int plv_state_vars_check(int n_var, const plv_state_var *vars, int n_dx) {
   if (n_var < 0 || (n_var > 0 && !vars)) return PLV_E_BADARG;
@@ -358,11 +361,13 @@ int plv_state_vars_check(int n_var, const plv_state_var *vars, int n_dx) {
   }
   return PLV_OK;
 }
+}  // namespace plv
+extern "C" {
 
 int plv_state_boxplus(int n_var, const plv_state_var *vars, const double *dx, int n_dx) {
   if (!dx) return PLV_E_BADARG;
   // every entry is checked before the first one is applied: a bad list leaves the state as it was
-  if (const int rc = plv_state_vars_check(n_var, vars, n_dx)) return rc;
+  if (const int rc = plv::plv_state_vars_check(n_var, vars, n_dx)) return rc;
   for (int i = 0; i < n_var; ++i) {
     const plv_state_var &v = vars[i];
     if (v.kind == PLV_VAR_QUAT) {

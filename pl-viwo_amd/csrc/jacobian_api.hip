@@ -402,6 +402,8 @@ int plv_jacobian_columns(const plv_state_view *st, const plv_tracks *tr, int *co
   *k_out = k;
   return PLV_OK;
 }
+}  // extern "C"
+namespace plv {
 
 // One-submission point update (plv_camera_update_points): triangulation of every pool candidate, the selection loop, Jacobians +
 // null-space projection, gate, compression and EKFUpdate are enqueued back to back; one upload, one result download, one host
@@ -547,8 +549,6 @@ int plv_points_update_collect(plv_ctx *ctx, double *p_out, uint8_t *ok_out, doub
   return rc;
 }
 
-extern "C" int plv_camera_lines_job_pending(plv_ctx *ctx);  // line_api.hip
-extern "C" void plv_camera_lines_job_abort(plv_ctx *ctx);
 // (internal, tracker_api.hip) the speculative point batch was collected and nobody will use its update: the covariance as the batch found
 // it.  The stream is waited for and a line launch chained behind the batch is aborted first (its commit sits on top of the batch's: the
 // saved covariance undoes both).  Nothing is restored when the batch committed nothing (rejected, capped, skipped, ended at the gate).
@@ -578,6 +578,8 @@ int plv_points_update_fused(plv_ctx *ctx, const plv_state_view *st, const plv_tr
   TRY(plv_points_update_submit(ctx, st, all, tri, flags, max_sel, k, col_to_state, ld, sigma2, chi2_mult, res_norm_gate, nullptr));
   return plv_points_update_collect(ctx, p_out, ok_out, err_out, accepted, n_rows, dx, before_wait, before_wait_arg, nullptr, nullptr, nullptr);
 }
+}  // namespace plv
+extern "C" {
 
 int plv_build_jacobians_resident(plv_ctx *ctx, const plv_state_view *st, const plv_tracks *tr, int k,
                                  const int *col_to_state, int ld) {
@@ -929,8 +931,7 @@ int build_lines_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_stat
 
 }  // namespace
 
-extern "C" {
-
+namespace plv {
 // The line twin (plv_camera_update_lines): line triangulation, selection, Pluecker Jacobians, null space, gate, compression, EKF.
 // st_tri: the state the lines are triangulated on (the one before the point update, plv_camera_get_line_features); the Jacobians
 // are taken at st.
@@ -982,6 +983,9 @@ int plv_lines_update_fused(plv_ctx *ctx, const plv_state_view *st, const plv_sta
   TRY(plv_lines_update_fused_submit(ctx, st, st_tri, all, flags, max_sel, k, col_to_state, ld, sigma2, chi2_mult));
   return plv_lines_update_fused_finish(ctx, sigma2, chi2_mult, lines_out, ok_out, accepted, n_rows, dx, before_wait, before_wait_arg);
 }
+}  // namespace plv
+
+extern "C" {
 
 int plv_line_jacobian_columns(const plv_state_view *st, const plv_line_tracks *lt, int *col_to_state, int cap, int *k_out) {
   if (!col_to_state || !k_out) return PLV_E_BADARG;

@@ -28,6 +28,7 @@
 #include "radtan_core.hpp"
 #include "line_kernels.hpp"
 #include "update_state.hpp"
+#include "plv_internal.hpp"
 
 using namespace plv;
 using namespace plv::linehost;
@@ -499,8 +500,7 @@ template <class F> struct BoundingMemo {
 };
 template <class F> BoundingMemo<F> bounding_memo(F f) { return BoundingMemo<F>(f); }
 
-extern "C" {
-
+namespace plv {
 void plv_line_tracker_destroy(plv_ctx *ctx) {
   std::lock_guard<std::mutex> lk(g_mtx);
   auto it = g_lt.find(ctx);
@@ -529,6 +529,9 @@ void plv_line_tracker_destroy(plv_ctx *ctx) {
     g_lt.erase(it);
   }
 }
+}  // namespace plv
+
+extern "C" {
 
 int plv_line_walk_mode(plv_ctx *ctx, int on_device) {
   if (!ctx) return PLV_E_BADARG;
@@ -553,6 +556,8 @@ int plv_line_prefetch_mode(plv_ctx *ctx, int on) {
   T->prefetch = on != 0;
   return PLV_OK;
 }
+}  // extern "C"
+namespace plv {
 int plv_line_prefetch_enabled(plv_ctx *ctx) {
   {
     std::lock_guard<std::mutex> lk(g_mtx);
@@ -562,6 +567,8 @@ int plv_line_prefetch_enabled(plv_ctx *ctx) {
   std::lock_guard<std::mutex> lk(T->mtx);
   return T->prefetch && !T->walk_on_device ? 1 : 0;
 }
+}  // namespace plv
+extern "C" {
 
 int plv_detect_lines(plv_ctx *ctx, int which, float *lines, int cap, int *n_out) {
   if (!ctx || !n_out) return PLV_E_BADARG;
@@ -622,6 +629,8 @@ int plv_vanishing_points(const double *R_ItoC, const double *K8, double *vps) {
   return PLV_OK;
 }
 
+}  // extern "C"
+namespace plv {
 // TrackLSD::feed_monocular for the image currently in the ctx (fed by plv_tracker_feed / plv_feed_image,
 // which also is where the reference's second equalizeHist comes from: same input, same result).
 // (internal, the tracker feed) marks the point on the ctx stream the prefetched edge kernel has to wait for — the pyramid of the image
@@ -644,7 +653,7 @@ int plv_line_edges_fork(plv_ctx *ctx) {
 // The tracker feed's hook into the image feed (plv_ctx::edges_hook): plv_line_detect_launch for the image being fed, between its
 // histogram and its pyramid — the edge kernel equalises the raw image itself (canny_kernel), the worker gets the maps two launches
 // earlier, and the flow starts when it always did.  Host-walk configuration without hysteresis only (the shipped one).
-extern "C" void plv_line_edges_early(plv_ctx *ctx, const uint8_t *d_raw, int W, int H, const unsigned *d_hist) {
+void plv_line_edges_early(plv_ctx *ctx, const uint8_t *d_raw, int W, int H, const unsigned *d_hist) {
   LineTracker *T = ltr(ctx, false);
   std::lock_guard<std::mutex> lk(T->mtx);
   if (T->walk_on_device || !T->prefetch || ctx->cfg.canny_th1 != ctx->cfg.canny_th2) return;
@@ -653,6 +662,8 @@ extern "C" void plv_line_edges_early(plv_ctx *ctx, const uint8_t *d_raw, int W, 
   if (detect(ctx, T, PLV_PYR_CUR, none, true) == PLV_OK) ctx->edges_hook_fired = true;
   T->early_raw = nullptr, T->early_hist = nullptr;
 }
+}  // namespace plv
+extern "C" {
 
 // (test aid, plv_decision_trace) the last line update's batch: ids [n] as plv_camera_update_lines returned them and vals [n][3] = chi2,
 // the threshold it was held against, the norm of the projected residual (NaN: the line did not reach the gate)
@@ -784,6 +795,8 @@ static int feed_points_impl(plv_ctx *ctx, LineTracker *T, double timestamp, cons
   return PLV_OK;
 }
 
+}  // extern "C"
+namespace plv {
 // (internal) plv_line_tracker_feed_async with the frame's tracked points handed in (pts / pids = what plv_tracker_last returns once the
 // point tracker's feed is over): the point tracker's feed posts the line feed through this the moment its point list stands, in front
 // of its own database update (plv_camera_frame, round 6: the line worker's feed is the longer path of the frame)
@@ -814,6 +827,8 @@ int plv_line_tracker_feed_async_points(plv_ctx *ctx, double timestamp, const dou
   T->jcv.notify_all();
   return PLV_OK;
 }
+}  // namespace plv
+extern "C" {
 
 int plv_line_tracker_feed_async(plv_ctx *ctx, double timestamp, const double *vps) {
   if (!ctx || !vps) return PLV_E_BADARG;
@@ -919,9 +934,6 @@ int plv_line_db_append_measurements(plv_ctx *ctx, uint64_t id, int n, const doub
   return PLV_OK;
 }
 
-int plv_point_used_lookup(plv_ctx *ctx, uint64_t id, double *p);   // tracker_api.hip
-void plv_point_used_cleanup(plv_ctx *ctx, double t_oldest);
-
 static bool line_has_bounding_poses(const plv_state_view &st, double t) {  // as the kernels' bounding_start
   const int N = st.n_clones;
   if (N < 4) return false;
@@ -932,14 +944,14 @@ static bool line_has_bounding_poses(const plv_state_view &st, double t) {  // as
   return false;
 }
 
-
+}  // extern "C"
+namespace plv {
 // (internal) plv_camera_try_update turns the deferral on around its line update; plv_tracker_feed* runs what was left behind
 void plv_line_defer_finish(plv_ctx *ctx, int on) { ltr(ctx, false)->defer_finish = on != 0; }
 void plv_line_run_deferred(plv_ctx *ctx) { (void)ltr(ctx); }
+}  // namespace plv
+extern "C" {
 
-extern "C" int plv_point_chain_lookup(plv_ctx *ctx, uint64_t id);  // tracker_api.hip: index of a feature in the running point update's pool, or -1
-extern "C" void plv_point_anchor_fill(plv_ctx *ctx, int Lp, const int *pt_ptr, const int *pt_ids, int chained, double *anchor, uint8_t *has);  // tracker_api.hip
-extern "C" int plv_camera_get_line_features(plv_ctx *ctx, const plv_state_view *st);
 static void line_give_back(std::unordered_map<uint64_t, LineTrack> &unused, const LineCand &c, size_t i) {
   LineTrack &u = unused[c.id];
   if (u.t.empty() && u.points.empty()) {
@@ -1096,6 +1108,8 @@ void discard_line_pool(LineTracker *T) {
 }
 }  // namespace
 
+}  // extern "C"
+namespace plv {
 // (internal, plv_camera_try_update) forms the line pool now if the line feed of this frame has finished — polled while the point
 // update runs on the device.  Never blocks: returns 0 while the feed is still on the worker (try again), 1 when the pool is formed or
 // cannot be formed ahead of time (plv_camera_update_lines then forms it).
@@ -1141,6 +1155,8 @@ int plv_line_db_size_after_feed(plv_ctx *ctx) {
   std::lock_guard<std::mutex> lk(T->mtx);
   return (int)T->db.size();
 }
+}  // namespace plv
+extern "C" {
 
 // LineHelper::get_line_features' place in try_update (REF: UpdaterCamera.cpp:148-152: after get_features, before msckf_update's
 // correction reaches the state): records the state the line pool is to be triangulated on.  The pool itself (LineHelper.cpp:33-44)
@@ -1336,6 +1352,8 @@ static int lines_first_half(plv_ctx *ctx, LineTracker *T, const plv_state_view *
   return PLV_OK;
 }
 
+}  // extern "C"
+namespace plv {
 // (internal, plv_camera_try_update) the chained first half: called inside the point update's wait once the frame's line feed has
 // finished.  0: not possible now (the caller goes on as before), 1: the line launch is on the stream behind the point update.
 int plv_camera_lines_submit_chained(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, int cap) {
@@ -1375,6 +1393,8 @@ void plv_camera_lines_job_abort2(plv_ctx *ctx, int keep_pool) {
   T->ujob = LinesJob();
 }
 void plv_camera_lines_job_abort(plv_ctx *ctx) { plv_camera_lines_job_abort2(ctx, 0); }
+}  // namespace plv
+extern "C" {
 
 int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, double *dx,
                             plv_update_result *res, uint64_t *line_ids, uint8_t *accepted_out, double *lines_out, int cap) {

@@ -86,7 +86,7 @@ using namespace plv;
 
 static std::mutex g_state_mtx;
 static std::vector<std::pair<plv_ctx *, plv_ctx_update_state *>> g_states;
-plv_ctx_update_state *plv_update_state(plv_ctx *ctx) {
+plv_ctx_update_state *plv::plv_update_state(plv_ctx *ctx) {
   std::lock_guard<std::mutex> lk(g_state_mtx);
   for (auto &p : g_states)
     if (p.first == ctx) return p.second;
@@ -264,10 +264,6 @@ int plv_ctx_create(const plv_config *cfg, plv_ctx **out) {
   return PLV_OK;
 }
 
-void plv_frontend_destroy(plv_ctx *ctx);  // frontend_api.hip
-void plv_tracker_destroy(plv_ctx *ctx);   // tracker_api.hip
-void plv_line_tracker_destroy(plv_ctx *ctx);  // line_api.hip
-
 void plv_ctx_destroy(plv_ctx *ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
@@ -323,8 +319,6 @@ void plv_ctx_destroy(plv_ctx *ctx) {
   delete ctx;
 }
 
-extern "C" int plv_front_quiesce(plv_ctx *ctx);        // frontend_api.hip: a detection started ahead of time on the side stream
-extern "C" int plv_line_tracker_feed_wait(plv_ctx *ctx);
 // Everything the calls so far have started is finished at return: the ctx stream, the side stream of the detection that a point
 // update starts ahead of time, and the library's line worker (an asynchronous feed is joined; its status stays with
 // plv_line_tracker_feed_wait).  bench.py ends every timed step here.
@@ -687,6 +681,8 @@ int plv_feat_batch_upload(plv_ctx *ctx, int F, int fdim, int k, int ld, const in
 }
 
 static bool whitened_route(const plv_ctx_update_state *us, int Mtot, int k);
+}  // extern "C"
+namespace plv {
 // Called by the one-submission updates before they build their batch: fills plv_ctx::gate_stage so that the projected Jacobian
 // launch ends with the gate of every entry (gate_core.hpp) — verdicts, counter, stack — and plv_msckf_update_resident_launch starts
 // behind it.  The buffers are the ones that launch function reserves (same sizes: no reallocation in between).
@@ -750,6 +746,8 @@ int plv_update_gate_prepare(plv_ctx *ctx, int F, int fdim, int k, int ld, double
   }
   return PLV_OK;
 }
+}  // namespace plv
+extern "C" {
 static bool whitened_route(const plv_ctx_update_state *us, int Mtot, int k) {
   return Mtot > k && k <= 192 && us->compress_mode == 0 && !us->graph_mode;
 }
@@ -779,6 +777,8 @@ static int prior_start(plv_ctx *ctx, const int *d_cols, int k) {
   PLV_HIP_CHECK(hipEventRecord(ctx->aux_join, ctx->aux_stream));
   return PLV_OK;
 }
+}  // extern "C"
+namespace plv {
 // Called by the one-submission updates (jacobian_api.hip) with the update's shape: phase 0 before anything of the update is on the main
 // stream (its upload included), phase 1 right after the Jacobian launch with the column map in memory the device can read NOW (the
 // pinned staging block: the side stream does not wait for the upload).  When the update will take the whitened route its prior factor runs next to triangulation,
@@ -792,6 +792,8 @@ int plv_prior_prefetch(plv_ctx *ctx, int phase, const int *d_cols, int k, int F,
   ctx->prior_k = k;
   return PLV_OK;
 }
+}  // namespace plv
+extern "C" {
 
 int plv_msckf_update_resident_launch(plv_ctx *ctx, double sigma2, double chi2_mult, double res_norm_gate) {
   REQUIRE_CTX(ctx);

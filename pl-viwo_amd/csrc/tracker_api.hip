@@ -14,6 +14,7 @@
 #include <sys/resource.h>
 #include "plv_ctx.hpp"
 #include "update_state.hpp"
+#include "plv_internal.hpp"
 #include "gate_stage.hpp"
 
 namespace {
@@ -119,8 +120,7 @@ template <class F> struct BoundingMemo {
 };
 template <class F> BoundingMemo<F> bounding_memo(F f) { return BoundingMemo<F>(f); }
 
-extern "C" {
-
+namespace plv {
 void plv_tracker_destroy(plv_ctx *ctx) {
   std::lock_guard<std::mutex> lk(g_mtx);
   auto it = g_trk.find(ctx);
@@ -129,11 +129,13 @@ void plv_tracker_destroy(plv_ctx *ctx) {
     g_trk.erase(it);
   }
 }
+}  // namespace plv
+
+using namespace plv;
+
+extern "C" {
 
 static int tracker_feed_fed(plv_ctx *ctx, Tracker *T, double timestamp, const uint8_t *mask);
-extern "C" int plv_feed_image_enqueue(plv_ctx *ctx, const uint8_t *img, int stride);  // frontend_api.hip
-extern "C" int plv_line_prefetch_enabled(plv_ctx *ctx);                               // line_api.hip
-extern "C" void plv_line_edges_early(plv_ctx *ctx, const uint8_t *d_raw, int W, int H, const unsigned *d_hist);
 // the image feed with the line detector's edge kernel between its histogram and its pyramid (plv_ctx::edges_hook) when the frame's
 // lines are detected ahead of the line tracker's feed anyway; PLV_KNOB_EDGES_LATE / the other edge knobs keep the older orders
 static int feed_with_early_edges(plv_ctx *ctx, const std::function<int()> &feed) {
@@ -178,9 +180,6 @@ int plv_tracker_feed_downsampled(plv_ctx *ctx, double timestamp, const uint8_t *
 }
 
 static bool has_bounding_poses(const plv_state_view &st, double t);
-extern "C++" {
-namespace plv { int plv_front_match_device(plv_ctx *ctx, const float **d_p1, const float **d_n1, const uint8_t **d_mask, int *n); }  // frontend_api.hip
-}
 // Stages every track the frame's flow could send into the point update's pool and enqueues the update behind the flow (Tracker::Spec).
 // Called with T->mtx held, between the flow's launch and the wait for it; tp[i]: the database track of flow point i (or null).
 // Anything unusual leaves spec.active false: plv_camera_update_points then submits the update itself, as it always did.
@@ -359,10 +358,6 @@ static void spec_submit(plv_ctx *ctx, Tracker *T, double t_now, int n_flow, cons
 }
 
 // the rest of TrackKLT::feed_monocular once the image is equalised and its pyramid built
-extern "C" int plv_line_edges_fork(plv_ctx *ctx);         // line_api.hip
-extern "C" void plv_line_defer_finish(plv_ctx *ctx, int on);
-extern "C" void plv_line_run_deferred(plv_ctx *ctx);
-extern "C" int plv_perform_detection_ahead(plv_ctx *ctx, const uint8_t *mask, const float *pts, const uint64_t *ids, int n_in, int on_ctx_stream);  // frontend_api.hip
 static int tracker_feed_fed(plv_ctx *ctx, Tracker *T, double timestamp, const uint8_t *mask) {
   const int W = ctx->cfg.width, H = ctx->cfg.height;
   ++T->feed_seq;
@@ -499,10 +494,6 @@ static int tracker_feed_fed(plv_ctx *ctx, Tracker *T, double timestamp, const ui
   return PLV_OK;
 }
 
-extern "C" int plv_line_pool_prepare(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt);  // line_api.hip
-extern "C" int plv_line_tracker_feed_async_points(plv_ctx *ctx, double timestamp, const double *vps, int np, const float *pts, const uint64_t *pids);
-extern "C" void plv_line_pool_discard(plv_ctx *ctx);
-extern "C" int plv_line_db_size_after_feed(plv_ctx *ctx);
 // host work placed inside the point update's wait (called without T->mtx held)
 static void start_detection_ahead(void *arg) {
   plv_ctx *ctx = (plv_ctx *)arg;
@@ -520,11 +511,6 @@ static void start_detection_ahead(void *arg) {
 }
 // LineHelper::get_line_features' pool (times only: nothing the point update changes) while the device is busy with that update;
 // polled inside the update's wait (plv_ctx::wait_poll) until the line worker has finished the frame's feed
-extern "C" void plv_line_feed_pool_args(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt);  // line_api.hip
-extern "C" int plv_camera_lines_submit_chained(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, int cap);  // line_api.hip
-extern "C" int plv_camera_lines_job_pending(plv_ctx *ctx);
-extern "C" void plv_camera_lines_job_abort(plv_ctx *ctx);
-extern "C" void plv_camera_lines_job_abort2(plv_ctx *ctx, int keep_pool);
 static int poll_line_pool(void *arg) {
   plv_ctx *ctx = (plv_ctx *)arg;
   Tracker *T = trk(ctx);
@@ -542,12 +528,16 @@ static int poll_line_pool(void *arg) {
     (void)plv_camera_lines_submit_chained(ctx, T->early_st, T->early_lines, T->early_cap);
   return 1;
 }
+}  // extern "C"
+namespace plv {
 // index of a feature in the pool of the point update being run (its triangulation result decides whether point_used gets the point)
 int plv_point_chain_lookup(plv_ctx *ctx, uint64_t id) {
   Tracker *T = trk(ctx);
   auto it = T->chain_index.find(id);
   return it == T->chain_index.end() ? -1 : it->second;
 }
+}  // namespace plv
+extern "C" {
 
 int plv_decision_trace(plv_ctx *ctx, int on) {
   if (!ctx) return PLV_E_BADARG;
@@ -1288,6 +1278,8 @@ int plv_point_used_insert(plv_ctx *ctx, uint64_t id, const double *p_FinG, doubl
   return PLV_OK;
 }
 
+}  // extern "C"
+namespace plv {
 // line_api.hip: FeatureDatabase::get_feature(id) on point_used (Triangulated features only)
 int plv_point_used_lookup(plv_ctx *ctx, uint64_t id, double *p) {
   Tracker *T = trk(ctx);
@@ -1356,8 +1348,9 @@ void plv_tracker_run_deferred(void *arg) {
   f.swap(T->deferred_db);
   f();
 }
+}  // namespace plv
+extern "C" {
 
-extern "C" int plv_state_vars_check(int n_var, const plv_state_var *vars, int n_dx);  // init_api.cpp
 // Every argument plv_camera_try_update can refuse, checked before anything is enqueued (plv_camera_frame: before its feed, and so before
 // the speculative point update): a refused call leaves the covariance and the variables as they were.
 static int try_update_args(plv_ctx *ctx, const plv_state_view *st, const plv_try_update *io) {

@@ -1,8 +1,9 @@
-"""CPU tests: the C-ABI library loads and exports every symbol include/plviwo.h declares; without a
-GPU the compute entry points refuse to run (no CPU fallback)."""
+"""CPU tests: the C-ABI library loads and exports every symbol include/plviwo.h declares and nothing else;
+without a GPU the compute entry points refuse to run (no CPU fallback)."""
 import ctypes as C
 import os
 import re
+import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -20,6 +21,19 @@ def test_header_symbols_exported(pkg):
     missing = [n for n in names if not hasattr(lib, n)]
     assert not missing, f"declared in plviwo.h but not exported: {missing}"
     assert lib.plv_abi_version() == 1
+
+
+def test_exports_only_the_header(pkg):
+    """The library's dynamic symbol table is the header: every internal helper (csrc/plv_internal.hpp) and every C++ symbol
+    (plv::launch_*, kernel handles) stays local, so a ROS node that loads the .so sees the C ABI and nothing else."""
+    out = subprocess.run(["nm", "-D", "--defined-only", pkg.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    declared = set(_declared_symbols())
+    plv = {n for n in exported if n.startswith("plv_")}
+    assert plv == declared, {"exported, not declared": sorted(plv - declared), "declared, not exported": sorted(declared - plv)}
+    cxx = sorted(n for n in exported if n.startswith("_ZN3plv"))
+    assert not cxx, f"{len(cxx)} C++ symbols of namespace plv exported, e.g. {cxx[:5]}"
+    assert exported == declared, sorted(exported - declared)[:20]
 
 
 def test_python_binding_covers_header(pkg):
