@@ -126,16 +126,14 @@ __global__ void __launch_bounds__(256) ekf_dc_kernel(const double *__restrict__ 
 // diagonal or the factorisation was not positive definite; else P.upper -= dC, mirrored.
 // The last kernel of the update also mirrors the small result block (dx, flag, accepted, rows) into the caller's pinned host
 // buffer, so that no copy command sits between the end of the chain and the host's wait.
-__global__ void __launch_bounds__(1024) ekf_commit_kernel(double *__restrict__ P, int ldp, int n,
+__global__ void __launch_bounds__(256) ekf_commit_kernel(double *__restrict__ P, int ldp, int n,
                                                          const double *__restrict__ dC, int ldc, int *__restrict__ flag,
                                                          const unsigned *__restrict__ mirror_src, unsigned *__restrict__ mirror_dst,
                                                          int mirror_words, const int *__restrict__ skip, double *__restrict__ dx,
                                                          const unsigned *__restrict__ mirror2_src, unsigned *__restrict__ mirror2_dst,
-                                                         int mirror2_words, unsigned *done_word, unsigned done_val,
+                                                         int mirror2_words,
                                                          int *__restrict__ applied_out, const int *__restrict__ cap_words, int cap,
                                                          double *__restrict__ save, unsigned *__restrict__ save_word, unsigned save_seq) {
-  // done_word (pinned, optional; the launch then has ONE workgroup): behind the mirrors AND the covariance commit the workgroup stores
-  // done_val there, and the host, spinning on the word, knows both the results and the covariance to be final
   const bool skipped = skip && *skip == 0;  // (the gate accepted nothing: no correction, the covariance stays)
   // cap_words (a speculative point batch, SpecSelectArgs::words + 3): [0] the pool was larger than the selection loop's cap, [1] the
   // candidates the Jacobian launch selected on their own verdicts.  When that count reaches the cap the loop would have stopped
@@ -174,11 +172,6 @@ __global__ void __launch_bounds__(1024) ekf_commit_kernel(double *__restrict__ P
       }
     }
   }
-  if (done_word) {  // (gridDim.x == 1)
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(done_word, done_val, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
 }
 
 // ========================================================================================== launchers
@@ -212,15 +205,11 @@ static int launch_ekf_commit(plv_ctx *ctx, double *d_P, int n, int ldp, const do
                              void *mirror_dst, size_t mirror_bytes) {
   {
     ProfScope ps(ctx->prof, "ekf_commit_kernel", ctx->stream);
-    // with a completion word: one workgroup of 1024 threads does mirrors + commit + word (14 passes over a 119 x 119 covariance)
-    unsigned *dw = (mirror_dst && ctx->update_word_armed) ? (unsigned *)ctx->done_word(16) : nullptr;
-    const dim3 grid(dw ? 1 : std::min(64, cdiv(n * n, 256))), block(dw ? 1024 : 256);
-    hipLaunchKernelGGL(ekf_commit_kernel, grid, block, 0, ctx->stream, d_P, ldp, n, dC, n,
+    hipLaunchKernelGGL(ekf_commit_kernel, dim3(std::min(64, cdiv(n * n, 256))), dim3(256), 0, ctx->stream, d_P, ldp, n, dC, n,
                        d_flag, (const unsigned *)mirror_src, (unsigned *)mirror_dst, (int)(mirror_bytes / 4), ctx->skip_word, d_dx,
                        (const unsigned *)(mirror_dst ? ctx->mirror2_src : nullptr), (unsigned *)(mirror_dst ? ctx->mirror2_dst : nullptr),
-                       (int)((ctx->mirror2_bytes + 3) / 4), dw, ctx->update_seq, mirror_dst ? ctx->applied_word : nullptr,
+                       (int)((ctx->mirror2_bytes + 3) / 4), mirror_dst ? ctx->applied_word : nullptr,
                        mirror_dst ? ctx->cap_words : nullptr, ctx->cap, ctx->cov_save, ctx->cov_save_word, ctx->cov_save_seq);
-    ctx->update_word_used = dw != nullptr;
     if (mirror_dst && ctx->applied_word) ctx->applied_used = true;
     if (mirror_dst && ctx->mirror2_dst) ctx->mirror2_taken = true;
   }

@@ -48,9 +48,8 @@ struct FrontState {
   DetJob det_pending;
   hipStream_t det_stream = nullptr;
   hipEvent_t det_done = nullptr;
-  unsigned long long match_done_stamp = 0;  // plv_ctx::gather_stamp when match_done was recorded
-  unsigned match_word_seq = 0;              // nonzero: the flow's last kernel stores this number to plv_ctx::done_word(0)
-  hipEvent_t match_done = nullptr;  // behind the result copy of plv_perform_matching_launch: the wait does not cover what is enqueued after it
+  unsigned long long flow_done_stamp = 0;  // plv_ctx::gather_stamp when flow_done was recorded
+  hipEvent_t flow_done = nullptr;  // behind the result copy of plv_perform_matching_launch: the wait does not cover what is enqueued after it
 };
 
 #define TRY(expr)                  \
@@ -189,7 +188,7 @@ void plv_frontend_destroy(plv_ctx *ctx) {
   if (!s) return;
   if (s->det_pending.active) (void)hipEventSynchronize(s->det_done);
   if (s->det_done) (void)hipEventDestroy(s->det_done);
-  if (s->match_done) (void)hipEventDestroy(s->match_done);
+  if (s->flow_done) (void)hipEventDestroy(s->flow_done);
   if (s->det_stream) (void)hipStreamDestroy(s->det_stream);
   for (auto &b : s->img_pin) b.release();
   DevBuf *bufs[] = {&s->pyr_mem[0], &s->pyr_mem[1], &s->raw, &s->hist, &s->clahe_lut, &s->ds_src, &s->ds_dst, &s->pts0, &s->pts1, &s->n0, &s->n1,
@@ -492,16 +491,12 @@ int plv_perform_matching_launch(plv_ctx *ctx, int n, const float *pts0, const fl
                 (const float *)(hp + o_p1)));  // (+ the undistortion of both point sets on the same launch)
   const double fmax = std::max(ctx->cfg.intrinsics[0], ctx->cfg.intrinsics[1]);
   bool mirrored = false;
-  TRY(ctx->h_done.reserve(256));
-  const unsigned seq = ++ctx->match_seq;
   TRY(launch_ransac(ctx, d_n0, d_n1, n, ctx->cfg.ransac_thr_px / fmax, ctx->cfg.ransac_conf, mi, 0u, s->counts.as<int>(), d_st,
-                    d_mk, s->info.as<int>(), s->models.as<double>(), dp_ + o_p1, hp + o_p1, o_mk - o_p1, (uint8_t *)(hp + o_mk), &mirrored,
-                    (unsigned *)ctx->done_word(0), seq));
-  s->match_word_seq = mirrored ? seq : 0;
+                    d_mk, s->info.as<int>(), s->models.as<double>(), dp_ + o_p1, hp + o_p1, o_mk - o_p1, (uint8_t *)(hp + o_mk), &mirrored));
   if (!mirrored) PLV_HIP_CHECK(plv::memcpy_async(hp + o_p1, dp_ + o_p1, o_st - o_p1, hipMemcpyDeviceToHost, ctx->stream));
-  if (!s->match_done) PLV_HIP_CHECK(hipEventCreateWithFlags(&s->match_done, hipEventDisableTiming));
-  PLV_HIP_CHECK(hipEventRecord(s->match_done, ctx->stream));
-  s->match_done_stamp = ctx->gather_stamp;
+  if (!s->flow_done) PLV_HIP_CHECK(hipEventCreateWithFlags(&s->flow_done, hipEventDisableTiming));
+  PLV_HIP_CHECK(hipEventRecord(s->flow_done, ctx->stream));
+  s->flow_done_stamp = ctx->gather_stamp;
   s->pending_n = n;
   s->pending_ran = true;
   return PLV_OK;
@@ -528,13 +523,9 @@ int plv_perform_matching_wait(plv_ctx *ctx, float *pts1, uint8_t *mask_out, floa
     TRY(sync(ctx));  // (the per-kernel timer reads every event recorded so far)
   else
   {
-    // not the whole stream: the caller may have enqueued more behind the flow.  The flow's last kernel says when its results are in
-    // pinned memory; everything enqueued on the stream before it has finished by then as well (in-order stream).
-    if (s->match_word_seq && plv::knob(plv::PLV_KNOB_DONE_WORDS))
-      PLV_HIP_CHECK(plv::wait_done_word(ctx->done_word(0), s->match_word_seq, s->match_done));
-    else
-      PLV_HIP_CHECK(plv::event_sync(s->match_done));
-    if (s->match_done_stamp > ctx->cov_host_synced) ctx->cov_host_synced = s->match_done_stamp;
+    // not the whole stream: the caller may have enqueued more behind the flow
+    PLV_HIP_CHECK(plv::event_sync(s->flow_done));
+    if (s->flow_done_stamp > ctx->cov_host_synced) ctx->cov_host_synced = s->flow_done_stamp;
   }
   const size_t nn = (size_t)n;
   const size_t o_p1 = nn * 8, o_n0 = nn * 16, o_n1 = nn * 24, o_it = nn * 32, o_mk = nn * 36;
@@ -798,9 +789,7 @@ namespace plv {
 // The top-up detection of the NEXT frame, started now: on the current image (the next frame's last image) with the points this frame
 // ended with.  Runs on a side stream next to whatever the caller enqueues on the ctx stream (the updates); plv_perform_detection of
 // the next frame finds it finished (the per-kernel profiler follows it onto the side stream: Profiler::collect).
-// on_ctx_stream: enqueue behind what is on the ctx stream instead (the caller has submitted an update whose wait ends at its own
-// last kernel: the detection then runs in the device's idle time between that update and the next submission, not next to it).
-int plv_perform_detection_ahead(plv_ctx *ctx, const uint8_t *mask, const float *pts, const uint64_t *ids, int n_in, int on_ctx_stream) {
+int plv_perform_detection_ahead(plv_ctx *ctx, const uint8_t *mask, const float *pts, const uint64_t *ids, int n_in) {
   if (!ctx || n_in < 0 || (n_in > 0 && (!pts || !ids))) return PLV_E_BADARG;
   (void)hipSetDevice(ctx->device);
   FrontState *s = fe(ctx);
@@ -821,9 +810,8 @@ int plv_perform_detection_ahead(plv_ctx *ctx, const uint8_t *mask, const float *
     PLV_HIP_CHECK(hipStreamCreateWithFlags(&s->det_stream, hipStreamNonBlocking));
     PLV_HIP_CHECK(hipEventCreateWithFlags(&s->det_done, hipEventDisableTiming));
   }
-  hipStream_t st = on_ctx_stream ? ctx->stream : s->det_stream;
-  if (A.n_slots > 0) TRY(det_launch(ctx, s, s->pyr[s->cur], mask ? A.in_mask.data() : nullptr, A, st));  // (the job's own copy of the mask)
-  PLV_HIP_CHECK(hipEventRecord(s->det_done, st));
+  if (A.n_slots > 0) TRY(det_launch(ctx, s, s->pyr[s->cur], mask ? A.in_mask.data() : nullptr, A, s->det_stream));  // (the job's own copy of the mask)
+  PLV_HIP_CHECK(hipEventRecord(s->det_done, s->det_stream));
   A.active = true;
   return PLV_OK;
 }

@@ -156,9 +156,6 @@ int stage_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *s
     memcpy(h + o_rQ, tr->res_Q, 288 * (size_t)nobs);
     memcpy(h + o_rc, tr->res_clone, 4 * (size_t)nobs);
   }
-  // measurement knob PLV_KNOB_INPUTS_PINNED: no upload — the kernels read the pinned staging block over PCIe (every byte once or a
-  // few times; what a workgroup reuses it keeps in LDS)
-  const bool pinned_inputs = plv::knob(plv::PLV_KNOB_INPUTS_PINNED) && !(ex && ex->spec_li);  // (the speculative batch is patched on the device)
   // (an upload by a kernel of the ctx stream instead of the copy command was measured, alternating frame by frame: no difference)
   if (ex && ex->spec_li) {
     // the speculative batch is staged while the frame's flow occupies the ctx stream: its upload goes onto a stream of its own at once
@@ -170,9 +167,9 @@ int stage_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *s
     PLV_HIP_CHECK(plv::memcpy_async(us->jin.p, h, total, hipMemcpyHostToDevice, us->spec_stream));
     PLV_HIP_CHECK(hipEventRecord(us->spec_ev, us->spec_stream));
     PLV_HIP_CHECK(hipStreamWaitEvent(ctx->stream, us->spec_ev, 0));
-  } else if (!pinned_inputs)
+  } else
     PLV_HIP_CHECK(plv::memcpy_async(us->jin.p, h, total, hipMemcpyHostToDevice, ctx->stream));
-  const char *d = pinned_inputs ? (const char *)h : us->jin.as<char>();
+  const char *d = us->jin.as<char>();
   P.n_clones = N;
   P.clone_time = (const double *)(d + o_time);
   P.clone_R = (const double *)(d + o_R);
@@ -283,9 +280,9 @@ int build_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view
     ft->o_member = o_member, ft->o_words = o_words;
     // one launch for triangulation + Jacobians + null space while the selection has no cap to enforce (see the kernel); a speculative
     // batch holds more candidates than the cap, but its pool does not (spec_select_kernel empties every candidate otherwise)
-    fuse_tri = project && (F <= ft->max_sel || ft->spec) && !plv::knob(plv::PLV_KNOB_POINT_TRI_SEPARATE);
+    fuse_tri = project && (F <= ft->max_sel || ft->spec);
     if (ft->spec) {
-      if (!fuse_tri || plv::knob(plv::PLV_KNOB_INPUTS_PINNED)) {
+      if (!fuse_tri) {
         set_last_error("speculative point submission needs the fused triangulation launch");
         return PLV_E_BADARG;
       }
@@ -504,11 +501,7 @@ int plv_points_update_collect(plv_ctx *ctx, double *p_out, uint8_t *ok_out, doub
   // ... and work that becomes possible DURING the wait (the line pool, once the line worker has finished the frame's feed): the
   // caller's poll function is tried until it reports that nothing is left, or the update is done
   if (rc == PLV_OK && ctx->wait_poll && us->done_ev) {
-    auto running = [&]() {
-      if (us->word_seq) return __atomic_load_n((const unsigned *)ctx->done_word(16), __ATOMIC_ACQUIRE) != us->word_seq;
-      return hipEventQuery(us->done_ev) == hipErrorNotReady;
-    };
-    while (running() || plv::knob(plv::PLV_KNOB_CHAIN_ALWAYS)) {
+    while (hipEventQuery(us->done_ev) == hipErrorNotReady || plv::knob(plv::PLV_KNOB_CHAIN_ALWAYS)) {
       if (ctx->wait_poll(ctx->wait_poll_arg)) break;
       for (int i = 0; i < 32; ++i) __builtin_ia32_pause();
     }
@@ -757,12 +750,9 @@ int stage_line_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_vi
     memcpy(h + o_rQ, lt->res_Q, 288 * (size_t)nobs);
     memcpy(h + o_rc, lt->res_clone, 4 * (size_t)nobs);
   }
-  // measurement knob PLV_KNOB_INPUTS_PINNED: no upload — the kernels read the pinned staging block over PCIe (every byte once or a
-  // few times; what a workgroup reuses it keeps in LDS)
-  const bool pinned_inputs = plv::knob(plv::PLV_KNOB_INPUTS_PINNED) && !(ex && ex->spec_li);  // (the speculative batch is patched on the device)
   // (an upload by a kernel of the ctx stream instead of the copy command was measured, alternating frame by frame: no difference)
-  if (!pinned_inputs) PLV_HIP_CHECK(plv::memcpy_async(us->jin_l.p, h, total, hipMemcpyHostToDevice, ctx->stream));
-  const char *d = pinned_inputs ? (const char *)h : us->jin_l.as<char>();
+  PLV_HIP_CHECK(plv::memcpy_async(us->jin_l.p, h, total, hipMemcpyHostToDevice, ctx->stream));
+  const char *d = us->jin_l.as<char>();
   P.n_clones = N;
   P.clone_time = (const double *)(d + o_time);
   P.clone_R = (const double *)(d + o_R);
@@ -874,7 +864,7 @@ int build_lines_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_stat
     TRY(us->tri_l.reserve(total));
     char *d = us->tri_l.as<char>();
     // one launch for triangulation + Jacobians + null space while the selection has no cap to enforce (see the kernel)
-    fuse_tri = project && L <= ft->max_sel && !plv::knob(plv::PLV_KNOB_LINE_TRI_SEPARATE);
+    fuse_tri = project && L <= ft->max_sel;
     tri_cam = (double *)(d + o_cam), tri_imu = (double *)(d + o_imu), tri_valid = (unsigned char *)(d + o_valid);
     tri_lines = (double *)(d + o_lines), tri_ok = (unsigned char *)(d + o_ok);
     if (!fuse_tri) TRY(launch_triangulate_lines(ctx, Pt, tri_cam, tri_imu, tri_valid, tri_lines, tri_ok));

@@ -118,11 +118,6 @@ struct LineTracker {
   hipEvent_t canny_done = nullptr, labels_ready = nullptr;
   PinBuf pin;
   hipEvent_t edges_ready = nullptr;  // plv_line_detect_launch: the maps of image `pending_which` are on their way to the host
-  // measurement knob PLV_KNOB_EDGES_SIDE: the edge kernel of a prefetched detection on its own stream, behind the pyramid only
-  // (plv_line_edges_fork records pyr_done on the ctx stream before the flow is enqueued).  Slower than the default by 6-15 us per frame.
-  hipStream_t edge_stream = nullptr;
-  hipEvent_t pyr_done = nullptr;
-  bool edge_fork = false;
   // plv_line_edges_early: the detection being launched reads the RAW image of the frame being fed (the pyramid that will hold its
   // equalised form is not current yet) through its histogram
   std::vector<uint64_t> dec_ids;  // plv_decision_trace: the last line update's batch and its gate values (plv_last_line_decisions)
@@ -353,10 +348,8 @@ int detect(plv_ctx *ctx, LineTracker *T, int which, std::vector<float> &lines, b
     b.map = (uint8_t *)(hp + bytes);
     b.half = b.map + npix;
   }
-  // the worker's host stage splits its work by the components of the edge map when the device labels them (PLV_KNOB_LINE_LABELS_OFF:
-  // it walks the map as one sequence, as rounds 2-4 did)
-  const bool labels_off = plv::knob(plv::PLV_KNOB_LINE_LABELS_OFF);
-  const bool with_labels = launch_only && maps_to_host && !labels_off;
+  // the worker's host stage splits its work by the components of the edge map when the device labels them
+  const bool with_labels = launch_only && maps_to_host;
   if (with_labels) {
     TRY(T->lab.reserve(npix * sizeof(int)));
     TRY(T->lab_cnt.reserve(npix * sizeof(int)));
@@ -365,26 +358,18 @@ int detect(plv_ctx *ctx, LineTracker *T, int which, std::vector<float> &lines, b
     b.lab_cnt = T->lab_cnt.as<int>();
     b.lab_roots = T->lab_roots.as<int>();
     b.lab_out = (uint8_t *)(hp + lab_off);
-    if (!plv::knob(plv::PLV_KNOB_PART_LISTS_OFF)) {
-      b.blk_sorted = (uint8_t *)(hp + sorted_off);
-      b.blk_bins = (unsigned short *)(hp + bins_off);
-    }
+    b.blk_sorted = (uint8_t *)(hp + sorted_off);
+    b.blk_bins = (unsigned short *)(hp + bins_off);
   }
-  hipStream_t es = ctx->stream;
-  if (launch_only && maps_to_host && T->edge_fork) {
-    PLV_HIP_CHECK(hipStreamWaitEvent(T->edge_stream, T->pyr_done, 0));
-    es = T->edge_stream;
-  }
-  T->edge_fork = false;
-  if (!prelaunched) TRY(launch_line_edges(ctx, d_img, W, H, fp, b, es, early ? T->early_hist : nullptr));
+  if (!prelaunched) TRY(launch_line_edges(ctx, d_img, W, H, fp, b, ctx->stream, early ? T->early_hist : nullptr));
   if (with_labels && !T->ccl_stream) {
     PLV_HIP_CHECK(hipStreamCreateWithFlags(&T->ccl_stream, hipStreamNonBlocking));
     PLV_HIP_CHECK(hipEventCreateWithFlags(&T->canny_done, hipEventDisableTiming));
     PLV_HIP_CHECK(hipEventCreateWithFlags(&T->labels_ready, hipEventDisableTiming));
   }
-  if (with_labels) PLV_HIP_CHECK(hipEventRecord(T->canny_done, es));
+  if (with_labels) PLV_HIP_CHECK(hipEventRecord(T->canny_done, ctx->stream));
   if (launch_only && !T->edges_ready) PLV_HIP_CHECK(hipEventCreateWithFlags(&T->edges_ready, hipEventDisableTiming));
-  if (launch_only && maps_to_host) PLV_HIP_CHECK(hipEventRecord(T->edges_ready, es));  // (the two maps are the edge kernel's own stores)
+  if (launch_only && maps_to_host) PLV_HIP_CHECK(hipEventRecord(T->edges_ready, ctx->stream));  // (the two maps are the edge kernel's own stores)
   // the image feed's remaining launches (the pyramid) go behind the edge kernel NOW: what follows here is host work
   if (early && ctx->after_edges) TRY(ctx->after_edges(ctx->after_edges_arg));
   if (with_labels) {
@@ -435,7 +420,7 @@ int detect(plv_ctx *ctx, LineTracker *T, int which, std::vector<float> &lines, b
       PLV_HIP_CHECK(plv::memcpy_async(hmap + npix, T->half.p, npix, hipMemcpyDeviceToHost, ctx->stream));
     }
     if (launch_only) {
-      if (!maps_to_host) PLV_HIP_CHECK(hipEventRecord(T->edges_ready, es));  // (behind the two copy commands above)
+      if (!maps_to_host) PLV_HIP_CHECK(hipEventRecord(T->edges_ready, ctx->stream));  // (behind the two copy commands above)
       T->pending_which = which;
       T->pending_fed = plv_front_fed_count(ctx) + (early ? 1 : 0);  // (early: the image becomes the current one when its feed returns)
       if (!T->worker.joinable()) T->worker = std::thread(line_worker, T);
@@ -520,11 +505,9 @@ void plv_line_tracker_destroy(plv_ctx *ctx) {
     for (DevBuf *b : bufs) b->release();
     T->pin.release();
     if (T->edges_ready) (void)hipEventDestroy(T->edges_ready);
-    if (T->pyr_done) (void)hipEventDestroy(T->pyr_done);
     if (T->canny_done) (void)hipEventDestroy(T->canny_done);
     if (T->labels_ready) (void)hipEventDestroy(T->labels_ready);
     if (T->ccl_stream) (void)hipStreamDestroy(T->ccl_stream);
-    if (T->edge_stream) (void)hipStreamDestroy(T->edge_stream);
     delete T;
     g_lt.erase(it);
   }
@@ -633,23 +616,6 @@ int plv_vanishing_points(const double *R_ItoC, const double *K8, double *vps) {
 namespace plv {
 // TrackLSD::feed_monocular for the image currently in the ctx (fed by plv_tracker_feed / plv_feed_image,
 // which also is where the reference's second equalizeHist comes from: same input, same result).
-// (internal, the tracker feed) marks the point on the ctx stream the prefetched edge kernel has to wait for — the pyramid of the image
-// just fed — so that the kernel can be enqueued on its own stream after the flow has been enqueued on the ctx stream.
-int plv_line_edges_fork(plv_ctx *ctx) {
-  if (!ctx) return PLV_E_BADARG;
-  if (!plv::knob(plv::PLV_KNOB_EDGES_SIDE)) return 1;  // default: on the ctx stream, in front of the flow (plv_ctx.hpp "Measurement knobs")
-  LineTracker *T = ltr(ctx, false);
-  std::lock_guard<std::mutex> lk(T->mtx);
-  if (T->walk_on_device) return 1;
-  if (!T->edge_stream) {
-    PLV_HIP_CHECK(hipStreamCreateWithFlags(&T->edge_stream, hipStreamNonBlocking));
-    PLV_HIP_CHECK(hipEventCreateWithFlags(&T->pyr_done, hipEventDisableTiming));
-  }
-  PLV_HIP_CHECK(hipEventRecord(T->pyr_done, ctx->stream));
-  T->edge_fork = true;
-  return PLV_OK;
-}
-
 // The tracker feed's hook into the image feed (plv_ctx::edges_hook): plv_line_detect_launch for the image being fed, between its
 // histogram and its pyramid — the edge kernel equalises the raw image itself (canny_kernel), the worker gets the maps two launches
 // earlier, and the flow starts when it always did.  Host-walk configuration without hysteresis only (the shipped one).
@@ -1114,7 +1080,7 @@ namespace plv {
 // update runs on the device.  Never blocks: returns 0 while the feed is still on the worker (try again), 1 when the pool is formed or
 // cannot be formed ahead of time (plv_camera_update_lines then forms it).
 int plv_line_pool_prepare(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt) {
-  if (plv::knob(plv::PLV_KNOB_POOL_LATE) || !ctx || !st || !opt || opt->cpi || st->n_clones < 2 || st->dt_state_id >= 0) return 1;  // (a calibrated time offset moves the window test)
+  if (!ctx || !st || !opt || opt->cpi || st->n_clones < 2 || st->dt_state_id >= 0) return 1;  // (a calibrated time offset moves the window test)
   LineTracker *T;
   {
     std::lock_guard<std::mutex> lk(g_mtx);
@@ -1143,7 +1109,7 @@ int plv_line_pool_prepare(plv_ctx *ctx, const plv_state_view *st, const plv_upda
 void plv_line_feed_pool_args(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt) {
   LineTracker *T = ltr(ctx);
   T->feed.pool_on = false;
-  if (plv::knob(plv::PLV_KNOB_POOL_LATE) || !st || !opt || opt->cpi || st->n_clones < 2 || st->dt_state_id >= 0) return;
+  if (!st || !opt || opt->cpi || st->n_clones < 2 || st->dt_state_id >= 0) return;
   T->feed.pool_args = PoolArgs::of(st, opt);
   T->feed.pool_on = true;
 }

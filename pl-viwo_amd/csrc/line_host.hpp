@@ -33,8 +33,8 @@ struct Job {
   // the root of the pixel's 8-connected component) % parts.  With them the host stage splits the detection by components (host_extract).
   const uint8_t *hlab = nullptr;
   int parts = 0;
-  // (nullable) the parts' pixels in raster order per run of 256 pixels (ccl_flatten_kernel: blk_sorted / blk_bins; lists_from_labels
-  // forms the same on the host): a part is then staged and seeded from its own pixels (detect_part)
+  // the parts' pixels in raster order per run of 256 pixels (ccl_flatten_kernel: blk_sorted / blk_bins; lists_from_labels forms the same
+  // on the host): a part is staged and seeded from its own pixels (detect_part).  The split needs them next to the labels.
   const uint8_t *hsorted = nullptr;
   const unsigned short *hbins = nullptr;
   int2 *hpts = nullptr;
@@ -357,59 +357,40 @@ inline void detect_part(Fit &F, const Job &J, int p, Fit::Scratch &S, int slot, 
   auto stop = [&] { return F.winner[p].load(std::memory_order_relaxed) >= 0 || F.closed_gen.load(std::memory_order_relaxed) >= g; };
   if (stop()) return;  // (claimed just as the job was closed: nothing of the job is touched)
   const int w = J.w, h = J.h, pw = w + 2;
-  const bool listed = J.hsorted != nullptr && J.hbins != nullptr && w < 65536 && h < 65536;
-  if (S.pad.size() != (size_t)pw * (h + 2) || (listed && (S.clean_w != w || S.clean_h != h))) {
+  if (S.pad.size() != (size_t)pw * (h + 2) || S.clean_w != w || S.clean_h != h) {
     S.pad.assign((size_t)pw * (h + 2), 1);
     S.clean_w = w, S.clean_h = h;
   }
   uint8_t *m = S.pad.data();
-  if (listed) {
-    // The part's own pixels (a fraction of a per cent of the map) instead of a pass over the labels of the whole image per part: the
-    // thread's map holds no edge when a walk is over — every listed pixel is a seed or a chain's — so staging a part is writing its
-    // pixels, and its seeds are those pixels in the order they are listed in (raster order).
-    const int n = w * h, nblk = (n + 255) / 256, stride = J.parts + 1;
-    S.seeds.clear();
-    int row = 0, col = 0;  // of the run's first pixel (a run is 256 pixels: it ends on the same row or the next, w >= 256, or later)
-    for (int b = 0; b < nblk; ++b) {
-      const unsigned short *bn = J.hbins + (size_t)b * stride;
-      const uint8_t *so = J.hsorted + (size_t)b * 256;
-      // (bounds held against any content: a detection that has been superseded — plv_line_detect_launch for another image, then a
-      // detection from scratch — may still be reading these lists while the next edge launch rewrites them; its result is dropped, but
-      // a pixel outside the image would put an edge on the map's border and the walk off the map)
-      for (int q = std::min<int>(bn[p], 256), q1 = std::min<int>(bn[p + 1], 256); q < q1; ++q) {
-        if (b * 256 + (int)so[q] >= n) continue;
-        int x = col + so[q], y = row;
-        while (x >= w) x -= w, ++y;
-        m[(size_t)(y + 1) * pw + x + 1] = 2;
-        S.seeds.push_back((uint32_t)y << 16 | (uint32_t)x);
-      }
-      col += 256;
-      while (col >= w) col -= w, ++row;
+  // The part's own pixels (a fraction of a per cent of the map) instead of a pass over the labels of the whole image per part: the
+  // thread's map holds no edge when a walk is over — every listed pixel is a seed or a chain's — so staging a part is writing its
+  // pixels, and its seeds are those pixels in the order they are listed in (raster order).
+  const int n = w * h, nblk = (n + 255) / 256, stride = J.parts + 1;
+  S.seeds.clear();
+  int row = 0, col = 0;  // of the run's first pixel (a run is 256 pixels: it ends on the same row or the next, w >= 256, or later)
+  for (int b = 0; b < nblk; ++b) {
+    const unsigned short *bn = J.hbins + (size_t)b * stride;
+    const uint8_t *so = J.hsorted + (size_t)b * 256;
+    // (bounds held against any content: a detection that has been superseded — plv_line_detect_launch for another image, then a
+    // detection from scratch — may still be reading these lists while the next edge launch rewrites them; its result is dropped, but
+    // a pixel outside the image would put an edge on the map's border and the walk off the map)
+    for (int q = std::min<int>(bn[p], 256), q1 = std::min<int>(bn[p + 1], 256); q < q1; ++q) {
+      if (b * 256 + (int)so[q] >= n) continue;
+      int x = col + so[q], y = row;
+      while (x >= w) x -= w, ++y;
+      m[(size_t)(y + 1) * pw + x + 1] = 2;
+      S.seeds.push_back((uint32_t)y << 16 | (uint32_t)x);
     }
-  } else {
-    memset(m, 1, (size_t)pw);
-    memset(m + (size_t)(h + 1) * pw, 1, (size_t)pw);
-    const uint8_t want = (uint8_t)(p + 1);
-    for (int r = 0; r < h; ++r) {
-      uint8_t *row = m + (size_t)(r + 1) * pw;
-      const uint8_t *lr = J.hlab + (size_t)r * w;
-      row[0] = 1;
-      for (int x = 0; x < w; ++x) row[x + 1] = (uint8_t)(1 + (lr[x] == want));
-      row[w + 1] = 1;
-    }
+    col += 256;
+    while (col >= w) col -= w, ++row;
   }
   S.pts.resize((size_t)w * h);
   S.chains.resize(kChainCap);
   int counts[4] = {0, 0, 0, 0};
   const auto tp1 = std::chrono::steady_clock::now();
-  if (listed)
-    walk_listed(m, w, S.seeds.data(), S.seeds.size(), J.length_threshold, S.pts.data(), S.chains.data(), kChainCap, counts, stop);
-  else
-    walk_padded(m, w, h, J.length_threshold, S.pts.data(), S.chains.data(), kChainCap, counts);
-  S.clean_w = w, S.clean_h = h;  // (either walk has consumed every edge of the map)
+  walk_listed(m, w, S.seeds.data(), S.seeds.size(), J.length_threshold, S.pts.data(), S.chains.data(), kChainCap, counts, stop);
   if (stop()) {  // (a walk that was cut short may have left edges behind)
-    if (listed)
-      for (const uint32_t sd : S.seeds) m[(size_t)((sd >> 16) + 1) * pw + (sd & 0xffffu) + 1] = 1;
+    for (const uint32_t sd : S.seeds) m[(size_t)((sd >> 16) + 1) * pw + (sd & 0xffffu) + 1] = 1;
     return;
   }
   const auto tp2 = std::chrono::steady_clock::now();
@@ -620,9 +601,10 @@ inline int host_extract(HostStage *T, Job &J, bool timing) {
   // worker's path decides whether the line launch can be chained behind the point update (tracker_api.hip poll_line_pool), so the
   // second fitter joins at configs[2] as well: alternating frame by frame -9 us on the mean and -80 .. -130 us on p99
   // (bench.py --alternate-fit 1,2).  Tiny maps keep one: every hand-over between threads is a chance of a delayed wake-up.
-  // A labelled job is split by components over the walking thread and every configured helper (detect_part); without labels the walk
-  // is one sequence and the helpers only grow segments behind it.
-  const bool by_parts = J.hlab != nullptr && J.parts >= 1 && J.parts <= Fit::kParts;
+  // A labelled job with its parts' pixel lists is split by components over the walking thread and every configured helper (detect_part;
+  // a seed packs y << 16 | x); without them the walk is one sequence and the helpers only grow segments behind it.
+  const bool by_parts = J.hlab != nullptr && J.hsorted != nullptr && J.hbins != nullptr && J.parts >= 1 && J.parts <= Fit::kParts &&
+                        J.w < 65536 && J.h < 65536;
   const int nfit = by_parts ? std::min(fit_threads().load(std::memory_order_relaxed), J.parts - 1)
                             : std::min(std::min(fit_threads().load(std::memory_order_relaxed), 2), (size_t)J.w * J.h >= 60000 ? 2 : 1);
   quiesce_helpers(F);  // (a helper cut off inside a part of the last detection: Fit::part and winner are about to be written again, and
@@ -631,15 +613,13 @@ inline int host_extract(HostStage *T, Job &J, bool timing) {
     for (int p = 0; p < J.parts; ++p) F.winner[p].store(-1, std::memory_order_relaxed);
     // the order the parts are claimed in: the largest first (the threads' shares end level), sizes from the parts' pixel lists
     int size[Fit::kParts] = {};
-    if (J.hbins) {
-      const int nblk = (J.w * J.h + 255) / 256, stride = J.parts + 1;
-      for (int b = 0; b < nblk; ++b) {
-        const unsigned short *bn = J.hbins + (size_t)b * stride;
-        for (int p = 0; p < J.parts; ++p) size[p] += bn[p + 1] - bn[p];
-      }
+    const int nblk = (J.w * J.h + 255) / 256, stride = J.parts + 1;
+    for (int b = 0; b < nblk; ++b) {
+      const unsigned short *bn = J.hbins + (size_t)b * stride;
+      for (int p = 0; p < J.parts; ++p) size[p] += bn[p + 1] - bn[p];
     }
     for (int p = 0; p < J.parts; ++p) F.claim_order[p] = p;
-    if (J.hbins) std::stable_sort(F.claim_order, F.claim_order + J.parts, [&](int a, int b) { return size[a] > size[b]; });
+    std::stable_sort(F.claim_order, F.claim_order + J.parts, [&](int a, int b) { return size[a] > size[b]; });
   }
   F.next_part.store(0, std::memory_order_relaxed);
   F.job_t0 = T1;
@@ -657,15 +637,10 @@ inline int host_extract(HostStage *T, Job &J, bool timing) {
   if (by_parts) {
     claim_parts(F, J, 0, gen);
     // Every part is claimed; those still undecided are with threads that have not finished — most of the time about to, now and then
-    // descheduled for milliseconds (other tenants' work on the same cores).  This thread has nothing else to do: it runs such a part
-    // again, into the part's second output, the earliest claimed first; whichever run ends first counts and the other gives up.
-    // Every part is claimed; those still undecided are with threads that have not finished — most of the time about to, now and then
     // descheduled for milliseconds (other tenants' work on the same cores).  This thread takes the decided parts' chains into the
     // order of their seeds meanwhile (a part's chains come in that order: one merge of two sorted lists per part, all but the last
     // of them inside the wait), and when nothing is left to take in it runs an undecided part again, into the part's second output,
     // the earliest claimed first; whichever run ends first counts and the other gives up.
-    const bool wait_all = plv::knob(plv::PLV_KNOB_WAIT_ALL_HELPERS);  // (measurement: rounds 5-6a waited for every helper's report)
-    if (wait_all) wait_reports(F, nfit, gen);
     F.merged.clear();
     bool taken[Fit::kParts] = {};
     for (int left = J.parts; left > 0;) {
@@ -892,11 +867,6 @@ inline void run_on_helpers(HostStage *T, int nhelpers, const std::function<void(
   for (int sl = 1; sl <= nhelpers; ++sl) F.slot_claim[sl].store(0, std::memory_order_relaxed);  // (nobody is inside a generic job now: the last one was closed)
   const int gen = post_job(F, nullptr, nhelpers, false, &fn);
   fn(0);
-  if (plv::knob(plv::PLV_KNOB_WAIT_ALL_HELPERS)) {
-    wait_reports(F, nhelpers, gen);
-    F.closed_gen.store(gen);
-    return;
-  }
   for (int sl = 1; sl <= nhelpers; ++sl) {
     int unclaimed = 0;
     if (F.slot_claim[sl].compare_exchange_strong(unclaimed, 1)) fn(sl);
@@ -908,7 +878,7 @@ inline void run_on_helpers(HostStage *T, int nhelpers, const std::function<void(
 // line and the points, and the ranges' results are joined in line order — the same Assign as the serial call.
 inline void assign_points_parallel(HostStage *T, int nhelpers, const float *lines, int nl, const float *pts, const uint64_t *ids, int np, Assign &A,
                                    float assign_px = 5.0f) {
-  const int nt = plv::knob(plv::PLV_KNOB_ASSIGN_ONE_THREAD) ? 1 : std::max(1, std::min(nhelpers + 1, nl / 50));
+  const int nt = std::max(1, std::min(nhelpers + 1, nl / 50));
   if (nt == 1) {
     assign_points(lines, nl, pts, ids, np, A, assign_px);
     return;

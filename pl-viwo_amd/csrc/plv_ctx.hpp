@@ -69,26 +69,18 @@ inline hipError_t memcpy_async(void *dst, const void *src, size_t bytes, hipMemc
 }
 
 // Measurement knobs (plv_debug_knobs): alternative placements kept in the library so that tools can switch them frame by frame inside
-// one process — run-to-run drift on a box (+-25 us per frame) is larger than what most single changes move.
-//   1  the prefetched edge kernel on its own stream behind the pyramid instead of on the ctx stream in front of the flow (measured
-//      with tools: 6-15 us per frame SLOWER, four alternating runs of 600 frames; the default stays on the ctx stream)
+// one process — run-to-run drift on a box (+-25 us per frame) is larger than what most single changes move — and paths that tests
+// force which the library also takes on its own.  An alternative that was measured and lost goes, with its bit (profiles/HISTORY.md
+// names them); a retired bit is a no-op: plv_debug_knobs still stores and returns the whole mask.
 //   2  the whitened update's prior factor started behind the Jacobian launch instead of before the update's upload
-//   4  the edge kernel behind flow + RANSAC (PLV_KNOB_EDGES_LATE)          8  the next frame's detection on the ctx stream (PLV_KNOB_AHEAD_CTX)
-//  16  the line pool formed after the point update (PLV_LINE_POOL_LATE)    32 / 64  point / line triangulation as its own launch
-// 128  the Jacobian launches read their inputs from the pinned staging block instead of an uploaded copy
 // 1024 the gate as chi2_t_kernel + chi2_gate_kernel behind the Jacobian launch instead of as that launch's tail (gate_core.hpp)
-// 256  the flow's and the updates' waits on completion words their last kernels write into pinned memory (plv_ctx::h_done) instead of
-//      on HIP events: a bare word is seen 4.8 us earlier (tools/ubench/waitlat.hip), in the frame it gains nothing (0 .. 9 us SLOWER over
-//      four alternating runs: the commit then runs as one workgroup so that the word also covers the covariance)
-//  512 the prefetched edge kernel behind the pyramid (rounds 2-3) instead of between the histogram and the pyramid (round 4: it equalises
-//      the raw image itself, canny_kernel; the maps reach the line worker two launches earlier)
 // 2048 no chained line launch: the line half is staged and enqueued after the host has collected and applied the point update (round 3)
-// 8192 every whitened update takes its factor form (dense_kernels.hip "whitened update"; tests: the form the prior factor would pick
-//      only late in a drive runs on every batch)
 // 4096 the point update's wait keeps polling its hook until the hook is done even when the device has finished (tests: every frame's
 //      line launch is chained, whatever the timing of the line worker)
-enum : unsigned { PLV_KNOB_CHAIN_ALWAYS = 4096u, PLV_KNOB_NO_CHAIN = 2048u, PLV_KNOB_EDGES_SIDE = 1u, PLV_KNOB_PRIOR_LATE = 2u, PLV_KNOB_EDGES_LATE = 4u, PLV_KNOB_AHEAD_CTX = 8u, PLV_KNOB_POOL_LATE = 16u,
-                  PLV_KNOB_POINT_TRI_SEPARATE = 32u, PLV_KNOB_LINE_TRI_SEPARATE = 64u, PLV_KNOB_INPUTS_PINNED = 128u, PLV_KNOB_DONE_WORDS = 256u, PLV_KNOB_GATE_SEPARATE = 1024u, PLV_KNOB_EDGES_AFTER_PYRAMID = 512u, PLV_KNOB_FORCE_FACTOR_FORM = 8192u,
+// 8192 every whitened update takes its factor form (dense_kernels.hip "whitened update"; tests: the form the prior factor would pick
+//      only late in a drive runs on every batch)
+enum : unsigned { PLV_KNOB_PRIOR_LATE = 2u, PLV_KNOB_GATE_SEPARATE = 1024u, PLV_KNOB_NO_CHAIN = 2048u, PLV_KNOB_CHAIN_ALWAYS = 4096u,
+                  PLV_KNOB_FORCE_FACTOR_FORM = 8192u,
                   // reporting aids (round 5: every measurement switch that used to be an environment variable of its own is a bit here)
                   PLV_KNOB_HOST_TIMING = 1u << 14,    // phase table of the host side on stderr when the library unloads (HostPhases)
                   PLV_KNOB_LINE_TIMING = 1u << 15,    // the line worker's stages, per frame, on stderr
@@ -97,15 +89,10 @@ enum : unsigned { PLV_KNOB_CHAIN_ALWAYS = 4096u, PLV_KNOB_NO_CHAIN = 2048u, PLV_
                   PLV_KNOB_CHAIN_EVENTS = 1u << 18,   // HIP events around the chained launches (with HOST_TIMING)
                   PLV_KNOB_ALLOC_DEBUG = 1u << 19,    // every (re)allocation of a library buffer with a backtrace
                   PLV_KNOB_HOST_FAULTS = 1u << 20,    // HostPhase counts minor page faults instead of time
-                  PLV_KNOB_LK_LEGACY_LOOP = 1u << 21, // lk_kernel<0>: the iteration of rounds 2-4 (tools/lk_exp.py; same bits, slower)
-                  PLV_KNOB_LINE_LABELS_OFF = 1u << 22,
-                  PLV_KNOB_LK_AHEAD = 1u << 23,
-                  PLV_KNOB_TSQR_TREE = 1u << 29,          // the Householder compression as the tree of unblocked workgroup factorisations (rounds 1-6a) instead of hqr_kernel
-                  PLV_KNOB_HELPER_NAPS = 1u << 28,        // tests: the line detector's helper threads fall asleep (up to 200 us) at random when they pick a job up or start a part
-                  PLV_KNOB_WAIT_ALL_HELPERS = 1u << 27,   // the line worker's jobs wait for every helper thread's report (rounds 5-6a) instead of doing a late helper's share themselves
-                  PLV_KNOB_PART_LISTS_OFF = 1u << 26,     // the host stage builds a part's map from the labels of the whole image (round 5) instead of the part's own pixel list
-                  PLV_KNOB_ASSIGN_ONE_THREAD = 1u << 25,  // the line feed's point-line assignment on the worker alone (rounds 1-5)
-                  PLV_KNOB_NO_SPECULATION = 1u << 24 };    // plv_camera_frame submits the point update after the flow's result has reached the host (rounds 1-5), not behind the flow          // lk_ahead_kernel (round 6 experiment: all levels' templates first, search tiles a level ahead; same bits, no faster)  // the line detector's host stage walks the edge map as one sequence (rounds 2-4) instead of by labelled components
+                  PLV_KNOB_NO_SPECULATION = 1u << 24, // plv_camera_frame submits the point update after the flow's result has reached the host (rounds 1-5), not behind the flow
+                  PLV_KNOB_HELPER_NAPS = 1u << 28,    // tests: the line detector's helper threads fall asleep (up to 200 us) at random when they pick a job up or start a part
+                  PLV_KNOB_TSQR_TREE = 1u << 29 };    // the Householder compression as the tree of unblocked workgroup factorisations (rounds 1-6a) instead of hqr_kernel
+// Retired bits, no-ops now: 1, 4, 8, 16, 32, 64, 128, 256, 512, 1 << 21, 1 << 22, 1 << 23, 1 << 25, 1 << 26, 1 << 27.
 // The mask starts from PLV_DEBUG_KNOBS in the environment (the library's only measurement variable; plv_debug_knobs changes it at run time)
 inline std::atomic<unsigned> &knobs() {
   static std::atomic<unsigned> k{getenv("PLV_DEBUG_KNOBS") ? (unsigned)strtoul(getenv("PLV_DEBUG_KNOBS"), nullptr, 0) : 0u};
@@ -441,21 +428,6 @@ struct Profiler {
   }
 };
 
-// Waits until *word == want (a kernel stores it behind its results).  `ev` (recorded behind that kernel) is looked at now and then: a
-// chain that ended another way, or failed, must not hang the host.
-inline hipError_t wait_done_word(volatile unsigned *word, unsigned want, hipEvent_t ev) {
-  ++counters().syncs;
-  for (unsigned spins = 1;; ++spins) {
-    if (__atomic_load_n((const unsigned *)word, __ATOMIC_ACQUIRE) == want) return hipSuccess;
-    if ((spins & 8191u) == 0 && ev && hipEventQuery(ev) != hipErrorNotReady) {
-      const hipError_t e = hipEventSynchronize(ev);
-      std::atomic_thread_fence(std::memory_order_acquire);
-      return e;
-    }
-    __builtin_ia32_pause();
-  }
-}
-
 struct ProfScope {
   Profiler &p;
   hipStream_t s;
@@ -548,15 +520,6 @@ struct plv_ctx {
   double *cov_save = nullptr;
   unsigned *cov_save_word = nullptr;
   unsigned cov_save_seq = 0;
-  // Measurement knob PLV_KNOB_DONE_WORDS — completion words in pinned memory: the last kernel of the flow (word 0) and of an update
-  // (word 16) stores the call's sequence number there behind its result block (system-scope release) and the host spins on the word
-  // instead of waiting on an event.  Off by default (no gain in the frame, see the knob list).
-  plv::PinBuf h_done;
-  unsigned match_seq = 0, update_seq = 0;
-  bool update_word_armed = false;  // the update being enqueued may end in a kernel that stores update_seq to done_word(16) ...
-  bool update_word_used = false;   // ... and did
-  volatile unsigned *done_word(int i) { return h_done.p ? (volatile unsigned *)h_done.p + i : nullptr; }
-
   // Device word holding the number of features the gate accepted in the update being enqueued (null outside
   // plv_msckf_update_resident_launch): the compression and EKF kernels return at once when it is zero — an update in which the gate
   // took nothing (most line updates) costs their launches, not their pivot chains; ekf_commit_kernel then reports dx = 0.

@@ -46,8 +46,8 @@ int plv_front_match_device(plv_ctx *ctx, const float **d_p1, const float **d_n1,
 const uint8_t *plv_front_level0(plv_ctx *ctx, int which, int *w, int *h);
 // plv_ctx_synchronize: waits for a detection started ahead of time on the side stream (the job stays collectable)
 int plv_front_quiesce(plv_ctx *ctx);
-// starts the next frame's top-up detection ahead of time, on the side stream or (on_ctx_stream) behind the ctx stream
-int plv_perform_detection_ahead(plv_ctx *ctx, const uint8_t *mask, const float *pts, const uint64_t *ids, int n_in, int on_ctx_stream);
+// starts the next frame's top-up detection ahead of time, on the side stream
+int plv_perform_detection_ahead(plv_ctx *ctx, const uint8_t *mask, const float *pts, const uint64_t *ids, int n_in);
 
 // ---- tracker_api.hip
 // plv_ctx_destroy: the ctx's point tracker and feature database
@@ -68,8 +68,6 @@ void plv_tracker_run_deferred(void *ctx);
 void plv_line_tracker_destroy(plv_ctx *ctx);
 // whether the frame's lines are detected ahead of the line tracker's feed
 int plv_line_prefetch_enabled(plv_ctx *ctx);
-// marks the point on the ctx stream the prefetched edge kernel waits for (the pyramid of the image just fed)
-int plv_line_edges_fork(plv_ctx *ctx);
 // the tracker feed's hook into the image feed (plv_ctx::edges_hook): the edge kernel between histogram and pyramid
 void plv_line_edges_early(plv_ctx *ctx, const uint8_t *d_raw, int W, int H, const unsigned *d_hist);
 // plv_line_tracker_feed_async with the frame's tracked points handed in, posted the moment the point list stands

@@ -34,7 +34,6 @@ struct Tracker {
   uint64_t currid = 0;             // REF: TrackBase::currid (4*num_aruco + 1 - 1 = 0 without ArUco tags)
   int detect_ahead = 2;            // plv_tracker_detect_ahead: start the next frame's top-up detection ahead of time (1: at the end of the feed, 2: once the point update is submitted)
   bool ahead_deferred = false;     // ... asked for by the last feed, not started yet (start_detection_ahead)
-  bool ahead_on_ctx_stream = false;  // plv_camera_try_update with a line update to follow: the detection goes behind the point update
   bool defer_db = false;           // plv_camera_try_update: the point update leaves its database hand-back to run_deferred_db
   const plv_state_view *early_st = nullptr;       // plv_camera_try_update with a line update to follow: the line pool is formed inside
   const plv_update_options *early_lines = nullptr;  // the point update's wait when the frame's line feed has finished by then
@@ -137,9 +136,9 @@ extern "C" {
 
 static int tracker_feed_fed(plv_ctx *ctx, Tracker *T, double timestamp, const uint8_t *mask);
 // the image feed with the line detector's edge kernel between its histogram and its pyramid (plv_ctx::edges_hook) when the frame's
-// lines are detected ahead of the line tracker's feed anyway; PLV_KNOB_EDGES_LATE / the other edge knobs keep the older orders
+// lines are detected ahead of the line tracker's feed anyway
 static int feed_with_early_edges(plv_ctx *ctx, const std::function<int()> &feed) {
-  const bool early = !plv::knob(plv::PLV_KNOB_EDGES_LATE | plv::PLV_KNOB_EDGES_SIDE | plv::PLV_KNOB_EDGES_AFTER_PYRAMID) && plv_line_prefetch_enabled(ctx) != 0;
+  const bool early = plv_line_prefetch_enabled(ctx) != 0;
   ctx->edges_hook_fired = false;
   ctx->edges_hook = early ? plv_line_edges_early : nullptr;
   const int rc = feed();
@@ -188,7 +187,7 @@ static void spec_submit(plv_ctx *ctx, Tracker *T, double t_now, int n_flow, cons
   S.active = false;
   const plv_state_view *st = T->spec_st;
   const plv_update_options *opt = T->spec_opt;
-  if (plv::knob(plv::PLV_KNOB_NO_SPECULATION | plv::PLV_KNOB_GATE_SEPARATE | plv::PLV_KNOB_POINT_TRI_SEPARATE | plv::PLV_KNOB_INPUTS_PINNED) || !st || !opt || opt->cpi || opt->max_slam > 0 || opt->n_slam > 0 || st->n_clones < 4 || opt->max_msckf < 1 ||
+  if (plv::knob(plv::PLV_KNOB_NO_SPECULATION | plv::PLV_KNOB_GATE_SEPARATE) || !st || !opt || opt->cpi || opt->max_slam > 0 || opt->n_slam > 0 || st->n_clones < 4 || opt->max_msckf < 1 ||
       opt->max_obs < 2 || ctx->cov_n < 1 || ctx->decision_trace || n_flow < 10 || ctx->prof.on)
     return;
   {
@@ -372,8 +371,7 @@ static int tracker_feed_fed(plv_ctx *ctx, Tracker *T, double timestamp, const ui
   // With the line prefetch on (plv_line_prefetch_mode), resize + Canny of the new image and the copies of the two maps go first on
   // the stream and the library's line worker thread walks the edge chains and grows the segments while this thread runs the point
   // front-end; plv_line_tracker_feed of the same frame joins it.
-  // (enqueued further down, behind the flow + RANSAC of this frame: the point front-end starts the moment the pyramid is built, and
-  // the line worker, whose host stage has slack against the point update, gets its edge maps ~0.1 ms later)
+  // (when the image feed has not launched it already: enqueued further down, in front of the flow)
   bool prefetch_lines = plv_line_prefetch_enabled(ctx) != 0 && !ctx->edges_hook_fired;  // (fired: the image feed launched it already)
   ctx->edges_hook_fired = false;
   auto launch_prefetch = [&]() {
@@ -423,12 +421,9 @@ static int tracker_feed_fed(plv_ctx *ctx, Tracker *T, double timestamp, const ui
     plv::HostPhase ph("tracker_feed: perform_matching");
     // the line detector's pixel work (18 us) goes in FRONT of the flow: the edge maps then reach the library's line worker ~0.1 ms
     // earlier than behind flow + RANSAC, and the worker (chain walk, segment growth, assignment, matching) is the longer of the two
-    // paths that meet at the line update; PLV_KNOB_EDGES_LATE restores the old order
-    // (plv_line_edges_fork: a measurement knob that puts the kernel on its own stream behind the pyramid instead — the flow then does
-    //  not wait 18 us for it, and yet the frame is 6-15 us slower, measured alternating frame by frame)
-    if (!plv::knob(plv::PLV_KNOB_EDGES_LATE) && prefetch_lines && plv_line_edges_fork(ctx) != PLV_OK) launch_prefetch();
+    // paths that meet at the line update
+    launch_prefetch();
     const int rc_l = plv_perform_matching_launch(ctx, n, pts.data(), pts_new.data());
-    launch_prefetch();  // (inside the wait for the flow)
     if (rc_l == PLV_OK) plv_line_run_deferred(ctx);  // the previous frame's line database hand-back, if one was left behind
     TRY(rc_l);
     // ... and, while the flow runs: where every listed point's track sits in the database (one look-up each, the track's vectors
@@ -490,7 +485,7 @@ static int tracker_feed_fed(plv_ctx *ctx, Tracker *T, double timestamp, const ui
   // instead of in front of it; without an update in between, the next feed detects in place as usual
   T->ahead_deferred = T->detect_ahead == 2 && !T->ids_last.empty();
   if (T->detect_ahead == 1 && !T->ids_last.empty())
-    (void)plv_perform_detection_ahead(ctx, mask, T->pts_last.data(), T->ids_last.data(), (int)T->ids_last.size(), 0);
+    (void)plv_perform_detection_ahead(ctx, mask, T->pts_last.data(), T->ids_last.data(), (int)T->ids_last.size());
   return PLV_OK;
 }
 
@@ -502,10 +497,9 @@ static void start_detection_ahead(void *arg) {
     std::lock_guard<std::mutex> lk(T->mtx);
     if (T->ahead_deferred) {
       T->ahead_deferred = false;
-      // (with a line update to follow: behind the point update on the ctx stream — its wait ends at the update's own last kernel and
-      // the detection fills the device's idle time until the line update is submitted; else on the side stream, next to the update)
+      // (on the side stream, next to the update)
       (void)plv_perform_detection_ahead(ctx, T->mask_last.empty() ? nullptr : T->mask_last.data(), T->pts_last.data(), T->ids_last.data(),
-                                        (int)T->ids_last.size(), T->ahead_on_ctx_stream ? 1 : 0);
+                                        (int)T->ids_last.size());
     }
   }
 }
@@ -1379,9 +1373,8 @@ int plv_camera_try_update(plv_ctx *ctx, const plv_state_view *st, plv_try_update
   };
   // the next frame's top-up detection runs on the side stream next to the point update.  (Round 2 placed it on the ctx stream behind
   // the update when a line update follows; since the line pool is formed inside the point update's wait, the line update is submitted
-  // right after that wait and would queue behind the detection: PLV_KNOB_AHEAD_CTX restores that placement for measurements.)
+  // right after that wait and would queue behind the detection.)
   T->defer_db = io->opt_lines != nullptr;
-  T->ahead_on_ctx_stream = io->opt_lines != nullptr && plv::knob(plv::PLV_KNOB_AHEAD_CTX);
   T->early_st = io->opt_lines ? st : nullptr;
   T->early_lines = io->opt_lines;
   T->early_cap = io->line_cap;
@@ -1424,7 +1417,7 @@ int plv_camera_try_update(plv_ctx *ctx, const plv_state_view *st, plv_try_update
   int rc = plv_camera_update_points(ctx, st, io->opt_points, io->dx_points, io->res_points, io->msckf_ids, io->msckf_accepted, io->p_FinG);
   ctx->wait_poll = nullptr;
   ch.ready = false;
-  T->defer_db = T->ahead_on_ctx_stream = false;
+  T->defer_db = false;
   T->early_st = nullptr, T->early_lines = nullptr;
   bool chained = io->opt_lines && plv_camera_lines_job_pending(ctx);
   if (chained && (plv_update_state(ctx)->last_route >= 5 || io->res_points->status != PLV_OK)) {

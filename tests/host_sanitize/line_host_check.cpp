@@ -164,20 +164,17 @@ int main(int argc, char **argv) {
       Job J;
       J.w = w, J.h = h, J.length_threshold = 20, J.distance_threshold = 1.414213562f, J.thr2 = 1600.0f;
       J.hmap = maps[i].data(), J.hhalf = halves[i].data(), J.hpts = pts.data(), J.hc = chains.data();
-      // every other pass with the components labelled: the detection split into 16, 3 or 1 parts over the walking thread and the
-      // helpers (host_extract -> detect_part) must give the same segments in the same order
-      // (the second half of the passes with the parts' pixel lists next to the labels — what ccl_flatten_kernel leaves: a part is then
-      // staged and seeded from its own pixels on the thread's persistent map)
+      // every other pass with the components labelled and the parts' pixel lists next to the labels (what ccl_flatten_kernel leaves):
+      // the detection split into 16, 3 or 1 parts over the walking thread and the helpers (host_extract -> detect_part, a part staged
+      // and seeded from its own pixels on the thread's persistent map) must give the same segments in the same order
       std::vector<uint8_t> lab, sorted;
       std::vector<unsigned short> bins;
       if ((r + i) % 2 == 1) {
         J.parts = r % 3 == 0 ? plv::linehost::Fit::kParts : (r % 3 == 1 ? 3 : 1);
         lab = component_labels(maps[i].data(), w, h, J.parts);
         J.hlab = lab.data();
-        if (r >= 3) {
-          plv::linehost::lists_from_labels(lab.data(), (int)npix, J.parts, sorted, bins);
-          J.hsorted = sorted.data(), J.hbins = bins.data();
-        }
+        plv::linehost::lists_from_labels(lab.data(), (int)npix, J.parts, sorted, bins);
+        J.hsorted = sorted.data(), J.hbins = bins.data();
       }
       // (the last two passes with helper threads that fall asleep at random — when they pick a job up, when they start a part: jobs
       // are closed without them, parts run a second time, late helpers find closed jobs; same segments, same assignment)
