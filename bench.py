@@ -27,6 +27,11 @@ Two timed segments of K steps each over consecutive frames of the stream: (1) th
 library with std::chrono::steady_clock.  `config.stress`: the update chain alone at SURVEY §8(d)'s sizing (F = 70 features x 15
 observations, then L = 80 lines x 15) on the HIP library and on the oracle.
 
+A plain run renders the frames it consumes, runs the prologue and the warm-up, times segment (1), writes --dump-outputs and prints
+the line: what the headline figure needs.  `--full` adds everything else — segment (2), the segment timed through the Python driver
+(`ms_per_step_python`), `config.variants`, `roofline`, `config.stress` and `cpu_baseline` — over the frames after segment (1); in a
+plain run those fields are null.  Both runs drive the same stream, so segment (1) times the same frames either way.
+
 Workloads: C (default) = BASELINE configs[2], the configuration the metric is quoted on (752x480, 250 tracked points + lines,
 15-clone window); B = configs[1] (no lines); D = configs[3] (1280x720, 500 points + lines, 20-clone window).
 
@@ -70,15 +75,17 @@ ROUND = "r06"
 
 
 # --------------------------------------------------------------------------------------------------------------- the stream
-def build_stream(wl, n_frames, workers, cache=None):
+def build_stream(wl, n_frames, workers, cache=None, n_render=None):
     """Sensor streams + rendered frames of the drive, in memory.  Rendering forks worker processes: called before anything touches
     the GPU — or not at all when `cache` names a stream an earlier run saved (a profiled run must not fork: the profiler's library
-    has initialised the GPU before Python starts)."""
+    has initialised the GPU before Python starts).  The drive is n_frames camera frames long; only its first n_render (default: all)
+    are rendered and played, the IMU and wheel streams cover the whole drive (their noise is drawn for its whole length)."""
     import synth_dataset as sd
     sd.set_camera(wl["w"], wl["h"])
     sd.set_mount(*wl["mount"])
     SCENE = wl["scene"]
     sim = sd.simulate(seconds=n_frames / wl["hz"] + 0.2, cam_hz=wl["hz"], style=SCENE)
+    n_frames = min(n_frames, n_render or n_frames)
     tc = sim["cam_times"][:n_frames]
     imgs = None
     if cache and os.path.exists(cache):
@@ -482,15 +489,19 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="C")
+    ap.add_argument("--full", action="store_true",
+                    help="after the main timed segment, also the host-image segment, the segment timed through the Python driver, the "
+                         "variants, the roofline pass, the stress leg and the CPU baseline (a plain run measures the headline figure only)")
     ap.add_argument("--cpu-frames", type=int, default=200)
     ap.add_argument("--cpu-budget-s", type=float, default=40.0, help="upper bound of the CPU baseline's wall time per pass")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-stress", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the timed segments with host images")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-stress", action="store_true", help="with --full: skip the stress leg")
+    ap.add_argument("--no-pcie", action="store_true", help="with --full: skip the timed segments with host images")
     ap.add_argument("--images", choices=("resident", "host", "pinned"), default="resident",
                     help="measurement aid: where the FIRST timed segment's images are when a step starts (resident = in HBM, the contract's "
                          "`value`; host = any host buffer; pinned = the library's page-locked block, plv_image_buffer)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the short segments with non-default library settings (config.variants)")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the short segments with non-default library settings "
+                                                               "(config.variants)")
     ap.add_argument("--render-workers", type=int, default=0, help="0 = min(32, cores)")
     ap.add_argument("--stream-cache", default=None, help=".npz of the rendered frames: written when missing, loaded (no rendering, no fork) when present")
     ap.add_argument("--alternate-modes", default=None, help="measurement aid: e.g. 0,1 — the timed segment cycles through these "
@@ -524,9 +535,12 @@ def main():
         npy = max(10, min(40, args.steps))      # (the segment timed through the Python driver: config.ms_per_step_python)
         n_gpu_frames = PROLOGUE + args.warmup + args.steps + seg2 + npy + nprof + 6 * nvar + 8 * LEAD_IN   # (three alternating variants of 2 * nvar frames)
         n_cpu_frames = 0 if (args.no_cpu or rank != 0) else PROLOGUE + args.cpu_frames
+        # (the drive is as long as a --full run needs either way, so that segment (1) sees the same IMU noise; a plain run renders and
+        # plays the frames up to the end of segment (1) only)
+        n_played = None if args.full else PROLOGUE + args.warmup + LEAD_IN + args.steps
         workers = args.render_workers or max(1, min(32, (os.cpu_count() or 1) // max(1, world)))
         t0 = time.perf_counter()
-        stream = build_stream(wl, max(n_gpu_frames, n_cpu_frames), workers, args.stream_cache)
+        stream = build_stream(wl, max(n_gpu_frames, n_cpu_frames), workers, args.stream_cache, n_render=n_played)
         t_render = time.perf_counter() - t0
 
     dist = None
@@ -742,12 +756,8 @@ def main():
     if os.environ.get("PLV_BENCH_FINGERPRINT"):     # (determinism checks: the filter's state after the timed segment, to the last bit)
         print("[fingerprint] p = %r  q = %r  trace(P) = %r  routes = %r" % (tuple(float(x) for x in sm.state.imu.p), tuple(float(x) for x in sm.state.imu.q),
                                                                           float(np.trace(ctx.cov_download(sm.state.n))), pkg.route_counts()), file=sys.stderr)
-    if os.environ.get("PLV_BENCH_STOP_AFTER_MAIN"):   # (measurement aid: the library's phase table then covers the timed segment only)
-        print("[main segment] ms per step %.4f  p50 %.4f" % (seg["elapsed"] / args.steps * 1e3, float(np.median(seg["per"]))), file=sys.stderr)
-        sm.close()
-        sys.exit(0)
-    seg_pcie = seg_pin = seg_res_alt = None
-    if not args.no_pcie:
+    seg_pcie = seg_pin = seg_res_alt = seg_py = None
+    if args.full and not args.no_pcie:
         # (2) host images, measured ALTERNATING with the resident hand-over over the next 3 * steps frames (frame f: resident, any host
         # buffer, the library's pinned block, ...): consecutive segments are other frames of the drive, whose cost differs by more than
         # the hand-over's (round 6: 20-step segments showed the pinned block 40 us SLOWER than any buffer, frame by frame it is 13 us
@@ -759,12 +769,13 @@ def main():
             v = [float(x) for x in seg_alt["per"][j::3]]
             return dict(seg_alt, per=v, elapsed=reduce_max(float(np.mean(v)) * 1e-3 * args.steps, dist))
         seg_res_alt, seg_pcie, seg_pin = third(0), third(1), third(2)
-    seg_py = timed_segment(npy, through_python=True)                  # (3) as (1), the Python driver's marshalling inside the step
+    if args.full:
+        seg_py = timed_segment(npy, through_python=True)              # (3) as (1), the Python driver's marshalling inside the step
     elapsed, per, per_frame, cnt, stats, split = (seg[k] for k in ("elapsed", "per", "per_frame", "cnt", "stats", "split"))
     n_state = sm.state.n
     spin_us, fit_threads = pkg.line_worker_config()
     variants = None
-    if not args.no_variants:
+    if args.full and not args.no_variants:
         # non-default library settings over the next frames of the stream (short segments, resident images): (a) the reference's own
         # update route (Householder compression + EKF step); (b) the library's threads blocking at once instead of polling
         # Each variant is measured ALTERNATING with the default, frame by frame, over the next 2 * nvar frames of the stream: later
@@ -792,7 +803,7 @@ def main():
     # ---- roofline leg: HIP events around every kernel launch of the camera step, on the stream each kernel is launched on (a separate
     # pass over the next frames of the stream, same schedule as the timed passes, so that the event records do not perturb them)
     roof = None
-    if rank == 0:
+    if args.full and rank == 0:
         import work_model as wm
         ctx.prof_reset()
         b2 = dict(sm.stats)
@@ -865,11 +876,11 @@ def main():
     sm.close()
 
     stress = None
-    if rank == 0 and not args.no_stress:
+    if args.full and rank == 0 and not args.no_stress:
         stress = stress_update(pkg, device, max(20, min(100, args.steps)), not args.no_cpu)
 
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if args.full and rank == 0 and not args.no_cpu:
         if cpus_before is not None:
             os.sched_setaffinity(0, cpus_before)   # (the CPU baseline gets every core the process is allowed, not the GPU path's L3 complex)
         cpu = cpu_baseline(wl, stream, args.cpu_frames, args.cpu_budget_s, [1, 4, max(1, min(16, os.cpu_count() or 1))])
@@ -927,10 +938,11 @@ def main():
             "methodology": "round 5 on: timed region = plv_camera_frame + plv_ctx_synchronize on pre-marshalled arguments (ms_per_step_python = with the Python "
                            "driver's marshalling inside, what rounds 1-4 reported); process + library threads pinned to one L3 complex next to the GPU (--pin); "
                            "60 untimed prologue frames; round 6: value_pcie_inclusive (any host buffer) and value_pinned_host_image (plv_image_buffer) beside the "
-                           "resident-image `value`",
+                           "resident-image `value`; a plain run times the first segment only, --full adds the other segments, the roofline "
+                           "pass, the stress leg and the CPU baseline (null otherwise)",
             "tracked_points_per_frame": mean(per_frame["tracked"]), "lines_kept_per_frame": mean(per_frame["kept"]) if wl["lines"] else 0,
             "lines_accepted_per_frame": round(stats["lines_accepted"] / args.steps, 2), "msckf_features_per_frame": round(stats["cam_features"] / args.steps, 2),
-            "ms_per_step_python": seg_py["elapsed"] / npy * 1e3,
+            "ms_per_step_python": None if seg_py is None else seg_py["elapsed"] / npy * 1e3,
             "ms_per_step_pcie_inclusive": None if seg_pcie is None else seg_pcie["elapsed"] / args.steps * 1e3,
             "value_pcie_inclusive": None if seg_pcie is None else args.steps * world / seg_pcie["elapsed"],
             # the image in the library's page-locked block when the step starts (plv_image_buffer: the adapters' route): the transfer is inside
@@ -959,7 +971,7 @@ def main():
                 "cpu_affinity": pinned,
                 "timed_region": "plv_camera_frame + plv_ctx_synchronize on arguments marshalled beforehand (SystemManager.camera_prepare): two ctypes calls; "
                                 "ms_per_step_python = the same step with the Python driver's marshalling inside it, over the next frames",
-                "ms_per_step_python": round(seg_py["elapsed"] / npy * 1e3, 4),
+                "ms_per_step_python": None if seg_py is None else round(seg_py["elapsed"] / npy * 1e3, 4),
                 "ms_per_step_pcie_inclusive": None if seg_pcie is None else round(seg_pcie["elapsed"] / args.steps * 1e3, 4),
                 "ms_per_step_pinned_host_image": None if seg_pin is None else round(seg_pin["elapsed"] / args.steps * 1e3, 4),
                 "host_threads": {"caller": 1, "library_line_worker": 1 if wl["lines"] else 0,

@@ -5,11 +5,11 @@ SystemManager.feed_measurement_camera, next to the library's own clock (plv_coun
 argument dictionaries), ~10 inside Context.camera_frame, ~11 per Context.synchronize call — the 44 us between `ms_per_step` and
 `config.ms_per_step_inside_the_library`.
 
-    python tools/debug/python_overhead.py          (needs a GPU; runs bench.py --steps 200 without its CPU / stress / variant legs)
+    python tools/debug/python_overhead.py          (needs a GPU; runs bench.py --full --steps 200 without its CPU / stress / variant legs)
 """
 import sys, os, time
 sys.path.insert(0, os.getcwd())
-sys.argv = ["bench.py", "--steps", "200", "--warmup", "20", "--no-variants", "--no-stress", "--no-cpu", "--no-pcie"]
+sys.argv = ["bench.py", "--full", "--steps", "200", "--warmup", "20", "--no-variants", "--no-stress", "--no-cpu", "--no-pcie"]
 import importlib, types
 import numpy as np
 import __graft_entry__ as ge

@@ -10,7 +10,7 @@ REPO=$(pwd)
 CACHE=/tmp/plv_stream_$WL.npz
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout 900 python3 bench.py --workload $WL --stream-cache $CACHE > "$OUT/bench_line.json" 2> "$OUT/bench_stderr.log"
+timeout 900 python3 bench.py --full --workload $WL --stream-cache $CACHE > "$OUT/bench_line.json" 2> "$OUT/bench_stderr.log"
 A="--workload $WL --steps 100 --warmup 10 --no-cpu --no-stress --no-pcie --no-variants --stream-cache $CACHE"
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$REPO/$OUT/stats" -o run -- python3 "$REPO/bench.py" $A > "$REPO/$OUT/stats.log" 2>&1
