@@ -1,0 +1,291 @@
+// camera_tracks.hpp — host bookkeeping the point update (tracker_api.hip) and the line update (line_api.hip) share: the
+// bounding-pose test, and the mechanics that move a feature track between its database, the update's pool and the hand-back to
+// the database (db_unused).  A track keeps its observations in t (one time each) and uv / uvn (W floats each); the decisions —
+// window margins, which tracks stay in the pool, what goes back — are the callers'.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+#include "../../include/plviwo.h"
+
+namespace plv {
+
+// State::bounding_times + bounding_poses_n (order 3): the first of the four clones that interpolate time t, -1 when there is none.
+// REF: PL-VIWO/src/state/State.cpp:1023-1136 (same test as the kernels' bounding_start)
+inline int bounding_start_host(const plv_state_view &st, double t) {
+  const int N = st.n_clones;
+  if (N < 4) return -1;
+  const double *ct = st.clone_time;
+  if (t < ct[0] - st.dt_exp || t > ct[N - 1] + st.dt_exp) return -1;
+  if (t > ct[N - 1]) return -1;
+  int n_b = -1;
+  for (int i = 0; i < N - 1; ++i)
+    if (ct[i] - st.dt_exp <= t && t <= ct[i + 1] + st.dt_exp) {
+      n_b = i;
+      break;
+    }
+  if (n_b < 0) return -1;
+  int start = n_b - 1;
+  if (n_b - 1 < 0)
+    start = 0;
+  else if (n_b + 2 >= N)
+    start = N - 4;
+  if (start < 0 || start + 4 > N) return -1;
+  return start;
+}
+// is there an interpolation window for time t?
+inline bool has_bounding_poses(const plv_state_view &st, double t) { return bounding_start_host(st, t) >= 0; }
+
+// bounding_start_host answered from a small memo: the observations of a window carry the time stamps of the last few frames (~16
+// distinct values), asked for thousands of times per update
+struct BoundingMemo {
+  const plv_state_view &st;
+  double t[40];
+  int s0[40];
+  int n = 0;
+  explicit BoundingMemo(const plv_state_view &s) : st(s) {}
+  int operator()(double tq) {
+    for (int i = n - 1; i >= 0; --i)
+      if (t[i] == tq) return s0[i];
+    const int r = bounding_start_host(st, tq);
+    if (n < 40) t[n] = tq, s0[n++] = r;
+    return r;
+  }
+};
+
+struct Track {  // ov_core::Feature, one camera  (REF: open_vins/ov_core/src/feat/Feature.h:43-77)
+  static constexpr int W = 2;  // floats of uv / uvn per observation: an image point
+  std::vector<double> t;
+  std::vector<float> uv, uvn;
+  // (transient, Tracker::Spec) index of the track's point in the flow's batch of feed number li_seq
+  int li = -1;
+  unsigned long long li_seq = 0;
+};
+
+struct LineTrack {  // LineFeature, one camera   REF: linefeat/LineFeature.h:22-107
+  static constexpr int W = 4;  // floats of uv / uvn per observation: the segment's two end points
+  std::vector<double> t;
+  std::vector<float> uv, uvn;
+  std::vector<int> points;     // ids of the point features assigned at every observation (appended, REF :50-52)
+  int D = 0;
+};
+
+// what a track that starts from another one's observations takes along besides them: nothing for a point; a line's direction class
+// and point list (copy_to_db copies the feature's point list)
+inline void copy_track_meta(Track &, const Track &) {}
+inline void copy_track_meta(LineTrack &dst, const LineTrack &src) {
+  if (dst.t.empty() && dst.points.empty()) {
+    dst.D = src.D;
+    dst.points = src.points;
+  }
+}
+
+template <class TrackT> struct PoolCand {
+  uint64_t id;
+  TrackT tr;
+};
+template <class TrackT> using TrackMap = std::unordered_map<uint64_t, TrackT>;
+
+// observation i of src appended to dst
+template <class TrackT> void append_obs(TrackT &dst, const TrackT &src, size_t i) {
+  constexpr size_t W = TrackT::W;
+  dst.t.push_back(src.t[i]);
+  dst.uv.insert(dst.uv.end(), src.uv.begin() + W * i, src.uv.begin() + W * (i + 1));
+  dst.uvn.insert(dst.uvn.end(), src.uvn.begin() + W * i, src.uvn.begin() + W * (i + 1));
+}
+
+// observation i of feature id's track src goes back to the database later (db_unused)
+template <class TrackT> void give_back(TrackMap<TrackT> &unused, uint64_t id, const TrackT &src, size_t i) {
+  TrackT &u = unused[id];
+  copy_track_meta(u, src);
+  append_obs(u, src, i);
+}
+
+// a whole candidate goes back: nothing of it went back earlier — the track is handed over as it is; else behind what did
+template <class TrackT> void give_back_all(TrackMap<TrackT> &unused, PoolCand<TrackT> &c) {
+  if (unused.find(c.id) == unused.end()) {
+    unused.emplace(c.id, std::move(c.tr));
+    c.tr = TrackT{};
+    return;
+  }
+  for (size_t i = 0; i < c.tr.t.size(); ++i) give_back(unused, c.id, c.tr, i);
+}
+
+// the observations i with keep(i) stay, in order (keep may read observation i of tr: it is still in place); returns how many
+template <class TrackT, class Keep> size_t trim_track(TrackT &tr, Keep keep) {
+  constexpr size_t W = TrackT::W;
+  size_t n = 0;
+  for (size_t i = 0; i < tr.t.size(); ++i) {
+    if (!keep(i)) continue;
+    if (n != i) {
+      tr.t[n] = tr.t[i];
+      std::copy(tr.uv.begin() + W * i, tr.uv.begin() + W * (i + 1), tr.uv.begin() + W * n);
+      std::copy(tr.uvn.begin() + W * i, tr.uvn.begin() + W * (i + 1), tr.uvn.begin() + W * n);
+    }
+    ++n;
+  }
+  tr.t.resize(n);
+  tr.uv.resize(W * n);
+  tr.uvn.resize(W * n);
+  return n;
+}
+
+// cleanup_measurements on one track (REF FeatureDatabase.cpp:286-323): observations older than t go; returns how many stay
+template <class TrackT> size_t drop_before(TrackT &tr, double t) {
+  return trim_track(tr, [&tr, t](size_t i) { return !(tr.t[i] < t); });
+}
+
+// remove_unusable_measurements on one track (REF CamHelper.cpp:740-775): with tm = time + dt, observations with tm > t_new go back
+// (unused), those with tm < t_old are dropped; returns how many stay
+template <class TrackT> size_t trim_to_window(TrackMap<TrackT> &unused, uint64_t id, TrackT &tr, double dt, double t_new, double t_old) {
+  return trim_track(tr, [&unused, id, &tr, dt, t_new, t_old](size_t i) {
+    const double tm = tr.t[i] + dt;
+    if (tm > t_new) {
+      give_back(unused, id, tr, i);
+      return false;
+    }
+    return !(tm < t_old);
+  });
+}
+
+// features_containing_older(t_old) + features_not_containing_newer(t_new) (REF CamHelper.cpp:631-637, LineHelper.cpp:33-38): every
+// track with an observation older than t_old or none newer than t_new leaves the database for the pool, in ascending id order.  The
+// caller holds the database's lock.
+template <class TrackT> void take_pool(TrackMap<TrackT> &db, double t_old, double t_new, std::vector<PoolCand<TrackT>> &pool) {
+  // (the tracks to take are remembered by position: extracting by iterator needs no second look-up — 180 hash look-ups were 8 of the
+  //  line pool's 15 us on the worker's path in front of the line launch)
+  static thread_local std::vector<std::pair<uint64_t, typename TrackMap<TrackT>::iterator>> take;
+  take.clear();
+  for (auto it = db.begin(); it != db.end(); ++it) {
+    bool older = false, newer = false;
+    for (double t : it->second.t) {
+      older = older || t < t_old;
+      newer = newer || t > t_new;
+    }
+    if (older || !newer) take.emplace_back(it->first, it);
+  }
+  std::sort(take.begin(), take.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+  pool.reserve(pool.size() + take.size());
+  for (auto &tk : take) pool.push_back(PoolCand<TrackT>{tk.first, std::move(db.extract(tk.second).mapped())});
+}
+
+// REF CamHelper.cpp:640 sort(feats_pool, feat_sort): long tracks first, ties in the order they stand.  The order is found on
+// (length, position) pairs and every candidate moved once — a stable sort of the candidates themselves moves each ~8 times
+template <class TrackT> void sort_long_first(std::vector<PoolCand<TrackT>> &pool) {
+  static thread_local std::vector<std::pair<int, int>> ord;
+  ord.clear();
+  for (size_t i = 0; i < pool.size(); ++i) ord.emplace_back(-(int)pool[i].tr.t.size(), (int)i);
+  std::sort(ord.begin(), ord.end());
+  std::vector<PoolCand<TrackT>> sorted;
+  sorted.reserve(pool.size());
+  for (const auto &o : ord) sorted.push_back(std::move(pool[(size_t)o.second]));
+  pool.swap(sorted);
+}
+
+// the pool in the layout of the device batch (plv_tracks / plv_line_tracks): ptr (CSR over the candidates), times, uv, uvn
+template <class TrackT>
+void flatten_pool(const std::vector<PoolCand<TrackT>> &pool, std::vector<int> &ptr, std::vector<double> &t, std::vector<float> &uv, std::vector<float> &uvn) {
+  constexpr size_t W = TrackT::W;
+  ptr.assign(pool.size() + 1, 0);
+  for (size_t f = 0; f < pool.size(); ++f) ptr[f + 1] = ptr[f] + (int)pool[f].tr.t.size();
+  const size_t nobs = (size_t)ptr.back();
+  t.resize(nobs), uv.resize(W * nobs), uvn.resize(W * nobs);
+  for (size_t f = 0; f < pool.size(); ++f) {
+    const TrackT &tr = pool[f].tr;
+    std::copy(tr.t.begin(), tr.t.end(), t.begin() + ptr[f]);
+    std::copy(tr.uv.begin(), tr.uv.end(), uv.begin() + W * ptr[f]);
+    std::copy(tr.uvn.begin(), tr.uvn.end(), uvn.begin() + W * ptr[f]);
+  }
+}
+
+// use_imu_res: the pose of every pool observation from the CPI table (plv_update_options::cpi), in the order of the flattened pool
+// (flatten_pool): R 9 and p 3 per observation, with the table's covariances (noise) Q 36 and the clone index C as well
+struct CpiPoses {
+  bool on = false, noise = false;
+  std::vector<double> R, p, Q;
+  std::vector<int> C;
+};
+
+// REF CamHelper.cpp get_imu_poses (:356-365): the poses for every observation of the pool (time + dt); an observation the table
+// cannot serve leaves its track for `unused`.  A failing call of the table returns its status with the pool as it was.
+template <class TrackT>
+int cpi_attach(plv_ctx *ctx, const plv_state_view *st, const plv_cpi_table *cpi, bool noise, double dt, std::vector<PoolCand<TrackT>> &pool,
+               TrackMap<TrackT> &unused, CpiPoses &out) {
+  std::vector<double> tq;
+  for (const PoolCand<TrackT> &c : pool)
+    for (double t : c.tr.t) tq.push_back(t + dt);
+  std::vector<double> Rq(9 * tq.size()), pq(3 * tq.size());
+  std::vector<uint8_t> okq(tq.size());
+  int rc = plv_cpi_poses(ctx, st, cpi, (int)tq.size(), tq.data(), Rq.data(), pq.data(), okq.data());
+  std::vector<double> Qq(noise ? 36 * tq.size() : 0);
+  std::vector<int> Cq(noise ? tq.size() : 0);
+  if (rc == PLV_OK && noise) {
+    std::vector<uint8_t> okn(tq.size());
+    rc = plv_cpi_noise(st, cpi, (int)tq.size(), tq.data(), Qq.data(), Cq.data(), okn.data());
+    for (size_t i = 0; i < tq.size(); ++i) okq[i] = okq[i] && okn[i];
+  }
+  if (rc != PLV_OK) return rc;
+  out = CpiPoses();
+  out.on = true, out.noise = noise;
+  size_t o = 0;
+  for (PoolCand<TrackT> &c : pool) {
+    TrackT kept;
+    copy_track_meta(kept, c.tr);
+    for (size_t i = 0; i < c.tr.t.size(); ++i, ++o) {
+      if (!okq[o]) {
+        give_back(unused, c.id, c.tr, i);
+        continue;
+      }
+      append_obs(kept, c.tr, i);
+      out.R.insert(out.R.end(), &Rq[9 * o], &Rq[9 * o] + 9);
+      out.p.insert(out.p.end(), &pq[3 * o], &pq[3 * o] + 3);
+      if (noise) {
+        out.Q.insert(out.Q.end(), &Qq[36 * o], &Qq[36 * o] + 36);
+        out.C.push_back(Cq[o]);
+      }
+    }
+    c.tr = std::move(kept);
+  }
+  return PLV_OK;
+}
+
+// the observations the two-step route builds its update from (the selected tracks' plv_tracks / plv_line_tracks): times, uv and,
+// with CPI poses, theirs
+struct ObsGather {
+  std::vector<double> t, R, p, Q;
+  std::vector<int> C;
+  std::vector<float> uv;
+};
+// observation i of tr, the flattened pool's observation o (CpiPoses' index)
+template <class TrackT> void gather_obs(ObsGather &g, const TrackT &tr, size_t i, const CpiPoses &cpi, size_t o) {
+  constexpr size_t W = TrackT::W;
+  g.t.push_back(tr.t[i]);
+  g.uv.insert(g.uv.end(), tr.uv.begin() + W * i, tr.uv.begin() + W * (i + 1));
+  if (!cpi.on) return;
+  g.R.insert(g.R.end(), &cpi.R[9 * o], &cpi.R[9 * o] + 9);
+  g.p.insert(g.p.end(), &cpi.p[3 * o], &cpi.p[3 * o] + 3);
+  if (cpi.noise) {
+    g.Q.insert(g.Q.end(), &cpi.Q[36 * o], &cpi.Q[36 * o] + 36);
+    g.C.push_back(cpi.C[o]);
+  }
+}
+
+// append_new_measurements (REF FeatureDatabase.cpp): tr's observations appended to the database's track of id — tr itself when the
+// database has none.  The caller holds the database's lock.
+template <class TrackT> typename TrackMap<TrackT>::iterator put_track(TrackMap<TrackT> &db, uint64_t id, TrackT &tr) {
+  auto ins = db.try_emplace(id);
+  TrackT &d = ins.first->second;
+  if (ins.second) {
+    d = std::move(tr);
+  } else {
+    d.t.insert(d.t.end(), tr.t.begin(), tr.t.end());
+    d.uv.insert(d.uv.end(), tr.uv.begin(), tr.uv.end());
+    d.uvn.insert(d.uvn.end(), tr.uvn.begin(), tr.uvn.end());
+  }
+  return ins.first;
+}
+
+}  // namespace plv

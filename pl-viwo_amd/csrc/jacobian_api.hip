@@ -9,6 +9,7 @@
 #include "nullspace_core.hpp"
 #include "update_kernels.hpp"
 #include "update_state.hpp"
+#include "camera_tracks.hpp"
 
 using namespace plv;
 
@@ -19,46 +20,6 @@ using namespace plv;
   } while (0)
 
 namespace {
-
-// State::bounding_times + bounding_poses_n (order 3), host copy used for the column bookkeeping.
-// REF: PL-VIWO/src/state/State.cpp:1023-1136
-int bounding_start_host(const plv_state_view &st, double t) {
-  const int N = st.n_clones;
-  if (N < 4) return -1;
-  const double *ct = st.clone_time;
-  if (t < ct[0] - st.dt_exp || t > ct[N - 1] + st.dt_exp) return -1;
-  if (t > ct[N - 1]) return -1;
-  int n_b = -1;
-  for (int i = 0; i < N - 1; ++i)
-    if (ct[i] - st.dt_exp <= t && t <= ct[i + 1] + st.dt_exp) {
-      n_b = i;
-      break;
-    }
-  if (n_b < 0) return -1;
-  int start = n_b - 1;
-  if (n_b - 1 < 0)
-    start = 0;
-  else if (n_b + 2 >= N)
-    start = N - 4;
-  if (start < 0 || start + 4 > N) return -1;
-  return start;
-}
-// the same answer from a small memo: a batch's observations carry the time stamps of the last few frames (~16 distinct values), asked
-// for hundreds of times per call of the column functions below (8-9 us of the caller's thread in front of the line launch)
-struct BoundingStartMemo {
-  const plv_state_view &st;
-  double t[24];
-  int s0[24];
-  int n = 0;
-  explicit BoundingStartMemo(const plv_state_view &s) : st(s) {}
-  int operator()(double tq) {
-    for (int i = n - 1; i >= 0; --i)
-      if (t[i] == tq) return s0[i];
-    const int r = bounding_start_host(st, tq);
-    if (n < 24) t[n] = tq, s0[n++] = r;
-    return r;
-  }
-};
 
 int check_views(const plv_state_view *st, const plv_tracks *tr) {
   if (!st || !tr || st->n_clones < 1 || !st->clone_time || !st->clone_R || !st->clone_p || !st->clone_R_fej ||
@@ -387,7 +348,7 @@ int plv_jacobian_columns(const plv_state_view *st, const plv_tracks *tr, int *co
   // (a window start that has been seen adds nothing: 700 observations meet ~14 distinct windows, and the search through the
   // column list per pose was 29 us of the caller's thread in front of the point launch at configs[2])
   std::vector<uint8_t> seen_s0((size_t)std::max(st->n_clones, 1), 0);
-  BoundingStartMemo start_of(*st);
+  BoundingMemo start_of(*st);
   for (int f = 0; f < tr->n_feat; ++f)
     for (int o = tr->obs_ptr[f]; o < tr->obs_ptr[f + 1]; ++o) {
       const int s0 = start_of(tr->obs_time[o] + st->cam_dt);
@@ -991,7 +952,7 @@ int plv_line_jacobian_columns(const plv_state_view *st, const plv_line_tracks *l
   };
   // REF: LineHelper.cpp:757-788 — `order` of get_interpolated_jacobian: four poses, then the time offset
   std::vector<uint8_t> seen_s0((size_t)std::max(st->n_clones, 1), 0);  // (see plv_jacobian_columns)
-  BoundingStartMemo start_of(*st);
+  BoundingMemo start_of(*st);
   for (int l = 0; l < lt->n_lines; ++l)
     for (int o = lt->obs_ptr[l]; o < lt->obs_ptr[l + 1]; ++o) {
       const int s0 = start_of(lt->obs_time[o] + st->cam_dt);

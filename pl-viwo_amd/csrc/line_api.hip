@@ -29,6 +29,7 @@
 #include "line_kernels.hpp"
 #include "update_state.hpp"
 #include "plv_internal.hpp"
+#include "camera_tracks.hpp"
 
 using namespace plv;
 using namespace plv::linehost;
@@ -42,17 +43,6 @@ namespace {
     if (_rc != PLV_OK) return _rc; \
   } while (0)
 
-struct LineTrack {  // LineFeature, one camera   REF: linefeat/LineFeature.h:22-107
-  std::vector<double> t;
-  std::vector<float> uv, uvn;  // 4 per observation
-  std::vector<int> points;     // ids of the point features assigned at every observation (appended, REF :50-52)
-  int D = 0;
-};
-
-struct LineCand {
-  uint64_t id;
-  LineTrack tr;
-};
 // The pool of LineHelper::get_line_features (REF: linefeat/LineHelper.cpp:33-44: features_containing_older + features_not_containing_newer,
 // remove_unusable_measurements, sort) taken out of the database.  It reads times only, so plv_camera_try_update forms it while the
 // point update is still running on the device (form_line_pool below); plv_camera_update_lines consumes it.
@@ -70,8 +60,8 @@ struct LinePool {
   bool valid = false;
   double t_prev_frame = 0, state_time = 0, t_oldest = 0, t_oldest2 = 0, dt = 0;
   int n_clones = 0, n_pool = 0, db_size_before = 0;
-  std::vector<LineCand> pool;                       // trimmed, sorted long to short
-  std::unordered_map<uint64_t, LineTrack> unused;   // db_unused so far (observations newer than the window)
+  std::vector<PoolCand<LineTrack>> pool;            // trimmed, sorted long to short
+  TrackMap<LineTrack> unused;                       // db_unused so far (observations newer than the window)
 };
 
 // plv_camera_update_lines in two halves: what the first (pool, staging, launch of triangulation + Jacobians + gate) hands to the
@@ -90,9 +80,7 @@ struct LinesJob {
   std::vector<double> anchor, ot;
   std::vector<float> uv, uvn;
   std::vector<uint8_t> has, flags;
-  std::vector<std::vector<double>> cpiR, cpip, cpiQ;
-  std::vector<std::vector<int>> cpiC;
-  std::vector<double> allR, allp;
+  CpiPoses cpi;
   std::vector<double> lg_two_step;   // TWO_STEP: the triangulation ran as its own call inside the first half
   std::vector<uint8_t> ok_two_step;
   double us_pool = 0;
@@ -466,24 +454,6 @@ int detect(plv_ctx *ctx, LineTracker *T, int which, std::vector<float> &lines, b
 
 
 }  // namespace
-
-// the same test answered from a small memo: the observations of a window carry ~16 distinct time stamps (the camera frames), asked
-// for thousands of times per update
-template <class F> struct BoundingMemo {
-  F f;
-  double t[40];
-  bool v[40];
-  int n = 0;
-  explicit BoundingMemo(F f_) : f(f_) {}
-  bool operator()(double tq) {
-    for (int i = n - 1; i >= 0; --i)
-      if (t[i] == tq) return v[i];
-    const bool r = f(tq);
-    if (n < 40) t[n] = tq, v[n++] = r;
-    return r;
-  }
-};
-template <class F> BoundingMemo<F> bounding_memo(F f) { return BoundingMemo<F>(f); }
 
 namespace plv {
 void plv_line_tracker_destroy(plv_ctx *ctx) {
@@ -900,16 +870,6 @@ int plv_line_db_append_measurements(plv_ctx *ctx, uint64_t id, int n, const doub
   return PLV_OK;
 }
 
-static bool line_has_bounding_poses(const plv_state_view &st, double t) {  // as the kernels' bounding_start
-  const int N = st.n_clones;
-  if (N < 4) return false;
-  const double *ct = st.clone_time;
-  if (t < ct[0] - st.dt_exp || t > ct[N - 1] + st.dt_exp || t > ct[N - 1]) return false;
-  for (int i = 0; i < N - 1; ++i)
-    if (ct[i] - st.dt_exp <= t && t <= ct[i + 1] + st.dt_exp) return true;
-  return false;
-}
-
 }  // extern "C"
 namespace plv {
 // (internal) plv_camera_try_update turns the deferral on around its line update; plv_tracker_feed* runs what was left behind
@@ -918,35 +878,7 @@ void plv_line_run_deferred(plv_ctx *ctx) { (void)ltr(ctx); }
 }  // namespace plv
 extern "C" {
 
-static void line_give_back(std::unordered_map<uint64_t, LineTrack> &unused, const LineCand &c, size_t i) {
-  LineTrack &u = unused[c.id];
-  if (u.t.empty() && u.points.empty()) {
-    u.D = c.tr.D;
-    u.points = c.tr.points;  // copy_to_db copies the feature's point list
-  }
-  u.t.push_back(c.tr.t[i]);
-  u.uv.insert(u.uv.end(), c.tr.uv.begin() + 4 * i, c.tr.uv.begin() + 4 * i + 4);
-  u.uvn.insert(u.uvn.end(), c.tr.uvn.begin() + 4 * i, c.tr.uvn.begin() + 4 * i + 4);
-}
-
 namespace {
-// cleanup_measurements on one track (REF LineHelper.cpp:549-551): observations older than the oldest clone go; true = nothing left
-inline bool line_track_drop_before(LineTrack &tr, double t_oldest) {
-  size_t keep = 0;
-  for (size_t i = 0; i < tr.t.size(); ++i)
-    if (!(tr.t[i] < t_oldest)) {
-      if (keep != i) {
-        tr.t[keep] = tr.t[i];
-        std::copy(tr.uv.begin() + 4 * i, tr.uv.begin() + 4 * i + 4, tr.uv.begin() + 4 * keep);
-        std::copy(tr.uvn.begin() + 4 * i, tr.uvn.begin() + 4 * i + 4, tr.uvn.begin() + 4 * keep);
-      }
-      ++keep;
-    }
-  tr.t.resize(keep);
-  tr.uv.resize(4 * keep);
-  tr.uvn.resize(4 * keep);
-  return keep == 0;
-}
 // host work placed inside the line update's wait: the point database's hand-back, then the caller's own
 struct LineWaitHook {
   plv_ctx *ctx;
@@ -971,25 +903,7 @@ void form_line_pool(LineTracker *T, const PoolArgs &A, LinePool &R) {
   {
     std::lock_guard<std::mutex> lk(T->mtx);
     R.db_size_before = (int)T->db.size();
-    // (the tracks to take are remembered by position: extracting by iterator needs no second look-up — 180 hash look-ups were 8 of
-    //  this stage's 15 us on the worker's path in front of the line launch)
-    static thread_local std::vector<std::pair<uint64_t, decltype(T->db)::iterator>> take;
-    take.clear();
-    const double t_old = t_oldest2 - dt, t_new = opt->t_prev_frame - dt;
-    for (auto it = T->db.begin(); it != T->db.end(); ++it) {  // REF LineHelper.cpp:33-38 (:74-130)
-      bool older = false, newer = false;
-      for (double t : it->second.t) {
-        older = older || t < t_old;
-        newer = newer || t > t_new;
-      }
-      if (older || !newer) take.emplace_back(it->first, it);
-    }
-    std::sort(take.begin(), take.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
-    R.pool.reserve(take.size());
-    for (auto &tk : take) {
-      auto node = T->db.extract(tk.second);  // (the track leaves the database with its node)
-      R.pool.push_back(LineCand{tk.first, std::move(node.mapped())});
-    }
+    take_pool(T->db, t_oldest2 - dt, opt->t_prev_frame - dt, R.pool);  // REF LineHelper.cpp:33-38 (:74-130)
   }
   ph_scan.stop();
   plv::HostPhase ph_trim("line pool: trim + sort");
@@ -997,42 +911,14 @@ void form_line_pool(LineTracker *T, const PoolArgs &A, LinePool &R) {
   R.unused.reserve(R.pool.size());
   size_t kept_cands = 0;  // (candidates that stay are moved down once: erasing from the middle of the vector shifted the rest every time)
   for (size_t ci = 0; ci < R.pool.size(); ++ci) {  // REF :652-682 (hard-coded 0.01 s margins)
-    LineCand *it = &R.pool[ci];
-    LineTrack &tr = it->tr;
-    size_t keep = 0;
-    for (size_t i = 0; i < tr.t.size(); ++i) {
-      const double tm = tr.t[i] + dt;
-      if (tm > opt->state_time + 0.01) {
-        line_give_back(R.unused, *it, i);
-        continue;
-      }
-      if (tm < t_oldest - 0.01) continue;
-      if (keep != i) {
-        tr.t[keep] = tr.t[i];
-        std::copy(tr.uv.begin() + 4 * i, tr.uv.begin() + 4 * i + 4, tr.uv.begin() + 4 * keep);
-        std::copy(tr.uvn.begin() + 4 * i, tr.uvn.begin() + 4 * i + 4, tr.uvn.begin() + 4 * keep);
-      }
-      ++keep;
-    }
-    tr.t.resize(keep);
-    tr.uv.resize(4 * keep);
-    tr.uvn.resize(4 * keep);
-    if (keep >= 2) {
-      if (kept_cands != ci) R.pool[kept_cands] = std::move(*it);
+    PoolCand<LineTrack> &c = R.pool[ci];
+    if (trim_to_window(R.unused, c.id, c.tr, dt, opt->state_time + 0.01, t_oldest - 0.01) >= 2) {
+      if (kept_cands != ci) R.pool[kept_cands] = std::move(c);
       ++kept_cands;
     }
   }
   R.pool.resize(kept_cands);
-  // REF :640 sort by track length, long tracks first, ties in the order they stand (ascending id): the order is found on (length,
-  // position) pairs and every candidate moved once — a stable sort of the candidates themselves moves each ~8 times, ~120 bytes a move
-  static thread_local std::vector<std::pair<int, int>> ord;
-  ord.clear();
-  for (size_t i = 0; i < R.pool.size(); ++i) ord.emplace_back(-(int)R.pool[i].tr.t.size(), (int)i);
-  std::sort(ord.begin(), ord.end());
-  std::vector<LineCand> sorted;
-  sorted.reserve(R.pool.size());
-  for (const auto &o : ord) sorted.push_back(std::move(R.pool[(size_t)o.second]));
-  R.pool.swap(sorted);
+  sort_long_first(R.pool);  // REF :640
 }
 }  // namespace
 
@@ -1058,14 +944,8 @@ void discard_line_pool(LineTracker *T) {
     for (size_t i = 0; i < nb; ++i) order.push_back({tr.t[i], {1, (int)i}});
     std::stable_sort(order.begin(), order.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
     LineTrack m;
-    m.D = d.D, m.points = d.points;
-    for (const auto &e : order) {
-      const LineTrack &src = e.second.first ? tr : d;
-      const size_t i = (size_t)e.second.second;
-      m.t.push_back(src.t[i]);
-      m.uv.insert(m.uv.end(), src.uv.begin() + 4 * i, src.uv.begin() + 4 * i + 4);
-      m.uvn.insert(m.uvn.end(), src.uvn.begin() + 4 * i, src.uvn.begin() + 4 * i + 4);
-    }
+    copy_track_meta(m, d);
+    for (const auto &e : order) append_obs(m, e.second.first ? tr : d, (size_t)e.second.second);
     d = std::move(m);
   };
   for (auto &c : R.pool) put(c.id, c.tr);
@@ -1157,8 +1037,7 @@ static int lines_first_half(plv_ctx *ctx, LineTracker *T, const plv_state_view *
   auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count(); };
   plv::HostPhase ph_pool("update_lines: pool + staging");
   const double dt = st->cam_dt, t_oldest = st->clone_time[0];
-  auto has_bounding = bounding_memo([st](double tq) { return line_has_bounding_poses(*st, tq); });
-  typedef LineCand Cand;
+  BoundingMemo start_of(*st);
   LinePool &LP = J.LP;
   if (T->pool_prep.valid && T->pool_prep.t_prev_frame == opt->t_prev_frame && T->pool_prep.state_time == opt->state_time && T->pool_prep.dt == dt &&
       T->pool_prep.n_clones == st->n_clones && T->pool_prep.t_oldest == t_oldest && T->pool_prep.t_oldest2 == st->clone_time[1]) {
@@ -1168,9 +1047,7 @@ static int lines_first_half(plv_ctx *ctx, LineTracker *T, const plv_state_view *
     discard_line_pool(T);
     form_line_pool(T, PoolArgs::of(st, opt), LP);
   }
-  std::vector<Cand> &pool = LP.pool;
-  std::unordered_map<uint64_t, LineTrack> &unused = LP.unused;
-  auto give_back = [&](const Cand &c, size_t i) { line_give_back(unused, c, i); };
+  std::vector<PoolCand<LineTrack>> &pool = LP.pool;
   plv::HostPhase ph_p1("update_lines: pool a (scan + take) done -> b (trim + sort)");
   if (pool.empty()) {
     J.stage = LinesJob::EMPTY;
@@ -1179,62 +1056,24 @@ static int lines_first_half(plv_ctx *ctx, LineTracker *T, const plv_state_view *
   // ---- triangulate every pool line (REF :45-63; get_imu_poses drops views without bounding clones)
   const int Lp = J.Lp = (int)pool.size();
   // ---- use_imu_res: poses from the CPI table (plv_update_options::cpi); views it cannot serve go back to the database
-  J.cpiR.resize(opt->cpi ? Lp : 0), J.cpip.resize(opt->cpi ? Lp : 0), J.cpiQ.resize(opt->cpi ? Lp : 0), J.cpiC.resize(opt->cpi ? Lp : 0);
-  auto &cpiR = J.cpiR, &cpip = J.cpip, &cpiQ = J.cpiQ;
-  auto &cpiC = J.cpiC;
   const bool imu_cov = opt->cpi && opt->cpi->Q && st->use_imu_cov && !st->use_pol_cov;
   if (opt->cpi) {
-    std::vector<double> tq;
-    for (const Cand &c : pool)
-      for (double t : c.tr.t) tq.push_back(t + dt);
-    std::vector<double> Rq(9 * tq.size()), pq(3 * tq.size());
-    std::vector<uint8_t> okq(tq.size());
-    int rc0 = plv_cpi_poses(ctx, st, opt->cpi, (int)tq.size(), tq.data(), Rq.data(), pq.data(), okq.data());
-    std::vector<double> Qq(imu_cov ? 36 * tq.size() : 0);
-    std::vector<int> Cq(imu_cov ? tq.size() : 0);
-    if (rc0 == PLV_OK && imu_cov) {
-      std::vector<uint8_t> okn(tq.size());
-      rc0 = plv_cpi_noise(st, opt->cpi, (int)tq.size(), tq.data(), Qq.data(), Cq.data(), okn.data());
-      for (size_t i = 0; i < tq.size(); ++i) okq[i] = okq[i] && okn[i];
-    }
+    const int rc0 = cpi_attach(ctx, st, opt->cpi, imu_cov, dt, pool, LP.unused, J.cpi);
     if (rc0 != PLV_OK) {
       J.stage = LinesJob::FAILED, J.rc = rc0;
       return PLV_OK;
     }
-    size_t o = 0;
-    for (int l = 0; l < Lp; ++l) {
-      Cand &c = pool[l];
-      LineTrack kept;
-      kept.D = c.tr.D;
-      kept.points = c.tr.points;
-      for (size_t i = 0; i < c.tr.t.size(); ++i, ++o) {
-        if (!okq[o]) {
-          give_back(c, i);
-          continue;
-        }
-        kept.t.push_back(c.tr.t[i]);
-        kept.uv.insert(kept.uv.end(), c.tr.uv.begin() + 4 * i, c.tr.uv.begin() + 4 * i + 4);
-        kept.uvn.insert(kept.uvn.end(), c.tr.uvn.begin() + 4 * i, c.tr.uvn.begin() + 4 * i + 4);
-        cpiR[l].insert(cpiR[l].end(), &Rq[9 * o], &Rq[9 * o] + 9);
-        cpip[l].insert(cpip[l].end(), &pq[3 * o], &pq[3 * o] + 3);
-        if (imu_cov) {
-          cpiQ[l].insert(cpiQ[l].end(), &Qq[36 * o], &Qq[36 * o] + 36);
-          cpiC[l].push_back(Cq[o]);
-        }
-      }
-      c.tr = std::move(kept);
-    }
   }
   ph_p1.stop();
   plv::HostPhase ph_p2("update_lines: pool c (anchors + arrays + valid)");
-  J.ptr.assign(Lp + 1, 0), J.D.resize(Lp), J.anchor.assign(3 * (size_t)Lp, 0.0), J.has.assign(Lp, 0);
+  J.D.resize(Lp), J.anchor.assign(3 * (size_t)Lp, 0.0), J.has.assign(Lp, 0);
   std::vector<int> &ptr = J.ptr, &D = J.D;
+  flatten_pool(pool, ptr, J.ot, J.uv, J.uvn);
   plv_ctx::ChainState &ch = ctx->chain;
   {
     std::vector<int> &pp = J.pt_ptr, &pi = J.pt_ids;
     pp.assign(1, 0), pi.clear();
     for (int l = 0; l < Lp; ++l) {
-      ptr[l + 1] = ptr[l] + (int)pool[l].tr.t.size();
       D[l] = pool[l].tr.D;
       pi.insert(pi.end(), pool[l].tr.points.begin(), pool[l].tr.points.end());
       pp.push_back((int)pi.size());
@@ -1248,13 +1087,6 @@ static int lines_first_half(plv_ctx *ctx, LineTracker *T, const plv_state_view *
     J.stage = LinesJob::EMPTY;
     return PLV_OK;
   }
-  J.ot.resize(nobs), J.uv.resize(4 * (size_t)nobs), J.uvn.resize(4 * (size_t)nobs);
-  for (int l = 0; l < Lp; ++l) {
-    const LineTrack &tr = pool[l].tr;
-    std::copy(tr.t.begin(), tr.t.end(), J.ot.begin() + ptr[l]);
-    std::copy(tr.uv.begin(), tr.uv.end(), J.uv.begin() + 4 * (size_t)ptr[l]);
-    std::copy(tr.uvn.begin(), tr.uvn.end(), J.uvn.begin() + 4 * (size_t)ptr[l]);
-  }
   plv_line_tracks all{};
   all.n_lines = Lp;
   all.obs_ptr = ptr.data();
@@ -1264,17 +1096,13 @@ static int lines_first_half(plv_ctx *ctx, LineTracker *T, const plv_state_view *
   all.D = D.data();
   all.anchor_pt = J.anchor.data();
   all.has_pt = J.has.data();
-  if (opt->cpi) {
-    for (int l = 0; l < Lp; ++l) {
-      J.allR.insert(J.allR.end(), cpiR[l].begin(), cpiR[l].end());
-      J.allp.insert(J.allp.end(), cpip[l].begin(), cpip[l].end());
-    }
-    all.res_R = J.allR.data();
-    all.res_p = J.allp.data();
+  if (J.cpi.on) {
+    all.res_R = J.cpi.R.data();
+    all.res_p = J.cpi.p.data();
   }
   J.valid_n.assign(Lp, 0);
   for (int l = 0; l < Lp; ++l) {
-    for (double t : pool[l].tr.t) J.valid_n[l] += has_bounding(t + dt);
+    for (double t : pool[l].tr.t) J.valid_n[l] += start_of(t + dt) >= 0;
     J.most_valid = std::max(J.most_valid, J.valid_n[l]);
   }
   J.cols.resize(ctx->cfg.max_state_dim > 0 ? ctx->cfg.max_state_dim : 1024);
@@ -1399,28 +1227,19 @@ int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_up
       plv_line_tracks all{};
       all.n_lines = J.Lp, all.obs_ptr = J.ptr.data(), all.obs_time = J.ot.data(), all.seg_uv = J.uv.data(), all.seg_uvn = J.uvn.data();
       all.D = J.D.data(), all.anchor_pt = J.anchor.data(), all.has_pt = J.has.data();
-      if (opt->cpi) all.res_R = J.allR.data(), all.res_p = J.allp.data();
+      if (J.cpi.on) all.res_R = J.cpi.R.data(), all.res_p = J.cpi.p.data();
       const int rc2 = plv_triangulate_lines(ctx, st_tri, &all, J.lg_two_step.data(), J.ok_two_step.data());
       if (rc2 != PLV_OK) J.stage = LinesJob::FAILED, J.rc = rc2;
     }
   }
   T->ujob.pending = false;
   const double dt = st->cam_dt, t_oldest = st->clone_time[0];
-  auto has_bounding = bounding_memo([st](double tq) { return line_has_bounding_poses(*st, tq); });
-  typedef LineCand Cand;
+  BoundingMemo start_of(*st);
+  typedef PoolCand<LineTrack> Cand;
   LinePool &LP = J.LP;
   std::vector<Cand> &pool = LP.pool;
-  std::unordered_map<uint64_t, LineTrack> &unused = LP.unused;
-  auto give_back = [&](const Cand &c, size_t i) { line_give_back(unused, c, i); };
+  TrackMap<LineTrack> &unused = LP.unused;
   res->n_pool = LP.n_pool;
-  auto give_back_all = [&](Cand &c) {
-    if (unused.find(c.id) == unused.end()) {  // nothing of this line went back earlier: hand the track over as it is
-      unused.emplace(c.id, std::move(c.tr));
-      c.tr = LineTrack{};
-      return;
-    }
-    for (size_t i = 0; i < c.tr.t.size(); ++i) give_back(c, i);
-  };
   std::vector<int> lazy_back;  // pool candidates whose whole track returns to the database: moved there by the deferred hand-back
   // cleanup_measurements over the tracks that stayed in the database, placed inside the update's wait for the device (they do not
   // depend on its result); finish() then cleans only what returns
@@ -1428,7 +1247,7 @@ int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_up
   std::function<void()> scan_db_early = [&]() {
     if (!opt->window_full || db_scanned_early) return;
     std::lock_guard<std::mutex> lk(T->mtx);
-    for (auto it = T->db.begin(); it != T->db.end();) it = line_track_drop_before(it->second, t_oldest) ? T->db.erase(it) : std::next(it);
+    for (auto it = T->db.begin(); it != T->db.end();) it = drop_before(it->second, t_oldest) == 0 ? T->db.erase(it) : std::next(it);
     db_scanned_early = true;
   };
   auto finish = [&](int rc) {
@@ -1441,19 +1260,11 @@ int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_up
     // try_update) cleanup_measurements(oldest clone).  Whole tracks (`whole`: candidates the update did not take and of which nothing
     // went back earlier) enter the database with one insertion; the cleanup touches every track, or — when the database was cleaned
     // inside the update's wait (scan_db_early below) — only the tracks that return now.
-    auto hand_back = [T, window_full, t_oldest, scanned](std::unordered_map<uint64_t, LineTrack> &un, std::vector<Cand> *cands, const std::vector<int> *whole) {
+    auto hand_back = [T, window_full, t_oldest, scanned](TrackMap<LineTrack> &un, std::vector<Cand> *cands, const std::vector<int> *whole) {
       std::lock_guard<std::mutex> lk(T->mtx);
       auto put = [&](uint64_t id, LineTrack &tr) {
-        auto ins = T->db.try_emplace(id);
-        LineTrack &d = ins.first->second;
-        if (ins.second) {
-          d = std::move(tr);
-        } else {
-          d.t.insert(d.t.end(), tr.t.begin(), tr.t.end());
-          d.uv.insert(d.uv.end(), tr.uv.begin(), tr.uv.end());
-          d.uvn.insert(d.uvn.end(), tr.uvn.begin(), tr.uvn.end());
-        }
-        if (window_full && scanned && line_track_drop_before(d, t_oldest)) T->db.erase(ins.first);
+        const auto it = put_track(T->db, id, tr);
+        if (window_full && scanned && drop_before(it->second, t_oldest) == 0) T->db.erase(it);
       };
       if (whole)
         for (int l : *whole) {
@@ -1461,18 +1272,18 @@ int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_up
           if (un.find(c.id) == un.end())
             put(c.id, c.tr);
           else  // (parts of it went back earlier: behind those, as give_back_all does)
-            for (size_t i = 0; i < c.tr.t.size(); ++i) line_give_back(un, c, i);
+            for (size_t i = 0; i < c.tr.t.size(); ++i) give_back(un, c.id, c.tr, i);
         }
       for (auto &kv : un) put(kv.first, kv.second);
       if (window_full && !scanned)
-        for (auto it = T->db.begin(); it != T->db.end();) it = line_track_drop_before(it->second, t_oldest) ? T->db.erase(it) : std::next(it);
+        for (auto it = T->db.begin(); it != T->db.end();) it = drop_before(it->second, t_oldest) == 0 ? T->db.erase(it) : std::next(it);
     };
     // (point_used->cleanup_measurements is not deferred: it takes the point tracker's lock, which a feed in progress holds)
     if (window_full) plv_point_used_cleanup(ctx, t_oldest);
     if (T->defer_finish) {
       // plv_camera_try_update: nothing reads the line database before the next frame's feed; the hand-back (and the release of the
       // pooled tracks) runs in that frame's wait for the flow, or at the next call that reaches the tracker
-      auto held = std::make_shared<std::unordered_map<uint64_t, LineTrack>>(std::move(unused));
+      auto held = std::make_shared<TrackMap<LineTrack>>(std::move(unused));
       auto used_up = std::make_shared<std::vector<Cand>>(std::move(pool));
       auto lazy = std::make_shared<std::vector<int>>(std::move(lazy_back));
       T->deferred = [hand_back, held, used_up, lazy]() { hand_back(*held, used_up.get(), lazy.get()); };
@@ -1492,14 +1303,11 @@ int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_up
   std::fill(dx, dx + ctx->cov_n, 0.0);
   if (J.stage == LinesJob::EMPTY) return finish(PLV_OK);
   if (J.stage == LinesJob::FAILED) {
-    for (Cand &c : pool) give_back_all(c);
+    for (Cand &c : pool) give_back_all(unused, c);
     return finish(J.rc);
   }
   const int Lp = J.Lp, nobs = J.nobs;
   std::vector<int> &valid_n = J.valid_n, &cols = J.cols;
-  auto &cpiR = J.cpiR, &cpip = J.cpip, &cpiQ = J.cpiQ;
-  auto &cpiC = J.cpiC;
-  const bool imu_cov = opt->cpi && opt->cpi->Q && st->use_imu_cov && !st->use_pol_cov;
   std::vector<double> lg(6 * (size_t)Lp);
   std::vector<uint8_t> ok(Lp);
   int k = J.k, n_rows = 0, rc = PLV_OK;
@@ -1519,7 +1327,7 @@ int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_up
     }
     fused_ran = rc == PLV_OK;
     if (rc != PLV_OK) {
-      for (Cand &c : pool) give_back_all(c);
+      for (Cand &c : pool) give_back_all(unused, c);
       return finish(rc);
     }
   } else if (J.stage == LinesJob::FUSED_NOTHING) {
@@ -1556,33 +1364,23 @@ int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_up
   // ---- UpdaterCamera::lines_update
   const int L = (int)sel.size();
   std::vector<int> sptr(L + 1, 0);
-  std::vector<double> st_t, sl(6 * (size_t)L), selR, selp, selQ;
-  std::vector<int> selC;
-  std::vector<float> suv;
+  std::vector<double> sl(6 * (size_t)L);
+  ObsGather g;
   for (int q = 0; q < L; ++q) {
     const Cand &c = pool[sel[q]];
     int seen = 0;
     // (behind a fused launch the loop only hands back views without bounding clones: none when every view counted as usable)
     const bool nothing_to_do = fused_ran && valid_n[sel[q]] == (int)c.tr.t.size();
     for (size_t i = 0; !nothing_to_do && i < c.tr.t.size(); ++i) {
-      if (!has_bounding(c.tr.t[i] + dt)) {
-        give_back(c, i);
+      if (start_of(c.tr.t[i] + dt) < 0) {
+        give_back(unused, c.id, c.tr, i);
         continue;
       }
       if (seen++ < n_skip[sel[q]]) continue;
       if (fused_ran) continue;  // (the batch was built on the device: the two-step route's arrays are not needed)
-      st_t.push_back(c.tr.t[i]);
-      suv.insert(suv.end(), c.tr.uv.begin() + 4 * i, c.tr.uv.begin() + 4 * i + 4);
-      if (opt->cpi) {
-        selR.insert(selR.end(), &cpiR[sel[q]][9 * i], &cpiR[sel[q]][9 * i] + 9);
-        selp.insert(selp.end(), &cpip[sel[q]][3 * i], &cpip[sel[q]][3 * i] + 3);
-        if (imu_cov) {
-          selQ.insert(selQ.end(), &cpiQ[sel[q]][36 * i], &cpiQ[sel[q]][36 * i] + 36);
-          selC.push_back(cpiC[sel[q]][i]);
-        }
-      }
+      gather_obs(g, c.tr, i, J.cpi, J.ptr[sel[q]] + i);
     }
-    sptr[q + 1] = (int)st_t.size();
+    sptr[q + 1] = (int)g.t.size();
     std::copy(lg.begin() + 6 * (size_t)sel[q], lg.begin() + 6 * (size_t)sel[q] + 6, sl.begin() + 6 * (size_t)q);
     if (line_ids) line_ids[q] = c.id;
   }
@@ -1590,15 +1388,15 @@ int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_up
   plv_line_tracks lt{};
   lt.n_lines = L;
   lt.obs_ptr = sptr.data();
-  lt.obs_time = st_t.data();
-  lt.seg_uv = suv.data();
+  lt.obs_time = g.t.data();
+  lt.seg_uv = g.uv.data();
   lt.line_FinG = sl.data();
-  if (opt->cpi) {
-    lt.res_R = selR.data();
-    lt.res_p = selp.data();
-    if (imu_cov) {
-      lt.res_Q = selQ.data();
-      lt.res_clone = selC.data();
+  if (J.cpi.on) {
+    lt.res_R = g.R.data();
+    lt.res_p = g.p.data();
+    if (J.cpi.noise) {
+      lt.res_Q = g.Q.data();
+      lt.res_clone = g.C.data();
     }
   }
   std::vector<uint8_t> acc(L, 0);
@@ -1613,7 +1411,7 @@ int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_up
       if (rc == PLV_E_NOT_PSD) rc = PLV_OK;
     }
     if (rc != PLV_OK) {
-      for (int q = 0; q < L; ++q) give_back_all(pool[sel[q]]);
+      for (int q = 0; q < L; ++q) give_back_all(unused, pool[sel[q]]);
       return finish(rc);
     }
   }
@@ -1645,7 +1443,7 @@ int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_up
         continue;
       }
       for (size_t i = 0; i < c.tr.t.size(); ++i)
-        if (has_bounding(c.tr.t[i] + dt)) give_back(c, i);
+        if (start_of(c.tr.t[i] + dt) >= 0) give_back(unused, c.id, c.tr, i);
     }
   }
   return finish(PLV_OK);

@@ -16,16 +16,11 @@
 #include "update_state.hpp"
 #include "plv_internal.hpp"
 #include "gate_stage.hpp"
+#include "camera_tracks.hpp"
+
+using plv::Track;
 
 namespace {
-
-struct Track {  // ov_core::Feature, one camera  (REF: open_vins/ov_core/src/feat/Feature.h:43-77)
-  std::vector<double> t;
-  std::vector<float> uv, uvn;  // 2 per observation
-  // (transient, Tracker::Spec) index of the track's point in the flow's batch of feed number li_seq
-  int li = -1;
-  unsigned long long li_seq = 0;
-};
 
 struct Tracker {
   std::vector<float> pts_last;     // 2 per point
@@ -101,24 +96,6 @@ Tracker *trk(plv_ctx *ctx) {
 
 }  // namespace
 
-// the same test answered from a small memo: the observations of a window carry ~16 distinct time stamps (the camera frames), asked
-// for thousands of times per update
-template <class F> struct BoundingMemo {
-  F f;
-  double t[40];
-  bool v[40];
-  int n = 0;
-  explicit BoundingMemo(F f_) : f(f_) {}
-  bool operator()(double tq) {
-    for (int i = n - 1; i >= 0; --i)
-      if (t[i] == tq) return v[i];
-    const bool r = f(tq);
-    if (n < 40) t[n] = tq, v[n++] = r;
-    return r;
-  }
-};
-template <class F> BoundingMemo<F> bounding_memo(F f) { return BoundingMemo<F>(f); }
-
 namespace plv {
 void plv_tracker_destroy(plv_ctx *ctx) {
   std::lock_guard<std::mutex> lk(g_mtx);
@@ -178,7 +155,6 @@ int plv_tracker_feed_downsampled(plv_ctx *ctx, double timestamp, const uint8_t *
   return tracker_feed_fed(ctx, T, timestamp, mask ? small_mask.data() : nullptr);
 }
 
-static bool has_bounding_poses(const plv_state_view &st, double t);
 // Stages every track the frame's flow could send into the point update's pool and enqueues the update behind the flow (Tracker::Spec).
 // Called with T->mtx held, between the flow's launch and the wait for it; tp[i]: the database track of flow point i (or null).
 // Anything unusual leaves spec.active false: plv_camera_update_points then submits the update itself, as it always did.
@@ -196,10 +172,9 @@ static void spec_submit(plv_ctx *ctx, Tracker *T, double t_now, int n_flow, cons
   }
   plv::HostPhase ph("speculative point update: candidates staged + chain enqueued");
   const double dt = st->cam_dt, t_oldest = st->clone_time[0], t_oldest2 = st->clone_time[1];
-  auto has_bounding = bounding_memo([st](double tq) { return has_bounding_poses(*st, tq); });
   const double tm_new = t_now + dt;
   const bool new_usable = !(tm_new > opt->state_time + st->dt_exp) && !(tm_new < t_oldest - st->dt_exp);
-  const bool new_bounded = new_usable && has_bounding(tm_new);
+  const bool new_bounded = new_usable && has_bounding_poses(*st, tm_new);
   if (!(t_now > opt->t_prev_frame - dt)) return;  // (a surviving track counts as "seen in the newest frame": CamHelper.cpp:635, the usual case)
   // What the window tests say about an observation depends on its time alone, and the observations of all tracks carry the time
   // stamps of the last few feeds: the tests are evaluated once per stamp, the tracks are then walked with integer work only.
@@ -628,24 +603,7 @@ int plv_db_cleanup_measurements(plv_ctx *ctx, double t) {
   if (!ctx) return PLV_E_BADARG;
   Tracker *T = trk(ctx);
   std::lock_guard<std::mutex> lk(T->mtx);
-  for (auto it = T->db.begin(); it != T->db.end();) {
-    Track &tr = it->second;
-    size_t keep = 0;
-    for (size_t i = 0; i < tr.t.size(); ++i)
-      if (!(tr.t[i] < t)) {
-        tr.t[keep] = tr.t[i];
-        tr.uv[2 * keep] = tr.uv[2 * i], tr.uv[2 * keep + 1] = tr.uv[2 * i + 1];
-        tr.uvn[2 * keep] = tr.uvn[2 * i], tr.uvn[2 * keep + 1] = tr.uvn[2 * i + 1];
-        ++keep;
-      }
-    tr.t.resize(keep);
-    tr.uv.resize(2 * keep);
-    tr.uvn.resize(2 * keep);
-    if (keep == 0)
-      it = T->db.erase(it);
-    else
-      ++it;
-  }
+  for (auto it = T->db.begin(); it != T->db.end();) it = drop_before(it->second, t) == 0 ? T->db.erase(it) : std::next(it);
   return PLV_OK;
 }
 
@@ -669,20 +627,6 @@ int plv_db_append_measurements(plv_ctx *ctx, uint64_t id, int n, const double *t
   return PLV_OK;
 }
 
-// State::bounding_times + bounding_poses_n (order 3): is there an interpolation window for time t?
-// REF: PL-VIWO/src/state/State.cpp:1023-1136 (same test as the kernels' bounding_start)
-static bool has_bounding_poses(const plv_state_view &st, double t) {
-  const int N = st.n_clones;
-  if (N < 4) return false;
-  const double *ct = st.clone_time;
-  if (t < ct[0] - st.dt_exp || t > ct[N - 1] + st.dt_exp) return false;
-  if (t > ct[N - 1]) return false;
-  for (int i = 0; i < N - 1; ++i)
-    if (ct[i] - st.dt_exp <= t && t <= ct[i + 1] + st.dt_exp) return true;
-  return false;
-}
-
-
 int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, double *dx,
                              plv_update_result *res, uint64_t *msckf_ids, uint8_t *accepted_out, double *p_out) {
   if (!ctx || !st || !opt || !dx || !res || st->n_clones < 2 || opt->max_msckf < 1 || opt->max_obs < 2) return PLV_E_BADARG;
@@ -693,20 +637,11 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
   plv::HostPhase ph_pool("update_points: pool + staging");
   plv::RoctxRange rx_get("[Time-Cam] get features");
   const double dt = st->cam_dt;
-  auto has_bounding = bounding_memo([st](double tq) { return has_bounding_poses(*st, tq); });
+  BoundingMemo start_of(*st);
   const double t_oldest = st->clone_time[0], t_oldest2 = st->clone_time[1];  // no keyframes on this path
-  struct Cand {
-    uint64_t id;
-    Track tr;
-  };
+  typedef PoolCand<Track> Cand;
   std::vector<Cand> pool;
-  std::unordered_map<uint64_t, Track> unused;  // db_unused: goes back to the database at the end
-  auto give_back = [&](uint64_t id, double t, const float *uv, const float *uvn) {
-    Track &u = unused[id];
-    u.t.push_back(t);
-    u.uv.insert(u.uv.end(), uv, uv + 2);
-    u.uvn.insert(u.uvn.end(), uvn, uvn + 2);
-  };
+  TrackMap<Track> unused;  // db_unused: goes back to the database at the end
   T->last_slam.clear();
   T->last_init.clear();
   if (opt->n_slam > 0 && !opt->slam_ids) return PLV_E_BADARG;
@@ -725,31 +660,12 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
       auto it = T->db.find(opt->slam_ids[i]);
       if (it == T->db.end()) continue;
       Track &tr = it->second;
-      size_t keep = 0;
-      for (size_t q = 0; q < tr.t.size(); ++q) {
-        const double tm = tr.t[q] + dt;
-        if (tm > opt->state_time + st->dt_exp) {
-          give_back(it->first, tr.t[q], &tr.uv[2 * q], &tr.uvn[2 * q]);
-          continue;
-        }
-        if (tm < t_oldest - st->dt_exp) continue;
-        tr.t[keep] = tr.t[q];
-        tr.uv[2 * keep] = tr.uv[2 * q], tr.uv[2 * keep + 1] = tr.uv[2 * q + 1];
-        tr.uvn[2 * keep] = tr.uvn[2 * q], tr.uvn[2 * keep + 1] = tr.uvn[2 * q + 1];
-        ++keep;
-      }
-      tr.t.resize(keep);
-      tr.uv.resize(2 * keep);
-      tr.uvn.resize(2 * keep);
+      const size_t keep = trim_to_window(unused, it->first, tr, dt, opt->state_time + st->dt_exp, t_oldest - st->dt_exp);
       if (keep == 0) continue;
       // slam_update's own get_imu_poses (UpdaterCamera.cpp:303-304) leaves out what has no bounding clones
       Tracker::Listed e{it->first, Track{}, {0, 0, 0}};
-      for (size_t q = 0; q < keep; ++q) {
-        if (!has_bounding(tr.t[q] + dt)) continue;
-        e.tr.t.push_back(tr.t[q]);
-        e.tr.uv.insert(e.tr.uv.end(), &tr.uv[2 * q], &tr.uv[2 * q] + 2);
-        e.tr.uvn.insert(e.tr.uvn.end(), &tr.uvn[2 * q], &tr.uvn[2 * q] + 2);
-      }
+      for (size_t q = 0; q < keep; ++q)
+        if (start_of(tr.t[q] + dt) >= 0) append_obs(e.tr, tr, q);
       if (!e.tr.t.empty()) T->last_slam.push_back(std::move(e));
     }
   }
@@ -758,88 +674,39 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
     std::lock_guard<std::mutex> lk(T->mtx);
     // REF CamHelper.cpp:631-637 — features_containing_older(oldest_2nd_clone_time), then
     // features_not_containing_newer(t_hist[size-2]); both take the feature out of the database
-    std::vector<uint64_t> take;
-    for (const auto &kv : T->db) {
-      bool older = false, newer = false;
-      for (double t : kv.second.t) {
-        older = older || t < t_oldest2 - dt;
-        newer = newer || t > opt->t_prev_frame - dt;
-      }
-      if (older || !newer) take.push_back(kv.first);
-    }
-    std::sort(take.begin(), take.end());
-    pool.reserve(take.size());
-    for (uint64_t id : take) {
-      auto node = T->db.extract(id);  // (one lookup: the track leaves the database with its node)
-      pool.push_back(Cand{id, std::move(node.mapped())});
-    }
+    take_pool(T->db, t_oldest2 - dt, opt->t_prev_frame - dt, pool);
   }
   res->n_pool = (int)pool.size();
   // REF :740-775 remove_unusable_measurements, and get_imu_poses' bounding-pose test (:327-372)
-  for (auto it = pool.begin(); it != pool.end();) {
-    Track &tr = it->tr;
-    size_t keep = 0;
-    for (size_t i = 0; i < tr.t.size(); ++i) {
-      const double tm = tr.t[i] + dt;
-      if (tm > opt->state_time + st->dt_exp) {
-        give_back(it->id, tr.t[i], &tr.uv[2 * i], &tr.uvn[2 * i]);  // newer than the window: later
-        continue;
-      }
-      if (tm < t_oldest - st->dt_exp) continue;  // older than the window: discarded
-      tr.t[keep] = tr.t[i];
-      tr.uv[2 * keep] = tr.uv[2 * i], tr.uv[2 * keep + 1] = tr.uv[2 * i + 1];
-      tr.uvn[2 * keep] = tr.uvn[2 * i], tr.uvn[2 * keep + 1] = tr.uvn[2 * i + 1];
-      ++keep;
-    }
-    tr.t.resize(keep);
-    tr.uv.resize(2 * keep);
-    tr.uvn.resize(2 * keep);
-    if (keep == 1 && is_slam(it->id)) {  // REF :766-769 kept, then handed back by the n_meas < 2 test (:656-661)
-      give_back(it->id, tr.t[0], &tr.uv[0], &tr.uvn[0]);
-      it = pool.erase(it);
-    } else if (keep < 2) {
-      it = pool.erase(it);  // REF :766-771 a single measurement is dropped
-    } else {
-      ++it;
-    }
+  size_t kept_cands = 0;  // (candidates that stay are moved down once: erasing from the middle shifted the rest every time)
+  for (size_t ci = 0; ci < pool.size(); ++ci) {
+    Cand &c = pool[ci];
+    const size_t keep = trim_to_window(unused, c.id, c.tr, dt, opt->state_time + st->dt_exp, t_oldest - st->dt_exp);
+    if (keep == 1 && is_slam(c.id)) give_back(unused, c.id, c.tr, 0);  // REF :766-769 kept, then handed back by the n_meas < 2 test (:656-661)
+    if (keep < 2) continue;  // REF :766-771 a single measurement is dropped
+    if (kept_cands != ci) pool[kept_cands] = std::move(c);
+    ++kept_cands;
   }
-  // REF :640 sort(feats_pool, feat_sort): long tracks first
-  std::stable_sort(pool.begin(), pool.end(), [](const Cand &a, const Cand &b) { return a.tr.t.size() > b.tr.t.size(); });
+  pool.resize(kept_cands);
+  sort_long_first(pool);  // REF :640
   auto finish = [&](int rc) {
     res->n_returned = (int)unused.size();
     const bool window_full = opt->window_full != 0;
-    auto hand_back = [ctx, T, window_full, t_oldest](std::unordered_map<uint64_t, Track> &un) {
+    auto hand_back = [ctx, T, window_full, t_oldest](TrackMap<Track> &un) {
       {
         std::lock_guard<std::mutex> lk(T->mtx);
-        for (auto &kv : un) {  // REF :702-703 / :727-729 append_new_measurements
-          Track &d = T->db[kv.first];
-          if (d.t.empty()) {
-            d = std::move(kv.second);
-            continue;
-          }
-          d.t.insert(d.t.end(), kv.second.t.begin(), kv.second.t.end());
-          d.uv.insert(d.uv.end(), kv.second.uv.begin(), kv.second.uv.end());
-          d.uvn.insert(d.uvn.end(), kv.second.uvn.begin(), kv.second.uvn.end());
-        }
+        for (auto &kv : un) put_track(T->db, kv.first, kv.second);  // REF :702-703 / :727-729 append_new_measurements
       }
       // REF CamHelper.cpp:733-737: cleanup_features runs on every try_update, whether or not anything was updated
       if (window_full) (void)plv_db_cleanup_measurements(ctx, t_oldest);
     };
     if (T->defer_db) {  // plv_camera_try_update: nothing before the line update's submission reads the point database
-      auto held = std::make_shared<std::unordered_map<uint64_t, Track>>(std::move(unused));
+      auto held = std::make_shared<TrackMap<Track>>(std::move(unused));
       T->deferred_db = [hand_back, held]() { hand_back(*held); };
     } else {
       hand_back(unused);
     }
     return rc;
-  };
-  auto give_back_all = [&](Cand &c) {
-    if (unused.find(c.id) == unused.end()) {  // nothing of this feature went back earlier: hand the track over as it is
-      unused.emplace(c.id, std::move(c.tr));
-      c.tr = Track{};
-      return;
-    }
-    for (size_t i = 0; i < c.tr.t.size(); ++i) give_back(c.id, c.tr.t[i], &c.tr.uv[2 * i], &c.tr.uvn[2 * i]);
   };
   // ---- this frame's update may be on the stream already (Tracker::Spec: enqueued behind the flow by the feed, its pool decided on the
   // device).  The pool above is the same one — formed from the database as always — and says which candidates' results to read.
@@ -870,7 +737,7 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
     if (T->chain_ok && T->early_lines)
       for (int f = 0; f < Fp0; ++f) {
         int v = 0;
-        for (double t : pool[f].tr.t) v += has_bounding(t + dt);
+        for (double t : pool[f].tr.t) v += start_of(t + dt) >= 0;
         if (v >= 2) T->chain_index.emplace(pool[f].id, cand_of[f]);  // (the chained line launch reads the candidates' triangulation results)
       }
     std::vector<double> cp(3 * (size_t)S.F), ce(S.F);
@@ -886,7 +753,7 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
     // (an exit that does not use the batch's update: the covariance goes back to what the batch found, plv_points_spec_undo)
     auto fail = [&](const char *why) {
       plv::set_last_error("speculative point update: %s (host pool %d, device pool %d%s)", why, Fp0, count, over ? ", over the cap" : "");
-      for (Cand &c : pool) give_back_all(c);
+      for (Cand &c : pool) give_back_all(unused, c);
       const int rc_u = plv_points_spec_undo(ctx);
       return finish(rc_u != PLV_OK ? rc_u : PLV_E_DEVICE);
     };
@@ -902,7 +769,7 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
       ++plv::counters().spec_over[over == 1 ? 2 : 1];
     } else {
       if (rc_s != PLV_OK && rc_s != PLV_E_NOT_PSD) {
-        for (Cand &c : pool) give_back_all(c);
+        for (Cand &c : pool) give_back_all(unused, c);
         (void)plv_points_spec_undo(ctx);
         return finish(rc_s);
       }
@@ -932,55 +799,23 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
   //      feature it never reaches keeps its observations either way)
   const int Fp = (int)pool.size();
   // ---- use_imu_res: poses from the CPI table; what it cannot serve leaves the track here (get_imu_poses, :356-365)
-  std::vector<std::vector<double>> cpiR(opt->cpi ? Fp : 0), cpip(opt->cpi ? Fp : 0), cpiQ(opt->cpi ? Fp : 0);
-  std::vector<std::vector<int>> cpiC(opt->cpi ? Fp : 0);
+  CpiPoses cpi;
   const bool imu_cov = opt->cpi && opt->cpi->Q && st->use_imu_cov && !st->use_pol_cov;  // REF CamHelper.cpp:214-224
   if (opt->cpi) {
-    std::vector<double> tq;
-    for (const Cand &c : pool)
-      for (double t : c.tr.t) tq.push_back(t + dt);
-    std::vector<double> Rq(9 * tq.size()), pq(3 * tq.size());
-    std::vector<uint8_t> okq(tq.size());
-    int rc0 = plv_cpi_poses(ctx, st, opt->cpi, (int)tq.size(), tq.data(), Rq.data(), pq.data(), okq.data());
-    std::vector<double> Qq(imu_cov ? 36 * tq.size() : 0);
-    std::vector<int> Cq(imu_cov ? tq.size() : 0);
-    if (rc0 == PLV_OK && imu_cov) {
-      std::vector<uint8_t> okn(tq.size());
-      rc0 = plv_cpi_noise(st, opt->cpi, (int)tq.size(), tq.data(), Qq.data(), Cq.data(), okn.data());
-      for (size_t i = 0; i < tq.size(); ++i) okq[i] = okq[i] && okn[i];
-    }
+    const int rc0 = cpi_attach(ctx, st, opt->cpi, imu_cov, dt, pool, unused, cpi);
     if (rc0 != PLV_OK) {
-      for (Cand &c : pool) give_back_all(c);
+      for (Cand &c : pool) give_back_all(unused, c);
       return finish(rc0);
     }
-    size_t o = 0;
-    for (int f = 0; f < Fp; ++f) {
-      Cand &c = pool[f];
-      Track kept;
-      for (size_t i = 0; i < c.tr.t.size(); ++i, ++o) {
-        if (!okq[o]) {
-          give_back(c.id, c.tr.t[i], &c.tr.uv[2 * i], &c.tr.uvn[2 * i]);
-          continue;
-        }
-        kept.t.push_back(c.tr.t[i]);
-        kept.uv.insert(kept.uv.end(), &c.tr.uv[2 * i], &c.tr.uv[2 * i] + 2);
-        kept.uvn.insert(kept.uvn.end(), &c.tr.uvn[2 * i], &c.tr.uvn[2 * i] + 2);
-        cpiR[f].insert(cpiR[f].end(), &Rq[9 * o], &Rq[9 * o] + 9);
-        cpip[f].insert(cpip[f].end(), &pq[3 * o], &pq[3 * o] + 3);
-        if (imu_cov) {
-          cpiQ[f].insert(cpiQ[f].end(), &Qq[36 * o], &Qq[36 * o] + 36);
-          cpiC[f].push_back(Cq[o]);
-        }
-      }
-      c.tr = std::move(kept);
-    }
   }
-  std::vector<int> ptr(Fp + 1, 0), valid_n(Fp, 0);
+  std::vector<int> ptr, valid_n(Fp, 0);
+  std::vector<double> ot;
+  std::vector<float> ouv, ouvn;
+  flatten_pool(pool, ptr, ot, ouv, ouvn);
   int most_valid = 0;
   for (int f = 0; f < Fp; ++f) {
-    ptr[f + 1] = ptr[f] + (int)pool[f].tr.t.size();
     // get_imu_poses (:327-372): observations without bounding clones do not count (and go back to the database below)
-    for (double t : pool[f].tr.t) valid_n[f] += has_bounding(t + dt);
+    for (double t : pool[f].tr.t) valid_n[f] += start_of(t + dt) >= 0;
     most_valid = std::max(most_valid, valid_n[f]);
   }
   const int nobs = ptr[Fp];
@@ -988,29 +823,17 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
     if (!spec_done) std::fill(dx, dx + ctx->cov_n, 0.0);
     return finish(PLV_OK);
   }
-  std::vector<double> ot(nobs), pf(3 * (size_t)Fp), err(Fp);
-  std::vector<float> ouv(2 * (size_t)nobs), ouvn(2 * (size_t)nobs);
+  std::vector<double> pf(3 * (size_t)Fp), err(Fp);
   std::vector<uint8_t> ok(Fp);
-  for (int f = 0; f < Fp; ++f) {
-    const Track &tr = pool[f].tr;
-    std::copy(tr.t.begin(), tr.t.end(), ot.begin() + ptr[f]);
-    std::copy(tr.uv.begin(), tr.uv.end(), ouv.begin() + 2 * (size_t)ptr[f]);
-    std::copy(tr.uvn.begin(), tr.uvn.end(), ouvn.begin() + 2 * (size_t)ptr[f]);
-  }
   plv_tracks all{};
   all.n_feat = Fp;
   all.obs_ptr = ptr.data();
   all.obs_time = ot.data();
   all.obs_uv = ouv.data();
   all.obs_uvn = ouvn.data();
-  std::vector<double> allR, allp;
-  if (opt->cpi) {
-    for (int f = 0; f < Fp; ++f) {
-      allR.insert(allR.end(), cpiR[f].begin(), cpiR[f].end());
-      allp.insert(allp.end(), cpip[f].begin(), cpip[f].end());
-    }
-    all.res_R = allR.data();
-    all.res_p = allp.data();
+  if (cpi.on) {
+    all.res_R = cpi.R.data();
+    all.res_p = cpi.p.data();
   }
   std::vector<int> cols(ctx->cfg.max_state_dim > 0 ? ctx->cfg.max_state_dim : 1024);
   int k = 0, n_rows = 0, rc = PLV_OK;
@@ -1063,7 +886,7 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
         fused_ran = rc == PLV_OK;
       }
       if (rc != PLV_OK) {
-        for (Cand &c : pool) give_back_all(c);
+        for (Cand &c : pool) give_back_all(unused, c);
         return finish(rc);
       }
     }
@@ -1071,7 +894,7 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
     start_detection_ahead(ctx);
     rc = plv_triangulate(ctx, st, &all, &opt->tri, pf.data(), ok.data(), err.data());
     if (rc != PLV_OK) {
-      for (Cand &c : pool) give_back_all(c);
+      for (Cand &c : pool) give_back_all(unused, c);
       return finish(rc);
     }
   }
@@ -1105,7 +928,7 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
   for (int f = 0; f < Fp; ++f) {
     Cand &c = pool[f];
     if ((int)sel.size() >= opt->max_msckf) {  // :651-653 break; the rest returns to the database (:702)
-      give_back_all(c);
+      give_back_all(unused, c);
       continue;
     }
     const int valid = valid_n[f];
@@ -1116,20 +939,17 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
       u.newest = c.tr.t.back();
     }
     if (valid < 2 || !ok[f] || !(err[f] < 3.0)) {  // :656-683
-      give_back_all(c);
+      give_back_all(unused, c);
       continue;
     }
     // :685-693 a long track becomes a new in-state landmark while there is room
     if (valid >= opt->init_min_meas && opt->n_slam + (int)T->last_init.size() < opt->max_slam) {
       Tracker::Listed e{c.id, Track{}, {pf[3 * (size_t)f], pf[3 * (size_t)f + 1], pf[3 * (size_t)f + 2]}};
       for (size_t i = 0; i < c.tr.t.size(); ++i) {
-        if (!has_bounding(c.tr.t[i] + dt)) {
-          give_back(c.id, c.tr.t[i], &c.tr.uv[2 * i], &c.tr.uvn[2 * i]);
-          continue;
-        }
-        e.tr.t.push_back(c.tr.t[i]);
-        e.tr.uv.insert(e.tr.uv.end(), &c.tr.uv[2 * i], &c.tr.uv[2 * i] + 2);
-        e.tr.uvn.insert(e.tr.uvn.end(), &c.tr.uvn[2 * i], &c.tr.uvn[2 * i] + 2);
+        if (start_of(c.tr.t[i] + dt) < 0)
+          give_back(unused, c.id, c.tr, i);
+        else
+          append_obs(e.tr, c.tr, i);
       }
       T->last_init.push_back(std::move(e));
       continue;
@@ -1152,31 +972,20 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
   // ---- UpdaterCamera::msckf_update on the selected features
   const int F = (int)sel.size();
   std::vector<int> sptr(F + 1, 0);
-  std::vector<double> st_t, sp(3 * (size_t)F), selR, selp, selQ;
-  std::vector<int> selC;
-  std::vector<float> suv;
+  std::vector<double> sp(3 * (size_t)F);
+  ObsGather g;
   for (int q = 0; q < F; ++q) {
     const Cand &c = pool[sel[q]];
     int seen = 0;
     for (size_t i = 0; i < c.tr.t.size(); ++i) {
-      if (!has_bounding(c.tr.t[i] + dt)) {
-        give_back(c.id, c.tr.t[i], &c.tr.uv[2 * i], &c.tr.uvn[2 * i]);
+      if (start_of(c.tr.t[i] + dt) < 0) {
+        give_back(unused, c.id, c.tr, i);
         continue;
       }
       if (seen++ < n_skip[sel[q]]) continue;
-      st_t.push_back(c.tr.t[i]);
-      suv.push_back(c.tr.uv[2 * i]);
-      suv.push_back(c.tr.uv[2 * i + 1]);
-      if (opt->cpi) {
-        selR.insert(selR.end(), &cpiR[sel[q]][9 * i], &cpiR[sel[q]][9 * i] + 9);
-        selp.insert(selp.end(), &cpip[sel[q]][3 * i], &cpip[sel[q]][3 * i] + 3);
-        if (imu_cov) {
-          selQ.insert(selQ.end(), &cpiQ[sel[q]][36 * i], &cpiQ[sel[q]][36 * i] + 36);
-          selC.push_back(cpiC[sel[q]][i]);
-        }
-      }
+      gather_obs(g, c.tr, i, cpi, ptr[sel[q]] + i);
     }
-    sptr[q + 1] = (int)st_t.size();
+    sptr[q + 1] = (int)g.t.size();
     std::copy(pf.begin() + 3 * (size_t)sel[q], pf.begin() + 3 * (size_t)sel[q] + 3, sp.begin() + 3 * (size_t)q);
     if (msckf_ids) msckf_ids[q] = c.id;
   }
@@ -1188,16 +997,16 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
     plv_tracks tr{};
     tr.n_feat = F;
     tr.obs_ptr = sptr.data();
-    tr.obs_time = st_t.data();
-    tr.obs_uv = suv.data();
+    tr.obs_time = g.t.data();
+    tr.obs_uv = g.uv.data();
     tr.p_FinG = sp.data();
     tr.p_FinG_fej = sp.data();  // MSCKF features: FEJ value = estimate (REF CamHelper.cpp:556-557)
-    if (opt->cpi) {
-      tr.res_R = selR.data();
-      tr.res_p = selp.data();
-      if (imu_cov) {
-        tr.res_Q = selQ.data();
-        tr.res_clone = selC.data();
+    if (cpi.on) {
+      tr.res_R = g.R.data();
+      tr.res_p = g.p.data();
+      if (cpi.noise) {
+        tr.res_Q = g.Q.data();
+        tr.res_clone = g.C.data();
       }
     }
     rc = plv_jacobian_columns(st, &tr, cols.data(), (int)cols.size(), &k);
@@ -1208,7 +1017,7 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
       if (rc == PLV_E_NOT_PSD) rc = PLV_OK;  // EKFUpdate returned false: nothing changed, the call itself succeeded
     }
     if (rc != PLV_OK) {
-      for (int q = 0; q < F; ++q) give_back_all(pool[sel[q]]);
+      for (int q = 0; q < F; ++q) give_back_all(unused, pool[sel[q]]);
       return finish(rc);
     }
   }
@@ -1219,7 +1028,7 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
     if (!acc[q]) {  // REF UpdaterCamera.cpp:266-268: only gate failures go back; what EKFUpdate then rejects is consumed all the same
       const Cand &c = pool[sel[q]];
       for (size_t i = 0; i < c.tr.t.size(); ++i)
-        if (has_bounding(c.tr.t[i] + dt)) give_back(c.id, c.tr.t[i], &c.tr.uv[2 * i], &c.tr.uvn[2 * i]);
+        if (start_of(c.tr.t[i] + dt) >= 0) give_back(unused, c.id, c.tr, i);
     }
   }
   return finish(PLV_OK);
