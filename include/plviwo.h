@@ -49,6 +49,10 @@ enum {
 
 /* ---------------------------------------------------------------- configuration */
 enum { PLV_HIST_NONE = 0, PLV_HIST_HISTOGRAM = 1, PLV_HIST_CLAHE = 2 }; /* REF: TrackBase.h:78 */
+/* Camera models (REF: State.cpp:74-80 `distortion_model`): what intrinsics[4..7] mean.  Radtan: k1 k2 p1 p2 (CamRadtan).
+ * Equidistant (fisheye): k1 k2 k3 k4 of theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8) (CamEqui).
+ * The default is radtan; plv_set_camera_model chooses. */
+enum { PLV_CAM_RADTAN = 0, PLV_CAM_EQUIDISTANT = 1 };
 
 typedef struct plv_config {
   /* image / tracker.  REF: TrackKLT ctor TrackKLT.h:57-62, UpdaterCamera.cpp:41 */
@@ -65,7 +69,8 @@ typedef struct plv_config {
   double ransac_thr_px;  /* 2.0  REF: TrackKLT.cpp:873 (divided by max focal length inside) */
   double ransac_conf;    /* 0.999 */
   int ransac_max_iters;  /* 1000 (OpenCV default for findFundamentalMat) */
-  double intrinsics[8];  /* fx fy cx cy k1 k2 p1 p2  REF: CamBase.h:56-82 */
+  double intrinsics[8];  /* fx fy cx cy k1 k2 p1 p2 (radtan) or fx fy cx cy k1 k2 k3 k4 (equidistant,
+                            plv_set_camera_model)  REF: CamBase.h:56-82 */
   /* line front-end.  REF: TrackLSD.h:269-273, TrackLSD.cpp:200-231,780,824 */
   int line_length_threshold;   /* 20 (half-res px) */
   float line_distance_threshold; /* 1.41421356 */
@@ -284,7 +289,8 @@ int plv_pyramid_download(plv_ctx *ctx, int which, int level, int *w, int *h, uin
 int plv_lk_track(plv_ctx *ctx, int n, const float *pts0, float *pts1, uint8_t *status, int *iters);
 
 /* plv_undistort replaces CamRadtan::undistort_f per point (REF: ov_core/src/cam/CamRadtan.h:99-120,
- * cv::undistortPoints with K, D from cfg.intrinsics): pixel uv -> normalised xy, float. */
+ * cv::undistortPoints with K, D from cfg.intrinsics): pixel uv -> normalised xy, float.  Under PLV_CAM_EQUIDISTANT it is
+ * CamEqui::undistort_f (REF: CamEqui.h:108-131, cv::fisheye::undistortPoints of OpenCV 4.2). */
 int plv_undistort(plv_ctx *ctx, int n, const float *uv, float *xy);
 
 /* plv_ransac_fundamental replaces cv::findFundamentalMat(m1, m2, FM_RANSAC, thr, ransac_conf,
@@ -375,7 +381,8 @@ typedef struct plv_state_view {
   const double *clone_p_fej;   /* [n_clones][3]                    (pos_fej())        */
   const int *clone_state_id;   /* [n_clones] covariance index of each clone's 6-dof error (Type::id()) */
   double R_ItoC[9], p_IinC[3]; /* camera extrinsics, State::cam_extrinsic             */
-  double intrinsics[8];        /* State::cam_intrinsic value (fx fy cx cy k1 k2 p1 p2) */
+  double intrinsics[8];        /* State::cam_intrinsic value (fx fy cx cy k1 k2 p1 p2, or k1..k4 under the equidistant
+                                  model of the ctx: plv_set_camera_model) */
   double cam_dt;               /* State::cam_dt value                                  */
   int extrinsic_state_id;      /* covariance index, or -1 unless do_calib_ext          */
   int intrinsic_state_id;      /* ... -1 unless do_calib_int                           */
@@ -572,7 +579,8 @@ int plv_line_match(const float *lines_new, int n_new, const int *rel_ptr_new, co
 /* TrackLSD::LineClassification (REF :318-366): 0..3 for vps = [x y z][2]. */
 int plv_line_classification(const float *line, const double *vps);
 /* LineHelper::Vanishing_Points (REF: linefeat/LineHelper.cpp:1026-1088): vps[3][2] from R_ItoC (row-major) and
- * the 8 intrinsics. */
+ * the 8 intrinsics.  Always the radtan formula, whatever the camera model: LineHelper::Distort (:1058-1088) has its
+ * fisheye branch commented out, so under PLV_CAM_EQUIDISTANT k1..k4 go in as k1 k2 p1 p2, as in the reference. */
 int plv_vanishing_points(const double *R_ItoC, const double *K8, double *vps);
 
 /* TrackLSD::feed_monocular (REF :70-192) for the image currently held by the ctx — call after
@@ -929,8 +937,16 @@ int plv_init_imu_wheel(const plv_iw_init_options *opt, plv_iw_init_state *state,
                        const double *am, int n_wheel, const double *tw, const double *m1, const double *m2, double *imustate, int *ok,
                        int *mode, double *init12);
 /* StateHelper::EKFUpdate refreshes the tracker's camera model after every update when the intrinsics are calibrated
- * online (REF: PL-VIWO/src/state/StateHelper.cpp:163-168): same for the ctx (undistortion, RANSAC threshold). */
+ * online (REF: PL-VIWO/src/state/StateHelper.cpp:163-168): same for the ctx (undistortion, RANSAC threshold).  K8 is
+ * read under the ctx's camera model (plv_config::intrinsics). */
 int plv_set_camera_intrinsics(plv_ctx *ctx, const double *K8);
+/* The camera model of the ctx's intrinsics (REF: State.cpp:74-80, `distortion_model`): PLV_CAM_RADTAN (the default) or
+ * PLV_CAM_EQUIDISTANT; anything else is PLV_E_BADARG.  Like plv_set_camera_intrinsics it takes effect at the next call:
+ * the front-end's undistortion (LK tail, plv_undistort, the kept lines' end points), the point residuals and Jacobians
+ * (plv_build_jacobians[_resident], the fused updates, SLAM) and the triangulation's reprojection error.  Unchanged under
+ * either model, as in the reference: the vanishing points (radtan formula), the line Jacobians (pinhole K, no distortion
+ * term), the RANSAC threshold and the downsampling rule. */
+int plv_set_camera_model(plv_ctx *ctx, int model);
 /* plv_config::win_size after the context was made (REF: TrackKLT.h:143-144 `win_size`, the winSize of calcOpticalFlowPyrLK at
  * TrackKLT.cpp:857-858 and of buildOpticalFlowPyramid at :71): odd, 3 .. 21.  The pyramids are laid out for the window they were
  * made with (a level exists while both its sides exceed the window): a window that would change the number of levels is refused

@@ -26,6 +26,9 @@ PLV_E_CAPACITY = -5
 PLV_E_NO_DEVICE = -6
 PLV_E_NUMERIC = -7
 
+PLV_CAM_RADTAN = 0
+PLV_CAM_EQUIDISTANT = 1
+
 
 class PlvConfig(C.Structure):
     _fields_ = [
@@ -151,6 +154,7 @@ def load_library():
         "plv_init_imu_wheel": (C.c_int, [C.POINTER(PlvIwInitOptions), C.POINTER(PlvIwInitState), C.c_int, dp, dp, dp, C.c_int, dp, dp, dp,
                                          dp, ip, ip, dp]),
         "plv_set_camera_intrinsics": (C.c_int, [vp, dp]),
+        "plv_set_camera_model": (C.c_int, [vp, C.c_int]),
         "plv_set_lk_window": (C.c_int, [vp, C.c_int]),
         "plv_wheel_update": (C.c_int, [vp, C.POINTER(PlvWheelOptions), C.POINTER(PlvWheelState), C.c_int, dp, dp, dp, u8p, dp]),
         "plv_next_clone_time": (C.c_int, [C.POINTER(PlvCloneSchedule), dp, ip]),
@@ -781,6 +785,8 @@ class Context:
     """One plv_ctx (one camera / one HIP stream).  Raises PlvError on any non-OK status except
     where a method documents a returned status."""
 
+    CAMERA_MODELS = ("radtan", "equidistant")   # index = PLV_CAM_RADTAN / PLV_CAM_EQUIDISTANT (set_camera_model)
+
     def __init__(self, cfg=None):
         self.lib = load_library()
         self.cfg = cfg if cfg is not None else default_config()
@@ -1136,6 +1142,14 @@ class Context:
     def set_camera_intrinsics(self, K8):
         K8 = _c64(K8)
         self._chk(self.lib.plv_set_camera_intrinsics(self.h, _dp(K8)))
+
+    def set_camera_model(self, model):
+        """plv_set_camera_model: "radtan" | "equidistant" (or PLV_CAM_*); intrinsics[4..7] are k1 k2 p1 p2 / k1 k2 k3 k4"""
+        if isinstance(model, str):
+            if model not in self.CAMERA_MODELS:
+                raise PlvError(PLV_E_BADARG, f"unknown camera model {model!r} (known: {', '.join(self.CAMERA_MODELS)})")
+            model = self.CAMERA_MODELS.index(model)
+        self._chk(self.lib.plv_set_camera_model(self.h, int(model)))
 
     def cov_marginalize(self, idx, size):
         self._chk(self.lib.plv_cov_marginalize(self.h, int(idx), int(size)))

@@ -417,6 +417,7 @@ int plv_lk_track(plv_ctx *ctx, int n, const float *pts0, float *pts1, uint8_t *s
 static CamK cam_of(plv_ctx *ctx) {
   CamK K;
   for (int i = 0; i < 8; ++i) K.v[i] = ctx->cfg.intrinsics[i];
+  K.model = ctx->cam_model;
   return K;
 }
 

@@ -4,13 +4,14 @@
 //   pyrdown_kernel                 K2  cv::buildOpticalFlowPyramid REF call site: TrackKLT.cpp:71
 //   lk_kernel                      K3  cv::calcOpticalFlowPyrLK    REF call site: TrackKLT.cpp:857-858
 //   undistort_kernel               K6  cv::undistortPoints         REF call site: ov_core/src/cam/CamRadtan.h:99-120
+//                                      (cv::fisheye::undistortPoints under the equidistant model: CamEqui.h:108-131)
 //   ransac_*_kernel                K7  cv::findFundamentalMat      REF call site: TrackKLT.cpp:870-873
 //
 // Arithmetic contract (DESIGN.md "Front-end arithmetic"): integer image arithmetic is exact
 // (LUT, 5x5 binomial, Scharr, 14-bit bilinear weights); LK's normal-equation sums are exact
 // int64 wave reductions rounded to float once, so tracked positions are comparable bit-for-bit
 // with the CPU oracle whatever the reduction order.
-#include "radtan_core.hpp"
+#include "cam_models.hpp"
 #include <algorithm>
 
 #include "frontend_kernels.hpp"
@@ -609,7 +610,7 @@ __global__ void __launch_bounds__(64 * LK4_WAVES) lk_kernel(PyrDesc prev, PyrDes
   }
   if (n0 && tid < 2) {
     float xn, yn;
-    undistort_radtan(K.v, tid == 0 ? px0 : nextx, tid == 0 ? py0 : nexty, xn, yn);
+    undistort_model(K.model, K.v, tid == 0 ? px0 : nextx, tid == 0 ? py0 : nexty, xn, yn);
     float *dst = tid == 0 ? n0 : n1;
     dst[2 * pt] = xn;
     dst[2 * pt + 1] = yn;
@@ -620,7 +621,7 @@ __global__ void __launch_bounds__(64 * LK4_WAVES) lk_kernel(PyrDesc prev, PyrDes
 __global__ void undistort_kernel(CamK K, int n, const float *__restrict__ uv, float *__restrict__ xy) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  undistort_radtan(K.v, uv[2 * i], uv[2 * i + 1], xy[2 * i], xy[2 * i + 1]);
+  undistort_model(K.model, K.v, uv[2 * i], uv[2 * i + 1], xy[2 * i], xy[2 * i + 1]);
 }
 // both point sets of perform_matching in one launch
 __global__ void undistort2_kernel(CamK K, int n, const float *__restrict__ uv0, const float *__restrict__ uv1,
@@ -628,10 +629,10 @@ __global__ void undistort2_kernel(CamK K, int n, const float *__restrict__ uv0, 
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 2 * n) return;
   if (i < n)
-    undistort_radtan(K.v, uv0[2 * i], uv0[2 * i + 1], xy0[2 * i], xy0[2 * i + 1]);
+    undistort_model(K.model, K.v, uv0[2 * i], uv0[2 * i + 1], xy0[2 * i], xy0[2 * i + 1]);
   else {
     i -= n;
-    undistort_radtan(K.v, uv1[2 * i], uv1[2 * i + 1], xy1[2 * i], xy1[2 * i + 1]);
+    undistort_model(K.model, K.v, uv1[2 * i], uv1[2 * i + 1], xy1[2 * i], xy1[2 * i + 1]);
   }
 }
 

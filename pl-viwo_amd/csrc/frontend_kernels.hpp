@@ -16,6 +16,7 @@ struct PyrDesc {
 
 struct CamK {
   double v[8];
+  int model;  // PLV_CAM_RADTAN / PLV_CAM_EQUIDISTANT
 };
 
 int launch_equalize(plv_ctx *ctx, const uint8_t *d_src, uint8_t *d_dst, int npix, unsigned *d_hist);

@@ -141,6 +141,7 @@ int stage_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *s
   memcpy(P.R_ItoC, st->R_ItoC, 72);
   memcpy(P.p_IinC, st->p_IinC, 24);
   memcpy(P.K, st->intrinsics, 64);
+  P.cam_model = ctx->cam_model;
   P.cam_dt = st->cam_dt;
   P.dt_exp = st->dt_exp;
   P.sigma_pix = st->sigma_pix;
@@ -724,6 +725,7 @@ int stage_line_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_vi
   memcpy(P.R_ItoC, st->R_ItoC, 72);
   memcpy(P.p_IinC, st->p_IinC, 24);
   memcpy(P.K, st->intrinsics, 64);
+  P.cam_model = ctx->cam_model;
   P.cam_dt = st->cam_dt;
   P.dt_exp = st->dt_exp;
   P.sigma_pix = st->sigma_pix;

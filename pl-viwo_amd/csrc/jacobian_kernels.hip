@@ -4,6 +4,7 @@
 //                     State::get_interpolated_jacobian (FEJ polynomial) REF: PL/state/State.cpp:833-973
 //                     State::get_interpolated_pose_poly (residual pose) REF: PL/state/State.cpp:979-1021
 //                     CamRadtan::distort_f / compute_distort_jacobian  REF: OV/cam/CamRadtan.h:127-198
+//                     CamEqui::distort_f / compute_distort_jacobian    REF: OV/cam/CamEqui.h:136-229 (cam_models.hpp)
 //
 // One THREAD per observation: the work per observation is a few thousand scalar fp64 operations on
 // 3x3 blocks (two polynomial interpolations on so(3) x R^3, projection, distortion Jacobians, 2x2
@@ -23,6 +24,7 @@ __device__ __forceinline__ void jac_stamp(int id) {
 }
 }  // namespace plv
 #define GATE_STAMP(id) jac_stamp(id)
+#include "cam_models.hpp"
 #include "gate_core.hpp"
 #include "jacobian_kernels.hpp"
 #include "nullspace_core.hpp"
@@ -292,7 +294,7 @@ struct WinTab {
 // the corrected one).  The second state comes in as two pointer VALUES: a pointer to its JacParams keeps that whole struct — and
 // the caller's — in scratch memory (a select between members of two structs becomes a select of their addresses: 48 bytes of
 // scratch stores per lane at the top of every workgroup, 1.1 MB per line launch in round 5's WRITE_SIZE).
-__device__ void build_window_tables(const JacParams &P, WinTab *tab, const double *Rt = nullptr, const double *pt = nullptr) {
+__device__ __forceinline__ void build_window_tables(const JacParams &P, WinTab *tab, const double *Rt = nullptr, const double *pt = nullptr) {
   const int nwin = max(P.n_clones - 3, 0);
   const int ntask = nwin * (Rt ? 3 : 2);
   const double *const R_est = P.clone_R, *const R_fej = P.clone_R_fej, *const p_est = P.clone_p, *const p_fej = P.clone_p_fej;
@@ -331,7 +333,7 @@ __device__ void build_window_tables(const JacParams &P, WinTab *tab, const doubl
   __syncthreads();
 }
 
-__device__ void interpolate_tab(const JacParams &P, const WinTab &T, int s0, double t, bool want_jac, Interp &o) {
+__device__ __forceinline__ void interpolate_tab(const JacParams &P, const WinTab &T, int s0, double t, bool want_jac, Interp &o) {
   const double dtm = t - P.clone_time[s0];
   const double pw[4] = {1.0, dtm, dtm * dtm, dtm * dtm * dtm};
   double lam[3], lamd[3];
@@ -421,7 +423,7 @@ __global__ void __launch_bounds__(128) jacobian_kernel(JacParams P) {
 
 // The reference's selection loop on the device: candidate f is taken when it passes its own tests and fewer than max_sel
 // candidates before it did.  Called by every thread of the workgroup.
-__device__ bool candidate_selected(const JacParams &P, int f) {
+__device__ __forceinline__ bool candidate_selected(const JacParams &P, int f) {
   auto base = [&](int g) { return P.sel_flags[g] && P.tri_ok[g] && (!P.tri_err || P.tri_err[g] < 3.0); };
   int before = 0;
   for (int g0 = 0; g0 < f; g0 += blockDim.x) {
@@ -435,7 +437,7 @@ __device__ bool candidate_selected(const JacParams &P, int f) {
 // row-major in LDS, projected there (nullspace_core.hpp) and only the projected block goes to global memory — one launch, one
 // 1.7 MB write and one 1.7 MB read less on the update chain.  The covariance gathers of the update ride on it as extra workgroups
 // (they read the column map from the packed input block: the resident copy is being written by workgroup 0).
-__device__ void triangulate_feature(const JacParams &P, int f, int o0, int o1, double *poses, unsigned char *valid, const float *uvn, const float *uv,
+__device__ __forceinline__ void triangulate_feature(const JacParams &P, int f, int o0, int o1, double *poses, unsigned char *valid, const float *uvn, const float *uv,
                                     const plv_tri_options &opt, double *__restrict__ p_out, unsigned char *__restrict__ ok_out,
                                     double *__restrict__ err_out, int max_obs, double *tri_smem, double *tot, bool poses_ready = false,
                                     double *res_l = nullptr);
@@ -521,6 +523,14 @@ __device__ __forceinline__ void rows_est_part(const JacParams &P, const V3 &pf, 
   const V3 p_FinI = mv(R_GtoI, vsub(pf, p_IinG));
   const V3 p_FinC = vadd(mv(R_ItoC, p_FinI), p_IinC);
   const double un = p_FinC[0] / p_FinC[2], vn = p_FinC[1] / p_FinC[2];
+  if (P.cam_model == PLV_CAM_EQUIDISTANT) {  // CamEqui::distort_f / compute_distort_jacobian (cam_models.hpp)
+    double x1, y1;
+    distort_equidistant_f(K, (float)un, (float)vn, x1, y1);
+    r2[0] = (double)uv[0] - (double)(float)(K[0] * x1 + K[2]);
+    r2[1] = (double)uv[1] - (double)(float)(K[1] * y1 + K[3]);
+    distort_jacobian_equidistant(K, un, vn, dzn, dzeta);
+    return;
+  }
   {
     const double x = (double)(float)un, y = (double)(float)vn;
     const double r = sqrt(x * x + y * y), r_2 = r * r, r_4 = r_2 * r_2;
@@ -825,6 +835,8 @@ __device__ __forceinline__ void jacobian_rows_split(const JacParams &P, const V3
         for (int q = 0; q < 9; ++q) pr[PRE_G + q] = dpC_dpG.m[q];
 #pragma unroll
         for (int q = 0; q < 3; ++q) pr[PRE_LEVER + q] = lever[q];
+      } else if (wave == 1 && P.cam_model == PLV_CAM_EQUIDISTANT) {  // (straight into the slot: fewer registers live on this wave)
+        rows_est_part(P, pf, uv_l + 2 * i, ldM(pr + PRE_RE), ldV(pr + PRE_PE), pr + PRE_R2, pr + PRE_DZN, pr + PRE_DZETA);
       } else if (wave == 1) {
         double r2[2], dzn[4], dzeta[16];
         rows_est_part(P, pf, uv_l + 2 * i, ldM(pr + PRE_RE), ldV(pr + PRE_PE), r2, dzn, dzeta);
@@ -919,7 +931,9 @@ __host__ __device__ inline FusedLds fused_lds_layout(int ld, int ncol, int fdim,
 }
 static_assert(sizeof(WinTab) % 8 == 0, "fused_lds_layout counts WinTab in doubles");
 
-__global__ void __launch_bounds__(256) jacobian_nullspace_kernel(JacParams P, int F, GatherArgs g, PointTriStage tri, GateStage gate) {
+// (the kernel sits at the inliner's basic-block budget: the helpers it calls are __forceinline__ so that none becomes a call that would
+// pin the parameter structs in scratch, and waves_per_eu(2) holds the register budget of two waves per SIMD — DESIGN.md §5)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) jacobian_nullspace_kernel(JacParams P, int F, GatherArgs g, PointTriStage tri, GateStage gate) {
   extern __shared__ double jsm[];
   __shared__ int s_rows, s_base;
   __shared__ double tri_tot[32], s_tri[5];
@@ -1078,7 +1092,7 @@ __global__ void __launch_bounds__(256) jacobian_nullspace_kernel(JacParams P, in
 //   FeatureInitializer::single_triangulation          REF: OV/feat/FeatureInitializer.cpp:30-112
 //   FeatureInitializer::single_gaussnewton            REF: OV/feat/FeatureInitializer.cpp:197-375
 //   CamHelper::moving_consistency (mean reprojection) REF: PL/update/cam/CamHelper.cpp:426-483
-__device__ void campose_one(const JacParams &P, int o, double *__restrict__ poses /*[n_obs][12]*/, unsigned char *__restrict__ valid,
+__device__ __forceinline__ void campose_one(const JacParams &P, int o, double *__restrict__ poses /*[n_obs][12]*/, unsigned char *__restrict__ valid,
                             double *__restrict__ imu) {
   const double tm = P.obs_time[o] + P.cam_dt;
   const int s0 = bounding_start(P, tm);
@@ -1267,7 +1281,7 @@ static_assert(sizeof(TriObs) == 15 * 8, "tri_smem_doubles counts 15 doubles per 
 // of LDS, tot: 32 doubles of LDS.  Wave-level synchronisation only (the lanes run in lockstep; the fences order the LDS traffic).
 // Observations o0 .. o1 - 1 index poses / valid / uvn / uv: the global arrays of triangulate_kernel (o0 = obs_ptr[f]) or a workgroup's
 // LDS copies of its own feature's observations (o0 = 0, poses_ready: the caller has filled poses and valid).
-__device__ void triangulate_feature(const JacParams &P, int f, int o0, int o1, double *poses, unsigned char *valid, const float *uvn, const float *uv,
+__device__ __forceinline__ void triangulate_feature(const JacParams &P, int f, int o0, int o1, double *poses, unsigned char *valid, const float *uvn, const float *uv,
                                     const plv_tri_options &opt, double *__restrict__ p_out, unsigned char *__restrict__ ok_out,
                                     double *__restrict__ err_out, int max_obs, double *tri_smem, double *tot, bool poses_ready,
                                     double *res_l /* LDS copy of the result for the caller's workgroup: p [3], ok, err */) {
@@ -1524,10 +1538,15 @@ __device__ void triangulate_feature(const JacParams &P, int f, int o0, int o1, d
     for (int q = lane; q < M; q += 64) {
       const int o = list[q];
       const V3 pC = mv(ldM(poses + 12 * o), vsub(pg, ldV(poses + 12 * o + 9)));
-      const double x = (double)(float)(pC[0] / pC[2]), y = (double)(float)(pC[1] / pC[2]);
-      const double r = sqrt(x * x + y * y), r_2 = r * r, r_4 = r_2 * r_2;
-      const double x1 = x * (1 + K[4] * r_2 + K[5] * r_4) + 2 * K[6] * x * y + K[7] * (r_2 + 2 * x * x);
-      const double y1 = y * (1 + K[4] * r_2 + K[5] * r_4) + K[6] * (r_2 + 2 * y * y) + 2 * K[7] * x * y;
+      double x1, y1;
+      if (P.cam_model == PLV_CAM_EQUIDISTANT) {
+        distort_equidistant_f(K, (float)(pC[0] / pC[2]), (float)(pC[1] / pC[2]), x1, y1);
+      } else {
+        const double x = (double)(float)(pC[0] / pC[2]), y = (double)(float)(pC[1] / pC[2]);
+        const double r = sqrt(x * x + y * y), r_2 = r * r, r_4 = r_2 * r_2;
+        x1 = x * (1 + K[4] * r_2 + K[5] * r_4) + 2 * K[6] * x * y + K[7] * (r_2 + 2 * x * x);
+        y1 = y * (1 + K[4] * r_2 + K[5] * r_4) + K[6] * (r_2 + 2 * y * y) + 2 * K[7] * x * y;
+      }
       const double r0 = (double)uv[2 * o] - (double)(float)(K[0] * x1 + K[2]);
       const double r1 = (double)uv[2 * o + 1] - (double)(float)(K[1] * y1 + K[3]);
       term[q * TRI_TERMS] = sqrt(r0 * r0 + r1 * r1);

@@ -12,6 +12,7 @@ struct JacParams {
   double R_ItoC[9], p_IinC[3], K[8];
   double cam_dt, dt_exp, sigma_pix, intr_ori_cov, intr_pos_cov;
   int use_pol_cov, feat_rep;
+  int cam_model;  // of K: PLV_CAM_RADTAN / PLV_CAM_EQUIDISTANT, a runtime value — the fused kernels stay one symbol each
   int col_ext, col_int, col_dt;
   // tracks (device pointers)
   int n_feat, n_obs;

@@ -25,7 +25,7 @@
 #include <vector>
 
 #include "line_host.hpp"
-#include "radtan_core.hpp"
+#include "cam_models.hpp"
 #include "line_kernels.hpp"
 #include "update_state.hpp"
 #include "plv_internal.hpp"
@@ -142,6 +142,7 @@ struct LineTracker {
     plv_ctx *ctx = nullptr;
     double timestamp = 0, vps[6] = {0, 0, 0, 0, 0, 0};
     double K8[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the camera model at post time (the caller may refresh ctx->cfg.intrinsics while the job runs)
+    int cam_model = 0;
     std::vector<float> pts;
     std::vector<uint64_t> pids;
     int rc = PLV_OK;
@@ -166,7 +167,7 @@ LineTracker *ltr(plv_ctx *ctx, bool run_deferred = true);  // (defined after Lin
 void form_line_pool(LineTracker *T, const PoolArgs &A, LinePool &R);
 void discard_line_pool(LineTracker *T);
 // (feed_points_impl is defined further down, outside this namespace: the worker reaches it through this pointer)
-int (*g_feed_impl)(plv_ctx *, LineTracker *, double, const double *, int, const float *, const uint64_t *, const double *) = nullptr;
+int (*g_feed_impl)(plv_ctx *, LineTracker *, double, const double *, int, const float *, const uint64_t *, const double *, int) = nullptr;
 void line_worker(LineTracker *T) {
   for (;;) {
     bool do_detect = false, do_feed = false, do_deferred = false;
@@ -197,7 +198,7 @@ void line_worker(LineTracker *T) {
         plv::host_phases().add("line worker: feed job starts after its post", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - T->feed_posted).count());
       const auto Fs = std::chrono::steady_clock::now();
       plv::counters().w_feed_start_ns += (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(Fs - T->feed_posted).count();
-      const int rc = g_feed_impl(F.ctx, T, F.timestamp, F.vps, (int)F.pids.size(), F.pts.data(), F.pids.data(), F.K8);
+      const int rc = g_feed_impl(F.ctx, T, F.timestamp, F.vps, (int)F.pids.size(), F.pts.data(), F.pids.data(), F.K8, F.cam_model);
       if (rc == PLV_OK && F.pool_on) {
         discard_line_pool(T);
         form_line_pool(T, F.pool_args, T->pool_prep);
@@ -648,19 +649,21 @@ int plv_line_tracker_feed(plv_ctx *ctx, double timestamp, const double *vps) {
   return plv_line_tracker_feed_points(ctx, timestamp, vps, np, pts.data(), pids.data());
 }
 
-static int feed_points_impl(plv_ctx *ctx, LineTracker *T, double timestamp, const double *vps, int np, const float *pts, const uint64_t *pids, const double *K8);
+static int feed_points_impl(plv_ctx *ctx, LineTracker *T, double timestamp, const double *vps, int np, const float *pts, const uint64_t *pids, const double *K8,
+                            int cam_model);
 int plv_line_tracker_feed_points(plv_ctx *ctx, double timestamp, const double *vps, int np, const float *pts, const uint64_t *pids) {
   if (!ctx || !vps || np < 0 || (np > 0 && (!pts || !pids))) return PLV_E_BADARG;
   (void)hipSetDevice(ctx->device);
   LineTracker *T = ltr(ctx);
   std::lock_guard<std::mutex> lk(T->mtx);
-  return feed_points_impl(ctx, T, timestamp, vps, np, pts, pids, ctx->cfg.intrinsics);
+  return feed_points_impl(ctx, T, timestamp, vps, np, pts, pids, ctx->cfg.intrinsics, ctx->cam_model);
 }
 
 // TrackLSD::feed_monocular after the histogram equalisation, on the tracker state of T (the caller holds T->mtx or is the worker).
 // K8: the camera model of feed_measurement's time (REF: UpdaterCamera.cpp:77-116 runs before try_update refreshes it,
 // StateHelper.cpp:163-168) — a snapshot when the call runs on the worker next to the point update.
-static int feed_points_impl(plv_ctx *ctx, LineTracker *T, double timestamp, const double *vps, int np, const float *pts, const uint64_t *pids, const double *K8) {
+static int feed_points_impl(plv_ctx *ctx, LineTracker *T, double timestamp, const double *vps, int np, const float *pts, const uint64_t *pids, const double *K8,
+                            int cam_model) {
   plv::HostPhase ph_all("line_tracker_feed: whole call");
   std::vector<float> lines;
   if (T->cached_which == PLV_PYR_CUR && T->cached_fed == plv_front_fed_count(ctx)) {
@@ -695,10 +698,10 @@ static int feed_points_impl(plv_ctx *ctx, LineTracker *T, double timestamp, cons
       if (match[q] >= 0) fid[q] = (uint64_t)(int)T->ids_last[match[q]];  // REF :153-158 (`int id`)
     if (timing) F_match = std::chrono::steady_clock::now();
     // CamBase::undistort_line: both end points through undistort_f.  A few dozen points: the arithmetic of undistort_kernel
-    // (radtan_core.hpp, bit-identical on host and device) run here instead of a launch + copy + synchronisation round trip
+    // (radtan_core.hpp / cam_models.hpp, one source on host and device) run here instead of a launch + copy + synchronisation round trip
     std::vector<float> un(4 * (size_t)std::max(nk, 1));
     for (int q = 0; q < 2 * nk; ++q)
-      undistort_radtan(K8, fl[2 * (size_t)q], fl[2 * (size_t)q + 1], un[2 * (size_t)q], un[2 * (size_t)q + 1]);
+      undistort_model(cam_model, K8, fl[2 * (size_t)q], fl[2 * (size_t)q + 1], un[2 * (size_t)q], un[2 * (size_t)q + 1]);
     if (timing) F_und = std::chrono::steady_clock::now();
     for (int q = 0; q < nk; ++q) {
       const int D = plv_line_classification(fl.data() + 4 * q, vps);
@@ -746,7 +749,7 @@ int plv_line_tracker_feed_async_points(plv_ctx *ctx, double timestamp, const dou
   const bool detecting = !T->walk_on_device && T->worker.joinable() && T->pending_which == PLV_PYR_CUR && T->pending_fed == plv_front_fed_count(ctx);
   if (!detecting) {  // no detection of this frame on the worker: nothing to overlap with, and the detector's HIP calls stay on this thread
     F.pool_on = false;
-    F.rc = feed_points_impl(ctx, T, timestamp, vps, np, F.pts.data(), F.pids.data(), ctx->cfg.intrinsics);
+    F.rc = feed_points_impl(ctx, T, timestamp, vps, np, F.pts.data(), F.pids.data(), ctx->cfg.intrinsics, ctx->cam_model);
     return F.rc;
   }
   g_feed_impl = feed_points_impl;
@@ -754,6 +757,7 @@ int plv_line_tracker_feed_async_points(plv_ctx *ctx, double timestamp, const dou
   F.timestamp = timestamp;
   std::copy(vps, vps + 6, F.vps);
   std::copy(ctx->cfg.intrinsics, ctx->cfg.intrinsics + 8, F.K8);
+  F.cam_model = ctx->cam_model;
   F.rc = PLV_OK;
   {
     std::lock_guard<std::mutex> lk2(T->jm);

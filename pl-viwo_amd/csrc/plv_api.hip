@@ -219,6 +219,12 @@ int plv_set_camera_intrinsics(plv_ctx *ctx, const double *K8) {
   return PLV_OK;
 }
 
+int plv_set_camera_model(plv_ctx *ctx, int model) {
+  if (!ctx || (model != PLV_CAM_RADTAN && model != PLV_CAM_EQUIDISTANT)) return PLV_E_BADARG;
+  ctx->cam_model = model;  // read with cfg.intrinsics (cam_of, the Jacobian staging, the line feed)
+  return PLV_OK;
+}
+
 int plv_ctx_create(const plv_config *cfg, plv_ctx **out) {
   if (!cfg || !out) {
     set_last_error("plv_ctx_create: null argument");

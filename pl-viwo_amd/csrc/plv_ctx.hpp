@@ -442,6 +442,8 @@ struct ProfScope {
 
 struct plv_ctx {
   plv_config cfg;
+  // camera model of cfg.intrinsics (PLV_CAM_RADTAN / PLV_CAM_EQUIDISTANT, plv_set_camera_model): read wherever cfg.intrinsics is
+  int cam_model = 0;
   int device = 0;
   hipStream_t stream = nullptr;
   plv::Profiler prof;

@@ -415,8 +415,10 @@ class SystemManager:
             raise OptionsError("replay driver: one camera (cam.max_n: 1, use_stereo: false)")
         if e.cam.enabled and e.cam.max_slam != 0 and e.cam.feat_rep != 0:
             raise OptionsError("replay driver: in-state landmarks (cam.max_slam > 0) are driven in the GLOBAL_3D representation only")
-        if e.cam.enabled and e.cam.distortion_model[0] != "radtan":
-            raise OptionsError("only the radtan camera model is built (SURVEY §8 a7)")
+        cam_model = e.cam.distortion_model[0] if e.cam.enabled else "radtan"
+        if cam_model != "radtan" and cam_model not in getattr(context_factory or Context, "CAMERA_MODELS", ()):
+            raise OptionsError(f"camera model {cam_model!r}: this context builds the radtan model only" if cam_model == "equidistant"
+                               else f"camera model {cam_model!r}: the models built are radtan and equidistant")
         if e.use_imu_cov and not e.use_pol_cov and not e.use_imu_res:
             # CamHelper.cpp:217-224 reads state->cpis.at(tm + dt), a record that only get_interpolated_pose_imu creates (use_imu_res)
             raise OptionsError("est.use_imu_cov needs est.use_imu_res (the CPI records behind the observation poses)")
@@ -437,6 +439,8 @@ class SystemManager:
         cfg.max_rows_per_feat = max(cfg.max_rows_per_feat, 2 * max_obs)
         cfg.device = device
         self.ctx = (context_factory or Context)(cfg)
+        if cam_model != "radtan":
+            self.ctx.set_camera_model(cam_model)          # State.cpp:74-80 (CamEqui)
         import os
         if os.environ.get("PLV_AHEAD") and hasattr(self.ctx, "tracker_detect_ahead"):
             self.ctx.tracker_detect_ahead(int(os.environ["PLV_AHEAD"]))
