@@ -959,7 +959,7 @@ void plv_jpl_left_update(int n, double *q, const double *dth, double *R);
 
 
 /* ---------------------------------------------------------------------------------------------
- * Trajectory I/O and the ATE evaluator: the accuracy half of the metric.
+ * Trajectory I/O and the evaluator (ATE, 2-D ATE, RPE, NEES): the accuracy half of the metric.
  * Poses are [n][7] = tx ty tz qx qy qz qw (JPL quaternion), as the reference logs and loads them.
  * ------------------------------------------------------------------------------------------- */
 /* State_Logger's header line and one `t x y z qx qy qz qw [12 covariance terms]` line (REF: PL-VIWO/src/utils/
@@ -988,6 +988,31 @@ typedef struct plv_stats { double min, max, median, mean, rmse, std, ninetynine;
  * ori_err[i] = |log_so3(R_aligned^T R_gt)| in degrees, pos_err[i] = |p_gt - p_aligned|.  Every output is nullable. */
 int plv_traj_ate(plv_ctx *ctx, int method, int n, const double *est_poses, const double *gt_poses, int n_aligned, double *R,
                  double *t, double *s, double *aligned, double *ori_err, double *pos_err, plv_stats *ori, plv_stats *pos);
+/* ResultTrajectory::calculate_ate_2d (REF: ResultTrajectory.cpp:99-137): the same alignment and aligned estimate as plv_traj_ate,
+ * ori_err[i] = the z component of log_so3(R_aligned^T R_gt) in degrees, signed; pos_err[i] = the norm of the x-y difference.
+ * ori_err / pos_err [n] and the two statistics are nullable. */
+int plv_traj_ate_2d(plv_ctx *ctx, int method, int n, const double *est_poses, const double *gt_poses, int n_aligned, double *ori_err,
+                    double *pos_err, plv_stats *ori, plv_stats *pos);
+/* ResultTrajectory::calculate_rpe (REF: ResultTrajectory.cpp:139-239) on n associated pose pairs, which the call aligns itself
+ * (est to gt by `method`, as the ctor does :56).  The accumulated distance along the ground truth is the reference's recurrence
+ * acc[i] = acc[i-1] + |p_i - p_(i-1)| in that order.  For each of the n_seg lengths (metres) and every start pose, end_idx is what
+ * compute_comparison_indices_length returns (REF: ResultTrajectory.h:169-198): the first i >= start that minimises
+ * |acc[i] - (acc[start] + length)| if that error is strictly below 0.5 m, else -1; an earlier index wins a tie.  The error of the
+ * pair is T_error = inv(T_m1_m2) T_c1_c2 rotated into the world by the end pose (:180-228): pos_err = |translation|, ori_err =
+ * |log_so3| in degrees.  end_idx, ori_err, pos_err are [n_seg][n] (the errors are written only where end_idx >= 0), n_valid, ori and
+ * pos are [n_seg], the valid values in start order; a length without a segment leaves its statistics zero and one valid value
+ * gives NaN std / ninetynine, as Statistics.h does.  Every output is nullable.  The ground-truth positions must be finite.
+ * PLV_E_CAPACITY when n_seg * n exceeds 2^31 - 1. */
+int plv_traj_rpe(plv_ctx *ctx, int method, int n, const double *est_poses, const double *gt_poses, int n_seg, const double *segments,
+                 int *end_idx, double *ori_err, double *pos_err, int *n_valid, plv_stats *ori, plv_stats *pos);
+/* ResultTrajectory::calculate_nees (REF: ResultTrajectory.cpp:241-286) on n associated pose pairs; the call aligns the ground truth
+ * to the estimate itself (the ctor's second alignment :57,76-77).  cov_ori / cov_pos [n][9] are the estimate's 3x3 marginals as
+ * plv_traj_load fills them.  e = -log_so3(R_gt_in_est R_est^T), nees_ori[i] = e^T cov_ori^-1 e; nees_pos[i] the same form with
+ * p_gt_in_est - p_est; the inverse is by cofactors, as Eigen's.  A pose whose either value is NaN is left out of n_valid and the
+ * statistics, and both its outputs are NaN (:267-270).  nees_ori, nees_pos, n_valid, ori, pos are nullable.  PLV_E_BADARG when
+ * cov_ori or cov_pos is NULL (the reference warns and returns, :244-250). */
+int plv_traj_nees(plv_ctx *ctx, int method, int n, const double *est_poses, const double *gt_poses, const double *cov_ori,
+                  const double *cov_pos, double *nees_ori, double *nees_pos, int *n_valid, plv_stats *ori, plv_stats *pos);
 
 
 /* ---------------------------------------------------------------------------------------------

@@ -166,6 +166,10 @@ def load_library():
         "plv_traj_associate": (C.c_int, [C.c_double, C.c_double, C.c_int, dp, C.c_int, dp, ip, ip, ip]),
         "plv_traj_ate": (C.c_int, [vp, C.c_int, C.c_int, dp, dp, C.c_int, dp, dp, dp, dp, dp, dp, C.POINTER(PlvStats),
                                    C.POINTER(PlvStats)]),
+        "plv_traj_ate_2d": (C.c_int, [vp, C.c_int, C.c_int, dp, dp, C.c_int, dp, dp, C.POINTER(PlvStats), C.POINTER(PlvStats)]),
+        "plv_traj_rpe": (C.c_int, [vp, C.c_int, C.c_int, dp, dp, C.c_int, dp, ip, dp, dp, ip, C.POINTER(PlvStats),
+                                   C.POINTER(PlvStats)]),
+        "plv_traj_nees": (C.c_int, [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, ip, C.POINTER(PlvStats), C.POINTER(PlvStats)]),
         "plv_cpi_poses": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvCpiTable), C.c_int, dp, dp, dp, u8p]),
         "plv_camera_update_list": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, u64p, ip, dp, fp, fp, dp]),
         "plv_slam_marg_flags": (C.c_int, [vp, C.c_int, u64p, ip, u8p]),
@@ -1107,6 +1111,45 @@ class Context:
         self._chk(self.lib.plv_traj_ate(self.h, ALIGN[method], n, _dp(est), _dp(gt), n_aligned, _dp(R), _dp(t), C.byref(s), _dp(al),
                                         _dp(oe), _dp(pe), C.byref(so), C.byref(sp)))
         return dict(R=R, t=t, s=s.value, aligned=al, ori_err=oe, pos_err=pe, ori=so.as_dict(), pos=sp.as_dict())
+
+    def traj_ate_2d(self, est, gt, method="posyaw", n_aligned=-1):
+        """ResultTrajectory::calculate_ate_2d: signed yaw error (deg) and x-y position error per pose."""
+        est, gt = _c64(est), _c64(gt)
+        n = len(est)
+        oe, pe = np.zeros(n), np.zeros(n)
+        so, sp = PlvStats(), PlvStats()
+        self._chk(self.lib.plv_traj_ate_2d(self.h, ALIGN[method], n, _dp(est), _dp(gt), n_aligned, _dp(oe), _dp(pe), C.byref(so),
+                                           C.byref(sp)))
+        return dict(ori_err=oe, pos_err=pe, ori=so.as_dict(), pos=sp.as_dict())
+
+    def traj_rpe(self, est, gt, segments, method="posyaw"):
+        """ResultTrajectory::calculate_rpe: one dict per segment length (metres) with end_idx [n] (-1 = no segment starts there),
+        ori_err (deg) / pos_err [n] (NaN where end_idx < 0), n = the number of segments, and their statistics."""
+        est, gt, seg = _c64(est), _c64(gt), _c64(segments).reshape(-1)
+        n, ns = len(est), len(seg)
+        end = np.full((ns, n), -1, dtype=np.int32)
+        oe, pe = np.full((ns, n), np.nan), np.full((ns, n), np.nan)
+        nv = np.zeros(max(ns, 1), dtype=np.int32)
+        so, sp = (PlvStats * max(ns, 1))(), (PlvStats * max(ns, 1))()
+        self._chk(self.lib.plv_traj_rpe(self.h, ALIGN[method], n, _dp(est), _dp(gt), ns, _dp(seg), _ip(end), _dp(oe), _dp(pe), _ip(nv),
+                                        so, sp))
+        return [dict(length=float(seg[k]), end_idx=end[k], ori_err=oe[k], pos_err=pe[k], n=int(nv[k]), ori=so[k].as_dict(),
+                     pos=sp[k].as_dict()) for k in range(ns)]
+
+    def traj_nees(self, est, gt, cov_ori, cov_pos, method="posyaw"):
+        """ResultTrajectory::calculate_nees with the estimate's logged 3x3 marginals ([n][3][3], as traj_load returns them);
+        None for a covariance is refused by the library.  nees_ori / nees_pos are NaN where the pose was skipped; n = the rest."""
+        est, gt = _c64(est), _c64(gt)
+        n = len(est)
+        co = _c64(cov_ori).reshape(-1) if cov_ori is not None else None
+        cp = _c64(cov_pos).reshape(-1) if cov_pos is not None else None
+        if (co is not None and co.size != 9 * n) or (cp is not None and cp.size != 9 * n):
+            raise ValueError("cov_ori / cov_pos must hold one 3x3 block per pose")
+        no, npos, nv = np.zeros(n), np.zeros(n), C.c_int()
+        so, sp = PlvStats(), PlvStats()
+        self._chk(self.lib.plv_traj_nees(self.h, ALIGN[method], n, _dp(est), _dp(gt), _dp(co), _dp(cp), _dp(no), _dp(npos), C.byref(nv),
+                                         C.byref(so), C.byref(sp)))
+        return dict(nees_ori=no, nees_pos=npos, n=nv.value, ori=so.as_dict(), pos=sp.as_dict())
 
     def cpi_poses(self, st, cpi, t_q):
         t_q = _f64(t_q)

@@ -6,6 +6,10 @@
 //   AlignUtils::get_best_yaw / get_mean            REF: open_vins/ov_eval/src/alignment/AlignUtils.h:53-72
 //   AlignTrajectory::align_*                       REF: open_vins/ov_eval/src/alignment/AlignTrajectory.cpp:26-166
 //   ResultTrajectory ctor / calculate_ate          REF: open_vins/ov_eval/src/calc/ResultTrajectory.cpp:26-121
+//   ResultTrajectory::calculate_ate_2d             REF: open_vins/ov_eval/src/calc/ResultTrajectory.cpp:99-137
+//   ResultTrajectory::calculate_rpe                REF: open_vins/ov_eval/src/calc/ResultTrajectory.cpp:139-239
+//   compute_comparison_indices_length              REF: open_vins/ov_eval/src/calc/ResultTrajectory.h:169-198
+//   ResultTrajectory::calculate_nees               REF: open_vins/ov_eval/src/calc/ResultTrajectory.cpp:241-286
 //   Statistics::calculate                          REF: open_vins/ov_eval/src/utils/Statistics.h:72-119
 //
 // File parsing, association and the order statistics are host logic; everything that touches every pose (the two
@@ -145,7 +149,9 @@ __device__ void log_so3_dev(const double *R, double *w) {  // quat_ops.h:273-313
   w[0] = mag * (R32 - R23), w[1] = mag * (R13 - R31), w[2] = mag * (R21 - R12);
 }
 
-// ResultTrajectory ctor :72-82 (the aligned estimate) + calculate_ate :91-115 (errors), thread per pose
+// ResultTrajectory ctor :72-82 (the aligned estimate) + calculate_ate :91-115 (errors), thread per pose.  TWO_D is calculate_ate_2d
+// (:106-115): the signed z component of the log and the norm of the x-y difference; the 3-D instantiation is the kernel as it was.
+template <bool TWO_D>
 __global__ void __launch_bounds__(256) traj_ate_kernel(int n, const double *__restrict__ est, const double *__restrict__ gt, Align A,
                                                        double *__restrict__ aligned, double *__restrict__ ori_err,
                                                        double *__restrict__ pos_err) {
@@ -167,15 +173,148 @@ __global__ void __launch_bounds__(256) traj_ate_kernel(int n, const double *__re
 #pragma unroll
     for (int c = 0; c < 3; ++c) eR[3 * r + c] = Re[r] * Rg[c] + Re[3 + r] * Rg[3 + c] + Re[6 + r] * Rg[6 + c];  // Re^T Rg
   log_so3_dev(eR, w);
-  ori_err[i] = 180.0 / M_PI * sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
   const double dx = g[0] - p[0], dy = g[1] - p[1], dz = g[2] - p[2];
-  pos_err[i] = sqrt(dx * dx + dy * dy + dz * dz);
+  if constexpr (TWO_D) {
+    ori_err[i] = 180.0 / M_PI * w[2];
+    pos_err[i] = sqrt(dx * dx + dy * dy);
+  } else {
+    ori_err[i] = 180.0 / M_PI * sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+    pos_err[i] = sqrt(dx * dx + dy * dy + dz * dz);
+  }
   if (aligned) {
 #pragma unroll
     for (int r = 0; r < 3; ++r) aligned[7 * (size_t)i + r] = p[r];
 #pragma unroll
     for (int r = 0; r < 4; ++r) aligned[7 * (size_t)i + 3 + r] = q[r];
   }
+}
+
+// |acc[i] - (acc[start] + L)| with the reference's grouping (ResultTrajectory.h:184): ties fall where its scan lets them fall
+__device__ __forceinline__ double seg_err(const double *__restrict__ acc, int i, double target) { return fabs(acc[i] - target); }
+
+// compute_comparison_indices_length (ResultTrajectory.h:169-198) + the pair error of calculate_rpe (.cpp:180-228), one thread per
+// (segment length, start).  The reference scans i = start .. n-1 and keeps the first i whose error is strictly below the best so
+// far, beginning at max_dist_diff: the first minimiser of e(i) = |acc[i] - target|, if that minimum is below the limit.  acc is
+// non-decreasing and rounding is monotone, so e(i) as computed never rises before j = the first acc[j] >= target and never falls
+// after it.  The minimum right of j is therefore e(j) at j itself; left of j it is e(j - 1), first reached at the first i with
+// e(i) <= e(j - 1) (a standing vehicle repeats acc values, and a subtraction may round neighbours to one error): a second
+// bisection over the non-increasing stretch.  The left candidate precedes j, so it wins a tie.  A latency-bound gather: ~2 log2(n)
+// dependent loads of acc through the cache, then four poses; no LDS, no atomics.
+__global__ void __launch_bounds__(256) traj_rpe_kernel(int n, int n_seg, const double *__restrict__ acc, const double *__restrict__ seg,
+                                                       double max_dist_diff, const double *__restrict__ aligned,
+                                                       const double *__restrict__ gt, int *__restrict__ end_idx,
+                                                       double *__restrict__ ori_err, double *__restrict__ pos_err) {
+  const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= (size_t)n_seg * n) return;
+  const int start = (int)(k % n);
+  const double target = acc[start] + seg[k / n];
+  int lo = start, hi = n;  // j: the first index in [start, n) with acc[j] >= target, n when there is none
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (acc[mid] >= target)
+      hi = mid;
+    else
+      lo = mid + 1;
+  }
+  const int j = lo;
+  int best = -1;
+  double best_err = max_dist_diff;
+  if (j > start) {
+    const double e_left = seg_err(acc, j - 1, target);
+    lo = start, hi = j - 1;
+    while (lo < hi) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (seg_err(acc, mid, target) <= e_left)
+        hi = mid;
+      else
+        lo = mid + 1;
+    }
+    if (e_left < best_err) best = lo, best_err = e_left;
+  }
+  if (j < n) {
+    const double e_right = seg_err(acc, j, target);
+    if (e_right < best_err) best = j;
+  }
+  end_idx[k] = best;
+  if (best < 0) return;
+  // T_c1_c2 = Inv_se3(T_c1) T_c2 with T = [quat_2_Rot(q)^T, p] (:183-194), likewise T_m1_m2 of the ground truth (:198-209)
+  const double *c1 = aligned + 7 * (size_t)start, *c2 = aligned + 7 * (size_t)best, *m1 = gt + 7 * (size_t)start, *m2 = gt + 7 * (size_t)best;
+  double Q1[9], Q2[9], G1[9], G2[9], Rc[9], Rm[9], tc[3], tm[3];
+  quat_2_rot(c1 + 3, Q1);
+  quat_2_rot(c2 + 3, Q2);
+  quat_2_rot(m1 + 3, G1);
+  quat_2_rot(m2 + 3, G2);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      Rc[3 * r + c] = Q1[3 * r] * Q2[3 * c] + Q1[3 * r + 1] * Q2[3 * c + 1] + Q1[3 * r + 2] * Q2[3 * c + 2];  // Q1 Q2^T
+      Rm[3 * r + c] = G1[3 * r] * G2[3 * c] + G1[3 * r + 1] * G2[3 * c + 1] + G1[3 * r + 2] * G2[3 * c + 2];
+    }
+    // Inv_se3's translation -R^T p, added last by the 4x4 product
+    tc[r] = (Q1[3 * r] * c2[0] + Q1[3 * r + 1] * c2[1] + Q1[3 * r + 2] * c2[2]) + -(Q1[3 * r] * c1[0] + Q1[3 * r + 1] * c1[1] + Q1[3 * r + 2] * c1[2]);
+    tm[r] = (G1[3 * r] * m2[0] + G1[3 * r + 1] * m2[1] + G1[3 * r + 2] * m2[2]) + -(G1[3 * r] * m1[0] + G1[3 * r + 1] * m1[1] + G1[3 * r + 2] * m1[2]);
+  }
+  // T_error_in_c2 = Inv_se3(T_m1_m2) T_c1_c2 (:213), then into the world by the end pose's rotation Q2^T (:215-222)
+  double Re[9], te[3], RQ[9], Rw[9], tw[3], w[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Re[3 * r + c] = Rm[r] * Rc[c] + Rm[3 + r] * Rc[3 + c] + Rm[6 + r] * Rc[6 + c];  // Rm^T Rc
+    te[r] = (Rm[r] * tc[0] + Rm[3 + r] * tc[1] + Rm[6 + r] * tc[2]) + -(Rm[r] * tm[0] + Rm[3 + r] * tm[1] + Rm[6 + r] * tm[2]);
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) RQ[3 * r + c] = Re[3 * r] * Q2[c] + Re[3 * r + 1] * Q2[3 + c] + Re[3 * r + 2] * Q2[6 + c];  // Re Q2
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Rw[3 * r + c] = Q2[r] * RQ[c] + Q2[3 + r] * RQ[3 + c] + Q2[6 + r] * RQ[6 + c];  // Q2^T (Re Q2)
+    tw[r] = Q2[r] * te[0] + Q2[3 + r] * te[1] + Q2[6 + r] * te[2];
+  }
+  log_so3_dev(Rw, w);
+  pos_err[k] = sqrt(tw[0] * tw[0] + tw[1] * tw[1] + tw[2] * tw[2]);
+  ori_err[k] = 180.0 / M_PI * sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+}
+
+// e^T C^-1 e with the 3x3 inverse by cofactors over the determinant, as Eigen's fixed-size inverse() forms it
+__device__ double quad_form_inv3(const double *__restrict__ m, const double *e) {
+  auto cof = [&](int i, int j) {
+    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+    return m[3 * i1 + j1] * m[3 * i2 + j2] - m[3 * i1 + j2] * m[3 * i2 + j1];
+  };
+  const double c0[3] = {cof(0, 0), cof(1, 0), cof(2, 0)};
+  const double invdet = 1.0 / (c0[0] * m[0] + c0[1] * m[3] + c0[2] * m[6]);
+  double v[3] = {0, 0, 0};  // e^T inv, inv(r, c) = cof(c, r) * invdet
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) v[c] += e[r] * ((r == 0 ? c0[c] : cof(c, r)) * invdet);
+  return v[0] * e[0] + v[1] * e[1] + v[2] * e[2];
+}
+
+// calculate_nees :253-275, thread per pose: gt_in_est is the ground truth aligned to the estimate (the ctor's second alignment).
+// A pose whose either value is NaN is skipped by the reference (:267-270): both outputs are NaN there.
+__global__ void __launch_bounds__(256) traj_nees_kernel(int n, const double *__restrict__ est, const double *__restrict__ gt_in_est,
+                                                        const double *__restrict__ cov_ori, const double *__restrict__ cov_pos,
+                                                        double *__restrict__ nees_ori, double *__restrict__ nees_pos) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double *e = est + 7 * (size_t)i, *g = gt_in_est + 7 * (size_t)i;
+  double Rg[9], Re[9], eR[9], w[3];
+  quat_2_rot(g + 3, Rg);
+  quat_2_rot(e + 3, Re);
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) eR[3 * r + c] = Rg[3 * r] * Re[3 * c] + Rg[3 * r + 1] * Re[3 * c + 1] + Rg[3 * r + 2] * Re[3 * c + 2];  // Rg Re^T
+  log_so3_dev(eR, w);
+  const double eo[3] = {-w[0], -w[1], -w[2]}, ep[3] = {g[0] - e[0], g[1] - e[1], g[2] - e[2]};
+  double no = quad_form_inv3(cov_ori + 9 * (size_t)i, eo), np = quad_form_inv3(cov_pos + 9 * (size_t)i, ep);
+  if (isnan(no) || isnan(np)) no = np = NAN;
+  nees_ori[i] = no;
+  nees_pos[i] = np;
 }
 
 // ---------------------------------------------------------------------------------------- host 3x3 helpers
@@ -507,40 +646,171 @@ static int device_align(plv_ctx *ctx, int method, int n, const double *d_est, co
   return PLV_OK;
 }
 
-int plv_traj_ate(plv_ctx *ctx, int method, int n, const double *est_poses, const double *gt_poses, int n_aligned, double *R_out,
-                 double *t_out, double *s_out, double *aligned, double *ori_err, double *pos_err, plv_stats *ori, plv_stats *pos) {
-  if (!ctx || !est_poses || !gt_poses || n < 1) return PLV_E_BADARG;
+// The evaluator's common front: uploads the n pose pairs, aligns `from` to `to` (AlignTrajectory::align_trajectory(from, to, ...)) and
+// runs traj_ate_kernel over them, which leaves `from` expressed in `to`'s frame (the ctor's loop :72-82) and the per-pose errors on
+// the device.  extra_bytes more of the evaluation buffer are reserved behind them for the caller's own kernel.
+struct EvalDev {
+  double *from, *to, *aligned, *ori_err, *pos_err;
+  void *extra;
+};
+static int align_on_device(plv_ctx *ctx, int method, bool two_d, int n, const double *from, const double *to, int n_aligned,
+                           size_t extra_bytes, Align *A, EvalDev *d) {
   (void)hipSetDevice(ctx->device);
   auto *us = plv_update_state(ctx);
   const size_t bytes = (size_t)n * 7 * sizeof(double);
-  TRY(us->eval.reserve(bytes * 3 + (size_t)n * 2 * sizeof(double)));
-  double *d_est = us->eval.as<double>(), *d_gt = d_est + (size_t)n * 7, *d_al = d_gt + (size_t)n * 7, *d_oe = d_al + (size_t)n * 7,
-         *d_pe = d_oe + n;
-  PLV_HIP_CHECK(plv::memcpy_async(d_est, est_poses, bytes, hipMemcpyHostToDevice, ctx->stream));
-  PLV_HIP_CHECK(plv::memcpy_async(d_gt, gt_poses, bytes, hipMemcpyHostToDevice, ctx->stream));
-  Align A{};
-  TRY(device_align(ctx, method, n, d_est, d_gt, est_poses, gt_poses, n_aligned, A.R, A.t, &A.s));
+  TRY(us->eval.reserve(bytes * 3 + (size_t)n * 2 * sizeof(double) + extra_bytes));
+  d->from = us->eval.as<double>(), d->to = d->from + (size_t)n * 7, d->aligned = d->to + (size_t)n * 7;
+  d->ori_err = d->aligned + (size_t)n * 7, d->pos_err = d->ori_err + n, d->extra = d->pos_err + n;
+  PLV_HIP_CHECK(plv::memcpy_async(d->from, from, bytes, hipMemcpyHostToDevice, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(d->to, to, bytes, hipMemcpyHostToDevice, ctx->stream));
+  *A = Align{};
+  TRY(device_align(ctx, method, n, d->from, d->to, from, to, n_aligned, A->R, A->t, &A->s));
   double q[4];
-  h_rot_2_quat(A.R, q);
-  A.qinv[0] = -q[0], A.qinv[1] = -q[1], A.qinv[2] = -q[2], A.qinv[3] = q[3];
+  h_rot_2_quat(A->R, q);
+  A->qinv[0] = -q[0], A->qinv[1] = -q[1], A->qinv[2] = -q[2], A->qinv[3] = q[3];
   {
     ProfScope ps(ctx->prof, "traj_ate_kernel", ctx->stream);
-    hipLaunchKernelGGL(traj_ate_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, d_est, d_gt, A, d_al, d_oe, d_pe);
+    hipLaunchKernelGGL(two_d ? traj_ate_kernel<true> : traj_ate_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n,
+                       d->from, d->to, *A, d->aligned, d->ori_err, d->pos_err);
   }
   PLV_HIP_CHECK(hipGetLastError());
+  return PLV_OK;
+}
+
+// the per-pose errors of align_on_device back on the host, and their statistics
+static int collect_errors(plv_ctx *ctx, int n, const EvalDev &d, double *aligned, double *ori_err, double *pos_err, plv_stats *ori,
+                          plv_stats *pos) {
   std::vector<double> oe(n), pe(n);
-  PLV_HIP_CHECK(plv::memcpy_async(oe.data(), d_oe, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  PLV_HIP_CHECK(plv::memcpy_async(pe.data(), d_pe, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (aligned) PLV_HIP_CHECK(plv::memcpy_async(aligned, d_al, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(oe.data(), d.ori_err, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(pe.data(), d.pos_err, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (aligned) PLV_HIP_CHECK(plv::memcpy_async(aligned, d.aligned, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
   ctx->prof.collect();
-  if (R_out) std::copy(A.R, A.R + 9, R_out);
-  if (t_out) std::copy(A.t, A.t + 3, t_out);
-  if (s_out) *s_out = A.s;
   if (ori_err) std::copy(oe.begin(), oe.end(), ori_err);
   if (pos_err) std::copy(pe.begin(), pe.end(), pos_err);
   if (ori) stats_of(oe, ori);
   if (pos) stats_of(pe, pos);
+  return PLV_OK;
+}
+
+int plv_traj_ate(plv_ctx *ctx, int method, int n, const double *est_poses, const double *gt_poses, int n_aligned, double *R_out,
+                 double *t_out, double *s_out, double *aligned, double *ori_err, double *pos_err, plv_stats *ori, plv_stats *pos) {
+  if (!ctx || !est_poses || !gt_poses || n < 1) return PLV_E_BADARG;
+  Align A;
+  EvalDev d;
+  TRY(align_on_device(ctx, method, false, n, est_poses, gt_poses, n_aligned, 0, &A, &d));
+  TRY(collect_errors(ctx, n, d, aligned, ori_err, pos_err, ori, pos));
+  if (R_out) std::copy(A.R, A.R + 9, R_out);
+  if (t_out) std::copy(A.t, A.t + 3, t_out);
+  if (s_out) *s_out = A.s;
+  return PLV_OK;
+}
+
+int plv_traj_ate_2d(plv_ctx *ctx, int method, int n, const double *est_poses, const double *gt_poses, int n_aligned, double *ori_err,
+                    double *pos_err, plv_stats *ori, plv_stats *pos) {
+  if (!ctx || !est_poses || !gt_poses || n < 1) return PLV_E_BADARG;
+  Align A;
+  EvalDev d;
+  TRY(align_on_device(ctx, method, true, n, est_poses, gt_poses, n_aligned, 0, &A, &d));
+  return collect_errors(ctx, n, d, nullptr, ori_err, pos_err, ori, pos);
+}
+
+int plv_traj_rpe(plv_ctx *ctx, int method, int n, const double *est_poses, const double *gt_poses, int n_seg, const double *segments,
+                 int *end_idx, double *ori_err, double *pos_err, int *n_valid, plv_stats *ori, plv_stats *pos) {
+  if (!ctx || !est_poses || !gt_poses || n < 1 || n_seg < 0 || (n_seg && !segments)) return PLV_E_BADARG;
+  const size_t total = (size_t)n_seg * n;
+  if (total > (size_t)0x7fffffff) {
+    set_last_error("plv_traj_rpe: %d segment lengths x %d poses exceed 2^31 - 1 (start, length) pairs", n_seg, n);
+    return PLV_E_CAPACITY;
+  }
+  if (total == 0) return PLV_OK;
+  // accum_distances :143-149: the reference's recurrence in its order, one addition per pose (a re-associated prefix sum rounds
+  // differently and could move an end index at a tie or at the limit)
+  std::vector<double> acc(n);
+  acc[0] = 0;
+  for (int i = 1; i < n; ++i) {
+    const double *a = gt_poses + 7 * (size_t)i, *b = a - 7;
+    const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+    acc[i] = acc[i - 1] + std::sqrt(dx * dx + dy * dy + dz * dz);
+  }
+  Align A;
+  EvalDev d;
+  // behind the common block: acc [n], segments [n_seg], ori / pos errors [n_seg][n], end indices [n_seg][n]
+  const size_t extra = ((size_t)n + n_seg + 2 * total) * sizeof(double) + total * sizeof(int);
+  TRY(align_on_device(ctx, method, false, n, est_poses, gt_poses, -1, extra, &A, &d));
+  double *d_acc = static_cast<double *>(d.extra), *d_seg = d_acc + n, *d_oe = d_seg + n_seg, *d_pe = d_oe + total;
+  int *d_end = reinterpret_cast<int *>(d_pe + total);
+  PLV_HIP_CHECK(plv::memcpy_async(d_acc, acc.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(d_seg, segments, (size_t)n_seg * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  {
+    ProfScope ps(ctx->prof, "traj_rpe_kernel", ctx->stream);
+    hipLaunchKernelGGL(traj_rpe_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, n, n_seg, d_acc, d_seg,
+                       0.5 /* max_dist_diff :154 */, d.aligned, d.to, d_end, d_oe, d_pe);
+  }
+  PLV_HIP_CHECK(hipGetLastError());
+  std::vector<int> end(total);
+  std::vector<double> oe(total), pe(total);
+  PLV_HIP_CHECK(plv::memcpy_async(end.data(), d_end, total * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(oe.data(), d_oe, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(pe.data(), d_pe, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
+  ctx->prof.collect();
+  std::vector<double> vo, vp;
+  for (int s = 0; s < n_seg; ++s) {
+    vo.clear(), vp.clear();
+    for (size_t k = (size_t)s * n; k < (size_t)(s + 1) * n; ++k) {
+      if (end[k] < 0) continue;  // the device left ori / pos untouched there
+      vo.push_back(oe[k]);       // start order, as the reference pushes them; Statistics sorts a copy
+      vp.push_back(pe[k]);
+      if (ori_err) ori_err[k] = oe[k];
+      if (pos_err) pos_err[k] = pe[k];
+    }
+    if (n_valid) n_valid[s] = (int)vo.size();
+    if (ori) stats_of(vo, ori + s);
+    if (pos) stats_of(vp, pos + s);
+  }
+  if (end_idx) std::copy(end.begin(), end.end(), end_idx);
+  return PLV_OK;
+}
+
+int plv_traj_nees(plv_ctx *ctx, int method, int n, const double *est_poses, const double *gt_poses, const double *cov_ori,
+                  const double *cov_pos, double *nees_ori, double *nees_pos, int *n_valid, plv_stats *ori, plv_stats *pos) {
+  if (!ctx || !est_poses || !gt_poses || n < 1) return PLV_E_BADARG;
+  if (!cov_ori || !cov_pos) {  // the reference warns and returns (:244-250)
+    set_last_error("plv_traj_nees: the estimate carries no covariance (cov_ori / cov_pos is NULL)");
+    return PLV_E_BADARG;
+  }
+  Align A;
+  EvalDev d;
+  // the ctor's second alignment (:57): the ground truth aligned to the estimate, so `from` is gt and `aligned` is gt_poses_aignedtoEST
+  const size_t cov_bytes = (size_t)n * 9 * sizeof(double);
+  TRY(align_on_device(ctx, method, false, n, gt_poses, est_poses, -1, 2 * cov_bytes, &A, &d));
+  double *d_co = static_cast<double *>(d.extra), *d_cp = d_co + (size_t)n * 9;
+  PLV_HIP_CHECK(plv::memcpy_async(d_co, cov_ori, cov_bytes, hipMemcpyHostToDevice, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(d_cp, cov_pos, cov_bytes, hipMemcpyHostToDevice, ctx->stream));
+  {
+    // the 3-D errors of the alignment pass are not needed: their slots take the two NEES values
+    ProfScope ps(ctx->prof, "traj_nees_kernel", ctx->stream);
+    hipLaunchKernelGGL(traj_nees_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, d.to, d.aligned, d_co, d_cp, d.ori_err,
+                       d.pos_err);
+  }
+  PLV_HIP_CHECK(hipGetLastError());
+  std::vector<double> no(n), np(n);
+  PLV_HIP_CHECK(plv::memcpy_async(no.data(), d.ori_err, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(np.data(), d.pos_err, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
+  ctx->prof.collect();
+  std::vector<double> vo, vp;
+  for (int i = 0; i < n; ++i) {
+    if (std::isnan(no[i])) continue;  // the kernel sets both when either is NaN
+    vo.push_back(no[i]);
+    vp.push_back(np[i]);
+  }
+  if (nees_ori) std::copy(no.begin(), no.end(), nees_ori);
+  if (nees_pos) std::copy(np.begin(), np.end(), nees_pos);
+  if (n_valid) *n_valid = (int)vo.size();
+  if (ori) stats_of(vo, ori);
+  if (pos) stats_of(vp, pos);
   return PLV_OK;
 }
 

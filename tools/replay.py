@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Replays a dataset directory through the filter on the GPU and scores the trajectory (run_bag + ov_eval in one command).
 
-    python tools/replay.py CONFIG.yaml [--dataset DIR] [--gt FILE] [--align posyaw] [--out result.json]
+    python tools/replay.py CONFIG.yaml [--dataset DIR] [--gt FILE] [--align posyaw] [--rpe 8,16,24] [--nees] [--out result.json]
     python tools/replay.py --synthetic 12 [--out result.json]        # renders tests/synth_dataset.py first (CPU), then replays it
 """
 import argparse
@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--gt")
     ap.add_argument("--align", default="posyaw")
     ap.add_argument("--out")
+    ap.add_argument("--rpe", help="comma-separated segment lengths in metres: relative pose error per length (ov_eval's calculate_rpe)")
+    ap.add_argument("--nees", action="store_true", help="NEES of the logged pose covariance against the ground truth (calculate_nees)")
     ap.add_argument("--synthetic", type=float, default=0.0, help="seconds of the synthetic dataset to render and replay")
     ap.add_argument("--no-wheel", action="store_true")
     ap.add_argument("--no-lines", action="store_true")
@@ -55,11 +57,20 @@ def main():
     res = dict(config=a.config, wall_s=round(time.time() - t0, 2), stats=stats, poses_logged=len(times), trajectory=op.sys.path_trajectory)
     if a.gt and len(times) > 2:
         ctx = pkg.Context(pkg.default_config(752, 480))
-        et, ep = pkg.traj_load(op.sys.path_trajectory)[:2]
+        et, ep, co, cp = pkg.traj_load(op.sys.path_trajectory)
         gt_t, gt_p = pkg.traj_load(a.gt)[:2]
         ei, gi = pkg.traj_associate(et, gt_t)
         r = ctx.traj_ate(ep[ei], gt_p[gi], a.align)
         res["ate"] = dict(method=a.align, n=len(ei), pos=r["pos"], ori=r["ori"], length_m=pkg.traj_length(ep))
+        if a.rpe:
+            lengths = [float(x) for x in a.rpe.split(",") if x.strip()]
+            res["rpe"] = [dict(length_m=s["length"], n=s["n"], pos=s["pos"], ori=s["ori"])
+                          for s in ctx.traj_rpe(ep[ei], gt_p[gi], lengths, a.align)]
+        if a.nees:
+            if len(co) != len(et):
+                raise SystemExit(f"--nees: {len(co)} of {len(et)} logged poses carry a covariance")
+            r = ctx.traj_nees(ep[ei], gt_p[gi], co[ei], cp[ei], a.align)
+            res["nees"] = dict(method=a.align, n=r["n"], n_poses=len(ei), pos=r["pos"], ori=r["ori"])
         ctx.close()
     print(json.dumps(res, indent=1, default=float))
     if a.out:
