@@ -119,12 +119,17 @@ def _first_divergence(a, b, names):
     return None
 
 
-def value_drift(a, b, thr):
+def value_drift(a, b, thr, kind="points"):
     """How far apart the two runs' test values are, update by update: for every point update both runs recorded, the largest relative
     difference of a recorded value (condition number, depths, baseline ratio, reprojection error, chi2, residual norm) over the
     features that pass every test in both runs (a failing entry's values are often garbage: the depth of a point at infinity) —
     [(update, largest difference, which value, feature id)].  The first updates show the arithmetic alone (same state in, two
-    implementations, values of condition 1e3 .. 1e4); later ones the two filters' states drifting apart."""
+    implementations, values of condition 1e3 .. 1e4); later ones the two filters' states drifting apart.
+    kind="lines": the same over the line updates — chi2 and the norm of the projected residual (neither depends on the basis the null
+    space was projected with) of the lines that pass the gate in both runs; a line that fails it does so by orders of magnitude, on
+    the scale error the reference's triangulation leaves, and its chi2 says little about the arithmetic."""
+    if kind == "lines":
+        return _line_value_drift(a, b)
     names = ("n_obs", "triangulated", "reproj_px", "gate_passed", "tri_cond", "tri_depth", "refined_depth", "baseline_ratio", "chi2", "chi2_threshold", "res_norm")
     cols = [2, 4, 5, 6, 7, 8, 10]
     out = []
@@ -143,6 +148,26 @@ def value_drift(a, b, thr):
     return out
 
 
+def _line_value_drift(a, b):
+    names = ("chi2", "chi2_threshold", "res_norm")   # columns of Context.last_line_decisions
+    cols = [0, 2]
+    out = []
+    for k, (ra, rb) in enumerate(zip(a, b)):
+        if ra[0] != "lines" or rb[0] != "lines" or ra[7] is None or rb[7] is None:
+            continue
+        (ia, va), (ib, vb) = ra[7], rb[7]
+        common, xa, xb = np.intersect1d(ia, ib, return_indices=True)
+        keep = [q for q in range(len(common)) if all(len(t) == 1 and t[0][3] for t in (line_tests_of(va[xa[q]]), line_tests_of(vb[xb[q]])))]
+        if not keep:
+            continue
+        A, B = va[xa[keep]][:, cols], vb[xb[keep]][:, cols]
+        rel = np.abs(A - B) / np.maximum(np.maximum(np.abs(A), np.abs(B)), 1e-300)
+        rel[np.isnan(rel)] = np.inf   # (a passing line's residual norm is a number on both sides)
+        i, j = np.unravel_index(np.argmax(rel), rel.shape)
+        out.append((k, float(rel[i, j]), names[cols[j]], int(common[keep[i]])))
+    return out
+
+
 def check_tie(summary_, first_updates=3, first_tol=1e-8, window=10, factor=20.0):
     """What the replay tests assert about a divergence.  (1) It is a decision on values (triangulation / chi2), never on the
     measurements (pool), the sequence of updates or an update's status.  (2) The two implementations agree on identical input: over
@@ -155,6 +180,13 @@ def check_tie(summary_, first_updates=3, first_tol=1e-8, window=10, factor=20.0)
     early = [d for d in drift["all"] if d[0] < 2 * first_updates][:first_updates]
     if early and max(d[1] for d in early) > first_tol:
         bad.append(f"the first updates' values differ by {max(d[1] for d in early):.3g} (> {first_tol:g}): {early}")
+    # the same of the line values, over the first line updates that recorded any (point and wheel updates sit between them in the
+    # list, and a drive's first line updates find nothing to triangulate)
+    ld = summary_.get("line_value_drift", {})
+    first_l = set(ld.get("updates_with_values", [])[:2 * first_updates])
+    early_l = [d for d in ld.get("all", []) if d[0] in first_l][:first_updates]
+    if early_l and max(d[1] for d in early_l) > first_tol:
+        bad.append(f"the first updates' line values differ by {max(d[1] for d in early_l):.3g} (> {first_tol:g}): {early_l}")
     if fd is None:
         return bad
     if fd["split"] not in ("triangulation", "chi2"):
@@ -195,6 +227,7 @@ def summary(a, b, thr=None):
                                   ids_a_only=sorted(ia - ib)[:8], ids_b_only=sorted(ib - ia)[:8],
                                   accepted_a_only=sorted(acc_a - acc_b)[:8], accepted_b_only=sorted(acc_b - acc_a)[:8]))
     drift = value_drift(a, b, thr) if thr is not None else []
+    drift_l = value_drift(a, b, thr, kind="lines") if thr is not None else []
     fd = first_divergence(a, b, thr=thr)
     upto = fd["update"] if fd is not None and "update" in fd else n
     before = [d for d in drift if d[0] < upto]
@@ -203,6 +236,11 @@ def summary(a, b, thr=None):
                                  all=drift, first_updates=drift[:5], before_the_first_divergence=before[-5:],
                                  largest_before_the_first_divergence=max(before, key=lambda d: d[1]) if before else None,
                                  at_every_20th_update=drift[::20]),
+                line_value_drift=dict(what="the same per line update: chi2 and norm of the projected residual of the lines that pass the gate in both runs (update, difference, value, line)",
+                                      all=drift_l, updates_with_values=[k for k, (ra, rb) in enumerate(zip(a, b)) if ra[0] == rb[0] == "lines" and ra[7] is not None and rb[7] is not None],
+                                      first_updates=drift_l[:5], before_the_first_divergence=[d for d in drift_l if d[0] < upto][-5:],
+                                      largest_before_the_first_divergence=max((d for d in drift_l if d[0] < upto), key=lambda d: d[1], default=None),
+                                      at_every_20th_update=drift_l[::20]),
                 tie_check=None)
     out["tie_check"] = check_tie(out) if thr is not None else None
     # the first update whose pools agree and whose verdicts do not (a run that parted on a pool goes on: what splits it NEXT is the
@@ -218,7 +256,7 @@ def summary(a, b, thr=None):
             if ids:
                 out["first_decision_on_values"] = dict(update=k, kind=ra[0], frame=int(ra[1]), ids=ids[:8], tie=[tie_record(i, ra, rb, thr) for i in ids[:8]])
                 break
-    del out["value_drift"]["all"]
+    del out["value_drift"]["all"], out["line_value_drift"]["all"]
     return out
 
 

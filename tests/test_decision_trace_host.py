@@ -72,6 +72,48 @@ def test_a_pool_that_differs_is_reported_with_the_feature():
     assert s["updates_with_identical_decisions"] == 9
 
 
+def _lines(frame, ids, chi2s, norms, thr=9.49):
+    ids = np.array(ids, dtype=np.uint64)
+    vals = np.array([[c, thr, r] for c, r in zip(chi2s, norms)])   # Context.last_line_decisions: chi2, threshold, residual norm
+    acc = np.array([c < thr for c in chi2s], dtype=np.uint8)
+    return ("lines", frame, 0.05 * frame, len(ids), ids, acc, 0, (ids, vals), np.full(6, 1e-3))
+
+
+def test_line_values_are_compared_like_point_values():
+    """value_drift over the line records: chi2 and residual norm of the lines that pass the gate in both runs, a key of its own in
+    summary(), and check_tie's first-updates bound on them."""
+    def run(eps_chi2, eps_norm, eps_failing=0.0):
+        out = []
+        for f in range(1, 12):
+            out.append(_points(f, [10 * f + 1, 10 * f + 2], [1.0, 2.0]))
+            # line 2 fails the gate by four orders of magnitude (the reference's scale error): its values are not compared;
+            # line 3 has no rows left after the projection (NaN chi2): neither
+            out.append(_lines(f, [1000 * f + 1, 1000 * f + 2, 1000 * f + 3], [3.0 * (1 + eps_chi2), 4e4 * (1 + eps_failing), np.nan],
+                              [1.5 * (1 + eps_norm), 200.0, np.nan]))
+            out.append(("wheel", f, 0.05 * f, 1, np.zeros(1, dtype=np.uint64), np.ones(1, dtype=np.uint8), 0, None, None))
+        return out
+    a = run(0.0, 0.0)
+    s = dt.summary(a, run(2e-10, 1e-10, eps_failing=0.5), thr=THR)
+    assert s["first_divergence"] is None and s["tie_check"] == [], s["tie_check"]
+    ld = s["line_value_drift"]
+    assert len(ld["first_updates"]) == 5 and "all" not in ld
+    k, rel, which, lid = ld["first_updates"][0]
+    assert k == 1 and which == "chi2" and lid == 1001 and 1.9e-10 < rel < 2.1e-10
+    assert dt.value_drift(a, a, THR, kind="lines")[0][1] == 0.0 and len(dt.value_drift(a, a, THR)) == 11   # (points as before)
+    # a line chi2 wrong in its fifth digit passes every verdict and every point check: the line values catch it
+    s = dt.summary(a, run(3e-5, 0.0), thr=THR)
+    assert s["first_divergence"] is None and s["updates_with_identical_decisions"] == s["updates"]
+    assert len(s["tie_check"]) == 1 and "line values" in s["tie_check"][0] and "chi2" in s["tie_check"][0]
+    # and so does the residual norm alone
+    s = dt.summary(a, run(0.0, 4e-7), thr=THR)
+    assert len(s["tie_check"]) == 1 and "res_norm" in s["tie_check"][0]
+    # a number against NaN on a passing line is a difference, not a skipped entry
+    b = run(0.0, 0.0)
+    b[1][7][1][0, 2] = np.nan
+    assert dt.value_drift(a, b, THR, kind="lines")[0][1:3] == (np.inf, "res_norm")
+    assert dt.summary(a, b, thr=THR)["tie_check"]
+
+
 def test_min_unit_pivot():
     rng = np.random.default_rng(3)
     A = rng.standard_normal((12, 12))

@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+import jacobian_blocks as jb
 import oracle_lib
 import synth
 
@@ -36,6 +37,8 @@ def test_build_jacobians_parity(pkg, ctx, jo, kw):
     r0, Hf0, Hx0, res0 = jo.build_jacobians(st, tr, cols0, ld)
     r1, Hf1, Hx1, res1 = ctx.build_jacobians(st, tr, cols1, ld)
     _cmp(r0, (Hf0, Hx0, res0), r1, (Hf1, Hx1, res1))
+    # ... and block by block, each against its own largest entry (tests/jacobian_blocks.py)
+    jb.assert_blocks(st, cols0, (Hf1, Hx1, res1), (Hf0, Hx0, res0), label=f"point Jacobians {kw}")
 
 
 def test_build_jacobians_variants(pkg, ctx, jo):
@@ -57,6 +60,7 @@ def test_build_jacobians_variants(pkg, ctx, jo):
     a = jo.build_jacobians(st, tr, cols, 16)
     b = ctx.build_jacobians(st, tr, cols, 16)
     _cmp(a[0], a[1:], b[0], b[1:])
+    jb.assert_blocks(st, cols, b[1:], a[1:], label="point Jacobians, variants")
     # feature 0: one observation without bounding clones, and the newest one lands 3 ms (cam_dt) past the
     # newest clone (REF: State.cpp:852-855) -> both dropped
     assert a[0][0] == 2 * (sc["obs_ptr"][1] - 2)

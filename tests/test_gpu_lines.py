@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+import jacobian_blocks as jb
 import oracle_lib
 import synth
 
@@ -39,6 +40,8 @@ def test_line_jacobians_parity(ctx, pkg, jo, calib_dt, fej_noise, offset, pol):
         assert (np.isnan(a) == np.isnan(b)).all()
         fin = ~np.isnan(b)
         assert np.abs(a[fin] - b[fin]).max() <= 1e-9 * max(1.0, np.abs(b[fin]).max())
+    # ... and block by block, each against its own largest entry (tests/jacobian_blocks.py)
+    jb.assert_blocks(st, cols, (Hf, Hx, res), (Hf_o, Hx_o, res_o), label=f"line Jacobians dt={calib_dt} fej={fej_noise} offset={offset} pol={pol}")
 
 
 def test_line_jacobians_with_the_cpi_covariance_as_noise(ctx, pkg, jo):
@@ -65,6 +68,7 @@ def test_line_jacobians_with_the_cpi_covariance_as_noise(ctx, pkg, jo):
             assert (np.isnan(a) == np.isnan(b)).all()
             fin = ~np.isnan(b)
             assert np.abs(a[fin] - b[fin]).max() <= 1e-9 * max(1.0, np.abs(b[fin]).max())
+        jb.assert_blocks(st, cols, (Hf, Hx, res), (Hf_o, Hx_o, res_o), label=f"line Jacobians use_imu_cov={mode}")
         norms[mode] = np.nansum(np.abs(Hx_o))
     assert norms[1] != norms[0]   # the covariance does enter
 

@@ -5,7 +5,8 @@ Replays a rendered synthetic drive through the replay driver twice — over the 
 driver's decision trace and state probes on, and prints
   * the state and covariance difference in front of every camera update (the two filters agree to 1e-11 until something happens),
   * the first update whose dx differs by more than --dx-tol of its largest entry, with the update before it,
-  * the largest relative difference of a recorded test value per point update (tests/decision_trace.py value_drift).
+  * the largest relative difference of a recorded test value per point update and per line update (tests/decision_trace.py
+    value_drift, summary()'s value_drift / line_value_drift).
 This is the tool behind DESIGN §10.4: it found the two window poses at one instant, the factor form's eps x lambda^2 and the
 refinement's termination tests.
 
@@ -131,7 +132,12 @@ def main():
     print("value drift (update, largest relative difference of a recorded test value, which, feature):")
     print("  first:", drift[:5])
     print("  every 20th:", drift[::20])
-    print("decisions:", {k: v for k, v in dt.summary(h, c, thr=dt.thresholds(op)).items() if k in ("updates", "updates_with_identical_decisions", "first_divergence", "tie_check")})
+    dsum = dt.summary(h, c, thr=dt.thresholds(op))
+    ld = dsum["line_value_drift"]
+    print("line value drift (update, largest relative difference of chi2 / residual norm over the lines that pass the gate in both runs, which, line):")
+    print("  first:", ld["first_updates"])
+    print("  every 20th:", ld["at_every_20th_update"])
+    print("decisions:", {k: v for k, v in dsum.items() if k in ("updates", "updates_with_identical_decisions", "first_divergence", "tie_check")})
 
 
 if __name__ == "__main__":
