@@ -278,6 +278,40 @@ int plv_feed_staged(plv_ctx *ctx, int slot);
  * be overwritten before the call it was handed to has returned.  REF: the CameraData the caller builds, ROSSubscriber /
  * run_bag -> UpdaterCamera::feed_measurement (UpdaterCamera.cpp:77). */
 int plv_image_buffer(plv_ctx *ctx, int index, uint8_t **ptr, int *stride);
+
+/* ---- camera images in the sensor's encoding
+ *
+ * The 8-bit encodings a sensor_msgs/Image can carry to the reference's Image2Data, which hands them to
+ * cv_bridge::toCvShare(msg, MONO8) (REF: PL-VIWO/src/core/ROSHelper.cpp:151-173): a Bayer mosaic is demosaicked, a colour image is
+ * flattened to grey.  Here that step runs on the device (grey_from_encoded_kernel) and leaves the grey image where the front end
+ * reads it.  The names are the ROS encoding strings ("mono8", "bayer_rggb8", "bgr8", ...); the four letters of a Bayer name are the
+ * colours at (row 0, col 0), (0, 1), (1, 0), (1, 1).  Integer arithmetic, weights R 4899, G 9617, B 1868 over 2^14:
+ *   colour   Y = (R*4899 + G*9617 + B*1868 + 8192) >> 14, alpha ignored
+ *   Bayer    interior site of colour c in {R, B}, o the other: (diag4*w[o] + cross4*w[G] + centre*4*w[c] + 2^15) >> 16;
+ *            site G: ((left+right)*w[colour of left] + (up+down)*w[colour of up] + centre*2*w[G] + 2^14) >> 15;
+ *            row 0 copies row 1 and row H-1 row H-2, then column 0 copies column 1 and column W-1 column W-2; 3 x 3 at least
+ *   mono8    a copy
+ * (cv::cvtColor as recalled, not a pinned oracle: DESIGN.md "Image encodings".)  16-bit, YUV and compressed images are not taken. */
+enum { PLV_ENC_MONO8 = 0, PLV_ENC_BAYER_RGGB8, PLV_ENC_BAYER_BGGR8, PLV_ENC_BAYER_GBRG8, PLV_ENC_BAYER_GRBG8,
+       PLV_ENC_BGR8, PLV_ENC_RGB8, PLV_ENC_BGRA8, PLV_ENC_RGBA8 };
+/* Encoding string -> PLV_ENC_* value, -1 for anything else ("mono16" included).  Host logic: needs no device. */
+int plv_encoding_from_name(const char *name);
+/* 1, 3 or 4; 0 for a value that is no encoding. */
+int plv_encoding_bytes_per_pixel(int encoding);
+/* Converts a host image of the context's width x height (rows `stride` >= width * bytes-per-pixel apart) into HBM slot `slot`
+ * (0..7), which then holds what plv_image_stage would hold for the converted grey image: plv_feed_staged, plv_tracker_feed_staged
+ * and plv_camera_frame with slot >= 0 take it from there.  Stream-ordered: the caller's buffer is free at return, nothing waits for
+ * the device (the next data-returning call on the ctx does).  A NULL pointer, a bad slot or encoding, or a stride below
+ * width * bytes-per-pixel -> PLV_E_BADARG, the slot as it was. */
+int plv_image_stage_encoded(plv_ctx *ctx, int slot, const uint8_t *data, int stride, int encoding);
+/* The encoded twin of plv_image_buffer: a page-locked block of width * height * bytes-per-pixel bytes (packed rows, index 0..3),
+ * allocated on first use.  The conversion kernel reads an image that lies in such a block from there (no host copy, no copy
+ * command); any other `data` is first copied into a block like these by the call it is handed to.  A block must not be overwritten
+ * before the conversion that reads it has run (the next call on the ctx that returns data has waited for it). */
+int plv_raw_image_buffer(plv_ctx *ctx, int index, int encoding, uint8_t **ptr, int *stride);
+/* The conversion alone (host in, host out, synchronous), any size from 1 x 1 (Bayer: 3 x 3): grey is w x h bytes, rows
+ * grey_stride >= w apart. */
+int plv_image_convert(plv_ctx *ctx, const uint8_t *data, int stride, int encoding, int w, int h, uint8_t *grey, int grey_stride);
 int plv_pyramid_levels(plv_ctx *ctx, int which);
 /* level geometry and (if out != NULL, w*h bytes, packed) pixels of one pyramid level */
 int plv_pyramid_download(plv_ctx *ctx, int which, int level, int *w, int *h, uint8_t *out);
@@ -342,6 +376,10 @@ int plv_tracker_detect_ahead(plv_ctx *ctx, int on);
 /* plv_tracker_feed from an image already resident in HBM (plv_image_stage, slots 0..7): the camera driver's DMA target in a
  * deployment, and the form bench.py times (no PCIe copy inside the frame). */
 int plv_tracker_feed_staged(plv_ctx *ctx, double timestamp, int slot, const uint8_t *mask);
+/* plv_tracker_feed for a host image in its sensor encoding (PLV_ENC_*; `data` as for plv_image_stage_encoded): the conversion is
+ * enqueued on the context's stream into the frame's raw image and the device feed follows it.  Same tracker state as
+ * plv_tracker_feed of the converted image.  A refused argument (PLV_E_BADARG) leaves the tracker untouched. */
+int plv_tracker_feed_encoded(plv_ctx *ctx, double timestamp, const uint8_t *data, int stride, int encoding, const uint8_t *mask);
 /* feed_measurement with OptionsCamera::downsample (REF: UpdaterCamera.cpp:85-98): cv::pyrDown(img, Size(cols / 2.0,
  * rows / 2.0)) of image and mask on the device, then the same path.  The context is created at the halved
  * resolution with halved intrinsics, as the reference's option loader does (OptionsCamera.cpp:123-138). */

@@ -28,6 +28,10 @@ PLV_E_NUMERIC = -7
 
 PLV_CAM_RADTAN = 0
 PLV_CAM_EQUIDISTANT = 1
+# the 8-bit image encodings the library converts to grey on the device (PLV_ENC_*; the names are the ROS encoding strings)
+ENCODINGS = {"mono8": 0, "bayer_rggb8": 1, "bayer_bggr8": 2, "bayer_gbrg8": 3, "bayer_grbg8": 4, "bgr8": 5, "rgb8": 6, "bgra8": 7,
+             "rgba8": 8}
+_ENC_BPP = (1, 1, 1, 1, 1, 3, 3, 4, 4)
 
 
 class PlvConfig(C.Structure):
@@ -105,6 +109,11 @@ def load_library():
         "plv_image_stage": (C.c_int, [vp, C.c_int, u8p, C.c_int]),
         "plv_feed_staged": (C.c_int, [vp, C.c_int]),
         "plv_image_buffer": (C.c_int, [vp, C.c_int, C.POINTER(u8p), ip]),
+        "plv_encoding_from_name": (C.c_int, [C.c_char_p]),
+        "plv_encoding_bytes_per_pixel": (C.c_int, [C.c_int]),
+        "plv_image_stage_encoded": (C.c_int, [vp, C.c_int, u8p, C.c_int, C.c_int]),
+        "plv_raw_image_buffer": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(u8p), ip]),
+        "plv_image_convert": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_int, C.c_int, u8p, C.c_int]),
         "plv_pyramid_levels": (C.c_int, [vp, C.c_int]),
         "plv_pyramid_download": (C.c_int, [vp, C.c_int, C.c_int, ip, ip, u8p]),
         "plv_lk_track": (C.c_int, [vp, C.c_int, fp, fp, u8p, ip]),
@@ -118,6 +127,7 @@ def load_library():
                                             C.POINTER(C.c_uint64), ip]),
         "plv_tracker_feed": (C.c_int, [vp, C.c_double, u8p, C.c_int, u8p]),
         "plv_tracker_feed_staged": (C.c_int, [vp, C.c_double, C.c_int, u8p]),
+        "plv_tracker_feed_encoded": (C.c_int, [vp, C.c_double, u8p, C.c_int, C.c_int, u8p]),
         "plv_tracker_detect_ahead": (C.c_int, [vp, C.c_int]),
         "plv_tracker_feed_downsampled": (C.c_int, [vp, C.c_double, u8p, C.c_int, C.c_int, C.c_int, u8p, C.c_int]),
         "plv_downsample": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_int, u8p, C.c_int]),
@@ -229,6 +239,16 @@ def load_library():
     lib._plv_signatures = sig
     _lib = lib
     return lib
+
+
+def encoding_from_name(name):
+    """plv_encoding_from_name: the PLV_ENC_* value of a ROS encoding string, -1 for one the library does not take (needs no device)"""
+    return int(load_library().plv_encoding_from_name(str(name).encode()))
+
+
+def encoding_bytes_per_pixel(encoding):
+    """plv_encoding_bytes_per_pixel: 1, 3 or 4 (0: no encoding)"""
+    return int(load_library().plv_encoding_bytes_per_pixel(int(encoding)))
 
 
 def _dp(a):
@@ -983,6 +1003,57 @@ class Context:
         buf = (C.c_uint8 * (self.cfg.height * stride.value)).from_address(C.addressof(ptr.contents))
         return np.frombuffer(buf, dtype=np.uint8).reshape(self.cfg.height, stride.value)[:, :self.cfg.width]
 
+    # ---- images in the sensor's encoding
+    @staticmethod
+    def _encoding(encoding):
+        e = ENCODINGS.get(encoding, -1) if isinstance(encoding, str) else int(encoding)
+        if not 0 <= e < len(_ENC_BPP):
+            raise PlvError(PLV_E_BADARG, f"unknown image encoding {encoding!r}")
+        return e, _ENC_BPP[e]
+
+    def _encoded_rows(self, data, encoding, shape=None):
+        """(array, row stride in bytes, encoding value) of an encoded image: H x W (1 byte per pixel) or H x W x bpp, uint8, the last
+        axes contiguous (rows may be padded: a slice of a wider array keeps its stride)"""
+        e, bpp = self._encoding(encoding)
+        a = np.asarray(data)
+        if a.dtype != np.uint8:
+            a = a.astype(np.uint8)
+        if bpp == 1 and a.ndim == 3 and a.shape[2] == 1:
+            a = a[:, :, 0]
+        want = 2 if bpp == 1 else 3
+        if a.ndim != want or (bpp > 1 and a.shape[2] != bpp):
+            raise PlvError(PLV_E_BADARG, f"image shape {a.shape} does not fit {bpp} byte(s) per pixel")
+        inner = a.strides[1:] == ((1,) if bpp == 1 else (bpp, 1))
+        if not inner or a.strides[0] < a.shape[1] * bpp:
+            a = np.ascontiguousarray(a)
+        if shape is not None and a.shape[:2] != shape:
+            raise PlvError(PLV_E_BADARG, f"image shape {a.shape[:2]} != {shape}")
+        return a, int(a.strides[0]), e
+
+    def image_stage_encoded(self, slot, data, encoding):
+        """plv_image_stage_encoded: converts the encoded image (name or PLV_ENC_* value) to grey into HBM slot `slot`; enqueued only"""
+        a, stride, e = self._encoded_rows(data, encoding, (self.cfg.height, self.cfg.width))
+        self._chk(self.lib.plv_image_stage_encoded(self.h, int(slot), a.ctypes.data_as(C.POINTER(C.c_uint8)), stride, e))
+
+    def raw_image_buffer(self, index, encoding):
+        """numpy view of the library's page-locked block `index` for an image in `encoding` (plv_raw_image_buffer): height x width, or
+        height x width x bytes-per-pixel; an image written into it is converted from where it lies"""
+        e, bpp = self._encoding(encoding)
+        ptr, stride = C.POINTER(C.c_uint8)(), C.c_int()
+        self._chk(self.lib.plv_raw_image_buffer(self.h, int(index), e, C.byref(ptr), C.byref(stride)))
+        h, w = self.cfg.height, self.cfg.width
+        buf = (C.c_uint8 * (h * stride.value)).from_address(C.addressof(ptr.contents))
+        v = np.frombuffer(buf, dtype=np.uint8).reshape(h, stride.value)
+        return v[:, :w] if bpp == 1 else v[:, :w * bpp].reshape(h, w, bpp)
+
+    def image_convert(self, data, encoding):
+        """plv_image_convert: the grey image of an encoded image of any size (host in, host out)"""
+        a, stride, e = self._encoded_rows(data, encoding)
+        h, w = a.shape[:2]
+        out = np.zeros((h, w), dtype=np.uint8)
+        self._chk(self.lib.plv_image_convert(self.h, a.ctypes.data_as(C.POINTER(C.c_uint8)), stride, e, w, h, _u8p(out), w))
+        return out
+
     def pyramid_levels(self, which=0):
         return self.lib.plv_pyramid_levels(self.h, which)
 
@@ -1549,6 +1620,12 @@ class Context:
         img = np.ascontiguousarray(img, dtype=np.uint8)
         m = np.ascontiguousarray(mask, dtype=np.uint8) if mask is not None else None
         self._chk(self.lib.plv_tracker_feed(self.h, float(timestamp), _u8p(img), img.shape[1], _u8p(m)))
+
+    def tracker_feed_encoded(self, timestamp, data, encoding, mask=None):
+        """plv_tracker_feed_encoded: tracker_feed of an image in its sensor encoding (converted on the device, in front of the feed)"""
+        a, stride, e = self._encoded_rows(data, encoding, (self.cfg.height, self.cfg.width))
+        m = np.ascontiguousarray(mask, dtype=np.uint8) if mask is not None else None
+        self._chk(self.lib.plv_tracker_feed_encoded(self.h, float(timestamp), a.ctypes.data_as(C.POINTER(C.c_uint8)), stride, e, _u8p(m)))
 
     def tracker_detect_ahead(self, on):
         self._chk(self.lib.plv_tracker_detect_ahead(self.h, int(on)))

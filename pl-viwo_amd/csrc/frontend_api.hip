@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "detect_kernels.hpp"
+#include "encoding_kernels.hpp"
 #include "frontend_kernels.hpp"
 #include "line_kernels.hpp"
 #include "plv_internal.hpp"
@@ -45,6 +46,11 @@ struct FrontState {
   PinBuf det_pin;
   PinBuf img_pin[6];       // host images on their way to the device (plv_feed_image_enqueue): the caller's buffer is free at return
   int img_pin_next = 0;
+  // images in their sensor encoding (plv_image_stage_encoded ...): nothing here is allocated before the first of them arrives
+  PinBuf raw_pin[6];       // packed encoded images the conversion kernel reads in place: [0] [1] the library's own, [2 ..] plv_raw_image_buffer
+  hipEvent_t raw_done[2] = {nullptr, nullptr};  // behind the conversion that read own block i: the block is free once it has passed
+  int raw_pin_next = 0;
+  DevBuf cv_src, cv_dst;   // staging of plv_image_convert
   DetJob det_pending;
   hipStream_t det_stream = nullptr;
   hipEvent_t det_done = nullptr;
@@ -180,6 +186,66 @@ int upload_image(plv_ctx *ctx, FrontState *s, void *dst, const uint8_t *img, int
   return PLV_OK;
 }
 
+// ---- images in their sensor encoding
+int check_encoded(const char *who, const uint8_t *data, int stride, int encoding, int w) {
+  const int bpp = encoding_bpp(encoding);
+  if (bpp == 0) {
+    set_last_error("%s: %d is no PLV_ENC_* encoding", who, encoding);
+    return PLV_E_BADARG;
+  }
+  if (!data) {
+    set_last_error("%s: null image", who);
+    return PLV_E_BADARG;
+  }
+  if (stride < w * bpp) {
+    set_last_error("%s: stride %d < width %d x %d bytes per pixel", who, stride, w, bpp);
+    return PLV_E_BADARG;
+  }
+  return PLV_OK;
+}
+
+// Where the conversion kernel reads a W x H image from: `data` itself when it lies (packed) in one of the library's page-locked raw
+// blocks, else one of the library's own two blocks, into which the image is copied here.  *own: that block's index, or -1.
+int encoded_source(FrontState *s, const uint8_t *data, int stride, int bpp, const uint8_t **h_src, int *own) {
+  const size_t row = (size_t)s->W * bpp, bytes = row * s->H;
+  *own = -1;
+  if ((size_t)stride == row)
+    for (auto &b : s->raw_pin)
+      if (b.p && data >= b.as<uint8_t>() && data + bytes <= b.as<uint8_t>() + b.cap && ((data - b.as<uint8_t>()) & 15) == 0) {
+        *h_src = data;
+        return PLV_OK;
+      }
+  plv::HostPhase ph("encoded image: host copy into the pinned block");
+  TRY(s->raw_pin[0].reserve(bytes));  // (both at the first image: the second call must not allocate)
+  TRY(s->raw_pin[1].reserve(bytes));
+  const int i = s->raw_pin_next;
+  s->raw_pin_next ^= 1;
+  // the conversion that read this block two images ago: normally long finished
+  if (s->raw_done[i] && hipEventQuery(s->raw_done[i]) == hipErrorNotReady) PLV_HIP_CHECK(plv::event_sync(s->raw_done[i]));
+  uint8_t *dst = s->raw_pin[i].as<uint8_t>();
+  if ((size_t)stride == row) {
+    memcpy(dst, data, bytes);
+  } else {
+    for (int y = 0; y < s->H; ++y) memcpy(dst + (size_t)y * row, data + (size_t)y * stride, row);
+  }
+  *h_src = dst;
+  *own = i;
+  return PLV_OK;
+}
+
+// the conversion of a host image into d_dst (W x H grey bytes in HBM), enqueued on the ctx stream; arguments checked by the caller
+int convert_enqueue(plv_ctx *ctx, FrontState *s, const uint8_t *data, int stride, int encoding, uint8_t *d_dst) {
+  const uint8_t *h_src = nullptr;
+  int own = -1;
+  TRY(encoded_source(s, data, stride, encoding_bpp(encoding), &h_src, &own));
+  TRY(launch_grey_from_encoded(ctx, h_src, true, d_dst, s->W, s->H, encoding));
+  if (own >= 0) {
+    if (!s->raw_done[own]) PLV_HIP_CHECK(hipEventCreateWithFlags(&s->raw_done[own], hipEventDisableTiming));
+    PLV_HIP_CHECK(hipEventRecord(s->raw_done[own], ctx->stream));
+  }
+  return PLV_OK;
+}
+
 }  // namespace
 
 namespace plv {
@@ -191,6 +257,11 @@ void plv_frontend_destroy(plv_ctx *ctx) {
   if (s->flow_done) (void)hipEventDestroy(s->flow_done);
   if (s->det_stream) (void)hipStreamDestroy(s->det_stream);
   for (auto &b : s->img_pin) b.release();
+  for (auto &b : s->raw_pin) b.release();
+  for (auto &e : s->raw_done)
+    if (e) (void)hipEventDestroy(e);
+  s->cv_src.release();
+  s->cv_dst.release();
   DevBuf *bufs[] = {&s->pyr_mem[0], &s->pyr_mem[1], &s->raw, &s->hist, &s->clahe_lut, &s->ds_src, &s->ds_dst, &s->pts0, &s->pts1, &s->n0, &s->n1,
                     &s->status, &s->iters, &s->mask, &s->counts, &s->info, &s->io, &s->models, &s->det_in, &s->det_out,
                     &s->det_mask, &s->subpix_tab, &s->det_cand, &s->det_cand_n};
@@ -234,8 +305,72 @@ int plv_feed_image_enqueue(plv_ctx *ctx, const uint8_t *img, int stride) {
   // no copy command: the histogram kernel reads the pinned block over PCIe (16 bytes per lane) and leaves the image in s->raw
   return feed_device(ctx, s, s->raw.as<uint8_t>(), h_src);
 }
+
+// plv_tracker_feed_encoded's image feed: the conversion into the frame's raw image, then the device feed, all enqueued
+int plv_feed_encoded_enqueue(plv_ctx *ctx, const uint8_t *data, int stride, int encoding) {
+  if (!ctx) return PLV_E_BADARG;
+  (void)hipSetDevice(ctx->device);
+  FrontState *s = fe(ctx);
+  TRY(check_encoded("plv_tracker_feed_encoded", data, stride, encoding, s->W));
+  if (encoding == PLV_ENC_MONO8) return plv_feed_image_enqueue(ctx, data, stride);  // (already grey: the host route's feed)
+  TRY(ensure_pyramids(ctx, s));
+  TRY(convert_enqueue(ctx, s, data, stride, encoding, s->raw.as<uint8_t>()));
+  return feed_device(ctx, s, s->raw.as<uint8_t>());
+}
 }  // namespace plv
 extern "C" {
+
+int plv_image_stage_encoded(plv_ctx *ctx, int slot, const uint8_t *data, int stride, int encoding) {
+  if (!ctx || slot < 0 || slot >= 8) {
+    set_last_error("plv_image_stage_encoded: no context or slot %d outside 0 .. 7", slot);
+    return PLV_E_BADARG;
+  }
+  (void)hipSetDevice(ctx->device);
+  FrontState *s = fe(ctx);
+  TRY(check_encoded("plv_image_stage_encoded", data, stride, encoding, s->W));
+  TRY(ensure_pyramids(ctx, s));
+  TRY(s->slots[slot].reserve((size_t)s->W * s->H));
+  // stream-ordered, no host sync: the next call on this ctx that returns data synchronises
+  return convert_enqueue(ctx, s, data, stride, encoding, s->slots[slot].as<uint8_t>());
+}
+
+// The encoded twin of plv_image_buffer: the conversion kernel reads an image written here where it lies.  The pointer stands until
+// the same index is asked for with an encoding of more bytes per pixel (the block then grows).
+int plv_raw_image_buffer(plv_ctx *ctx, int index, int encoding, uint8_t **ptr, int *stride) {
+  const int bpp = encoding_bpp(encoding);
+  if (!ctx || !ptr || index < 0 || index >= 4 || bpp == 0) {
+    set_last_error("plv_raw_image_buffer: no context / pointer, index %d outside 0 .. 3 or encoding %d unknown", index, encoding);
+    return PLV_E_BADARG;
+  }
+  (void)hipSetDevice(ctx->device);
+  FrontState *s = fe(ctx);
+  TRY(s->raw_pin[2 + index].reserve((size_t)s->W * s->H * bpp));  // (blocks 0 and 1 are the library's own)
+  *ptr = s->raw_pin[2 + index].as<uint8_t>();
+  if (stride) *stride = s->W * bpp;
+  return PLV_OK;
+}
+
+int plv_image_convert(plv_ctx *ctx, const uint8_t *data, int stride, int encoding, int w, int h, uint8_t *grey, int grey_stride) {
+  if (!ctx || !grey || w < 1 || h < 1 || grey_stride < w) {
+    set_last_error("plv_image_convert: no context / output, or a %d x %d image with output stride %d", w, h, grey_stride);
+    return PLV_E_BADARG;
+  }
+  TRY(check_encoded("plv_image_convert", data, stride, encoding, w));
+  const int bpp = encoding_bpp(encoding);
+  if (bpp == 1 && encoding != PLV_ENC_MONO8 && (w < 3 || h < 3)) {
+    set_last_error("plv_image_convert: a Bayer mosaic is 3 x 3 at least, not %d x %d", w, h);
+    return PLV_E_BADARG;
+  }
+  (void)hipSetDevice(ctx->device);
+  FrontState *s = fe(ctx);
+  const size_t row = (size_t)w * bpp;
+  TRY(s->cv_src.reserve(row * h));
+  TRY(s->cv_dst.reserve((size_t)w * h));
+  PLV_HIP_CHECK(hipMemcpy2DAsync(s->cv_src.p, row, data, (size_t)stride, row, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
+  TRY(launch_grey_from_encoded(ctx, s->cv_src.as<uint8_t>(), false, s->cv_dst.as<uint8_t>(), w, h, encoding));
+  PLV_HIP_CHECK(hipMemcpy2DAsync(grey, (size_t)grey_stride, s->cv_dst.p, (size_t)w, (size_t)w, (size_t)h, hipMemcpyDeviceToHost, ctx->stream));
+  return sync(ctx);
+}
 
 // A pinned host block of the library for the caller to write the next image into (a camera driver's DMA target, cv_bridge's copy
 // target: `cv::Mat(h, w, CV_8UC1, ptr)`): plv_tracker_feed / plv_camera_frame recognise a pointer into it and skip their own host

@@ -38,6 +38,8 @@ int plv_state_vars_check(int n_var, const plv_state_var *vars, int n_dx);
 void plv_frontend_destroy(plv_ctx *ctx);
 // plv_feed_image without the wait at its end (the tracker's path: the feed goes on to enqueue the flow and waits there)
 int plv_feed_image_enqueue(plv_ctx *ctx, const uint8_t *img, int stride);
+// plv_tracker_feed_encoded's image feed: conversion of the encoded host image into the frame's raw image + the device feed, enqueued
+int plv_feed_encoded_enqueue(plv_ctx *ctx, const uint8_t *data, int stride, int encoding);
 // images fed so far: identifies the frame a cached detection belongs to
 int plv_front_fed_count(plv_ctx *ctx);
 // where the flow launched last leaves its results on the device: positions, normalised coordinates [n][2], inlier mask [n]

@@ -140,6 +140,18 @@ int plv_tracker_feed_staged(plv_ctx *ctx, double timestamp, int slot, const uint
   return tracker_feed_fed(ctx, T, timestamp, mask);
 }
 
+int plv_tracker_feed_encoded(plv_ctx *ctx, double timestamp, const uint8_t *data, int stride, int encoding, const uint8_t *mask) {
+  if (!ctx || !data) {
+    set_last_error("plv_tracker_feed_encoded: no context or null image");
+    return PLV_E_BADARG;
+  }
+  Tracker *T = trk(ctx);
+  std::lock_guard<std::mutex> lk(T->mtx);
+  // the conversion in front of the feed, on the same stream (a refused argument returns before anything is enqueued)
+  TRY(feed_with_early_edges(ctx, [&] { return plv_feed_encoded_enqueue(ctx, data, stride, encoding); }));
+  return tracker_feed_fed(ctx, T, timestamp, mask);
+}
+
 int plv_tracker_feed_downsampled(plv_ctx *ctx, double timestamp, const uint8_t *img, int stride, int src_w, int src_h,
                                  const uint8_t *mask, int mask_stride) {
   if (!ctx || !img) return PLV_E_BADARG;

@@ -15,8 +15,10 @@
 // TrackLSD_HIP / UpdaterCameraHIP / StateHelperHIP find it through context().  The second takes a ctx the caller made (PlvContext.h).
 #pragma once
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "plviwo.h"
@@ -76,6 +78,43 @@ public:
       PRINT_ERROR(RED "[TrackKLT_HIP]: %s\n" RESET, plv_last_error());  // TrackKLT.cpp:37-43 exits on bad sizes as well
       std::exit(EXIT_FAILURE);
     }
+    after_feed(cam_id, message.timestamp, img, mask);
+  }
+
+  // feed_new_camera for a sensor_msgs/Image as it arrives — `data`, `step` and `encoding` of the message ("mono8", "bayer_rggb8",
+  // "bgr8", ...: plv_encoding_from_name) — instead of the MONO8 image cv_bridge::toCvShare would make of it on the host
+  // (REF: PL-VIWO/src/core/ROSHelper.cpp:151-173).  The bytes go into one of the library's page-locked raw blocks, the conversion
+  // kernel reads them there into an HBM slot, and the frame takes the staged path.  img_last stays empty: there is no host grey image.
+  void feed_new_camera(double timestamp, size_t cam_id, const uint8_t *data, int step, const std::string &encoding, const cv::Mat &mask) {
+    std::lock_guard<std::mutex> lck(mtx_feeds.at(cam_id));
+    const int slot = stage_encoded(data, step, encoding);
+    if (slot < 0 || !mask.isContinuous() || plv_tracker_feed_staged(ctx, timestamp, slot, mask.empty() ? nullptr : mask.data) != PLV_OK) {
+      PRINT_ERROR(RED "[TrackKLT_HIP]: %s\n" RESET, plv_last_error());
+      std::exit(EXIT_FAILURE);
+    }
+    after_feed(cam_id, timestamp, cv::Mat(), mask);
+  }
+
+  // the message's bytes -> raw block (alternating) -> plv_image_stage_encoded: the HBM slot that holds the grey image, or -1
+  // (plv_last_error says why; an encoding the library does not take among the reasons)
+  int stage_encoded(const uint8_t *data, int step, const std::string &encoding) {
+    const int enc = plv_encoding_from_name(encoding.c_str());
+    uint8_t *blk = nullptr;
+    int bstride = 0;
+    if (!data || step < 0 || plv_raw_image_buffer(ctx, raw_index, enc, &blk, &bstride) != PLV_OK) return -1;
+    if (step < bstride) return plv_image_stage_encoded(ctx, raw_index, data, step, enc) == PLV_OK ? raw_index : -1;  // (refused: the library names the cause)
+    const int rows = camera_calib.begin()->second->h();
+    for (int y = 0; y < rows; ++y) std::memcpy(blk + (size_t)y * bstride, data + (size_t)y * step, (size_t)bstride);
+    const int slot = raw_index;
+    raw_index = (raw_index + 1) & 3;
+    return plv_image_stage_encoded(ctx, slot, blk, bstride, enc) == PLV_OK ? slot : -1;
+  }
+
+  plv_ctx *context() const { return ctx; }
+
+protected:
+  // TrackBase's observable state after a feed: pts_last / ids_last, the database mirror, img_last / img_mask_last
+  void after_feed(size_t cam_id, double timestamp, const cv::Mat &img, const cv::Mat &mask) {
     int n = 0;
     plv_tracker_last(ctx, nullptr, nullptr, 1 << 30, &n);
     std::vector<float> xy(2 * (size_t)n + 2);
@@ -90,7 +129,7 @@ public:
     if (mirror_db && have_last) {  // TrackKLT.cpp:176-179: every surviving point is an observation of this frame
       for (int i = 0; i < n; ++i) {
         const cv::Point2f npt = camera_calib.at(cam_id)->undistort_cv(kps[i].pt);
-        database->update_feature(kid[i], message.timestamp, cam_id, kps[i].pt.x, kps[i].pt.y, npt.x, npt.y);
+        database->update_feature(kid[i], timestamp, cam_id, kps[i].pt.x, kps[i].pt.y, npt.x, npt.y);
       }
     }
     have_last = true;
@@ -101,12 +140,10 @@ public:
     ids_last[cam_id] = kid;
   }
 
-  plv_ctx *context() const { return ctx; }
-
-protected:
   std::shared_ptr<plv_ctx> owned;  // (first constructor)
   plv_ctx *ctx;
   bool mirror_db, have_last = false;
+  int raw_index = 0;  // the raw block (and HBM slot) the next encoded message goes into: 0 .. 3
 };
 
 }  // namespace ov_core

@@ -101,6 +101,20 @@ public:
     }
   }
 
+  // feed_measurement for a sensor_msgs/Image as it arrives (data, step, encoding: "bayer_rggb8", "bgr8", ...): the conversion to grey
+  // cv_bridge would make on the host runs on the device (TrackKLT_HIP::feed_new_camera's overload), the frame takes the staged path
+  void feed_measurement(double timestamp, const uint8_t *data, int step, const std::string &encoding, const cv::Mat &mask) {
+    t_hist.push_back(timestamp);
+    if (t_hist.size() > 100) t_hist.pop_front();
+    trackFEATS->feed_new_camera(timestamp, 0, data, step, encoding, mask);
+    if (trackLSDS) {
+      ov_core::CameraData stamp;  // (the line tracker's feed reads the time alone: the image is the one the context holds)
+      stamp.timestamp = timestamp;
+      auto vps = TrackLSD_HIP::vanishing_points(state->cam_extrinsic.at(0)->Rot(), state->cam_intrinsic.at(0)->value());
+      trackLSDS->feed_new_camera(stamp, vps, /*async*/ true);
+    }
+  }
+
   // UpdaterCamera::try_update: point update, dx applied, line update, dx applied.  Returns false when EKFUpdate rejected one.
   bool try_update() {
     if (!state->have_polynomial() || t_hist.size() < 2) return true;
@@ -198,7 +212,20 @@ public:
   }
   // returns false when EKFUpdate rejected one of the two updates (the state is then as the other one left it)
   bool frame(const ov_core::CameraData &camdata) {
-    t_hist.push_back(camdata.timestamp);
+    const cv::Mat &img = camdata.images.at(0), &mask = camdata.masks.at(0);
+    return frame_from(camdata.timestamp, -1, img.data, (int)img.step, mask);
+  }
+  // ... for a sensor_msgs/Image as it arrives (data, step, encoding): staged through a page-locked raw block and converted to grey on
+  // the device (plv_raw_image_buffer + plv_image_stage_encoded), then the one-call frame from that HBM slot
+  bool frame(double timestamp, const uint8_t *data, int step, const std::string &encoding, const cv::Mat &mask) {
+    const int slot = trackFEATS->stage_encoded(data, step, encoding);
+    if (slot < 0) return false;
+    return frame_from(timestamp, slot, nullptr, 0, mask);
+  }
+
+private:
+  bool frame_from(double timestamp, int slot, const uint8_t *img, int step, const cv::Mat &mask) {
+    t_hist.push_back(timestamp);
     if (t_hist.size() > 100) t_hist.pop_front();
     const auto &oc = state->op->cam;
     plv_update_options o{};
@@ -218,15 +245,12 @@ public:
     build_mean(m);
     plv_try_update up{&o, trackLSDS ? &o : nullptr, (int)m.vars.size(), m.vars.data(), dx_p.data(), dx_l.data(), &rp, &rl,
                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0x7fffffff, 0};
-    const cv::Mat &img = camdata.images.at(0), &mask = camdata.masks.at(0);
-    plv_camera_frame_io io{camdata.timestamp, -1, img.data, (int)img.step, mask.empty() ? nullptr : mask.data, trackLSDS ? 1 : 0,
-                           update ? &up : nullptr, 0};
+    plv_camera_frame_io io{timestamp, slot, img, step, mask.empty() ? nullptr : mask.data, trackLSDS ? 1 : 0, update ? &up : nullptr, 0};
     if (plv_camera_frame(ctx, &m.w.v, &io) != PLV_OK) return false;
     if (update) write_back(m);
     return rp.status == PLV_OK && rl.status == PLV_OK;
   }
 
-private:
   std::shared_ptr<State> state;
   plv_ctx *ctx;
   std::shared_ptr<ov_core::TrackKLT_HIP> trackFEATS;

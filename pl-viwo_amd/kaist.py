@@ -136,6 +136,15 @@ class KaistDataset:
         from .replay import read_image
         return bayer_rg_to_grey(read_image(self.frames[i][1]))
 
+    encoding = "bayer_rggb8"    # what raw_image delivers, as a ROS encoding string (the library converts it on the device)
+
+    def raw_image(self, i):
+        """the mosaic as read: what the camera's sensor_msgs/Image carries"""
+        from .replay import read_image
+        return read_image(self.frames[i][1])
+
+    to_grey = staticmethod(bayer_rg_to_grey)    # the host yardstick of that conversion: image(i) = to_grey(raw_image(i))
+
     def wheel_intrinsics(self):
         """(r_l, r_r, base) of EncoderParameter.txt, the values config_wheel.yaml's `intrinsics` rounds to 0.3 / 0.3 / 1.5"""
         e = self.encoder

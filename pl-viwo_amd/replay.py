@@ -17,6 +17,7 @@ Complex Urban raw directory (sensor_data/xsens_imu.csv, encoder.csv, image/stere
 """
 import os
 import struct
+import time
 import zlib
 
 import numpy as np
@@ -174,6 +175,14 @@ class Dataset:
     def image(self, i):
         return read_image(self.frames[i][1])
 
+    encoding = "mono8"      # what raw_image delivers (a ROS encoding string): these layouts hold grey images
+    raw_image = image
+
+    @staticmethod
+    def to_grey(raw):
+        """raw_image -> the grey image, on the host (image(i) = to_grey(raw_image(i)))"""
+        return raw
+
 
 def open_dataset(root, use_wheel=True, use_cam=True):
     """Dataset for this layout / EuRoC, or kaist.KaistDataset for a KAIST Complex Urban raw directory (sensor_data/xsens_imu.csv)"""
@@ -203,8 +212,10 @@ class TrajectoryLogger:
         self.f.close()
 
 
-def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_obs=24, **system_kw):
-    """run_bag's main loop.  Returns (SystemManager statistics, times, poses [n][7] = p, q)."""
+def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_obs=24, host_images=False, **system_kw):
+    """run_bag's main loop.  Returns (SystemManager statistics, times, poses [n][7] = p, q).  A dataset whose frames are not grey
+    (Dataset.encoding, e.g. the Bayer mosaics of a KAIST directory) hands them over as they are read and the library converts them
+    on the device; host_images: the dataset converts them on the host (Dataset.image), as a context without the conversion has to."""
     ds = dataset if dataset is not None else open_dataset(op.sys.path_bag, use_wheel=op.est.wheel.enabled, use_cam=op.est.cam.enabled)
     sys = SystemManager(op, device=device, max_obs=max_obs, **system_kw)
     path = trajectory_path if trajectory_path is not None else (op.sys.path_trajectory if op.sys.save_trajectory else None)
@@ -215,6 +226,10 @@ def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_
     if op.est.cam.enabled and op.est.cam.use_mask.get(0):
         mask = read_image(op.est.cam.mask_path[0])
     times, poses = [], []
+    encoding = getattr(ds, "encoding", "mono8")
+    has_raw = hasattr(ds, "raw_image") and hasattr(ds, "to_grey")
+    device_images = not host_images and encoding != "mono8" and has_raw and hasattr(sys.ctx, "image_stage_encoded")
+    cam_wall, cam_frames = 0.0, 0       # wall time of the camera messages past the file read: conversion + feed + update
     for k, (t, kind, i) in enumerate(ds.msgs):
         if t > t_finish:
             break
@@ -228,7 +243,13 @@ def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_
                 if log:
                     log.save(sys)
         elif kind == CAM:
-            sys.feed_measurement_camera(t, ds.image(i), mask)
+            raw = ds.raw_image(i) if has_raw else None       # (the file read is not the camera side's time)
+            t0 = time.perf_counter()
+            if device_images:
+                sys.feed_measurement_camera_encoded(t, raw, encoding, mask)
+            else:
+                sys.feed_measurement_camera(t, ds.to_grey(raw) if has_raw else ds.image(i), mask)
+            cam_wall, cam_frames = cam_wall + time.perf_counter() - t0, cam_frames + 1
         else:
             r = ds.wheel[i]
             sys.feed_measurement_wheel(r[0], r[1], r[2])
@@ -238,7 +259,8 @@ def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_
         log.close()
     stats = dict(sys.stats)
     stats.update(distance_m=sys.distance, time_s={k: round(v, 4) for k, v in sys.tc.total.items()}, initialized=sys.state.initialized,
-                 startup_time=sys.state.startup_time, end_time=sys.state.time, n_state=sys.state.n, clone_freq=op.est.clone_freq)
+                 startup_time=sys.state.startup_time, end_time=sys.state.time, n_state=sys.state.n, clone_freq=op.est.clone_freq,
+                 image_route="device" if device_images else "host", time_camera_s=round(cam_wall, 6), camera_messages=cam_frames)
     sys.close()
     return stats, np.array(times), np.array(poses).reshape(-1, 7)
 

@@ -689,6 +689,18 @@ class SystemManager:
         if st.initialized:
             self.tc.dong("CAM")
 
+    def feed_measurement_camera_encoded(self, t, data, encoding, mask=None, slot=0):
+        """feed_measurement_camera for an image as the sensor delivers it (`encoding`: a ROS encoding string the library takes,
+        ENCODINGS): the conversion cv_bridge::toCvShare(msg, MONO8) makes on the host in the reference (REF: ROSHelper.cpp:151-173)
+        runs on the device, into HBM slot `slot`, and the frame takes the staged path.  With OptionsCamera::downsample the grey
+        image comes back (image_convert) and goes through the downsampled feed."""
+        if not self.op.est.cam.enabled:
+            return
+        if self.op.est.cam.downsample:
+            return self.feed_measurement_camera(t, self.ctx.image_convert(data, encoding), mask)
+        self.ctx.image_stage_encoded(slot, data, encoding)
+        return self.feed_measurement_camera(t, None, mask, staged_slot=slot)
+
     def feed_measurement_camera(self, t, img, mask=None, staged_slot=None):
         """UpdaterCamera::feed_measurement + try_update (REF: UpdaterCamera.cpp:77-195).  staged_slot: the image already sits in that
         HBM slot of the context (Context.image_stage); `img` is then not read."""

@@ -3,6 +3,7 @@
 
     python tools/replay.py CONFIG.yaml [--dataset DIR] [--gt FILE] [--align posyaw] [--rpe 8,16,24] [--nees] [--out result.json]
     python tools/replay.py --synthetic 12 [--out result.json]        # renders tests/synth_dataset.py first (CPU), then replays it
+    python tools/replay.py CONFIG.yaml --dataset KAIST_DIR [--host-images]   # Bayer frames: converted on the device unless --host-images
 """
 import argparse
 import importlib
@@ -30,6 +31,8 @@ def main():
     ap.add_argument("--no-wheel", action="store_true")
     ap.add_argument("--no-lines", action="store_true")
     ap.add_argument("--keep", help="directory to keep the synthetic dataset in")
+    ap.add_argument("--host-images", action="store_true", help="frames that are not grey (a KAIST directory's Bayer mosaics) are converted on the "
+                    "host by the dataset reader instead of on the device by the library (the comparison run)")
     a = ap.parse_args()
     pkg = ge.load_pkg()
     options = importlib.import_module("plviwo_amd.options")
@@ -52,7 +55,7 @@ def main():
     if not op.sys.save_trajectory:
         op.sys.save_trajectory, op.sys.path_trajectory = True, os.path.join(tempfile.mkdtemp(prefix="plv_out_"), "traj.txt")
     t0 = time.time()
-    stats, times, poses = rp.replay(op, progress=lambda s, t: print(f"  t={t:8.3f}  clones {s.stats['clones']}  cam accepted "
+    stats, times, poses = rp.replay(op, host_images=a.host_images, progress=lambda s, t: print(f"  t={t:8.3f}  clones {s.stats['clones']}  cam accepted "
                                                                     f"{s.stats['cam_accepted']}/{s.stats['cam_features']}  wheel {s.stats['wheel_accepted']}", flush=True))
     res = dict(config=a.config, wall_s=round(time.time() - t0, 2), stats=stats, poses_logged=len(times), trajectory=op.sys.path_trajectory)
     if a.gt and len(times) > 2:
