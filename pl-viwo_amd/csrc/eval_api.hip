@@ -596,8 +596,8 @@ static int device_align(plv_ctx *ctx, int method, int n, const double *d_est, co
   // ---- align_umeyama(data = est, model = gt)
   auto *us = plv_update_state(ctx);
   const int blocks = std::min(256, (n + 255) / 256);
-  TRY(us->tri.reserve((size_t)blocks * 16 * sizeof(double) + 64));
-  double *d_part = us->tri.as<double>();
+  TRY(us->staging_of(3).tri.reserve((size_t)blocks * 16 * sizeof(double) + 64));
+  double *d_part = us->staging_of(3).tri.as<double>();
   std::vector<double> part((size_t)blocks * 10);
   {
     ProfScope ps(ctx->prof, "traj_mean_kernel", ctx->stream);

@@ -10,6 +10,7 @@
 #include "update_kernels.hpp"
 #include "update_state.hpp"
 #include "camera_tracks.hpp"
+#include "stage_block.hpp"
 
 using namespace plv;
 
@@ -21,20 +22,134 @@ using namespace plv;
 
 namespace {
 
-int check_views(const plv_state_view *st, const plv_tracks *tr) {
+typedef plv::StageBlock StageBlock;
+typedef plv_ctx_update_state::Staging Staging;
+
+// the checks a point and a line batch share; tracks_ok: the caller's test of its own arrays.  `what` leads the error text
+template <class Tracks, class Ok> int check_views(const char *what, const plv_state_view *st, const Tracks *tr, Ok tracks_ok) {
   if (!st || !tr || st->n_clones < 1 || !st->clone_time || !st->clone_R || !st->clone_p || !st->clone_R_fej ||
-      !st->clone_p_fej || !st->clone_state_id || tr->n_feat < 1 || !tr->obs_ptr || !tr->obs_time || !tr->obs_uv ||
-      !tr->p_FinG || !tr->p_FinG_fej) {
-    set_last_error("jacobians: null view field");
+      !st->clone_p_fej || !st->clone_state_id || !tracks_ok(*tr)) {
+    set_last_error("%s: null view field", what);
     return PLV_E_BADARG;
   }
   if (st->intr_order != 3) {
-    set_last_error("jacobians: only intr_order = 3 is built (got %d)", st->intr_order);
+    set_last_error("%s: only intr_order = 3 is built (got %d)", what, st->intr_order);
     return PLV_E_BADARG;
   }
   if ((tr->res_R == nullptr) != (tr->res_p == nullptr)) return PLV_E_BADARG;
   return PLV_OK;
 }
+int check_views(const plv_state_view *st, const plv_tracks *tr) {
+  return check_views("jacobians", st, tr, [](const plv_tracks &t) {
+    return t.n_feat >= 1 && t.obs_ptr && t.obs_time && t.obs_uv && t.p_FinG && t.p_FinG_fej;
+  });
+}
+
+// Column order of a batch: every clone an observation interpolates over, in first-seen order.  Points (lines = false) put the
+// calibration blocks in front, lines the time offset behind each new window.
+int jacobian_columns(const plv_state_view *st, int n, const int *obs_ptr, const double *obs_time, bool lines, int *col_to_state, int cap,
+                     int *k_out) {
+  int k = 0;
+  auto push = [&](int id, int size) {
+    if (id < 0) return true;
+    for (int j = 0; j < k; ++j)
+      if (col_to_state[j] == id) return true;
+    if (k + size > cap) return false;
+    for (int d = 0; d < size; ++d) col_to_state[k++] = id + d;
+    return true;
+  };
+  // REF: CamHelper.cpp:74-95 calibration blocks first, then :98-110 interpolation poses in first-seen order
+  if (!lines && (!push(st->extrinsic_state_id, 6) || !push(st->intrinsic_state_id, 8) || !push(st->dt_state_id, 1))) return PLV_E_CAPACITY;
+  // (a window start that has been seen adds nothing: 700 observations meet ~14 distinct windows, and the search through the
+  // column list per pose was 29 us of the caller's thread in front of the point launch at configs[2])
+  std::vector<uint8_t> seen_s0((size_t)std::max(st->n_clones, 1), 0);
+  BoundingMemo start_of(*st);
+  for (int f = 0; f < n; ++f)
+    for (int o = obs_ptr[f]; o < obs_ptr[f + 1]; ++o) {
+      const int s0 = start_of(obs_time[o] + st->cam_dt);
+      if (s0 < 0 || seen_s0[s0]) continue;
+      seen_s0[s0] = 1;
+      for (int w = 0; w < 4; ++w)
+        if (!push(st->clone_state_id[s0 + w], 6)) return PLV_E_CAPACITY;
+      // REF: LineHelper.cpp:757-788 — `order` of get_interpolated_jacobian: four poses, then the time offset
+      if (lines && !push(st->dt_state_id, 1)) return PLV_E_CAPACITY;
+    }
+  *k_out = k;
+  return PLV_OK;
+}
+
+int max_obs(const int *obs_ptr, int n) {  // (sizes a launch's LDS)
+  int m = 1;
+  for (int f = 0; f < n; ++f) m = std::max(m, obs_ptr[f + 1] - obs_ptr[f]);
+  return m;
+}
+
+// The part of a packed block both batches carry: the clones of the state view, the residual poses with their covariances, the
+// column map.  The stager of a batch adds its own arrays in between, in the order of the block; pack() fills the pinned block,
+// fill() hands the device addresses and the view's scalars to the kernels' parameters.
+struct StateStage {
+  StageBlock &B;
+  const plv_state_view *st;
+  int k;
+  const int *col_to_state;
+  StageBlock::Slot<double> time, R, p, Rf, pf, rR, rp, rQ;
+  StageBlock::Slot<int> ccol, cols, rc;
+  int col_of(int sid) const {
+    if (sid < 0) return -1;
+    for (int j = 0; j < k; ++j)
+      if (col_to_state[j] == sid) return j;
+    return -1;
+  }
+  void add_clones() {
+    const size_t N = (size_t)st->n_clones;
+    time = B.add(st->clone_time, N), R = B.add<9>(st->clone_R, N), p = B.add<3>(st->clone_p, N);
+    Rf = B.add<9>(st->clone_R_fej, N), pf = B.add<3>(st->clone_p_fej, N), ccol = B.room<int>(N);
+  }
+  void add_res_poses(const double *res_R, const double *res_p, size_t nobs) {
+    if (res_R) rR = B.add<9>(res_R, nobs), rp = B.add<3>(res_p, nobs);
+  }
+  int add_res_noise(const double *res_Q, const int *res_clone, size_t nobs) {
+    if (res_Q && !res_clone) return PLV_E_BADARG;
+    if (res_Q) rQ = B.add<36>(res_Q, nobs), rc = B.add(res_clone, nobs);
+    return PLV_OK;
+  }
+  void add_cols() { cols = B.add(col_to_state, (size_t)k); }
+  int pack(Staging &sg) {  // (the caller enqueues the upload)
+    if (B.overflowed()) return PLV_E_CAPACITY;
+    TRY(sg.h_jin.reserve(B.total()));
+    TRY(sg.jin.reserve(B.total()));
+    B.copy_all(sg.h_jin.p, sg.jin.p);
+    int *ccol_h = B.host(ccol);
+    for (int i = 0; i < st->n_clones; ++i) ccol_h[i] = col_of(st->clone_state_id[i]);
+    return PLV_OK;
+  }
+  void fill(JacParams &P, const plv_ctx *ctx, int ld) const {
+    P.n_clones = st->n_clones;
+    P.clone_time = B.dev(time), P.clone_R = B.dev(R), P.clone_p = B.dev(p);
+    P.clone_R_fej = B.dev(Rf), P.clone_p_fej = B.dev(pf), P.clone_col = B.dev(ccol);
+    memcpy(P.R_ItoC, st->R_ItoC, sizeof P.R_ItoC);
+    memcpy(P.p_IinC, st->p_IinC, sizeof P.p_IinC);
+    memcpy(P.K, st->intrinsics, sizeof P.K);
+    P.cam_model = ctx->cam_model;
+    P.cam_dt = st->cam_dt;
+    P.dt_exp = st->dt_exp;
+    P.sigma_pix = st->sigma_pix;
+    P.intr_ori_cov = st->intr_ori_cov;
+    P.intr_pos_cov = st->intr_pos_cov;
+    P.use_pol_cov = st->use_pol_cov;
+    P.use_imu_cov = st->use_imu_cov && rQ ? 1 : 0;
+    P.intr_err_mlt = st->intr_err_mlt;
+    P.res_R = B.dev(rR), P.res_p = B.dev(rp), P.res_Q = B.dev(rQ), P.res_clone = B.dev(rc);
+    P.feat_rep = st->feat_rep;
+    P.col_dt = col_of(st->dt_state_id);
+    P.k = k;
+    P.ld = ld;
+    P.cols_in = B.dev(cols);
+    P.cols_out = nullptr;
+    P.in_base = B.dev_base();
+    P.in_bytes = (int)B.total();
+  }
+};
 
 // Packs every input array into one pinned block, uploads it with one copy and fills JacParams.
 struct StageExtra {  // optional riders of the packed block (one-submission update): normalised coordinates, admissibility flags
@@ -53,154 +168,148 @@ struct StageExtra {  // optional riders of the packed block (one-submission upda
 };
 int stage_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *st, const plv_tracks *tr, int k,
                  const int *col_to_state, int ld, JacParams &P, StageExtra *ex = nullptr) {
-  const int N = st->n_clones, F = tr->n_feat, nobs = tr->obs_ptr[F];
+  const int F = tr->n_feat, nobs = tr->obs_ptr[F];
   if (nobs < 1) {
     set_last_error("jacobians: no observations");
     return PLV_E_BADARG;
   }
-  auto col_of = [&](int sid) {
-    if (sid < 0) return -1;
-    for (int j = 0; j < k; ++j)
-      if (col_to_state[j] == sid) return j;
-    return -1;
-  };
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 15) & ~(size_t)15;
-    return o;
-  };
-  const size_t o_time = take(8 * N), o_R = take(72 * N), o_p = take(24 * N), o_Rf = take(72 * N), o_pf = take(24 * N),
-               o_ccol = take(4 * N), o_ptr = take(4 * (F + 1)), o_of = take(4 * nobs), o_ot = take(8 * nobs),
-               o_uv = take(8 * nobs), o_pg = take(24 * F), o_pgf = take(24 * F),
-               o_rR = tr->res_R ? take(72 * nobs) : 0, o_rp = tr->res_R ? take(24 * nobs) : 0, o_cols = take(4 * (size_t)k),
-               o_xuvn = ex && ex->uvn ? take(8 * nobs) : 0, o_xfl = ex && ex->flags ? take(F) : 0,
-               o_rQ = tr->res_Q ? take(288 * (size_t)nobs) : 0, o_rc = tr->res_Q ? take(4 * (size_t)nobs) : 0,
-               o_sli = ex && ex->spec_li ? take(4 * (size_t)F) : 0, o_sme = ex && ex->spec_li ? take(F) : 0, o_spv = ex && ex->spec_li ? take(F) : 0,
-               o_send = ex && ex->spec_li ? take(4 * (size_t)F) : 0;
-  const size_t total = off;
-  TRY(us->h_jin.reserve(total));
-  TRY(us->jin.reserve(total));
-  char *h = us->h_jin.as<char>();
-  memcpy(h + o_cols, col_to_state, 4 * (size_t)k);
-  if (ex && ex->uvn) memcpy(h + o_xuvn, ex->uvn, 8 * nobs);
-  if (ex && ex->flags) memcpy(h + o_xfl, ex->flags, F);
-  if (ex && ex->spec_li) {
-    memcpy(h + o_sli, ex->spec_li, 4 * (size_t)F);
-    memcpy(h + o_sme, ex->spec_meta, F);
-    memcpy(h + o_spv, ex->spec_prevalid, F);
-    memcpy(h + o_send, tr->obs_ptr + 1, 4 * (size_t)F);  // (overwritten by spec_select_kernel)
+  const bool spec = ex && ex->spec_li;
+  StageBlock B;
+  StateStage S{B, st, k, col_to_state};
+  S.add_clones();
+  const auto ptr = B.add(tr->obs_ptr, F + 1), of = B.room<int>(nobs);
+  const auto ot = B.add(tr->obs_time, nobs);
+  const auto uv = B.add<2>(tr->obs_uv, nobs);
+  const auto pg = B.add<3>(tr->p_FinG, F), pgf = B.add<3>(tr->p_FinG_fej, F);
+  S.add_res_poses(tr->res_R, tr->res_p, nobs);
+  S.add_cols();
+  StageBlock::Slot<float> xuvn;
+  StageBlock::Slot<uint8_t> xfl, sme, spv;
+  StageBlock::Slot<int> sli, send;
+  if (ex && ex->uvn) xuvn = B.add<2>(ex->uvn, nobs);
+  if (ex && ex->flags) xfl = B.add(ex->flags, F);
+  TRY(S.add_res_noise(tr->res_Q, tr->res_clone, nobs));
+  if (spec) {
+    sli = B.add(ex->spec_li, F), sme = B.add(ex->spec_meta, F), spv = B.add(ex->spec_prevalid, F);
+    send = B.add(tr->obs_ptr + 1, F);  // (overwritten by spec_select_kernel)
   }
-  memcpy(h + o_time, st->clone_time, 8 * N);
-  memcpy(h + o_R, st->clone_R, 72 * N);
-  memcpy(h + o_p, st->clone_p, 24 * N);
-  memcpy(h + o_Rf, st->clone_R_fej, 72 * N);
-  memcpy(h + o_pf, st->clone_p_fej, 24 * N);
-  int *ccol = (int *)(h + o_ccol);
-  for (int i = 0; i < N; ++i) ccol[i] = col_of(st->clone_state_id[i]);
-  memcpy(h + o_ptr, tr->obs_ptr, 4 * (F + 1));
-  int *of = (int *)(h + o_of);
+  Staging &sg = us->staging_of(3);
+  TRY(S.pack(sg));
+  int *of_h = B.host(of);
   for (int f = 0; f < F; ++f) {
     if (tr->obs_ptr[f + 1] < tr->obs_ptr[f]) return PLV_E_BADARG;
-    for (int o = tr->obs_ptr[f]; o < tr->obs_ptr[f + 1]; ++o) of[o] = f;
-  }
-  memcpy(h + o_ot, tr->obs_time, 8 * nobs);
-  memcpy(h + o_uv, tr->obs_uv, 8 * nobs);
-  memcpy(h + o_pg, tr->p_FinG, 24 * F);
-  memcpy(h + o_pgf, tr->p_FinG_fej, 24 * F);
-  if (tr->res_R) {
-    memcpy(h + o_rR, tr->res_R, 72 * nobs);
-    memcpy(h + o_rp, tr->res_p, 24 * nobs);
-  }
-  if (tr->res_Q) {
-    if (!tr->res_clone) return PLV_E_BADARG;
-    memcpy(h + o_rQ, tr->res_Q, 288 * (size_t)nobs);
-    memcpy(h + o_rc, tr->res_clone, 4 * (size_t)nobs);
+    for (int o = tr->obs_ptr[f]; o < tr->obs_ptr[f + 1]; ++o) of_h[o] = f;
   }
   // (an upload by a kernel of the ctx stream instead of the copy command was measured, alternating frame by frame: no difference)
-  if (ex && ex->spec_li) {
+  if (spec) {
     // the speculative batch is staged while the frame's flow occupies the ctx stream: its upload goes onto a stream of its own at once
     // (a copy command behind the flow would sit between the flow's last kernel and the update's first); the ctx stream waits for it
     if (!us->spec_stream) {
       PLV_HIP_CHECK(hipStreamCreateWithFlags(&us->spec_stream, hipStreamNonBlocking));
       PLV_HIP_CHECK(hipEventCreateWithFlags(&us->spec_ev, hipEventDisableTiming));
     }
-    PLV_HIP_CHECK(plv::memcpy_async(us->jin.p, h, total, hipMemcpyHostToDevice, us->spec_stream));
+    PLV_HIP_CHECK(plv::memcpy_async(sg.jin.p, sg.h_jin.p, B.total(), hipMemcpyHostToDevice, us->spec_stream));
     PLV_HIP_CHECK(hipEventRecord(us->spec_ev, us->spec_stream));
     PLV_HIP_CHECK(hipStreamWaitEvent(ctx->stream, us->spec_ev, 0));
   } else
-    PLV_HIP_CHECK(plv::memcpy_async(us->jin.p, h, total, hipMemcpyHostToDevice, ctx->stream));
-  const char *d = us->jin.as<char>();
-  P.n_clones = N;
-  P.clone_time = (const double *)(d + o_time);
-  P.clone_R = (const double *)(d + o_R);
-  P.clone_p = (const double *)(d + o_p);
-  P.clone_R_fej = (const double *)(d + o_Rf);
-  P.clone_p_fej = (const double *)(d + o_pf);
-  P.clone_col = (const int *)(d + o_ccol);
-  memcpy(P.R_ItoC, st->R_ItoC, 72);
-  memcpy(P.p_IinC, st->p_IinC, 24);
-  memcpy(P.K, st->intrinsics, 64);
-  P.cam_model = ctx->cam_model;
-  P.cam_dt = st->cam_dt;
-  P.dt_exp = st->dt_exp;
-  P.sigma_pix = st->sigma_pix;
-  P.intr_ori_cov = st->intr_ori_cov;
-  P.intr_pos_cov = st->intr_pos_cov;
-  P.use_pol_cov = st->use_pol_cov;
-  P.use_imu_cov = st->use_imu_cov && tr->res_Q ? 1 : 0;
-  P.intr_err_mlt = st->intr_err_mlt;
-  P.res_Q = tr->res_Q ? (const double *)(d + o_rQ) : nullptr;
-  P.res_clone = tr->res_Q ? (const int *)(d + o_rc) : nullptr;
-  P.feat_rep = st->feat_rep;
-  P.col_ext = col_of(st->extrinsic_state_id);
-  P.col_int = col_of(st->intrinsic_state_id);
-  P.col_dt = col_of(st->dt_state_id);
+    PLV_HIP_CHECK(plv::memcpy_async(sg.jin.p, sg.h_jin.p, B.total(), hipMemcpyHostToDevice, ctx->stream));
+  S.fill(P, ctx, ld);
+  P.col_ext = S.col_of(st->extrinsic_state_id);
+  P.col_int = S.col_of(st->intrinsic_state_id);
   P.n_feat = F;
   P.n_obs = nobs;
-  P.obs_ptr = (const int *)(d + o_ptr);
-  P.obs_feat = (const int *)(d + o_of);
-  P.obs_time = (const double *)(d + o_ot);
-  P.obs_uv = (const float *)(d + o_uv);
-  P.p_FinG = (const double *)(d + o_pg);
-  P.p_FinG_fej = (const double *)(d + o_pgf);
-  P.res_R = tr->res_R ? (const double *)(d + o_rR) : nullptr;
-  P.res_p = tr->res_R ? (const double *)(d + o_rp) : nullptr;
-  P.k = k;
-  P.ld = ld;
-  P.cols_in = (const int *)(d + o_cols);
-  P.cols_out = nullptr;
-  P.in_base = d;
+  P.obs_ptr = B.dev(ptr), P.obs_feat = B.dev(of), P.obs_time = B.dev(ot), P.obs_uv = B.dev(uv);
+  P.p_FinG = B.dev(pg), P.p_FinG_fej = B.dev(pgf);
   // (what every workgroup touches first thing: the whole block — or, of a speculative batch, whose block holds every candidate's
   //  observations, the state and the ranges in front of them)
-  P.in_bytes = (ex && ex->spec_li) ? (int)o_of : (int)total;
+  if (spec) P.in_bytes = (int)B.offset(of);
   if (ex) {
-    ex->d_uvn = ex->uvn ? (const float *)(d + o_xuvn) : nullptr;
-    ex->d_flags = ex->flags ? (const uint8_t *)(d + o_xfl) : nullptr;
-    if (ex->spec_li) {
-      ex->d_spec_li = (const int *)(d + o_sli), ex->d_spec_meta = (const uint8_t *)(d + o_sme), ex->d_spec_prevalid = (const uint8_t *)(d + o_spv);
-      ex->d_obs_end = (int *)(us->jin.as<char>() + o_send), ex->d_obs_uv = (float *)(us->jin.as<char>() + o_uv);
+    ex->d_uvn = B.dev(xuvn), ex->d_flags = B.dev(xfl);
+    if (spec) {
+      ex->d_spec_li = B.dev(sli), ex->d_spec_meta = B.dev(sme), ex->d_spec_prevalid = B.dev(spv);
+      ex->d_obs_end = const_cast<int *>(B.dev(send)), ex->d_obs_uv = const_cast<float *>(B.dev(uv));
       P.obs_end = ex->d_obs_end;
     }
   }
   return PLV_OK;
 }
 
-// builds the batch into us->bHf ([Hf | Hx | res]) and us->brows on the device
 // the column map as the host staged it: same offset in the pinned block as in the device copy (or the pinned block itself)
-static const int *host_copy_of(plv_ctx_update_state *us, const int *cols_in, bool lines = false) {
-  plv::PinBuf &hb = lines ? us->h_jin_l : us->h_jin;
-  plv::DevBuf &db = lines ? us->jin_l : us->jin;
-  const char *c = (const char *)cols_in, *hj = hb.as<char>();
-  if (c >= hj && c < hj + hb.cap) return cols_in;
-  return (const int *)(hj + (c - db.as<char>()));
+const int *host_copy_of(plv_ctx_update_state *us, const int *cols_in, int fdim) {
+  Staging &sg = us->staging_of(fdim);
+  const char *c = (const char *)cols_in, *hj = sg.h_jin.as<char>();
+  if (c >= hj && c < hj + sg.h_jin.cap) return cols_in;
+  return (const int *)(hj + (c - sg.jin.as<char>()));
 }
+
+// A batch of n features of measurement size fdim (3 points, 6 lines) is built into us->bHf ([Hf | Hx | res]) and us->brows on the device
+int reserve_batch(plv_ctx *ctx, plv_ctx_update_state *us, int n, int fdim, int k, int ld) {
+  TRY(us->bHf.reserve_units((size_t)n, (size_t)std::max(ctx->cfg.num_features, 64), (size_t)(fdim + k + 1) * ld * 8));
+  TRY(us->brows.reserve((size_t)n * 4));
+  return us->bcols_of(fdim).reserve((size_t)k * 4);
+}
+// Launches the staged batch and books it in us->b*.  project (resident update path): build + null-space projection in one launch,
+// launch_projected(gather, gblocks) — the column map is published by its workgroup 0, and when a covariance of matching size is
+// resident its gathers ride along; prior_ahead: the prior factor's second phase follows on the side stream.  Else launch_plain().
+// ph_launch / ph_prior: labels of the two host phases (null: not timed).
+template <class Projected, class Plain>
+int launch_batch(plv_ctx *ctx, plv_ctx_update_state *us, JacParams &P, int n, int fdim, int k, const int *col_to_state, int ld, bool project,
+                 bool prior_ahead, const char *ph_launch, const char *ph_prior, Projected launch_projected, Plain launch_plain) {
+  P.rows = us->brows.as<int>();
+  P.Hf = us->bHf.as<double>();
+  P.Hx = P.Hf + (size_t)n * fdim * ld;
+  P.res = P.Hx + (size_t)n * k * ld;
+  us->b_projected = false;
+  us->b_gather_token = 0;
+  if (project) {
+    P.cols_out = us->bcols_of(fdim).as<int>();
+    bool can_gather = ctx->cov_n > 0;
+    for (int j = 0; j < k && can_gather; ++j) can_gather = col_to_state[j] >= 0 && col_to_state[j] < ctx->cov_n;
+    GatherArgs g{};
+    int gblocks = 0;
+    plv::HostPhase ph_l(ph_launch);
+    if (can_gather) {
+      const int cn = ctx->cov_n;
+      TRY(gather_args(ctx, ctx->d_P.as<double>(), cn, cn, P.cols_in, k, g));
+      gblocks = (std::max(k * cn, std::max(k * k, cn)) + 255) / 256;
+    }
+    TRY(launch_projected(can_gather ? &g : nullptr, gblocks));
+    ph_l.stop();
+    plv::HostPhase ph_p1(ph_prior);
+    if (can_gather && prior_ahead) TRY(plv_prior_prefetch(ctx, 1, host_copy_of(us, P.cols_in, fdim), k, n, ld - fdim));
+    ph_p1.stop();
+    us->b_projected = true;
+    us->b_gather_token = can_gather ? ctx->gather_stamp : 0;
+  } else {
+    TRY(launch_plain());
+  }
+  us->bF = n;
+  us->bfdim = fdim;
+  us->bk = k;
+  us->bld = ld;
+  us->bmaxrows = ld;
+  us->b_on_device_rows = true;
+  return PLV_OK;
+}
+// host out: the un-projected systems of the batch just built
+int download_batch(plv_ctx *ctx, plv_ctx_update_state *us, int n, int fdim, int k, int ld, int *rows, double *Hf, double *Hx, double *res) {
+  const size_t nHf = (size_t)n * fdim * ld, nHx = (size_t)n * k * ld, nr = (size_t)n * ld;
+  const double *d = us->bHf.as<double>();
+  PLV_HIP_CHECK(plv::memcpy_async(Hf, d, nHf * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(Hx, d + nHf, nHx * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(res, d + nHf + nHx, nr * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(rows, us->brows.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
+  ctx->prof.collect();
+  return PLV_OK;
+}
+
 struct FusedTri {  // triangulate on the device first and let the Jacobian launch take its candidates from the result
   const plv_tri_options *opt;
   const float *uvn;
   const uint8_t *flags;
   int max_sel;
-  size_t o_p, o_err, o_ok;  // out: where the results sit in us->tri (p [F][3], err [F], ok [F], contiguous)
+  size_t o_p, o_err, o_ok;  // out: where the results sit in the point staging's tri (p [F][3], err [F], ok [F], contiguous)
   const plv_points_spec *spec = nullptr;  // speculative submission: the candidates' membership is decided on the device (spec_select_kernel)
   size_t o_member = 0, o_words = 0;       // out (spec): member [F] and the words (SpecSelectArgs) behind ok, part of the mirrored result block
   const int *d_words = nullptr;           // out (spec): the words on the device
@@ -210,23 +319,20 @@ int build_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view
   TRY(check_views(st, tr));
   if (k < 1 || ld < 2 || !col_to_state) return PLV_E_BADARG;
   const int F = tr->n_feat;
-  const size_t nHf = (size_t)F * 3 * ld, nHx = (size_t)F * k * ld;
-  TRY(us->bHf.reserve_units((size_t)F, (size_t)std::max(ctx->cfg.num_features, 64), (size_t)(3 + k + 1) * ld * 8));
-  TRY(us->brows.reserve((size_t)F * 4));
-  TRY(us->bcols.reserve((size_t)k * 4));
+  TRY(reserve_batch(ctx, us, F, 3, k, ld));
+  const bool prior_ahead = project && ctx->cov_n > 0;
   {
     plv::HostPhase ph("build: prior prefetch, phase 0");
-    if (project && ctx->cov_n > 0) TRY(plv_prior_prefetch(ctx, 0, nullptr, k, F, ld - 3));  // (before the upload goes onto the stream)
+    if (prior_ahead) TRY(plv_prior_prefetch(ctx, 0, nullptr, k, F, ld - 3));  // (before the upload goes onto the stream)
   }
   plv::HostPhase ph_stage("build: inputs staged + upload enqueued");
   JacParams P{};
   bool fuse_tri = false;
-  int tri_max_obs = 1;
   double *tri_poses = nullptr, *tri_p = nullptr, *tri_err = nullptr;
   unsigned char *tri_valid = nullptr, *tri_ok = nullptr;
   const float *tri_uvn = nullptr;
   const plv_tri_options *tri_opt = nullptr;
-  for (int f = 0; f < F; ++f) tri_max_obs = std::max(tri_max_obs, tr->obs_ptr[f + 1] - tr->obs_ptr[f]);  // (sizes the launch's LDS)
+  const int tri_max_obs = max_obs(tr->obs_ptr, F);
   if (ft) {
     StageExtra ex;
     ex.uvn = ft->uvn;
@@ -237,8 +343,9 @@ int build_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view
     const size_t o_pose = 0, o_valid = (size_t)nobs * 96, o_p = (o_valid + nobs + 15) & ~(size_t)15, o_err = o_p + (size_t)F * 24,
                  o_ok = o_err + (size_t)F * 8, o_member = o_ok + F, o_words = (o_member + F + 7) & ~(size_t)7, o_order = o_words + 32,
                  total = o_order + 4 * (size_t)spec_grid(ft->max_sel) + 16;
-    TRY(us->tri.reserve(total));
-    char *d = us->tri.as<char>();
+    plv::DevBuf &tri = us->staging_of(3).tri;
+    TRY(tri.reserve(total));
+    char *d = tri.as<char>();
     ft->o_member = o_member, ft->o_words = o_words;
     // one launch for triangulation + Jacobians + null space while the selection has no cap to enforce (see the kernel); a speculative
     // batch holds more candidates than the cap, but its pool does not (spec_select_kernel empties every candidate otherwise)
@@ -281,51 +388,22 @@ int build_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view
     P.tri_err = (const double *)(d + o_err);
     P.max_sel = ft->max_sel;
     ft->o_p = o_p, ft->o_err = o_err, ft->o_ok = o_ok;
-
   } else {
     TRY(stage_inputs(ctx, us, st, tr, k, col_to_state, ld, P));
   }
   ph_stage.stop();
-  P.cols_out = us->bcols.as<int>();
-  P.rows = us->brows.as<int>();
-  P.Hf = us->bHf.as<double>();
-  P.Hx = P.Hf + nHf;
-  P.res = P.Hx + nHx;
-  us->b_projected = false;
-  us->b_gather_token = 0;
-  if (project) {
-    // resident update path: build + project in one launch; when a covariance of matching size is resident its gathers ride along
-    bool can_gather = ctx->cov_n > 0;
-    for (int j = 0; j < k && can_gather; ++j) can_gather = col_to_state[j] >= 0 && col_to_state[j] < ctx->cov_n;
-    GatherArgs g{};
-    int gblocks = 0;
-    plv::HostPhase ph_l("build: gather arguments + Jacobian launch");
-    if (can_gather) {
-      const int n = ctx->cov_n;
-      TRY(gather_args(ctx, ctx->d_P.as<double>(), n, n, P.cols_in, k, g));
-      gblocks = (std::max(k * n, std::max(k * k, n)) + 255) / 256;
-    }
-    if (fuse_tri)
-      TRY(launch_jacobians_projected(ctx, P, can_gather ? &g : nullptr, gblocks, tri_opt, tri_poses, tri_valid, tri_uvn, tri_p, tri_ok, tri_err, tri_max_obs));
-    else
-      TRY(launch_jacobians_projected(ctx, P, can_gather ? &g : nullptr, gblocks, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tri_max_obs));
-    ph_l.stop();
-    plv::HostPhase ph_p1("build: prior prefetch, phase 1 (side stream)");
-    if (can_gather)  // (the column map as the host staged it: same offset in the pinned block as in the device copy)
-      TRY(plv_prior_prefetch(ctx, 1, host_copy_of(us, P.cols_in), k, F, ld - 3));
-    ph_p1.stop();
-    us->b_projected = true;
-    us->b_gather_token = can_gather ? ctx->gather_stamp : 0;
-  } else {
-    TRY(launch_jacobians(ctx, P));
-  }
-  us->bF = F;
-  us->bfdim = 3;
-  us->bk = k;
-  us->bld = ld;
-  us->bmaxrows = ld;
-  us->b_on_device_rows = true;
-  return PLV_OK;
+  return launch_batch(
+      ctx, us, P, F, 3, k, col_to_state, ld, project, prior_ahead, "build: gather arguments + Jacobian launch",
+      "build: prior prefetch, phase 1 (side stream)",
+      [&](const GatherArgs *g, int gblocks) {
+        if (fuse_tri)
+          return launch_jacobians_projected(ctx, P, g, gblocks, tri_opt, tri_poses, tri_valid, tri_uvn, tri_p, tri_ok, tri_err, tri_max_obs);
+        return launch_jacobians_projected(ctx, P, g, gblocks, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tri_max_obs);
+      },
+      [&] {
+        P.cols_out = us->bcols.as<int>();
+        return launch_jacobians(ctx, P);
+      });
 }
 
 }  // namespace
@@ -335,31 +413,7 @@ extern "C" {
 int plv_jacobian_columns(const plv_state_view *st, const plv_tracks *tr, int *col_to_state, int cap, int *k_out) {
   if (!col_to_state || !k_out) return PLV_E_BADARG;
   TRY(check_views(st, tr));
-  int k = 0;
-  auto push = [&](int id, int size) {
-    if (id < 0) return true;
-    for (int j = 0; j < k; ++j)
-      if (col_to_state[j] == id) return true;
-    if (k + size > cap) return false;
-    for (int d = 0; d < size; ++d) col_to_state[k++] = id + d;
-    return true;
-  };
-  // REF: CamHelper.cpp:74-95 calibration blocks first, then :98-110 interpolation poses in first-seen order
-  if (!push(st->extrinsic_state_id, 6) || !push(st->intrinsic_state_id, 8) || !push(st->dt_state_id, 1)) return PLV_E_CAPACITY;
-  // (a window start that has been seen adds nothing: 700 observations meet ~14 distinct windows, and the search through the
-  // column list per pose was 29 us of the caller's thread in front of the point launch at configs[2])
-  std::vector<uint8_t> seen_s0((size_t)std::max(st->n_clones, 1), 0);
-  BoundingMemo start_of(*st);
-  for (int f = 0; f < tr->n_feat; ++f)
-    for (int o = tr->obs_ptr[f]; o < tr->obs_ptr[f + 1]; ++o) {
-      const int s0 = start_of(tr->obs_time[o] + st->cam_dt);
-      if (s0 < 0 || seen_s0[s0]) continue;
-      seen_s0[s0] = 1;
-      for (int w = 0; w < 4; ++w)
-        if (!push(st->clone_state_id[s0 + w], 6)) return PLV_E_CAPACITY;
-    }
-  *k_out = k;
-  return PLV_OK;
+  return jacobian_columns(st, tr->n_feat, tr->obs_ptr, tr->obs_time, false, col_to_state, cap, k_out);
 }
 }  // extern "C"
 namespace plv {
@@ -385,6 +439,7 @@ int plv_points_update_submit(plv_ctx *ctx, const plv_state_view *st, const plv_t
   if (!ctx || !all || !tri || !flags || !all->obs_uvn) return PLV_E_BADARG;
   (void)hipSetDevice(ctx->device);
   auto *us = plv_update_state(ctx);
+  auto &sg = us->staging_of(3);
   PointJob &J = point_job(ctx);
   J = PointJob();
   std::vector<double> p_dummy(3 * (size_t)std::max(all->n_feat, 1), 0.0);
@@ -410,11 +465,11 @@ int plv_points_update_submit(plv_ctx *ctx, const plv_state_view *st, const plv_t
   us->b_single_use = true;
   const int F = all->n_feat;
   const size_t mirror_bytes = spec ? (ft.o_words + 20 - ft.o_p) : (size_t)F * 33;
-  TRY(us->h_tri.reserve(mirror_bytes + 16));
+  TRY(sg.h_tri.reserve(mirror_bytes + 16));
   plv::HostPhase ph_b("points fused: gate .. EKF enqueued");
   // the triangulation results reach the host with the update's result block (copied by its last kernel), or by a copy command when
   // the chain ended another way; either lands before the wait below returns
-  ctx->mirror2_src = us->tri.as<char>() + ft.o_p, ctx->mirror2_dst = us->h_tri.p, ctx->mirror2_bytes = mirror_bytes, ctx->mirror2_taken = false;
+  ctx->mirror2_src = sg.tri.as<char>() + ft.o_p, ctx->mirror2_dst = sg.h_tri.p, ctx->mirror2_bytes = mirror_bytes, ctx->mirror2_taken = false;
   // (for a line launch chained behind this update, plv_camera_try_update: the commit kernel leaves "state changed" in a device word)
   TRY(us->chain_words.reserve(64));
   us->applied_word = us->chain_words.as<int>();
@@ -433,11 +488,11 @@ int plv_points_update_submit(plv_ctx *ctx, const plv_state_view *st, const plv_t
   spec_save_arm(ctx, us, false);
   us->applied_armed = rc == PLV_OK && ctx->applied_used;
   ctx->applied_word = nullptr, ctx->applied_used = false;
-  us->pt_tri_p = (const double *)(us->tri.as<char>() + ft.o_p), us->pt_tri_ok = (const unsigned char *)(us->tri.as<char>() + ft.o_ok), us->pt_tri_F = F;
+  us->pt_tri_p = (const double *)(sg.tri.as<char>() + ft.o_p), us->pt_tri_ok = (const unsigned char *)(sg.tri.as<char>() + ft.o_ok), us->pt_tri_F = F;
   const bool mirrored = ctx->mirror2_taken;
   ctx->mirror2_src = nullptr, ctx->mirror2_dst = nullptr, ctx->mirror2_bytes = 0, ctx->mirror2_taken = false;
   if (!mirrored)
-    PLV_HIP_CHECK(plv::memcpy_async(us->h_tri.p, us->tri.as<char>() + ft.o_p, mirror_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    PLV_HIP_CHECK(plv::memcpy_async(sg.h_tri.p, sg.tri.as<char>() + ft.o_p, mirror_bytes, hipMemcpyDeviceToHost, ctx->stream));
   ph_b.stop();
   plv::frame_mark("@ point chain enqueued");
   if (J.chain_events) (void)hipEventRecord(g_ce[2], ctx->stream);
@@ -488,7 +543,7 @@ int plv_points_update_collect(plv_ctx *ctx, double *p_out, uint8_t *ok_out, doub
       plv::host_phases().add("points fused: HOST entry -> results read", host_us);
     }
   }
-  const char *h = us->h_tri.as<char>();
+  const char *h = us->staging_of(3).h_tri.as<char>();
   memcpy(p_out, h, (size_t)F * 24);
   memcpy(err_out, h + (size_t)F * 24, (size_t)F * 8);
   memcpy(ok_out, h + (size_t)F * 32, (size_t)F);
@@ -551,18 +606,9 @@ int plv_build_jacobians(plv_ctx *ctx, const plv_state_view *st, const plv_tracks
   if (!ctx || !rows || !Hf || !Hx || !res) return PLV_E_BADARG;
   (void)hipSetDevice(ctx->device);
   auto *us = plv_update_state(ctx);
-  TRY(build_on_device(ctx, us, st, tr, k, col_to_state, ld, false));  // host out: the un-projected systems
+  TRY(build_on_device(ctx, us, st, tr, k, col_to_state, ld, false));
   us->b_single_use = false;
-  const int F = tr->n_feat;
-  const size_t nHf = (size_t)F * 3 * ld, nHx = (size_t)F * k * ld, nr = (size_t)F * ld;
-  const double *d = us->bHf.as<double>();
-  PLV_HIP_CHECK(plv::memcpy_async(Hf, d, nHf * 8, hipMemcpyDeviceToHost, ctx->stream));
-  PLV_HIP_CHECK(plv::memcpy_async(Hx, d + nHf, nHx * 8, hipMemcpyDeviceToHost, ctx->stream));
-  PLV_HIP_CHECK(plv::memcpy_async(res, d + nHf + nHx, nr * 8, hipMemcpyDeviceToHost, ctx->stream));
-  PLV_HIP_CHECK(plv::memcpy_async(rows, us->brows.p, (size_t)F * 4, hipMemcpyDeviceToHost, ctx->stream));
-  PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
-  ctx->prof.collect();
-  return PLV_OK;
+  return download_batch(ctx, us, tr->n_feat, 3, k, ld, rows, Hf, Hx, res);
 }
 
 
@@ -586,13 +632,11 @@ int plv_triangulate(plv_ctx *ctx, const plv_state_view *st, const plv_tracks *tr
   TRY(stage_inputs(ctx, us, st, &t2, 0, dummy_cols, 2, P));
   const size_t o_pose = 0, o_valid = (size_t)nobs * 96, o_uvn = (o_valid + nobs + 15) & ~(size_t)15, o_p = o_uvn + (size_t)nobs * 8,
                o_err = o_p + (size_t)F * 24, o_ok = o_err + (size_t)F * 8, total = o_ok + F + 16;
-  TRY(us->tri.reserve(total));
-  char *d = us->tri.as<char>();
+  TRY(us->staging_of(3).tri.reserve(total));
+  char *d = us->staging_of(3).tri.as<char>();
   PLV_HIP_CHECK(plv::memcpy_async(d + o_uvn, tr->obs_uvn, (size_t)nobs * 8, hipMemcpyHostToDevice, ctx->stream));
-  int max_obs = 1;
-  for (int f = 0; f < F; ++f) max_obs = std::max(max_obs, tr->obs_ptr[f + 1] - tr->obs_ptr[f]);
   TRY(launch_triangulate(ctx, P, (double *)(d + o_pose), (unsigned char *)(d + o_valid), (const float *)(d + o_uvn), *opt,
-                         (double *)(d + o_p), (unsigned char *)(d + o_ok), (double *)(d + o_err), max_obs));
+                         (double *)(d + o_p), (unsigned char *)(d + o_ok), (double *)(d + o_err), max_obs(tr->obs_ptr, F)));
   PLV_HIP_CHECK(plv::memcpy_async(p_FinG, d + o_p, (size_t)F * 24, hipMemcpyDeviceToHost, ctx->stream));
   PLV_HIP_CHECK(plv::memcpy_async(ok, d + o_ok, (size_t)F, hipMemcpyDeviceToHost, ctx->stream));
   if (reproj_err) PLV_HIP_CHECK(plv::memcpy_async(reproj_err, d + o_err, (size_t)F * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -607,17 +651,9 @@ namespace {
 
 // ------------------------------------------------------------------------------------------ lines
 int check_line_views(const plv_state_view *st, const plv_line_tracks *lt, bool need_lines, bool need_uvn) {
-  if (!st || !lt || st->n_clones < 1 || !st->clone_time || !st->clone_R || !st->clone_p || !st->clone_R_fej ||
-      !st->clone_p_fej || !st->clone_state_id || lt->n_lines < 1 || !lt->obs_ptr || !lt->obs_time || !lt->seg_uv ||
-      (need_lines && !lt->line_FinG) || (need_uvn && !lt->seg_uvn)) {
-    set_last_error("line jacobians: null view field");
-    return PLV_E_BADARG;
-  }
-  if (st->intr_order != 3) {
-    set_last_error("line jacobians: only intr_order = 3 is built (got %d)", st->intr_order);
-    return PLV_E_BADARG;
-  }
-  if ((lt->res_R == nullptr) != (lt->res_p == nullptr)) return PLV_E_BADARG;
+  TRY(check_views("line jacobians", st, lt, [=](const plv_line_tracks &t) {
+    return t.n_lines >= 1 && t.obs_ptr && t.obs_time && t.seg_uv && !(need_lines && !t.line_FinG) && !(need_uvn && !t.seg_uvn);
+  }));
   if (lt->has_pt && !lt->anchor_pt) return PLV_E_BADARG;
   return PLV_OK;
 }
@@ -633,153 +669,67 @@ int stage_line_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_vi
     set_last_error("line jacobians: no observations");
     return PLV_E_BADARG;
   }
-  auto col_of = [&](int sid) {
-    if (sid < 0) return -1;
-    for (int j = 0; j < k; ++j)
-      if (col_to_state[j] == sid) return j;
-    return -1;
-  };
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 15) & ~(size_t)15;
-    return o;
-  };
-  const size_t o_time = take(8 * N), o_R = take(72 * N), o_p = take(24 * N), o_Rf = take(72 * N), o_pf = take(24 * N),
-               o_ccol = take(4 * N), o_ptr = take(4 * (L + 1)), o_ot = take(8 * nobs), o_uv = take(16 * nobs),
-               o_uvn = lt->seg_uvn ? take(16 * nobs) : 0, o_lg = lt->line_FinG ? take(48 * L) : 0,
-               o_D = lt->D ? take(4 * L) : 0, o_ap = lt->has_pt ? take(24 * L) : 0, o_hp = lt->has_pt ? take(L) : 0,
-               o_rR = lt->res_R ? take(72 * nobs) : 0, o_rp = lt->res_R ? take(24 * nobs) : 0,
-               o_rQ = lt->res_Q ? take(288 * (size_t)nobs) : 0, o_rc = lt->res_Q ? take(4 * (size_t)nobs) : 0,
-               o_cols = take(4 * (size_t)k), o_xfl = ex && ex->flags ? take(L) : 0;
+  for (int l = 0; l < L; ++l)
+    if (lt->obs_ptr[l + 1] < lt->obs_ptr[l]) return PLV_E_BADARG;
+  StageBlock B;
+  StateStage S{B, st, k, col_to_state};
+  S.add_clones();
+  const auto ptr = B.add(lt->obs_ptr, L + 1);
+  const auto ot = B.add(lt->obs_time, nobs);
+  const auto uv = B.add<4>(lt->seg_uv, nobs);
+  StageBlock::Slot<float> uvn;
+  StageBlock::Slot<double> lg, ap, tR, tp, cq, aold;
+  StageBlock::Slot<int> D, cid, aptr, af;
+  StageBlock::Slot<uint8_t> hp, xfl, aho;
+  if (lt->seg_uvn) uvn = B.add<4>(lt->seg_uvn, nobs);
+  if (lt->line_FinG) lg = B.add<6>(lt->line_FinG, L);
+  if (lt->D) D = B.add(lt->D, L);
+  if (lt->has_pt) ap = B.add<3>(lt->anchor_pt, L), hp = B.add(lt->has_pt, L);
+  S.add_res_poses(lt->res_R, lt->res_p, nobs);
+  TRY(S.add_res_noise(lt->res_Q, lt->res_clone, nobs));
+  S.add_cols();
+  if (ex && ex->flags) xfl = B.add(ex->flags, L);
   const bool two_states = st_tri && Pt && st_tri != st && st_tri->n_clones == N;
-  const size_t o_tR = two_states ? take(72 * N) : 0, o_tp = two_states ? take(24 * N) : 0;
+  if (two_states) tR = B.add<9>(st_tri->clone_R, N), tp = B.add<3>(st_tri->clone_p, N);
   // chained launch (plv_ctx::chain): quaternions + covariance indices for the kernel's own x (+) dx, anchor candidates
   const plv_ctx::ChainState &ch = ctx->chain;
   const bool chained = ch.on && ch.ready && !two_states && (int)ch.q.size() == 4 * N && (int)ch.ids.size() == N + 3 && (int)ch.anc_ptr.size() == L + 1;
-  const size_t n_anc = chained ? ch.anc_f.size() : 0;
-  const size_t o_cq = chained ? take(32 * (size_t)N) : 0, o_cid = chained ? take(4 * (size_t)(N + 3)) : 0, o_aptr = chained ? take(4 * (size_t)(L + 1)) : 0,
-               o_af = chained ? take(4 * n_anc + 4) : 0, o_aho = chained ? take(n_anc + 4) : 0, o_aold = chained ? take(24 * n_anc + 8) : 0;
   if (ch.on && !chained) {
     set_last_error("line jacobians: chained launch asked for without its state");
     return PLV_E_BADARG;
   }
-  const size_t total = off;
-  TRY(us->h_jin_l.reserve(total));
-  TRY(us->jin_l.reserve(total));
-  char *h = us->h_jin_l.as<char>();
-  memcpy(h + o_cols, col_to_state, 4 * (size_t)k);
-  if (ex && ex->flags) memcpy(h + o_xfl, ex->flags, L);
-  if (two_states) {
-    memcpy(h + o_tR, st_tri->clone_R, 72 * N);
-    memcpy(h + o_tp, st_tri->clone_p, 24 * N);
-  }
   if (chained) {
-    memcpy(h + o_cq, ch.q.data(), 32 * (size_t)N);
-    memcpy(h + o_cid, ch.ids.data(), 4 * (size_t)(N + 3));
-    memcpy(h + o_aptr, ch.anc_ptr.data(), 4 * (size_t)(L + 1));
-    if (n_anc) {
-      memcpy(h + o_af, ch.anc_f.data(), 4 * n_anc);
-      memcpy(h + o_aho, ch.anc_has_old.data(), n_anc);
-      memcpy(h + o_aold, ch.anc_old.data(), 24 * n_anc);
-    }
+    const size_t n_anc = ch.anc_f.size();  // (possibly none: a spare value keeps the three arrays apart)
+    cq = B.add<4>(ch.q.data(), N), cid = B.add(ch.ids.data(), N + 3), aptr = B.add(ch.anc_ptr.data(), L + 1);
+    af = B.add(ch.anc_f.data(), n_anc, 1), aho = B.add(ch.anc_has_old.data(), n_anc, 4), aold = B.add<3>(ch.anc_old.data(), n_anc, 1);
   }
-  memcpy(h + o_time, st->clone_time, 8 * N);
-  memcpy(h + o_R, st->clone_R, 72 * N);
-  memcpy(h + o_p, st->clone_p, 24 * N);
-  memcpy(h + o_Rf, st->clone_R_fej, 72 * N);
-  memcpy(h + o_pf, st->clone_p_fej, 24 * N);
-  int *ccol = (int *)(h + o_ccol);
-  for (int i = 0; i < N; ++i) ccol[i] = col_of(st->clone_state_id[i]);
-  for (int l = 0; l < L; ++l)
-    if (lt->obs_ptr[l + 1] < lt->obs_ptr[l]) return PLV_E_BADARG;
-  memcpy(h + o_ptr, lt->obs_ptr, 4 * (L + 1));
-  memcpy(h + o_ot, lt->obs_time, 8 * nobs);
-  memcpy(h + o_uv, lt->seg_uv, 16 * nobs);
-  if (lt->seg_uvn) memcpy(h + o_uvn, lt->seg_uvn, 16 * nobs);
-  if (lt->line_FinG) memcpy(h + o_lg, lt->line_FinG, 48 * L);
-  if (lt->D) memcpy(h + o_D, lt->D, 4 * L);
-  if (lt->has_pt) {
-    memcpy(h + o_ap, lt->anchor_pt, 24 * L);
-    memcpy(h + o_hp, lt->has_pt, L);
-  }
-  if (lt->res_R) {
-    memcpy(h + o_rR, lt->res_R, 72 * nobs);
-    memcpy(h + o_rp, lt->res_p, 24 * nobs);
-  }
-  if (lt->res_Q) {
-    if (!lt->res_clone) return PLV_E_BADARG;
-    memcpy(h + o_rQ, lt->res_Q, 288 * (size_t)nobs);
-    memcpy(h + o_rc, lt->res_clone, 4 * (size_t)nobs);
-  }
+  Staging &sg = us->staging_of(6);
+  TRY(S.pack(sg));
   // (an upload by a kernel of the ctx stream instead of the copy command was measured, alternating frame by frame: no difference)
-  PLV_HIP_CHECK(plv::memcpy_async(us->jin_l.p, h, total, hipMemcpyHostToDevice, ctx->stream));
-  const char *d = us->jin_l.as<char>();
-  P.n_clones = N;
-  P.clone_time = (const double *)(d + o_time);
-  P.clone_R = (const double *)(d + o_R);
-  P.clone_p = (const double *)(d + o_p);
-  P.clone_R_fej = (const double *)(d + o_Rf);
-  P.clone_p_fej = (const double *)(d + o_pf);
-  P.clone_col = (const int *)(d + o_ccol);
-  memcpy(P.R_ItoC, st->R_ItoC, 72);
-  memcpy(P.p_IinC, st->p_IinC, 24);
-  memcpy(P.K, st->intrinsics, 64);
-  P.cam_model = ctx->cam_model;
-  P.cam_dt = st->cam_dt;
-  P.dt_exp = st->dt_exp;
-  P.sigma_pix = st->sigma_pix;
-  P.intr_ori_cov = st->intr_ori_cov;
-  P.intr_pos_cov = st->intr_pos_cov;
-  P.use_pol_cov = st->use_pol_cov;
-  P.use_imu_cov = st->use_imu_cov && lt->res_Q ? 1 : 0;
-  P.intr_err_mlt = st->intr_err_mlt;
-  P.res_Q = lt->res_Q ? (const double *)(d + o_rQ) : nullptr;
-  P.res_clone = lt->res_Q ? (const int *)(d + o_rc) : nullptr;
-  P.feat_rep = st->feat_rep;
+  PLV_HIP_CHECK(plv::memcpy_async(sg.jin.p, sg.h_jin.p, B.total(), hipMemcpyHostToDevice, ctx->stream));
+  S.fill(P, ctx, ld);
   P.col_ext = P.col_int = -1;
-  P.col_dt = col_of(st->dt_state_id);
   P.n_feat = L;
   P.n_obs = nobs;
-  P.obs_ptr = (const int *)(d + o_ptr);
-  P.obs_time = (const double *)(d + o_ot);
-  P.seg_uv = (const float *)(d + o_uv);
-  P.seg_uvn = lt->seg_uvn ? (const float *)(d + o_uvn) : nullptr;
-  P.line_FinG = lt->line_FinG ? (const double *)(d + o_lg) : nullptr;
-  P.lineD = lt->D ? (const int *)(d + o_D) : nullptr;
-  P.anchor_pt = lt->has_pt ? (const double *)(d + o_ap) : nullptr;
-  P.has_pt = lt->has_pt ? (const unsigned char *)(d + o_hp) : nullptr;
-  P.res_R = lt->res_R ? (const double *)(d + o_rR) : nullptr;
-  P.res_p = lt->res_R ? (const double *)(d + o_rp) : nullptr;
-  P.k = k;
-  P.ld = ld;
-  P.cols_in = (const int *)(d + o_cols);
-  P.in_base = d;
-  P.in_bytes = (int)total;
-  P.cols_out = nullptr;
+  P.obs_ptr = B.dev(ptr), P.obs_time = B.dev(ot), P.seg_uv = B.dev(uv), P.seg_uvn = B.dev(uvn);
+  P.line_FinG = B.dev(lg), P.lineD = B.dev(D), P.anchor_pt = B.dev(ap), P.has_pt = B.dev(hp);
   if (chained) {
-    auto *us2 = us;
-    P.chain_dx = us2->result.as<double>();  // (dx leads the status block of the update launched last: the point update)
-    P.chain_applied = us2->applied_word;
-    P.chain_status = (const int *)(us2->result.as<char>() + (size_t)ctx->cov_n * 8);
-    P.chain_q = (const double *)(d + o_cq);
-    P.chain_id = (const int *)(d + o_cid);
-    memcpy(P.chain_qe, ch.qe, 32);
-    P.anc_ptr = (const int *)(d + o_aptr);
-    P.anc_f = (const int *)(d + o_af);
-    P.anc_has_old = (const unsigned char *)(d + o_aho);
-    P.anc_old = (const double *)(d + o_aold);
-    P.anc_tri_p = us2->pt_tri_p;
-    P.anc_tri_ok = us2->pt_tri_ok;
+    P.chain_dx = us->result.as<double>();  // (dx leads the status block of the update launched last: the point update)
+    P.chain_applied = us->applied_word;
+    P.chain_status = (const int *)(us->result.as<char>() + (size_t)ctx->cov_n * 8);
+    P.chain_q = B.dev(cq), P.chain_id = B.dev(cid);
+    memcpy(P.chain_qe, ch.qe, sizeof P.chain_qe);
+    P.anc_ptr = B.dev(aptr), P.anc_f = B.dev(af), P.anc_has_old = B.dev(aho), P.anc_old = B.dev(aold);
+    P.anc_tri_p = us->pt_tri_p;
+    P.anc_tri_ok = us->pt_tri_ok;
   }
-  if (ex) ex->d_flags = ex->flags ? (const uint8_t *)(d + o_xfl) : nullptr;
+  if (ex) ex->d_flags = B.dev(xfl);
   if (Pt) {
     *Pt = P;
     if (two_states) {
-      Pt->clone_R = (const double *)(d + o_tR);
-      Pt->clone_p = (const double *)(d + o_tp);
-      memcpy(Pt->R_ItoC, st_tri->R_ItoC, 72);
-      memcpy(Pt->p_IinC, st_tri->p_IinC, 24);
+      Pt->clone_R = B.dev(tR), Pt->clone_p = B.dev(tp);
+      memcpy(Pt->R_ItoC, st_tri->R_ItoC, sizeof Pt->R_ItoC);
+      memcpy(Pt->p_IinC, st_tri->p_IinC, sizeof Pt->p_IinC);
       Pt->cam_dt = st_tri->cam_dt;
     }
   }
@@ -789,7 +739,7 @@ int stage_line_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_vi
 struct FusedLineTri {
   const uint8_t *flags;
   int max_sel;
-  size_t o_lines, o_ok;  // out: results in us->tri (lines [L][6], ok [L])
+  size_t o_lines, o_ok;  // out: results in the line staging's tri (lines [L][6], ok [L])
   const plv_state_view *st_tri = nullptr;  // the state of the triangulation when it is not the one of the Jacobians
 };
 int build_lines_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *st, const plv_line_tracks *lt, int k,
@@ -797,10 +747,7 @@ int build_lines_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_stat
   TRY(check_line_views(st, lt, ft == nullptr, ft != nullptr));
   if (k < 1 || ld < 2 || !col_to_state) return PLV_E_BADARG;
   const int L = lt->n_lines;
-  const size_t nHf = (size_t)L * 6 * ld, nHx = (size_t)L * k * ld;
-  TRY(us->bHf.reserve_units((size_t)L, (size_t)std::max(ctx->cfg.num_features, 64), (size_t)(6 + k + 1) * ld * 8));
-  TRY(us->brows.reserve((size_t)L * 4));
-  TRY(us->bcols_l.reserve((size_t)k * 4));
+  TRY(reserve_batch(ctx, us, L, 6, k, ld));
   // The prior factor of the whitened update, ahead of time on the side stream — not for the one-submission line update (gate probe): it
   // accepts a line or two, fewer rows than columns, and then goes through EKFUpdate on the rows themselves (plv_api.hip, round 6); the
   // four enqueue calls were 8-10 us of the caller's thread in front of the line launch, the factor 50 us of side-stream work per frame
@@ -818,14 +765,13 @@ int build_lines_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_stat
     TRY(stage_line_inputs(ctx, us, st, lt, k, col_to_state, ld, P, &ex, ft ? ft->st_tri : nullptr, &Pt));
   }
   plv::HostPhase ph_rest("build lines: gather arguments + launch + prior prefetch");
-  us->b_projected = false;
-  us->b_gather_token = 0;
   if (ft) {
     const int nobs = lt->obs_ptr[L];
     const size_t o_cam = 0, o_imu = (size_t)nobs * 96, o_lines = o_imu + (size_t)nobs * 96, o_ok = o_lines + (size_t)L * 48,
                  o_valid = (o_ok + L + 15) & ~(size_t)15, total = o_valid + nobs + 16;
-    TRY(us->tri_l.reserve(total));
-    char *d = us->tri_l.as<char>();
+    plv::DevBuf &tri = us->staging_of(6).tri;
+    TRY(tri.reserve(total));
+    char *d = tri.as<char>();
     // one launch for triangulation + Jacobians + null space while the selection has no cap to enforce (see the kernel)
     fuse_tri = project && L <= ft->max_sel;
     tri_cam = (double *)(d + o_cam), tri_imu = (double *)(d + o_imu), tri_valid = (unsigned char *)(d + o_valid);
@@ -842,44 +788,17 @@ int build_lines_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_stat
       ctx->gate_stage.probe_stride_a = 48, ctx->gate_stage.probe_off_b = L * 48, ctx->gate_stage.probe_stride_b = 1;
     }
   }
-  P.rows = us->brows.as<int>();
-  P.Hf = us->bHf.as<double>();
-  P.Hx = P.Hf + nHf;
-  P.res = P.Hx + nHx;
-  if (project) {
-    // resident update path: build + project in one launch (the column map is published by its workgroup 0); when a covariance of
-    // matching size is resident its gathers ride along
-    P.cols_out = us->bcols_l.as<int>();
-    bool can_gather = ctx->cov_n > 0;
-    for (int j = 0; j < k && can_gather; ++j) can_gather = col_to_state[j] >= 0 && col_to_state[j] < ctx->cov_n;
-    GatherArgs g{};
-    int gblocks = 0;
-    if (can_gather) {
-      const int n = ctx->cov_n;
-      TRY(gather_args(ctx, ctx->d_P.as<double>(), n, n, P.cols_in, k, g));
-      gblocks = (std::max(k * n, std::max(k * k, n)) + 255) / 256;
-    }
-    int line_max_obs = 1;  // (sizes the launch's LDS)
-    for (int l = 0; l < L; ++l) line_max_obs = std::max(line_max_obs, lt->obs_ptr[l + 1] - lt->obs_ptr[l]);
-    if (fuse_tri)
-      TRY(launch_line_jacobians_projected(ctx, P, can_gather ? &g : nullptr, gblocks, &Pt, tri_cam, tri_imu, tri_valid, tri_lines, tri_ok, line_max_obs));
-    else
-      TRY(launch_line_jacobians_projected(ctx, P, can_gather ? &g : nullptr, gblocks, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, line_max_obs));
-    if (can_gather && prior_ahead)
-      TRY(plv_prior_prefetch(ctx, 1, host_copy_of(us, P.cols_in, true), k, L, ld - 6));
-    us->b_projected = true;
-    us->b_gather_token = can_gather ? ctx->gather_stamp : 0;
-  } else {
-    PLV_HIP_CHECK(plv::memcpy_async(us->bcols_l.p, col_to_state, (size_t)k * 4, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch_line_jacobians(ctx, P));
-  }
-  us->bF = L;
-  us->bfdim = 6;
-  us->bk = k;
-  us->bld = ld;
-  us->bmaxrows = ld;
-  us->b_on_device_rows = true;
-  return PLV_OK;
+  return launch_batch(
+      ctx, us, P, L, 6, k, col_to_state, ld, project, prior_ahead, nullptr, nullptr,
+      [&](const GatherArgs *g, int gblocks) {
+        const int line_max_obs = max_obs(lt->obs_ptr, L);
+        if (fuse_tri) return launch_line_jacobians_projected(ctx, P, g, gblocks, &Pt, tri_cam, tri_imu, tri_valid, tri_lines, tri_ok, line_max_obs);
+        return launch_line_jacobians_projected(ctx, P, g, gblocks, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, line_max_obs);
+      },
+      [&]() -> int {  // (nothing publishes the column map on this route)
+        PLV_HIP_CHECK(plv::memcpy_async(us->bcols_l.p, col_to_state, (size_t)k * 4, hipMemcpyHostToDevice, ctx->stream));
+        return launch_line_jacobians(ctx, P);
+      });
 }
 
 }  // namespace
@@ -897,11 +816,12 @@ int plv_lines_update_fused_submit(plv_ctx *ctx, const plv_state_view *st, const 
   if (!ctx || !all || !flags) return PLV_E_BADARG;
   (void)hipSetDevice(ctx->device);
   auto *us = plv_update_state(ctx);
+  auto &sg = us->staging_of(6);
   FusedLineTri ft{flags, max_sel, 0, 0, st_tri};
   const int L = all->n_lines;
-  TRY(us->h_tri_l.reserve((size_t)L * 49 + 16));
+  TRY(sg.h_tri.reserve((size_t)L * 49 + 16));
   TRY(plv_update_gate_prepare(ctx, L, 6, k, ld, sigma2, chi2_mult, 0.0, 1));
-  ctx->gate_stage.probe_dst = (unsigned char *)us->h_tri_l.p;  // (probe_src and the strides: build_lines_on_device, where the results' place is decided)
+  ctx->gate_stage.probe_dst = (unsigned char *)sg.h_tri.p;  // (probe_src and the strides: build_lines_on_device, where the results' place is decided)
   TRY(build_lines_on_device(ctx, us, st, all, k, col_to_state, ld, true, &ft));
   us->b_single_use = true;
   us->lt_o_lines = ft.o_lines, us->lt_L = L;
@@ -912,18 +832,19 @@ int plv_lines_update_fused_finish(plv_ctx *ctx, double sigma2, double chi2_mult,
   if (!ctx || !lines_out || !ok_out || !accepted || !dx) return PLV_E_BADARG;
   (void)hipSetDevice(ctx->device);
   auto *us = plv_update_state(ctx);
+  auto &sg = us->staging_of(6);
   const int L = us->lt_L;
   // the gate's workgroups leave their verdicts and the triangulated lines in pinned memory and the launch function looks at them
   // before it enqueues compression + EKF (plv_ctx::probe): a line update in which nothing passes the gate ends there
   ctx->probe = true, ctx->probe_done = false;
-  ctx->probe_src = us->tri_l.as<char>() + us->lt_o_lines, ctx->probe_dst = us->h_tri_l.p;
+  ctx->probe_src = sg.tri.as<char>() + us->lt_o_lines, ctx->probe_dst = sg.h_tri.p;
   ctx->probe_stride_a = 48, ctx->probe_off_b = L * 48, ctx->probe_stride_b = 1;
   ctx->probe_hook = before_wait, ctx->probe_hook_arg = before_wait_arg;
   int rc = plv_msckf_update_resident_launch(ctx, sigma2, chi2_mult, 0.0);
   ctx->probe = false, ctx->probe_src = nullptr, ctx->probe_dst = nullptr, ctx->probe_hook = nullptr, ctx->probe_hook_arg = nullptr;
   if (rc == PLV_OK) rc = plv_msckf_update_resident_wait(ctx, accepted, n_rows, dx);
   else PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
-  const char *h = us->h_tri_l.as<char>();
+  const char *h = sg.h_tri.as<char>();
   memcpy(lines_out, h, (size_t)L * 48);
   memcpy(ok_out, h + (size_t)L * 48, (size_t)L);
   return rc;
@@ -943,29 +864,7 @@ extern "C" {
 int plv_line_jacobian_columns(const plv_state_view *st, const plv_line_tracks *lt, int *col_to_state, int cap, int *k_out) {
   if (!col_to_state || !k_out) return PLV_E_BADARG;
   TRY(check_line_views(st, lt, false, false));
-  int k = 0;
-  auto push = [&](int id, int size) {
-    if (id < 0) return true;
-    for (int j = 0; j < k; ++j)
-      if (col_to_state[j] == id) return true;
-    if (k + size > cap) return false;
-    for (int d = 0; d < size; ++d) col_to_state[k++] = id + d;
-    return true;
-  };
-  // REF: LineHelper.cpp:757-788 — `order` of get_interpolated_jacobian: four poses, then the time offset
-  std::vector<uint8_t> seen_s0((size_t)std::max(st->n_clones, 1), 0);  // (see plv_jacobian_columns)
-  BoundingMemo start_of(*st);
-  for (int l = 0; l < lt->n_lines; ++l)
-    for (int o = lt->obs_ptr[l]; o < lt->obs_ptr[l + 1]; ++o) {
-      const int s0 = start_of(lt->obs_time[o] + st->cam_dt);
-      if (s0 < 0 || seen_s0[s0]) continue;
-      seen_s0[s0] = 1;
-      for (int w = 0; w < 4; ++w)
-        if (!push(st->clone_state_id[s0 + w], 6)) return PLV_E_CAPACITY;
-      if (!push(st->dt_state_id, 1)) return PLV_E_CAPACITY;
-    }
-  *k_out = k;
-  return PLV_OK;
+  return jacobian_columns(st, lt->n_lines, lt->obs_ptr, lt->obs_time, true, col_to_state, cap, k_out);
 }
 
 int plv_build_line_jacobians_resident(plv_ctx *ctx, const plv_state_view *st, const plv_line_tracks *lt, int k,
@@ -985,16 +884,7 @@ int plv_build_line_jacobians(plv_ctx *ctx, const plv_state_view *st, const plv_l
   auto *us = plv_update_state(ctx);
   TRY(build_lines_on_device(ctx, us, st, lt, k, col_to_state, ld, false));
   us->b_single_use = false;
-  const int L = lt->n_lines;
-  const size_t nHf = (size_t)L * 6 * ld, nHx = (size_t)L * k * ld, nr = (size_t)L * ld;
-  const double *d = us->bHf.as<double>();
-  PLV_HIP_CHECK(plv::memcpy_async(Hf, d, nHf * 8, hipMemcpyDeviceToHost, ctx->stream));
-  PLV_HIP_CHECK(plv::memcpy_async(Hx, d + nHf, nHx * 8, hipMemcpyDeviceToHost, ctx->stream));
-  PLV_HIP_CHECK(plv::memcpy_async(res, d + nHf + nHx, nr * 8, hipMemcpyDeviceToHost, ctx->stream));
-  PLV_HIP_CHECK(plv::memcpy_async(rows, us->brows.p, (size_t)L * 4, hipMemcpyDeviceToHost, ctx->stream));
-  PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
-  ctx->prof.collect();
-  return PLV_OK;
+  return download_batch(ctx, us, lt->n_lines, 6, k, ld, rows, Hf, Hx, res);
 }
 
 int plv_triangulate_lines(plv_ctx *ctx, const plv_state_view *st, const plv_line_tracks *lt, double *line_FinG,
@@ -1009,8 +899,8 @@ int plv_triangulate_lines(plv_ctx *ctx, const plv_state_view *st, const plv_line
   TRY(stage_line_inputs(ctx, us, st, lt, 0, dummy_cols, 2, P));
   const size_t o_cam = 0, o_imu = (size_t)nobs * 96, o_lines = o_imu + (size_t)nobs * 96, o_valid = o_lines + (size_t)L * 48,
                o_ok = o_valid + ((nobs + 15) & ~(size_t)15), total = o_ok + L + 16;
-  TRY(us->tri.reserve(total));
-  char *d = us->tri.as<char>();
+  TRY(us->staging_of(3).tri.reserve(total));
+  char *d = us->staging_of(3).tri.as<char>();
   TRY(launch_triangulate_lines(ctx, P, (double *)(d + o_cam), (double *)(d + o_imu), (unsigned char *)(d + o_valid),
                                (double *)(d + o_lines), (unsigned char *)(d + o_ok)));
   PLV_HIP_CHECK(plv::memcpy_async(line_FinG, d + o_lines, (size_t)L * 48, hipMemcpyDeviceToHost, ctx->stream));
@@ -1090,8 +980,8 @@ int plv_cpi_poses(plv_ctx *ctx, const plv_state_view *st, const plv_cpi_table *c
   };
   put(cpi->t, n), put(cpi->clone_t, n), put(cpi->dt, n), put(cpi->R_I0toIk, 9 * n), put(cpi->alpha, 3 * n), put(cpi->v, 3 * n);
   put(st->clone_time, nc), put(st->clone_R, 9 * nc), put(st->clone_p, 3 * nc), put(t_q, nq);
-  TRY(us->tri.reserve((in_d + out_d) * sizeof(double) + nq + 16));
-  double *d = us->tri.as<double>();
+  TRY(us->staging_of(3).tri.reserve((in_d + out_d) * sizeof(double) + nq + 16));
+  double *d = us->staging_of(3).tri.as<double>();
   PLV_HIP_CHECK(plv::memcpy_async(d, h.data(), in_d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   CpiParams C{};
   C.n = cpi->n, C.n_clones = st->n_clones, C.n_q = n_q;

@@ -305,19 +305,12 @@ void plv_ctx_destroy(plv_ctx *ctx) {
   if (us) {
     plv::DevBuf *ub[] = {&us->q95, &us->result, &us->result_l, &us->covck, &us->bHf, &us->bHx, &us->bres, &us->brows, &us->bcols, &us->bcols_l, &us->bwork};
     for (auto *b : ub) b->release();
-    us->jin.release();
-    us->tri.release();
-    us->jin_l.release();
-    us->tri_l.release();
-    us->h_jin_l.release();
-    us->h_tri_l.release();
+    for (auto &s : us->stg) s.release();
     us->chain_words.release();
     us->eval.release();
     if (us->done_ev) (void)hipEventDestroy(us->done_ev);
     if (us->gexec) (void)hipGraphExecDestroy(us->gexec);
     us->gexec = nullptr;
-    us->h_jin.release();
-    us->h_tri.release();
     delete us;
   }
   (void)hipStreamDestroy(ctx->stream);

@@ -185,7 +185,7 @@ struct HostPhase {  // scope timer (PLV_KNOB_HOST_FAULTS: the scope's minor page
   static bool faults() {
     return knob(PLV_KNOB_HOST_FAULTS);
   }
-  explicit HostPhase(const char *l) : label(l), on(host_phases().on) {
+  explicit HostPhase(const char *l) : label(l), on(l && host_phases().on) {  // (no label: nothing is timed)
     if (on && faults()) f0 = thread_minor_faults();
     if (on) t0 = std::chrono::steady_clock::now();
   }

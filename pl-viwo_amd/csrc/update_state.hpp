@@ -73,15 +73,17 @@ struct plv_ctx_update_state {
   GraphKey gkey_seen{}, gkey{};
   hipGraphExec_t gexec = nullptr;
   int graph_replays = 0, graph_captures = 0;
-  // jacobian inputs
-  plv::DevBuf jin, tri, eval;
-  plv::PinBuf h_jin;  // dedicated pinned staging: its upload is not followed by a host sync
-  plv::PinBuf h_tri;  // triangulation results of the one-submission updates
-  // the line half's own staging, triangulation and result blocks (round 4): the line launch of a frame is staged and enqueued while
-  // the point update is still running and being collected (plv_camera_try_update's chained line launch), so nothing of the two
-  // halves may share a buffer the host writes or reads
-  plv::DevBuf jin_l, tri_l;
-  plv::PinBuf h_jin_l, h_tri_l;
+  // Staging of a Jacobian batch, one set per measurement kind: packed inputs (device + pinned; the pinned block's upload is not
+  // followed by a host sync) and the triangulation results of the one-submission updates.  The line launch of a frame is staged and
+  // enqueued while the point update is still running and being collected (plv_camera_try_update's chained line launch), so nothing
+  // of the two halves may share a buffer the host writes or reads.
+  struct Staging {
+    plv::DevBuf jin, tri;
+    plv::PinBuf h_jin, h_tri;
+    void release() { jin.release(), tri.release(), h_jin.release(), h_tri.release(); }
+  } stg[2];
+  Staging &staging_of(int fdim) { return stg[fdim == 6 ? 1 : 0]; }
+  plv::DevBuf eval;
   size_t lt_o_lines = 0;  // plv_lines_update_fused_submit -> _finish: where the triangulated lines sit in tri_l, how many
   int lt_L = 0;
   int pending_fdim = 3;  // measurement size of the launched, not yet collected update (selects the pinned result block)

@@ -65,6 +65,24 @@ def test_line_host_stage_under_sanitizers(maps, tmp_path, san):
     assert "WARNING: ThreadSanitizer" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
 
 
+def test_stage_block_packer_under_sanitizers(tmp_path):
+    """pl-viwo_amd/csrc/stage_block.hpp, the packer of the Jacobian batches' one upload, under AddressSanitizer + UBSan: a point and a
+    line batch in the stagers' order, every optional array present and absent, in a heap block of exactly the reported size — each
+    array reads back, offsets are multiples of 16, nothing overlaps, absent arrays are null, the padded sizes add up to the total, and
+    the point batch's obs_feat sits behind exactly the arrays in front of it (JacParams::in_bytes of a speculative batch)."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "stage_block_check")
+    src = os.path.join(ROOT, "tests", "host_sanitize", "stage_block_check.cpp")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+           "-I" + os.path.join(ROOT, "include"), src, "-o", exe, "-L/opt/rocm/lib", "-lamdhip64", "-lpthread", "-Wl,-rpath,/opt/rocm/lib"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"), timeout=120)
+    assert r.returncode == 0 and "ok: stage blocks packed" in r.stdout, (r.stdout[-3000:], r.stderr[-4000:])
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+
+
 def test_helper_threads_are_clamped_to_the_allowed_cpus(tmp_path):
     """the default number of polling helper threads of the line detector's host stage is min(7, allowed CPUs - 2),
     at most two below six CPUs, none below three — the caller's thread and the line worker keep a CPU each."""
