@@ -934,7 +934,10 @@ int plv_wheel_linear_system(plv_ctx *ctx, const plv_wheel_options *opt, const pl
                             int *rows, double *R_3D, double *p_3D);
 /* UpdaterWheel::update from the selected samples on (REF: :72-139): the system above, Chi2Check with the full Cov_3D and
  * StateHelper::EKFUpdate on the resident covariance.  The full (6 x 6 or 3 x 3) noise is applied by whitening (H <- L^-1 H, res <- L^-1 res
- * with Cov_3D = L L^T), which is the same update.  *accepted = 0 when the gate fails; PLV_E_NOT_PSD as plv_ekf_update. */
+ * with Cov_3D = L L^T) while every Cholesky pivot keeps more than 1e-6 of its diagonal entry, and in its eigenbasis otherwise
+ * (Cov_3D = V D V^T: H <- V^T H, res <- V^T res, R <- diag(D)): either way the same S = H P H^T + Cov_3D, the same gate and the same
+ * update, also where Cov_3D is singular (the 2D types at standstill).  *accepted = 0 when the gate fails; PLV_E_NOT_PSD as plv_ekf_update;
+ * PLV_E_NUMERIC when the preintegrated measurement or its covariance is not finite (nothing changed). */
 int plv_wheel_update(plv_ctx *ctx, const plv_wheel_options *opt, const plv_wheel_state *st, int n_data, const double *t,
                      const double *m1, const double *m2, uint8_t *accepted, double *dx);
 

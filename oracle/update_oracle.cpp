@@ -298,6 +298,7 @@ int orc_slam_update(double *P, int n, int ldp, const double *H, int rows, int k,
   Mat Pm = Mat::from(P, n, n, ldp), Hm = Mat::from(H, rows, k, ldh), rm = Mat::from(res, rows, 1, rows), d;
   *accepted = 0;
   for (int i = 0; i < n; ++i) dx[i] = 0.0;
+  if (rows < 2) return 0;  // a system of fewer than two rows is skipped (UpdaterCamera.cpp:313-316)
   double chi;
   Mat Ps = marginal_cov(Pm, cols, k);
   if (!chi2(Ps, Hm, rm, 1.0, chi) || !(chi < chi2_mult * q95[rows])) return 0;  // Chi2Check (UpdaterStatistics.cpp:47-84)

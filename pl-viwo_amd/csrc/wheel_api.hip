@@ -8,9 +8,14 @@
 //
 // wheel_kernel: one workgroup.  The preintegration is a sequential recursion over the wheel samples between two clones
 // (RK4 on a quaternion + a 6x6 covariance): lane 0 integrates the means, the 6x6 products Phi Cov Phi^T + Phi_n Q Phi_n^T
-// are one element per lane.  The linear system is then laid down by lane 0, whitened by the Cholesky factor of the
-// preintegrated covariance (so that the shared chi-square / EKF kernels, which take R = I, apply the full 6x6 noise), and
-// handed to plv_slam_update's path: gate, then the covariance update on the resident P.
+// are one element per lane.  The linear system is then laid down by lane 0 and rotated into the eigenbasis of the preintegrated
+// covariance, Cov = V D V^T (Jacobi rotations on lane 0): V^T H, V^T res and the diagonal D are the same measurement with the
+// full 6x6 (3x3) noise R = Cov, in the form plv_ekf_update takes.  Nothing divides by a pivot of Cov, so a covariance that is
+// only positive SEMI-definite (the 2D types at standstill: no noise enters the lateral coordinate) is applied like any other.
+// wheel_gate_kernel forms S = (V^T H) P (V^T H)^T + D on the resident P for the chi-square gate; the update uses the same S.
+// Where every pivot of the Cholesky factorisation Cov = L L^T keeps more than kCholPivotMin of its diagonal entry, the kernels also
+// leave the system whitened by L (H <- L^-1 H, res <- L^-1 res, R = I) and plv_wheel_update takes that one through the shared
+// chi-square / EKF kernels: the same update again, and the arithmetic every well-conditioned covariance has always gone through.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -36,7 +41,7 @@ struct WheelArgs {
   plv_wheel_state st;
   int n_data, k;
   const double *t, *m1, *m2;  // device
-  double *out;                // [H 6*k col-major][res 6][Cov 36][R 9][p 3][Hw 6*k][resw 6]
+  double *out;                // [H 6*k col-major][res 6][Cov 36][R 9][p 3][Hw 6*k][resw 6][D 6][Hc 6*k][resc 6][chol 1]   (Hw = V^T H, Cov = V D V^T; Hc = L^-1 H, Cov = L L^T)
 };
 
 __device__ __forceinline__ void wheel_vel(const WheelArgs &A, double a1, double a2, D3 &w, D3 &v) {
@@ -66,10 +71,114 @@ __device__ __forceinline__ void put3w(double *M, int ldm_, int r0, int c0, const
     for (int c = 0; c < 3; ++c) M[(r0 + r) * ldm_ + c0 + c] = B.m[3 * r + c];
 }
 
+// Cyclic Jacobi on a symmetric M x M matrix (row-major, overwritten): A -> diagonal d, V's columns the eigenvectors, A = V d V^T.
+// A zero off-diagonal entry takes no rotation, so a row / column of zeros keeps its exact zero eigenvalue and its unit vector.
+// One thread.  REF for the rotation: Golub & Van Loan, Matrix Computations, alg. 8.4.1 (symmetric Schur 2 x 2).
+template <int M>
+__device__ void jacobi_eig(double *A, double *V, double *d) {
+  for (int e = 0; e < M * M; ++e) V[e] = (e % (M + 1) == 0) ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    double off = 0.0;
+    for (int p = 0; p < M; ++p)
+      for (int q = p + 1; q < M; ++q) off += fabs(A[p * M + q]);
+    if (off == 0.0) break;
+    for (int p = 0; p < M; ++p)
+      for (int q = p + 1; q < M; ++q) {
+        const double apq = A[p * M + q];
+        if (apq == 0.0) continue;
+        const double app = A[p * M + p], aqq = A[q * M + q];
+        // an entry that no longer moves either diagonal is done (it would only be chased through underflow otherwise)
+        if (sweep > 3 && fabs(app) + 100.0 * fabs(apq) == fabs(app) && fabs(aqq) + 100.0 * fabs(apq) == fabs(aqq)) {
+          A[p * M + q] = A[q * M + p] = 0.0;
+          continue;
+        }
+        const double theta = (aqq - app) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+        for (int i = 0; i < M; ++i) {  // A <- A J
+          const double aip = A[i * M + p], aiq = A[i * M + q];
+          A[i * M + p] = c * aip - sn * aiq;
+          A[i * M + q] = sn * aip + c * aiq;
+        }
+        for (int i = 0; i < M; ++i) {  // A <- J^T A
+          const double api = A[p * M + i], aqi = A[q * M + i];
+          A[p * M + i] = c * api - sn * aqi;
+          A[q * M + i] = sn * api + c * aqi;
+        }
+        A[p * M + q] = A[q * M + p] = 0.0;
+        for (int i = 0; i < M; ++i) {  // V <- V J
+          const double vip = V[i * M + p], viq = V[i * M + q];
+          V[i * M + p] = c * vip - sn * viq;
+          V[i * M + q] = sn * vip + c * viq;
+        }
+      }
+  }
+  // (a covariance is positive semi-definite: an eigenvalue below zero is rounding of a zero one)
+  for (int i = 0; i < M; ++i) d[i] = A[i * M + i] < 0.0 ? 0.0 : A[i * M + i];
+}
+
+// A Cholesky pivot d^2 = Cov_jj - sum L_jq^2 is the variance of row j given the rows before it; whitening by L divides by its root
+// and loses about eps * Cov_jj / d^2 of the result.  Below this fraction (and for a zero or non-finite entry) the eigenbasis is used.
+constexpr double kCholPivotMin = 1e-6;
+
+// Cov = L L^T (lower, row-major M x M); returns whether every pivot passed kCholPivotMin.  One thread.
+template <int M>
+__device__ bool cholesky_wellposed(const double *C, double *L) {
+  bool ok = true;
+  for (int e = 0; e < M * M; ++e) L[e] = 0.0;
+  for (int j = 0; j < M; ++j) {
+    double d = C[j * M + j];
+    for (int q = 0; q < j; ++q) d -= L[j * M + q] * L[j * M + q];
+    if (!(d > kCholPivotMin * C[j * M + j])) ok = false;
+    d = sqrt(d);
+    L[j * M + j] = d;
+    for (int i2 = j + 1; i2 < M; ++i2) {
+      double v = C[i2 * M + j];
+      for (int q = 0; q < j; ++q) v -= L[i2 * M + q] * L[j * M + q];
+      L[i2 * M + j] = v / d;
+    }
+  }
+  return ok;
+}
+
+// Whitened system: forward substitution with L, one column per lane (column k = the residual)
+template <int M>
+__device__ __forceinline__ void whiten_columns(const double *L, const double *Hr, const double *resv, int k, int tid, double *oHc, double *oresc) {
+  for (int col = tid; col <= k; col += 64) {
+    double y[M];
+#pragma unroll
+    for (int i2 = 0; i2 < M; ++i2) {
+      double v = col < k ? Hr[i2 * k + col] : resv[i2];
+      for (int q = 0; q < i2; ++q) v -= L[i2 * M + q] * y[q];
+      y[i2] = v / L[i2 * M + i2];
+    }
+#pragma unroll
+    for (int i2 = 0; i2 < M; ++i2) {
+      if (col < k) oHc[col * M + i2] = y[i2];
+      else oresc[i2] = y[i2];
+    }
+  }
+}
+
+// Rotated system, one column per lane (column k = the residual): y = V^T x.  Hr row-major [M][k]; oHw col-major M x k.
+template <int M>
+__device__ __forceinline__ void rotate_columns(const double *V, const double *Hr, const double *resv, int k, int tid, double *oHw, double *oresw) {
+  for (int col = tid; col <= k; col += 64) {
+#pragma unroll
+    for (int i2 = 0; i2 < M; ++i2) {
+      double y = 0.0;
+#pragma unroll
+      for (int q = 0; q < M; ++q) y += V[q * M + i2] * (col < k ? Hr[q * k + col] : resv[q]);
+      if (col < k) oHw[col * M + i2] = y;
+      else oresw[i2] = y;
+    }
+  }
+}
+
 __global__ void __launch_bounds__(64) wheel_kernel(WheelArgs A) {
   __shared__ double Cov[36], Ptr[36], Pns[36], Qd[6], X[36], Y[36];
   __shared__ double R3[9], p3[3], dRdi[9], dpdi[9];
-  __shared__ double Hr[6 * 24], resv[6], L[36];
+  __shared__ double Hr[6 * 24], resv[6], V[36], Dg[6], L[36], chol;
   const int tid = threadIdx.x, r = tid / 6, c = tid % 6;
   const bool el = tid < 36;
   if (el) Cov[tid] = 0.0;
@@ -226,19 +335,10 @@ __global__ void __launch_bounds__(64) wheel_kernel(WheelArgs A) {
       put3w(Hr, k, 0, hc, mscale(-1.0, ldm(dRdi)));
       put3w(Hr, k, 3, hc, mscale(-1.0, ldm(dpdi)));
     }
-    // Cholesky of the preintegrated covariance (6 x 6, lower), for the whitening below
-    for (int e = 0; e < 36; ++e) L[e] = 0.0;
-    for (int j = 0; j < 6; ++j) {
-      double d = Cov[j * 6 + j];
-      for (int q = 0; q < j; ++q) d -= L[j * 6 + q] * L[j * 6 + q];
-      d = sqrt(d);
-      L[j * 6 + j] = d;
-      for (int i2 = j + 1; i2 < 6; ++i2) {
-        double v = Cov[i2 * 6 + j];
-        for (int q = 0; q < j; ++q) v -= L[i2 * 6 + q] * L[j * 6 + q];
-        L[i2 * 6 + j] = v / d;
-      }
-    }
+    // eigenbasis of the preintegrated covariance (X is free after the recursion)
+    for (int e = 0; e < 36; ++e) X[e] = Cov[e];
+    jacobi_eig<6>(X, V, Dg);
+    chol = cholesky_wellposed<6>(Cov, L) ? 1.0 : 0.0;
   }
   __syncthreads();
   double *oH = A.out, *ores = oH + 6 * k, *oC = ores + 6, *oR = oC + 36, *op = oR + 9, *oHw = op + 3, *oresw = oHw + 6 * k;
@@ -250,21 +350,11 @@ __global__ void __launch_bounds__(64) wheel_kernel(WheelArgs A) {
   if (el) oC[tid] = Cov[tid];
   if (tid < 9) oR[tid] = R3[tid];
   if (tid < 3) op[tid] = p3[tid];
-  // whitened system: forward substitution with L, one column per lane (column k = the residual)
-  for (int col = tid; col <= k; col += 64) {
-    double y[6];
-#pragma unroll
-    for (int i2 = 0; i2 < 6; ++i2) {
-      double v = col < k ? Hr[i2 * k + col] : resv[i2];
-      for (int q = 0; q < i2; ++q) v -= L[i2 * 6 + q] * y[q];
-      y[i2] = v / L[i2 * 6 + i2];
-    }
-#pragma unroll
-    for (int i2 = 0; i2 < 6; ++i2) {
-      if (col < k) oHw[col * 6 + i2] = y[i2];
-      else oresw[i2] = y[i2];
-    }
-  }
+  if (tid < 6) oresw[6 + tid] = Dg[tid];
+  rotate_columns<6>(V, Hr, resv, k, tid, oHw, oresw);
+  double *oHc = oresw + 12, *oresc = oHc + 6 * k;
+  if (tid == 0) oresc[6] = chol;
+  whiten_columns<6>(L, Hr, resv, k, tid, oHc, oresc);
 }
 
 // Sensitivities of one constant-rate planar arc: heading `a`, turn rate `r` (the heading advances by -r dt) and forward speed `s`
@@ -295,10 +385,10 @@ __device__ inline ArcSens arc_sensitivities(double a, double r, double s, double
 }
 
 // The 2D types (REF: preintegration_2D :502-646, preintegration_intrinsics_2D :426-470, compute_linear_system_2D :217-325):
-// scalar recursions and a 3x3 covariance, all on lane 0; the lanes then whiten one column each.
-// out: [H 3*k col-major][res 3][Cov 9][R 9 = I][meas 3 = theta x y][Hw 3*k][resw 3]
+// scalar recursions and a 3x3 covariance, all on lane 0; the lanes then rotate one column each.
+// out: [H 3*k col-major][res 3][Cov 9][R 9 = I][meas 3 = theta x y][Hw 3*k][resw 3][D 3][Hc 3*k][resc 3][chol 1]
 __global__ void __launch_bounds__(64) wheel2d_kernel(WheelArgs A) {
-  __shared__ double Hr[3 * 24], resv[3], L[9], C2[9], meas[3];
+  __shared__ double Hr[3 * 24], resv[3], V[9], Dg[3], C2[9], meas[3], L[9], chol;
   const int tid = threadIdx.x, k = A.k;
   if (tid == 0) {
     double head = 0, px = 0, py = 0;   // the preintegrated planar pose: heading, position
@@ -448,21 +538,9 @@ __global__ void __launch_bounds__(64) wheel2d_kernel(WheelArgs A) {
         Hr[1 * k + hc + c] = -g_px[c];
         Hr[2 * k + hc + c] = -g_py[c];
       }
-    for (int e = 0; e < 9; ++e) {
-      C2[e] = C[e];
-      L[e] = 0.0;
-    }
-    for (int j = 0; j < 3; ++j) {
-      double d = C[j * 3 + j];
-      for (int q = 0; q < j; ++q) d -= L[j * 3 + q] * L[j * 3 + q];
-      d = sqrt(d);
-      L[j * 3 + j] = d;
-      for (int i2 = j + 1; i2 < 3; ++i2) {
-        double v = C[i2 * 3 + j];
-        for (int q = 0; q < j; ++q) v -= L[i2 * 3 + q] * L[j * 3 + q];
-        L[i2 * 3 + j] = v / d;
-      }
-    }
+    for (int e = 0; e < 9; ++e) C2[e] = C[e];
+    chol = cholesky_wellposed<3>(C, L) ? 1.0 : 0.0;
+    jacobi_eig<3>(C, V, Dg);
     meas[0] = head, meas[1] = px, meas[2] = py;
   }
   __syncthreads();
@@ -476,19 +554,62 @@ __global__ void __launch_bounds__(64) wheel2d_kernel(WheelArgs A) {
     oC[tid] = C2[tid];
     oR[tid] = (tid % 4 == 0) ? 1.0 : 0.0;
   }
-  for (int col = tid; col <= k; col += 64) {
-    double y[3];
-#pragma unroll
-    for (int i2 = 0; i2 < 3; ++i2) {
-      double v = col < k ? Hr[i2 * k + col] : resv[i2];
-      for (int q = 0; q < i2; ++q) v -= L[i2 * 3 + q] * y[q];
-      y[i2] = v / L[i2 * 3 + i2];
+  if (tid < 3) oresw[3 + tid] = Dg[tid];
+  rotate_columns<3>(V, Hr, resv, k, tid, oHw, oresw);
+  double *oHc = oresw + 6, *oresc = oHc + 3 * k;
+  if (tid == 0) oresc[3] = chol;
+  whiten_columns<3>(L, Hr, resv, k, tid, oHc, oresc);
+}
+
+// Chi2Check on the rotated system: chi2 = r^T S^-1 r, S = H P[cols, cols] H^T + diag(D)   (REF: UpdaterStatistics.cpp:94-117).
+// One workgroup: the M x k products one element per lane, the M x M Cholesky and the forward substitution on lane 0.
+// H col-major M x k, P col-major n x n; chi2 is NaN when S is not positive definite (the caller then rejects).
+struct WheelGateArgs {
+  const double *P;
+  int n, k, rows;
+  int cols[24];
+  const double *H, *res, *D;
+  double *chi2;
+};
+__global__ void __launch_bounds__(64) wheel_gate_kernel(WheelGateArgs G) {
+  __shared__ double T[6 * 24], S[36];
+  const int tid = threadIdx.x, k = G.k, M = G.rows;
+  for (int e = tid; e < M * k; e += 64) {  // T = H P[cols, cols]
+    const int i = e / k, b = e - i * k;
+    double s = 0.0;
+    for (int a = 0; a < k; ++a) s += G.H[a * M + i] * G.P[(size_t)G.cols[b] * G.n + G.cols[a]];
+    T[i * k + b] = s;
+  }
+  __syncthreads();
+  if (tid < M * M) {
+    const int i = tid / M, j = tid - i * M;
+    double s = 0.0;
+    for (int b = 0; b < k; ++b) s += T[i * k + b] * G.H[b * M + j];
+    S[tid] = s + (i == j ? G.D[i] : 0.0);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double L[36], y[6], chi = 0.0;
+    bool bad = false;
+    for (int j = 0; j < M; ++j) {
+      double d = S[j * M + j];
+      for (int q = 0; q < j; ++q) d -= L[j * M + q] * L[j * M + q];
+      if (!(d > 0.0)) bad = true;
+      d = sqrt(d);
+      L[j * M + j] = d;
+      for (int i = j + 1; i < M; ++i) {
+        double v = S[j * M + i];  // selfadjointView<Upper>
+        for (int q = 0; q < j; ++q) v -= L[i * M + q] * L[j * M + q];
+        L[i * M + j] = v / d;
+      }
     }
-#pragma unroll
-    for (int i2 = 0; i2 < 3; ++i2) {
-      if (col < k) oHw[col * 3 + i2] = y[i2];
-      else oresw[i2] = y[i2];
+    for (int i = 0; i < M; ++i) {
+      double v = G.res[i];
+      for (int q = 0; q < i; ++q) v -= L[i * M + q] * y[q];
+      y[i] = v / L[i * M + i];
+      chi += y[i] * y[i];
     }
+    *G.chi2 = bad ? NAN : chi;
   }
 }
 
@@ -506,14 +627,14 @@ int wheel_columns(const plv_wheel_options *op, const plv_wheel_state *st, int *c
 
 // runs the kernel; host copies of every output block
 int wheel_system(plv_ctx *ctx, const plv_wheel_options *op, const plv_wheel_state *st, int n_data, const double *t, const double *m1,
-                 const double *m2, std::vector<double> &out, int &k, int &rows) {
+                 const double *m2, std::vector<double> &out, int &k, int &rows, double **d_out = nullptr) {
   if (!ctx || !op || !st || n_data < 2 || !t || !m1 || !m2 || op->type < 0 || op->type > PLV_WHEEL2D_CEN) return PLV_E_BADARG;
   k = 12 + (op->do_calib_ext ? 6 : 0) + (op->do_calib_dt ? 1 : 0) + (op->do_calib_int ? 3 : 0);
   rows = op->type >= PLV_WHEEL2D_ANG ? 3 : 6;
   (void)hipSetDevice(ctx->device);
   auto *us = plv_update_state(ctx);
-  const size_t nd = (size_t)n_data, n_out = (size_t)2 * rows * k + rows + (size_t)rows * rows + 9 + 3 + rows;
-  TRY(us->eval.reserve((3 * nd + n_out) * 8));
+  const size_t nd = (size_t)n_data, n_out = (size_t)3 * rows * k + rows + (size_t)rows * rows + 9 + 3 + 3 * rows + 1;
+  TRY(us->eval.reserve((3 * nd + n_out + 1) * 8));  // (+ 1: the gate's chi2, plv_wheel_update)
   double *d = us->eval.as<double>();
   std::vector<double> h(3 * nd);
   std::copy(t, t + nd, h.begin());
@@ -539,6 +660,7 @@ int wheel_system(plv_ctx *ctx, const plv_wheel_options *op, const plv_wheel_stat
   PLV_HIP_CHECK(plv::memcpy_async(out.data(), A.out, n_out * 8, hipMemcpyDeviceToHost, ctx->stream));
   PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
   ctx->prof.collect();
+  if (d_out) *d_out = A.out;
   return PLV_OK;
 }
 
@@ -625,22 +747,56 @@ int plv_wheel_update(plv_ctx *ctx, const plv_wheel_options *opt, const plv_wheel
   if (!accepted || !dx || !ctx || ctx->cov_n < 1) return PLV_E_BADARG;
   std::vector<double> out;
   int k = 0, rows = 0;
-  TRY(wheel_system(ctx, opt, st, n_data, t, m1, m2, out, k, rows));
-  int cols[24];
-  wheel_columns(opt, st, cols);
+  double *d_out = nullptr;
+  TRY(wheel_system(ctx, opt, st, n_data, t, m1, m2, out, k, rows, &d_out));
+  WheelGateArgs G{};
+  wheel_columns(opt, st, G.cols);
+  const int n = ctx->cov_n;
   for (int i = 0; i < k; ++i)
-    if (cols[i] < 0 || cols[i] >= ctx->cov_n) {
-      set_last_error("plv_wheel_update: column %d maps to state %d outside the covariance (%d)", i, cols[i], ctx->cov_n);
+    if (G.cols[i] < 0 || G.cols[i] >= n) {
+      set_last_error("plv_wheel_update: column %d maps to state %d outside the covariance (%d)", i, G.cols[i], n);
       return PLV_E_BADARG;
     }
-  const double *Hw = out.data() + (size_t)rows * k + rows + (size_t)rows * rows + 12, *resw = Hw + (size_t)rows * k;
-  for (int i = 0; i < rows * k + rows; ++i)
+  // the measurement in the eigenbasis of its noise: Hw = V^T H, resw = V^T res, R = diag(D)
+  const size_t o_hw = (size_t)rows * k + rows + (size_t)rows * rows + 12, o_resw = o_hw + (size_t)rows * k, o_D = o_resw + rows;
+  const size_t o_hc = o_D + rows, o_resc = o_hc + (size_t)rows * k, o_chol = o_resc + rows;
+  const double *Hw = out.data() + o_hw, *resw = out.data() + o_resw, *D = out.data() + o_D;
+  for (int i = 0; i < rows * k + 2 * rows; ++i)
     if (!std::isfinite(Hw[i])) {
-      set_last_error("plv_wheel_update: the preintegrated covariance is not positive definite");
+      set_last_error("plv_wheel_update: the preintegrated measurement or its covariance is not finite");
       return PLV_E_NUMERIC;
     }
-  // Chi2Check(H, res, Cov) + EKFUpdate(H, res, Cov) == the same two steps on the whitened system with R = I
-  return plv_slam_update(ctx, rows, k, rows, Hw, resw, cols, opt->chi2_mult, accepted, dx);
+  if (out[o_chol] != 0.0) {
+    // a well-conditioned covariance: Chi2Check + EKFUpdate on the system whitened by its Cholesky factor, R = I
+    const double *Hc = out.data() + o_hc, *resc = out.data() + o_resc;
+    for (int i = 0; i < rows * k + rows; ++i)
+      if (!std::isfinite(Hc[i])) {
+        set_last_error("plv_wheel_update: the whitened measurement is not finite");
+        return PLV_E_NUMERIC;
+      }
+    return plv_slam_update(ctx, rows, k, rows, Hc, resc, G.cols, opt->chi2_mult, accepted, dx);
+  }
+  *accepted = 0;
+  std::fill(dx, dx + n, 0.0);
+  // Chi2Check(H, res, Cov): S = H P H^T + Cov, in the rotated basis
+  G.P = ctx->d_P.as<double>();
+  G.n = n, G.k = k, G.rows = rows;
+  G.H = d_out + o_hw, G.res = d_out + o_resw, G.D = d_out + o_D;
+  G.chi2 = d_out + o_chol + 1;
+  {
+    ProfScope ps(ctx->prof, "wheel_gate_kernel", ctx->stream);
+    hipLaunchKernelGGL(wheel_gate_kernel, dim3(1), dim3(64), 0, ctx->stream, G);
+  }
+  PLV_HIP_CHECK(hipGetLastError());
+  double chi = 0.0;
+  PLV_HIP_CHECK(plv::memcpy_async(&chi, G.chi2, 8, hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
+  ctx->prof.collect();
+  if (!(chi < opt->chi2_mult * plv_chi2_quantile95(rows))) return PLV_OK;  // REF: UpdaterWheel.cpp:126-131
+  // EKFUpdate(H, res, Cov) == the rotated rows with the diagonal noise D
+  const int rc = plv_ekf_update(ctx, nullptr, n, n, Hw, rows, k, rows, G.cols, resw, D, dx);
+  if (rc == PLV_OK) *accepted = 1;
+  return rc;
 }
 
 }  // extern "C"

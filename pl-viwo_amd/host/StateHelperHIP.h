@@ -42,8 +42,9 @@ public:
 
   // StateHelper::EKFUpdate.  The camera path passes R = I (UpdaterCamera.cpp:290), the GPS path a diagonal, the wheel path a DENSE 6 x 6 /
   // 3 x 3 preintegration covariance (UpdaterWheel.cpp:130-134).  plv_ekf_update takes a diagonal; a dense R is applied by whitening
-  // with its Cholesky factor, R = L L^T: H <- L^-1 H, res <- L^-1 res, R <- I — the same K res and the same K M^T (what
-  // plv_wheel_update does inside its kernel).  resident = covariance mode (b).
+  // with its Cholesky factor, R = L L^T: H <- L^-1 H, res <- L^-1 res, R <- I — the same K res and the same K M^T.  (plv_wheel_update
+  // does the same inside its kernel and rotates into the eigenbasis of R where R is singular, as for a standing vehicle; a caller
+  // that keeps UpdaterWheel::update on the host goes through the LLT below and skips such an update.)  resident = covariance mode (b).
   static bool EKFUpdate(plv_ctx *ctx, std::shared_ptr<State> state, const VEC_TYPE &H_order, const Eigen::MatrixXd &H,
                         const Eigen::VectorXd &res, const Eigen::MatrixXd &R, bool resident = false) {
     const std::vector<int> cols = col_to_state(H_order);
