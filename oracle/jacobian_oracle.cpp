@@ -593,10 +593,36 @@ static void sym_eig3(const M3 &A, double ev[3]) {
 static double *g_tri_debug = nullptr;
 void orc_set_tri_debug(double *four) { g_tri_debug = four; }
 
+// (test aid, tests/triangulation_cases.py) when set, orc_triangulate says which way a feature went, ORC_TRI_TRACE_INTS ints per feature:
+//   [0] valid observations   [1] the stage that ended it (TriStage)   [2] how the refinement ended (TriExit)   [3] passes of its loop
+//   [4] steps accepted (the small-decrease one included)   [5] number of failed-step streaks
+//   [6 + 2 s], [7 + 2 s]  length of streak s and whether an accepted step followed it (the first ORC_TRI_TRACE_STREAKS streaks)
+// The batch form takes one record per feature.  Off (nullptr) by default; the results do not depend on it.
+enum TriStage { TRI_TOO_FEW = 0, TRI_LINEAR_SOLVE, TRI_COND, TRI_LIN_DEPTH_LOW, TRI_LIN_DEPTH_HIGH, TRI_NAN, TRI_REF_DEPTH_LOW, TRI_REF_DEPTH_HIGH,
+                TRI_BASELINE, TRI_ACCEPTED };
+enum TriExit { LM_NONE = 0, LM_SMALL_DECREASE, LM_FIVE_RUNS, LM_LAM_CAP, LM_SMALL_STEP, LM_SOLVE_FAILED };
+enum { ORC_TRI_TRACE_STREAKS = 8, ORC_TRI_TRACE_INTS = 6 + 2 * ORC_TRI_TRACE_STREAKS };
+static int *g_tri_trace = nullptr;
+void orc_set_tri_trace(int *rec) { g_tri_trace = rec; }
+static int tri_stage(int *tr, int stage) {  // records the verdict; returns what orc_triangulate returns
+  if (tr) tr[1] = stage;
+  return stage == TRI_ACCEPTED ? 1 : 0;
+}
+static void tri_streak(int *tr, int len, int accepted) {
+  if (!tr || len == 0) return;
+  if (tr[5] < ORC_TRI_TRACE_STREAKS) tr[6 + 2 * tr[5]] = len, tr[7 + 2 * tr[5]] = accepted;
+  ++tr[5];
+}
+
 int orc_triangulate(int M, const double *Rc, const double *pc, const float *uvn, double min_dist, double max_dist,
                     double max_cond, double max_baseline, int refine, double *p_FinG_out) {
   if (g_tri_debug) g_tri_debug[0] = g_tri_debug[1] = g_tri_debug[2] = g_tri_debug[3] = std::nan("");
-  if (M < 2) return 0;
+  int *const trc = g_tri_trace;
+  if (trc) {
+    memset(trc, 0, sizeof(int) * ORC_TRI_TRACE_INTS);
+    trc[0] = M;
+  }
+  if (M < 2) return tri_stage(trc, TRI_TOO_FEW);
   const M3 R_GtoA = getM(Rc + 9 * (M - 1));
   const V3 p_AinG = getV(pc + 3 * (M - 1));
   M3 A{{0, 0, 0, 0, 0, 0, 0, 0, 0}};
@@ -612,12 +638,13 @@ int orc_triangulate(int M, const double *Rc, const double *pc, const float *uvn,
     b = addv(b, mul(Ai, p_CiinA));
   }
   V3 pf;
-  if (!solve3(A, b, pf)) return 0;
+  if (!solve3(A, b, pf)) return tri_stage(trc, TRI_LINEAR_SOLVE);
   double ev[3];
   sym_eig3(A, ev);
   double condA = ev[0] / ev[2];
   if (g_tri_debug) g_tri_debug[0] = std::fabs(condA), g_tri_debug[1] = pf[2];
-  if (std::fabs(condA) > max_cond || pf[2] < min_dist || pf[2] > max_dist || std::isnan(norm(pf))) return 0;
+  if (std::fabs(condA) > max_cond || pf[2] < min_dist || pf[2] > max_dist || std::isnan(norm(pf)))
+    return tri_stage(trc, std::fabs(condA) > max_cond ? TRI_COND : pf[2] < min_dist ? TRI_LIN_DEPTH_LOW : pf[2] > max_dist ? TRI_LIN_DEPTH_HIGH : TRI_NAN);
   if (refine) {
     // FeatureInitializerOptions defaults: max_runs 5, init_lamda 1e-3, max_lamda 1e10, min_dx 1e-6,
     // min_dcost 1e-6, lam_mult 10  (REF: FeatureInitializerOptions.h:36-69)
@@ -628,7 +655,9 @@ int orc_triangulate(int M, const double *Rc, const double *pc, const float *uvn,
     M3 Hess{{0}};
     V3 grad{{0, 0, 0}};
     double cost_old = tri_error(M, Rc, pc, uvn, R_GtoA, p_AinG, alpha, beta, rho);
+    int lm_exit = LM_NONE, streak = 0;  // (the trace's; the loop does not read them)
     while (runs < 5 && lam < 1e10 && eps > 1e-6) {
+      if (trc) ++trc[3];
       if (recompute) {
         memset(Hess.m, 0, sizeof(Hess.m));
         grad = V3{{0, 0, 0}};
@@ -654,16 +683,26 @@ int orc_triangulate(int M, const double *Rc, const double *pc, const float *uvn,
       M3 Hl = Hess;
       for (int r = 0; r < 3; ++r) Hl(r, r) *= (1.0 + lam);
       V3 dx;
-      if (!solve3(Hl, grad, dx)) break;
+      if (!solve3(Hl, grad, dx)) {
+        lm_exit = LM_SOLVE_FAILED;
+        break;
+      }
       double cost = tri_error(M, Rc, pc, uvn, R_GtoA, p_AinG, alpha + dx[0], beta + dx[1], rho + dx[2]);
       if (cost <= cost_old && (cost_old - cost) / cost_old < 1e-6) {
         alpha += dx[0];
         beta += dx[1];
         rho += dx[2];
         eps = 0;
+        lm_exit = LM_SMALL_DECREASE;
+        if (trc) ++trc[4];
+        tri_streak(trc, streak, 1);
+        streak = 0;
         break;
       }
       if (cost <= cost_old) {
+        if (trc) ++trc[4];
+        tri_streak(trc, streak, 1);
+        streak = 0;
         recompute = true;
         cost_old = cost;
         alpha += dx[0];
@@ -675,7 +714,12 @@ int orc_triangulate(int M, const double *Rc, const double *pc, const float *uvn,
       } else {
         recompute = false;
         lam = lam * 10;
+        ++streak;
       }
+    }
+    if (trc) {
+      tri_streak(trc, streak, 0);
+      trc[2] = lm_exit != LM_NONE ? lm_exit : runs >= 5 ? LM_FIVE_RUNS : lam >= 1e10 ? LM_LAM_CAP : LM_SMALL_STEP;  // (the order the loop tests in)
     }
     pf = V3{{alpha / rho, beta / rho, 1 / rho}};
     // baseline test: components of the camera offsets orthogonal to p_FinA (the reference spans that
@@ -689,13 +733,14 @@ int orc_triangulate(int M, const double *Rc, const double *pc, const float *uvn,
       base_max = std::max(base_max, norm(perp));
     }
     if (g_tri_debug) g_tri_debug[2] = pf[2], g_tri_debug[3] = norm(pf) / base_max;
-    if (pf[2] < min_dist || pf[2] > max_dist || (norm(pf) / base_max) > max_baseline || std::isnan(norm(pf))) return 0;
+    if (pf[2] < min_dist || pf[2] > max_dist || (norm(pf) / base_max) > max_baseline || std::isnan(norm(pf)))
+      return tri_stage(trc, pf[2] < min_dist ? TRI_REF_DEPTH_LOW : pf[2] > max_dist ? TRI_REF_DEPTH_HIGH : (norm(pf) / base_max) > max_baseline ? TRI_BASELINE : TRI_NAN);
   }
   const V3 pg = addv(mul(tr(R_GtoA), pf), p_AinG);
   p_FinG_out[0] = pg[0];
   p_FinG_out[1] = pg[1];
   p_FinG_out[2] = pg[2];
-  return 1;
+  return tri_stage(trc, TRI_ACCEPTED);
 }
 
 
@@ -736,9 +781,12 @@ int orc_triangulate_batch(const plv_state_view *st, const plv_tracks *trk, const
     pf[0] = pf[1] = pf[2] = 0;
     double *const dbg_all = g_tri_debug;  // (batch form: four values per feature)
     if (dbg_all) g_tri_debug = dbg_all + 4 * (size_t)f;
+    int *const trc_all = g_tri_trace;
+    if (trc_all) g_tri_trace = trc_all + ORC_TRI_TRACE_INTS * (size_t)f;
     ok[f] = (uint8_t)orc_triangulate(M, Rc.data(), pc.data(), uvn.data(), opt->min_dist, opt->max_dist, opt->max_cond_number,
                                      opt->max_baseline, opt->refine_features, pf);
     g_tri_debug = dbg_all;
+    g_tri_trace = trc_all;
     double e = 0;
     if (ok[f]) {
       for (int m = 0; m < M; ++m) {
@@ -957,10 +1005,19 @@ int orc_build_line_jacobians(const plv_state_view *st, const plv_line_tracks *lt
   return 0;
 }
 
+// (test aid, the line twin of orc_set_tri_trace) when set, orc_triangulate_lines says which way a line went, `stride` doubles per line:
+//   [0] valid observations   [1] index of the first valid one within the track (-1: none)   [2] branch: 0 too few, 1 anchored with its
+//   class D, 2 plane pairs   [3] plane pairs tried   [4] plane pairs used   [5 ...] every |cos| held against 0.99, NaN behind the last
+static double *g_line_trace = nullptr;
+static int g_line_trace_stride = 0;
+void orc_set_line_trace(double *rec, int stride) { g_line_trace = rec, g_line_trace_stride = rec ? stride : 0; }
+
 int orc_triangulate_lines(const plv_state_view *st, const plv_line_tracks *lt, double *line_FinG, unsigned char *ok) {
   const M3 R_ItoC = getM(st->R_ItoC);
   const V3 p_IinC = getV(st->p_IinC);
   for (int l = 0; l < lt->n_lines; ++l) {
+    double *const ltr = g_line_trace ? g_line_trace + (size_t)g_line_trace_stride * l : nullptr;
+    const int ncos = g_line_trace_stride - 5;
     ok[l] = 0;
     for (int i = 0; i < 6; ++i) line_FinG[6 * l + i] = 0;
     // usable views (LineHelper::get_imu_poses drops the ones without bounding clones)
@@ -975,8 +1032,13 @@ int orc_triangulate_lines(const plv_state_view *st, const plv_line_tracks *lt, d
       RI.push_back(R);
       pI.push_back(p);
     }
+    if (ltr) {
+      ltr[0] = (double)obs.size(), ltr[1] = obs.empty() ? -1.0 : (double)(obs[0] - lt->obs_ptr[l]), ltr[2] = ltr[3] = ltr[4] = 0;
+      for (int i = 0; i < ncos; ++i) ltr[5 + i] = std::nan("");
+    }
     if (obs.size() < 2) continue;  // :204-206
     const int D = lt->D ? lt->D[l] : 0;
+    if (ltr) ltr[2] = (D > 0 && lt->has_pt && lt->has_pt[l]) ? 1 : 2;
     if (D > 0 && lt->has_pt && lt->has_pt[l]) {  // :231-293
       const V3 e{{D == 1 ? 1.0 : 0.0, D == 2 ? 1.0 : 0.0, D == 3 ? 1.0 : 0.0}};
       const V3 dir = mul(tr(RI[0]), e);
@@ -1008,7 +1070,10 @@ int orc_triangulate_lines(const plv_state_view *st, const plv_line_tracks *lt, d
     plane(p11, p12, cam0, pl0);
     V3 dsum{{0, 0, 0}}, nsum{{0, 0, 0}};
     double dnorm = 0;
-    int cnt = 0;
+    int cnt = 0, tried = 0;
+    double cos_spill;
+    double *const cos_rec = ltr && ncos > 1 ? ltr + 5 : &cos_spill;
+    const int cos_cap = ltr && ncos > 1 ? ncos - 1 : 0;
     for (size_t m = 1; m < obs.size(); ++m) {
       const M3 R0i = mul(RC[m], tr(RC[0]));
       const V3 pi0 = mul(RC[0], sub(pC[m], pC[0]));
@@ -1023,6 +1088,8 @@ int orc_triangulate_lines(const plv_state_view *st, const plv_line_tracks *lt, d
       n1 = sc(n1, 1 / norm(n1));
       n2 = sc(n2, 1 / norm(n2));
       const double cth = dot(n1, n2) / (norm(n1) * norm(n2));
+      cos_rec[tried < cos_cap ? tried : cos_cap] = std::fabs(cth);  // (slot cos_cap takes what does not fit: no pointer test per pair)
+      ++tried;
       if (std::fabs(cth) >= 0.99) continue;
       auto dp = [&](int i, int j) { return pl0[i] * pl1[j] - pl1[i] * pl0[j]; };
       const V3 head{{dp(0, 3), dp(1, 3), dp(2, 3)}}, tail{{-dp(1, 2), dp(0, 2), -dp(0, 1)}};
@@ -1031,6 +1098,7 @@ int orc_triangulate_lines(const plv_state_view *st, const plv_line_tracks *lt, d
       dnorm += norm(tail);
       ++cnt;
     }
+    if (ltr) ltr[3] = tried, ltr[4] = cnt;
     if (cnt == 0) continue;
     const V3 rhead = sc(dsum, 1 / dnorm), rtail = sc(nsum, 1.0 / cnt);  // line_result = [dir; normal]
     const M3 R0t = tr(RC[0]);

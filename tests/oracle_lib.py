@@ -390,6 +390,12 @@ class JacOracle:
         lib.orc_triangulate_lines.restype = C.c_int
         lib.orc_cpi_poses.argtypes = [sv, C.POINTER(pkg.PlvCpiTable), C.c_int, dp, dp, dp, u8p]
         lib.orc_cpi_poses.restype = C.c_int
+        lib.orc_set_tri_debug.argtypes = [dp]
+        lib.orc_set_tri_debug.restype = None
+        lib.orc_set_tri_trace.argtypes = [ip]
+        lib.orc_set_tri_trace.restype = None
+        lib.orc_set_line_trace.argtypes = [dp, C.c_int]
+        lib.orc_set_line_trace.restype = None
 
     def cpi_poses(self, st, cpi, t_q):
         t_q = np.ascontiguousarray(t_q, dtype=np.float64)
@@ -465,6 +471,54 @@ class JacOracle:
 
 
 JacOracle.triangulate_batch = JacOracle._tb
+
+# the oracle's triangulation traces (orc_set_tri_trace / orc_set_line_trace in oracle/jacobian_oracle.cpp)
+TRI_STAGES = ("too few observations", "linear solve failed", "condition number", "linear depth low", "linear depth high", "NaN",
+              "refined depth low", "refined depth high", "baseline ratio", "accepted")
+LM_EXITS = ("none", "small decrease", "five runs", "lam cap", "small step", "solve failed")
+TRI_TRACE_STREAKS = 8
+TRI_TRACE_INTS = 6 + 2 * TRI_TRACE_STREAKS
+LINE_BRANCHES = ("too few", "anchored", "plane pairs")
+
+
+def _tb_traced(self, st, tr, **opt):
+    """triangulate_batch with the trace on: (p, ok, err, values [F][4] = condition number, linear depth, refined depth, baseline ratio,
+    trace [F][TRI_TRACE_INTS] = valid observations, stage, LM exit, passes, accepted steps, streaks, (length, accepted after) per streak)"""
+    F = tr.c.n_feat
+    vals, trace = np.full((F, 4), np.nan), np.zeros((F, TRI_TRACE_INTS), dtype=np.int32)
+    self.lib.orc_set_tri_debug(_dp(vals))
+    self.lib.orc_set_tri_trace(_ip(trace))
+    try:
+        p, ok, err = self._tb(st, tr, **opt)
+    finally:
+        self.lib.orc_set_tri_debug(None)
+        self.lib.orc_set_tri_trace(None)
+    return p, ok, err, vals, trace
+
+
+def _tl_traced(self, st, lt, ncos=160):
+    """triangulate_lines with the trace on: (lines, ok, trace [L][5 + ncos] = valid observations, first valid one, branch, pairs tried,
+    pairs used, every |cos| held against 0.99 (NaN behind the last))"""
+    L = lt.c.n_lines
+    trace = np.zeros((L, 5 + ncos))
+    self.lib.orc_set_line_trace(_dp(trace), 5 + ncos)
+    try:
+        out, ok = self.triangulate_lines(st, lt)
+    finally:
+        self.lib.orc_set_line_trace(None, 0)
+    assert (trace[:, 3] <= ncos).all()
+    return out, ok, trace
+
+
+def streaks(rec):
+    """[(length, accepted after)] of one point trace record"""
+    n = int(rec[5])
+    assert n <= TRI_TRACE_STREAKS
+    return [(int(rec[6 + 2 * s]), bool(rec[7 + 2 * s])) for s in range(n)]
+
+
+JacOracle.triangulate_batch_traced = _tb_traced
+JacOracle.triangulate_lines_traced = _tl_traced
 
 _jac = None
 
