@@ -333,6 +333,15 @@ int plv_undistort(plv_ctx *ctx, int n, const float *uv, float *xy);
 int plv_ransac_fundamental(plv_ctx *ctx, int n, const float *m1, const float *m2, double thr, uint32_t seed,
                            uint8_t *mask, int *n_inliers, int *iters_used);
 
+/* plv_ransac_hypotheses is a diagnostic entry: the first of plv_ransac_fundamental's two launches alone.  Hypothesis h = 0 ..
+ * nhyp-1 draws its seven points, solves the seven-point problem and counts the inliers of each model, whatever the adaptive loop
+ * would have stopped at.  models[h] = 28 doubles: the (up to) three fundamental matrices in the order of the cubic's roots, row-major,
+ * then a 3-bit mask saying which of them are valid (numbers under a cleared bit mean nothing).  counts[h] = the inliers of the valid
+ * models, compacted in root order, -1 behind the last.  With n == 7 the sample is points 0 .. 6 for every h.  n < 7, nhyp < 1 or
+ * nhyp > 4096: PLV_E_BADARG. */
+int plv_ransac_hypotheses(plv_ctx *ctx, int n, const float *m1, const float *m2, double thr, uint32_t seed, int nhyp,
+                          double *models, int *counts);
+
 /* plv_perform_matching replaces TrackKLT::perform_matching (REF: TrackKLT.cpp:829-886) on the
  * last -> current pyramids: LK, undistort both point sets, RANSAC with thr = ransac_thr_px /
  * max(fx,fy), mask_out = klt & ransac.  n < 10 -> all-zero mask, PLV_OK (REF :848-852).

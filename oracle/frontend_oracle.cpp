@@ -331,16 +331,28 @@ double det_cbrt(double x) {  // x >= 0
   return y;
 }
 
+// (test aid, tests/ransac_cases.py) when set, the RANSAC gate counts here which way it went: orc_set_ransac_trace below names the
+// slots.  Counting only: no value the gate computes depends on it.
+enum {
+  RT_C1_ZERO, RT_LINEAR, RT_QUAD_NEG, RT_QUAD, RT_THREE, RT_DOUBLE, RT_ONE, RT_XR_CLAMP, RT_RANK_FAIL, RT_RANK_STEP, RT_F8_ZERO,
+  RT_NONFINITE, RT_RETRY, RT_NO_SUBSET, RT_HYPOTHESES, RT_SLOTS
+};
+long long *g_ransac_trace = nullptr;
+inline void rt_count(int slot) {
+  if (g_ransac_trace) ++g_ransac_trace[slot];
+}
+
 // real roots of c3 x^3 + c2 x^2 + c1 x + c0 (cv::solveCubic's case analysis, trigonometric form)
 int solve_cubic(double c3, double c2, double c1, double c0, double *roots) {
   if (c3 == 0) {
     if (c2 == 0) {
-      if (c1 == 0) return 0;
+      if (c1 == 0) return rt_count(RT_C1_ZERO), 0;
       roots[0] = -c0 / c1;
-      return 1;
+      return rt_count(RT_LINEAR), 1;
     }
     double d = c1 * c1 - 4 * c2 * c0;
-    if (d < 0) return 0;
+    if (d < 0) return rt_count(RT_QUAD_NEG), 0;
+    rt_count(RT_QUAD);
     d = std::sqrt(d);
     double q = 1. / (2 * c2);
     roots[0] = (-c1 - d) * q;
@@ -355,6 +367,8 @@ int solve_cubic(double c3, double c2, double c1, double c0, double *roots) {
   if (d > 0) {
     // theta = acos(R / sqrt(Q^3)); the roots are -2 sqrt(Q) cos(theta / 3 + 2 pi k / 3) - a1 / 3
     double xr = R / std::sqrt(Qcubed);
+    rt_count(RT_THREE);
+    if (xr < -1.0 || xr > 1.0) rt_count(RT_XR_CLAMP);
     xr = xr < -1.0 ? -1.0 : (xr > 1.0 ? 1.0 : xr);
     const double ct = det_cos_third(xr), st = std::sqrt(1.0 - ct * ct);
     double sqrtQ = std::sqrt(Q);
@@ -364,6 +378,7 @@ int solve_cubic(double c3, double c2, double c1, double c0, double *roots) {
     roots[2] = t0 * (-0.5 * ct + 0.8660254037844386 * st) - t2;
     return 3;
   } else if (d == 0) {
+    rt_count(RT_DOUBLE);
     if (R >= 0) {
       roots[0] = -2 * det_cbrt(R) - a1 / 3;
       roots[1] = det_cbrt(R) - a1 / 3;
@@ -373,6 +388,7 @@ int solve_cubic(double c3, double c2, double c1, double c0, double *roots) {
     }
     return 2;
   } else {
+    rt_count(RT_ONE);
     d = std::sqrt(-d);
     double e = det_cbrt(d + std::fabs(R));
     if (R > 0) e = -e;
@@ -392,7 +408,11 @@ bool nullspace_7x9(double A[7][9], double f1[9], double f2[9]) {
     for (int r = i; r < 7; ++r)
       for (int c = i; c < 9; ++c)
         if (std::fabs(A[r][c]) > best) best = std::fabs(A[r][c]), pr = r, pc = c;
-    if (!(best > 1e-14)) return false;
+    if (!(best > 1e-14)) {
+      rt_count(RT_RANK_FAIL);
+      if (g_ransac_trace) g_ransac_trace[RT_RANK_STEP] = i;
+      return false;
+    }
     if (pr != i)
       for (int c = 0; c < 9; ++c) std::swap(A[pr][c], A[i][c]);
     if (pc != i) {
@@ -458,12 +478,17 @@ int run7point(const float *m1, const float *m2, const int *idx, double *F) {
       mu = 1. / s;
       lambda *= mu;
       Fk[8] = 1.;
-    } else
+    } else {
       Fk[8] = 0.;
+      rt_count(RT_F8_ZERO);
+    }
     for (int i = 0; i < 8; ++i) Fk[i] = g[i] * lambda + f2[i] * mu;
     bool finite = true;
     for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(Fk[i]);
-    if (finite) ++nout;
+    if (finite)
+      ++nout;
+    else
+      rt_count(RT_NONFINITE);
   }
   return nout;
 }
@@ -508,10 +533,13 @@ bool get_subset(const float *m1, const float *m2, int n, uint32_t seed, uint32_t
       if (dup) continue;
       idx[i++] = cand;
     }
-    if (i < 7) continue;
-    if (collinear_last(m1, idx, 7) || collinear_last(m2, idx, 7)) continue;
+    if (i < 7 || collinear_last(m1, idx, 7) || collinear_last(m2, idx, 7)) {
+      rt_count(RT_RETRY);
+      continue;
+    }
     return true;
   }
+  rt_count(RT_NO_SUBSET);
   return false;
 }
 
@@ -541,6 +569,7 @@ int ransac_fundamental(const float *m1, const float *m2, int n, double thr, doub
   int it = 0;
   for (; it < niters; ++it) {
     int idx[7];
+    rt_count(RT_HYPOTHESES);
     if (n == 7) {
       for (int i = 0; i < 7; ++i) idx[i] = i;
     } else if (!get_subset(m1, m2, n, seed, (uint32_t)it, idx)) {
@@ -707,6 +736,42 @@ int orc_ransac_fundamental(const float *m1, const float *m2, int n, double thr, 
 }
 
 int orc_run7point(const float *m1, const float *m2, const int *idx, double *F) { return run7point(m1, m2, idx, F); }
+
+// (test aid, the RANSAC twin of orc_set_tri_trace) when set, one call of orc_ransac_fundamental or orc_ransac_hypotheses adds to
+// counters[16]: cubic exits by branch — [0] c1 == 0 (no root), [1] linear, [2] quadratic with d < 0, [3] quadratic with d >= 0,
+// [4] three roots, [5] d == 0, [6] one root — [7] xr clamps, [8] rank failures of the 7x9 elimination, [9] the elimination step of
+// the last one (-1: none), [10] models with F[8] = 0, [11] non-finite models dropped, [12] subset attempts repeated, [13] hypotheses
+// whose 16 attempts all failed, [14] hypotheses visited.  The caller zeroes them ([9] = -1).  Null switches it off.
+void orc_set_ransac_trace(long long *counters) { g_ransac_trace = counters; }
+
+// What get_subset + run7point + the inlier count give for hypothesis h = 0 .. nhyp-1, whatever the adaptive loop would have made of
+// them: F[h][27] the models compacted as run7point compacts them, nmodels[h], counts[h][3] (-1 beyond nmodels[h]).  A hypothesis
+// without a subset has no model.  With n == 7 the sample is rows 0 .. 6 and only hypothesis 0 exists.
+void orc_ransac_hypotheses(const float *m1, const float *m2, int n, double thr, uint32_t seed, int nhyp, double *F, int *nmodels,
+                           int *counts) {
+  const float t = (float)(thr * thr);
+  for (int h = 0; h < nhyp; ++h) {
+    double *Fh = F + 27 * (size_t)h;
+    for (int e = 0; e < 27; ++e) Fh[e] = 0;
+    nmodels[h] = 0;
+    for (int k = 0; k < 3; ++k) counts[3 * h + k] = -1;
+    if (n < 7 || (n == 7 && h > 0)) continue;
+    int idx[7];
+    rt_count(RT_HYPOTHESES);
+    if (n == 7) {
+      for (int i = 0; i < 7; ++i) idx[i] = i;
+    } else if (!get_subset(m1, m2, n, seed, (uint32_t)h, idx)) {
+      continue;
+    }
+    const int nm = nmodels[h] = run7point(m1, m2, idx, Fh);
+    for (int e = 9 * nm; e < 27; ++e) Fh[e] = 0;  // (a dropped model's numbers are not part of the answer)
+    for (int k = 0; k < nm; ++k) {
+      int good = 0;
+      for (int i = 0; i < n; ++i) good += epi_err(Fh + 9 * k, m1, m2, i) <= t;
+      counts[3 * h + k] = good;
+    }
+  }
+}
 
 // TrackKLT::perform_matching REF: TrackKLT.cpp:829-886.  pts1 holds the initial guess (== pts0 in
 // the reference's monocular path) and receives the tracked positions; n1/n0 receive the

@@ -119,6 +119,7 @@ def load_library():
         "plv_lk_track": (C.c_int, [vp, C.c_int, fp, fp, u8p, ip]),
         "plv_undistort": (C.c_int, [vp, C.c_int, fp, fp]),
         "plv_ransac_fundamental": (C.c_int, [vp, C.c_int, fp, fp, C.c_double, C.c_uint32, u8p, ip, ip]),
+        "plv_ransac_hypotheses": (C.c_int, [vp, C.c_int, fp, fp, C.c_double, C.c_uint32, C.c_int, dp, ip]),
         "plv_perform_matching": (C.c_int, [vp, C.c_int, fp, fp, u8p, fp, fp, C.POINTER(C.c_longlong)]),
         "plv_update_graph_mode": (C.c_int, [vp, C.c_int, ip, ip]),
         "plv_perform_matching_launch": (C.c_int, [vp, C.c_int, fp, fp]),
@@ -1088,6 +1089,14 @@ class Context:
         self._chk(self.lib.plv_ransac_fundamental(self.h, n, _fp(m1), _fp(m2), float(thr), seed, _u8p(mask),
                                                   C.byref(good), C.byref(it)))
         return mask, good.value, it.value
+
+    def ransac_hypotheses(self, m1, m2, thr, seed=0, nhyp=1000):
+        """(diagnostic) every hypothesis of the RANSAC gate: (F [nhyp][3][3][3] in root order, valid [nhyp] 3-bit masks, counts [nhyp][3])"""
+        m1 = np.ascontiguousarray(m1, dtype=np.float32)
+        m2 = np.ascontiguousarray(m2, dtype=np.float32)
+        models, counts = np.zeros((nhyp, 28)), np.zeros((nhyp, 3), dtype=np.int32)
+        self._chk(self.lib.plv_ransac_hypotheses(self.h, m1.shape[0], _fp(m1), _fp(m2), float(thr), seed, nhyp, _dp(models), _ip(counts)))
+        return models[:, :27].reshape(nhyp, 3, 3, 3).copy(), models[:, 27].astype(np.int32), counts
 
     def perform_matching_launch(self, pts0, pts1_init):
         pts0 = np.ascontiguousarray(pts0, dtype=np.float32)

@@ -591,6 +591,20 @@ int plv_ransac_fundamental(plv_ctx *ctx, int n, const float *m1, const float *m2
   return PLV_OK;
 }
 
+int plv_ransac_hypotheses(plv_ctx *ctx, int n, const float *m1, const float *m2, double thr, uint32_t seed, int nhyp, double *models,
+                          int *counts) {
+  if (!ctx || n < 7 || nhyp < 1 || nhyp > 4096 || !m1 || !m2 || !models || !counts) return PLV_E_BADARG;
+  (void)hipSetDevice(ctx->device);
+  FrontState *s = fe(ctx);
+  TRY(reserve_points(s, n, nhyp));
+  PLV_HIP_CHECK(plv::memcpy_async(s->n0.p, m1, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(s->n1.p, m2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  TRY(launch_ransac_hyp(ctx, s->n0.as<float>(), s->n1.as<float>(), n, thr, seed, nhyp, s->counts.as<int>(), s->models.as<double>()));
+  PLV_HIP_CHECK(plv::memcpy_async(models, s->models.p, (size_t)nhyp * 28 * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(counts, s->counts.p, (size_t)nhyp * 3 * 4, hipMemcpyDeviceToHost, ctx->stream));
+  return sync(ctx);
+}
+
 int plv_perform_matching_launch(plv_ctx *ctx, int n, const float *pts0, const float *pts1_init) {
   if (!ctx || n < 0 || (n > 0 && (!pts0 || !pts1_init))) return PLV_E_BADARG;
   FrontState *s0 = fe(ctx);

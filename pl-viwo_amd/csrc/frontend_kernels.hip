@@ -777,7 +777,10 @@ __device__ __forceinline__ float epi_err9(const double (&F)[9], float fx1, float
   c = F[2] * x2 + F[5] * y2 + F[8];
   double s1 = 1. / (a * a + b * b);
   double d1 = x1 * a + y1 * b + c;
-  return (float)fmax(d1 * d1 * s1, d2 * d2 * s2);
+  // std::max(e1, e2), as cv's computeError has it, not fmax: with e1 NaN (a zero epipolar line through the point: 0 * inf) the error
+  // is NaN and the point no inlier, whatever e2 is
+  const double e1 = d1 * d1 * s1, e2 = d2 * d2 * s2;
+  return (float)(e1 < e2 ? e2 : e1);
 }
 __device__ __forceinline__ float epi_err9(const double (&F)[9], const float *m1, const float *m2, int i) {
   return epi_err9(F, m1[2 * i], m1[2 * i + 1], m2[2 * i], m2[2 * i + 1]);
@@ -1358,6 +1361,16 @@ int launch_ransac(plv_ctx *ctx, const float *d_m1, const float *d_m2, int n, dou
                        (int)(mir_bytes / 4), mir_mask);
     if (mirrored) *mirrored = mir_dst != nullptr;
   }
+  PLV_HIP_CHECK(hipGetLastError());
+  return PLV_OK;
+}
+
+// The first half of launch_ransac alone, for plv_ransac_hypotheses: nhyp hypotheses, whatever the adaptive loop would stop at.
+int launch_ransac_hyp(plv_ctx *ctx, const float *d_m1, const float *d_m2, int n, double thr, unsigned seed, int nhyp, int *d_counts,
+                      double *d_models) {
+  const float t = (float)(thr * thr);
+  ProfScope ps(ctx->prof, "ransac_hyp_kernel", ctx->stream);
+  hipLaunchKernelGGL(ransac_hyp_kernel, dim3(nhyp), dim3(64), 0, ctx->stream, d_m1, d_m2, n, t, seed, d_counts, d_models);
   PLV_HIP_CHECK(hipGetLastError());
   return PLV_OK;
 }

@@ -38,5 +38,7 @@ int launch_ransac(plv_ctx *ctx, const float *d_m1, const float *d_m2, int n, dou
                   // *mirrored tells whether a kernel that does it was launched (not for n < 7)
                   const void *mir_src = nullptr, void *mir_dst = nullptr, size_t mir_bytes = 0, uint8_t *mir_mask = nullptr,
                   bool *mirrored = nullptr);
+int launch_ransac_hyp(plv_ctx *ctx, const float *d_m1, const float *d_m2, int n, double thr, unsigned seed, int nhyp, int *d_counts,
+                      double *d_models);
 
 }  // namespace plv

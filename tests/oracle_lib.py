@@ -206,6 +206,10 @@ class FrontOracle:
         L.orc_perform_matching.argtypes = [C.c_void_p, C.c_void_p, C.c_int, fp, fp, dp, C.c_int, C.c_int, C.c_float,
                                            C.c_double, C.c_double, C.c_int, C.c_uint32, u8, fp, fp, C.c_int]
         L.orc_perform_matching.restype = C.c_int
+        L.orc_set_ransac_trace.argtypes = [C.POINTER(C.c_longlong)]
+        L.orc_set_ransac_trace.restype = None
+        L.orc_ransac_hypotheses.argtypes = [fp, fp, C.c_int, C.c_double, C.c_uint32, C.c_int, dp, ip, ip]
+        L.orc_ransac_hypotheses.restype = None
 
     def equalize_hist(self, img):
         img = np.ascontiguousarray(img, dtype=np.uint8)
@@ -254,6 +258,32 @@ class FrontOracle:
                                                seed, mask.ctypes.data_as(u8), C.byref(it))
         return mask, good, it.value
 
+    def ransac_hypotheses(self, m1, m2, thr, seed=0, nhyp=1000):
+        """(F [nhyp][3][3][3], nmodels [nhyp], counts [nhyp][3]): every hypothesis' compacted models and their inlier counts"""
+        m1 = np.ascontiguousarray(m1, dtype=np.float32)
+        m2 = np.ascontiguousarray(m2, dtype=np.float32)
+        F, nm, cnt = np.zeros((nhyp, 27)), np.zeros(nhyp, dtype=np.int32), np.zeros((nhyp, 3), dtype=np.int32)
+        self.lib.orc_ransac_hypotheses(m1.ctypes.data_as(fp), m2.ctypes.data_as(fp), m1.shape[0], thr, seed, nhyp, _dp(F), _ip(nm),
+                                       _ip(cnt))
+        return F.reshape(nhyp, 3, 3, 3), nm, cnt
+
+    def ransac_traced(self, m1, m2, thr, conf=0.999, max_iters=1000, seed=0):
+        """ransac with the trace on: (mask, inliers, iterations used, trace dict keyed by RANSAC_TRACE)"""
+        return self._traced(self.ransac, m1, m2, thr, conf, max_iters, seed)
+
+    def ransac_hypotheses_traced(self, m1, m2, thr, seed=0, nhyp=1000):
+        return self._traced(self.ransac_hypotheses, m1, m2, thr, seed, nhyp)
+
+    def _traced(self, fn, *args):
+        rec = np.zeros(16, dtype=np.int64)
+        rec[RANSAC_TRACE.index("rank_step")] = -1
+        self.lib.orc_set_ransac_trace(rec.ctypes.data_as(C.POINTER(C.c_longlong)))
+        try:
+            out = fn(*args)
+        finally:
+            self.lib.orc_set_ransac_trace(None)
+        return tuple(out) + (dict(zip(RANSAC_TRACE, (int(v) for v in rec))),)
+
     def run7point(self, m1, m2, idx):
         m1 = np.ascontiguousarray(m1, dtype=np.float32)
         m2 = np.ascontiguousarray(m2, dtype=np.float32)
@@ -276,6 +306,11 @@ class FrontOracle:
                                            mask.ctypes.data_as(u8), n0.ctypes.data_as(fp), n1.ctypes.data_as(fp),
                                            nthreads)
         return rc, pts1, mask, n0, n1
+
+
+# the slots of orc_set_ransac_trace (oracle/frontend_oracle.cpp)
+RANSAC_TRACE = ("c1_zero", "linear", "quad_neg", "quad", "three", "double", "one", "xr_clamp", "rank_fail", "rank_step", "f8_zero",
+                "nonfinite", "retry", "no_subset", "hypotheses")
 
 
 class OraclePyramid:

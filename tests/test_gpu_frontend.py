@@ -7,6 +7,7 @@ import pytest
 
 import oracle_lib
 import synth
+from ransac_cases import two_view as _two_view
 
 pytestmark = pytest.mark.gpu
 
@@ -155,20 +156,6 @@ def test_undistort_bit_exact(pkg, fo):
     K = np.array(list(c.cfg.intrinsics))
     assert np.array_equal(c.undistort(uv), fo.undistort(K, uv))
     c.close()
-
-
-def _two_view(n, seed, outliers):
-    rng = np.random.default_rng(seed)
-    X = np.column_stack([rng.uniform(-4, 4, n), rng.uniform(-3, 3, n), rng.uniform(4, 12, n)])
-    th = 0.05
-    R = np.array([[np.cos(th), 0, np.sin(th)], [0, 1, 0], [-np.sin(th), 0, np.cos(th)]])
-    X2 = X @ R.T + np.array([0.3, 0.05, 0.1])
-    m1, m2 = X[:, :2] / X[:, 2:], X2[:, :2] / X2[:, 2:]
-    m1 = m1 + rng.normal(0, 0.3 / 458, m1.shape)
-    m2 = m2 + rng.normal(0, 0.3 / 458, m2.shape)
-    bad = rng.choice(n, outliers, replace=False)
-    m2[bad] += rng.uniform(-0.2, 0.2, (outliers, 2))
-    return m1.astype(np.float32), m2.astype(np.float32)
 
 
 @pytest.mark.parametrize("n,outl,seed", [(250, 50, 2), (500, 200, 3), (40, 5, 4), (7, 0, 5), (12, 0, 6)])
