@@ -1351,7 +1351,7 @@ class Context:
                                                    _dp(lg), cap))
         m = res.n_msckf
         return dict(dx=dx, n_pool=res.n_pool, n_lines=m, n_accepted=res.n_accepted, n_rows=res.n_rows, n_returned=res.n_returned,
-                    status=res.status, ids=ids[:m].copy(), accepted=acc[:m].copy(), line_FinG=lg[:m].copy())
+                    status=res.status, ids=ids[:m].copy(), accepted=acc[:m].copy(), line_FinG=lg[:m].copy(), n_truncated=res.n_truncated)
 
     def _try_update_io(self, plus, n, max_msckf, max_obs, t_prev_frame, state_time, window_full=True, chi2_mult=1.0, min_dist=0.1, max_dist=60.0,
                        max_cond=1e4, max_baseline=40.0, refine=True, init_min_meas=10, lines=True, cap=512):

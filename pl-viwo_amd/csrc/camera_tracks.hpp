@@ -58,6 +58,7 @@ struct BoundingMemo {
 
 struct Track {  // ov_core::Feature, one camera  (REF: open_vins/ov_core/src/feat/Feature.h:43-77)
   static constexpr int W = 2;  // floats of uv / uvn per observation: an image point
+  static constexpr int P = 3;  // doubles of the triangulated feature: p_FinG
   std::vector<double> t;
   std::vector<float> uv, uvn;
   // (transient, Tracker::Spec) index of the track's point in the flow's batch of feed number li_seq
@@ -67,6 +68,7 @@ struct Track {  // ov_core::Feature, one camera  (REF: open_vins/ov_core/src/fea
 
 struct LineTrack {  // LineFeature, one camera   REF: linefeat/LineFeature.h:22-107
   static constexpr int W = 4;  // floats of uv / uvn per observation: the segment's two end points
+  static constexpr int P = 6;  // doubles of the triangulated feature: line_FinG
   std::vector<double> t;
   std::vector<float> uv, uvn;
   std::vector<int> points;     // ids of the point features assigned at every observation (appended, REF :50-52)
@@ -271,6 +273,86 @@ template <class TrackT> void gather_obs(ObsGather &g, const TrackT &tr, size_t i
     g.Q.insert(g.Q.end(), &cpi.Q[36 * o], &cpi.Q[36 * o] + 36);
     g.C.push_back(cpi.C[o]);
   }
+}
+
+// ---- the batch tail of an update: what follows the triangulation and gate results of the pool.  start_of: BoundingMemo (or the
+// like); an observation is usable when its time + dt has bounding clones (get_imu_poses, REF CamHelper.cpp:327-372)
+
+template <class TrackT, class StartOf> int usable_views(const TrackT &tr, double dt, StartOf &start_of) {
+  return (int)std::count_if(tr.t.begin(), tr.t.end(), [&](double t) { return start_of(t + dt) >= 0; });
+}
+// usable views of every pool candidate; returns the largest count
+template <class TrackT, class StartOf>
+int count_usable(const std::vector<PoolCand<TrackT>> &pool, double dt, StartOf &start_of, std::vector<int> &valid_n) {
+  valid_n.assign(pool.size(), 0);
+  int most = 0;
+  for (size_t f = 0; f < pool.size(); ++f) most = std::max(most, valid_n[f] = usable_views(pool[f].tr, dt, start_of));
+  return most;
+}
+
+// the selection loop's result, and the two-step route's arrays of the selected tracks (plv_tracks / plv_line_tracks)
+template <class TrackT> struct Selection {
+  std::vector<int> sel;       // pool indices, in the order they were taken
+  std::vector<int> n_skip;    // per pool candidate: usable observations a truncated track leaves out (its oldest)
+  std::vector<int> sptr;      // CSR over sel of g's observations
+  std::vector<double> feat;   // TrackT::P per selected track
+  ObsGather g;
+  std::vector<uint8_t> acc;   // the gate's verdict per selected track
+  explicit Selection(size_t n_pool) : n_skip(n_pool, 0) {}
+  // batch capacity of the update (the reference has none): candidate f is taken; of `valid` usable observations the newest max_obs
+  // are used, the older ones are consumed with the feature — counted in n_truncated
+  void take(int f, int valid, int max_obs, int &n_truncated) {
+    if (valid > max_obs) n_skip[f] = valid - max_obs, ++n_truncated;
+    sel.push_back(f);
+  }
+};
+
+// the selected tracks, in order: views without bounding clones go back, the n_skip oldest usable ones are left out, the rest is
+// gathered for the two-step route (ptr: flatten_pool's, the index of CpiPoses); the feature values (feat_all: P per pool candidate)
+// and ids of the selected.  Behind a fused launch the batch was built on the device: nothing is gathered, and a track whose views
+// all counted as usable is not walked at all.
+template <class TrackT, class StartOf>
+void gather_selected(const std::vector<PoolCand<TrackT>> &pool, const std::vector<int> &valid_n, const std::vector<int> &ptr, const CpiPoses &cpi,
+                     const double *feat_all, bool fused_ran, double dt, StartOf &start_of, TrackMap<TrackT> &unused, Selection<TrackT> &S,
+                     uint64_t *ids_out) {
+  constexpr size_t P = TrackT::P;
+  const size_t n = S.sel.size();
+  S.sptr.assign(n + 1, 0), S.feat.resize(P * n);
+  for (size_t q = 0; q < n; ++q) {
+    const int f = S.sel[q];
+    const PoolCand<TrackT> &c = pool[f];
+    int seen = 0;
+    const bool nothing_to_do = fused_ran && valid_n[f] == (int)c.tr.t.size();
+    for (size_t i = 0; !nothing_to_do && i < c.tr.t.size(); ++i) {
+      if (start_of(c.tr.t[i] + dt) < 0) {
+        give_back(unused, c.id, c.tr, i);
+        continue;
+      }
+      if (seen++ < S.n_skip[f] || fused_ran) continue;
+      gather_obs(S.g, c.tr, i, cpi, ptr[f] + i);
+    }
+    S.sptr[q + 1] = (int)S.g.t.size();
+    std::copy(feat_all + P * f, feat_all + P * (f + 1), S.feat.begin() + P * q);
+    if (ids_out) ids_out[q] = c.id;
+  }
+}
+
+// REF UpdaterCamera.cpp:266-268 / :441-444: only what the gate rejected goes back (what EKFUpdate then rejects is consumed all the
+// same) — every usable view, the skipped oldest of a truncated track included.  whole(f): the caller returns candidate f's track
+// itself (true), or leaves it to the view-by-view copy.  Writes the verdicts to accepted_out (may be null); returns how many passed.
+template <class TrackT, class StartOf, class Whole>
+int return_rejected(const std::vector<PoolCand<TrackT>> &pool, const Selection<TrackT> &S, double dt, StartOf &start_of, TrackMap<TrackT> &unused,
+                    uint8_t *accepted_out, Whole whole) {
+  int n_accepted = 0;
+  for (size_t q = 0; q < S.sel.size(); ++q) {
+    n_accepted += S.acc[q];
+    if (accepted_out) accepted_out[q] = S.acc[q];
+    if (S.acc[q] || whole(S.sel[q])) continue;
+    const PoolCand<TrackT> &c = pool[S.sel[q]];
+    for (size_t i = 0; i < c.tr.t.size(); ++i)
+      if (start_of(c.tr.t[i] + dt) >= 0) give_back(unused, c.id, c.tr, i);
+  }
+  return n_accepted;
 }
 
 // append_new_measurements (REF FeatureDatabase.cpp): tr's observations appended to the database's track of id — tr itself when the

@@ -30,6 +30,7 @@
 #include "update_state.hpp"
 #include "plv_internal.hpp"
 #include "camera_tracks.hpp"
+#include "update_tail.hpp"
 
 using namespace plv;
 using namespace plv::linehost;
@@ -84,6 +85,14 @@ struct LinesJob {
   std::vector<double> lg_two_step;   // TWO_STEP: the triangulation ran as its own call inside the first half
   std::vector<uint8_t> ok_two_step;
   double us_pool = 0;
+  // the pool as the device batch (valid while the job's arrays stand)
+  plv_line_tracks view() const {
+    plv_line_tracks all{};
+    all.n_lines = Lp, all.obs_ptr = ptr.data(), all.obs_time = ot.data(), all.seg_uv = uv.data(), all.seg_uvn = uvn.data();
+    all.D = D.data(), all.anchor_pt = anchor.data(), all.has_pt = has.data();
+    if (cpi.on) all.res_R = cpi.R.data(), all.res_p = cpi.p.data();
+    return all;
+  }
 };
 
 struct LineTracker {
@@ -1091,24 +1100,8 @@ static int lines_first_half(plv_ctx *ctx, LineTracker *T, const plv_state_view *
     J.stage = LinesJob::EMPTY;
     return PLV_OK;
   }
-  plv_line_tracks all{};
-  all.n_lines = Lp;
-  all.obs_ptr = ptr.data();
-  all.obs_time = J.ot.data();
-  all.seg_uv = J.uv.data();
-  all.seg_uvn = J.uvn.data();
-  all.D = D.data();
-  all.anchor_pt = J.anchor.data();
-  all.has_pt = J.has.data();
-  if (J.cpi.on) {
-    all.res_R = J.cpi.R.data();
-    all.res_p = J.cpi.p.data();
-  }
-  J.valid_n.assign(Lp, 0);
-  for (int l = 0; l < Lp; ++l) {
-    for (double t : pool[l].tr.t) J.valid_n[l] += start_of(t + dt) >= 0;
-    J.most_valid = std::max(J.most_valid, J.valid_n[l]);
-  }
+  const plv_line_tracks all = J.view();
+  J.most_valid = count_usable(pool, dt, start_of, J.valid_n);
   J.cols.resize(ctx->cfg.max_state_dim > 0 ? ctx->cfg.max_state_dim : 1024);
   // ---- one submission (see plv_camera_update_points): line triangulation, the selection below, Jacobians, null space, gate,
   // compression and EKFUpdate back to back on the stream, one synchronisation.  CPI poses and over-long tracks take the two-step route.
@@ -1130,6 +1123,7 @@ static int lines_first_half(plv_ctx *ctx, LineTracker *T, const plv_state_view *
   plv::HostPhase ph_cols("update_lines: columns");
   int rc = plv_line_jacobian_columns(st, &all, J.cols.data(), (int)J.cols.size(), &J.k);
   ph_cols.stop();
+  bool launched = false;
   if (rc == PLV_OK && J.k > 0) {
     plv::HostPhase ph_sub("update_lines: fused submit (gate prepare + stage + upload + launch)");
     ctx->gate_rows_hint = 2 * J.most_valid;
@@ -1137,16 +1131,10 @@ static int lines_first_half(plv_ctx *ctx, LineTracker *T, const plv_state_view *
     rc = plv_lines_update_fused_submit(ctx, st, st_tri, &all, J.flags.data(), cap, J.k, J.cols.data(), 2 * opt->max_obs, st->sigma_pix * st->sigma_pix,
                                        opt->chi2_mult);
     ch.on = false;
-    if (rc == PLV_OK) {
-      J.stage = LinesJob::FUSED_LAUNCHED;
-      return PLV_OK;
-    }
+    launched = rc == PLV_OK;
   }
-  if (rc == PLV_OK) {  // (no column: nothing to linearise)
-    J.stage = LinesJob::FUSED_NOTHING;
-    return PLV_OK;
-  }
-  J.stage = LinesJob::FAILED, J.rc = rc;
+  if (rc != PLV_OK) J.stage = LinesJob::FAILED, J.rc = rc;
+  else J.stage = launched ? LinesJob::FUSED_LAUNCHED : LinesJob::FUSED_NOTHING;  // (no column: nothing to linearise)
   return PLV_OK;
 }
 
@@ -1194,67 +1182,63 @@ void plv_camera_lines_job_abort(plv_ctx *ctx) { plv_camera_lines_job_abort2(ctx,
 }  // namespace plv
 extern "C" {
 
-int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, double *dx,
-                            plv_update_result *res, uint64_t *line_ids, uint8_t *accepted_out, double *lines_out, int cap) {
-  if (!ctx || !st || !opt || !dx || !res || st->n_clones < 2 || opt->max_obs < 2) return PLV_E_BADARG;
-  LineTracker *T = ltr(ctx);
-  *res = plv_update_result{0, 0, 0, 0, 0, PLV_OK, 0, 0, 0};
-  const bool timing = plv::knob(plv::PLV_KNOB_UPDATE_TIMING);
-  plv::NsScope ns_lines(plv::counters().lines_ns);
-  plv::HostPhase ph_all("update_lines: whole call");
-  plv::RoctxRange rx_line("[Time-Cam] LINE update");
-  auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count(); };
-  LinesJob Jlocal;
-  const bool resumed = T->ujob.pending && T->ujob.cap == cap && T->ujob.n_clones == st->n_clones && T->ujob.state_time == opt->state_time &&
-                       T->ujob.t_prev_frame == opt->t_prev_frame;
-  if (T->ujob.pending && !resumed) {  // (a chained first half for other arguments than these: cannot be — its launch may be on the stream)
-    plv::set_last_error("plv_camera_update_lines: a chained submission for another window is pending");
-    return PLV_E_BADARG;
+namespace {
+// the first half run on the spot (no chained one waits for its second): on the state plv_camera_get_line_features recorded
+int lines_first_half_now(plv_ctx *ctx, LineTracker *T, const plv_state_view *st, const plv_update_options *opt, int cap, LinesJob &J) {
+  // the state of the triangulation: what plv_camera_get_line_features recorded (same window), else the state handed in
+  LineTracker::TriState tri_keep;
+  std::swap(tri_keep, T->tri_state);
+  T->tri_state.valid = false;
+  if (tri_keep.valid) {  // (the vectors moved: re-point the view)
+    tri_keep.view.clone_time = tri_keep.clone_time.data();
+    tri_keep.view.clone_R = tri_keep.view.clone_R_fej = tri_keep.clone_R.data();
+    tri_keep.view.clone_p = tri_keep.view.clone_p_fej = tri_keep.clone_p.data();
+    tri_keep.view.clone_state_id = tri_keep.clone_id.data();
+    if (tri_keep.view.n_clones != st->n_clones || memcmp(tri_keep.clone_time.data(), st->clone_time, 8 * (size_t)st->n_clones) != 0) tri_keep.valid = false;
   }
-  LinesJob &J = resumed ? T->ujob : Jlocal;
-  if (!resumed) {
-    // the state of the triangulation: what plv_camera_get_line_features recorded (same window), else the state handed in
-    LineTracker::TriState tri_keep;
-    std::swap(tri_keep, T->tri_state);
-    T->tri_state.valid = false;
-    if (tri_keep.valid) {  // (the vectors moved: re-point the view)
-      tri_keep.view.clone_time = tri_keep.clone_time.data();
-      tri_keep.view.clone_R = tri_keep.view.clone_R_fej = tri_keep.clone_R.data();
-      tri_keep.view.clone_p = tri_keep.view.clone_p_fej = tri_keep.clone_p.data();
-      tri_keep.view.clone_state_id = tri_keep.clone_id.data();
-      if (tri_keep.view.n_clones != st->n_clones || memcmp(tri_keep.clone_time.data(), st->clone_time, 8 * (size_t)st->n_clones) != 0) tri_keep.valid = false;
-    }
-    const plv_state_view *st_tri = tri_keep.valid ? &tri_keep.view : st;
-    TRY(lines_first_half(ctx, T, st, st_tri, opt, cap, J, false));
-    if (J.stage == LinesJob::TWO_STEP) {  // (triangulation as its own synchronous call, on st_tri while it is in scope)
-      J.ok_two_step.resize(J.Lp), J.lg_two_step.resize(6 * (size_t)J.Lp);
-      plv_line_tracks all{};
-      all.n_lines = J.Lp, all.obs_ptr = J.ptr.data(), all.obs_time = J.ot.data(), all.seg_uv = J.uv.data(), all.seg_uvn = J.uvn.data();
-      all.D = J.D.data(), all.anchor_pt = J.anchor.data(), all.has_pt = J.has.data();
-      if (J.cpi.on) all.res_R = J.cpi.R.data(), all.res_p = J.cpi.p.data();
-      const int rc2 = plv_triangulate_lines(ctx, st_tri, &all, J.lg_two_step.data(), J.ok_two_step.data());
-      if (rc2 != PLV_OK) J.stage = LinesJob::FAILED, J.rc = rc2;
-    }
+  const plv_state_view *st_tri = tri_keep.valid ? &tri_keep.view : st;
+  TRY(lines_first_half(ctx, T, st, st_tri, opt, cap, J, false));
+  if (J.stage == LinesJob::TWO_STEP) {  // (triangulation as its own synchronous call, on st_tri while it is in scope)
+    J.ok_two_step.resize(J.Lp), J.lg_two_step.resize(6 * (size_t)J.Lp);
+    const plv_line_tracks all = J.view();
+    const int rc2 = plv_triangulate_lines(ctx, st_tri, &all, J.lg_two_step.data(), J.ok_two_step.data());
+    if (rc2 != PLV_OK) J.stage = LinesJob::FAILED, J.rc = rc2;
   }
-  T->ujob.pending = false;
+  return PLV_OK;
+}
+
+typedef PoolCand<LineTrack> Cand;
+
+// The second half of one plv_camera_update_lines call: what its stages share.
+struct LinesUpdate {
+  plv_ctx *ctx;
+  LineTracker *T;
+  const plv_state_view *st;
+  const plv_update_options *opt;
+  double *dx;
+  plv_update_result *res;
+  LinesJob &J;
   const double dt = st->cam_dt, t_oldest = st->clone_time[0];
-  BoundingMemo start_of(*st);
-  typedef PoolCand<LineTrack> Cand;
-  LinePool &LP = J.LP;
-  std::vector<Cand> &pool = LP.pool;
-  TrackMap<LineTrack> &unused = LP.unused;
-  res->n_pool = LP.n_pool;
+  BoundingMemo start_of{*st};
+  std::vector<Cand> &pool = J.LP.pool;
+  TrackMap<LineTrack> &unused = J.LP.unused;
   std::vector<int> lazy_back;  // pool candidates whose whole track returns to the database: moved there by the deferred hand-back
+  bool db_scanned_early = false;
+  std::vector<double> lg;
+  std::vector<uint8_t> ok, acc_all;
+  int n_rows = 0;
+  bool fused_ran = false;
+
   // cleanup_measurements over the tracks that stayed in the database, placed inside the update's wait for the device (they do not
   // depend on its result); finish() then cleans only what returns
-  bool db_scanned_early = false;
-  std::function<void()> scan_db_early = [&]() {
+  void scan_db_early() {
     if (!opt->window_full || db_scanned_early) return;
     std::lock_guard<std::mutex> lk(T->mtx);
     for (auto it = T->db.begin(); it != T->db.end();) it = drop_before(it->second, t_oldest) == 0 ? T->db.erase(it) : std::next(it);
     db_scanned_early = true;
-  };
-  auto finish = [&](int rc) {
+  }
+
+  int finish(int rc) {
     plv::HostPhase ph_fin("update_lines: finish (counts, point_used clean-up, hand-back closure)");
     res->n_returned = (int)unused.size();
     for (int l : lazy_back) res->n_returned += unused.find(pool[l].id) == unused.end() ? 1 : 0;
@@ -1263,8 +1247,8 @@ int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_up
     // REF :71 / cleanup_lines :545-546 append_new_measurements, then LineHelper.cpp:549-551, UpdaterCamera.cpp:186-188 (on every
     // try_update) cleanup_measurements(oldest clone).  Whole tracks (`whole`: candidates the update did not take and of which nothing
     // went back earlier) enter the database with one insertion; the cleanup touches every track, or — when the database was cleaned
-    // inside the update's wait (scan_db_early below) — only the tracks that return now.
-    auto hand_back = [T, window_full, t_oldest, scanned](TrackMap<LineTrack> &un, std::vector<Cand> *cands, const std::vector<int> *whole) {
+    // inside the update's wait (scan_db_early) — only the tracks that return now.
+    auto hand_back = [T = T, window_full, t_oldest = t_oldest, scanned](TrackMap<LineTrack> &un, std::vector<Cand> *cands, const std::vector<int> *whole) {
       std::lock_guard<std::mutex> lk(T->mtx);
       auto put = [&](uint64_t id, LineTrack &tr) {
         const auto it = put_track(T->db, id, tr);
@@ -1303,124 +1287,46 @@ int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_up
       lazy_back.clear();
     }
     return rc;
-  };
-  std::fill(dx, dx + ctx->cov_n, 0.0);
-  if (J.stage == LinesJob::EMPTY) return finish(PLV_OK);
-  if (J.stage == LinesJob::FAILED) {
+  }
+  // a failing exit: the whole pool returns to the database
+  int abandon(int rc) {
     for (Cand &c : pool) give_back_all(unused, c);
-    return finish(J.rc);
+    return finish(rc);
   }
-  const int Lp = J.Lp, nobs = J.nobs;
-  std::vector<int> &valid_n = J.valid_n, &cols = J.cols;
-  std::vector<double> lg(6 * (size_t)Lp);
-  std::vector<uint8_t> ok(Lp);
-  int k = J.k, n_rows = 0, rc = PLV_OK;
-  const double us_pool = J.us_pool;
-  plv::HostPhase ph_dev("update_lines: device submission + wait");
-  const auto U1 = std::chrono::steady_clock::now();
-  std::vector<uint8_t> acc_all(Lp, 0);
-  bool fused_ran = false;
-  if (J.stage == LinesJob::FUSED_LAUNCHED) {
-    LineWaitHook hook{ctx, &scan_db_early};
-    rc = plv_lines_update_fused_finish(ctx, st->sigma_pix * st->sigma_pix, opt->chi2_mult, lg.data(), ok.data(), acc_all.data(), &n_rows, dx,
-                                       line_wait_hook, &hook);
-    res->status = rc == PLV_E_NOT_PSD ? rc : PLV_OK;
-    if (rc == PLV_E_NOT_PSD) {
-      rc = PLV_OK;
-      std::fill(dx, dx + ctx->cov_n, 0.0);
+
+  // triangulation and gate results of the pool, by the job's stage: the fused launch's (waited for here), none, or the two-step
+  // triangulation's
+  int collect() {
+    const int Lp = J.Lp;
+    lg.resize(6 * (size_t)Lp), ok.resize(Lp), acc_all.assign(Lp, 0);
+    if (J.stage == LinesJob::FUSED_LAUNCHED) {
+      std::function<void()> scan = [this]() { scan_db_early(); };
+      LineWaitHook hook{ctx, &scan};
+      int rc = plv_lines_update_fused_finish(ctx, st->sigma_pix * st->sigma_pix, opt->chi2_mult, lg.data(), ok.data(), acc_all.data(), &n_rows, dx,
+                                             line_wait_hook, &hook);
+      rc = ekf_returned_false(rc, &res->status, dx, ctx->cov_n);
+      fused_ran = rc == PLV_OK;
+      return rc;
     }
-    fused_ran = rc == PLV_OK;
-    if (rc != PLV_OK) {
-      for (Cand &c : pool) give_back_all(unused, c);
-      return finish(rc);
-    }
-  } else if (J.stage == LinesJob::FUSED_NOTHING) {
-    std::fill(ok.begin(), ok.end(), 0);
-  } else {  // TWO_STEP
-    lg = J.lg_two_step;
-    ok = J.ok_two_step;
+    if (J.stage == LinesJob::TWO_STEP) lg = J.lg_two_step, ok = J.ok_two_step;  // (FUSED_NOTHING: ok stays 0 for every line)
+    return PLV_OK;
   }
-  const double us_dev = since(U1);
-  ph_dev.stop();
-  plv::frame_mark("@ line gate / update collected");
-  plv::HostPhase ph_post("update_lines: selection + database");
-  if (timing) fprintf(stderr, "update lines: pool + staging %.1f us (%d lines, %d observations), device submission + wait %.1f us\n", us_pool, Lp, nobs, us_dev);
-  std::vector<int> sel;
-  std::vector<int> n_skip(Lp, 0);  // usable observations a truncated track leaves out (its first ones)
-  for (int l = 0; l < Lp; ++l) {
-    const int valid = valid_n[l];
-    if (!ok[l] || valid < 2 || (int)sel.size() >= cap) {
-      lazy_back.push_back(l);  // (the whole track goes back: finish() does it, deferred when the caller allows)
-      continue;
-    }
-    if (valid > opt->max_obs) {  // batch capacity (none in the reference): the last max_obs usable observations, counted in n_truncated
-      n_skip[l] = valid - opt->max_obs;
-      ++res->n_truncated;
-    }
-    sel.push_back(l);
-  }
-  res->n_msckf = (int)sel.size();
-  plv::frame_mark("@ line selection loop done");
-  if (sel.empty()) {
-    if (fused_ran) std::fill(dx, dx + ctx->cov_n, 0.0);
-    return finish(PLV_OK);
-  }
-  // ---- UpdaterCamera::lines_update
-  const int L = (int)sel.size();
-  std::vector<int> sptr(L + 1, 0);
-  std::vector<double> sl(6 * (size_t)L);
-  ObsGather g;
-  for (int q = 0; q < L; ++q) {
-    const Cand &c = pool[sel[q]];
-    int seen = 0;
-    // (behind a fused launch the loop only hands back views without bounding clones: none when every view counted as usable)
-    const bool nothing_to_do = fused_ran && valid_n[sel[q]] == (int)c.tr.t.size();
-    for (size_t i = 0; !nothing_to_do && i < c.tr.t.size(); ++i) {
-      if (start_of(c.tr.t[i] + dt) < 0) {
-        give_back(unused, c.id, c.tr, i);
+
+  void select(Selection<LineTrack> &S, int cap) {
+    for (int l = 0; l < J.Lp; ++l) {
+      const int valid = J.valid_n[l];
+      if (!ok[l] || valid < 2 || (int)S.sel.size() >= cap) {
+        lazy_back.push_back(l);  // (the whole track goes back: finish() does it, deferred when the caller allows)
         continue;
       }
-      if (seen++ < n_skip[sel[q]]) continue;
-      if (fused_ran) continue;  // (the batch was built on the device: the two-step route's arrays are not needed)
-      gather_obs(g, c.tr, i, J.cpi, J.ptr[sel[q]] + i);
+      S.take(l, valid, opt->max_obs, res->n_truncated);
     }
-    sptr[q + 1] = (int)g.t.size();
-    std::copy(lg.begin() + 6 * (size_t)sel[q], lg.begin() + 6 * (size_t)sel[q] + 6, sl.begin() + 6 * (size_t)q);
-    if (line_ids) line_ids[q] = c.id;
+    res->n_msckf = (int)S.sel.size();
   }
-  if (lines_out) std::copy(sl.begin(), sl.end(), lines_out);
-  plv_line_tracks lt{};
-  lt.n_lines = L;
-  lt.obs_ptr = sptr.data();
-  lt.obs_time = g.t.data();
-  lt.seg_uv = g.uv.data();
-  lt.line_FinG = sl.data();
-  if (J.cpi.on) {
-    lt.res_R = g.R.data();
-    lt.res_p = g.p.data();
-    if (J.cpi.noise) {
-      lt.res_Q = g.Q.data();
-      lt.res_clone = g.C.data();
-    }
-  }
-  std::vector<uint8_t> acc(L, 0);
-  if (fused_ran) {
-    for (int q = 0; q < L; ++q) acc[q] = acc_all[sel[q]];
-  } else {
-    rc = plv_line_jacobian_columns(st, &lt, cols.data(), (int)cols.size(), &k);
-    if (rc == PLV_OK) rc = plv_build_line_jacobians_resident(ctx, st, &lt, k, cols.data(), 2 * opt->max_obs);
-    if (rc == PLV_OK) {
-      rc = plv_msckf_update_resident(ctx, st->sigma_pix * st->sigma_pix, opt->chi2_mult, 0.0, acc.data(), &n_rows, dx);
-      res->status = rc;
-      if (rc == PLV_E_NOT_PSD) rc = PLV_OK;
-    }
-    if (rc != PLV_OK) {
-      for (int q = 0; q < L; ++q) give_back_all(unused, pool[sel[q]]);
-      return finish(rc);
-    }
-  }
-  res->n_rows = n_rows;
-  if (ctx->decision_trace) {  // (plv_last_line_decisions: the gate's values of the lines that reached it, in the order of line_ids)
+
+  // (plv_last_line_decisions: the gate's values of the lines that reached it, in the order of line_ids)
+  int record_decisions(const Selection<LineTrack> &S) {
+    const int L = (int)S.sel.size();
     const double nan = std::numeric_limits<double>::quiet_NaN();
     const int Fg = ctx->dec_F_l;
     std::vector<double> gv(3 * (size_t)std::max(Fg, 1), nan);
@@ -1428,29 +1334,75 @@ int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_up
     ctx->dec_F_l = 0;
     T->dec_ids.resize(L), T->dec_vals.assign(3 * (size_t)L, nan);
     for (int q = 0; q < L; ++q) {
-      const int gi = fused_ran ? sel[q] : q;
-      T->dec_ids[q] = pool[sel[q]].id;
+      const int gi = fused_ran ? S.sel[q] : q;
+      T->dec_ids[q] = pool[S.sel[q]].id;
       if (gi < Fg) std::copy(gv.begin() + 3 * (size_t)gi, gv.begin() + 3 * (size_t)gi + 3, T->dec_vals.begin() + 3 * (size_t)q);
     }
+    return PLV_OK;
   }
+
+  // REF UpdaterCamera.cpp:441-444 copy_to_db(lbd_unused, line) of a rejected line: every view usable and nothing of the line handed
+  // back earlier — the usual case — makes the copy the reference builds view by view the track itself, returned whole by the
+  // hand-back like the candidates the update never took
+  bool returns_whole(int l) {
+    if (J.valid_n[l] != (int)pool[l].tr.t.size() || unused.find(pool[l].id) != unused.end()) return false;  // (valid_n: the views with bounding clones)
+    lazy_back.push_back(l);
+    return true;
+  }
+};
+}  // namespace
+
+int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, double *dx,
+                            plv_update_result *res, uint64_t *line_ids, uint8_t *accepted_out, double *lines_out, int cap) {
+  if (!ctx || !st || !opt || !dx || !res || st->n_clones < 2 || opt->max_obs < 2) return PLV_E_BADARG;
+  LineTracker *T = ltr(ctx);
+  *res = plv_update_result{0, 0, 0, 0, 0, PLV_OK, 0, 0, 0};
+  const bool timing = plv::knob(plv::PLV_KNOB_UPDATE_TIMING);
+  plv::NsScope ns_lines(plv::counters().lines_ns);
+  plv::HostPhase ph_all("update_lines: whole call");
+  plv::RoctxRange rx_line("[Time-Cam] LINE update");
+  auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count(); };
+  LinesJob Jlocal;
+  const bool resumed = T->ujob.pending && T->ujob.cap == cap && T->ujob.n_clones == st->n_clones && T->ujob.state_time == opt->state_time &&
+                       T->ujob.t_prev_frame == opt->t_prev_frame;
+  if (T->ujob.pending && !resumed) {  // (a chained first half for other arguments than these: cannot be — its launch may be on the stream)
+    plv::set_last_error("plv_camera_update_lines: a chained submission for another window is pending");
+    return PLV_E_BADARG;
+  }
+  LinesJob &J = resumed ? T->ujob : Jlocal;
+  if (!resumed) TRY(lines_first_half_now(ctx, T, st, opt, cap, J));
+  T->ujob.pending = false;
+  LinesUpdate U{ctx, T, st, opt, dx, res, J};
+  res->n_pool = J.LP.n_pool;
+  std::fill(dx, dx + ctx->cov_n, 0.0);
+  if (J.stage == LinesJob::EMPTY) return U.finish(PLV_OK);
+  if (J.stage == LinesJob::FAILED) return U.abandon(J.rc);
+  plv::HostPhase ph_dev("update_lines: device submission + wait");
+  const auto U1 = std::chrono::steady_clock::now();
+  int rc = U.collect();
+  if (rc != PLV_OK) return U.abandon(rc);
+  const double us_dev = since(U1);
+  ph_dev.stop();
+  plv::frame_mark("@ line gate / update collected");
+  plv::HostPhase ph_post("update_lines: selection + database");
+  if (timing) fprintf(stderr, "update lines: pool + staging %.1f us (%d lines, %d observations), device submission + wait %.1f us\n", J.us_pool, J.Lp, J.nobs, us_dev);
+  Selection<LineTrack> S(J.Lp);
+  U.select(S, cap);
+  plv::frame_mark("@ line selection loop done");
+  if (S.sel.empty()) {
+    if (U.fused_ran) std::fill(dx, dx + ctx->cov_n, 0.0);
+    return U.finish(PLV_OK);
+  }
+  // ---- UpdaterCamera::lines_update
+  gather_selected(U.pool, J.valid_n, J.ptr, J.cpi, U.lg.data(), U.fused_ran, U.dt, U.start_of, U.unused, S, line_ids);
+  if (lines_out) std::copy(S.feat.begin(), S.feat.end(), lines_out);
+  rc = update_selected(ctx, st, opt, J.cpi, U.pool, U.unused, S, U.acc_all, U.fused_ran, J.cols, ctx->cov_n, &res->status, &U.n_rows, dx);
+  if (rc != PLV_OK) return U.finish(rc);
+  res->n_rows = U.n_rows;
+  if (ctx->decision_trace) TRY(U.record_decisions(S));
   plv::frame_mark("@ line arrays of the selected done");
-  for (int q = 0; q < L; ++q) {
-    res->n_accepted += acc[q];
-    if (accepted_out) accepted_out[q] = acc[q];
-    if (!acc[q]) {  // REF UpdaterCamera.cpp:441-444 copy_to_db(lbd_unused, line): gate failures only
-      const Cand &c = pool[sel[q]];
-      // (every view usable and nothing of the line handed back earlier — the usual case: the copy the reference makes view by view
-      // is the track itself, returned whole by the hand-back like the candidates the update never took)
-      const bool whole = valid_n[sel[q]] == (int)c.tr.t.size() && unused.find(c.id) == unused.end();  // (valid_n: the views with bounding clones)
-      if (whole) {
-        lazy_back.push_back(sel[q]);
-        continue;
-      }
-      for (size_t i = 0; i < c.tr.t.size(); ++i)
-        if (start_of(c.tr.t[i] + dt) >= 0) give_back(unused, c.id, c.tr, i);
-    }
-  }
-  return finish(PLV_OK);
+  res->n_accepted = return_rejected(U.pool, S, U.dt, U.start_of, U.unused, accepted_out, [&U](int l) { return U.returns_whole(l); });
+  return U.finish(PLV_OK);
 }
 
 }  // extern "C"

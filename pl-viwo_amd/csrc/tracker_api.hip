@@ -17,6 +17,7 @@
 #include "plv_internal.hpp"
 #include "gate_stage.hpp"
 #include "camera_tracks.hpp"
+#include "update_tail.hpp"
 
 using plv::Track;
 
@@ -639,72 +640,38 @@ int plv_db_append_measurements(plv_ctx *ctx, uint64_t id, int n, const double *t
   return PLV_OK;
 }
 
-int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, double *dx,
-                             plv_update_result *res, uint64_t *msckf_ids, uint8_t *accepted_out, double *p_out) {
-  if (!ctx || !st || !opt || !dx || !res || st->n_clones < 2 || opt->max_msckf < 1 || opt->max_obs < 2) return PLV_E_BADARG;
-  Tracker *T = trk(ctx);
-  *res = plv_update_result{0, 0, 0, 0, 0, PLV_OK, 0, 0, 0};
-  plv::NsScope ns_points(plv::counters().points_ns);
-  plv::HostPhase ph_all("update_points: whole call");
-  plv::HostPhase ph_pool("update_points: pool + staging");
-  plv::RoctxRange rx_get("[Time-Cam] get features");
-  const double dt = st->cam_dt;
-  BoundingMemo start_of(*st);
-  const double t_oldest = st->clone_time[0], t_oldest2 = st->clone_time[1];  // no keyframes on this path
-  typedef PoolCand<Track> Cand;
+namespace {
+typedef PoolCand<Track> Cand;
+
+// One plv_camera_update_points call: what its stages share.  A stage returns GO_ON, or the status of a call it has ended (finish ran).
+enum { GO_ON = 1 };
+struct PointsUpdate {
+  plv_ctx *ctx;
+  Tracker *T;
+  const plv_state_view *st;
+  const plv_update_options *opt;
+  double *dx;
+  plv_update_result *res;
+  const double dt = st->cam_dt, t_oldest = st->clone_time[0], t_oldest2 = st->clone_time[1];  // no keyframes on this path
+  BoundingMemo start_of{*st};
   std::vector<Cand> pool;
   TrackMap<Track> unused;  // db_unused: goes back to the database at the end
-  T->last_slam.clear();
-  T->last_init.clear();
-  if (opt->n_slam > 0 && !opt->slam_ids) return PLV_E_BADARG;
-  auto is_slam = [&](uint64_t id) {
-    for (int i = 0; i < opt->n_slam; ++i)
-      if (opt->slam_ids[i] == id) return true;
-    return false;
-  };
-  {
-    // REF CamHelper.cpp:621-628 — landmarks of the state with a live track.  get_feature(id) is called without
-    // `remove`, so the Feature object stays in the database (and may enter the pool below as well);
-    // remove_unusable_measurements then edits that shared object: too-new observations are parked in db_unused,
-    // too-old ones are dropped, a landmark may keep a single observation (:766-769).
-    std::lock_guard<std::mutex> lk(T->mtx);
-    for (int i = 0; i < opt->n_slam; ++i) {
-      auto it = T->db.find(opt->slam_ids[i]);
-      if (it == T->db.end()) continue;
-      Track &tr = it->second;
-      const size_t keep = trim_to_window(unused, it->first, tr, dt, opt->state_time + st->dt_exp, t_oldest - st->dt_exp);
-      if (keep == 0) continue;
-      // slam_update's own get_imu_poses (UpdaterCamera.cpp:303-304) leaves out what has no bounding clones
-      Tracker::Listed e{it->first, Track{}, {0, 0, 0}};
-      for (size_t q = 0; q < keep; ++q)
-        if (start_of(tr.t[q] + dt) >= 0) append_obs(e.tr, tr, q);
-      if (!e.tr.t.empty()) T->last_slam.push_back(std::move(e));
-    }
-  }
-  res->n_slam = (int)T->last_slam.size();
-  {
-    std::lock_guard<std::mutex> lk(T->mtx);
-    // REF CamHelper.cpp:631-637 — features_containing_older(oldest_2nd_clone_time), then
-    // features_not_containing_newer(t_hist[size-2]); both take the feature out of the database
-    take_pool(T->db, t_oldest2 - dt, opt->t_prev_frame - dt, pool);
-  }
-  res->n_pool = (int)pool.size();
-  // REF :740-775 remove_unusable_measurements, and get_imu_poses' bounding-pose test (:327-372)
-  size_t kept_cands = 0;  // (candidates that stay are moved down once: erasing from the middle shifted the rest every time)
-  for (size_t ci = 0; ci < pool.size(); ++ci) {
-    Cand &c = pool[ci];
-    const size_t keep = trim_to_window(unused, c.id, c.tr, dt, opt->state_time + st->dt_exp, t_oldest - st->dt_exp);
-    if (keep == 1 && is_slam(c.id)) give_back(unused, c.id, c.tr, 0);  // REF :766-769 kept, then handed back by the n_meas < 2 test (:656-661)
-    if (keep < 2) continue;  // REF :766-771 a single measurement is dropped
-    if (kept_cands != ci) pool[kept_cands] = std::move(c);
-    ++kept_cands;
-  }
-  pool.resize(kept_cands);
-  sort_long_first(pool);  // REF :640
-  auto finish = [&](int rc) {
+  CpiPoses cpi;
+  std::vector<int> ptr, valid_n, cols;
+  std::vector<double> ot, pf, err;
+  std::vector<float> ouv, ouvn;
+  std::vector<uint8_t> ok, acc_all;
+  plv_tracks all{};
+  int most_valid = 0, n_rows = 0;
+  // the route taken: spec_done — the speculative batch's update is the frame's (its n_rows / status: s_rows / s_status); fused_ran —
+  // triangulation, gate and update came from one submission (that batch, or the fused call); neither: the two-step route
+  bool spec_done = false, fused_ran = false;
+  int s_rows = 0, s_status = PLV_OK;
+
+  int finish(int rc) {
     res->n_returned = (int)unused.size();
     const bool window_full = opt->window_full != 0;
-    auto hand_back = [ctx, T, window_full, t_oldest](TrackMap<Track> &un) {
+    auto hand_back = [ctx = ctx, T = T, window_full, t_oldest = t_oldest](TrackMap<Track> &un) {
       {
         std::lock_guard<std::mutex> lk(T->mtx);
         for (auto &kv : un) put_track(T->db, kv.first, kv.second);  // REF :702-703 / :727-729 append_new_measurements
@@ -719,18 +686,69 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
       hand_back(unused);
     }
     return rc;
-  };
+  }
+  // nothing more to update with: dx is zero unless an update ran
+  int finish_early(bool updated) {
+    if (!updated) std::fill(dx, dx + ctx->cov_n, 0.0);
+    return finish(PLV_OK);
+  }
+  // a failing exit: the whole pool returns to the database
+  int abandon(int rc) {
+    for (Cand &c : pool) give_back_all(unused, c);
+    return finish(rc);
+  }
+
+  // REF CamHelper.cpp:621-628 — landmarks of the state with a live track.  get_feature(id) is called without `remove`, so the
+  // Feature object stays in the database (and may enter the pool below as well); remove_unusable_measurements then edits that
+  // shared object: too-new observations are parked in db_unused, too-old ones are dropped, a landmark may keep a single
+  // observation (:766-769).
+  void slam_landmarks() {
+    std::lock_guard<std::mutex> lk(T->mtx);
+    for (int i = 0; i < opt->n_slam; ++i) {
+      auto it = T->db.find(opt->slam_ids[i]);
+      if (it == T->db.end()) continue;
+      Track &tr = it->second;
+      const size_t keep = trim_to_window(unused, it->first, tr, dt, opt->state_time + st->dt_exp, t_oldest - st->dt_exp);
+      if (keep == 0) continue;
+      // slam_update's own get_imu_poses (UpdaterCamera.cpp:303-304) leaves out what has no bounding clones
+      Tracker::Listed e{it->first, Track{}, {0, 0, 0}};
+      for (size_t q = 0; q < keep; ++q)
+        if (start_of(tr.t[q] + dt) >= 0) append_obs(e.tr, tr, q);
+      if (!e.tr.t.empty()) T->last_slam.push_back(std::move(e));
+    }
+  }
+
+  bool is_slam(uint64_t id) const { return std::find(opt->slam_ids, opt->slam_ids + opt->n_slam, id) != opt->slam_ids + opt->n_slam; }
+
+  // the pool of the window: taken out of the database, trimmed to the window, long tracks first
+  void take_pool_of_window() {
+    {
+      std::lock_guard<std::mutex> lk(T->mtx);
+      // REF CamHelper.cpp:631-637 — features_containing_older(oldest_2nd_clone_time), then
+      // features_not_containing_newer(t_hist[size-2]); both take the feature out of the database
+      take_pool(T->db, t_oldest2 - dt, opt->t_prev_frame - dt, pool);
+    }
+    res->n_pool = (int)pool.size();
+    // REF :740-775 remove_unusable_measurements, and get_imu_poses' bounding-pose test (:327-372)
+    size_t kept_cands = 0;  // (candidates that stay are moved down once: erasing from the middle shifted the rest every time)
+    for (size_t ci = 0; ci < pool.size(); ++ci) {
+      Cand &c = pool[ci];
+      const size_t keep = trim_to_window(unused, c.id, c.tr, dt, opt->state_time + st->dt_exp, t_oldest - st->dt_exp);
+      if (keep == 1 && is_slam(c.id)) give_back(unused, c.id, c.tr, 0);  // REF :766-769 kept, then handed back by the n_meas < 2 test (:656-661)
+      if (keep < 2) continue;  // REF :766-771 a single measurement is dropped
+      if (kept_cands != ci) pool[kept_cands] = std::move(c);
+      ++kept_cands;
+    }
+    pool.resize(kept_cands);
+    sort_long_first(pool);  // REF :640
+  }
+
   // ---- this frame's update may be on the stream already (Tracker::Spec: enqueued behind the flow by the feed, its pool decided on the
-  // device).  The pool above is the same one — formed from the database as always — and says which candidates' results to read.
-  Tracker::Spec &S = T->spec;
-  bool spec_done = false;
-  std::vector<double> s_pf, s_err;
-  std::vector<uint8_t> s_ok, s_acc;
-  int s_rows = 0, s_status = PLV_OK;
-  if (S.active) {
+  // device).  The pool is the same one — formed from the database as always — and says which candidates' results to read.  Three
+  // outcomes: the batch's update is used (spec_done), the update is run again the long way (GO_ON without spec_done), the call failed.
+  int collect_speculative() {
+    Tracker::Spec &S = T->spec;
     S.active = false;
-    ph_pool.stop();
-    rx_get.stop();
     const int Fp0 = (int)pool.size();
     const bool same = S.t_prev_frame == opt->t_prev_frame && S.state_time == opt->state_time && S.dt == dt && S.n_clones == st->n_clones &&
                       S.t_oldest == t_oldest && S.t_oldest2 == t_oldest2 && S.max_msckf == opt->max_msckf && S.max_obs == opt->max_obs && !opt->cpi &&
@@ -747,11 +765,8 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
     //  the results — then the chained launch has seen the status and ended without touching anything, like behind a rejected update)
     T->chain_ok = same && known && Fp0 <= plv::spec_grid(opt->max_msckf);
     if (T->chain_ok && T->early_lines)
-      for (int f = 0; f < Fp0; ++f) {
-        int v = 0;
-        for (double t : pool[f].tr.t) v += start_of(t + dt) >= 0;
-        if (v >= 2) T->chain_index.emplace(pool[f].id, cand_of[f]);  // (the chained line launch reads the candidates' triangulation results)
-      }
+      for (int f = 0; f < Fp0; ++f)
+        if (usable_views(pool[f].tr, dt, start_of) >= 2) T->chain_index.emplace(pool[f].id, cand_of[f]);  // (the chained line launch reads the candidates' triangulation results)
     std::vector<double> cp(3 * (size_t)S.F), ce(S.F);
     std::vector<uint8_t> cok(S.F), cacc(S.F), cmem(S.F);
     int count = 0, over = 0, nrows = 0;
@@ -765,156 +780,116 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
     // (an exit that does not use the batch's update: the covariance goes back to what the batch found, plv_points_spec_undo)
     auto fail = [&](const char *why) {
       plv::set_last_error("speculative point update: %s (host pool %d, device pool %d%s)", why, Fp0, count, over ? ", over the cap" : "");
-      for (Cand &c : pool) give_back_all(unused, c);
       const int rc_u = plv_points_spec_undo(ctx);
-      return finish(rc_u != PLV_OK ? rc_u : PLV_E_DEVICE);
+      return abandon(rc_u != PLV_OK ? rc_u : PLV_E_DEVICE);
     };
     if (!same) return fail("the batch was staged for another update than the one asked for");
     if (over || Fp0 > plv::spec_grid(opt->max_msckf)) {
       // over == 1: the pool exceeds the launch — the device left every candidate empty and updated nothing; over == 2: the pool exceeds
       // max_msckf and max_msckf of its candidates passed their tests — the selection loop would have stopped inside the pool
-      // (REF CamHelper.cpp:651-653), the device committed nothing (ekf_commit_kernel).  The long way below.
+      // (REF CamHelper.cpp:651-653), the device committed nothing (ekf_commit_kernel).  The long way follows.
       if (!(over && Fp0 > opt->max_msckf && count == Fp0 && (over == 1) == (Fp0 > plv::spec_grid(opt->max_msckf))))
-        return fail("host and device disagree on the pool's size");
+        return fail("host and device disagree on the pool's size");  // (the device may have committed by now)
       if (plv::host_phases().on) plv::host_phases().add(over == 1 ? "speculative point update: pool larger than the launch, run again the long way (count)" : "speculative point update: pool cut by the selection cap, run again the long way (count)", 1.0);
       if (plv_camera_lines_job_pending(ctx)) plv_camera_lines_job_abort2(ctx, 1);  // (a chained line launch saw the status and did nothing; its pool stays formed)
       ++plv::counters().spec_over[over == 1 ? 2 : 1];
-    } else {
-      if (rc_s != PLV_OK && rc_s != PLV_E_NOT_PSD) {
-        for (Cand &c : pool) give_back_all(unused, c);
-        (void)plv_points_spec_undo(ctx);
-        return finish(rc_s);
-      }
-      if (!known || count != Fp0) return fail("host and device disagree on the pool");
-      for (int f = 0; f < Fp0; ++f)
-        if (!cmem[cand_of[f]]) return fail("a track of the host's pool is not in the device's");
-      s_pf.resize(3 * (size_t)Fp0), s_err.resize(Fp0), s_ok.resize(Fp0), s_acc.resize(Fp0);
-      for (int f = 0; f < Fp0; ++f) {
-        const int c = cand_of[f];
-        std::copy(cp.begin() + 3 * (size_t)c, cp.begin() + 3 * (size_t)c + 3, s_pf.begin() + 3 * (size_t)f);
-        s_err[f] = ce[c], s_ok[f] = cok[c], s_acc[f] = cacc[c];
-      }
-      s_rows = nrows;
-      s_status = rc_s == PLV_E_NOT_PSD ? rc_s : PLV_OK;
-      if (rc_s == PLV_E_NOT_PSD) std::fill(dx, dx + ctx->cov_n, 0.0);  // EKFUpdate returned false: nothing changed
-      spec_done = true;
-      plv_update_state(ctx)->spec_save_seq = 0;  // (the batch's update is used: nothing to undo)
-      ++plv::counters().speculated;
-      if (Fp0 > opt->max_msckf) ++plv::counters().spec_over[0];
+      return GO_ON;
     }
-  }
-  if (pool.empty()) {
-    if (!spec_done) std::fill(dx, dx + ctx->cov_n, 0.0);
-    return finish(PLV_OK);
-  }
-  // ---- triangulate the whole pool in one call (the reference goes feature by feature until the cap; a
-  //      feature it never reaches keeps its observations either way)
-  const int Fp = (int)pool.size();
-  // ---- use_imu_res: poses from the CPI table; what it cannot serve leaves the track here (get_imu_poses, :356-365)
-  CpiPoses cpi;
-  const bool imu_cov = opt->cpi && opt->cpi->Q && st->use_imu_cov && !st->use_pol_cov;  // REF CamHelper.cpp:214-224
-  if (opt->cpi) {
-    const int rc0 = cpi_attach(ctx, st, opt->cpi, imu_cov, dt, pool, unused, cpi);
-    if (rc0 != PLV_OK) {
-      for (Cand &c : pool) give_back_all(unused, c);
-      return finish(rc0);
+    if (rc_s != PLV_OK && rc_s != PLV_E_NOT_PSD) {
+      (void)plv_points_spec_undo(ctx);
+      return abandon(rc_s);
     }
+    if (!known || count != Fp0) return fail("host and device disagree on the pool");  // (the device has committed by now)
+    for (int f = 0; f < Fp0; ++f)
+      if (!cmem[cand_of[f]]) return fail("a track of the host's pool is not in the device's");
+    pf.resize(3 * (size_t)Fp0), err.resize(Fp0), ok.resize(Fp0), acc_all.resize(Fp0);
+    for (int f = 0; f < Fp0; ++f) {  // the update ran behind the flow: its results, candidate by candidate
+      const int c = cand_of[f];
+      std::copy(cp.begin() + 3 * (size_t)c, cp.begin() + 3 * (size_t)c + 3, pf.begin() + 3 * (size_t)f);
+      err[f] = ce[c], ok[f] = cok[c], acc_all[f] = cacc[c];
+    }
+    s_rows = nrows;
+    (void)ekf_returned_false(rc_s, &s_status, dx, ctx->cov_n);
+    spec_done = true;
+    plv_update_state(ctx)->spec_save_seq = 0;  // (the batch's update is used: nothing to undo)
+    ++plv::counters().speculated;
+    if (Fp0 > opt->max_msckf) ++plv::counters().spec_over[0];
+    return GO_ON;
   }
-  std::vector<int> ptr, valid_n(Fp, 0);
-  std::vector<double> ot;
-  std::vector<float> ouv, ouvn;
-  flatten_pool(pool, ptr, ot, ouv, ouvn);
-  int most_valid = 0;
-  for (int f = 0; f < Fp; ++f) {
-    // get_imu_poses (:327-372): observations without bounding clones do not count (and go back to the database below)
-    for (double t : pool[f].tr.t) valid_n[f] += start_of(t + dt) >= 0;
-    most_valid = std::max(most_valid, valid_n[f]);
+
+  // ---- the whole pool as one batch (the reference goes feature by feature until the cap; a feature it never reaches keeps its
+  // observations either way): CPI poses, the flattened arrays, the usable views of every candidate
+  int stage_pool() {
+    if (pool.empty()) return finish_early(spec_done);
+    // ---- use_imu_res: poses from the CPI table; what it cannot serve leaves the track here (get_imu_poses, :356-365)
+    const bool imu_cov = opt->cpi && opt->cpi->Q && st->use_imu_cov && !st->use_pol_cov;  // REF CamHelper.cpp:214-224
+    if (opt->cpi) {
+      const int rc0 = cpi_attach(ctx, st, opt->cpi, imu_cov, dt, pool, unused, cpi);
+      if (rc0 != PLV_OK) return abandon(rc0);
+    }
+    const size_t Fp = pool.size();
+    flatten_pool(pool, ptr, ot, ouv, ouvn);
+    // get_imu_poses (:327-372): observations without bounding clones do not count (and go back to the database in the batch tail)
+    most_valid = count_usable(pool, dt, start_of, valid_n);
+    if (ptr[Fp] == 0) return finish_early(spec_done);
+    pf.resize(3 * Fp), err.resize(Fp), ok.resize(Fp), acc_all.resize(Fp, 0);  // (a used speculative batch has filled them)
+    all.n_feat = (int)Fp, all.obs_ptr = ptr.data(), all.obs_time = ot.data(), all.obs_uv = ouv.data(), all.obs_uvn = ouvn.data();
+    if (cpi.on) all.res_R = cpi.R.data(), all.res_p = cpi.p.data();
+    cols.resize(ctx->cfg.max_state_dim > 0 ? ctx->cfg.max_state_dim : 1024);
+    return GO_ON;
   }
-  const int nobs = ptr[Fp];
-  if (nobs == 0) {
-    if (!spec_done) std::fill(dx, dx + ctx->cov_n, 0.0);
-    return finish(PLV_OK);
-  }
-  std::vector<double> pf(3 * (size_t)Fp), err(Fp);
-  std::vector<uint8_t> ok(Fp);
-  plv_tracks all{};
-  all.n_feat = Fp;
-  all.obs_ptr = ptr.data();
-  all.obs_time = ot.data();
-  all.obs_uv = ouv.data();
-  all.obs_uvn = ouvn.data();
-  if (cpi.on) {
-    all.res_R = cpi.R.data();
-    all.res_p = cpi.p.data();
-  }
-  std::vector<int> cols(ctx->cfg.max_state_dim > 0 ? ctx->cfg.max_state_dim : 1024);
-  int k = 0, n_rows = 0, rc = PLV_OK;
-  // ---- one submission (the default): every pool candidate is triangulated, the selection loop below runs on the device too
+
+  // ---- one submission (the default): every pool candidate is triangulated, the selection loop runs on the device too
   // (jacobian_nullspace_kernel: candidate_selected), Jacobians / gate / compression / EKFUpdate follow on the stream, and the host
   // reads triangulation results, gate decisions and dx after ONE synchronisation.  The batch then holds all candidates (the ones
   // the loop does not take are empty systems) and its column set is the union over all of them: a permutation / zero columns of the
   // reference's, which changes neither dx nor P beyond rounding.  Poses from the CPI table, in-state landmarks and tracks longer
   // than the batch rows take the two-step route (triangulate, select on the host, then build + update).
-  const bool fused = !opt->cpi && opt->max_slam == 0 && most_valid <= opt->max_obs;
-  ph_pool.stop();
-  rx_get.stop();
-  plv::frame_mark("@ update_points: pool + staging done");
-  plv::RoctxRange rx_upd("[Time-Cam] MSCKF update");
-  plv::HostPhase ph_dev("update_points: device submission + wait");
-  std::vector<uint8_t> acc_all(Fp, 0);
-  bool fused_ran = false;
-  if (fused && spec_done) {  // the update ran behind the flow: its results, candidate by candidate
-    std::copy(s_pf.begin(), s_pf.end(), pf.begin());
-    std::copy(s_err.begin(), s_err.end(), err.begin());
-    std::copy(s_ok.begin(), s_ok.end(), ok.begin());
-    std::copy(s_acc.begin(), s_acc.end(), acc_all.begin());
-    n_rows = s_rows;
-    res->status = s_status;
-    fused_ran = true;
-  } else if (fused) {
+  bool fused_route() const { return !opt->cpi && opt->max_slam == 0 && most_valid <= opt->max_obs; }
+
+  // triangulation and gate results of the pool, by route: the speculative batch's, the fused call's, or (two-step) the triangulation alone
+  int triangulate_and_gate() {
+    const int Fp = (int)pool.size();
+    if (fused_route() && spec_done) {
+      n_rows = s_rows;
+      res->status = s_status;
+      fused_ran = true;
+      return GO_ON;
+    }
+    if (!fused_route()) {
+      start_detection_ahead(ctx);
+      const int rc_t = plv_triangulate(ctx, st, &all, &opt->tri, pf.data(), ok.data(), err.data());
+      return rc_t == PLV_OK ? GO_ON : abandon(rc_t);
+    }
     std::vector<uint8_t> flags(Fp);
     bool any = false;
     for (int f = 0; f < Fp; ++f) any = (flags[f] = valid_n[f] >= 2) || any;
-    if (any) {
-      all.p_FinG = all.p_FinG_fej = pf.data();
-      rc = plv_jacobian_columns(st, &all, cols.data(), (int)cols.size(), &k);
-      if (rc == PLV_OK && k > 0) {
-        ctx->gate_rows_hint = 2 * most_valid;
-        T->chain_index.clear();
-        T->chain_ok = Fp <= opt->max_msckf;  // (the selection loop cannot reach its cap: a candidate is taken on its own verdict)
-        if (T->chain_ok && T->early_lines)
-          for (int f = 0; f < Fp; ++f)
-            if (flags[f]) T->chain_index.emplace(pool[f].id, f);
-        plv::frame_mark("@ update_points: columns done, fused call");
-        rc = plv_points_update_fused(ctx, st, &all, &opt->tri, flags.data(), opt->max_msckf, k, cols.data(), 2 * opt->max_obs,
+    if (!any) return GO_ON;
+    int k = 0;
+    all.p_FinG = all.p_FinG_fej = pf.data();
+    int rc_f = plv_jacobian_columns(st, &all, cols.data(), (int)cols.size(), &k);
+    if (rc_f == PLV_OK && k > 0) {
+      ctx->gate_rows_hint = 2 * most_valid;
+      T->chain_index.clear();
+      T->chain_ok = Fp <= opt->max_msckf;  // (the selection loop cannot reach its cap: a candidate is taken on its own verdict)
+      if (T->chain_ok && T->early_lines)
+        for (int f = 0; f < Fp; ++f)
+          if (flags[f]) T->chain_index.emplace(pool[f].id, f);
+      plv::frame_mark("@ update_points: columns done, fused call");
+      rc_f = plv_points_update_fused(ctx, st, &all, &opt->tri, flags.data(), opt->max_msckf, k, cols.data(), 2 * opt->max_obs,
                                      st->sigma_pix * st->sigma_pix, opt->chi2_mult, 3.0, pf.data(), ok.data(), err.data(), acc_all.data(),
                                      &n_rows, dx, start_detection_ahead, ctx);
-        T->chain_ok = false;
-        res->status = rc == PLV_E_NOT_PSD ? rc : PLV_OK;
-        if (rc == PLV_E_NOT_PSD) {
-          rc = PLV_OK;  // EKFUpdate returned false: nothing changed, the call itself succeeded
-          std::fill(dx, dx + ctx->cov_n, 0.0);
-        }
-        fused_ran = rc == PLV_OK;
-      }
-      if (rc != PLV_OK) {
-        for (Cand &c : pool) give_back_all(unused, c);
-        return finish(rc);
-      }
+      T->chain_ok = false;
+      rc_f = ekf_returned_false(rc_f, &res->status, dx, ctx->cov_n);
+      fused_ran = rc_f == PLV_OK;
     }
-  } else {
-    start_detection_ahead(ctx);
-    rc = plv_triangulate(ctx, st, &all, &opt->tri, pf.data(), ok.data(), err.data());
-    if (rc != PLV_OK) {
-      for (Cand &c : pool) give_back_all(unused, c);
-      return finish(rc);
-    }
+    return rc_f == PLV_OK ? GO_ON : abandon(rc_f);
   }
-  ph_dev.stop();
-  rx_upd.stop();
-  if (ctx->decision_trace) {
-    // the values behind the verdicts, for the comparison of two runs decision by decision (tests/decision_trace.py): what the host
-    // already holds, and what the kernels left on the device (NaN: a test that was not reached, or a route that does not report)
+
+  // the values behind the verdicts, for the comparison of two runs decision by decision (tests/decision_trace.py): what the host
+  // already holds, and what the kernels left on the device (NaN: a test that was not reached, or a route that does not report)
+  int record_decisions() {
+    const int Fp = (int)pool.size();
     const double nan = std::numeric_limits<double>::quiet_NaN();
     T->dec_ids.resize(Fp);
     T->dec_vals.assign((size_t)Fp * PLV_DECISION_VALUES, nan);
@@ -931,119 +906,95 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
       for (int i = 0; i < 4; ++i) v[4 + i] = tri[4 * (size_t)f + i];
       for (int i = 0; i < 3; ++i) v[8 + i] = gate[3 * (size_t)f + i];
     }
+    return PLV_OK;
   }
-  plv::RoctxRange rx_db("[Time-Cam] DB clan up");  // (sic, UpdaterCamera.cpp:174)
-  plv::HostPhase ph_post("update_points: selection + database");
+
   // ---- REF :648-699 the selection loop
-  std::vector<int> sel;
-  std::vector<int> n_skip(Fp, 0);  // usable observations a truncated track leaves out (its oldest)
-  for (int f = 0; f < Fp; ++f) {
-    Cand &c = pool[f];
-    if ((int)sel.size() >= opt->max_msckf) {  // :651-653 break; the rest returns to the database (:702)
-      give_back_all(unused, c);
-      continue;
-    }
-    const int valid = valid_n[f];
-    if (valid >= 2 && ok[f]) {  // copy_to_db(db_used, feat): dynamic (:677) and MSCKF (:697) features, Triangulated = true
-      std::lock_guard<std::mutex> lk(T->mtx);
-      Tracker::UsedPoint &u = T->used[c.id];
-      std::copy(pf.begin() + 3 * (size_t)f, pf.begin() + 3 * (size_t)f + 3, u.p);
-      u.newest = c.tr.t.back();
-    }
-    if (valid < 2 || !ok[f] || !(err[f] < 3.0)) {  // :656-683
-      give_back_all(unused, c);
-      continue;
-    }
-    // :685-693 a long track becomes a new in-state landmark while there is room
-    if (valid >= opt->init_min_meas && opt->n_slam + (int)T->last_init.size() < opt->max_slam) {
-      Tracker::Listed e{c.id, Track{}, {pf[3 * (size_t)f], pf[3 * (size_t)f + 1], pf[3 * (size_t)f + 2]}};
-      for (size_t i = 0; i < c.tr.t.size(); ++i) {
-        if (start_of(c.tr.t[i] + dt) < 0)
-          give_back(unused, c.id, c.tr, i);
-        else
-          append_obs(e.tr, c.tr, i);
-      }
-      T->last_init.push_back(std::move(e));
-      continue;
-    }
-    // batch capacity of the MSCKF update (the reference has none): the newest max_obs observations are used, the older ones are
-    // consumed with the feature; counted in res->n_truncated
-    if (valid > opt->max_obs) {
-      n_skip[f] = valid - opt->max_obs;  // the first (oldest) usable observations are left out
-      ++res->n_truncated;
-    }
-    sel.push_back(f);
-  }
-  res->n_msckf = (int)sel.size();
-  res->n_init = (int)T->last_init.size();
-  if (plv::host_phases().on && Fp > opt->max_msckf) fprintf(stderr, "[plv over] pool %d selected %d\n", Fp, (int)sel.size());
-  if (sel.empty()) {
-    if (!fused_ran) std::fill(dx, dx + ctx->cov_n, 0.0);
-    return finish(PLV_OK);
-  }
-  // ---- UpdaterCamera::msckf_update on the selected features
-  const int F = (int)sel.size();
-  std::vector<int> sptr(F + 1, 0);
-  std::vector<double> sp(3 * (size_t)F);
-  ObsGather g;
-  for (int q = 0; q < F; ++q) {
-    const Cand &c = pool[sel[q]];
-    int seen = 0;
-    for (size_t i = 0; i < c.tr.t.size(); ++i) {
-      if (start_of(c.tr.t[i] + dt) < 0) {
-        give_back(unused, c.id, c.tr, i);
+  void select(Selection<Track> &S) {
+    const int Fp = (int)pool.size();
+    for (int f = 0; f < Fp; ++f) {
+      Cand &c = pool[f];
+      if ((int)S.sel.size() >= opt->max_msckf) {  // :651-653 break; the rest returns to the database (:702)
+        give_back_all(unused, c);
         continue;
       }
-      if (seen++ < n_skip[sel[q]]) continue;
-      gather_obs(g, c.tr, i, cpi, ptr[sel[q]] + i);
-    }
-    sptr[q + 1] = (int)g.t.size();
-    std::copy(pf.begin() + 3 * (size_t)sel[q], pf.begin() + 3 * (size_t)sel[q] + 3, sp.begin() + 3 * (size_t)q);
-    if (msckf_ids) msckf_ids[q] = c.id;
-  }
-  if (p_out) std::copy(sp.begin(), sp.end(), p_out);
-  std::vector<uint8_t> acc(F, 0);
-  if (fused_ran) {
-    for (int q = 0; q < F; ++q) acc[q] = acc_all[sel[q]];
-  } else {
-    plv_tracks tr{};
-    tr.n_feat = F;
-    tr.obs_ptr = sptr.data();
-    tr.obs_time = g.t.data();
-    tr.obs_uv = g.uv.data();
-    tr.p_FinG = sp.data();
-    tr.p_FinG_fej = sp.data();  // MSCKF features: FEJ value = estimate (REF CamHelper.cpp:556-557)
-    if (cpi.on) {
-      tr.res_R = g.R.data();
-      tr.res_p = g.p.data();
-      if (cpi.noise) {
-        tr.res_Q = g.Q.data();
-        tr.res_clone = g.C.data();
+      const int valid = valid_n[f];
+      if (valid >= 2 && ok[f]) {  // copy_to_db(db_used, feat): dynamic (:677) and MSCKF (:697) features, Triangulated = true
+        std::lock_guard<std::mutex> lk(T->mtx);
+        Tracker::UsedPoint &u = T->used[c.id];
+        std::copy(pf.begin() + 3 * (size_t)f, pf.begin() + 3 * (size_t)f + 3, u.p);
+        u.newest = c.tr.t.back();
       }
+      if (valid < 2 || !ok[f] || !(err[f] < 3.0)) {  // :656-683
+        give_back_all(unused, c);
+        continue;
+      }
+      // :685-693 a long track becomes a new in-state landmark while there is room
+      if (valid >= opt->init_min_meas && opt->n_slam + (int)T->last_init.size() < opt->max_slam) {
+        Tracker::Listed e{c.id, Track{}, {pf[3 * (size_t)f], pf[3 * (size_t)f + 1], pf[3 * (size_t)f + 2]}};
+        for (size_t i = 0; i < c.tr.t.size(); ++i) {
+          if (start_of(c.tr.t[i] + dt) < 0)
+            give_back(unused, c.id, c.tr, i);
+          else
+            append_obs(e.tr, c.tr, i);
+        }
+        T->last_init.push_back(std::move(e));
+        continue;
+      }
+      S.take(f, valid, opt->max_obs, res->n_truncated);
     }
-    rc = plv_jacobian_columns(st, &tr, cols.data(), (int)cols.size(), &k);
-    if (rc == PLV_OK) rc = plv_build_jacobians_resident(ctx, st, &tr, k, cols.data(), 2 * opt->max_obs);
-    if (rc == PLV_OK) {
-      rc = plv_msckf_update_resident(ctx, st->sigma_pix * st->sigma_pix, opt->chi2_mult, 3.0, acc.data(), &n_rows, dx);
-      res->status = rc;
-      if (rc == PLV_E_NOT_PSD) rc = PLV_OK;  // EKFUpdate returned false: nothing changed, the call itself succeeded
-    }
-    if (rc != PLV_OK) {
-      for (int q = 0; q < F; ++q) give_back_all(unused, pool[sel[q]]);
-      return finish(rc);
-    }
+    res->n_msckf = (int)S.sel.size();
+    res->n_init = (int)T->last_init.size();
+    if (plv::host_phases().on && Fp > opt->max_msckf) fprintf(stderr, "[plv over] pool %d selected %d\n", Fp, (int)S.sel.size());
   }
-  res->n_rows = n_rows;
-  for (int q = 0; q < F; ++q) {
-    res->n_accepted += acc[q];
-    if (accepted_out) accepted_out[q] = acc[q];
-    if (!acc[q]) {  // REF UpdaterCamera.cpp:266-268: only gate failures go back; what EKFUpdate then rejects is consumed all the same
-      const Cand &c = pool[sel[q]];
-      for (size_t i = 0; i < c.tr.t.size(); ++i)
-        if (start_of(c.tr.t[i] + dt) >= 0) give_back(unused, c.id, c.tr, i);
-    }
+};
+}  // namespace
+
+int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, double *dx,
+                             plv_update_result *res, uint64_t *msckf_ids, uint8_t *accepted_out, double *p_out) {
+  if (!ctx || !st || !opt || !dx || !res || st->n_clones < 2 || opt->max_msckf < 1 || opt->max_obs < 2) return PLV_E_BADARG;
+  Tracker *T = trk(ctx);
+  *res = plv_update_result{0, 0, 0, 0, 0, PLV_OK, 0, 0, 0};
+  plv::NsScope ns_points(plv::counters().points_ns);
+  plv::HostPhase ph_all("update_points: whole call");
+  plv::HostPhase ph_pool("update_points: pool + staging");
+  plv::RoctxRange rx_get("[Time-Cam] get features");
+  PointsUpdate U{ctx, T, st, opt, dx, res};
+  T->last_slam.clear();
+  T->last_init.clear();
+  if (opt->n_slam > 0 && !opt->slam_ids) return PLV_E_BADARG;
+  U.slam_landmarks();
+  res->n_slam = (int)T->last_slam.size();
+  U.take_pool_of_window();
+  int rc;
+  if (T->spec.active) {
+    ph_pool.stop();
+    rx_get.stop();
+    if ((rc = U.collect_speculative()) != GO_ON) return rc;
   }
-  return finish(PLV_OK);
+  if ((rc = U.stage_pool()) != GO_ON) return rc;
+  ph_pool.stop();
+  rx_get.stop();
+  plv::frame_mark("@ update_points: pool + staging done");
+  plv::RoctxRange rx_upd("[Time-Cam] MSCKF update");
+  plv::HostPhase ph_dev("update_points: device submission + wait");
+  if ((rc = U.triangulate_and_gate()) != GO_ON) return rc;
+  ph_dev.stop();
+  rx_upd.stop();
+  if (ctx->decision_trace) TRY(U.record_decisions());
+  plv::RoctxRange rx_db("[Time-Cam] DB clan up");  // (sic, UpdaterCamera.cpp:174)
+  plv::HostPhase ph_post("update_points: selection + database");
+  Selection<Track> S(U.pool.size());
+  U.select(S);
+  if (S.sel.empty()) return U.finish_early(U.fused_ran);
+  // ---- UpdaterCamera::msckf_update on the selected features
+  gather_selected(U.pool, U.valid_n, U.ptr, U.cpi, U.pf.data(), U.fused_ran, U.dt, U.start_of, U.unused, S, msckf_ids);
+  if (p_out) std::copy(S.feat.begin(), S.feat.end(), p_out);
+  rc = update_selected(ctx, st, opt, U.cpi, U.pool, U.unused, S, U.acc_all, U.fused_ran, U.cols, ctx->cov_n, &res->status, &U.n_rows, dx);
+  if (rc != PLV_OK) return U.finish(rc);
+  res->n_rows = U.n_rows;
+  res->n_accepted = return_rejected(U.pool, S, U.dt, U.start_of, U.unused, accepted_out, [](int) { return false; });
+  return U.finish(PLV_OK);
 }
 
 int plv_camera_update_list(plv_ctx *ctx, int which, int cap_feat, int cap_obs, int *n_feat, uint64_t *ids, int *obs_ptr,

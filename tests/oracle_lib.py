@@ -898,7 +898,7 @@ class FrameOracle:
         assert rc == 0, rc
         m = res.n_msckf
         return dict(dx=dx, n_pool=res.n_pool, n_lines=m, n_accepted=res.n_accepted, n_rows=res.n_rows, n_returned=res.n_returned, status=res.status,
-                    ids=ids[:m].copy(), accepted=acc[:m].copy(), line_FinG=lg[:m].copy())
+                    ids=ids[:m].copy(), accepted=acc[:m].copy(), line_FinG=lg[:m].copy(), n_truncated=res.n_truncated)
 
     def camera_frame(self, P, st, timestamp, img, mask=None, use_lines=False, update=None):
         """orc_frame_camera_frame with the structures of Context.camera_frame; update = the argument dict of Context._try_update_io"""

@@ -83,6 +83,24 @@ def test_stage_block_packer_under_sanitizers(tmp_path):
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
 
 
+def test_batch_tail_conserves_observations_under_sanitizers(tmp_path):
+    """pl-viwo_amd/csrc/camera_tracks.hpp, the device-free pieces of the point and line updates' batch tail (usable-view count, capacity
+    cut, gather of the selected tracks, return of what the gate rejected) under AddressSanitizer + UBSan: hand-made point and line
+    tracks, behind a fused launch and on the two-step route, accepted and rejected, truncated and not — every observation of every
+    pool track ends in exactly one of the batch, the skipped oldest views of a consumed track, and what returns to the database."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "camera_tracks_check")
+    src = os.path.join(ROOT, "tests", "host_sanitize", "camera_tracks_check.cpp")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+           "-I" + os.path.join(ROOT, "include"), src, "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"), timeout=120)
+    assert r.returncode == 0 and "ok: batch tail conserves the pool's observations" in r.stdout, (r.stdout[-3000:], r.stderr[-4000:])
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+
+
 def test_helper_threads_are_clamped_to_the_allowed_cpus(tmp_path):
     """the default number of polling helper threads of the line detector's host stage is min(7, allowed CPUs - 2),
     at most two below six CPUs, none below three — the caller's thread and the line worker keep a CPU each."""
