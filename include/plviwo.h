@@ -951,6 +951,65 @@ int plv_wheel_update(plv_ctx *ctx, const plv_wheel_options *opt, const plv_wheel
                      const double *m1, const double *m2, uint8_t *accepted, double *dx);
 
 /* ---------------------------------------------------------------------------------------------
+ * Zero-velocity updater.  The reference constructs a ZuptUpdater whenever camera and wheel are enabled (REF: PL-VIWO/src/core/
+ * SystemManager.cpp:50-52, 116-121) but its class and options are not part of the published snapshot; the measurement and the
+ * detector below are those of the upstream updater (open_vins UpdaterZeroVelocity).  While the vehicle stands, every IMU interval i
+ * (dt_i = t[i+1] - t[i], a = noise_mult) measures
+ *   gyro            r = -sqrt(dt_i / a) / sigma_w * (wm_i - bg)               H[bg] = -sqrt(dt_i / a) / sigma_w * I
+ *   accelerometer   r = -sqrt(dt_i / a) / sigma_a * (am_i - ba - R(q) g)      H[theta] = -sqrt(dt_i / a) / sigma_a * skew(R(q_fej) g),
+ *                                                                             H[ba] = -sqrt(dt_i / a) / sigma_a * I
+ * and three rows pin the velocity, r = -v / sigma_v, H[v] = I / sigma_v (propagation and cloning keep running through a stop, so
+ * velocity is a pseudo-measurement, not a frozen state).  R = I; JPL-left error state; the Jacobian on the first estimate.
+ * The device emits the exact 9 x 12 orthogonal compression of that stack (T = sum dt_i, w_bar / a_bar the dt-weighted means):
+ *   rows 0-2: c_w = sqrt(T / a) / sigma_w, H[bg] = -c_w I, r = -c_w (w_bar - bg)
+ *   rows 3-5: c_a = sqrt(T / a) / sigma_a, H[theta] = -c_a skew(R(q_fej) g), H[ba] = -c_a I, r = -c_a (a_bar - ba - R(q) g)
+ *   rows 6-8: the velocity rows
+ * which has the stack's H^T H and H^T r and the residual Q1^T r of an orthonormal basis Q1 of the range of H: dx, the posterior
+ * covariance and the chi-square are those of measurement_compress_inplace + Chi2Check + EKFUpdate on the full stack.
+ * Columns (k = 12): theta (imu_id + 0..2), v (imu_id + 6..8), bg (imu_id + 9..11), ba (imu_id + 12..14).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct plv_zupt_options {
+  double chi2_mult, max_velocity, noise_mult, max_disparity, sigma_v, max_wheel_speed;
+  int min_disparity_feats;
+} plv_zupt_options;
+
+typedef struct plv_zupt_result {
+  int stationary, imu_passed, disparity_passed, wheel_vetoed, updated;
+  double chi2, chi2_threshold, speed, disparity_mean, disparity_std;
+  int disparity_n;
+} plv_zupt_result;
+
+/* The compressed system from the device over n >= 2 ascending samples t / wm [n][3] / am [n][3] (as plv_select_imu_readings returns
+ * them): H (9 x 12 col-major), res (9), col_to_state (12).  PLV_E_BADARG for n < 2, sample times that do not increase, or a sigma_w,
+ * sigma_a, sigma_v or noise_mult that is not positive; PLV_E_NUMERIC when any output is not finite. */
+int plv_zupt_system(plv_ctx *ctx, const plv_zupt_options *opt, const plv_imu_state *imu, const plv_imu_noise *noise, int n,
+                    const double *t, const double *wm, const double *am, int imu_id, double *H, double *res, int *col_to_state);
+/* The system, the gate chi2 < chi2_mult * plv_chi2_quantile95(9) (skipped when `force`; *chi2 is reported either way) and
+ * StateHelper::EKFUpdate on the resident covariance.  *accepted = 0 when the gate fails.  A failed gate, PLV_E_NOT_PSD (as
+ * plv_ekf_update), PLV_E_NUMERIC and PLV_E_BADARG leave the covariance as it was and dx (cov_n) zero. */
+int plv_zupt_update(plv_ctx *ctx, const plv_zupt_options *opt, const plv_imu_state *imu, const plv_imu_noise *noise, int n,
+                    const double *t, const double *wm, const double *am, int imu_id, int force, double *chi2, uint8_t *accepted,
+                    double *dx);
+/* FeatureHelper::compute_disparity(db, time0, time1, ...) (REF: open_vins/ov_core/src/feat/FeatureHelper.h:60-108) on the point
+ * database: over the tracks observed at both stamps, the norm of the raw-pixel displacement (float differences), its mean and its
+ * standard deviation (n - 1 form) in double.  Fewer than two pairs give mean = std = -1 and n = 0: the evident intent of :90-94,
+ * where the reference sets these values but forgets to return and goes on to divide by the count.  Host logic. */
+int plv_db_disparity(plv_ctx *ctx, double time0, double time1, double *mean, double *std, int *n);
+/* The detector and the update, by the upstream rule:
+ *   wheel_vetoed     = wheel_speed_max >= 0 && wheel_speed_max > max_wheel_speed   (the caller passes the largest absolute rim speed
+ *                      over the window in m/s, or a negative value when it has no wheel data)
+ *   disparity_passed = n >= min_disparity_feats && mean < max_disparity            (plv_db_disparity(cam_time0, cam_time1))
+ *   imu_passed       = chi2 < chi2_mult * plv_chi2_quantile95(9) && |v| <= max_velocity
+ *   stationary       = !wheel_vetoed && (disparity_passed || imu_passed)
+ * When stationary the update is applied (whatever the gate says when only the disparity passed, as upstream does) and
+ * result->updated = 1; otherwise nothing changes.  Every field of the result is filled whatever the verdict: a vetoed frame still costs
+ * the upload, the kernel and the chi-square (a caller that only wants the verdict compares its rim speed first and leaves the call
+ * out).  Return codes and their guarantees as plv_zupt_update. */
+int plv_zupt_try_update(plv_ctx *ctx, const plv_zupt_options *opt, const plv_imu_state *imu, const plv_imu_noise *noise, int n,
+                        const double *t, const double *wm, const double *am, int imu_id, double cam_time0, double cam_time1,
+                        double wheel_speed_max, plv_zupt_result *result, double *dx);
+
+/* ---------------------------------------------------------------------------------------------
  * State initialisation (REF: PL-VIWO/src/init/Initializer.cpp:93-113 picks one of the two).
  * imustate [17] = time, q_GtoI (JPL x y z w), p_IinG, v_IinG, bias_g, bias_a, as Initializer::set_state takes it
  * (REF: Initializer.cpp:175-180; the initial covariance is cov_size * I_15 there).  Host logic, no device work.

@@ -168,6 +168,13 @@ def load_library():
         "plv_set_camera_model": (C.c_int, [vp, C.c_int]),
         "plv_set_lk_window": (C.c_int, [vp, C.c_int]),
         "plv_wheel_update": (C.c_int, [vp, C.POINTER(PlvWheelOptions), C.POINTER(PlvWheelState), C.c_int, dp, dp, dp, u8p, dp]),
+        "plv_zupt_system": (C.c_int, [vp, C.POINTER(PlvZuptOptions), C.POINTER(PlvImuState), C.POINTER(PlvImuNoise), C.c_int, dp, dp, dp,
+                                      C.c_int, dp, dp, ip]),
+        "plv_zupt_update": (C.c_int, [vp, C.POINTER(PlvZuptOptions), C.POINTER(PlvImuState), C.POINTER(PlvImuNoise), C.c_int, dp, dp, dp,
+                                      C.c_int, C.c_int, dp, u8p, dp]),
+        "plv_db_disparity": (C.c_int, [vp, C.c_double, C.c_double, dp, dp, ip]),
+        "plv_zupt_try_update": (C.c_int, [vp, C.POINTER(PlvZuptOptions), C.POINTER(PlvImuState), C.POINTER(PlvImuNoise), C.c_int, dp, dp, dp,
+                                          C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(PlvZuptResult), dp]),
         "plv_next_clone_time": (C.c_int, [C.POINTER(PlvCloneSchedule), dp, ip]),
         "plv_closest_clone_time": (C.c_int, [C.POINTER(PlvStateView), C.c_int, C.c_double, dp, ip]),
         "plv_traj_header": (C.c_int, [C.c_char_p, C.c_int]),
@@ -461,6 +468,26 @@ class PlvWheelState(C.Structure):
                 arr[i] = float(x)
         s.pose0_id, s.pose1_id, s.ext_id, s.dt_id, s.intr_id = pose0_id, pose1_id, ext_id, dt_id, intr_id
         return s
+
+
+class PlvZuptOptions(C.Structure):
+    _fields_ = [("chi2_mult", C.c_double), ("max_velocity", C.c_double), ("noise_mult", C.c_double), ("max_disparity", C.c_double),
+                ("sigma_v", C.c_double), ("max_wheel_speed", C.c_double), ("min_disparity_feats", C.c_int)]
+
+
+class PlvZuptResult(C.Structure):
+    _fields_ = [("stationary", C.c_int), ("imu_passed", C.c_int), ("disparity_passed", C.c_int), ("wheel_vetoed", C.c_int),
+                ("updated", C.c_int), ("chi2", C.c_double), ("chi2_threshold", C.c_double), ("speed", C.c_double),
+                ("disparity_mean", C.c_double), ("disparity_std", C.c_double), ("disparity_n", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def zupt_options(chi2_mult=1.0, max_velocity=1.0, noise_mult=1.0, max_disparity=1.0, sigma_v=0.05, max_wheel_speed=0.05,
+                 min_disparity_feats=20):
+    """plv_zupt_options with the defaults of options.py (est.zupt)"""
+    return PlvZuptOptions(chi2_mult, max_velocity, noise_mult, max_disparity, sigma_v, max_wheel_speed, min_disparity_feats)
 
 
 class PlvCloneSchedule(C.Structure):
@@ -1169,6 +1196,39 @@ class Context:
         rc = self.lib.plv_wheel_update(self.h, C.byref(opt), C.byref(st), len(t), _dp(t), _dp(m1), _dp(m2), _u8p(acc), _dp(dx))
         self._chk(rc, allow=(PLV_E_NOT_PSD,))
         return rc, int(acc[0]), dx
+
+    # ---- zero-velocity updater
+    def zupt_system(self, opt, imu, noise, t, wm, am, imu_id=0):
+        """plv_zupt_system: (H 9 x 12, res 9, col_to_state 12)"""
+        t, wm, am = _c64(t), _c64(wm), _c64(am)
+        H, res, cols = np.zeros(9 * 12), np.zeros(9), np.zeros(12, dtype=np.int32)
+        self._chk(self.lib.plv_zupt_system(self.h, C.byref(opt), C.byref(imu), C.byref(noise), len(t), _dp(t), _dp(wm), _dp(am), int(imu_id),
+                                           _dp(H), _dp(res), _ip(cols)))
+        return H.reshape(12, 9).T.copy(), res, cols
+
+    def zupt_update(self, opt, imu, noise, t, wm, am, n, imu_id=0, force=False):
+        """plv_zupt_update on the resident covariance of n states: (rc, chi2, accepted, dx); rc is PLV_OK or PLV_E_NOT_PSD"""
+        t, wm, am = _c64(t), _c64(wm), _c64(am)
+        acc, dx, chi2 = np.zeros(1, dtype=np.uint8), np.zeros(n), C.c_double()
+        rc = self.lib.plv_zupt_update(self.h, C.byref(opt), C.byref(imu), C.byref(noise), len(t), _dp(t), _dp(wm), _dp(am), int(imu_id),
+                                      1 if force else 0, C.byref(chi2), _u8p(acc), _dp(dx))
+        self._chk(rc, allow=(PLV_E_NOT_PSD,))
+        return rc, chi2.value, int(acc[0]), dx
+
+    def db_disparity(self, time0, time1):
+        """plv_db_disparity: (mean, std, n) of the raw-pixel displacement of the tracks seen at both stamps; (-1, -1, 0) below two"""
+        mean, std, n = C.c_double(), C.c_double(), C.c_int()
+        self._chk(self.lib.plv_db_disparity(self.h, float(time0), float(time1), C.byref(mean), C.byref(std), C.byref(n)))
+        return mean.value, std.value, n.value
+
+    def zupt_try_update(self, opt, imu, noise, t, wm, am, n, cam_time0, cam_time1, wheel_speed_max=-1.0, imu_id=0):
+        """plv_zupt_try_update: (rc, the plv_zupt_result as a dict, dx); rc is PLV_OK or PLV_E_NOT_PSD"""
+        t, wm, am = _c64(t), _c64(wm), _c64(am)
+        res, dx = PlvZuptResult(), np.zeros(n)
+        rc = self.lib.plv_zupt_try_update(self.h, C.byref(opt), C.byref(imu), C.byref(noise), len(t), _dp(t), _dp(wm), _dp(am), int(imu_id),
+                                          float(cam_time0), float(cam_time1), float(wheel_speed_max), C.byref(res), _dp(dx))
+        self._chk(rc, allow=(PLV_E_NOT_PSD,))
+        return rc, res.as_dict(), dx
 
     def cpi_integrate(self, noise, t_given, clone_t, R_clone, v_clone, bg, ba, t, wm, am):
         """State::create_new_cpi_integrate: (ok, PlvCpiRecord)."""

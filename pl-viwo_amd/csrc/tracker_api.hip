@@ -5,6 +5,7 @@
 // This is bookkeeping (vectors and a hash map), exactly what the reference keeps on the host;
 // every image / point computation goes through the device entry points of frontend_api.hip.
 #include <algorithm>
+#include <cmath>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -637,6 +638,37 @@ int plv_db_append_measurements(plv_ctx *ctx, uint64_t id, int n, const double *t
   tr.t.insert(tr.t.end(), t, t + n);
   tr.uv.insert(tr.uv.end(), uv, uv + 2 * (size_t)n);
   tr.uvn.insert(tr.uvn.end(), uvn, uvn + 2 * (size_t)n);
+  return PLV_OK;
+}
+
+// FeatureHelper::compute_disparity(db, time0, time1, ...)   REF: open_vins/ov_core/src/feat/FeatureHelper.h:60-108
+// Raw pixel coordinates, the difference and its norm in float, the statistics in double, std with n - 1.  The tracks are visited in
+// ascending id (the reference iterates an unordered_map), so the sums have a defined order.
+int plv_db_disparity(plv_ctx *ctx, double time0, double time1, double *mean, double *std, int *n) {
+  if (!ctx || !mean || !std || !n) return PLV_E_BADARG;
+  Tracker *T = trk(ctx);
+  std::lock_guard<std::mutex> lk(T->mtx);
+  std::vector<std::pair<uint64_t, double>> disp;
+  for (auto &kv : T->db) {
+    const Track &tr = kv.second;
+    const auto it0 = std::find(tr.t.begin(), tr.t.end(), time0), it1 = std::find(tr.t.begin(), tr.t.end(), time1);
+    if (it0 == tr.t.end() || it1 == tr.t.end()) continue;   // :77-78
+    const size_t i0 = it0 - tr.t.begin(), i1 = it1 - tr.t.begin();
+    const float du = tr.uv[2 * i1] - tr.uv[2 * i0], dv = tr.uv[2 * i1 + 1] - tr.uv[2 * i0 + 1];
+    disp.emplace_back(kv.first, (double)std::sqrt(du * du + dv * dv));
+  }
+  if (disp.size() < 2) {   // :90-94
+    *mean = -1.0, *std = -1.0, *n = 0;
+    return PLV_OK;
+  }
+  std::sort(disp.begin(), disp.end());
+  double m = 0.0, var = 0.0;
+  for (auto &d : disp) m += d.second;
+  m /= (double)disp.size();
+  for (auto &d : disp) var += (d.second - m) * (d.second - m);
+  *mean = m;
+  *std = std::sqrt(var / (double)(disp.size() - 1));
+  *n = (int)disp.size();
   return PLV_OK;
 }
 

@@ -231,6 +231,25 @@ def _load_wheel(p):
     return w
 
 
+def _load_zupt(p):
+    """The zero-velocity updater's options (the reference loads an OptionsZupt, OptionsEstimator.cpp:67,73,95, whose header is not
+    part of the snapshot): chi2_mult / max_velocity / noise_mult / max_disparity with upstream's defaults (open_vins
+    VioManagerOptions zupt_*), min_disparity_feats upstream's constant, sigma_v the deviation of the velocity pseudo-measurement,
+    max_wheel_speed the rim speed above which the wheels veto a standstill.  Off unless the master file names `config_zupt` and
+    that file exists; every key is optional."""
+    f = "config_zupt"
+    z = SimpleNamespace(enabled=False, chi2_mult=1.0, max_velocity=1.0, noise_mult=1.0, max_disparity=1.0, min_disparity_feats=20,
+                        sigma_v=0.05, max_wheel_speed=0.05)
+    rel = p.master.get(f)
+    if rel is None or not os.path.exists(os.path.join(p.folder, rel)):
+        return z
+    for key in ("enabled", "chi2_mult", "max_velocity", "noise_mult", "max_disparity", "min_disparity_feats", "sigma_v", "max_wheel_speed"):
+        setattr(z, key, p.get(f, "zupt", key, getattr(z, key), False))
+    if z.enabled and not (z.sigma_v > 0 and z.noise_mult > 0):
+        raise OptionsError("zupt.sigma_v and zupt.noise_mult must be positive")
+    return z
+
+
 class InterpolationError:
     """OptionsEstimator::interpolation_error (REF: OptionsEstimator.h:58-107): per clone rate and polynomial order, the slope of the
     pose-interpolation error against the estimated acceleration."""
@@ -289,6 +308,7 @@ def _load_estimator(p):
     if int(e.use_imu_cov) + int(e.use_pol_cov) > 1:   # :52-57
         raise OptionsError("More than 1 cov method enabled.")
     e.init, e.imu, e.cam, e.wheel = _load_init(p), _load_imu(p), _load_camera(p), _load_wheel(p)
+    e.zupt = _load_zupt(p)
     return e
 
 

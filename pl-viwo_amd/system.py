@@ -10,7 +10,8 @@ REF: PL-VIWO/src/core/SystemManager.cpp:55-135 (feed_measurement_imu / _camera /
 The camera path follows the intended flow feed_measurement -> try_update (as published, SystemManager.cpp:107-127 returns
 before try_update once the filter is initialised).  Scope of this driver: one camera (monocular), MSCKF points and lines
 (in-state SLAM landmarks in the GLOBAL_3D representation; the shipped configuration has cam.max_slam: 0), wheel optional; `use_imu_res` takes the poses of the camera update from the CPI records of plv_propagate; GPS / LiDAR / stereo /
-simulation are outside SURVEY §8.
+simulation are outside SURVEY §8.  With `est.zupt.enabled` a camera frame first asks the zero-velocity updater (REF: SystemManager.cpp:50-52,
+116-121; _zupt_try_update) and leaves its camera update out when that one applied.
 """
 import ctypes
 import os
@@ -20,7 +21,7 @@ import time as _time
 import numpy as np
 
 from . import BoxPlus, PlvStateView, jpl_left_update
-from . import (Context, CpiTable, IwInitializer, PlvError, PlvImuState, PlvWheelOptions, PlvWheelState, StateView, Tracks, WHEEL_TYPES, default_config,
+from . import (Context, CpiTable, IwInitializer, PlvError, PlvImuState, PlvWheelOptions, PlvWheelState, PlvZuptOptions, StateView, Tracks, WHEEL_TYPES, default_config,
                imu_noise, init_imu_static, next_clone_time, reset_cpi, select_imu_readings, select_wheel_data)
 from .options import OptionsError
 
@@ -461,10 +462,17 @@ class SystemManager:
         self.whl = SampleBuffer(3)   # t, m1, m2
         self.whl_last_updated = -1.0
         self.wheel_opt = None
+        self.last_zupt = None        # the plv_zupt_result of the last zero-velocity check
         if e.wheel.enabled:
             wl = e.wheel
             self.wheel_opt = PlvWheelOptions(WHEEL_TYPES[wl.type], wl.noise_w, wl.noise_v, wl.noise_p, int(wl.do_calib_ext), int(wl.do_calib_dt),
                                              int(wl.do_calib_int), wl.chi2_mult)
+        # ZuptUpdater (REF: SystemManager.cpp:50-52): off unless the configuration names a config_zupt file that enables it
+        z = e.zupt
+        self.zupt_opt = None
+        if z.enabled and e.cam.enabled:
+            self.zupt_opt = PlvZuptOptions(z.chi2_mult, z.max_velocity, z.noise_mult, z.max_disparity, z.sigma_v, z.max_wheel_speed,
+                                           int(z.min_disparity_feats))
         # Initializer (REF: Initializer.cpp:58-91)
         self.iw_init = None
         if not e.init.imu_only_init and e.wheel.enabled:
@@ -476,7 +484,7 @@ class SystemManager:
         self._lines_in_flight = False
         self.stats = dict(clones=0, cam_updates=0, cam_features=0, cam_accepted=0, line_updates=0, lines_accepted=0, wheel_updates=0, wheel_accepted=0,
                           not_psd=0, frames=0, line_pool=0, lines_triangulated=0, lines_tracked=0, slam_initialized=0, slam_updates=0,
-                          slam_marginalized=0)
+                          slam_marginalized=0, zupt_updates=0)
         self.distance = 0.0
 
     def close(self):
@@ -642,7 +650,7 @@ class SystemManager:
         if not e.cam.enabled:
             return None
         if not (self.one_call_update and self.one_call_frame and e.cam.max_slam == 0 and not e.use_imu_res and not e.cam.downsample and not st.slam
-                and hasattr(self.ctx, "camera_frame")):
+                and self.zupt_opt is None and hasattr(self.ctx, "camera_frame")):
             return None
         if not _bookkeeping_done:
             if st.initialized:
@@ -743,7 +751,8 @@ class SystemManager:
         self._marginalize_slam_features()
         self.stats["frames"] += 1
         if st.initialized:
-            self._camera_try_update()
+            if self.zupt_opt is None or not self._zupt_try_update(float(t)):
+                self._camera_try_update()
             self.tc.dong("CAM")
         self._join_lines()
 
@@ -752,6 +761,66 @@ class SystemManager:
             self.ctx.line_tracker_feed_wait()
             self.stats["lines_tracked"] += self.ctx.line_db_size()
             self._lines_in_flight = False
+
+    def _wheel_rim_speed(self, time0, time1):
+        """The largest absolute rim speed (m/s) the wheel buffer holds over (time0, time1], by what the wheel type measures; negative
+        when the wheels are off or the window has no wheel sample."""
+        if self.wheel_opt is None or not len(self.whl):
+            return -1.0
+        st = self.state
+        toff = float(st.wheel_dt.v[0])
+        w = self.whl.view()
+        a, b = np.searchsorted(w[:, 0], [time0 - toff, time1 - toff], side="right")
+        if b <= a:
+            return -1.0
+        m1, m2 = w[a:b, 1], w[a:b, 2]
+        rl, rr, base = (float(x) for x in st.wheel_intr.v)
+        kind = self.op.est.wheel.type
+        if kind.endswith("Ang"):      # wheel angular velocities
+            left, right = m1 * rl, m2 * rr
+        elif kind.endswith("Lin"):    # rim speeds
+            left, right = m1, m2
+        else:                         # yaw rate and forward speed of the axle's centre
+            left, right = m2 - m1 * base / 2, m2 + m1 * base / 2
+        return float(max(np.abs(left).max(), np.abs(right).max()))
+
+    def _zupt_try_update(self, t):
+        """The zero-velocity check of a camera frame (REF: SystemManager.cpp:116-121 "First check if current state is stationary"),
+        once both feeds of the frame are in: the IMU samples over (previous stamp + cam_dt, min(stamp + cam_dt, newest IMU stamp)],
+        the disparity of the tracks between the two frames and the rim speed over the same window go to plv_zupt_try_update.
+        True when a zero-velocity update was applied: the frame's camera update is then left out."""
+        st = self.state
+        self._join_lines()
+        if len(self.cam_t_hist) < 2 or len(self.imu) < 2:
+            return False
+        cam_dt = float(st.cam_dt.v[0])
+        t_prev = self.cam_t_hist[-2]
+        time0, time1 = t_prev + cam_dt, min(t + cam_dt, self.imu.t(-1))
+        if not time1 > time0:
+            return False
+        v = self.imu.view()
+        k = max(0, int(np.searchsorted(v[:, 0], time0, side="right")) - 2)   # only the tail that can matter
+        ok, ts, wm, am = select_imu_readings(np.ascontiguousarray(v[k:, 0]), np.ascontiguousarray(v[k:, 1:4]), np.ascontiguousarray(v[k:, 4:7]),
+                                             time0, time1)
+        if not ok or len(ts) < 2:
+            return False
+        rim = self._wheel_rim_speed(time0, time1)
+        if rim >= 0 and rim > self.zupt_opt.max_wheel_speed:
+            return False      # the wheels veto the frame (plv_zupt_try_update's own first test): a moving frame costs no device work
+        rc, res, dx = self.ctx.zupt_try_update(self.zupt_opt, st.imu, self.noise, ts, wm, am, st.n, t_prev, t, rim)
+        done = rc == 0 and bool(res["updated"])
+        if self.decisions is not None and (res["stationary"] or rc != 0):
+            self.decisions.append(("zupt", self.stats["frames"], st.time, 1, np.zeros(1, dtype=np.uint64), np.array([1 if done else 0], dtype=np.uint8),
+                                   int(rc), None, np.array(dx, dtype=float)))
+        self.last_zupt = res
+        if rc != 0:
+            self.stats["not_psd"] += 1
+            return False
+        if not done:
+            return False
+        st.apply(dx)
+        self.stats["zupt_updates"] += 1
+        return True
 
     def _marginalize_slam_features(self):   # UpdaterCamera.cpp:118-137 + StateHelper::marginalize_slam :203-213
         st = self.state

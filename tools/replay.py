@@ -56,7 +56,7 @@ def main():
         op.sys.save_trajectory, op.sys.path_trajectory = True, os.path.join(tempfile.mkdtemp(prefix="plv_out_"), "traj.txt")
     t0 = time.time()
     stats, times, poses = rp.replay(op, host_images=a.host_images, progress=lambda s, t: print(f"  t={t:8.3f}  clones {s.stats['clones']}  cam accepted "
-                                                                    f"{s.stats['cam_accepted']}/{s.stats['cam_features']}  wheel {s.stats['wheel_accepted']}", flush=True))
+                                                                    f"{s.stats['cam_accepted']}/{s.stats['cam_features']}  wheel {s.stats['wheel_accepted']}  zupt {s.stats['zupt_updates']}", flush=True))
     res = dict(config=a.config, wall_s=round(time.time() - t0, 2), stats=stats, poses_logged=len(times), trajectory=op.sys.path_trajectory)
     if a.gt and len(times) > 2:
         ctx = pkg.Context(pkg.default_config(752, 480))
