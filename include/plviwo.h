@@ -834,6 +834,63 @@ int plv_slam_initialize(plv_ctx *ctx, int rows, int k, int ld, const double *Hf,
 /* StateHelper::marginalize (REF: StateHelper.cpp:235-303): drop rows / columns [id, id + size). */
 int plv_cov_marginalize(plv_ctx *ctx, int id, int size);
 
+/* ---- The same two steps for a whole list in one call each, the systems device-resident (slam_pass.hip).  Called between
+ * plv_camera_update_points and plv_camera_update_lines in the two-call form; plv_camera_try_update / plv_camera_frame keep refusing
+ * max_slam > 0. */
+typedef struct plv_landmark {   /* ov_type::Landmark as the caller's state holds it */
+  uint64_t featid;              /* Landmark::_featid */
+  int id;                       /* covariance index of its three error states */
+  int rep;                      /* PLV_FEAT_GLOBAL_3D or PLV_FEAT_GLOBAL_FULL_INVERSE_DEPTH */
+  double value[3], fej[3];      /* in that representation: xyz, or (theta, phi, rho) */
+} plv_landmark;
+/* Landmark::set_from_xyz / get_xyz (REF: open_vins/ov_core/src/types/Landmark.cpp:65-101, 26-44) for the two representations the
+ * reference's options accept (OptionsCamera.cpp:55): rho = 1 / |p|, phi = acos(rho z), theta = atan2(y, x) and back
+ * p = (cos theta sin phi, sin theta sin phi, cos phi) / rho.  Host arithmetic; any other rep, or a null pointer: PLV_E_BADARG. */
+int plv_landmark_from_xyz(int rep, const double *p, double *out);
+int plv_landmark_xyz(int rep, const double *v, double *out);
+
+typedef struct plv_slam_result {
+  int n_list;     /* entries of the list the pass walked                                           */
+  int n_applied;  /* verdict 1: updated / initialised                                              */
+  int n_gate;     /* verdict 2: Chi2Check (update) or the tests of StateHelper::initialize failed  */
+  int n_not_psd;  /* verdict 3: EKFUpdate rejected (covariance and variables as before that entry) */
+  int n_skipped;  /* verdict 0                                                                     */
+  int n_returned; /* initialisation: failed candidates handed back to the tracker database         */
+  int cov_n;      /* dimension of the resident covariance after the pass                           */
+} plv_slam_result;
+
+/* UpdaterCamera::slam_update (REF: UpdaterCamera.cpp:296-338) for a whole list.  tracks == NULL: the list is PLV_LIST_SLAM of the last
+ * plv_camera_update_points and ids (capacity: that list's size) receives its feature ids; otherwise the caller's own CSR tracks
+ * (p_FinG / p_FinG_fej ignored, res_R / res_p taken when given) whose feature ids the caller hands in through ids [tracks->n_feat].
+ * In list order, per landmark: the observations with bounding clones — and, with opt->cpi, a pose from that table, taken once at entry
+ * as plv_camera_update_points takes them —, the system of get_feature_jacobian_full on the CURRENT state with p_FinG = xyz(value),
+ * p_FinG_fej = xyz(fej), the landmark's three columns appended, Chi2Check (opt->chi2_mult x the 95 % quantile), EKFUpdate on the
+ * resident covariance; the correction is then applied to every variable of `vars` (plv_state_boxplus; plv_set_camera_intrinsics when
+ * st->intrinsic_state_id >= 0) and to every landmark's value (+= dx[id .. id + 3]) before the next one is linearised.  `st` must stay
+ * current under that, as for plv_camera_try_update: its clone arrays are the variables' val / out, its calibration fields their mirrors.
+ * A landmark with fewer than 2 rows, more than opt->max_obs usable observations or no entry in lms is skipped; a gate failure changes
+ * nothing; PLV_E_NOT_PSD of one EKF step leaves covariance and variables as before that landmark and the pass goes on.
+ * verdict [n_list]: 0 skipped, 1 applied, 2 gate, 3 not PSD.  dx_each (nullable, test aid: a copy per landmark, not for timed runs)
+ * [n_list][cov_n]: the correction of every entry (zero unless applied).
+ * One host synchronisation per landmark (the result block: dx, status, verdict) plus a constant per call; the systems never leave the
+ * device.  Refused before anything is enqueued (PLV_E_BADARG; covariance, variables, landmarks and databases untouched): null
+ * pointers, an unknown rep, a landmark or variable with id + size beyond the covariance. */
+int plv_camera_update_slam(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, int n_var, const plv_state_var *vars,
+                           int n_lm, plv_landmark *lms, const plv_tracks *tracks, plv_slam_result *res, uint64_t *ids, uint8_t *verdict,
+                           double *dx_each);
+/* UpdaterCamera::slam_init (REF: UpdaterCamera.cpp:340-369) over PLV_LIST_INIT (tracks == NULL), or over the caller's tracks with
+ * their triangulated p_FinG.  Per candidate: create_landmark (value = fej = from_xyz(p) in st->feat_rep), StateHelper::initialize as
+ * plv_slam_initialize defines it — Jacobians, Givens split, gate, initialize_invertible and the EKF step on device-resident rows: two
+ * host synchronisations —; on success the landmark is appended to lms (*n_lm grows, id = the covariance dimension before), its value
+ * receives dx_init in the representation's coordinates, and the EKF correction is applied as in plv_camera_update_slam.  A candidate
+ * whose id is in opt->slam_ids or in lms is consumed without growing the state; a failed candidate of the library's own list goes
+ * back to the tracker database (:363-364).  verdict as above (2: any test of StateHelper::initialize).  dx_each (nullable)
+ * [n_list][3 + cov_n at entry + 3 n_list]: dx_init, then the EKF correction over the grown state.  cap_lm < *n_lm + the list's
+ * size: PLV_E_BADARG, like the other refused arguments. */
+int plv_camera_init_slam(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, int n_var, const plv_state_var *vars,
+                         int *n_lm, int cap_lm, plv_landmark *lms, const plv_tracks *tracks, plv_slam_result *res, uint64_t *ids,
+                         uint8_t *verdict, double *dx_each);
+
 /* ---------------------------------------------------------------------------------------------
  * IMU propagation + window maintenance on the device-resident covariance.
  * ------------------------------------------------------------------------------------------- */

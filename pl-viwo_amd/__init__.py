@@ -210,6 +210,12 @@ def load_library():
         "plv_slam_update": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dp, dp, ip, C.c_double, u8p, dp]),
         "plv_slam_initialize": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp, ip, C.c_double, u8p, dp, dp]),
         "plv_cov_marginalize": (C.c_int, [vp, C.c_int, C.c_int]),
+        "plv_landmark_from_xyz": (C.c_int, [C.c_int, dp, dp]),
+        "plv_landmark_xyz": (C.c_int, [C.c_int, dp, dp]),
+        "plv_camera_update_slam": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvUpdateOptions), C.c_int, vp, C.c_int, vp,
+                                             C.POINTER(PlvTracks), C.POINTER(PlvSlamResult), u64p, u8p, dp]),
+        "plv_camera_init_slam": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvUpdateOptions), C.c_int, vp, ip, C.c_int, vp,
+                                           C.POINTER(PlvTracks), C.POINTER(PlvSlamResult), u64p, u8p, dp]),
         "plv_detect_lines": (C.c_int, [vp, C.c_int, fp, C.c_int, ip]),
         "plv_line_detect_launch": (C.c_int, [vp, C.c_int]),
         "plv_line_detect_finish": (C.c_int, [vp, C.c_int]),
@@ -336,6 +342,77 @@ class PlvTriOptions(C.Structure):
 
 class PlvStateVar(C.Structure):
     _fields_ = [("kind", C.c_int), ("id", C.c_int), ("size", C.c_int), ("val", C.c_void_p), ("out", C.c_void_p), ("mirror", C.c_void_p)]
+
+
+class PlvLandmark(C.Structure):
+    _fields_ = [("featid", C.c_uint64), ("id", C.c_int), ("rep", C.c_int), ("value", C.c_double * 3), ("fej", C.c_double * 3)]
+
+
+class PlvSlamResult(C.Structure):
+    _fields_ = [("n_list", C.c_int), ("n_applied", C.c_int), ("n_gate", C.c_int), ("n_not_psd", C.c_int), ("n_skipped", C.c_int),
+                ("n_returned", C.c_int), ("cov_n", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+FEAT_REPS = {"GLOBAL_3D": 0, "GLOBAL_FULL_INVERSE_DEPTH": 1}    # PLV_FEAT_*: what an in-state landmark can be held in
+
+
+def _rep(rep):
+    return FEAT_REPS[rep] if isinstance(rep, str) and rep in FEAT_REPS else (int(rep) if not isinstance(rep, str) else -1)
+
+
+def landmark_from_xyz(rep, p):
+    """plv_landmark_from_xyz: Landmark::set_from_xyz — a position as the value of a landmark held in `rep` (a name of FEAT_REPS or PLV_FEAT_*)."""
+    p, out = _c64(p), np.zeros(3)
+    rc = load_library().plv_landmark_from_xyz(_rep(rep), _dp(p), _dp(out))
+    if rc != PLV_OK:
+        raise PlvError(rc, f"plv_landmark_from_xyz: representation {rep!r}")
+    return out
+
+
+def landmark_xyz(rep, v):
+    """plv_landmark_xyz: Landmark::get_xyz — the position a landmark value stands for."""
+    v, out = _c64(v), np.zeros(3)
+    rc = load_library().plv_landmark_xyz(_rep(rep), _dp(v), _dp(out))
+    if rc != PLV_OK:
+        raise PlvError(rc, f"plv_landmark_xyz: representation {rep!r}")
+    return out
+
+
+class Landmarks:
+    """The plv_landmark array of a state (State::cam_SLAM_features in order of initialisation) with room to grow: what
+    camera_update_slam / camera_init_slam read, correct and append to."""
+
+    def __init__(self, cap=64):
+        self.a = (PlvLandmark * max(1, int(cap)))()
+        self.n = 0
+
+    def reserve(self, cap):
+        if cap > len(self.a):
+            b = (PlvLandmark * int(cap))()
+            C.memmove(b, self.a, C.sizeof(PlvLandmark) * self.n)
+            self.a = b
+
+    def append(self, featid, var_id, rep, value, fej=None):
+        self.reserve(self.n + 1)
+        e = self.a[self.n]
+        e.featid, e.id, e.rep = int(featid), int(var_id), _rep(rep)
+        e.value = (C.c_double * 3)(*np.asarray(value, dtype=np.float64))
+        e.fej = (C.c_double * 3)(*np.asarray(value if fej is None else fej, dtype=np.float64))
+        self.n += 1
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        if not 0 <= i < self.n:
+            raise IndexError(i)
+        return self.a[i]
+
+    def values(self):
+        return np.array([list(self.a[i].value) for i in range(self.n)]).reshape(-1, 3)
 
 
 class PlvTryUpdate(C.Structure):
@@ -1317,6 +1394,61 @@ class Context:
         self._chk(self.lib.plv_slam_initialize(self.h, rows, k, rows, _dp(Hf), _dp(Hx), _dp(res), _ip(cols), float(chi2_mult), _u8p(ok),
                                                _dp(dxi), _dp(dx)))
         return int(ok[0]), dxi, dx
+
+    # ---- ... a whole list per call, the systems device-resident (plv_camera_update_slam / plv_camera_init_slam)
+    LANDMARK_REPS = ("GLOBAL_3D", "GLOBAL_FULL_INVERSE_DEPTH")   # index = PLV_FEAT_*: what the two passes hold a landmark in
+
+    def _slam_pass_args(self, which, plus, max_obs, chi2_mult, slam_ids, cpi, tracks, ids):
+        sl = np.ascontiguousarray(slam_ids, dtype=np.uint64)
+        opt = PlvUpdateOptions(0, int(max_obs), float(chi2_mult), PlvTriOptions(0, 0, 0, 0, 0), 0.0, 0.0, 0, 0, len(sl),
+                               _u64p(sl) if len(sl) else None, 0, C.pointer(cpi.c) if cpi is not None else None)
+        if tracks is None:
+            n = C.c_int()
+            self._chk(self.lib.plv_camera_update_list(self.h, which, 0, 0, C.byref(n), None, None, None, None, None, None))
+            F = n.value
+            ids = np.zeros(max(F, 1), dtype=np.uint64)
+        else:
+            F = tracks.c.n_feat
+            ids = np.ascontiguousarray(ids, dtype=np.uint64).copy()
+            if len(ids) != F:
+                raise PlvError(PLV_E_BADARG, "landmark pass: one feature id per track")
+            ids = np.concatenate([ids, np.zeros(1, dtype=np.uint64)]) if F == 0 else ids
+        nv = plus.n if plus is not None else 0
+        pv = C.cast(plus.vars, C.c_void_p) if plus is not None else None
+        return opt, sl, F, ids, nv, pv, C.byref(tracks.c) if tracks is not None else None
+
+    def camera_update_slam(self, st, plus, landmarks, max_obs, chi2_mult=1.0, cpi=None, tracks=None, ids=None, want_dx=False):
+        """plv_camera_update_slam: UpdaterCamera::slam_update over the SLAM list of the last camera_update_points (tracks None) or over
+        the caller's tracks with their feature ids.  plus: the BoxPlus of every variable of the state (st's arrays must be its val / out /
+        mirror arrays); landmarks: a Landmarks, corrected in place.  Returns ids, verdict (0 skipped, 1 applied, 2 gate, 3 not PSD), the
+        counts and, with want_dx = the covariance dimension (a test aid: a copy per landmark), dx_each [n_list][cov_n]."""
+        opt, sl, F, ids, nv, pv, tr = self._slam_pass_args(0, plus, max_obs, chi2_mult, (), cpi, tracks, ids)
+        res, verdict = PlvSlamResult(), np.zeros(max(F, 1), dtype=np.uint8)
+        dx = np.zeros((max(F, 1), int(want_dx))) if want_dx else None
+        self._chk(self.lib.plv_camera_update_slam(self.h, C.byref(st.c), C.byref(opt), nv, pv, landmarks.n, C.cast(landmarks.a, C.c_void_p), tr,
+                                                  C.byref(res), _u64p(ids), _u8p(verdict), _dp(dx) if dx is not None else None))
+        out = dict(res.as_dict(), ids=ids[:F].copy(), verdict=verdict[:F].copy())
+        if dx is not None:
+            out["dx_each"] = dx[:F]
+        return out
+
+    def camera_init_slam(self, st, plus, landmarks, max_obs, chi2_mult=1.0, slam_ids=(), cpi=None, tracks=None, ids=None, want_dx=False):
+        """plv_camera_init_slam: UpdaterCamera::slam_init over the initialisation list of the last camera_update_points (tracks None) or
+        the caller's tracks (with p_FinG).  New landmarks are appended to `landmarks` in st's representation.  want_dx: the covariance
+        dimension at entry; dx_each rows are [dx_init (3), dx (grown state)]."""
+        opt, sl, F, ids, nv, pv, tr = self._slam_pass_args(1, plus, max_obs, chi2_mult, slam_ids, cpi, tracks, ids)
+        landmarks.reserve(landmarks.n + F)
+        res, verdict = PlvSlamResult(), np.zeros(max(F, 1), dtype=np.uint8)
+        dx = np.zeros((max(F, 1), 3 + int(want_dx) + 3 * F)) if want_dx else None
+        n_lm = C.c_int(landmarks.n)
+        self._chk(self.lib.plv_camera_init_slam(self.h, C.byref(st.c), C.byref(opt), nv, pv, C.byref(n_lm), len(landmarks.a),
+                                                C.cast(landmarks.a, C.c_void_p), tr, C.byref(res), _u64p(ids), _u8p(verdict),
+                                                _dp(dx) if dx is not None else None))
+        landmarks.n = n_lm.value
+        out = dict(res.as_dict(), ids=ids[:F].copy(), verdict=verdict[:F].copy())
+        if dx is not None:
+            out["dx_each"] = dx[:F]
+        return out
 
     def set_lk_window(self, win):
         """plv_set_lk_window: the LK window (plv_config.win_size) of a live context"""

@@ -956,9 +956,13 @@ int plv_cpi_noise(const plv_state_view *st, const plv_cpi_table *cpi, int n_q, c
   return PLV_OK;
 }
 
-int plv_cpi_poses(plv_ctx *ctx, const plv_state_view *st, const plv_cpi_table *cpi, int n_q, const double *t_q, double *R_GtoI,
-                  double *p_IinG, uint8_t *ok) {
-  if (!ctx || !st || !cpi || n_q < 0 || (n_q > 0 && (!t_q || !R_GtoI || !p_IinG || !ok)) || cpi->n < 0 || st->n_clones < 1)
+}  // extern "C"
+// resident (null R_GtoI / p_IinG): the poses stay on the device, *d_R_out / *d_p_out say where (the point staging's triangulation
+// block: valid until the next point update or triangulation of the ctx); only ok comes back
+static int cpi_poses_impl(plv_ctx *ctx, const plv_state_view *st, const plv_cpi_table *cpi, int n_q, const double *t_q, double *R_GtoI,
+                          double *p_IinG, uint8_t *ok, const double **d_R_out, const double **d_p_out) {
+  const bool resident = !R_GtoI && !p_IinG && d_R_out && d_p_out;
+  if (!ctx || !st || !cpi || n_q < 0 || (n_q > 0 && (!t_q || (!resident && (!R_GtoI || !p_IinG)) || !ok)) || cpi->n < 0 || st->n_clones < 1)
     return PLV_E_BADARG;
   if (cpi->n > 0 && (!cpi->t || !cpi->clone_t || !cpi->dt || !cpi->R_I0toIk || !cpi->alpha || !cpi->v)) return PLV_E_BADARG;
   for (int i = 1; i < cpi->n; ++i)
@@ -992,11 +996,17 @@ int plv_cpi_poses(plv_ctx *ctx, const plv_state_view *st, const plv_cpi_table *c
   unsigned char *d_ok = (unsigned char *)(d_p + 3 * nq);
   std::copy(cpi->gravity, cpi->gravity + 3, C.gravity);
   TRY(launch_cpi_poses(ctx, C, d_tq, d_R, d_p, d_ok));
-  PLV_HIP_CHECK(plv::memcpy_async(R_GtoI, d_R, 9 * nq * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  PLV_HIP_CHECK(plv::memcpy_async(p_IinG, d_p, 3 * nq * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (!resident) {
+    PLV_HIP_CHECK(plv::memcpy_async(R_GtoI, d_R, 9 * nq * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PLV_HIP_CHECK(plv::memcpy_async(p_IinG, d_p, 3 * nq * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  }
   PLV_HIP_CHECK(plv::memcpy_async(ok, d_ok, nq, hipMemcpyDeviceToHost, ctx->stream));
   PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
   ctx->prof.collect();
+  if (resident) {
+    *d_R_out = d_R, *d_p_out = d_p;
+    return PLV_OK;
+  }
   for (size_t q = 0; q < nq; ++q)
     if (!ok[q]) {
       std::fill(R_GtoI + 9 * q, R_GtoI + 9 * q + 9, 0.0);
@@ -1004,5 +1014,17 @@ int plv_cpi_poses(plv_ctx *ctx, const plv_state_view *st, const plv_cpi_table *c
     }
   return PLV_OK;
 }
+namespace plv {
+int plv_cpi_poses_resident(plv_ctx *ctx, const plv_state_view *st, const plv_cpi_table *cpi, int n_q, const double *t_q, uint8_t *ok,
+                           const double **d_R, const double **d_p) {
+  if (!d_R || !d_p) return PLV_E_BADARG;
+  return cpi_poses_impl(ctx, st, cpi, n_q, t_q, nullptr, nullptr, ok, d_R, d_p);
+}
+}  // namespace plv
 
+extern "C" {
+int plv_cpi_poses(plv_ctx *ctx, const plv_state_view *st, const plv_cpi_table *cpi, int n_q, const double *t_q, double *R_GtoI,
+                  double *p_IinG, uint8_t *ok) {
+  return cpi_poses_impl(ctx, st, cpi, n_q, t_q, R_GtoI, p_IinG, ok, nullptr, nullptr);
+}
 }  // extern "C"

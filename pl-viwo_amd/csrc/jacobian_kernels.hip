@@ -2465,6 +2465,43 @@ int launch_spec_select(plv_ctx *ctx, const SpecSelectArgs &A) {
   return PLV_OK;
 }
 
+// The system of ONE in-state (SLAM) landmark, written where the gate and the EKF step read it (slam_pass.hip): one workgroup, one lane
+// per observation, the row slot by ballot prefix as in jacobian_kernel.  The block is (k + 4) columns of ld rows, column-major:
+// [Hx (k) | Hf (3) | res] for an update — the landmark's own columns behind the state's, so that the block is the H of EKFUpdate under
+// the extended column map — or [Hf | Hx | res] for an initialisation (the layout the Givens split takes).  The landmark's position and
+// first estimate are P.p_FinG / P.p_FinG_fej[0], its observations [o0, o1) of the pass's staged tracks.
+__global__ void __launch_bounds__(128) landmark_system_kernel(JacParams P, LandmarkSys L) {
+  __shared__ WinTab tab[JAC_MAX_WIN];
+  const int ld = P.ld, k = P.k;
+  double *hx = L.block + (L.hf_first ? (size_t)3 * ld : 0), *hf = L.block + (L.hf_first ? 0 : (size_t)k * ld), *rs = L.block + (size_t)(k + 3) * ld;
+  for (int i = threadIdx.x; i < (k + 4) * ld; i += blockDim.x) L.block[i] = 0.0;
+  build_window_tables(P, tab);  // (ends with a barrier: also orders the zero fill before the row writes)
+  if (threadIdx.x >= 64) return;  // observation lanes = wave 0
+  int base = 0;
+  for (int ob = L.o0; ob < L.o1; ob += 64) {
+    const int o = ob + threadIdx.x;
+    const bool have = o < L.o1;
+    const double tm = (have ? P.obs_time[o] : 0.0) + P.cam_dt;
+    const int s0 = have ? bounding_start(P, tm) : -1;
+    const unsigned long long vmask = __ballot(s0 >= 0);
+    const int c = base + __popcll(vmask & ((1ull << threadIdx.x) - 1ull));
+    base += __popcll(vmask);
+    if (s0 >= 0 && 2 * c + 2 <= ld) jacobian_rows(P, tab, 0, o, s0, tm, c, hf, hx, rs, ld, 1);
+  }
+  if (threadIdx.x == 0) *L.rows = min(2 * base, ld);
+}
+
+int launch_landmark_system(plv_ctx *ctx, const JacParams &P, const LandmarkSys &L) {
+  ProfScope ps(ctx->prof, "landmark_system_kernel", ctx->stream);
+  if (2 * (P.n_clones - 3) > JAC_MAX_WIN) {
+    set_last_error("landmark system: %d clones exceed the window table (%d)", P.n_clones, JAC_MAX_WIN / 2 + 3);
+    return PLV_E_CAPACITY;
+  }
+  hipLaunchKernelGGL(landmark_system_kernel, dim3(1), dim3(128), 0, ctx->stream, P, L);
+  PLV_HIP_CHECK(hipGetLastError());
+  return PLV_OK;
+}
+
 int launch_jacobians(plv_ctx *ctx, const JacParams &P) {
   ProfScope ps(ctx->prof, "jacobian_kernel", ctx->stream);
   if (2 * (P.n_clones - 3) > JAC_MAX_WIN) {

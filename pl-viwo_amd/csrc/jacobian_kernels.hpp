@@ -135,6 +135,14 @@ struct SpecSelectArgs {
 int launch_spec_select(plv_ctx *ctx, const SpecSelectArgs &A);
 
 int launch_jacobians(plv_ctx *ctx, const JacParams &P);
+// landmark_system_kernel: where the system of one in-state landmark goes (device pointers)
+struct LandmarkSys {
+  double *block;  // (k + 4) x ld, column-major: [Hx | Hf | res], or [Hf | Hx | res] with hf_first
+  int *rows;      // 2 * (observations with bounding clones)
+  int o0, o1;     // the landmark's observations in P.obs_time / obs_uv / res_R ...
+  int hf_first;
+};
+int launch_landmark_system(plv_ctx *ctx, const JacParams &P, const LandmarkSys &L);
 struct GatherArgs;
 // the batch built AND null-space projected in one launch (resident update path); g != null: the covariance gathers ride along
 // tri_opt != null: every workgroup first triangulates its feature (arguments as launch_triangulate takes them)

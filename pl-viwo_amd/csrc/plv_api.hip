@@ -308,6 +308,7 @@ void plv_ctx_destroy(plv_ctx *ctx) {
     for (auto &s : us->stg) s.release();
     us->chain_words.release();
     us->eval.release();
+    us->slam.release();
     if (us->done_ev) (void)hipEventDestroy(us->done_ev);
     if (us->gexec) (void)hipGraphExecDestroy(us->gexec);
     us->gexec = nullptr;

@@ -98,6 +98,10 @@ void plv_camera_lines_job_abort(plv_ctx *ctx);
 // gate, compression, EKFUpdate) + plv_points_update_collect (host work inside the wait, the wait, results).  With `spec` the batch is
 // the speculative one; collect then also returns the device's membership (member [F], may be null) and *spec_over (1: the pool exceeded
 // max_sel and every candidate was left empty — nothing was updated, the caller runs the update the long way).
+// plv_cpi_poses with the poses left on the device (*d_R [n_q][9], *d_p [n_q][3]: valid until the ctx's next point update or
+// triangulation); ok [n_q] comes back
+int plv_cpi_poses_resident(plv_ctx *ctx, const plv_state_view *st, const plv_cpi_table *cpi, int n_q, const double *t_q, uint8_t *ok,
+                           const double **d_R, const double **d_p);
 int plv_points_update_submit(plv_ctx *ctx, const plv_state_view *st, const plv_tracks *all, const plv_tri_options *tri,
                              const uint8_t *flags, int max_sel, int k, const int *col_to_state, int ld, double sigma2,
                              double chi2_mult, double res_norm_gate, const plv_points_spec *spec);

@@ -153,6 +153,18 @@ __global__ void __launch_bounds__(256) cov_marginalize_kernel(const double *__re
 
 }  // namespace
 
+namespace plv {
+// cov_init_invertible_kernel on device-resident rows (slam_pass.hip): d_out [3] = H_L^-1 res, *d_flag = 1 when the reference rejects
+int launch_cov_init_invertible(plv_ctx *ctx, const double *d_P, int n, const int *d_cols, int k, const double *d_Hx, const double *d_Hf,
+                               const double *d_res, int ld, double *d_Pn, double *d_out, int *d_flag) {
+  ProfScope ps(ctx->prof, "cov_init_invertible_kernel", ctx->stream);
+  const size_t shm = (size_t)(3 * n + 32) * sizeof(double);
+  hipLaunchKernelGGL(cov_init_invertible_kernel, dim3(1), dim3(256), shm, ctx->stream, d_P, n, d_cols, k, d_Hx, d_Hf, d_res, ld, d_Pn, d_out, d_flag);
+  PLV_HIP_CHECK(hipGetLastError());
+  return PLV_OK;
+}
+}  // namespace plv
+
 extern "C" {
 
 int plv_cov_marginalize(plv_ctx *ctx, int id, int size) {

@@ -78,6 +78,10 @@ int launch_ekf_whitened(plv_ctx *ctx, double *d_P, int n, int ldp, int k, const 
 int launch_bchol_prior(plv_ctx *ctx, hipStream_t st, const double *d_P, int ldp, int n, const int *d_cols, int k, double *d_Lt, int ldl,
                        double *d_W0, int ldw, int *d_n_near);
 
+// slam_api.hip: StateHelper::initialize_invertible for a 3-dof landmark appended at index n, on device-resident rotated rows
+int launch_cov_init_invertible(plv_ctx *ctx, const double *d_P, int n, const int *d_cols, int k, const double *d_Hx, const double *d_Hf,
+                               const double *d_res, int ld, double *d_Pn, double *d_out, int *d_flag);
+
 // blocked_chol.hip
 struct WhitenC1Args {  // (whitened update: the tiles of C1 = P[:, cols] GP ride along in spare workgroups: blocked_chol.hip WhitenC1)
   const double *P;

@@ -84,6 +84,13 @@ struct plv_ctx_update_state {
   } stg[2];
   Staging &staging_of(int fdim) { return stg[fdim == 6 ? 1 : 0]; }
   plv::DevBuf eval;
+  // the landmark passes (slam_pass.hip): what a pass stages once (clone times and first estimates, every landmark's observations and
+  // column map), what it stages per landmark (the clone poses and the landmark as they are now), the landmark's system and its result
+  struct SlamPass {
+    plv::DevBuf stat, dyn, sys, res;
+    plv::PinBuf h_stat, h_dyn, h_res;
+    void release() { stat.release(), dyn.release(), sys.release(), res.release(), h_stat.release(), h_dyn.release(), h_res.release(); }
+  } slam;
   size_t lt_o_lines = 0;  // plv_lines_update_fused_submit -> _finish: where the triangulated lines sit in tri_l, how many
   int lt_L = 0;
   int pending_fdim = 3;  // measurement size of the launched, not yet collected update (selects the pinned result block)

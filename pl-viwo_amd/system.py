@@ -9,7 +9,8 @@ REF: PL-VIWO/src/core/SystemManager.cpp:55-135 (feed_measurement_imu / _camera /
 
 The camera path follows the intended flow feed_measurement -> try_update (as published, SystemManager.cpp:107-127 returns
 before try_update once the filter is initialised).  Scope of this driver: one camera (monocular), MSCKF points and lines
-(in-state SLAM landmarks in the GLOBAL_3D representation; the shipped configuration has cam.max_slam: 0), wheel optional; `use_imu_res` takes the poses of the camera update from the CPI records of plv_propagate; GPS / LiDAR / stereo /
+(in-state SLAM landmarks in either representation the reference accepts when the context has the landmark passes, GLOBAL_3D otherwise;
+the shipped configuration has cam.max_slam: 0), wheel optional; `use_imu_res` takes the poses of the camera update from the CPI records of plv_propagate; GPS / LiDAR / stereo /
 simulation are outside SURVEY §8.  With `est.zupt.enabled` a camera frame first asks the zero-velocity updater (REF: SystemManager.cpp:50-52,
 116-121; _zupt_try_update) and leaves its camera update out when that one applied.
 """
@@ -20,7 +21,7 @@ import time as _time
 
 import numpy as np
 
-from . import BoxPlus, PlvStateView, jpl_left_update
+from . import BoxPlus, Landmarks, PlvStateView, jpl_left_update, landmark_from_xyz, landmark_xyz
 from . import (Context, CpiTable, IwInitializer, PlvError, PlvImuState, PlvWheelOptions, PlvWheelState, PlvZuptOptions, StateView, Tracks, WHEEL_TYPES, default_config,
                imu_noise, init_imu_static, next_clone_time, reset_cpi, select_imu_readings, select_wheel_data)
 from .options import OptionsError
@@ -130,11 +131,30 @@ class Vec:
 
 
 class Landmark:
-    """ov_type::Landmark, GLOBAL_3D: value, first estimate, covariance index (REF: open_vins/ov_core/src/types/Landmark.h)."""
+    """ov_type::Landmark: value and first estimate in its representation (GLOBAL_3D: xyz; GLOBAL_FULL_INVERSE_DEPTH: theta, phi, rho),
+    covariance index; the position is a derived view (REF: open_vins/ov_core/src/types/Landmark.h, Landmark.cpp:26-101)."""
 
-    def __init__(self, featid, p, var_id):
-        self.featid, self.p, self.p_fej, self.id = int(featid), np.array(p, dtype=np.float64), np.array(p, dtype=np.float64), var_id
+    def __init__(self, featid, p, var_id, rep=0):
+        self.featid, self.id, self.rep = int(featid), var_id, int(rep)
+        self.value = landmark_from_xyz(self.rep, p)
+        self.fej = self.value.copy()
         self.update_fail_count = 0   # read by marginalize_slam_features (UpdaterCamera.cpp:130); nothing in the reference increments it
+
+    @property
+    def p(self):          # Landmark::get_xyz(false)
+        return landmark_xyz(self.rep, self.value)
+
+    @p.setter
+    def p(self, xyz):     # Landmark::set_from_xyz(p, false)
+        self.value = landmark_from_xyz(self.rep, xyz)
+
+    @property
+    def p_fej(self):
+        return landmark_xyz(self.rep, self.fej)
+
+    @p_fej.setter
+    def p_fej(self, xyz):
+        self.fej = landmark_from_xyz(self.rep, xyz)
 
 
 class State:
@@ -309,7 +329,7 @@ class State:
             w = self._window_arrays()
         w["plus"].apply(dx)               # every variable, the clone window and the state view's calibration fields: one C call
         for lm in self.slam.values():
-            lm.p = lm.p + dx[lm.id:lm.id + 3]
+            lm.value = lm.value + dx[lm.id:lm.id + 3]      # Landmark::update: in the representation's coordinates
         if self.cam_intr is not None and self.op.est.cam.do_calib_int:
             self.ctx.set_camera_intrinsics(self.cam_intr.v)     # StateHelper.cpp:163-168
 
@@ -403,6 +423,7 @@ class SystemManager:
 
     one_call_frame = os.environ.get("PLV_ONE_CALL", "2") == "2"
     one_call_update = True      # try_update through plv_camera_try_update (False: plv_camera_update_points / _lines with the dx applied here)
+    slam_pass = True            # in-state landmarks through camera_update_slam / camera_init_slam where the context has them (False: one by one)
 
     def __init__(self, op, device=0, max_obs=24, context_factory=None, iw_initializer_factory=None, decisions=None):
         """context_factory / iw_initializer_factory: stand-ins with the interface of Context / IwInitializer (the tests run the same
@@ -414,7 +435,7 @@ class SystemManager:
         e = op.est
         if e.cam.enabled and e.cam.max_n != 1:
             raise OptionsError("replay driver: one camera (cam.max_n: 1, use_stereo: false)")
-        if e.cam.enabled and e.cam.max_slam != 0 and e.cam.feat_rep != 0:
+        if e.cam.enabled and e.cam.max_slam != 0 and e.cam.feat_rep != 0 and not (self.slam_pass and hasattr(context_factory or Context, "LANDMARK_REPS")):
             raise OptionsError("replay driver: in-state landmarks (cam.max_slam > 0) are driven in the GLOBAL_3D representation only")
         cam_model = e.cam.distortion_model[0] if e.cam.enabled else "radtan"
         if cam_model != "radtan" and cam_model not in getattr(context_factory or Context, "CAMERA_MODELS", ()):
@@ -884,7 +905,7 @@ class SystemManager:
         self.tc.dong("[Time-Cam] get features + MSCKF update")
         self._count_points(out)
         if c.max_slam > 0:
-            self._slam_update_and_init(out)
+            self._slam_update_and_init(out, kw.get("cpi"))
         if self.use_lines:
             self.tc.ding("[Time-Cam] LINE update")
             self._join_lines()
@@ -947,7 +968,38 @@ class SystemManager:
         r = int(rows[0])
         return r, Hf[0].T[:r].copy(), Hx[0].T[:r].copy(), res[0][:r].copy(), cols
 
-    def _slam_update_and_init(self, out):   # UpdaterCamera::slam_update :296-338, slam_init :340-369
+    def _slam_passes(self, out, cpi):
+        """slam_update and slam_init as one library call each (plv_camera_update_slam / plv_camera_init_slam): the landmarks' systems stay
+        on the device, the corrections are applied to the state's own arrays by the calls (State.apply's prepared boxplus)."""
+        st, c = self.state, self.op.est.cam
+        w = st._window_arrays()
+        if w["imu"] is not st.imu:
+            st._win_dirty = True
+            w = st._window_arrays()
+        order = list(st.slam.values())
+        lms = Landmarks(len(order) + out["n_init"] + 1)
+        for lm in order:
+            lms.append(lm.featid, lm.id, lm.rep, lm.value, lm.fej)
+        sv = st.view()
+        if out["n_slam"]:
+            r = self.ctx.camera_update_slam(sv, w["plus"], lms, self.max_obs, chi2_mult=c.chi2_mult, cpi=cpi)
+            self.stats["slam_updates"] += r["n_applied"]
+            self.stats["not_psd"] += r["n_not_psd"]
+        if out["n_init"]:
+            r = self.ctx.camera_init_slam(sv, w["plus"], lms, self.max_obs, chi2_mult=c.chi2_mult, slam_ids=list(st.slam), cpi=cpi)
+            self.stats["slam_initialized"] += r["n_applied"]
+            st.n = r["cov_n"]
+        for i in range(len(lms)):
+            e = lms[i]
+            if i < len(order):
+                order[i].value = np.array(e.value)
+            else:
+                lm = st.slam[int(e.featid)] = Landmark(e.featid, landmark_xyz(e.rep, np.array(e.fej)), e.id, e.rep)
+                lm.value, lm.fej = np.array(e.value), np.array(e.fej)
+
+    def _slam_update_and_init(self, out, cpi=None):   # UpdaterCamera::slam_update :296-338, slam_init :340-369
+        if self.slam_pass and hasattr(self.ctx, "camera_update_slam"):
+            return self._slam_passes(out, cpi)
         st, c = self.state, self.op.est.cam
         if out["n_slam"]:
             lst = self.ctx.camera_update_list(0)

@@ -4,6 +4,7 @@
     python tools/replay.py CONFIG.yaml [--dataset DIR] [--gt FILE] [--align posyaw] [--rpe 8,16,24] [--nees] [--out result.json]
     python tools/replay.py --synthetic 12 [--out result.json]        # renders tests/synth_dataset.py first (CPU), then replays it
     python tools/replay.py CONFIG.yaml --dataset KAIST_DIR [--host-images]   # Bayer frames: converted on the device unless --host-images
+    python tools/replay.py --synthetic 12 --max-slam 12 --feat-rep GLOBAL_FULL_INVERSE_DEPTH   # in-state landmarks, either representation
 """
 import argparse
 import importlib
@@ -31,6 +32,8 @@ def main():
     ap.add_argument("--no-wheel", action="store_true")
     ap.add_argument("--no-lines", action="store_true")
     ap.add_argument("--keep", help="directory to keep the synthetic dataset in")
+    ap.add_argument("--max-slam", type=int, help="override cam.max_slam: long tracks become in-state landmarks")
+    ap.add_argument("--feat-rep", choices=("GLOBAL_3D", "GLOBAL_FULL_INVERSE_DEPTH"), help="override cam.feat_rep")
     ap.add_argument("--host-images", action="store_true", help="frames that are not grey (a KAIST directory's Bayer mosaics) are converted on the "
                     "host by the dataset reader instead of on the device by the library (the comparison run)")
     a = ap.parse_args()
@@ -52,6 +55,10 @@ def main():
         op.sys.path_bag = a.dataset
     if a.no_lines:
         op.est.cam.use_lines = False
+    if a.max_slam is not None:
+        op.est.cam.max_slam = a.max_slam
+    if a.feat_rep:
+        op.est.cam.feat_rep = options.FEAT_REP[a.feat_rep]
     if not op.sys.save_trajectory:
         op.sys.save_trajectory, op.sys.path_trajectory = True, os.path.join(tempfile.mkdtemp(prefix="plv_out_"), "traj.txt")
     t0 = time.time()
