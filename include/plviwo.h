@@ -609,10 +609,26 @@ int plv_line_detect_launch(plv_ctx *ctx, int which);
  * the segments; the next plv_line_tracker_feed[_points] of the SAME frame (no image fed in between) takes them instead of
  * detecting again.  Lets the caller place the host stage between plv_perform_matching_launch and _wait. */
 int plv_line_detect_finish(plv_ctx *ctx, int which);
-/* Where the detector's chain walk runs: 0 (default) = on the host between the device stages (Canny map down,
- * chains up), 1 = fld_walk_kernel on the device.  Same results; the walk is one dependent chain of
- * ~10^4 scalar steps, which a single GPU lane retires ~25x slower than a host core. */
+/* Where the detector's chain walk and segment fit run.  Same segments in the same order in every mode.
+ *   0 (default)  on the host between the device stages (Canny map down, segments up): the walk is one dependent chain of ~10^4
+ *                scalar steps, which a host core retires ~25x faster than a single GPU lane (DESIGN.md "Line detector").
+ *   1            fld_walk_kernel + fld_fit_kernel: the whole image walked by one wave, one lane per chain for the fit.
+ *   2            component-parallel, no host thread: the walk never leaves an 8-connected component of the edge map, so every
+ *                component is walked by a wave of its own on a bit map in LDS, the kept chains are ordered by their seeds and every
+ *                chain is fitted by a wave of its own.  A detection falls back to the kernels of mode 1 (plv_line_walk_info says
+ *                so) when the edge map has more components than the device lists (4096), when the bit map of the half-resolution
+ *                image exceeds 64 KB of LDS (above ~1400 x 1400 pixels), or when the Canny thresholds differ (hysteresis).
+ * Any other non-zero value means 1.  Modes 1 and 2 have no host stage: plv_line_detect_launch and the prefetch do nothing. */
 int plv_line_walk_mode(plv_ctx *ctx, int on_device);
+/* The last detection: the mode that ran (0, 1 or 2), the components walked and the pixels of the largest (mode 2, else 0), the chains
+ * kept (device modes, else 0), whether mode 2 fell back to mode 1's kernels.  Every pointer may be null. */
+int plv_line_walk_info(plv_ctx *ctx, int *mode, int *n_components, int *longest_component, int *n_chains, int *fell_back);
+/* The edge chains of the last detection when it ran on the device (modes 1 and 2), in output order (the raster order of their seeds):
+ * chain c has the points pts_xy[2 * chain_ptr[c]] .. pts_xy[2 * chain_ptr[c + 1]) as x, y in the half-resolution image.  chain_ptr
+ * holds cap_chains + 1 entries, pts_xy 2 * cap_pts (null: lengths only); the chains never hold more points than the half-resolution
+ * image has pixels.  n_chains (nullable) receives the number of chains; chain_ptr == NULL only queries it.  PLV_E_BADARG after a
+ * detection in mode 0 or before any; PLV_E_CAPACITY (nothing written) when a capacity is too small.  Valid until the next detection. */
+int plv_line_chains(plv_ctx *ctx, int cap_chains, int cap_pts, int *chain_ptr, int *pts_xy, int *n_chains);
 
 /* TrackLSD::AssignPointToLines (REF :744-792, including its bounding-box test on (x1,y1) / (x2,y2)):
  * kept[q] = input index of the q-th line that owns at least one point; CSR lists per kept line:

@@ -225,6 +225,8 @@ def load_library():
         "plv_camera_try_update": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvTryUpdate)]),
         "plv_camera_frame": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvCameraFrameIo)]),
         "plv_line_walk_mode": (C.c_int, [vp, C.c_int]),
+        "plv_line_walk_info": (C.c_int, [vp, ip, ip, ip, ip, ip]),
+        "plv_line_chains": (C.c_int, [vp, C.c_int, C.c_int, ip, ip, ip]),
         "plv_line_prefetch_mode": (C.c_int, [vp, C.c_int]),
         "plv_line_tracker_feed_async": (C.c_int, [vp, C.c_double, dp]),
         "plv_line_tracker_feed_wait": (C.c_int, [vp]),
@@ -1689,7 +1691,25 @@ class Context:
         self._chk(self.lib.plv_line_prefetch_mode(self.h, 1 if on else 0))
 
     def line_walk_mode(self, on_device):
-        self._chk(self.lib.plv_line_walk_mode(self.h, 1 if on_device else 0))
+        """plv_line_walk_mode: 0 / False host stage (default), 1 / True one wave for the image, 2 one wave per component and per chain"""
+        self._chk(self.lib.plv_line_walk_mode(self.h, int(on_device)))
+
+    def line_walk_info(self):
+        """plv_line_walk_info: the last detection as a dict (mode, n_components, longest_component, n_chains, fell_back)"""
+        v = [C.c_int() for _ in range(5)]
+        self._chk(self.lib.plv_line_walk_info(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("mode", "n_components", "longest_component", "n_chains", "fell_back"), (x.value for x in v)))
+
+    def line_chains(self):
+        """plv_line_chains: the edge chains of the last device detection in output order, a list of [len, 2] int32 arrays (x, y in the
+        half-resolution image)"""
+        n = C.c_int()
+        self._chk(self.lib.plv_line_chains(self.h, 0, 0, None, None, C.byref(n)))
+        ptr = np.zeros(n.value + 1, dtype=np.int32)
+        self._chk(self.lib.plv_line_chains(self.h, n.value, 0, _ip(ptr), None, C.byref(n)))
+        pts = np.zeros((max(int(ptr[-1]), 1), 2), dtype=np.int32)
+        self._chk(self.lib.plv_line_chains(self.h, n.value, int(ptr[-1]), _ip(ptr), _ip(pts), C.byref(n)))
+        return [pts[ptr[c]:ptr[c + 1]].copy() for c in range(n.value)]
 
     def assign_points_to_lines(self, lines, pts, ids):
         lines = np.ascontiguousarray(lines, dtype=np.float32).reshape(-1, 4)

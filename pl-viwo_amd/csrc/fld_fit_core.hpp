@@ -1,5 +1,5 @@
 // fld_fit_core.hpp — FastLineDetector's segment growing for ONE edge chain, shared by fld_fit_kernel (one lane per chain,
-// device-walk mode) and the host path of plv_detect_lines (default: the chain walk and the segment growth are one dependent
+// device-walk mode 1), fld_fit_wave_kernel (one wave per chain, mode 2) and the host path of plv_detect_lines (default: the chain walk and the segment growth are one dependent
 // scalar sequence per chain; a host core retires it ~25x faster than a single GPU lane, DESIGN.md "Line detector").
 //   REF (OpenCV contract): ximgproc/src/fast_line_detector.cpp lineDetection / extractSegments /
 //   additionalOperationsOnSegment; cv::fitLine(DIST_L2).
@@ -86,45 +86,62 @@ PLV_HD inline void inboard(int &x, int &y, int w, int h) {
 }
 
 
-// Segments of one chain P[0..total): writes them to out (capacity total / length_threshold + 1) and returns their number.
-PLV_HD inline int fit_chain(const uint8_t *src, int w, int h, int length_threshold, float distance_threshold, const int2 *P, int total,
-                            float4 *out) {
-  int nseg = 0;
-  for (int i = 0; i + length_threshold < total; ++i) {
-    int2 ps = P[i], pe = P[i + length_threshold];
-    L3 l = cr3(ps.x, ps.y, 1.0, pe.x, pe.y, 1.0);
-    bool is_line = true;
-    // Is every point between the two within distance_threshold of the chord?  The reference normalises the chord (a square root and
-    // three divisions) and compares |a' x + b' y + c'| with the threshold; most starts of a chain fail this test after a few points
-    // (round 6: 27 ns per chain point, two thirds of the detector's host time).  The chord through two pixels has integer
-    // coefficients, so v = a x + b y + c is exact and |v| / sqrt(a^2 + b^2) is the distance the reference rounds: when v^2 lies
-    // clear of threshold^2 (a^2 + b^2) — by 1e-9, the reference's own rounding is below 1e-12 — the verdict is taken from the
-    // integers; a value inside that band (a tie to nine digits) is decided by the reference's arithmetic.  Same verdicts, bit for bit.
-    {
-      const double s2 = l.a * l.a + l.b * l.b, thr = (double)distance_threshold;
-      const double lim = thr * thr * s2, lim_hi = lim * (1.0 + 1e-9), lim_lo = lim * (1.0 - 1e-9);
-      L3 ln = l;
-      bool normalised = false;
-      for (int j = 1; j < length_threshold; ++j) {
-        const int2 pt = P[i + j];
-        const double v = l.a * pt.x + l.b * pt.y + l.c, v2 = v * v;
-        if (v2 < lim_lo) continue;
-        if (v2 > lim_hi) {
-          is_line = false;
-          break;
-        }
-        if (!normalised) {  // (the reference's own sequence: dist_pl normalises the chord in place at its first call)
-          const double wv = sqrt(s2);
-          ln.a /= wv, ln.b /= wv, ln.c /= wv;
-          normalised = true;
-        }
-        if (fabs(ln.a * pt.x + ln.b * pt.y + ln.c) > distance_threshold) {
-          is_line = false;
-          break;
-        }
+// The chord test of extractSegments for the window that starts at point i of a chain.  It reads the chain only, so the starts of a chain
+// can be tested in any order, or all at once (fld_fit_wave_kernel); the growth below asks for the verdicts in ascending order.
+PLV_HD inline bool chord_is_line(const int2 *P, int i, int length_threshold, float distance_threshold) {
+  const int2 ps = P[i], pe = P[i + length_threshold];
+  const L3 l = cr3(ps.x, ps.y, 1.0, pe.x, pe.y, 1.0);
+  bool is_line = true;
+  // Is every point between the two within distance_threshold of the chord?  The reference normalises the chord (a square root and
+  // three divisions) and compares |a' x + b' y + c'| with the threshold; most starts of a chain fail this test after a few points
+  // (round 6: 27 ns per chain point, two thirds of the detector's host time).  The chord through two pixels has integer
+  // coefficients, so v = a x + b y + c is exact and |v| / sqrt(a^2 + b^2) is the distance the reference rounds: when v^2 lies
+  // clear of threshold^2 (a^2 + b^2) — by 1e-9, the reference's own rounding is below 1e-12 — the verdict is taken from the
+  // integers; a value inside that band (a tie to nine digits) is decided by the reference's arithmetic.  Same verdicts, bit for bit.
+  {
+    const double s2 = l.a * l.a + l.b * l.b, thr = (double)distance_threshold;
+    const double lim = thr * thr * s2, lim_hi = lim * (1.0 + 1e-9), lim_lo = lim * (1.0 - 1e-9);
+    L3 ln = l;
+    bool normalised = false;
+    for (int j = 1; j < length_threshold; ++j) {
+      const int2 pt = P[i + j];
+      const double v = l.a * pt.x + l.b * pt.y + l.c, v2 = v * v;
+      if (v2 < lim_lo) continue;
+      if (v2 > lim_hi) {
+        is_line = false;
+        break;
+      }
+      if (!normalised) {  // (the reference's own sequence: dist_pl normalises the chord in place at its first call)
+        const double wv = sqrt(s2);
+        ln.a /= wv, ln.b /= wv, ln.c /= wv;
+        normalised = true;
+      }
+      if (fabs(ln.a * pt.x + ln.b * pt.y + ln.c) > distance_threshold) {
+        is_line = false;
+        break;
       }
     }
-    if (!is_line) continue;
+  }
+  return is_line;
+}
+// chord_is_line computed where it is asked for (the host stage, fld_fit_kernel)
+struct ChordTest {
+  const int2 *P;
+  int length_threshold;
+  float distance_threshold;
+  PLV_HD bool operator()(int i) const { return chord_is_line(P, i, length_threshold, distance_threshold); }
+};
+
+// Segments of one chain P[0..total): writes them to out (capacity total / length_threshold + 1) and returns their number.
+// is_line(i): the chord test's verdict for the window that starts at i (asked for ascending i, every i at most once).
+template <class Verdict>
+PLV_HD inline int fit_chain_with(const uint8_t *src, int w, int h, int length_threshold, float distance_threshold, const int2 *P, int total,
+                                 float4 *out, Verdict &&is_line) {
+  int nseg = 0;
+  for (int i = 0; i + length_threshold < total; ++i) {
+    if (!is_line(i)) continue;
+    int2 ps = P[i], pe = P[i + length_threshold];
+    L3 l;
     // (the sums of the fit are exact integers: adding the window's points once the test has passed gives the values the reference
     //  accumulates while it tests)
     Fit fs{0, 0, 0, 0, 0, 0};
@@ -198,6 +215,10 @@ PLV_HD inline int fit_chain(const uint8_t *src, int w, int h, int length_thresho
     out[nseg++] = plv_make_float4(e1x, e1y, e2x, e2y);
   }
   return nseg;
+}
+PLV_HD inline int fit_chain(const uint8_t *src, int w, int h, int length_threshold, float distance_threshold, const int2 *P, int total,
+                            float4 *out) {
+  return fit_chain_with(src, w, h, length_threshold, distance_threshold, P, total, out, ChordTest{P, length_threshold, distance_threshold});
 }
 
 

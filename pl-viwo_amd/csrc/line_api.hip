@@ -8,7 +8,7 @@
 //   LineFeatureDatabase::update_feature             REF: linefeat/LineFeatureDatabase.cpp:40-76
 // Pixel work (half-resolution resize, Sobel, non-maximum suppression, hysteresis) runs on the device; the
 // detector's list processing (chain walk + segment growth) is a HOST stage by default (plv_line_walk_mode
-// selects the device kernels; DESIGN.md "Line detector" has the measurements behind that choice).  The rest
+// selects the device kernels, 1 serial or 2 component-parallel; DESIGN.md "Line detector" has the measurements behind that choice).  The rest
 // here is the reference's own host bookkeeping: id hand-over between frames and the line track store.
 #include <algorithm>
 #include <chrono>
@@ -103,7 +103,16 @@ struct LineTracker {
   std::vector<int> rel_ptr_last{0};  // CSR: point ids on each last line (ascending, the reference keeps a std::map)
   std::vector<uint64_t> rel_id_last;
   uint64_t currid = 1;  // REF: TrackLSD.cpp:32, ids are pre-incremented (:234)
-  bool walk_on_device = false;  // plv_line_walk_mode
+  bool walk_on_device = false;  // plv_line_walk_mode: 1 or 2
+  int walk_mode = 0;            // 0 host stage, 1 fld_walk_kernel + fld_fit_kernel, 2 one wave per component / per chain
+  // plv_line_walk_info / plv_line_chains: the last detection
+  struct WalkInfo {
+    int mode = 0, n_components = 0, longest_component = 0, n_chains = 0, fell_back = 0;
+  } winfo;
+  bool chains_valid = false;          // the last detection ran on the device: its chain table is below, its points are still in `pts`
+  std::vector<FldChain> last_chains;  // (output order)
+  int last_pts_extent = 0;            // points of `pts` the chains lie in
+  DevBuf comps, recs, recs_sorted;    // component-parallel walk (mode 2): line_kernels.hpp FldBuffers
   bool prefetch = false;        // plv_line_prefetch_mode: plv_tracker_feed* detects the lines of the new image ahead of plv_line_tracker_feed
   std::unordered_map<uint64_t, LineTrack> db;
   // device buffers of the detector
@@ -316,6 +325,8 @@ int detect(plv_ctx *ctx, LineTracker *T, int which, std::vector<float> &lines, b
   }
   const int w = W / 2, h = H / 2;
   const size_t npix = (size_t)w * h;
+  T->chains_valid = false;
+  if (!launch_only) T->winfo = LineTracker::WalkInfo{};
   // (a helper thread the last detection's host stage was closed without — cut off in the middle of a part — reads the job, the maps and
   // the lists this call rewrites, possibly in buffers it regrows: nobody is inside a job from here on.  Immediate, unless that thread
   // has been off its CPU for a whole frame.)
@@ -325,7 +336,7 @@ int detect(plv_ctx *ctx, LineTracker *T, int which, std::vector<float> &lines, b
   TRY(T->work.reserve(npix));
   TRY(T->pts.reserve(npix * sizeof(int2)));
   TRY(T->chains.reserve(kChainCap * sizeof(FldChain)));
-  TRY(T->counts.reserve(4 * sizeof(int)));
+  TRY(T->counts.reserve(12 * sizeof(int)));  // (4 counts, then the 8 words of the component walk)
   const size_t slot_cap = npix / (size_t)std::max(1, ctx->cfg.line_length_threshold) + kChainCap;
   TRY(T->segs.reserve(slot_cap * sizeof(float4)));
   TRY(T->seg_count.reserve(kChainCap * sizeof(int)));
@@ -337,7 +348,8 @@ int detect(plv_ctx *ctx, LineTracker *T, int which, std::vector<float> &lines, b
   // (behind the labels: the parts' pixel lists, ccl_flatten_kernel)
   const size_t nblk = (npix + 255) / 256, sorted_off = (lab_off + npix + 63) & ~(size_t)63, bins_off = sorted_off + nblk * 256;
   const size_t pin_end = bins_off + nblk * (size_t)(plv::line_label_parts() + 1) * sizeof(unsigned short);
-  TRY(T->pin.reserve(std::max(bytes + slot_cap * sizeof(float4), pin_end + 64)));
+  const size_t info_off = (std::max(bytes + slot_cap * sizeof(float4), pin_end + 64) + 63) & ~(size_t)63;  // (the component walk's 8 words)
+  TRY(T->pin.reserve(info_off + 64));
   char *hp = T->pin.as<char>();
   // host walk without hysteresis (the shipped thresholds are equal): the edge kernel writes the two maps straight into the pinned
   // buffer the host stage reads — no device copies of them, no copy commands behind the kernel
@@ -358,6 +370,27 @@ int detect(plv_ctx *ctx, LineTracker *T, int which, std::vector<float> &lines, b
     b.lab_out = (uint8_t *)(hp + lab_off);
     b.blk_sorted = (uint8_t *)(hp + sorted_off);
     b.blk_bins = (unsigned short *)(hp + bins_off);
+  }
+  // Mode 2 walks by components when the device labels them for this detection and the bit map of the half-resolution image fits in
+  // LDS; otherwise mode 1's kernels run (hysteresis rewrites the edge map behind the edge kernel's tile-local labels).  A third
+  // reason is only known on the device: more components than the root list holds (the kernels then hand over by themselves).
+  const bool comp_walk = T->walk_mode == 2 && fp.canny_low == fp.canny_high && plv::line_walk_lds_bytes(w, h) <= plv::kLineWalkLdsMax;
+  if (comp_walk) {
+    (void)join_job(T);  // (a detection launched ahead in mode 0 and never taken may still use the label buffers on its own stream)
+    const size_t rec_cap = npix / (size_t)(std::max(1, fp.length_threshold) + 1) + 1;
+    TRY(T->lab.reserve(npix * sizeof(int)));
+    TRY(T->lab_cnt.reserve(npix * sizeof(int)));
+    TRY(T->lab_roots.reserve(plv::line_label_roots_bytes()));
+    TRY(T->comps.reserve((size_t)plv::line_walk_components_cap() * sizeof(FldComp)));
+    TRY(T->recs.reserve(rec_cap * sizeof(FldRec)));
+    TRY(T->recs_sorted.reserve(rec_cap * sizeof(FldRec)));
+    b.lab_work = T->lab.as<int>();
+    b.lab_cnt = T->lab_cnt.as<int>();
+    b.lab_roots = T->lab_roots.as<int>();
+    b.comps = T->comps.as<FldComp>();
+    b.recs = T->recs.as<FldRec>();
+    b.recs_sorted = T->recs_sorted.as<FldRec>();
+    b.walk_info = T->counts.as<int>() + 4;
   }
   if (!prelaunched) TRY(launch_line_edges(ctx, d_img, W, H, fp, b, ctx->stream, early ? T->early_hist : nullptr));
   if (with_labels && !T->ccl_stream) {
@@ -437,12 +470,30 @@ int detect(plv_ctx *ctx, LineTracker *T, int which, std::vector<float> &lines, b
     ctx->prof.collect();
     return PLV_OK;
   }
-  TRY(launch_line_walk(ctx, w, h, fp, b));
-  TRY(launch_line_fit(ctx, w, h, fp, b));
+  int *hinfo = (int *)(hp + info_off);
+  if (comp_walk) {
+    TRY(launch_line_walk_components(ctx, w, h, fp, b));
+    TRY(launch_line_walk(ctx, w, h, fp, b, b.walk_info + 2));  // (the fallback decided on the device: these two leave at once otherwise)
+    TRY(launch_line_fit(ctx, w, h, fp, b, b.walk_info + 2));
+    PLV_HIP_CHECK(plv::memcpy_async(hinfo, b.walk_info, 8 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  } else {
+    TRY(launch_line_walk(ctx, w, h, fp, b));
+    TRY(launch_line_fit(ctx, w, h, fp, b));
+  }
   // download: counts, chain table, per-chain segment counts, segment slots
   PLV_HIP_CHECK(plv::memcpy_async(hp, T->counts.p, 16, hipMemcpyDeviceToHost, ctx->stream));
   PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
   const int n_chain = ((int *)hp)[0], n_slot = ((int *)hp)[1];
+  const bool by_components = comp_walk && hinfo[2] == 0;
+  if (comp_walk && hinfo[3] != 0) {
+    set_last_error("plv_detect_lines: the component walk left through its error word (%d)", hinfo[3]);
+    return PLV_E_DEVICE;
+  }
+  T->winfo.mode = by_components ? 2 : 1;
+  T->winfo.fell_back = T->walk_mode == 2 && !by_components ? 1 : 0;
+  T->winfo.n_components = by_components ? hinfo[0] : 0;
+  T->winfo.longest_component = by_components ? hinfo[1] : 0;
+  T->winfo.n_chains = std::min(n_chain, kChainCap);
   if (n_chain >= kChainCap) {
     set_last_error("plv_detect_lines: more than %d edge chains", kChainCap);
     return PLV_E_CAPACITY;
@@ -457,7 +508,12 @@ int detect(plv_ctx *ctx, LineTracker *T, int which, std::vector<float> &lines, b
     PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
     for (int c = 0; c < n_chain; ++c)  // chains are in raster order of their seeds = the detector's output order
       for (int q = 0; q < hn[c]; ++q) emit(hs[hc[c].slot + q]);
+    T->last_chains.assign(hc, hc + n_chain);
+  } else {
+    T->last_chains.clear();
   }
+  T->last_pts_extent = by_components ? hinfo[4] : ((int *)hp)[2];
+  T->chains_valid = true;
   ctx->prof.collect();
   return PLV_OK;
 }
@@ -481,7 +537,8 @@ void plv_line_tracker_destroy(plv_ctx *ctx) {
       T->worker.join();
     }
     // (the fitter threads end with T->host: ~HostStage)
-    DevBuf *bufs[] = {&T->half, &T->map, &T->work, &T->pts, &T->chains, &T->counts, &T->segs, &T->seg_count, &T->uv_in, &T->uv_out, &T->lab, &T->lab_cnt, &T->lab_roots};
+    DevBuf *bufs[] = {&T->half, &T->map, &T->work, &T->pts, &T->chains, &T->counts, &T->segs, &T->seg_count, &T->uv_in, &T->uv_out, &T->lab, &T->lab_cnt, &T->lab_roots,
+                      &T->comps, &T->recs, &T->recs_sorted};
     for (DevBuf *b : bufs) b->release();
     T->pin.release();
     if (T->edges_ready) (void)hipEventDestroy(T->edges_ready);
@@ -501,6 +558,48 @@ int plv_line_walk_mode(plv_ctx *ctx, int on_device) {
   LineTracker *T = ltr(ctx);
   std::lock_guard<std::mutex> lk(T->mtx);
   T->walk_on_device = on_device != 0;
+  T->walk_mode = on_device == 0 ? 0 : (on_device == 2 ? 2 : 1);
+  return PLV_OK;
+}
+
+int plv_line_walk_info(plv_ctx *ctx, int *mode, int *n_components, int *longest_component, int *n_chains, int *fell_back) {
+  if (!ctx) return PLV_E_BADARG;
+  LineTracker *T = ltr(ctx);
+  std::lock_guard<std::mutex> lk(T->mtx);
+  if (mode) *mode = T->winfo.mode;
+  if (n_components) *n_components = T->winfo.n_components;
+  if (longest_component) *longest_component = T->winfo.longest_component;
+  if (n_chains) *n_chains = T->winfo.n_chains;
+  if (fell_back) *fell_back = T->winfo.fell_back;
+  return PLV_OK;
+}
+
+int plv_line_chains(plv_ctx *ctx, int cap_chains, int cap_pts, int *chain_ptr, int *pts_xy, int *n_chains) {
+  if (!ctx || cap_chains < 0 || cap_pts < 0) return PLV_E_BADARG;
+  (void)hipSetDevice(ctx->device);
+  LineTracker *T = ltr(ctx);
+  std::lock_guard<std::mutex> lk(T->mtx);
+  if (!T->chains_valid) {
+    set_last_error("plv_line_chains: the last detection did not run on the device (plv_line_walk_mode 1 or 2)");
+    return PLV_E_BADARG;
+  }
+  const int n = (int)T->last_chains.size();
+  size_t total = 0;
+  for (const FldChain &c : T->last_chains) total += (size_t)c.len;
+  if (n_chains) *n_chains = n;
+  if (!chain_ptr) return PLV_OK;  // the query
+  if (n > cap_chains || (pts_xy && total > (size_t)cap_pts)) return PLV_E_CAPACITY;
+  chain_ptr[0] = 0;
+  for (int c = 0; c < n; ++c) chain_ptr[c + 1] = chain_ptr[c] + T->last_chains[c].len;
+  if (!pts_xy || total == 0) return PLV_OK;
+  std::vector<int2> hp((size_t)T->last_pts_extent);
+  PLV_HIP_CHECK(plv::memcpy_async(hp.data(), T->pts.p, hp.size() * sizeof(int2), hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
+  for (int c = 0; c < n; ++c) {
+    const FldChain &ch = T->last_chains[c];
+    if (ch.start < 0 || (size_t)ch.start + (size_t)ch.len > hp.size()) return PLV_E_DEVICE;
+    for (int q = 0; q < ch.len; ++q) pts_xy[2 * ((size_t)chain_ptr[c] + q)] = hp[(size_t)ch.start + q].x, pts_xy[2 * ((size_t)chain_ptr[c] + q) + 1] = hp[(size_t)ch.start + q].y;
+  }
   return PLV_OK;
 }
 

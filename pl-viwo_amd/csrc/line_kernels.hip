@@ -15,6 +15,10 @@
 //                    LDS latency, not HBM latency; the raster seed search tests 64 pixels per step.
 //   fld_fit_kernel   segment growing (incremental least-squares fit on exact integer sums), clamping,
 //                    orientation by side brightness: one lane per chain, chains are independent.
+//   fld_components_kernel / ccl_bbox_kernel / fld_walk_components_kernel / fld_chain_order_kernel / fld_fit_wave_kernel
+//                    the component-parallel detector (plv_line_walk_mode 2): the walk never leaves an 8-connected component of the
+//                    edge map, so every component is walked by a wave of its own on a bit map in LDS, the kept chains are put
+//                    into the order of their seeds, and every chain is fitted by a wave of its own.
 #include "line_kernels.hpp"
 
 #include "fld_fit_core.hpp"
@@ -315,9 +319,11 @@ template <bool IN_LDS>
 __global__ void __launch_bounds__(64) fld_walk_kernel(const uint8_t *__restrict__ map, int w, int h, int length_threshold,
                                                       uint8_t *__restrict__ gwork /* w*h scratch when !IN_LDS */,
                                                       int2 *__restrict__ pts, FldChain *__restrict__ chains, int chain_cap,
-                                                      int *__restrict__ counts /* [0] chains, [1] segment slots, [2] points */) {
+                                                      int *__restrict__ counts /* [0] chains, [1] segment slots, [2] points */,
+                                                      const int *__restrict__ gate /* nullable: run only when *gate != 0 */) {
   extern __shared__ uint8_t lmap[];
   const int lane = threadIdx.x;
+  if (gate && *gate == 0) return;  // (uniform) the component-parallel kernels have done the work
   const int npix = w * h;
   auto ld = [&](int i) -> int { return IN_LDS ? (int)lmap[i] : (int)gwork[i]; };
   auto st = [&](int i, uint8_t v) {
@@ -408,12 +414,364 @@ __global__ void __launch_bounds__(64) fld_walk_kernel(const uint8_t *__restrict_
   }
 }
 
+// ------------------------------------------------------------------------------------------ component-parallel chain walking
+// plv_line_walk_mode 2.  A chain only moves to non-zero 8-neighbours, so it stays inside one 8-connected component of the edge map,
+// and what one component consumes no other component can reach: the components are walked independently, one wave each, and the
+// detector's order (the raster order of the chain seeds) is restored afterwards (fld_chain_order_kernel).
+//
+// fld_components_kernel: the components that can hold a kept chain (length_threshold + 1 pixels or more: ccl_assign_kernel's argument),
+// out of the root list of ccl_roots_kernel; one workgroup.  Component k owns the points pts[pts_off, pts_off + cnt) (its kept chains
+// together cannot hold more points than it has pixels) and the chain records recs[rec_off, rec_off + cnt / min_px).  cnt[root]
+// becomes -(k + 1) for ccl_bbox_kernel; info: [0] components, [1] pixels of the largest, [2] 1 = more components than the root list
+// holds (nothing is listed: the caller's serial kernels run instead), [3] error word, [4] points owned, [5] chain records owned.
+__global__ void __launch_bounds__(1024) fld_components_kernel(int *__restrict__ cnt, const int *__restrict__ roots, const int *__restrict__ n_roots, int w,
+                                                              int min_px, FldComp *__restrict__ comps, int *__restrict__ info, int *__restrict__ counts) {
+  __shared__ int s_n[1024], s_pts[1024], s_rec[1024], s_max[1024];
+  const int t = threadIdx.x;
+  const int nr = *n_roots;
+  if (nr > CCL_ROOT_CAP) {  // (uniform)
+    if (t < 8) info[t] = t == 2 ? 1 : 0;
+    if (t < 4) counts[t] = 0;
+    return;
+  }
+  constexpr int PER = CCL_ROOT_CAP / 1024;
+  int root[PER], c[PER];
+  int n = 0, np = 0, nrec = 0, mx = 0;
+#pragma unroll
+  for (int q = 0; q < PER; ++q) {
+    const int j = t * PER + q;
+    root[q] = j < nr ? roots[j] : -1;
+    c[q] = root[q] >= 0 ? cnt[root[q]] : 0;
+    if (c[q] >= min_px) ++n, np += c[q], nrec += c[q] / min_px, mx = max(mx, c[q]);
+  }
+  s_n[t] = n, s_pts[t] = np, s_rec[t] = nrec, s_max[t] = mx;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {  // inclusive scans (and the maximum) over the threads
+    const int a = t >= off ? s_n[t - off] : 0, b = t >= off ? s_pts[t - off] : 0, d = t >= off ? s_rec[t - off] : 0, e = t >= off ? s_max[t - off] : 0;
+    __syncthreads();
+    s_n[t] += a, s_pts[t] += b, s_rec[t] += d, s_max[t] = max(s_max[t], e);
+    __syncthreads();
+  }
+  int k = s_n[t] - n, po = s_pts[t] - np, ro = s_rec[t] - nrec;
+#pragma unroll
+  for (int q = 0; q < PER; ++q) {
+    if (c[q] < min_px) continue;
+    FldComp cp;
+    cp.root = root[q], cp.cnt = c[q], cp.pts_off = po, cp.rec_off = ro;
+    cp.x0 = w, cp.x1 = -1, cp.y1 = -1, cp.n_rec = 0;
+    comps[k] = cp;
+    cnt[root[q]] = -(k + 1);
+    ++k, po += c[q], ro += c[q] / min_px;
+  }
+  if (t == 1023) info[0] = s_n[t], info[1] = s_max[t], info[2] = 0, info[3] = 0, info[4] = s_pts[t], info[5] = s_rec[t], info[6] = 0, info[7] = 0;
+  if (t < 4) counts[t] = 0;
+}
+// The bounding box of every listed component (its first row is the row of its root, the smallest index of the set).  A wave holds 64
+// consecutive pixels: the lanes of one component reduce their extremes among themselves and one of them goes to memory (blocks run
+// roughly in raster order, so without this every pixel of a new row would raise y1 at once); the boxes only grow, so a read that
+// already covers the wave's pixels spares the atomic.
+__global__ void __launch_bounds__(256) ccl_bbox_kernel(const int *__restrict__ L, int w, int n, const int *__restrict__ cnt, FldComp *__restrict__ comps) {
+  const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+  int k = -1;
+  if (i < n) {
+    const int r = L[i];
+    if (r >= 0) {
+      const int c = cnt[r];
+      if (c < 0) k = -c - 1;  // (a listed component)
+    }
+  }
+  const int y = i / w, x = i - y * w;
+  unsigned long long todo = __ballot(k >= 0);
+  while (todo != 0ull) {  // (uniform) one round per component among the wave's pixels
+    const int leader = __ffsll((long long)todo) - 1;
+    const int k0 = __shfl(k, leader, 64);
+    const bool mine = k == k0;
+    int mnx = mine ? x : 0x7fffffff, mxx = mine ? x : -1, mxy = mine ? y : -1;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      mnx = min(mnx, __shfl_xor(mnx, off, 64));
+      mxx = max(mxx, __shfl_xor(mxx, off, 64));
+      mxy = max(mxy, __shfl_xor(mxy, off, 64));
+    }
+    if (lane == leader) {
+      FldComp *cp = comps + k0;
+      if (mnx < __atomic_load_n(&cp->x0, __ATOMIC_RELAXED)) atomicMin(&cp->x0, mnx);
+      if (mxx > __atomic_load_n(&cp->x1, __ATOMIC_RELAXED)) atomicMax(&cp->x1, mxx);
+      if (mxy > __atomic_load_n(&cp->y1, __ATOMIC_RELAXED)) atomicMax(&cp->y1, mxy);
+    }
+    todo &= ~__ballot(mine);
+  }
+}
+
+// One wave per component: FastLineDetectorImpl::lineDetection's seed loop + getPointChain restricted to the component's pixels — the
+// scalar sequence of fld_walk_kernel (all lanes run the same walk), on the component's alive map as a BIT map in LDS:
+// the rows of its bounding box, 64 pixels per word (four waves fill it, eight loads in flight each; the other three leave at the one
+// barrier behind the fill).  One wave walks, with no barrier in the loop: every lane runs the same walk and stores the same words
+// into the map, so a lane only ever reads what it has written itself.  The points leave 64 at a time — lane q keeps the q-th point
+// of the current block of 64 in a register, the wave stores a block with one coalesced instruction when it is full or the chain
+// ends — so that a step never has a store to HBM in flight to wait for.  Every loop is bounded: a step or a seed consumes a pixel, the
+// walk carries the component's pixel count as its budget and leaves through the error word should it ever be exceeded.
+__global__ void __launch_bounds__(256) fld_walk_components_kernel(const int *__restrict__ L, int w, int h, int length_threshold,
+                                                                 FldComp *__restrict__ comps, int2 *__restrict__ pts, FldRec *__restrict__ recs,
+                                                                 int *__restrict__ info, int lds_words) {
+  extern __shared__ unsigned long long bits[];
+  const int k = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (k >= info[0]) return;  // (uniform)
+  FldComp cp = comps[k];
+  cp.root = __builtin_amdgcn_readfirstlane(cp.root), cp.cnt = __builtin_amdgcn_readfirstlane(cp.cnt);
+  cp.pts_off = __builtin_amdgcn_readfirstlane(cp.pts_off), cp.rec_off = __builtin_amdgcn_readfirstlane(cp.rec_off);
+  const int x0 = __builtin_amdgcn_readfirstlane(cp.x0), x1 = __builtin_amdgcn_readfirstlane(cp.x1), y0 = cp.root / w,
+            y1 = __builtin_amdgcn_readfirstlane(cp.y1);
+  const int wx0 = x0 >> 6, nW = (x1 >> 6) - wx0 + 1, nrows = y1 - y0 + 1, NW = nW * nrows;
+  if (x0 > x1 || y1 < y0 || x1 >= w || y1 >= h || NW > lds_words) {  // (cannot happen: the box of a component lies inside the image)
+    if (threadIdx.x == 0) atomicOr(info + 3, 2);
+    return;
+  }
+  for (int q0 = wave * 8; q0 < NW; q0 += 32) {
+    bool mine[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int q = min(q0 + u, NW - 1), r = q / nW, c = q - r * nW;
+      const int x = ((wx0 + c) << 6) + lane;
+      mine[u] = x < w && L[(size_t)(y0 + r) * w + min(x, w - 1)] == cp.root;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const unsigned long long m = __ballot(mine[u]);
+      if (lane == 0 && q0 + u < NW) bits[q0 + u] = m;
+    }
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  // the reference's neighbour order, dx = {1, 0, -1, -1, -1, 0, 1, 1}, dy = {1, 1, 1, 0, -1, -1, -1, 0}, as value + 1 per nibble
+  const unsigned kDx = 0x22100012u, kDy = 0x10001222u;
+  const int nb_dx = (int)((kDx >> (4 * (lane & 7))) & 3u) - 1, nb_dy = (int)((kDy >> (4 * (lane & 7))) & 3u) - 1;
+  const int rec_cap = cp.cnt / (length_threshold + 1);
+  int budget = cp.cnt;  // pixels left to consume
+  int n_pts = 0, n_rec = 0, scan = 0;
+  bool over = false;
+  while (scan < NW) {
+    // raster search for the next seed inside the box: 64 words at a time (pixels in front of the last seed are consumed for good)
+    const int kk = scan + lane;
+    const unsigned long long wv = kk < NW ? bits[kk] : 0ull;
+    const unsigned long long m = __ballot(wv != 0ull);
+    if (m == 0) {
+      scan += 64;
+      continue;
+    }
+    const int first = __ffsll((long long)m) - 1;
+    scan += first;
+    const unsigned long long word = __shfl(wv, first, 64);
+    const int row = scan / nW, col = scan - row * nW;
+    int x = ((wx0 + col) << 6) + __ffsll((long long)word) - 1, y = y0 + row;
+    if (--budget < 0) {
+      over = true;
+      break;
+    }
+    const int start = n_pts;
+    bits[scan] = word & (word - 1ull);  // (the seed is the lowest set bit of its word)
+    int2 held = make_int2(x, y);        // lane q: point start + 64 * block + q of this chain
+    int n_held = 1;                     // points of the current block
+    ++n_pts;
+    const int seed = y * w + x;
+    float direction = 0.0f;
+    int step = 0;
+    for (;;) {
+      // the eight neighbours, one per lane (lane & 7 = the neighbour's index: one load for all of them); the ballot is the
+      // neighbour mask every lane decides on
+      unsigned nb;
+      {
+        const int ci = x + nb_dx, ri = y + nb_dy;
+        const bool inb = ri >= y0 && ri <= y1 && ci >= x0 && ci <= x1;  // (no pixel of the component lies outside its box)
+        const int cc = min(max(ci, x0), x1), rc = min(max(ri, y0), y1);
+        const unsigned long long v = bits[(rc - y0) * nW + (cc >> 6) - wx0];
+        nb = (unsigned)__ballot(inb && ((v >> (cc & 63)) & 1ull) != 0ull) & 0xffu;
+      }
+      bool valid[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) valid[i] = ((nb >> i) & 1u) != 0u;
+      int pick = -1;
+      if (step == 0) {
+        pick = nb != 0u ? __ffs((int)nb) - 1 : -1;  // first valid neighbour
+        if (pick < 0) break;
+        direction = pick > 4 ? (float)(pick - 8) : (float)pick;
+      } else {
+        float min_dir_diff = 7.0f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const float curr = i > 4 ? (float)(i - 8) : (float)i;
+          float diff = fabsf(curr - direction);
+          diff = diff > 4.0f ? 8.0f - diff : diff;
+          const bool take = valid[i] && diff <= min_dir_diff;  // ties: the later neighbour wins
+          min_dir_diff = take ? diff : min_dir_diff;
+          pick = take ? i : pick;
+        }
+        if (pick < 0 || !(min_dir_diff < 2.0f)) break;
+        const int cdir = pick > 4 ? pick - 8 : pick;
+        // (the oracle rounds the product and the sum separately: never a fused multiply-add)
+        direction = __fdiv_rn(__fadd_rn(__fmul_rn(direction, (float)step), (float)cdir), (float)(step + 1));
+      }
+      x += (int)((kDx >> (4 * pick)) & 3u) - 1;
+      y += (int)((kDy >> (4 * pick)) & 3u) - 1;
+      if (--budget < 0) {
+        over = true;
+        break;
+      }
+      {
+        const int at = (y - y0) * nW + (x >> 6) - wx0;
+        bits[at] = bits[at] & ~(1ull << (x & 63));
+      }
+      if (n_held == 64) {  // (uniform) a full block: points n_pts - 64 .. n_pts - 1
+        pts[cp.pts_off + n_pts - 64 + lane] = held;
+        n_held = 0;
+      }
+      if (lane == n_held) held = make_int2(x, y);
+      ++n_held;
+      ++n_pts;
+      ++step;
+    }
+    if (over) break;
+    if (lane < n_held) pts[cp.pts_off + n_pts - n_held + lane] = held;  // the last block (a chain too short is overwritten by the next)
+    const int len = n_pts - start;
+    if (len >= length_threshold + 1) {
+      if (n_rec >= rec_cap) {  // (cannot happen: kept chains are disjoint sets of length_threshold + 1 pixels or more)
+        over = true;
+        break;
+      }
+      if (lane == 0) recs[cp.rec_off + n_rec] = FldRec{seed, cp.pts_off + start, len};
+      ++n_rec;
+    } else {
+      n_pts = start;  // too short: forget the points
+    }
+  }
+  if (lane == 0) {
+    comps[k].n_rec = over ? 0 : n_rec;
+    if (over) atomicOr(info + 3, 1);
+  }
+}
+
+// The kept chains of all components in the raster order of their seeds (the detector's output order) as the chain table of
+// fld_walk_kernel: start, len, slot (slots: the scan of len / length_threshold + 1), counts[0..2] as that kernel fills them, counts[3]
+// = the kept chains before the table's capacity cut them (the first chain_cap in seed order stay, as the serial kernel keeps them).
+// One workgroup: the records are gathered (gath), every record counts the seeds in front of it, tile by tile through LDS — seeds are
+// pixel indices, so the ranks are distinct — and the slots are scanned in ranked order.
+__global__ void __launch_bounds__(1024) fld_chain_order_kernel(const FldComp *__restrict__ comps, const FldRec *__restrict__ recs, FldRec *__restrict__ gath,
+                                                               int length_threshold, FldChain *__restrict__ chains, int chain_cap,
+                                                               int *__restrict__ counts, int *__restrict__ info) {
+  __shared__ int s_a[1024], s_b[1024], s_seed[1024];
+  const int t = threadIdx.x;
+  const int nc = info[0];
+  if (info[2] != 0) return;  // (uniform) nothing was listed: the serial kernels fill the table
+  constexpr int PER = CCL_ROOT_CAP / 1024;
+  int nrec[PER], mine = 0;
+#pragma unroll
+  for (int q = 0; q < PER; ++q) {
+    const int k = t * PER + q;
+    nrec[q] = k < nc ? comps[k].n_rec : 0;
+    mine += nrec[q];
+  }
+  s_a[t] = mine;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    const int a = t >= off ? s_a[t - off] : 0;
+    __syncthreads();
+    s_a[t] += a;
+    __syncthreads();
+  }
+  const int n = s_a[1023];
+  int at = s_a[t] - mine;
+#pragma unroll
+  for (int q = 0; q < PER; ++q) {
+    const int k = t * PER + q;
+    if (nrec[q] == 0) continue;
+    const int ro = comps[k].rec_off;
+    for (int j = 0; j < nrec[q]; ++j) gath[at++] = recs[ro + j];
+  }
+  __syncthreads();  // (the workgroup's stores to gath are visible to it from here on)
+  const int n_keep = min(n, chain_cap);
+  // ranks by seed; chains[rank].slot holds the chain's slots until the scan below
+  for (int base = 0; base < n; base += 1024) {
+    const int j = base + t;
+    const FldRec me = j < n ? gath[j] : FldRec{0, 0, 0};
+    int rank = 0;
+    for (int tb = 0; tb < n; tb += 1024) {
+      __syncthreads();
+      s_seed[t] = tb + t < n ? gath[tb + t].seed : 0x7fffffff;
+      __syncthreads();
+      const int m = min(1024, n - tb);
+      for (int q = 0; q < m; ++q) rank += s_seed[q] < me.seed;
+    }
+    if (j < n && rank < n_keep) chains[rank] = FldChain{me.start, me.len, me.len / length_threshold + 1};
+  }
+  __syncthreads();
+  // exclusive scan of the slots (and the sum of the lengths) over the ranked table, 1024 entries per round with a running carry
+  int carry_slot = 0, carry_len = 0;
+  for (int base = 0; base < n_keep; base += 1024) {
+    const int j = base + t;
+    const int sl = j < n_keep ? chains[j].slot : 0, ln = j < n_keep ? chains[j].len : 0;
+    __syncthreads();
+    s_a[t] = sl, s_b[t] = ln;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+      const int a = t >= off ? s_a[t - off] : 0, b = t >= off ? s_b[t - off] : 0;
+      __syncthreads();
+      s_a[t] += a, s_b[t] += b;
+      __syncthreads();
+    }
+    if (j < n_keep) chains[j].slot = carry_slot + s_a[t] - sl;
+    carry_slot += s_a[1023], carry_len += s_b[1023];
+  }
+  if (t == 0) counts[0] = n_keep, counts[1] = carry_slot, counts[2] = carry_len, counts[3] = n;
+}
+
+// ------------------------------------------------------------------------------------------ segment growing, one wave per chain
+// Phase 1: the lanes take the chord test of fit_chain (chord_is_line) for 64 starts of the chain at a time; the verdicts are a bit
+// vector in LDS (a window of FIT_WIN starts, refilled when the growth leaves it: a chain may be as long as its component).
+// Phase 2: fit_chain's growth, unchanged, reading the verdicts — every lane runs the same scalar sequence (uniform control flow,
+// broadcast loads), lane 0 stores.
+#define FIT_WIN 8192
+struct WaveVerdict {
+  unsigned long long *bits;  // [FIT_WIN / 64]; every lane stores the same words, so a lane reads what it has written itself
+  const int2 *P;
+  int n_starts, length_threshold, base, lane;
+  float distance_threshold;
+  __device__ void fill(int from) {
+    base = from;
+    const int end = min(n_starts, base + FIT_WIN);
+    for (int i0 = base; i0 < end; i0 += 64) {
+      const int i = i0 + lane;
+      const unsigned long long m = __ballot(i < end && chord_is_line(P, i, length_threshold, distance_threshold));
+      bits[(i0 - base) >> 6] = m;
+    }
+  }
+  __device__ bool operator()(int i) {
+    if (i >= base + FIT_WIN) fill(i);  // (uniform: every lane asks for the same i)
+    const int o = i - base;
+    return ((bits[o >> 6] >> (o & 63)) & 1ull) != 0ull;
+  }
+};
+__global__ void __launch_bounds__(64) fld_fit_wave_kernel(const uint8_t *__restrict__ src, int w, int h, int length_threshold, float distance_threshold,
+                                                          const int2 *__restrict__ pts, const FldChain *__restrict__ chains, const int *__restrict__ counts,
+                                                          const int *__restrict__ info, float4 *__restrict__ segs, int *__restrict__ seg_count) {
+  __shared__ unsigned long long vbits[FIT_WIN / 64];
+  const int c = blockIdx.x, lane = threadIdx.x;
+  if (info[2] != 0 || c >= counts[0]) return;  // (nothing listed: fld_fit_kernel fits the serial kernel's chains)
+  const FldChain ch = chains[c];
+  WaveVerdict V{vbits, pts + ch.start, ch.len - length_threshold, length_threshold, 0, lane, distance_threshold};
+  V.fill(0);
+  // (every lane stores the same segment to the same slot: one store of the wave)
+  const int ns = fit_chain_with(src, w, h, length_threshold, distance_threshold, pts + ch.start, ch.len, segs + ch.slot, V);
+  if (lane == 0) seg_count[c] = ns;
+}
+
 // ------------------------------------------------------------------------------------------ segment growing
 __global__ void __launch_bounds__(64) fld_fit_kernel(const uint8_t *__restrict__ src, int w, int h, int length_threshold,
                                                      float distance_threshold, const int2 *__restrict__ pts,
                                                      const FldChain *__restrict__ chains, const int *__restrict__ counts,
-                                                     float4 *__restrict__ segs, int *__restrict__ seg_count) {
+                                                     float4 *__restrict__ segs, int *__restrict__ seg_count,
+                                                     const int *__restrict__ gate /* nullable: run only when *gate != 0 */) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gate && *gate == 0) return;
   if (c >= counts[0]) return;
   const FldChain ch = chains[c];
   seg_count[c] = fit_chain(src, w, h, length_threshold, distance_threshold, pts + ch.start, ch.len, segs + ch.slot);
@@ -468,26 +826,74 @@ int line_label_parts() { return CCL_PARTS; }
 size_t line_label_roots_bytes() { return (CCL_ROOT_CAP + 4) * sizeof(int); }
 
 // stage 2 (device variant): chain walking by one wave
-int launch_line_walk(plv_ctx *ctx, int w, int h, const FldParams &fp, FldBuffers &b) {
+int launch_line_walk(plv_ctx *ctx, int w, int h, const FldParams &fp, FldBuffers &b, const int *gate) {
   ProfScope ps(ctx->prof, "fld_walk_kernel", ctx->stream);
   const size_t need = (size_t)w * h;
   if (need <= 150 * 1024) {
     PLV_HIP_CHECK(ensure_dyn_smem((const void *)fld_walk_kernel<true>, (int)need));
     hipLaunchKernelGGL(fld_walk_kernel<true>, dim3(1), dim3(64), need, ctx->stream, b.map, w, h, fp.length_threshold, b.work, b.pts,
-                       b.chains, b.chain_cap, b.counts);
+                       b.chains, b.chain_cap, b.counts, gate);
   } else {
     hipLaunchKernelGGL(fld_walk_kernel<false>, dim3(1), dim3(64), 0, ctx->stream, b.map, w, h, fp.length_threshold, b.work, b.pts,
-                       b.chains, b.chain_cap, b.counts);
+                       b.chains, b.chain_cap, b.counts, gate);
   }
   PLV_HIP_CHECK(hipGetLastError());
   return PLV_OK;
 }
 
 // stage 3: one lane per chain
-int launch_line_fit(plv_ctx *ctx, int w, int h, const FldParams &fp, FldBuffers &b) {
+int launch_line_fit(plv_ctx *ctx, int w, int h, const FldParams &fp, FldBuffers &b, const int *gate) {
   ProfScope ps(ctx->prof, "fld_fit_kernel", ctx->stream);
   hipLaunchKernelGGL(fld_fit_kernel, dim3(cdiv(b.chain_cap, 64)), dim3(64), 0, ctx->stream, b.half, w, h, fp.length_threshold,
-                     fp.distance_threshold, b.pts, b.chains, b.counts, b.segs, b.seg_count);
+                     fp.distance_threshold, b.pts, b.chains, b.counts, b.segs, b.seg_count, gate);
+  PLV_HIP_CHECK(hipGetLastError());
+  return PLV_OK;
+}
+
+// stages 2 and 3, component-parallel (plv_line_walk_mode 2), behind launch_line_edges with the label buffers set: the label kernels
+// up to the root list (the parts of ccl_assign_kernel / ccl_flatten_kernel are the host stage's), the components, their boxes, one wave
+// per component, the chains in seed order, one wave per chain.  With more components than the root list holds the device says so in
+// b.walk_info[2], these kernels leave at once and the serial kernels, launched behind them with that word as their gate, do the work.
+size_t line_walk_lds_bytes(int w, int h) { return (size_t)h * (size_t)((w + 63) / 64) * sizeof(unsigned long long); }
+int line_walk_components_cap() { return CCL_ROOT_CAP; }
+int launch_line_walk_components(plv_ctx *ctx, int w, int h, const FldParams &fp, FldBuffers &b) {
+  hipStream_t st = ctx->stream;
+  const int n = w * h, min_px = fp.length_threshold + 1;
+  const size_t lds = line_walk_lds_bytes(w, h);
+  if (lds > kLineWalkLdsMax || !b.lab_work || !b.comps) return PLV_E_BADARG;  // (the caller checks: detect() falls back before it gets here)
+  {
+    ProfScope ps(ctx->prof, "ccl_boundary_kernel", st);
+    hipLaunchKernelGGL(ccl_boundary_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, b.lab_work, w, h, b.lab_roots + CCL_ROOT_CAP);
+  }
+  {
+    ProfScope ps(ctx->prof, "ccl_roots_kernel", st);
+    hipLaunchKernelGGL(ccl_roots_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, b.lab_work, n, b.lab_cnt, b.lab_roots, b.lab_roots + CCL_ROOT_CAP);
+  }
+  {
+    ProfScope ps(ctx->prof, "fld_components_kernel", st);
+    hipLaunchKernelGGL(fld_components_kernel, dim3(1), dim3(1024), 0, st, b.lab_cnt, b.lab_roots, b.lab_roots + CCL_ROOT_CAP, w, min_px, b.comps, b.walk_info,
+                       b.counts);
+  }
+  {
+    ProfScope ps(ctx->prof, "ccl_bbox_kernel", st);
+    hipLaunchKernelGGL(ccl_bbox_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, b.lab_work, w, n, b.lab_cnt, b.comps);
+  }
+  {
+    // (a listed component has min_px pixels or more: at most n / min_px of them, and no more than the root list holds)
+    ProfScope ps(ctx->prof, "fld_walk_components_kernel", st);
+    hipLaunchKernelGGL(fld_walk_components_kernel, dim3(std::max(1, std::min(CCL_ROOT_CAP, n / min_px))), dim3(256), lds, st, b.lab_work, w, h,
+                       fp.length_threshold, b.comps, b.pts, b.recs, b.walk_info, (int)(lds / sizeof(unsigned long long)));
+  }
+  {
+    ProfScope ps(ctx->prof, "fld_chain_order_kernel", st);
+    hipLaunchKernelGGL(fld_chain_order_kernel, dim3(1), dim3(1024), 0, st, b.comps, b.recs, b.recs_sorted, fp.length_threshold, b.chains, b.chain_cap, b.counts,
+                       b.walk_info);
+  }
+  {
+    ProfScope ps(ctx->prof, "fld_fit_wave_kernel", st);
+    hipLaunchKernelGGL(fld_fit_wave_kernel, dim3(b.chain_cap), dim3(64), 0, st, b.half, w, h, fp.length_threshold, fp.distance_threshold, b.pts, b.chains,
+                       b.counts, b.walk_info, b.segs, b.seg_count);
+  }
   PLV_HIP_CHECK(hipGetLastError());
   return PLV_OK;
 }

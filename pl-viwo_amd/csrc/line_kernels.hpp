@@ -9,6 +9,14 @@ namespace plv {
 struct FldChain {
   int start, len, slot;  // points [start, start+len) of the chain buffer; first output slot
 };
+struct FldComp {  // a component of the edge map that can hold a kept chain (plv_line_walk_mode 2)
+  int root, cnt, pts_off, rec_off;  // root label, pixels, first point owned, first chain record owned
+  int x0, x1, y1, n_rec;            // bounding box (its first row is the root's), chains kept
+};
+struct FldRec {
+  int seed, start, len;  // a kept chain of a component: raster index of its seed, its points
+};
+const size_t kLineWalkLdsMax = 64 * 1024;  // the component walk's bit map of the half-resolution image must fit (1 bit per pixel)
 struct FldParams {
   int length_threshold;      // 20   REF: TrackLSD.h:269
   float distance_threshold;  // sqrt(2)   :270
@@ -29,6 +37,11 @@ struct FldBuffers {
   // (nullable, host-visible) the parts' pixels in raster order, per run of 256 pixels: see ccl_flatten_kernel
   uint8_t *blk_sorted = nullptr;        // [256 * ceil(w*h / 256)]
   unsigned short *blk_bins = nullptr;   // [ceil(w*h / 256)][line_label_parts() + 1]
+  // component-parallel walk (plv_line_walk_mode 2; null otherwise)
+  FldComp *comps = nullptr;        // [line_walk_components_cap()]
+  FldRec *recs = nullptr;          // [w*h / (length_threshold + 1) + 1] chain records, by component
+  FldRec *recs_sorted = nullptr;   // [same] gathered
+  int *walk_info = nullptr;        // [8] see fld_components_kernel
 };
 
 // d_hist: d_img is the RAW image and d_hist its histogram (the kernel equalises on the fly: canny_kernel); null: d_img is the equalised image
@@ -37,7 +50,11 @@ int launch_line_edges(plv_ctx *ctx, const uint8_t *d_img, int W, int H, const Fl
 int launch_line_labels(plv_ctx *ctx, int w, int h, FldBuffers &b, hipStream_t st, int length_threshold);
 int line_label_parts();         // parts launch_line_labels writes (the largest components first: 1 .. 8, then 8 hashed ones)
 size_t line_label_roots_bytes();
-int launch_line_walk(plv_ctx *ctx, int w, int h, const FldParams &fp, FldBuffers &b);
-int launch_line_fit(plv_ctx *ctx, int w, int h, const FldParams &fp, FldBuffers &b);
+// gate (nullable, device): the kernel runs only when *gate != 0 (the fallback of the component-parallel walk)
+int launch_line_walk(plv_ctx *ctx, int w, int h, const FldParams &fp, FldBuffers &b, const int *gate = nullptr);
+int launch_line_fit(plv_ctx *ctx, int w, int h, const FldParams &fp, FldBuffers &b, const int *gate = nullptr);
+size_t line_walk_lds_bytes(int w, int h);
+int line_walk_components_cap();
+int launch_line_walk_components(plv_ctx *ctx, int w, int h, const FldParams &fp, FldBuffers &b);
 
 }  // namespace plv
