@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "plv_ctx.hpp"
+#include "so3.hpp"
 #include "update_state.hpp"
 
 namespace plv {
@@ -97,56 +98,16 @@ struct Align {
   double R[9], t[3], s, qinv[4];  // qinv = Inv(rot_2_quat(R))
 };
 
-__device__ void quat_2_rot(const double *q, double *R) {  // quat_ops.h:152-157
+// quat_2_Rot as the evaluator has always formed it, on the device and on the host: each entry as (a or 0) - 2 q4 [q x] + 2 q q^T.  so3.hpp's
+// quat_2_Rot scales whole matrices instead ((2 q4^2 - 1) * I has -0 off the diagonal), and the two differ in the sign of a zero entry,
+// e.g. for q = (0, -1, 0, 0) in entry (1, 0): not merged.
+__host__ __device__ inline void quat_2_rot(const double *q, double *R) {  // REF: quat_ops.h:152-157
   const double a = 2 * q[3] * q[3] - 1;
   const double sk[9] = {0, -q[2], q[1], q[2], 0, -q[0], -q[1], q[0], 0};
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
     for (int c = 0; c < 3; ++c) R[3 * r + c] = (r == c ? a : 0.0) - 2 * q[3] * sk[3 * r + c] + 2 * q[r] * q[c];
-}
-
-__device__ void quat_mul(const double *q, const double *p, double *o) {  // quat_ops.h:180-195 (the code's L matrix: q4 I - [q x])
-  double r[4];
-  r[0] = q[3] * p[0] + q[2] * p[1] - q[1] * p[2] + q[0] * p[3];
-  r[1] = -q[2] * p[0] + q[3] * p[1] + q[0] * p[2] + q[1] * p[3];
-  r[2] = q[1] * p[0] - q[0] * p[1] + q[3] * p[2] + q[2] * p[3];
-  r[3] = -q[0] * p[0] - q[1] * p[1] - q[2] * p[2] + q[3] * p[3];
-  if (r[3] < 0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = -r[i];
-  }
-  const double nrm = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) o[i] = r[i] / nrm;
-}
-
-__device__ void log_so3_dev(const double *R, double *w) {  // quat_ops.h:273-313
-  const double R11 = R[0], R12 = R[1], R13 = R[2], R21 = R[3], R22 = R[4], R23 = R[5], R31 = R[6], R32 = R[7], R33 = R[8];
-  const double tr = R11 + R22 + R33;
-  if (tr + 1.0 < 1e-10) {
-    double k;
-    if (fabs(R33 + 1.0) > 1e-5) {
-      k = M_PI / sqrt(2.0 + 2.0 * R33);
-      w[0] = k * R13, w[1] = k * R23, w[2] = k * (1.0 + R33);
-    } else if (fabs(R22 + 1.0) > 1e-5) {
-      k = M_PI / sqrt(2.0 + 2.0 * R22);
-      w[0] = k * R12, w[1] = k * (1.0 + R22), w[2] = k * R32;
-    } else {
-      k = M_PI / sqrt(2.0 + 2.0 * R11);
-      w[0] = k * (1.0 + R11), w[1] = k * R21, w[2] = k * R31;
-    }
-    return;
-  }
-  double mag;
-  const double tr_3 = tr - 3.0;
-  if (tr_3 < -1e-7) {
-    const double theta = acos((tr - 1.0) / 2.0);
-    mag = theta / (2.0 * sin(theta));
-  } else {
-    mag = 0.5 - tr_3 / 12.0;
-  }
-  w[0] = mag * (R32 - R23), w[1] = mag * (R13 - R31), w[2] = mag * (R21 - R12);
 }
 
 // ResultTrajectory ctor :72-82 (the aligned estimate) + calculate_ate :91-115 (errors), thread per pose.  TWO_D is calculate_ate_2d
@@ -158,21 +119,21 @@ __global__ void __launch_bounds__(256) traj_ate_kernel(int n, const double *__re
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const double *e = est + 7 * (size_t)i, *g = gt + 7 * (size_t)i;
-  double p[3], q[4];
+  double p[3];
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     // s * R * p + t: Eigen evaluates (s * R) * p
     p[r] = (A.s * A.R[3 * r] * e[0] + A.s * A.R[3 * r + 1] * e[1] + A.s * A.R[3 * r + 2] * e[2]) + A.t[r];
   }
-  quat_mul(e + 3, A.qinv, q);
-  double Re[9], Rg[9], eR[9], w[3];
-  quat_2_rot(q, Re);
+  const Q4 q = quat_multiply(ldQ(e + 3), ldQ(A.qinv));
+  double Re[9], Rg[9], eR[9];
+  quat_2_rot(q.q, Re);
   quat_2_rot(g + 3, Rg);
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
     for (int c = 0; c < 3; ++c) eR[3 * r + c] = Re[r] * Rg[c] + Re[3 + r] * Rg[3 + c] + Re[6 + r] * Rg[6 + c];  // Re^T Rg
-  log_so3_dev(eR, w);
+  const V3 w = log_so3(ldM(eR));
   const double dx = g[0] - p[0], dy = g[1] - p[1], dz = g[2] - p[2];
   if constexpr (TWO_D) {
     ori_err[i] = 180.0 / M_PI * w[2];
@@ -256,7 +217,7 @@ __global__ void __launch_bounds__(256) traj_rpe_kernel(int n, int n_seg, const d
     tm[r] = (G1[3 * r] * m2[0] + G1[3 * r + 1] * m2[1] + G1[3 * r + 2] * m2[2]) + -(G1[3 * r] * m1[0] + G1[3 * r + 1] * m1[1] + G1[3 * r + 2] * m1[2]);
   }
   // T_error_in_c2 = Inv_se3(T_m1_m2) T_c1_c2 (:213), then into the world by the end pose's rotation Q2^T (:215-222)
-  double Re[9], te[3], RQ[9], Rw[9], tw[3], w[3];
+  double Re[9], te[3], RQ[9], Rw[9], tw[3];
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
 #pragma unroll
@@ -273,7 +234,7 @@ __global__ void __launch_bounds__(256) traj_rpe_kernel(int n, int n_seg, const d
     for (int c = 0; c < 3; ++c) Rw[3 * r + c] = Q2[r] * RQ[c] + Q2[3 + r] * RQ[3 + c] + Q2[6 + r] * RQ[6 + c];  // Q2^T (Re Q2)
     tw[r] = Q2[r] * te[0] + Q2[3 + r] * te[1] + Q2[6 + r] * te[2];
   }
-  log_so3_dev(Rw, w);
+  const V3 w = log_so3(ldM(Rw));
   pos_err[k] = sqrt(tw[0] * tw[0] + tw[1] * tw[1] + tw[2] * tw[2]);
   ori_err[k] = 180.0 / M_PI * sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
 }
@@ -302,14 +263,14 @@ __global__ void __launch_bounds__(256) traj_nees_kernel(int n, const double *__r
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const double *e = est + 7 * (size_t)i, *g = gt_in_est + 7 * (size_t)i;
-  double Rg[9], Re[9], eR[9], w[3];
+  double Rg[9], Re[9], eR[9];
   quat_2_rot(g + 3, Rg);
   quat_2_rot(e + 3, Re);
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
     for (int c = 0; c < 3; ++c) eR[3 * r + c] = Rg[3 * r] * Re[3 * c] + Rg[3 * r + 1] * Re[3 * c + 1] + Rg[3 * r + 2] * Re[3 * c + 2];  // Rg Re^T
-  log_so3_dev(eR, w);
+  const V3 w = log_so3(ldM(eR));
   const double eo[3] = {-w[0], -w[1], -w[2]}, ep[3] = {g[0] - e[0], g[1] - e[1], g[2] - e[2]};
   double no = quad_form_inv3(cov_ori + 9 * (size_t)i, eo), np = quad_form_inv3(cov_pos + 9 * (size_t)i, ep);
   if (isnan(no) || isnan(np)) no = np = NAN;
@@ -318,43 +279,6 @@ __global__ void __launch_bounds__(256) traj_nees_kernel(int n, const double *__r
 }
 
 // ---------------------------------------------------------------------------------------- host 3x3 helpers
-void h_quat_2_rot(const double *q, double *R) {
-  const double a = 2 * q[3] * q[3] - 1;
-  const double sk[9] = {0, -q[2], q[1], q[2], 0, -q[0], -q[1], q[0], 0};
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) R[3 * r + c] = (r == c ? a : 0.0) - 2 * q[3] * sk[3 * r + c] + 2 * q[r] * q[c];
-}
-
-void h_rot_2_quat(const double *rot, double *q) {  // quat_ops.h:88-120
-  auto R = [&](int r, int c) { return rot[3 * r + c]; };
-  const double T = R(0, 0) + R(1, 1) + R(2, 2);
-  if (R(0, 0) >= T && R(0, 0) >= R(1, 1) && R(0, 0) >= R(2, 2)) {
-    q[0] = std::sqrt((1 + 2 * R(0, 0) - T) / 4);
-    q[1] = (1 / (4 * q[0])) * (R(0, 1) + R(1, 0));
-    q[2] = (1 / (4 * q[0])) * (R(0, 2) + R(2, 0));
-    q[3] = (1 / (4 * q[0])) * (R(1, 2) - R(2, 1));
-  } else if (R(1, 1) >= T && R(1, 1) >= R(0, 0) && R(1, 1) >= R(2, 2)) {
-    q[1] = std::sqrt((1 + 2 * R(1, 1) - T) / 4);
-    q[0] = (1 / (4 * q[1])) * (R(0, 1) + R(1, 0));
-    q[2] = (1 / (4 * q[1])) * (R(1, 2) + R(2, 1));
-    q[3] = (1 / (4 * q[1])) * (R(2, 0) - R(0, 2));
-  } else if (R(2, 2) >= T && R(2, 2) >= R(0, 0) && R(2, 2) >= R(1, 1)) {
-    q[2] = std::sqrt((1 + 2 * R(2, 2) - T) / 4);
-    q[0] = (1 / (4 * q[2])) * (R(0, 2) + R(2, 0));
-    q[1] = (1 / (4 * q[2])) * (R(1, 2) + R(2, 1));
-    q[3] = (1 / (4 * q[2])) * (R(0, 1) - R(1, 0));
-  } else {
-    q[3] = std::sqrt((1 + T) / 4);
-    q[0] = (1 / (4 * q[3])) * (R(1, 2) - R(2, 1));
-    q[1] = (1 / (4 * q[3])) * (R(2, 0) - R(0, 2));
-    q[2] = (1 / (4 * q[3])) * (R(0, 1) - R(1, 0));
-  }
-  if (q[3] < 0)
-    for (int i = 0; i < 4; ++i) q[i] = -q[i];
-  const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  for (int i = 0; i < 4; ++i) q[i] /= n;
-}
-
 double det3(const double *a) {
   return a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]);
 }
@@ -567,8 +491,8 @@ static int device_align(plv_ctx *ctx, int method, int n, const double *d_est, co
   *s = 1;
   auto single = [&](bool yaw) {  // align_posyaw_single / align_se3_single
     double g[9], e[9];
-    h_quat_2_rot(h_gt + 3, g);
-    h_quat_2_rot(h_est + 3, e);
+    quat_2_rot(h_gt + 3, g);
+    quat_2_rot(h_est + 3, e);
     // g_rot = quat_2_Rot(q_gt)^T, est_rot = quat_2_Rot(q_es)^T
     if (yaw) {
       double CR[9];  // est_rot * g_rot^T = Re^T Rg
@@ -665,8 +589,7 @@ static int align_on_device(plv_ctx *ctx, int method, bool two_d, int n, const do
   PLV_HIP_CHECK(plv::memcpy_async(d->to, to, bytes, hipMemcpyHostToDevice, ctx->stream));
   *A = Align{};
   TRY(device_align(ctx, method, n, d->from, d->to, from, to, n_aligned, A->R, A->t, &A->s));
-  double q[4];
-  h_rot_2_quat(A->R, q);
+  const Q4 q = rot_2_quat(ldM(A->R));
   A->qinv[0] = -q[0], A->qinv[1] = -q[1], A->qinv[2] = -q[2], A->qinv[3] = q[3];
   {
     ProfScope ps(ctx->prof, "traj_ate_kernel", ctx->stream);

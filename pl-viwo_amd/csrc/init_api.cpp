@@ -3,7 +3,6 @@
 //   REF: PL-VIWO/src/init/imu/I_Initializer.cpp:44-150, PL-VIWO/src/init/imu_wheel/IW_Initializer.cpp:44-690,
 //        PL-VIWO/src/init/Initializer.cpp:93-113 (caller), open_vins/ov_core/src/utils/quat_ops.h.
 #include <algorithm>
-#include <array>
 #include <cmath>
 #include <complex>
 #include <cstring>
@@ -11,116 +10,54 @@
 
 #include "../../include/plviwo.h"
 #include "plv_internal.hpp"
+#include "so3.hpp"
 
 namespace {
 
-using V3 = std::array<double, 3>;
-using M3 = std::array<double, 9>;  // row-major
-using Q4 = std::array<double, 4>;  // JPL x y z w
+using namespace plv;  // V3 M3 Q4 and their arithmetic: so3.hpp
 
-V3 add(V3 a, V3 b) { return {a[0] + b[0], a[1] + b[1], a[2] + b[2]}; }
-V3 sub(V3 a, V3 b) { return {a[0] - b[0], a[1] - b[1], a[2] - b[2]}; }
-V3 scl(double s, V3 a) { return {s * a[0], s * a[1], s * a[2]}; }
-double dot(V3 a, V3 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-double nrm(V3 a) { return std::sqrt(dot(a, a)); }
-V3 cross(V3 a, V3 b) { return {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]}; }
-V3 ld(const double *p) { return {p[0], p[1], p[2]}; }
-M3 eye() { return {1, 0, 0, 0, 1, 0, 0, 0, 1}; }
-M3 mm(const M3 &a, const M3 &b) {
-  M3 c;
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) c[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
-  return c;
-}
-M3 tr(const M3 &a) { return {a[0], a[3], a[6], a[1], a[4], a[7], a[2], a[5], a[8]}; }
-V3 mv(const M3 &a, V3 v) {
-  return {a[0] * v[0] + a[1] * v[1] + a[2] * v[2], a[3] * v[0] + a[4] * v[1] + a[5] * v[2], a[6] * v[0] + a[7] * v[1] + a[8] * v[2]};
-}
-M3 madd(const M3 &a, const M3 &b) {
-  M3 c;
-  for (int i = 0; i < 9; ++i) c[i] = a[i] + b[i];
-  return c;
-}
-M3 mscl(double s, const M3 &a) {
-  M3 c;
-  for (int i = 0; i < 9; ++i) c[i] = s * a[i];
-  return c;
+// quat_2_Rot with the entries written out, the form the initialisers and plv_jpl_left_update have always used (so3.hpp's
+// jpl_left_update holds the same lines).  plv::quat_2_Rot's matrix expression differs from it in the sign of a zero entry, e.g. for
+// q = (0, -0.6, 0, -0.8) in entry (0, 1), and a planar wheel rotation q = (0, 0, z, w) is full of such entries: not merged.
+M3 quat_2_Rot_entries(const Q4 &q) {  // REF: quat_ops.h:152-157
+  const double x = q[0], y = q[1], z = q[2], w = q[3], c = 2 * w * w - 1;
+  return {c + 2 * x * x,          2 * w * z + 2 * x * y,  -2 * w * y + 2 * x * z,
+          -2 * w * z + 2 * y * x, c + 2 * y * y,          2 * w * x + 2 * y * z,
+          2 * w * y + 2 * z * x,  -2 * w * x + 2 * z * y, c + 2 * z * z};
 }
 
-M3 quat_2_Rot(Q4 q) {  // quat_ops.h:152-157
-  const double x = q[0], y = q[1], z = q[2], w = q[3], s = 2 * w * w - 1;
-  return {s + 2 * x * x,         2 * w * z + 2 * x * y,  -2 * w * y + 2 * x * z,
-          -2 * w * z + 2 * x * y, s + 2 * y * y,          2 * w * x + 2 * y * z,
-          2 * w * y + 2 * x * z,  -2 * w * x + 2 * y * z, s + 2 * z * z};
-}
-
-Q4 rot_2_quat(const M3 &R) {  // quat_ops.h:88-130
-  const double T = R[0] + R[4] + R[8];
-  Q4 q;
-  if (R[0] >= T && R[0] >= R[4] && R[0] >= R[8]) {
-    q[0] = std::sqrt((1 + 2 * R[0] - T) / 4);
-    q[1] = (1 / (4 * q[0])) * (R[1] + R[3]);
-    q[2] = (1 / (4 * q[0])) * (R[2] + R[6]);
-    q[3] = (1 / (4 * q[0])) * (R[5] - R[7]);
-  } else if (R[4] >= T && R[4] >= R[0] && R[4] >= R[8]) {
-    q[1] = std::sqrt((1 + 2 * R[4] - T) / 4);
-    q[0] = (1 / (4 * q[1])) * (R[1] + R[3]);
-    q[2] = (1 / (4 * q[1])) * (R[5] + R[7]);
-    q[3] = (1 / (4 * q[1])) * (R[6] - R[2]);
-  } else if (R[8] >= T && R[8] >= R[0] && R[8] >= R[4]) {
-    q[2] = std::sqrt((1 + 2 * R[8] - T) / 4);
-    q[0] = (1 / (4 * q[2])) * (R[2] + R[6]);
-    q[1] = (1 / (4 * q[2])) * (R[5] + R[7]);
-    q[3] = (1 / (4 * q[2])) * (R[1] - R[3]);
-  } else {
-    q[3] = std::sqrt((1 + T) / 4);
-    q[0] = (1 / (4 * q[3])) * (R[5] - R[7]);
-    q[1] = (1 / (4 * q[3])) * (R[6] - R[2]);
-    q[2] = (1 / (4 * q[3])) * (R[1] - R[3]);
-  }
-  if (q[3] < 0) q = {-q[0], -q[1], -q[2], -q[3]};
-  const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  return {q[0] / n, q[1] / n, q[2] / n, q[3] / n};
-}
-
-Q4 quatnorm(Q4 q) {  // quat_ops.h:496-501
-  if (q[3] < 0) q = {-q[0], -q[1], -q[2], -q[3]};
-  const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  return {q[0] / n, q[1] / n, q[2] / n, q[3] / n};
-}
-
-Q4 half_omega_times(V3 w, Q4 q, double dt) {  // 0.5 * Omega(w) * q * dt, Omega of quat_ops.h:482-489
+// 0.5 * Omega(w) * q * dt, Omega of quat_ops.h:482-489.  Not omega_times: that one negates term by term, this one the finished cross
+// and dot products, and the two differ in the sign of a zero (w = (1, 1, 0), q = (1, -1, 0, 0): the last entry is -0 here, +0 there).
+Q4 half_omega_times(const V3 &w, const Q4 &q, double dt) {
   const V3 v{q[0], q[1], q[2]};
-  const V3 c = cross(w, v);
-  return {0.5 * dt * (-c[0] + w[0] * q[3]), 0.5 * dt * (-c[1] + w[1] * q[3]), 0.5 * dt * (-c[2] + w[2] * q[3]), 0.5 * dt * (-dot(w, v))};
+  const V3 c = cross3(w, v);
+  return {0.5 * dt * (-c[0] + w[0] * q[3]), 0.5 * dt * (-c[1] + w[1] * q[3]), 0.5 * dt * (-c[2] + w[2] * q[3]), 0.5 * dt * (-dot3(w, v))};
 }
-
-Q4 axpy(Q4 a, double s, Q4 b) { return {a[0] + s * b[0], a[1] + s * b[1], a[2] + s * b[2], a[3] + s * b[3]}; }
 
 // IW_Initializer::IMU_prop_rk4 (REF: IW_Initializer.cpp:608-641): the rotation over dt for an angular velocity that changes
 // linearly from w1 to w2, RK4 on the JPL quaternion starting from the identity.
-Q4 prop_rk4(double dt, V3 w1, V3 w2) {
+Q4 prop_rk4(double dt, const V3 &w1, const V3 &w2) {
   V3 w = w1;
-  const V3 alpha = scl(1.0 / dt, sub(w2, w1));
+  const V3 alpha = vsc(vsub(w2, w1), 1.0 / dt);
   const Q4 dq0{0, 0, 0, 1};
   const Q4 k1 = half_omega_times(w, dq0, dt);
-  w = add(w, scl(0.5 * dt, alpha));
-  const Q4 k2 = half_omega_times(w, quatnorm(axpy(dq0, 0.5, k1)), dt);
-  const Q4 k3 = half_omega_times(w, quatnorm(axpy(dq0, 0.5, k2)), dt);
-  w = add(w, scl(0.5 * dt, alpha));
-  const Q4 k4 = half_omega_times(w, quatnorm(axpy(dq0, 1.0, k3)), dt);
+  w = vadd(w, vsc(alpha, 0.5 * dt));
+  const Q4 k2 = half_omega_times(w, quatnorm(qaxpy(dq0, 0.5, k1)), dt);
+  const Q4 k3 = half_omega_times(w, quatnorm(qaxpy(dq0, 0.5, k2)), dt);
+  w = vadd(w, vsc(alpha, 0.5 * dt));
+  const Q4 k4 = half_omega_times(w, quatnorm(qaxpy(dq0, 1.0, k3)), dt);
   Q4 r = dq0;
-  r = axpy(r, 1.0 / 6.0, k1), r = axpy(r, 1.0 / 3.0, k2), r = axpy(r, 1.0 / 3.0, k3), r = axpy(r, 1.0 / 6.0, k4);
+  r = qaxpy(r, 1.0 / 6.0, k1), r = qaxpy(r, 1.0 / 3.0, k2), r = qaxpy(r, 1.0 / 3.0, k3), r = qaxpy(r, 1.0 / 6.0, k4);
   return quatnorm(r);
 }
 
 // The rotation whose third column is the direction of `g` (REF: IW_Initializer.cpp:643-681, I_Initializer.cpp:117-135).
-M3 gram_schmidt(V3 g, bool normalise_y) {
-  const V3 z = scl(1.0 / nrm(g), g);
-  V3 x = sub(V3{1, 0, 0}, scl(z[0], z));
-  x = scl(1.0 / nrm(x), x);
-  V3 y = cross(z, x);
-  if (normalise_y) y = scl(1.0 / nrm(y), y);
+M3 gram_schmidt(const V3 &g, bool normalise_y) {
+  const V3 z = vsc(g, 1.0 / vnorm(g));
+  V3 x = vsub(V3{1, 0, 0}, vsc(z, z[0]));
+  x = vsc(x, 1.0 / vnorm(x));
+  V3 y = cross3(z, x);
+  if (normalise_y) y = vsc(y, 1.0 / vnorm(y));
   return {x[0], y[0], z[0], x[1], y[1], z[1], x[2], y[2], z[2]};
 }
 
@@ -154,46 +91,44 @@ struct IW {
   // The quantities every stage accumulates over the wheel intervals (REF: IW_Initializer.cpp:220-262 and its copies at
   // :286-326, :444-486, :500-545): returns false where the reference's assert(success) would fire.
   template <class F>
-  bool walk(V3 bg, const std::vector<Wheel> &wh, F &&per_interval) const {
+  bool walk(const V3 &bg, const std::vector<Wheel> &wh, F &&per_interval) const {
     double sum_dt = 0;
     V3 sum_R_a_dt{0, 0, 0};
-    M3 sum_R_dt{0, 0, 0, 0, 0, 0, 0, 0, 0}, R_IktoI0 = eye(), R_O0toOk = eye();
+    M3 sum_R_dt{0, 0, 0, 0, 0, 0, 0, 0, 0}, R_IktoI0 = eye3(), R_O0toOk = eye3();
     for (size_t i = 1; i < wh.size(); ++i) {
       const double ts = wh[i - 1].t + toff, te = wh[i].t + toff;
       Imu pr;
       if (!select_imu(all, ts, te, pr)) return false;
       for (size_t j = 0; j + 1 < pr.size(); ++j) {
         const double dt = pr.t[j + 1] - pr.t[j];
-        const V3 w0 = sub(ld(&pr.w[3 * j]), bg), w1 = sub(ld(&pr.w[3 * j + 3]), bg);
-        const V3 a = scl(0.5, add(ld(&pr.a[3 * j]), ld(&pr.a[3 * j + 3])));
-        sum_R_a_dt = add(sum_R_a_dt, scl(dt, mv(R_IktoI0, a)));
-        sum_R_dt = madd(sum_R_dt, mscl(dt, R_IktoI0));
+        const V3 w0 = vsub(ldV(&pr.w[3 * j]), bg), w1 = vsub(ldV(&pr.w[3 * j + 3]), bg);
+        const V3 a = vsc(vadd(ldV(&pr.a[3 * j]), ldV(&pr.a[3 * j + 3])), 0.5);
+        sum_R_a_dt = vadd(sum_R_a_dt, vsc(mv(R_IktoI0, a), dt));
+        sum_R_dt = ma(sum_R_dt, ms(R_IktoI0, dt));
         sum_dt += dt;
-        R_IktoI0 = mm(R_IktoI0, tr(quat_2_Rot(prop_rk4(dt, w0, w1))));
+        R_IktoI0 = mm(R_IktoI0, tp(quat_2_Rot_entries(prop_rk4(dt, w0, w1))));
       }
-      R_O0toOk = mm(quat_2_Rot(prop_rk4(te - ts, wh[i - 1].w, wh[i].w)), R_O0toOk);
-      const V3 v_ItinI0 = mv(R_OtoI, mv(tr(R_O0toOk), add(wh[i].v, cross(wh[i].w, p_IinO))));
+      R_O0toOk = mm(quat_2_Rot_entries(prop_rk4(te - ts, wh[i - 1].w, wh[i].w)), R_O0toOk);
+      const V3 v_ItinI0 = mv(R_OtoI, mv(tp(R_O0toOk), vadd(wh[i].v, cross3(wh[i].w, p_IinO))));
       per_interval(i, sum_dt, sum_R_a_dt, sum_R_dt, v_ItinI0);
     }
     return true;
   }
 };
 
-bool inv3(const M3 &a, M3 &o) {
-  const double c0 = a[4] * a[8] - a[5] * a[7], c1 = a[5] * a[6] - a[3] * a[8], c2 = a[3] * a[7] - a[4] * a[6];
-  const double det = a[0] * c0 + a[1] * c1 + a[2] * c2;
+bool inv3_checked(const M3 &a, M3 &o) {  // false where the determinant (as inv3 forms it) is zero or not finite
+  const double det = dot3(ldV(a.m), cross3(ldV(a.m + 3), ldV(a.m + 6)));
   if (det == 0 || !std::isfinite(det)) return false;
-  const double s = 1.0 / det;
-  o = {s * c0, s * (a[2] * a[7] - a[1] * a[8]), s * (a[1] * a[5] - a[2] * a[4]),
-       s * c1, s * (a[0] * a[8] - a[2] * a[6]), s * (a[2] * a[3] - a[0] * a[5]),
-       s * c2, s * (a[1] * a[6] - a[0] * a[7]), s * (a[0] * a[4] - a[1] * a[3])};
+  o = inv3(a);
   return true;
 }
 
 // Eigen's LLT (unblocked, lower) followed by solve(), including what it does on a matrix that is not positive definite: the
 // factorisation stops at the first non-positive pivot and solve() runs on what is in the matrix at that point.  The
 // reference evaluates every real root of the constraint polynomial through it (REF: IW_Initializer.cpp:393-394, 421).
-V3 llt_solve(M3 A, V3 b) {
+V3 llt_solve(const M3 &A_in, const V3 &b) {
+  double A[9];
+  std::copy(A_in.m, A_in.m + 9, A);
   for (int k = 0; k < 3; ++k) {
     double x = A[4 * k];
     for (int j = 0; j < k; ++j) x -= A[3 * k + j] * A[3 * k + j];
@@ -235,7 +170,8 @@ Poly padd(const Poly &a, const Poly &b, double sb = 1.0) {
 // The degree-6 polynomial in lambda whose real roots satisfy |(D - lambda I)^-1 d| = g (REF: IW_Initializer.cpp:683-690
 // compute_dongsi_coeff, a generated closed form there): g^2 det(M)^2 - |adj(M) d|^2 with M = D - lambda I, built by polynomial
 // arithmetic and scaled to a leading coefficient of 1.
-Poly dongsi_poly(const M3 &D, V3 d, double g) {
+Poly dongsi_poly(const M3 &Dm, const V3 &d, double g) {
+  const double *D = Dm.m;
   Poly M[9];
   for (int i = 0; i < 9; ++i) M[i] = (i % 4 == 0) ? Poly{D[i], -1.0} : Poly{D[i]};
   auto minor2 = [&](int a, int b, int c, int e) { return padd(pmul(M[a], M[e]), pmul(M[b], M[c]), -1.0); };
@@ -317,31 +253,12 @@ extern "C" {
 // for the driver's dx application (StateHelper::EKFUpdate :156-160 calls it per variable).
 void plv_jpl_left_update(int n, double *q, const double *dth, double *R) {
   for (int k = 0; k < n; ++k) {
-    double *Q = q + 4 * (size_t)k;
-    if (dth) {
-      const double *d = dth + 3 * (size_t)k;
-      double a[3] = {0.5 * d[0], 0.5 * d[1], 0.5 * d[2]}, b = 1.0;
-      const double nd = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2] + 1.0);
-      a[0] /= nd, a[1] /= nd, a[2] /= nd, b /= nd;
-      const double v[3] = {Q[0], Q[1], Q[2]}, w = Q[3];
-      double r[4];
-      r[0] = b * v[0] - (a[1] * v[2] - a[2] * v[1]) + a[0] * w;
-      r[1] = b * v[1] - (a[2] * v[0] - a[0] * v[2]) + a[1] * w;
-      r[2] = b * v[2] - (a[0] * v[1] - a[1] * v[0]) + a[2] * w;
-      r[3] = -(a[0] * v[0] + a[1] * v[1] + a[2] * v[2]) + b * w;
-      if (r[3] < 0)
-        for (double &x : r) x = -x;
-      const double nr = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
-      for (int i = 0; i < 4; ++i) Q[i] = r[i] / nr;
-    }
-    if (R) {
-      const double x = Q[0], y = Q[1], z = Q[2], w = Q[3], c = 2 * w * w - 1;
-      double *M = R + 9 * (size_t)k;
-      // (2 w^2 - 1) I - 2 w [q x] + 2 q q^T
-      M[0] = c + 2 * x * x, M[1] = 2 * w * z + 2 * x * y, M[2] = -2 * w * y + 2 * x * z;
-      M[3] = -2 * w * z + 2 * y * x, M[4] = c + 2 * y * y, M[5] = 2 * w * x + 2 * y * z;
-      M[6] = 2 * w * y + 2 * z * x, M[7] = -2 * w * x + 2 * z * y, M[8] = c + 2 * z * z;
-    }
+    double *Q = q + 4 * (size_t)k, M[9];
+    if (dth)
+      jpl_left_update(Q, dth + 3 * (size_t)k, Q, M);
+    else
+      std::copy_n(quat_2_Rot_entries(ldQ(Q)).m, 9, M);
+    if (R) std::copy_n(M, 9, R + 9 * (size_t)k);
   }
 }
 
@@ -395,22 +312,22 @@ int plv_init_imu_static(int n, const double *t, const double *wm, const double *
   int n1 = 0, n2 = 0, last2 = -1;
   V3 a1{0, 0, 0}, a2{0, 0, 0}, w2{0, 0, 0};
   for (int i = 0; i < n; ++i) {
-    if (t[i] > newest - window_time && t[i] <= newest) a1 = add(a1, ld(am + 3 * i)), ++n1;
-    if (t[i] > newest - 2 * window_time && t[i] <= newest - window_time) a2 = add(a2, ld(am + 3 * i)), w2 = add(w2, ld(wm + 3 * i)), ++n2, last2 = i;
+    if (t[i] > newest - window_time && t[i] <= newest) a1 = vadd(a1, ldV(am + 3 * i)), ++n1;
+    if (t[i] > newest - 2 * window_time && t[i] <= newest - window_time) a2 = vadd(a2, ldV(am + 3 * i)), w2 = vadd(w2, ldV(wm + 3 * i)), ++n2, last2 = i;
   }
   if (n1 < 2 || n2 < 2) return PLV_OK;  // :73-76
-  a1 = scl(1.0 / n1, a1), a2 = scl(1.0 / n2, a2), w2 = scl(1.0 / n2, w2);
+  a1 = vsc(a1, 1.0 / n1), a2 = vsc(a2, 1.0 / n2), w2 = vsc(w2, 1.0 / n2);
   double v1 = 0, v2 = 0;
   for (int i = 0; i < n; ++i) {
-    if (t[i] > newest - window_time && t[i] <= newest) v1 += dot(sub(ld(am + 3 * i), a1), sub(ld(am + 3 * i), a1));
-    if (t[i] > newest - 2 * window_time && t[i] <= newest - window_time) v2 += dot(sub(ld(am + 3 * i), a2), sub(ld(am + 3 * i), a2));
+    if (t[i] > newest - window_time && t[i] <= newest) v1 += dot3(vsub(ldV(am + 3 * i), a1), vsub(ldV(am + 3 * i), a1));
+    if (t[i] > newest - 2 * window_time && t[i] <= newest - window_time) v2 += dot3(vsub(ldV(am + 3 * i), a2), vsub(ldV(am + 3 * i), a2));
   }
   v1 = std::sqrt(v1 / (n1 - 1)), v2 = std::sqrt(v2 / (n2 - 1));
   if (v1 < imu_thresh) return PLV_OK;  // no jerk yet            :104-107
   if (v2 > imu_thresh) return PLV_OK;  // was not standing still :111-114
   const M3 Ro = gram_schmidt(a2, false);  // :117-135
   const Q4 q = rot_2_quat(Ro);
-  const V3 ba = sub(a2, mv(quat_2_Rot(q), ld(gravity)));
+  const V3 ba = vsub(a2, mv(quat_2_Rot_entries(q), ldV(gravity)));
   imustate[0] = t[last2];
   for (int i = 0; i < 4; ++i) imustate[1 + i] = q[i];
   for (int i = 0; i < 6; ++i) imustate[5 + i] = 0;
@@ -461,10 +378,8 @@ int plv_init_imu_wheel(const plv_iw_init_options *op, plv_iw_init_state *state, 
     wh[i] = {st[i], {0, 0, wz}, {vx, 0, 0}};
     if (wz != 0 || vx != 0) all_zero = false;  // wheel.second.norm() > 0   :52-58
   }
-  M3 R_ItoO;
-  std::copy(op->R_ItoO, op->R_ItoO + 9, R_ItoO.begin());
-  const IW iw{*op, all, tr(R_ItoO), ld(op->p_IinO), ld(op->gravity), toff};
-  const double gmag = nrm(iw.grav);
+  const IW iw{*op, all, tp(ldM(op->R_ItoO)), ldV(op->p_IinO), ldV(op->gravity), toff};
+  const double gmag = vnorm(iw.grav);
   if (mode) *mode = all_zero ? 0 : 1;
 
   // ---- init_bg_interpolate_imu (:169-197): bg = mean(w_imu(t_wheel) - R_OtoI w_O), IMU readings from the selected window
@@ -476,34 +391,34 @@ int plv_init_imu_wheel(const plv_iw_init_options *op, plv_iw_init_state *state, 
     for (size_t i = 0; i + 1 < imu.size(); ++i)
       if (tq >= imu.t[i] && tq < imu.t[i + 1]) {
         const double lam = (tq - imu.t[i]) / (imu.t[i + 1] - imu.t[i]);
-        const V3 wi = add(scl(1 - lam, ld(&imu.w[3 * i])), scl(lam, ld(&imu.w[3 * i + 3])));
-        bg = add(bg, sub(wi, mv(iw.R_OtoI, w.w)));
+        const V3 wi = vadd(vsc(ldV(&imu.w[3 * i]), 1 - lam), vsc(ldV(&imu.w[3 * i + 3]), lam));
+        bg = vadd(bg, vsub(wi, mv(iw.R_OtoI, w.w)));
         ++cnt;
         break;
       }
   }
   if (cnt < 1) return PLV_OK;
-  bg = scl(1.0 / cnt, bg);
+  bg = vsc(bg, 1.0 / cnt);
   // ---- init_vI_from_wheel (:199-204)
-  const V3 v_I0 = mv(iw.R_OtoI, add(wh[0].v, cross(wh[0].w, iw.p_IinO)));
+  const V3 v_I0 = mv(iw.R_OtoI, vadd(wh[0].v, cross3(wh[0].w, iw.p_IinO)));
   // ---- gravity in {I0}
   V3 g_I0;
   if (op->imu_gravity_aligned) {
     g_I0 = iw.grav;  // :208-210, :266-269
   } else if (all_zero) {  // init_gI_simple :206-264
     V3 g{0, 0, 0};
-    if (!iw.walk(bg, wh, [&](size_t, double sdt, V3 sRa, const M3 &, V3 v_It) { g = add(g, scl(1.0 / sdt, sub(add(v_I0, sRa), v_It))); }))
+    if (!iw.walk(bg, wh, [&](size_t, double sdt, const V3 &sRa, const M3 &, const V3 &v_It) { g = vadd(g, vsc(vsub(vadd(v_I0, sRa), v_It), 1.0 / sdt)); }))
       return PLV_OK;
-    g = scl(1.0 / (wh.size() - 1), g);
-    g_I0 = scl(gmag / nrm(g), g);
+    g = vsc(g, 1.0 / (wh.size() - 1));
+    g_I0 = vsc(g, gmag / vnorm(g));
   } else {  // init_gI_dongsi :266-432: min |A1 ba + A2 g - b| subject to |g| = gravity, A1 eliminated
     const size_t rows = 3 * wh.size();
     std::vector<double> A1(rows * 3, 0.0), A2(rows * 3, 0.0), bb(rows, 0.0);
-    if (!iw.walk(bg, wh, [&](size_t i, double sdt, V3 sRa, const M3 &sR, V3 v_It) {
-          const V3 r = sub(sub(v_It, v_I0), sRa);
+    if (!iw.walk(bg, wh, [&](size_t i, double sdt, const V3 &sRa, const M3 &sR, const V3 &v_It) {
+          const V3 r = vsub(vsub(v_It, v_I0), sRa);
           for (int a = 0; a < 3; ++a) {
             bb[3 * i + a] = r[a];
-            for (int c = 0; c < 3; ++c) A1[(3 * i + a) * 3 + c] = -sR[3 * a + c];
+            for (int c = 0; c < 3; ++c) A1[(3 * i + a) * 3 + c] = -sR(a, c);
             A2[(3 * i + a) * 3 + a] = -sdt;
           }
         }))
@@ -512,7 +427,7 @@ int plv_init_imu_wheel(const plv_iw_init_options *op, plv_iw_init_state *state, 
       M3 G{0, 0, 0, 0, 0, 0, 0, 0, 0};
       for (size_t r = 0; r < rows; ++r)
         for (int i = 0; i < 3; ++i)
-          for (int j = 0; j < 3; ++j) G[3 * i + j] += X[3 * r + i] * Y[3 * r + j];
+          for (int j = 0; j < 3; ++j) G(i, j) += X[3 * r + i] * Y[3 * r + j];
       return G;
     };
     auto gramv = [&](const std::vector<double> &X) {
@@ -527,48 +442,48 @@ int plv_init_imu_wheel(const plv_iw_init_options *op, plv_iw_init_state *state, 
       V3 e{0, 0, 0};
       e[c] = 1;
       const V3 x = llt_solve(A11, e);
-      for (int r = 0; r < 3; ++r) A11inv[3 * r + c] = x[r];
+      for (int r = 0; r < 3; ++r) A11inv(r, c) = x[r];
     }
     // D = A2^T (I - A1 A11^-1 A1^T) A2,  d = A2^T (I - A1 A11^-1 A1^T) b
-    const M3 Dm = madd(A22, mscl(-1.0, mm(tr(A12), mm(A11inv, A12))));
-    const V3 dv = sub(gramv(A2), mv(tr(A12), mv(A11inv, gramv(A1))));
+    const M3 Dm = ma(A22, ms(mm(tp(A12), mm(A11inv, A12)), -1.0));
+    const V3 dv = vsub(gramv(A2), mv(tp(A12), mv(A11inv, gramv(A1))));
     const Poly poly = dongsi_poly(Dm, dv, gmag);
     bool found = false;
     double lam_min = -1, cost_min = INFINITY;
     for (double lam : real_roots(poly)) {
       M3 Ml = Dm;
-      Ml[0] -= lam, Ml[4] -= lam, Ml[8] -= lam;
-      const double cost = std::abs(nrm(llt_solve(Ml, dv)) - gmag);
+      Ml(0, 0) -= lam, Ml(1, 1) -= lam, Ml(2, 2) -= lam;
+      const double cost = std::abs(vnorm(llt_solve(Ml, dv)) - gmag);
       if (!found || cost < cost_min) found = true, lam_min = lam, cost_min = cost;
     }
     if (!found) return PLV_OK;
     M3 Ml = Dm;
-    Ml[0] -= lam_min, Ml[4] -= lam_min, Ml[8] -= lam_min;
+    Ml(0, 0) -= lam_min, Ml(1, 1) -= lam_min, Ml(2, 2) -= lam_min;
     g_I0 = llt_solve(Ml, dv);
-    if (!(std::abs(nrm(g_I0) - gmag) <= 1e-3)) return PLV_OK;  // init_max_grav_difference :423-429
+    if (!(std::abs(vnorm(g_I0) - gmag) <= 1e-3)) return PLV_OK;  // init_max_grav_difference :423-429
   }
   // ---- init_ba (:434-493)
   V3 ba{0, 0, 0};
   bool singular = false;
-  if (!iw.walk(bg, wh, [&](size_t, double sdt, V3 sRa, const M3 &sR, V3 v_It) {
+  if (!iw.walk(bg, wh, [&](size_t, double sdt, const V3 &sRa, const M3 &sR, const V3 &v_It) {
         M3 inv;
-        if (!inv3(sR, inv)) {
+        if (!inv3_checked(sR, inv)) {
           singular = true;
           return;
         }
-        ba = add(ba, mv(inv, sub(sub(add(v_I0, sRa), scl(sdt, g_I0)), v_It)));
+        ba = vadd(ba, mv(inv, vsub(vsub(vadd(v_I0, sRa), vsc(g_I0, sdt)), v_It)));
       }) ||
       singular)
     return PLV_OK;
-  ba = scl(1.0 / (wh.size() - 1), ba);
-  if (!all_zero && nrm(ba) > gmag) return PLV_OK;  // dynamic_initialization :586-587
+  ba = vsc(ba, 1.0 / (wh.size() - 1));
+  if (!all_zero && vnorm(ba) > gmag) return PLV_OK;  // dynamic_initialization :586-587
   // ---- residual (:495-548): only its last block is looked at
   V3 res_tail{0, 0, 0};
-  if (!iw.walk(bg, wh, [&](size_t, double sdt, V3 sRa, const M3 &sR, V3 v_It) {
-        res_tail = add(add(sub(sub(v_It, v_I0), sRa), mv(sR, ba)), scl(sdt, g_I0));
+  if (!iw.walk(bg, wh, [&](size_t, double sdt, const V3 &sRa, const M3 &sR, const V3 &v_It) {
+        res_tail = vadd(vadd(vsub(vsub(v_It, v_I0), sRa), mv(sR, ba)), vsc(g_I0, sdt));
       }))
     return PLV_OK;
-  if (nrm(res_tail) / 3 > op->threshold * 100) {  // :567-571, :592-596
+  if (vnorm(res_tail) / 3 > op->threshold * 100) {  // :567-571, :592-596
     state->cnt_smooth = 0;
     return PLV_OK;
   }
@@ -588,7 +503,7 @@ int plv_init_imu_wheel(const plv_iw_init_options *op, plv_iw_init_state *state, 
   if (state->cnt_smooth > 3) {
     const M3 R_GtoI0 = gram_schmidt(g_I0, true);
     const Q4 q = rot_2_quat(R_GtoI0);
-    const V3 v_G = mv(tr(R_GtoI0), v_I0);
+    const V3 v_G = mv(tp(R_GtoI0), v_I0);
     imustate[0] = wh[0].t + toff;
     for (int i = 0; i < 4; ++i) imustate[1 + i] = q[i];
     for (int i = 0; i < 3; ++i) imustate[5 + i] = 0, imustate[8 + i] = v_G[i], imustate[11 + i] = bg[i], imustate[14 + i] = ba[i];

@@ -28,153 +28,9 @@ __device__ __forceinline__ void jac_stamp(int id) {
 #include "gate_core.hpp"
 #include "jacobian_kernels.hpp"
 #include "nullspace_core.hpp"
+#include "so3.hpp"
 
 namespace plv {
-
-struct V3 {
-  double v[3];
-  __device__ double &operator[](int i) { return v[i]; }
-  __device__ double operator[](int i) const { return v[i]; }
-};
-struct M3 {
-  double m[9];
-  __device__ double &operator()(int r, int c) { return m[3 * r + c]; }
-  __device__ double operator()(int r, int c) const { return m[3 * r + c]; }
-};
-__device__ __forceinline__ M3 eye3() { return M3{{1, 0, 0, 0, 1, 0, 0, 0, 1}}; }
-__device__ __forceinline__ M3 mm(const M3 &a, const M3 &b) {
-  M3 c;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) c(i, j) = a(i, 0) * b(0, j) + a(i, 1) * b(1, j) + a(i, 2) * b(2, j);
-  return c;
-}
-__device__ __forceinline__ M3 tp(const M3 &a) {
-  M3 c;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) c(i, j) = a(j, i);
-  return c;
-}
-__device__ __forceinline__ V3 mv(const M3 &a, const V3 &x) {
-  return V3{{a(0, 0) * x[0] + a(0, 1) * x[1] + a(0, 2) * x[2], a(1, 0) * x[0] + a(1, 1) * x[1] + a(1, 2) * x[2],
-             a(2, 0) * x[0] + a(2, 1) * x[1] + a(2, 2) * x[2]}};
-}
-__device__ __forceinline__ M3 ms(const M3 &a, double s) {
-  M3 c;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) c.m[i] = a.m[i] * s;
-  return c;
-}
-__device__ __forceinline__ M3 ma(const M3 &a, const M3 &b) {
-  M3 c;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) c.m[i] = a.m[i] + b.m[i];
-  return c;
-}
-__device__ __forceinline__ V3 vsub(const V3 &a, const V3 &b) { return V3{{a[0] - b[0], a[1] - b[1], a[2] - b[2]}}; }
-__device__ __forceinline__ V3 vadd(const V3 &a, const V3 &b) { return V3{{a[0] + b[0], a[1] + b[1], a[2] + b[2]}}; }
-__device__ __forceinline__ V3 vsc(const V3 &a, double s) { return V3{{a[0] * s, a[1] * s, a[2] * s}}; }
-__device__ __forceinline__ double vnorm(const V3 &a) { return sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); }
-__device__ __forceinline__ M3 skew3(const V3 &w) { return M3{{0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0}}; }
-__device__ __forceinline__ M3 inv3(const M3 &a) {
-  double c00 = a(1, 1) * a(2, 2) - a(1, 2) * a(2, 1), c01 = a(1, 2) * a(2, 0) - a(1, 0) * a(2, 2),
-         c02 = a(1, 0) * a(2, 1) - a(1, 1) * a(2, 0);
-  double det = a(0, 0) * c00 + a(0, 1) * c01 + a(0, 2) * c02;
-  double id = 1.0 / det;
-  M3 r;
-  r(0, 0) = c00 * id;
-  r(0, 1) = (a(0, 2) * a(2, 1) - a(0, 1) * a(2, 2)) * id;
-  r(0, 2) = (a(0, 1) * a(1, 2) - a(0, 2) * a(1, 1)) * id;
-  r(1, 0) = c01 * id;
-  r(1, 1) = (a(0, 0) * a(2, 2) - a(0, 2) * a(2, 0)) * id;
-  r(1, 2) = (a(0, 2) * a(1, 0) - a(0, 0) * a(1, 2)) * id;
-  r(2, 0) = c02 * id;
-  r(2, 1) = (a(0, 1) * a(2, 0) - a(0, 0) * a(2, 1)) * id;
-  r(2, 2) = (a(0, 0) * a(1, 1) - a(0, 1) * a(1, 0)) * id;
-  return r;
-}
-__device__ M3 exp_so3(const V3 &w) {  // REF: quat_ops.h:231-251
-  const M3 wx = skew3(w);
-  const double theta = vnorm(w);
-  double A, B;
-  if (theta < 1e-7) {
-    A = 1;
-    B = 0.5;
-  } else {
-    A = sin(theta) / theta;
-    B = (1 - cos(theta)) / (theta * theta);
-  }
-  if (theta == 0) return eye3();
-  return ma(ma(eye3(), ms(wx, A)), ms(mm(wx, wx), B));
-}
-__device__ V3 log_so3(const M3 &R) {  // REF: quat_ops.h:273-313
-  const double R11 = R(0, 0), R12 = R(0, 1), R13 = R(0, 2), R21 = R(1, 0), R22 = R(1, 1), R23 = R(1, 2), R31 = R(2, 0),
-               R32 = R(2, 1), R33 = R(2, 2);
-  const double trc = R11 + R22 + R33;
-  const double PI = 3.14159265358979323846;
-  if (trc + 1.0 < 1e-10) {
-    if (fabs(R33 + 1.0) > 1e-5) return vsc(V3{{R13, R23, 1.0 + R33}}, PI / sqrt(2.0 + 2.0 * R33));
-    if (fabs(R22 + 1.0) > 1e-5) return vsc(V3{{R12, 1.0 + R22, R32}}, PI / sqrt(2.0 + 2.0 * R22));
-    return vsc(V3{{1.0 + R11, R21, R31}}, PI / sqrt(2.0 + 2.0 * R11));
-  }
-  double magnitude;
-  const double tr_3 = trc - 3.0;
-  if (tr_3 < -1e-7) {
-    const double theta = acos((trc - 1.0) / 2.0);
-    magnitude = theta / (2.0 * sin(theta));
-  } else {
-    magnitude = 0.5 - tr_3 / 12.0;
-  }
-  return vsc(V3{{R32 - R23, R13 - R31, R21 - R12}}, magnitude);
-}
-__device__ M3 Jl_so3(const V3 &w) {  // REF: quat_ops.h:515-526
-  const double theta = vnorm(w);
-  if (theta < 1e-6) return eye3();
-  const V3 a = vsc(w, 1.0 / theta);
-  M3 aat;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) aat(i, j) = a[i] * a[j];
-  return ma(ma(ms(eye3(), sin(theta) / theta), ms(aat, 1 - sin(theta) / theta)), ms(skew3(a), (1 - cos(theta)) / theta));
-}
-// exp_so3(w) and Jl_so3(w) for the same w with ONE sin / cos evaluation (the transcendental calls are the long poles of the
-// per-observation chain); every other operation is the one of the two functions above, so the results are bit-identical.
-__device__ void exp_and_Jl(const V3 &w, M3 &Rexp, M3 &J) {
-  const M3 wx = skew3(w);
-  const double theta = vnorm(w);
-  const double st = sin(theta), ct = cos(theta);
-  double A, B;
-  if (theta < 1e-7) {
-    A = 1;
-    B = 0.5;
-  } else {
-    A = st / theta;
-    B = (1 - ct) / (theta * theta);
-  }
-  Rexp = theta == 0 ? eye3() : ma(ma(eye3(), ms(wx, A)), ms(mm(wx, wx), B));
-  if (theta < 1e-6) {
-    J = eye3();
-    return;
-  }
-  const V3 a = vsc(w, 1.0 / theta);
-  M3 aat;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) aat(i, j) = a[i] * a[j];
-  J = ma(ma(ms(eye3(), st / theta), ms(aat, 1 - st / theta)), ms(skew3(a), (1 - ct) / theta));
-}
-__device__ __forceinline__ M3 ldM(const double *p) {
-  M3 m;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) m.m[i] = p[i];
-  return m;
-}
-__device__ __forceinline__ V3 ldV(const double *p) { return V3{{p[0], p[1], p[2]}}; }
 
 // State::bounding_times + bounding_poses_n (order 3)   REF: State.cpp:1023-1136
 __device__ int bounding_start(const JacParams &P, double t) {
@@ -1581,11 +1437,6 @@ __global__ void __launch_bounds__(64) triangulate_kernel(JacParams P, double *po
 // kept: dz/dl starts from Identity(2,3) (third column stays zero) and ln_2 = l0^2 + l1 + l1 (:921-928);
 // the pose written back by get_interpolated_jacobian (first estimates) feeds dli_dI (:898,940-945)
 // while G_to_I keeps the estimate pose (:846-850).
-__device__ __forceinline__ V3 cross3(const V3 &a, const V3 &b) {
-  return V3{{a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]}};
-}
-__device__ __forceinline__ double dot3(const V3 &a, const V3 &b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
 // ---- the rows of one line observation in pieces (line_rows runs them one after the other on one lane; the fused launch spreads
 // them over the four waves, line_rows_split).  Every value is formed by the same expression wherever its piece runs.
 // (1) residual (signed distances of the segment's end points to the projected line) and dzli = d(residual)/d(line in the IMU frame,
@@ -1859,33 +1710,6 @@ __device__ __forceinline__ void line_rows_split(const JacParams &P, const V3 &nG
   }
 }
 
-// ov_type::JPLQuat::update on the device, operation for operation what plv_jpl_left_update (init_api.cpp) does on the host
-// (REF: open_vins/ov_core/src/types/JPLQuat.h:62-73, utils/quat_ops.h:152-157, 232-252): both sides are built -ffp-contract=off and
-// use + - * / sqrt only, so the state a chained launch forms is bit for bit the one the host forms when it applies the same dx.
-__device__ __forceinline__ void jpl_left_update_dev(const double *Qin, const double *d, double *M) {
-  double a[3] = {0.5 * d[0], 0.5 * d[1], 0.5 * d[2]}, b = 1.0;
-  const double nd = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2] + 1.0);
-  a[0] /= nd, a[1] /= nd, a[2] /= nd, b /= nd;
-  const double v[3] = {Qin[0], Qin[1], Qin[2]}, w0 = Qin[3];
-  double r[4];
-  r[0] = b * v[0] - (a[1] * v[2] - a[2] * v[1]) + a[0] * w0;
-  r[1] = b * v[1] - (a[2] * v[0] - a[0] * v[2]) + a[1] * w0;
-  r[2] = b * v[2] - (a[0] * v[1] - a[1] * v[0]) + a[2] * w0;
-  r[3] = -(a[0] * v[0] + a[1] * v[1] + a[2] * v[2]) + b * w0;
-  if (r[3] < 0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = -r[i];
-  }
-  const double nr = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
-  double Q[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) Q[i] = r[i] / nr;
-  const double x = Q[0], y = Q[1], z = Q[2], w = Q[3], c = 2 * w * w - 1;
-  M[0] = c + 2 * x * x, M[1] = 2 * w * z + 2 * x * y, M[2] = -2 * w * y + 2 * x * z;
-  M[3] = -2 * w * z + 2 * y * x, M[4] = c + 2 * y * y, M[5] = 2 * w * x + 2 * y * z;
-  M[6] = 2 * w * y + 2 * z * x, M[7] = -2 * w * x + 2 * z * y, M[8] = c + 2 * z * z;
-}
-
 // line_jacobian_kernel + the null-space projection (+ triangulation in front, + the gate behind) in one launch: the line twin of
 // jacobian_nullspace_kernel, same order of work (inputs to LDS, window tables, [wave 0: poses on the state Pt + plane intersection |
 // waves 1-3: both interpolations on the state P into the LDS slots], rows over four waves, compact-WY null space with six
@@ -1940,7 +1764,7 @@ __global__ void __launch_bounds__(256) line_jacobian_nullspace_kernel(JacParams 
 #pragma unroll
       for (int q = 0; q < 3; ++q) s_cp[3 * t + q] = id >= 0 ? P.clone_p[3 * t + q] + dx[id + 3 + q] : P.clone_p[3 * t + q];
       if (id >= 0) {
-        jpl_left_update_dev(P.chain_q + 4 * t, dx + id, s_cR + 9 * t);
+        jpl_left_update(P.chain_q + 4 * t, dx + id, nullptr, s_cR + 9 * t);
       } else {
 #pragma unroll
         for (int q = 0; q < 9; ++q) s_cR[9 * t + q] = P.clone_R[9 * t + q];
@@ -1948,7 +1772,7 @@ __global__ void __launch_bounds__(256) line_jacobian_nullspace_kernel(JacParams 
     } else if (t == 64) {
       const int id = P.chain_id[N];
       if (id >= 0) {
-        jpl_left_update_dev(P.chain_qe, dx + id, s_cal);
+        jpl_left_update(P.chain_qe, dx + id, nullptr, s_cal);
 #pragma unroll
         for (int q = 0; q < 3; ++q) s_cal[9 + q] = P.p_IinC[q] + dx[id + 3 + q];
       } else {

@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "plv_ctx.hpp"
-#include "so3_dev.hpp"
+#include "so3.hpp"
 #include "update_state.hpp"
 
 namespace plv {
@@ -30,8 +30,6 @@ namespace {
     int _rc = (expr);              \
     if (_rc != PLV_OK) return _rc; \
   } while (0)
-
-using namespace so3;
 
 // LDS image of plv_imu_state: q4 p3 v3 bg3 ba3 qf4 pf3 vf3
 enum { IQ = 0, IP = 4, IV = 7, IBG = 10, IBA = 13, IQF = 16, IPF = 20, IVF = 23, IMU_N = 26 };
@@ -48,85 +46,79 @@ struct PropArgs {
   double R0[9], t_given;      // mode 1: clones.at(clone_t)->Rot(), the requested time
 };
 
-__device__ __forceinline__ void put3(double *M, int ldm, int r0, int c0, const DM3 &B) {
+__device__ __forceinline__ void put3(double *M, int ldm, int r0, int c0, const M3 &B) {
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) M[(r0 + r) * ldm + c0 + c] = B.m[3 * r + c];
+    for (int c = 0; c < 3; ++c) M[(r0 + r) * ldm + c0 + c] = B(r, c);
 }
 
 // predict_mean_rk4 + the blocks of predict_and_compute; one thread
 __device__ void mean_and_jacobians(double *imu, const PropArgs &A, int i, double *F, double *G) {
   const double dt = A.t[i + 1] - A.t[i];
-  const D3 g{A.g[0], A.g[1], A.g[2]};
-  const D3 bg = ld3(imu + IBG), ba = ld3(imu + IBA);
-  const D3 w1 = ld3(A.wm + 3 * i) - bg, a1 = ld3(A.am + 3 * i) - ba, w2 = ld3(A.wm + 3 * (i + 1)) - bg, a2 = ld3(A.am + 3 * (i + 1)) - ba;
-  D3 w_hat = w1, a_hat = a1;
-  const D3 w_alpha = (1.0 / dt) * (w2 - w1), a_jerk = (1.0 / dt) * (a2 - a1);
-  const DQ q_0{imu[IQ], imu[IQ + 1], imu[IQ + 2], imu[IQ + 3]};
-  const D3 p_0 = ld3(imu + IP), v_0 = ld3(imu + IV);
-  const DQ dq_0{0, 0, 0, 1};
-  auto vdot = [&](DQ dq) { return mvec(mtr(q2R(qmul(dq, q_0))), a_hat) - g; };
-  auto qdot = [&](DQ dq) {
-    const DQ o = omega_times(w_hat, dq);
-    return DQ{0.5 * o.x, 0.5 * o.y, 0.5 * o.z, 0.5 * o.w};
+  const V3 g = ldV(A.g);
+  const V3 bg = ldV(imu + IBG), ba = ldV(imu + IBA);
+  const V3 w1 = vsub(ldV(A.wm + 3 * i), bg), a1 = vsub(ldV(A.am + 3 * i), ba), w2 = vsub(ldV(A.wm + 3 * (i + 1)), bg), a2 = vsub(ldV(A.am + 3 * (i + 1)), ba);
+  V3 w_hat = w1, a_hat = a1;
+  const V3 w_alpha = vsc(vsub(w2, w1), 1.0 / dt), a_jerk = vsc(vsub(a2, a1), 1.0 / dt);
+  const Q4 q_0 = ldQ(imu + IQ);
+  const V3 p_0 = ldV(imu + IP), v_0 = ldV(imu + IV);
+  const Q4 dq_0{{0, 0, 0, 1}};
+  auto vdot = [&](const Q4 &dq) { return vsub(mv(tp(quat_2_Rot(quat_multiply(dq, q_0))), a_hat), g); };
+  auto k_q = [&](const Q4 &dq) {  // dt * (0.5 * Omega(w_hat) dq)
+    const Q4 o = omega_times(w_hat, dq);
+    return Q4{{dt * (0.5 * o[0]), dt * (0.5 * o[1]), dt * (0.5 * o[2]), dt * (0.5 * o[3])}};
   };
-  const DQ q0d = qdot(dq_0);
-  const D3 v0d = vdot(dq_0);
-  const DQ k1_q{dt * q0d.x, dt * q0d.y, dt * q0d.z, dt * q0d.w};
-  const D3 k1_p = dt * v_0, k1_v = dt * v0d;
-  w_hat = w_hat + (0.5 * dt) * w_alpha;
-  a_hat = a_hat + (0.5 * dt) * a_jerk;
-  const DQ dq_1 = qnorm(qaxpy(dq_0, 0.5, k1_q));
-  const D3 v_1 = v_0 + 0.5 * k1_v;
-  const DQ q1d = qdot(dq_1);
-  const D3 v1d = vdot(dq_1);
-  const DQ k2_q{dt * q1d.x, dt * q1d.y, dt * q1d.z, dt * q1d.w};
-  const D3 k2_p = dt * v_1, k2_v = dt * v1d;
-  const DQ dq_2 = qnorm(qaxpy(dq_0, 0.5, k2_q));
-  const D3 v_2 = v_0 + 0.5 * k2_v;
-  const DQ q2d = qdot(dq_2);
-  const D3 v2d = vdot(dq_2);
-  const DQ k3_q{dt * q2d.x, dt * q2d.y, dt * q2d.z, dt * q2d.w};
-  const D3 k3_p = dt * v_2, k3_v = dt * v2d;
-  w_hat = w_hat + (0.5 * dt) * w_alpha;
-  a_hat = a_hat + (0.5 * dt) * a_jerk;
-  const DQ dq_3 = qnorm(qaxpy(dq_0, 1.0, k3_q));
-  const D3 v_3 = v_0 + k3_v;
-  const DQ q3d = qdot(dq_3);
-  const D3 v3d = vdot(dq_3);
-  const DQ k4_q{dt * q3d.x, dt * q3d.y, dt * q3d.z, dt * q3d.w};
-  const D3 k4_p = dt * v_3, k4_v = dt * v3d;
-  const DQ dq = qnorm(qaxpy(qaxpy(qaxpy(qaxpy(dq_0, 1.0 / 6.0, k1_q), 1.0 / 3.0, k2_q), 1.0 / 3.0, k3_q), 1.0 / 6.0, k4_q));
-  const DQ new_q = qmul(dq, q_0);
-  const D3 new_p = (((p_0 + (1.0 / 6.0) * k1_p) + (1.0 / 3.0) * k2_p) + (1.0 / 3.0) * k3_p) + (1.0 / 6.0) * k4_p;
-  const D3 new_v = (((v_0 + (1.0 / 6.0) * k1_v) + (1.0 / 3.0) * k2_v) + (1.0 / 3.0) * k3_v) + (1.0 / 6.0) * k4_v;
+  const Q4 k1_q = k_q(dq_0);
+  const V3 k1_p = vsc(v_0, dt), k1_v = vsc(vdot(dq_0), dt);
+  w_hat = vadd(w_hat, vsc(w_alpha, 0.5 * dt));
+  a_hat = vadd(a_hat, vsc(a_jerk, 0.5 * dt));
+  const Q4 dq_1 = quatnorm(qaxpy(dq_0, 0.5, k1_q));
+  const V3 v_1 = vadd(v_0, vsc(k1_v, 0.5));
+  const Q4 k2_q = k_q(dq_1);
+  const V3 k2_p = vsc(v_1, dt), k2_v = vsc(vdot(dq_1), dt);
+  const Q4 dq_2 = quatnorm(qaxpy(dq_0, 0.5, k2_q));
+  const V3 v_2 = vadd(v_0, vsc(k2_v, 0.5));
+  const Q4 k3_q = k_q(dq_2);
+  const V3 k3_p = vsc(v_2, dt), k3_v = vsc(vdot(dq_2), dt);
+  w_hat = vadd(w_hat, vsc(w_alpha, 0.5 * dt));
+  a_hat = vadd(a_hat, vsc(a_jerk, 0.5 * dt));
+  const Q4 dq_3 = quatnorm(qaxpy(dq_0, 1.0, k3_q));
+  const V3 v_3 = vadd(v_0, k3_v);
+  const Q4 k4_q = k_q(dq_3);
+  const V3 k4_p = vsc(v_3, dt), k4_v = vsc(vdot(dq_3), dt);
+  const Q4 dq = quatnorm(qaxpy(qaxpy(qaxpy(qaxpy(dq_0, 1.0 / 6.0, k1_q), 1.0 / 3.0, k2_q), 1.0 / 3.0, k3_q), 1.0 / 6.0, k4_q));
+  const Q4 new_q = quat_multiply(dq, q_0);
+  auto rk4_sum = [](const V3 &x0, const V3 &k1, const V3 &k2, const V3 &k3, const V3 &k4) {
+    return vadd(vadd(vadd(vadd(x0, vsc(k1, 1.0 / 6.0)), vsc(k2, 1.0 / 3.0)), vsc(k3, 1.0 / 3.0)), vsc(k4, 1.0 / 6.0));
+  };
+  const V3 new_p = rk4_sum(p_0, k1_p, k2_p, k3_p, k4_p), new_v = rk4_sum(v_0, k1_v, k2_v, k3_v, k4_v);
   // ---- Jacobians with the first estimates (Propagator.cpp:189-220); local ids theta 0, p 3, v 6, bg 9, ba 12
   for (int e = 0; e < 225; ++e) F[e] = 0.0;
   for (int e = 0; e < 180; ++e) G[e] = 0.0;
-  const DM3 Rfej = q2R(DQ{imu[IQF], imu[IQF + 1], imu[IQF + 2], imu[IQF + 3]}), RfT = mtr(Rfej);
-  const DM3 dR = mmul(q2R(new_q), RfT);
-  const D3 v_fej = ld3(imu + IVF), p_fej = ld3(imu + IPF);
-  const DM3 thbg = mscale(dt, mmul(mscale(-1.0, dR), Jl(dt * w1)));  // -dR * Jr_so3(-w_hat dt) * dt, Jr(x) = Jl(-x)
+  const M3 Rfej = quat_2_Rot(ldQ(imu + IQF)), RfT = tp(Rfej);
+  const M3 dR = mm(quat_2_Rot(new_q), RfT);
+  const V3 v_fej = ldV(imu + IVF), p_fej = ldV(imu + IPF);
+  const M3 thbg = ms(mm(ms(dR, -1.0), Jl_so3(vsc(w1, dt))), dt);  // -dR * Jr_so3(-w_hat dt) * dt, Jr(x) = Jl(-x)
   put3(F, 15, 0, 0, dR);
   put3(F, 15, 0, 9, thbg);
-  put3(F, 15, 9, 9, eyem());
-  put3(F, 15, 6, 0, mmul(mscale(-1.0, skewm((new_v - v_fej) + dt * g)), RfT));
-  put3(F, 15, 6, 6, eyem());
-  put3(F, 15, 6, 12, mscale(-dt, RfT));
-  put3(F, 15, 12, 12, eyem());
-  put3(F, 15, 3, 0, mmul(mscale(-1.0, skewm(((new_p - p_fej) - dt * v_fej) + (0.5 * dt * dt) * g)), RfT));
-  put3(F, 15, 3, 6, mscale(dt, eyem()));
-  put3(F, 15, 3, 12, mscale(-0.5 * dt * dt, RfT));
-  put3(F, 15, 3, 3, eyem());
+  put3(F, 15, 9, 9, eye3());
+  put3(F, 15, 6, 0, mm(ms(skew3(vadd(vsub(new_v, v_fej), vsc(g, dt))), -1.0), RfT));
+  put3(F, 15, 6, 6, eye3());
+  put3(F, 15, 6, 12, ms(RfT, -dt));
+  put3(F, 15, 12, 12, eye3());
+  put3(F, 15, 3, 0, mm(ms(skew3(vadd(vsub(vsub(new_p, p_fej), vsc(v_fej, dt)), vsc(g, 0.5 * dt * dt))), -1.0), RfT));
+  put3(F, 15, 3, 6, ms(eye3(), dt));
+  put3(F, 15, 3, 12, ms(RfT, -0.5 * dt * dt));
+  put3(F, 15, 3, 3, eye3());
   put3(G, 12, 0, 0, thbg);
-  put3(G, 12, 6, 3, mscale(-dt, RfT));
-  put3(G, 12, 3, 3, mscale(-0.5 * dt * dt, RfT));
-  put3(G, 12, 9, 6, eyem());
-  put3(G, 12, 12, 9, eyem());
+  put3(G, 12, 6, 3, ms(RfT, -dt));
+  put3(G, 12, 3, 3, ms(RfT, -0.5 * dt * dt));
+  put3(G, 12, 9, 6, eye3());
+  put3(G, 12, 12, 9, eye3());
   // value and fej := propagated mean (:229-237)
-  imu[IQ] = imu[IQF] = new_q.x, imu[IQ + 1] = imu[IQF + 1] = new_q.y, imu[IQ + 2] = imu[IQF + 2] = new_q.z, imu[IQ + 3] = imu[IQF + 3] = new_q.w;
-  st3(imu + IP, new_p), st3(imu + IPF, new_p), st3(imu + IV, new_v), st3(imu + IVF, new_v);
+  for (int e = 0; e < 4; ++e) imu[IQ + e] = imu[IQF + e] = new_q[e];
+  stV(imu + IP, new_p), stV(imu + IPF, new_p), stV(imu + IV, new_v), stV(imu + IVF, new_v);
 }
 
 // plv_cpi_accum image (doubles): clone_t 0, DT 1, R 2..10, alpha 11, beta 14, bw 17, ba 20, v_clone 23, P_meas 26..250
@@ -138,22 +130,20 @@ enum { CR_T = 0, CR_DT = 1, CR_CL = 2, CR_R = 3, CR_AL = 12, CR_V = 15, CR_W = 1
 __device__ void cpi_means(double *cpi, const PropArgs &A, int i, double *wx, double *ax, double *Rold, double *Rmid, double *Rnew) {
   const double delta_t = A.t[i + 1] - A.t[i];
   cpi[CA_DT] += delta_t;
-  const D3 bw = ld3(cpi + CA_BW), bal = ld3(cpi + CA_BA);
-  D3 w_hat = ld3(A.wm + 3 * i) - bw, a_hat = ld3(A.am + 3 * i) - bal;
-  w_hat = w_hat + (ld3(A.wm + 3 * (i + 1)) - bw);
-  w_hat = 0.5 * w_hat;
-  a_hat = a_hat + (ld3(A.am + 3 * (i + 1)) - bal);
-  a_hat = 0.5 * a_hat;
-  const double mag_w = nrm3(w_hat), w_dt = mag_w * delta_t;
+  const V3 bw = ldV(cpi + CA_BW), bal = ldV(cpi + CA_BA);
+  V3 w_hat = vsub(ldV(A.wm + 3 * i), bw), a_hat = vsub(ldV(A.am + 3 * i), bal);
+  w_hat = vadd(w_hat, vsub(ldV(A.wm + 3 * (i + 1)), bw));
+  w_hat = vsc(w_hat, 0.5);
+  a_hat = vadd(a_hat, vsub(ldV(A.am + 3 * (i + 1)), bal));
+  a_hat = vsc(a_hat, 0.5);
+  const double mag_w = vnorm(w_hat), w_dt = mag_w * delta_t;
   const bool small_w = mag_w < 0.008726646;
   const double dt_2 = delta_t * delta_t, cos_wt = cos(w_dt), sin_wt = sin(w_dt);
-  const DM3 w_x = skewm(w_hat), a_x = skewm(a_hat), w_x_2 = mmul(w_x, w_x), I = eyem();
-  DM3 R_k2tau;
-#pragma unroll
-  for (int e = 0; e < 9; ++e) R_k2tau.m[e] = cpi[CA_R + e];
-  const DM3 R_t2t1 = small_w ? madd(msub(I, mscale(delta_t, w_x)), mscale(dt_2 / 2, w_x_2))
-                             : madd(msub(I, mscale(sin_wt / mag_w, w_x)), mscale((1.0 - cos_wt) / (mag_w * mag_w), w_x_2));
-  const DM3 R_k2tau1 = mmul(R_t2t1, R_k2tau), R_tau12k = mtr(R_k2tau1);
+  const M3 w_x = skew3(w_hat), a_x = skew3(a_hat), w_x_2 = mm(w_x, w_x), I = eye3();
+  const M3 R_k2tau = ldM(cpi + CA_R);
+  const M3 R_t2t1 = small_w ? ma(msb(I, ms(w_x, delta_t)), ms(w_x_2, dt_2 / 2))
+                            : ma(msb(I, ms(w_x, sin_wt / mag_w)), ms(w_x_2, (1.0 - cos_wt) / (mag_w * mag_w)));
+  const M3 R_k2tau1 = mm(R_t2t1, R_k2tau), R_tau12k = tp(R_k2tau1);
   double f_1, f_2, f_3, f_4;
   if (small_w) {
     f_1 = -(pow(delta_t, 3) / 3);
@@ -166,18 +156,18 @@ __device__ void cpi_means(double *cpi, const PropArgs &A, int i, double *wx, dou
     f_3 = -(1 - cos_wt) / (mag_w * mag_w);
     f_4 = (w_dt - sin_wt) / pow(mag_w, 3);
   }
-  const DM3 alpha_arg = madd(madd(mscale(dt_2 / 2.0, I), mscale(f_1, w_x)), mscale(f_2, w_x_2));
-  const DM3 Beta_arg = madd(madd(mscale(delta_t, I), mscale(f_3, w_x)), mscale(f_4, w_x_2));
-  const DM3 H_al = mmul(R_tau12k, alpha_arg), H_be = mmul(R_tau12k, Beta_arg);
-  D3 alpha = ld3(cpi + CA_AL), beta = ld3(cpi + CA_BE);
-  alpha = alpha + (delta_t * beta + mvec(H_al, a_hat));
-  beta = beta + mvec(H_be, a_hat);
-  st3(cpi + CA_AL, alpha);
-  st3(cpi + CA_BE, beta);
+  const M3 alpha_arg = ma(ma(ms(I, dt_2 / 2.0), ms(w_x, f_1)), ms(w_x_2, f_2));
+  const M3 Beta_arg = ma(ma(ms(I, delta_t), ms(w_x, f_3)), ms(w_x_2, f_4));
+  const M3 H_al = mm(R_tau12k, alpha_arg), H_be = mm(R_tau12k, Beta_arg);
+  V3 alpha = ldV(cpi + CA_AL), beta = ldV(cpi + CA_BE);
+  alpha = vadd(alpha, vadd(vsc(beta, delta_t), mv(H_al, a_hat)));
+  beta = vadd(beta, mv(H_be, a_hat));
+  stV(cpi + CA_AL, alpha);
+  stV(cpi + CA_BE, beta);
   const double hw = mag_w * .5 * delta_t;
-  DM3 R_mid = small_w ? madd(msub(I, mscale(.5 * delta_t, w_x)), mscale(pow(.5 * delta_t, 2) / 2, w_x_2))
-                      : madd(msub(I, mscale(sin(hw) / mag_w, w_x)), mscale((1.0 - cos(hw)) / (mag_w * mag_w), w_x_2));
-  R_mid = mmul(R_mid, R_k2tau);
+  M3 R_mid = small_w ? ma(msb(I, ms(w_x, .5 * delta_t)), ms(w_x_2, pow(.5 * delta_t, 2) / 2))
+                     : ma(msb(I, ms(w_x, sin(hw) / mag_w)), ms(w_x_2, (1.0 - cos(hw)) / (mag_w * mag_w)));
+  R_mid = mm(R_mid, R_k2tau);
 #pragma unroll
   for (int e = 0; e < 9; ++e) {
     wx[e] = w_x.m[e], ax[e] = a_x.m[e], Rold[e] = R_k2tau.m[e], Rmid[e] = R_mid.m[e], Rnew[e] = R_k2tau1.m[e];
@@ -221,7 +211,7 @@ __global__ void __launch_bounds__(256) propagate_kernel(PropArgs A) {
   }
   __syncthreads();
   if (tid == 0) {  // R_GtoIk = state->imu->Rot() at entry (:46) / clones.at(clone_t)->Rot() (State.cpp:389)
-    const DM3 R0 = q2R(DQ{imu[IQ], imu[IQ + 1], imu[IQ + 2], imu[IQ + 3]});
+    const M3 R0 = quat_2_Rot(ldQ(imu + IQ));
     for (int e = 0; e < 9; ++e) RGtoIk[e] = A.mode == 1 ? A.R0[e] : R0.m[e];
   }
   for (int i = 0; i < A.n_data - 1; ++i) {

@@ -22,13 +22,11 @@
 #include <vector>
 
 #include "plv_ctx.hpp"
-#include "so3_dev.hpp"
+#include "so3.hpp"
 #include "update_state.hpp"
 
 namespace plv {
 namespace {
-
-using namespace so3;
 
 #define TRY(expr)                  \
   do {                             \
@@ -44,31 +42,25 @@ struct WheelArgs {
   double *out;                // [H 6*k col-major][res 6][Cov 36][R 9][p 3][Hw 6*k][resw 6][D 6][Hc 6*k][resc 6][chol 1]   (Hw = V^T H, Cov = V D V^T; Hc = L^-1 H, Cov = L L^T)
 };
 
-__device__ __forceinline__ void wheel_vel(const WheelArgs &A, double a1, double a2, D3 &w, D3 &v) {
+__device__ __forceinline__ void wheel_vel(const WheelArgs &A, double a1, double a2, V3 &w, V3 &v) {
   const double rl = A.st.intr[0], rr = A.st.intr[1], b = A.st.intr[2];
   if (A.op.type == PLV_WHEEL3D_ANG) {
-    w = {0, 0, (a2 * rr - a1 * rl) / b};
-    v = {(a2 * rr + a1 * rl) / 2, 0, 0};
+    w = V3{{0, 0, (a2 * rr - a1 * rl) / b}};
+    v = V3{{(a2 * rr + a1 * rl) / 2, 0, 0}};
   } else if (A.op.type == PLV_WHEEL3D_LIN) {
-    w = {0, 0, (a2 - a1) / b};
-    v = {(a2 + a1) / 2, 0, 0};
+    w = V3{{0, 0, (a2 - a1) / b}};
+    v = V3{{(a2 + a1) / 2, 0, 0}};
   } else {
-    w = {0, 0, a1};
-    v = {a2, 0, 0};
+    w = V3{{0, 0, a1}};
+    v = V3{{a2, 0, 0}};
   }
 }
 
-__device__ __forceinline__ DM3 ldm(const double *p) {
-  DM3 m;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) m.m[i] = p[i];
-  return m;
-}
-__device__ __forceinline__ void put3w(double *M, int ldm_, int r0, int c0, const DM3 &B) {
+__device__ __forceinline__ void put3w(double *M, int ldm_, int r0, int c0, const M3 &B) {
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) M[(r0 + r) * ldm_ + c0 + c] = B.m[3 * r + c];
+    for (int c = 0; c < 3; ++c) M[(r0 + r) * ldm_ + c0 + c] = B(r, c);
 }
 
 // Cyclic Jacobi on a symmetric M x M matrix (row-major, overwritten): A -> diagonal d, V's columns the eigenvectors, A = V d V^T.
@@ -192,19 +184,19 @@ __global__ void __launch_bounds__(64) wheel_kernel(WheelArgs A) {
   for (int i = 0; i < A.n_data - 1; ++i) {
     const double dt = A.t[i + 1] - A.t[i];
     if (tid == 0) {
-      const DM3 R_3D = ldm(R3);
-      const D3 p_3D = ld3(p3);
+      const M3 R_3D = ldM(R3);
+      const V3 p_3D = ldV(p3);
       if (A.op.do_calib_int) {  // preintegration_intrinsics_3D
         const double rl = A.st.intr[0], rr = A.st.intr[1], b = A.st.intr[2];
         const double w_l = A.m1[i], w_r = A.m2[i];
-        const D3 w{0, 0, (w_r * rr - w_l * rl) / b}, v{(w_r * rr + w_l * rl) / 2, 0, 0};
-        DM3 Hwx{{0, 0, 0, 0, 0, 0, -w_l / b, w_r / b, -(w_r * rr - w_l * rl) / (b * b)}};
-        DM3 Hvx{{w_l / 2, w_r / 2, 0, 0, 0, 0, 0, 0, 0}};
-        const DM3 R = exp3((-dt) * w);
-        const DM3 Hth = mscale(dt, Jl((-dt) * w));
-        const DM3 dR = ldm(dRdi), dp = ldm(dpdi);
-        const DM3 ndp = madd(msub(dp, mmul(mmul(mtr(R_3D), skewm(dt * v)), dR)), mscale(dt, mmul(mtr(R_3D), Hvx)));
-        const DM3 ndR = madd(mmul(R, dR), mmul(Hth, Hwx));
+        const V3 w{{0, 0, (w_r * rr - w_l * rl) / b}}, v{{(w_r * rr + w_l * rl) / 2, 0, 0}};
+        M3 Hwx{{0, 0, 0, 0, 0, 0, -w_l / b, w_r / b, -(w_r * rr - w_l * rl) / (b * b)}};
+        M3 Hvx{{w_l / 2, w_r / 2, 0, 0, 0, 0, 0, 0, 0}};
+        const M3 R = exp_so3(vsc(w, -dt));
+        const M3 Hth = ms(Jl_so3(vsc(w, -dt)), dt);
+        const M3 dR = ldM(dRdi), dp = ldM(dpdi);
+        const M3 ndp = ma(msb(dp, mm(mm(tp(R_3D), skew3(vsc(v, dt))), dR)), ms(mm(tp(R_3D), Hvx), dt));
+        const M3 ndR = ma(mm(R, dR), mm(Hth, Hwx));
 #pragma unroll
         for (int e = 0; e < 9; ++e) {
           dpdi[e] = ndp.m[e];
@@ -212,36 +204,36 @@ __global__ void __launch_bounds__(64) wheel_kernel(WheelArgs A) {
         }
       }
       // preintegration_3D: RK4 means
-      D3 w1, v1, w2, v2;
+      V3 w1, v1, w2, v2;
       wheel_vel(A, A.m1[i], A.m2[i], w1, v1);
       wheel_vel(A, A.m1[i + 1], A.m2[i + 1], w2, v2);
-      D3 w_hat = w1, v_hat = v1;
-      const D3 w_alpha = (1.0 / dt) * (w2 - w1), v_jerk = (1.0 / dt) * (v2 - v1);
-      const DQ q_local = R2q(R_3D);
-      const DQ dq_0{0, 0, 0, 1};
-      auto qdot = [&](DQ dq) {
-        const DQ o = omega_times(w_hat, dq);
-        return DQ{dt * (0.5 * o.x), dt * (0.5 * o.y), dt * (0.5 * o.z), dt * (0.5 * o.w)};
+      V3 w_hat = w1, v_hat = v1;
+      const V3 w_alpha = vsc(vsub(w2, w1), 1.0 / dt), v_jerk = vsc(vsub(v2, v1), 1.0 / dt);
+      const Q4 q_local = rot_2_quat(R_3D);
+      const Q4 dq_0{{0, 0, 0, 1}};
+      auto qdot = [&](const Q4 &dq) {
+        const Q4 o = omega_times(w_hat, dq);
+        return Q4{{dt * (0.5 * o[0]), dt * (0.5 * o[1]), dt * (0.5 * o[2]), dt * (0.5 * o[3])}};
       };
-      auto pdot = [&](DQ dq) { return dt * mvec(mtr(q2R(qmul(dq, q_local))), v_hat); };
-      const DQ k1_q = qdot(dq_0);
-      const D3 k1_p = pdot(dq_0);
-      w_hat = w_hat + (0.5 * dt) * w_alpha;
-      v_hat = v_hat + (0.5 * dt) * v_jerk;
-      const DQ dq_1 = qnorm(qaxpy(dq_0, 0.5, k1_q));
-      const DQ k2_q = qdot(dq_1);
-      const D3 k2_p = pdot(dq_1);
-      const DQ dq_2 = qnorm(qaxpy(dq_0, 0.5, k2_q));
-      const DQ k3_q = qdot(dq_2);
-      const D3 k3_p = pdot(dq_2);
-      w_hat = w_hat + (0.5 * dt) * w_alpha;
-      v_hat = v_hat + (0.5 * dt) * v_jerk;
-      const DQ dq_3 = qnorm(qaxpy(dq_0, 1.0, k3_q));
-      const DQ k4_q = qdot(dq_3);
-      const D3 k4_p = pdot(dq_3);
-      const DQ dq = qnorm(qaxpy(qaxpy(qaxpy(qaxpy(dq_0, 1.0 / 6.0, k1_q), 1.0 / 3.0, k2_q), 1.0 / 3.0, k3_q), 1.0 / 6.0, k4_q));
-      const DM3 R_new = q2R(qmul(dq, q_local));
-      const D3 new_p = (((p_3D + (1.0 / 6.0) * k1_p) + (1.0 / 3.0) * k2_p) + (1.0 / 3.0) * k3_p) + (1.0 / 6.0) * k4_p;
+      auto pdot = [&](const Q4 &dq) { return vsc(mv(tp(quat_2_Rot(quat_multiply(dq, q_local))), v_hat), dt); };
+      const Q4 k1_q = qdot(dq_0);
+      const V3 k1_p = pdot(dq_0);
+      w_hat = vadd(w_hat, vsc(w_alpha, 0.5 * dt));
+      v_hat = vadd(v_hat, vsc(v_jerk, 0.5 * dt));
+      const Q4 dq_1 = quatnorm(qaxpy(dq_0, 0.5, k1_q));
+      const Q4 k2_q = qdot(dq_1);
+      const V3 k2_p = pdot(dq_1);
+      const Q4 dq_2 = quatnorm(qaxpy(dq_0, 0.5, k2_q));
+      const Q4 k3_q = qdot(dq_2);
+      const V3 k3_p = pdot(dq_2);
+      w_hat = vadd(w_hat, vsc(w_alpha, 0.5 * dt));
+      v_hat = vadd(v_hat, vsc(v_jerk, 0.5 * dt));
+      const Q4 dq_3 = quatnorm(qaxpy(dq_0, 1.0, k3_q));
+      const Q4 k4_q = qdot(dq_3);
+      const V3 k4_p = pdot(dq_3);
+      const Q4 dq = quatnorm(qaxpy(qaxpy(qaxpy(qaxpy(dq_0, 1.0 / 6.0, k1_q), 1.0 / 3.0, k2_q), 1.0 / 3.0, k3_q), 1.0 / 6.0, k4_q));
+      const M3 R_new = quat_2_Rot(quat_multiply(dq, q_local));
+      const V3 new_p = vadd(vadd(vadd(vadd(p_3D, vsc(k1_p, 1.0 / 6.0)), vsc(k2_p, 1.0 / 3.0)), vsc(k3_p, 1.0 / 3.0)), vsc(k4_p, 1.0 / 6.0));
       // Phi_tr, Phi_ns, Q
       const double nw = A.op.noise_w * A.op.noise_w, nv = A.op.noise_v * A.op.noise_v, np = A.op.noise_p * A.op.noise_p, b = A.st.intr[2];
       double q0, q3;
@@ -254,15 +246,15 @@ __global__ void __launch_bounds__(64) wheel_kernel(WheelArgs A) {
       }
       Qd[0] = q0, Qd[3] = q3, Qd[1] = Qd[2] = Qd[4] = Qd[5] = np / dt;
       for (int e = 0; e < 36; ++e) Ptr[e] = Pns[e] = 0.0;
-      const DM3 RT = mtr(R_3D);
-      put3w(Ptr, 6, 0, 0, mmul(R_new, RT));
-      put3w(Ptr, 6, 3, 0, mmul(mscale(-1.0, RT), skewm(mvec(RT, new_p - p_3D))));
-      put3w(Ptr, 6, 3, 3, eyem());
-      put3w(Pns, 6, 0, 0, mscale(dt, eyem()));
-      put3w(Pns, 6, 3, 3, mscale(dt, RT));
+      const M3 RT = tp(R_3D);
+      put3w(Ptr, 6, 0, 0, mm(R_new, RT));
+      put3w(Ptr, 6, 3, 0, mm(ms(RT, -1.0), skew3(mv(RT, vsub(new_p, p_3D)))));
+      put3w(Ptr, 6, 3, 3, eye3());
+      put3w(Pns, 6, 0, 0, ms(eye3(), dt));
+      put3w(Pns, 6, 3, 3, ms(RT, dt));
 #pragma unroll
       for (int e = 0; e < 9; ++e) R3[e] = R_new.m[e];
-      st3(p3, new_p);
+      stV(p3, new_p);
     }
     __syncthreads();
     double a = 0.0, bq = 0.0;
@@ -292,48 +284,48 @@ __global__ void __launch_bounds__(64) wheel_kernel(WheelArgs A) {
   }
   const int k = A.k;
   if (tid == 0) {  // compute_linear_system_3D
-    const DM3 R_3D = ldm(R3);
-    const D3 p_3D = ld3(p3);
-    D3 pI0 = ld3(A.st.p0), pI1 = ld3(A.st.p1);
-    DM3 RG0 = ldm(A.st.R0), RG1 = ldm(A.st.R1);
-    const D3 pIinO = ld3(A.st.p_IinO);
-    const DM3 RItoO = ldm(A.st.R_ItoO);
-    const D3 pOinI = mvec(mscale(-1.0, mtr(RItoO)), pIinO);
-    DM3 RO0toO1 = mmul(mmul(mmul(RItoO, RG1), mtr(RG0)), mtr(RItoO));
-    const D3 r_ori = -1.0 * log3(mmul(R_3D, mtr(RO0toO1)));
-    const D3 p_est = mvec(mmul(RItoO, RG0), ((pI1 + mvec(mtr(RG1), pOinI)) - pI0) - mvec(mtr(RG0), pOinI));
-    const D3 r_pos = p_3D - p_est;
-    st3(resv, r_ori);
-    st3(resv + 3, r_pos);
+    const M3 R_3D = ldM(R3);
+    const V3 p_3D = ldV(p3);
+    V3 pI0 = ldV(A.st.p0), pI1 = ldV(A.st.p1);
+    M3 RG0 = ldM(A.st.R0), RG1 = ldM(A.st.R1);
+    const V3 pIinO = ldV(A.st.p_IinO);
+    const M3 RItoO = ldM(A.st.R_ItoO);
+    const V3 pOinI = mv(ms(tp(RItoO), -1.0), pIinO);
+    M3 RO0toO1 = mm(mm(mm(RItoO, RG1), tp(RG0)), tp(RItoO));
+    const V3 r_ori = vsc(log_so3(mm(R_3D, tp(RO0toO1))), -1.0);
+    const V3 p_est = mv(mm(RItoO, RG0), vsub(vsub(vadd(pI1, mv(tp(RG1), pOinI)), pI0), mv(tp(RG0), pOinI)));
+    const V3 r_pos = vsub(p_3D, p_est);
+    stV(resv, r_ori);
+    stV(resv + 3, r_pos);
     for (int e = 0; e < 6 * k; ++e) Hr[e] = 0.0;
-    pI0 = ld3(A.st.p0_fej), pI1 = ld3(A.st.p1_fej), RG0 = ldm(A.st.R0_fej), RG1 = ldm(A.st.R1_fej);
-    RO0toO1 = mmul(mmul(mmul(RItoO, RG1), mtr(RG0)), mtr(RItoO));
-    const DM3 RO1toO0 = mtr(RO0toO1);
-    const DM3 dzr_dth0 = mmul(mmul(mscale(-1.0, RItoO), RG1), mtr(RG0)), dzr_dth1 = RItoO;
-    const DM3 dzp_dth0 = mmul(RItoO, skewm((mvec(RG0, pI1) + mvec(mmul(RG0, mtr(RG1)), pOinI)) - mvec(RG0, pI0)));
-    const DM3 dzp_dp0 = mmul(mscale(-1.0, RItoO), RG0);
-    const DM3 dzp_dth1 = mmul(mmul(mmul(mscale(-1.0, RItoO), RG0), mtr(RG1)), skewm(pOinI));
-    const DM3 dzp_dp1 = mmul(RItoO, RG0);
+    pI0 = ldV(A.st.p0_fej), pI1 = ldV(A.st.p1_fej), RG0 = ldM(A.st.R0_fej), RG1 = ldM(A.st.R1_fej);
+    RO0toO1 = mm(mm(mm(RItoO, RG1), tp(RG0)), tp(RItoO));
+    const M3 RO1toO0 = tp(RO0toO1);
+    const M3 dzr_dth0 = mm(mm(ms(RItoO, -1.0), RG1), tp(RG0)), dzr_dth1 = RItoO;
+    const M3 dzp_dth0 = mm(RItoO, skew3(vsub(vadd(mv(RG0, pI1), mv(mm(RG0, tp(RG1)), pOinI)), mv(RG0, pI0))));
+    const M3 dzp_dp0 = mm(ms(RItoO, -1.0), RG0);
+    const M3 dzp_dth1 = mm(mm(mm(ms(RItoO, -1.0), RG0), tp(RG1)), skew3(pOinI));
+    const M3 dzp_dp1 = mm(RItoO, RG0);
     put3w(Hr, k, 0, 0, dzr_dth0), put3w(Hr, k, 0, 6, dzr_dth1);
     put3w(Hr, k, 3, 0, dzp_dth0), put3w(Hr, k, 3, 3, dzp_dp0), put3w(Hr, k, 3, 6, dzp_dth1), put3w(Hr, k, 3, 9, dzp_dp1);
     int hc = 12;
     if (A.op.do_calib_ext) {
-      put3w(Hr, k, 0, hc, msub(eyem(), RO0toO1));
-      put3w(Hr, k, 3, hc, madd(skewm(mvec(mmul(RItoO, RG0), pI1 - pI0) - mvec(RO1toO0, pIinO)), mmul(RO1toO0, skewm(pIinO))));
-      put3w(Hr, k, 3, hc + 3, madd(mscale(-1.0, RO1toO0), eyem()));
+      put3w(Hr, k, 0, hc, msb(eye3(), RO0toO1));
+      put3w(Hr, k, 3, hc, ma(skew3(vsub(mv(mm(RItoO, RG0), vsub(pI1, pI0)), mv(RO1toO0, pIinO))), mm(RO1toO0, skew3(pIinO))));
+      put3w(Hr, k, 3, hc + 3, ma(ms(RO1toO0, -1.0), eye3()));
       hc += 6;
     }
     if (A.op.do_calib_dt) {
-      const D3 w0 = ld3(A.st.w0), v0 = ld3(A.st.v0), w1 = ld3(A.st.w1), v1 = ld3(A.st.v1);
-      const D3 a = mvec(dzr_dth0, w0) + mvec(dzr_dth1, w1);
-      const D3 cc = ((mvec(dzp_dth0, w0) + mvec(dzp_dp0, v0)) + mvec(dzp_dth1, w1)) + mvec(dzp_dp1, v1);
-      Hr[0 * k + hc] = a.x, Hr[1 * k + hc] = a.y, Hr[2 * k + hc] = a.z;
-      Hr[3 * k + hc] = cc.x, Hr[4 * k + hc] = cc.y, Hr[5 * k + hc] = cc.z;
+      const V3 w0 = ldV(A.st.w0), v0 = ldV(A.st.v0), w1 = ldV(A.st.w1), v1 = ldV(A.st.v1);
+      const V3 a = vadd(mv(dzr_dth0, w0), mv(dzr_dth1, w1));
+      const V3 cc = vadd(vadd(vadd(mv(dzp_dth0, w0), mv(dzp_dp0, v0)), mv(dzp_dth1, w1)), mv(dzp_dp1, v1));
+      Hr[0 * k + hc] = a[0], Hr[1 * k + hc] = a[1], Hr[2 * k + hc] = a[2];
+      Hr[3 * k + hc] = cc[0], Hr[4 * k + hc] = cc[1], Hr[5 * k + hc] = cc[2];
       hc += 1;
     }
     if (A.op.do_calib_int) {
-      put3w(Hr, k, 0, hc, mscale(-1.0, ldm(dRdi)));
-      put3w(Hr, k, 3, hc, mscale(-1.0, ldm(dpdi)));
+      put3w(Hr, k, 0, hc, ms(ldM(dRdi), -1.0));
+      put3w(Hr, k, 3, hc, ms(ldM(dpdi), -1.0));
     }
     // eigenbasis of the preintegrated covariance (X is free after the recursion)
     for (int e = 0; e < 36; ++e) X[e] = Cov[e];
@@ -483,26 +475,26 @@ __global__ void __launch_bounds__(64) wheel2d_kernel(WheelArgs A) {
       head = head_next, px = px_next, py = py_next;
     }
     // compute_linear_system_2D
-    D3 pI0 = ld3(A.st.p0), pI1 = ld3(A.st.p1);
-    DM3 RG0 = ldm(A.st.R0), RG1 = ldm(A.st.R1);
-    const D3 pIinO = ld3(A.st.p_IinO);
-    const DM3 RItoO = ldm(A.st.R_ItoO);
-    const D3 pOinI = mvec(mscale(-1.0, mtr(RItoO)), pIinO);
-    const double theta_est = log3(mmul(mmul(mmul(RItoO, RG1), mtr(RG0)), mtr(RItoO))).z;
-    const D3 d_est = mvec(mmul(RItoO, RG0), ((pI1 + mvec(mtr(RG1), pOinI)) - pI0) - mvec(mtr(RG0), pOinI));
+    V3 pI0 = ldV(A.st.p0), pI1 = ldV(A.st.p1);
+    M3 RG0 = ldM(A.st.R0), RG1 = ldM(A.st.R1);
+    const V3 pIinO = ldV(A.st.p_IinO);
+    const M3 RItoO = ldM(A.st.R_ItoO);
+    const V3 pOinI = mv(ms(tp(RItoO), -1.0), pIinO);
+    const double theta_est = log_so3(mm(mm(mm(RItoO, RG1), tp(RG0)), tp(RItoO)))[2];
+    const V3 d_est = mv(mm(RItoO, RG0), vsub(vsub(vadd(pI1, mv(tp(RG1), pOinI)), pI0), mv(tp(RG0), pOinI)));
     resv[0] = theta_est - head;
-    resv[1] = px - d_est.x;
-    resv[2] = py - d_est.y;
+    resv[1] = px - d_est[0];
+    resv[2] = py - d_est[1];
     for (int e = 0; e < 3 * k; ++e) Hr[e] = 0.0;
-    pI0 = ld3(A.st.p0_fej), pI1 = ld3(A.st.p1_fej), RG0 = ldm(A.st.R0_fej), RG1 = ldm(A.st.R1_fej);
-    const DM3 RO0toO1 = mmul(mmul(mmul(RItoO, RG1), mtr(RG0)), mtr(RItoO)), RO1toO0 = mtr(RO0toO1);
-    const DM3 A0 = mmul(mmul(mscale(-1.0, RItoO), RG1), mtr(RG0));
-    const DM3 Pth0 = mmul(RItoO, skewm(mvec(RG0, (pI1 + mvec(mtr(RG1), pOinI)) - pI0)));
-    const DM3 Pp0 = mmul(mscale(-1.0, RItoO), RG0);
-    const DM3 Pth1 = mmul(mmul(mmul(mscale(-1.0, RItoO), RG0), mtr(RG1)), skewm(pOinI));
-    const DM3 Pp1 = mmul(RItoO, RG0);
-    auto row_of = [&](int r, int c0, const DM3 &B, int br) {
-      for (int c = 0; c < 3; ++c) Hr[r * k + c0 + c] = B.m[3 * br + c];
+    pI0 = ldV(A.st.p0_fej), pI1 = ldV(A.st.p1_fej), RG0 = ldM(A.st.R0_fej), RG1 = ldM(A.st.R1_fej);
+    const M3 RO0toO1 = mm(mm(mm(RItoO, RG1), tp(RG0)), tp(RItoO)), RO1toO0 = tp(RO0toO1);
+    const M3 A0 = mm(mm(ms(RItoO, -1.0), RG1), tp(RG0));
+    const M3 Pth0 = mm(RItoO, skew3(mv(RG0, vsub(vadd(pI1, mv(tp(RG1), pOinI)), pI0))));
+    const M3 Pp0 = mm(ms(RItoO, -1.0), RG0);
+    const M3 Pth1 = mm(mm(mm(ms(RItoO, -1.0), RG0), tp(RG1)), skew3(pOinI));
+    const M3 Pp1 = mm(RItoO, RG0);
+    auto row_of = [&](int r, int c0, const M3 &B, int br) {
+      for (int c = 0; c < 3; ++c) Hr[r * k + c0 + c] = B(br, c);
     };
     row_of(0, 0, A0, 2);
     row_of(0, 6, RItoO, 2);
@@ -514,9 +506,9 @@ __global__ void __launch_bounds__(64) wheel2d_kernel(WheelArgs A) {
     }
     int hc = 12;
     if (A.op.do_calib_ext) {
-      row_of(0, hc, msub(eyem(), RO0toO1), 2);
-      const DM3 Dth = madd(skewm(mvec(mmul(RItoO, RG0), pI1 - pI0) - mvec(RO1toO0, pIinO)), mmul(RO1toO0, skewm(pIinO)));
-      const DM3 Dp = madd(mscale(-1.0, RO1toO0), eyem());
+      row_of(0, hc, msb(eye3(), RO0toO1), 2);
+      const M3 Dth = ma(skew3(vsub(mv(mm(RItoO, RG0), vsub(pI1, pI0)), mv(RO1toO0, pIinO))), mm(RO1toO0, skew3(pIinO)));
+      const M3 Dp = ma(ms(RO1toO0, -1.0), eye3());
       for (int r = 0; r < 2; ++r) {
         row_of(1 + r, hc, Dth, r);
         row_of(1 + r, hc + 3, Dp, r);
@@ -524,12 +516,12 @@ __global__ void __launch_bounds__(64) wheel2d_kernel(WheelArgs A) {
       hc += 6;
     }
     if (A.op.do_calib_dt) {
-      const D3 w0 = ld3(A.st.w0), v0 = ld3(A.st.v0), w1 = ld3(A.st.w1), v1 = ld3(A.st.v1);
-      const D3 a = mvec(A0, w0) + mvec(RItoO, w1);
-      const D3 cc = ((mvec(Pth0, w0) + mvec(Pp0, v0)) + mvec(Pth1, w1)) + mvec(Pp1, v1);
-      Hr[0 * k + hc] = a.z;
-      Hr[1 * k + hc] = cc.x;
-      Hr[2 * k + hc] = cc.y;
+      const V3 w0 = ldV(A.st.w0), v0 = ldV(A.st.v0), w1 = ldV(A.st.w1), v1 = ldV(A.st.v1);
+      const V3 a = vadd(mv(A0, w0), mv(RItoO, w1));
+      const V3 cc = vadd(vadd(vadd(mv(Pth0, w0), mv(Pp0, v0)), mv(Pth1, w1)), mv(Pp1, v1));
+      Hr[0 * k + hc] = a[2];
+      Hr[1 * k + hc] = cc[0];
+      Hr[2 * k + hc] = cc[1];
       hc += 1;
     }
     if (A.op.do_calib_int)

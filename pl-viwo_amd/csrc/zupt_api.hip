@@ -27,14 +27,12 @@
 #include <vector>
 
 #include "plv_ctx.hpp"
-#include "so3_dev.hpp"
+#include "so3.hpp"
 #include "update_state.hpp"
 #include "wave_ops.hpp"
 
 namespace plv {
 namespace {
-
-using namespace so3;
 
 #define TRY(expr)                  \
   do {                             \
@@ -70,14 +68,14 @@ __global__ void __launch_bounds__(64) zupt_kernel(ZuptArgs A) {
   if (tid == 0) {
     const double T = s[0];
     const double cw = sqrt(T / A.noise_mult) / A.sigma_w, ca = sqrt(T / A.noise_mult) / A.sigma_a;
-    const D3 g = ld3(A.gravity);
-    const D3 w_bar = (1.0 / T) * D3{s[1], s[2], s[3]}, a_bar = (1.0 / T) * D3{s[4], s[5], s[6]};
-    const D3 g_I = mvec(q2R(DQ{A.imu.q[0], A.imu.q[1], A.imu.q[2], A.imu.q[3]}), g);
-    const D3 g_I_fej = mvec(q2R(DQ{A.imu.q_fej[0], A.imu.q_fej[1], A.imu.q_fej[2], A.imu.q_fej[3]}), g);
-    st3(resv, (-cw) * (w_bar - ld3(A.imu.bg)));
-    st3(resv + 3, (-ca) * ((a_bar - ld3(A.imu.ba)) - g_I));
-    st3(resv + 6, (-1.0 / A.sigma_v) * ld3(A.imu.v));
-    const DM3 B = mscale(-ca, skewm(g_I_fej));
+    const V3 g = ldV(A.gravity);
+    const V3 w_bar = vsc(ldV(s + 1), 1.0 / T), a_bar = vsc(ldV(s + 4), 1.0 / T);
+    const V3 g_I = mv(quat_2_Rot(ldQ(A.imu.q)), g);
+    const V3 g_I_fej = mv(quat_2_Rot(ldQ(A.imu.q_fej)), g);
+    stV(resv, vsc(vsub(w_bar, ldV(A.imu.bg)), -cw));
+    stV(resv + 3, vsc(vsub(vsub(a_bar, ldV(A.imu.ba)), g_I), -ca));
+    stV(resv + 6, vsc(ldV(A.imu.v), -1.0 / A.sigma_v));
+    const M3 B = ms(skew3(g_I_fej), -ca);
 #pragma unroll
     for (int e = 0; e < 9; ++e) blk[e] = B.m[e];
     cw_s = cw, ca_s = ca;

@@ -19,7 +19,7 @@ Over-limit sizes never reach a kernel: 64 updating rows are refused by launch_ch
 CHI2_MAXM`, before chi2_t_kernel / chi2_gate_kernel are launched) both for plv_slam_initialize and plv_slam_update, and a clone beyond
 cfg.max_state_dim by plv_cov_clone's own check (propagate_api.hip, before d_P2 is reserved).
 
-Sixteen one-line mutations of the three files and of so3_dev.hpp (values only: no index or loop bound leaves its allocation),
+Sixteen one-line mutations of the three files and of so3_dev.hpp (since folded into so3.hpp: exp3 = exp_so3, Jl = Jl_so3; values only: no index or loop bound leaves its allocation),
 each built into a library of its own on a scratch copy and run on the MI355X against this module and against the three files the suite
 had before (test_gpu_propagate.py, test_gpu_wheel.py, test_gpu_slam.py):
 
