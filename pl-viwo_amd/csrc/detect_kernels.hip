@@ -106,6 +106,12 @@ __global__ void __launch_bounds__(256) fast_tiles_kernel(DetectParams P, int til
 // ---- K4, stage 2: the reference's "sort by response, keep the first num_features_grid" per cell.  Every candidate counts the
 // keys above its own: that is its position in the sorted order, the first nfg write their slot.  Then the bounds / mask /
 // occupied-box tests of Grider_GRID.h:141-147 and TrackKLT.cpp:455-461 per kept corner.
+// A cell can hold more local maxima than the LDS takes (strict 3x3 suppression leaves one per 2x2 block: 3 240 in a 150 x 96 cell, 56 109
+// in a 640 x 360 one).  Every maximum is stored (P.cand_cap is that bound), and a cell with more than P.lds_cap of them finds its nfg
+// largest keys by a radix selection over the stored list (BIG; the key's 40 significant bits, 8 at a time: the score, then the raster
+// order, so that a mass tie at the cut-off score is resolved exactly); those nfg keys are then ranked like the survivors of the
+// histogram cut-off.  BIG = false is built for the shapes whose bound fits the LDS: the selection is not in that kernel at all.
+template <bool BIG>
 __global__ void __launch_bounds__(256) fast_topk_kernel(DetectParams P, const unsigned long long *__restrict__ cand, int *__restrict__ cand_n) {
   // Round 4: the rank of a key is only wanted when it is below nfg (REF Grider_GRID.h:125-128 keeps the first num_features_grid of the
   // sorted cell), and a key's rank is the number of LARGER keys — so only keys at or above the score of the nfg-th best can have one,
@@ -115,21 +121,76 @@ __global__ void __launch_bounds__(256) fast_topk_kernel(DetectParams P, const un
   extern __shared__ unsigned long long keys[];
   __shared__ int hist[256], wtot[4], wcut[4], n_sel;
   const int cell = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int nc = min(cand_n[cell], P.cand_cap);
-  int *sel = (int *)(keys + P.cand_cap);  // indices of the survivors
+  const int n_found = cand_n[cell];
+  const int nc = min(n_found, P.cand_cap);
+  int *sel = (int *)(keys + P.lds_cap);  // indices of the survivors
   const int cw = P.cell_w, chh = P.cell_h;
   const int x0 = P.cells[2 * cell] * cw, y0 = P.cells[2 * cell + 1] * chh;
   hist[t] = 0;
   if (t == 0) n_sel = 0;
-  for (int r = nc + t; r < P.nfg; r += 256) P.out_valid[cell * P.nfg + r] = 0;
+  // every slot of the cell starts invalid, not only those beyond the key count: subpix_kernel reads the position of a valid slot
+  // whatever it holds, and a slot no winner reached holds what the buffer held before (the winners set theirs below, behind barriers)
+  for (int r = t; r < P.nfg; r += 256) P.out_valid[cell * P.nfg + r] = 0;
   __syncthreads();
-  for (int i = t; i < nc; i += 256) {
-    const unsigned long long k = cand[(size_t)cell * P.cand_cap + i];
-    keys[i] = k;
-    atomicAdd(&hist[min((int)(k >> 32), 255)], 1);
+  const unsigned long long *ck = cand + (size_t)cell * P.cand_cap;
+  int n_lds = nc;  // keys staged in LDS
+  if (BIG && nc > P.lds_cap) {  // (uniform)
+    // the nfg-th largest key, byte by byte from the top: `prefix` under `pmask` is what is known of it, `want` its rank among the keys
+    // that share the prefix.  nc > lds_cap >= nfg, so it exists; keys are unique, so exactly nfg keys are at or above it.
+    __shared__ int above;
+    unsigned long long prefix = 0, pmask = 0;
+    int want = P.nfg;
+    for (int shift = 32; shift >= 0; shift -= 8) {
+      for (int i = t; i < nc; i += 256) {
+        const unsigned long long k = ck[i];
+        if ((k & pmask) == prefix) atomicAdd(&hist[(int)(k >> shift) & 255], 1);
+      }
+      if (t == 0) above = 0;
+      __syncthreads();
+      int v = hist[t];  // suffix counts, as below
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int u = __shfl_down(v, off);
+        if (lane + off < 64) v += u;
+      }
+      if (lane == 0) wtot[wave] = v;
+      __syncthreads();
+      for (int w = wave + 1; w < 4; ++w) v += wtot[w];
+      const unsigned long long ok_mask = __ballot(v >= want);
+      if (lane == 0) wcut[wave] = ok_mask ? 64 * wave + 63 - __clzll((long long)ok_mask) : -1;
+      __syncthreads();
+      const int b = max(max(max(wcut[0], wcut[1]), max(wcut[2], wcut[3])), 0);
+      if (t == b + 1) above = v;  // keys that share the prefix and have a larger byte here
+      hist[t] = 0;
+      __syncthreads();
+      want -= above;
+      prefix |= (unsigned long long)b << shift;
+      pmask |= 0xffULL << shift;
+      __syncthreads();
+    }
+    for (int i = t; i < nc; i += 256) {
+      const unsigned long long k = ck[i];
+      if (k < prefix) continue;
+      const int q = atomicAdd(&n_sel, 1);
+      if (q < P.lds_cap) keys[q] = k;
+    }
+    __syncthreads();
+    n_lds = min(n_sel, P.lds_cap);
+    __syncthreads();
+    if (t == 0) n_sel = 0;
+    for (int i = t; i < n_lds; i += 256) atomicAdd(&hist[min((int)(keys[i] >> 32), 255)], 1);
+  } else {
+    for (int i = t; i < nc; i += 256) {
+      const unsigned long long k = ck[i];
+      keys[i] = k;
+      atomicAdd(&hist[min((int)(k >> 32), 255)], 1);
+    }
   }
   __syncthreads();
-  if (t == 0) cand_n[cell] = 0;  // ready for the next frame (stream order: stage 1 of the next detection comes after this kernel)
+  if (t == 0) {
+    cand_n[cell] = 0;  // ready for the next frame (stream order: stage 1 of the next detection comes after this kernel)
+    P.out_over[cell] = n_found > P.cand_cap ? 1 : 0;  // more maxima than were stored: the host refuses the result
+  }
   // suffix counts S[t] = keys with score >= t (scores above 255 sit in bin 255), then the largest t with S[t] >= nfg
   int v = hist[t];
 #pragma unroll
@@ -144,12 +205,12 @@ __global__ void __launch_bounds__(256) fast_topk_kernel(DetectParams P, const un
   if (lane == 0) wcut[wave] = ok_mask ? 64 * wave + 63 - __clzll((long long)ok_mask) : -1;
   __syncthreads();
   const int cut = max(max(wcut[0], wcut[1]), max(wcut[2], wcut[3]));  // -1: fewer than nfg keys in the cell, all of them rank
-  for (int i = t; i < nc; i += 256)
+  for (int i = t; i < n_lds; i += 256)
     if (min((int)(keys[i] >> 32), 255) >= cut) sel[atomicAdd(&n_sel, 1)] = i;
   __syncthreads();
   const int M = n_sel;
   // ranks of the survivors; the keys that get an output slot (rank < nfg) are collected
-  unsigned long long *wkey = (unsigned long long *)(sel + P.cand_cap + (P.cand_cap & 1));  // [nfg] (8-byte aligned: the index list is padded to even)
+  unsigned long long *wkey = (unsigned long long *)(sel + P.lds_cap + (P.lds_cap & 1));  // [nfg] (8-byte aligned: the index list is padded to even)
   int *wrank = (int *)(wkey + P.nfg);                                                       // [nfg]
   __shared__ int n_win;
   if (t == 0) n_win = 0;
@@ -159,14 +220,14 @@ __global__ void __launch_bounds__(256) fast_topk_kernel(DetectParams P, const un
     int rank = 0;
     for (int j = 0; j < M; ++j) rank += keys[sel[j]] > k;
     if (rank >= P.nfg) continue;
-    const int w = atomicAdd(&n_win, 1);  // (< nfg: ranks below nfg are distinct)
-    wkey[w] = k, wrank[w] = rank;
+    const int w = atomicAdd(&n_win, 1);  // (< nfg: ranks below nfg are distinct while the keys are — a stale list could repeat one)
+    if (w < P.nfg) wkey[w] = k, wrank[w] = rank;
   }
   __syncthreads();
   // REF TrackKLT.cpp:486-520: a detection inside the mask or within min_px_dist of an existing point is dropped — the test against the
   // existing points by the whole workgroup per winner (it used to be one thread walking all of them per winner: 500 dependent loads at
   // configs[3], the launch's slowest thread and most of its 90 us)
-  const int nw = n_win;
+  const int nw = min(n_win, P.nfg);
   for (int w = 0; w < nw; ++w) {
     const unsigned long long k = wkey[w];
     const int idx = 0x7fffffff - (int)(k & 0xffffffffULL);
@@ -267,9 +328,10 @@ __global__ void __launch_bounds__(64) subpix_kernel(const uint8_t *__restrict__ 
 }
 
 int launch_fast_cells(plv_ctx *ctx, const DetectParams &P, int n_cells, unsigned long long *d_cand, int *d_cand_n) {
-  const size_t topk_lds = (size_t)P.cand_cap * 8 + (size_t)(P.cand_cap + (P.cand_cap & 1)) * 4 + (size_t)std::max(P.nfg, 1) * 12;
-  if (P.cell_w * P.cell_h > 0x7fffffff / 2 || topk_lds > 60 * 1024) {
-    set_last_error("FAST: cell %dx%d / candidate capacity %d out of range", P.cell_w, P.cell_h, P.cand_cap);
+  const size_t topk_lds = (size_t)P.lds_cap * 8 + (size_t)(P.lds_cap + (P.lds_cap & 1)) * 4 + (size_t)std::max(P.nfg, 1) * 12;
+  if (P.cell_w * (long long)P.cell_h > 0x7fffffff / 2 || P.cand_cap < fast_cell_bound(P.cell_w, P.cell_h) || P.nfg > P.lds_cap || topk_lds > 60 * 1024) {
+    set_last_error("FAST: cell %dx%d / %d features per cell / candidate capacity %d (%d staged) out of range", P.cell_w, P.cell_h, P.nfg,
+                   P.cand_cap, P.lds_cap);
     return PLV_E_CAPACITY;
   }
   const int tiles_x = (P.cell_w + FAST_TILE - 1) / FAST_TILE, tiles_y = (P.cell_h + FAST_TILE - 1) / FAST_TILE;
@@ -278,8 +340,11 @@ int launch_fast_cells(plv_ctx *ctx, const DetectParams &P, int n_cells, unsigned
     hipLaunchKernelGGL(fast_tiles_kernel, dim3(n_cells * tiles_x * tiles_y), dim3(256), 0, ctx->stream, P, tiles_x, tiles_y, d_cand, d_cand_n);
   }
   {
-    ProfScope ps(ctx->prof, "fast_topk_kernel", ctx->stream);
-    hipLaunchKernelGGL(fast_topk_kernel, dim3(n_cells), dim3(256), topk_lds, ctx->stream, P, d_cand, d_cand_n);  // keys + survivor indices + winners
+    ProfScope ps(ctx->prof, "fast_topk_kernel", ctx->stream);  // keys + survivor indices + winners in LDS
+    if (P.cand_cap <= P.lds_cap)
+      hipLaunchKernelGGL(fast_topk_kernel<false>, dim3(n_cells), dim3(256), topk_lds, ctx->stream, P, d_cand, d_cand_n);
+    else
+      hipLaunchKernelGGL(fast_topk_kernel<true>, dim3(n_cells), dim3(256), topk_lds, ctx->stream, P, d_cand, d_cand_n);
   }
   PLV_HIP_CHECK(hipGetLastError());
   return PLV_OK;

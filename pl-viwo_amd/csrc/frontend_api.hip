@@ -19,7 +19,7 @@ struct DetJob {  // one top-up detection between its host stages (plv_perform_de
   std::vector<float> pts;            // kept points
   std::vector<uint64_t> ids;
   int cw = 0, ch = 0, nfg = 0, sxp = 0, syp = 0, n_cells = 0, n_slots = 0;
-  char *h_out = nullptr;             // pinned: [xy n_slots x 2 f32][resp n_slots f32][valid n_slots u8]
+  char *h_out = nullptr;             // pinned: [xy n_slots x 2 f32][resp n_slots f32][valid n_slots u8][over n_cells u8]
   // what an ahead-of-time job was started from
   bool active = false, has_mask = false;
   int fed = 0, n_in = 0;
@@ -786,9 +786,9 @@ int det_launch(plv_ctx *ctx, FrontState *s, const PyrDesc &pyr, const uint8_t *m
   const plv_config &c = ctx->cfg;
   const int n_cells = J.n_cells, n_slots = J.n_slots;
   const size_t o_cells = 0, o_boxes = ((size_t)n_cells * 8 + 15) & ~(size_t)15, in_total = o_boxes + ((J.boxes.size() * 4 + 15) & ~(size_t)15);
-  TRY(s->det_pin.reserve(in_total + (size_t)n_slots * 13 + 128));
+  TRY(s->det_pin.reserve(in_total + (size_t)n_slots * 13 + (size_t)n_cells + 128));
   TRY(s->det_in.reserve(in_total + 16));
-  const size_t o_xy = 0, o_resp = (size_t)n_slots * 8, o_valid = (size_t)n_slots * 12, out_total = (size_t)n_slots * 13;
+  const size_t o_xy = 0, o_resp = (size_t)n_slots * 8, o_valid = (size_t)n_slots * 12, o_over = (size_t)n_slots * 13, out_total = o_over + (size_t)n_cells;
   TRY(s->det_out.reserve(out_total + 16));
   char *hp = s->det_pin.as<char>();
   J.h_out = hp + ((in_total + 63) & ~(size_t)63);  // results land behind the inputs (both may be in flight at once)
@@ -824,13 +824,17 @@ int det_launch(plv_ctx *ctx, FrontState *s, const PyrDesc &pyr, const uint8_t *m
   P.cell_h = J.syp;
   P.threshold = c.fast_threshold;
   P.nfg = J.nfg;
-  P.cand_cap = 4096;
+  // every local maximum a cell can have is stored: none is dropped, whatever the image (in whole blocks of 4096 keys: the lists of
+  // the default shape, 3 240 keys at most, lie where they always did)
+  P.cand_cap = (int)std::min<long long>(((long long)fast_cell_bound(J.sxp, J.syp) + 4095) / 4096 * 4096, 0x7fffffff);
+  P.lds_cap = 4096;
   P.boxes = (const int *)(s->det_in.as<char>() + o_boxes);
   P.n_boxes = (int)J.boxes.size() / 2;
   P.min_px_dist = c.min_px_dist;
   P.out_xy = (float *)(s->det_out.as<char>() + o_xy);
   P.out_resp = (float *)(s->det_out.as<char>() + o_resp);
   P.out_valid = (uint8_t *)(s->det_out.as<char>() + o_valid);
+  P.out_over = (uint8_t *)(s->det_out.as<char>() + o_over);
   {  // per-cell candidate lists of fast_tiles_kernel; the counters start at zero and fast_topk_kernel leaves them at zero
     const size_t all_cells = (size_t)c.grid_x * c.grid_y;
     if (s->det_cand_n.cap < all_cells * 4) {
@@ -846,6 +850,20 @@ int det_launch(plv_ctx *ctx, FrontState *s, const PyrDesc &pyr, const uint8_t *m
   ctx->stream = keep;
   TRY(rc);
   PLV_HIP_CHECK(plv::memcpy_async(J.h_out, s->det_out.p, out_total, hipMemcpyDeviceToHost, stream));
+  return PLV_OK;
+}
+
+// The backstop behind the candidate storage: a cell that counted more maxima than were stored (its counter was not at zero when the
+// frame began, say) has no trustworthy top-k.  The whole detection is refused, before det_post has written anything.
+int det_check(const DetJob &J) {
+  if (J.n_slots <= 0) return PLV_OK;
+  const uint8_t *over = (const uint8_t *)(J.h_out + (size_t)J.n_slots * 13);
+  for (int i = 0; i < J.n_cells; ++i)
+    if (over[i]) {
+      set_last_error("plv_perform_detection: cell (%d, %d) of %dx%d pixels had more corner candidates than were stored", J.cells[2 * i],
+                     J.cells[2 * i + 1], J.sxp, J.syp);
+      return PLV_E_CAPACITY;
+    }
   return PLV_OK;
 }
 
@@ -917,6 +935,7 @@ int plv_perform_detection(plv_ctx *ctx, int which, const uint8_t *mask, float *p
     A.active = false;
     if (same) {
       if ((int)A.ids.size() > cap) return PLV_E_CAPACITY;
+      TRY(det_check(A));
       det_post(ctx, A, pts, ids, cap, currid, n_out);
       return PLV_OK;
     }
@@ -927,6 +946,7 @@ int plv_perform_detection(plv_ctx *ctx, int which, const uint8_t *mask, float *p
   if (J.n_slots > 0) {
     TRY(det_launch(ctx, s, pyr, mask, J, ctx->stream));
     TRY(sync(ctx));
+    TRY(det_check(J));
   }
   det_post(ctx, J, pts, ids, cap, currid, n_out);
   return PLV_OK;

@@ -347,6 +347,13 @@ class DetectOracle:
     def _unused(self):
         pass
 
+    def fast_score(self, img, x, y, thr):
+        """orc_fast_score: the FAST-9/16 score of one pixel (at least 3 pixels inside the image), 0 when it is no corner at thr"""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        self.lib.orc_fast_score.argtypes = [u8, C.c_int, C.c_int, C.c_int, C.c_int]
+        self.lib.orc_fast_score.restype = C.c_int
+        return int(self.lib.orc_fast_score(img.ctypes.data_as(u8), img.shape[1], int(x), int(y), int(thr)))
+
     def fast_roi(self, img, x0, y0, w, h, thr, cap=20000):
         img = np.ascontiguousarray(img, dtype=np.uint8)
         xy = np.zeros((cap, 2), dtype=np.float32)
