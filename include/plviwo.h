@@ -1196,6 +1196,78 @@ int plv_traj_rpe(plv_ctx *ctx, int method, int n, const double *est_poses, const
 int plv_traj_nees(plv_ctx *ctx, int method, int n, const double *est_poses, const double *gt_poses, const double *cov_ori,
                   const double *cov_pos, double *nees_ori, double *nees_pos, int *n_valid, plv_stats *ori, plv_stats *pos);
 
+/* ================================================================ track image (display path)
+ *
+ * The picture the reference publishes per camera frame: TrackBase::display_history / display_active (REF: open_vins/ov_core/src/track/
+ * TrackBase.cpp:90-100, 119-265) through UpdaterCamera::get_track_img (REF: UpdaterCamera.cpp:486-500), and the point-line picture of
+ * TrackLSD::DrawFeatures (REF: TrackLSD.cpp:832-887), drawn on the device over the equalised image the tracker works on.  The layout,
+ * colours and paint order are the reference's; the rasterisation is the library's own — cv::circle / cv::line / cv::rectangle "as laid
+ * out, not as rasterised" (DESIGN.md "The track image") — integer predicates that hold or fail per pixel on their own:
+ *   PLV_DRAW_RING  pixels with a <= (x - x0)^2 + (y - y0)^2 <= b (a filled disc of radius r: a = 0, b = r * r)
+ *   PLV_DRAW_BOX   outline of the rectangle with the corners (x0, y0), (x1, y1), ordered first: x on a vertical edge and y0 <= y <= y1,
+ *                  or y on a horizontal edge and x0 <= x <= x1
+ *   PLV_DRAW_SEG   dx = x1 - x0, dy = y1 - y0; x-major when |dx| >= |dy|: for every x between the ends, i = |x - x0|, the pixel
+ *                  (x, y0 + sign(dy) * floor((2 i |dy| + |dx|) / (2 |dx|))); dx = dy = 0: the one pixel; y-major with the roles swapped;
+ *                  a = thickness: the pixels at minor coordinate + 0 .. a - 1 (the layers use 1 and 2)
+ * Pixels outside the image are clipped.  The list is painted in order: the last primitive that covers a pixel gives its three bytes,
+ * a pixel nothing covers is (g, g, g) of the grey image.  Where the mask byte is non-zero, byte 2 of the pixel then becomes
+ * min(255, c + 26) for even c and min(255, c + 25) for odd c (cv::addWeighted(mask * 0.1 + img) on channel 2 with round-half-to-even,
+ * REF: TrackBase.cpp:257-260).  Coordinates beyond +-2^24 are refused (the predicates are evaluated in 64 bits). */
+enum { PLV_DRAW_RING = 0, PLV_DRAW_BOX = 1, PLV_DRAW_SEG = 2 };
+typedef struct plv_draw_prim {
+  int32_t kind, x0, y0, x1, y1, a, b;
+  uint8_t rgb[3], pad;
+} plv_draw_prim;
+/* The rasteriser alone (host in, host out, synchronous), any size from 1 x 1 (3 w h below 2^31): grey w x h bytes, rows `stride` >= w
+ * apart; prims [n]; mask (nullable) w x h bytes, rows mask_stride >= w apart; rgb 3 w x h bytes, rows rgb_stride >= 3 w apart.  An
+ * unknown kind, a NULL where data is needed, a stride below the row size or a coordinate beyond +-2^24: PLV_E_BADARG, rgb untouched. */
+int plv_draw_primitives(plv_ctx *ctx, const uint8_t *grey, int stride, int w, int h, const plv_draw_prim *prims, int n,
+                        const uint8_t *mask, int mask_stride, uint8_t *rgb, int rgb_stride);
+
+/* Layers of the track image.  small = min(W, H) < 400 (REF: TrackBase.cpp:127).  A float coordinate v becomes rne(v), round-half-to-even
+ * of the float32 value; a primitive with a non-finite coordinate or |v| > 2^20 is dropped.
+ *   PLV_VIZ_HISTORY  display_history: for every point of plv_tracker_last, in that order: if its id is highlighted a box at +-5 (+-3 when
+ *                    small; corners rne(x -/+ d), float32) and a disc of radius 2 (1), both (0, 255, 0); then, for the track the
+ *                    database holds for the id (n observations, none: skipped), z = n - 1 down to 1 while n - z <= max_tracks:
+ *                    channel k = clamp(c2[k] - (int)(1.0 * c1[k] / n * z), 0, 255), a disc (radius 2, 1 when small) at uv[z] and,
+ *                    when z + 1 < n, a thickness-1 segment uv[z] -> uv[z + 1]; for an id in `flagged` (the reference's Chi_test ==
+ *                    false branch, :188-207, whose flag the caller keeps) the colour is (0, 255, 255 - (int)(1.0 * 255 / n * z)) and
+ *                    the disc has radius 2
+ *   PLV_VIZ_ACTIVE   display_active: per last point a disc of radius 2 (1 when small) in (r1, g1, b1), then a box at +-3 in (r2, g2, b2)
+ *   PLV_VIZ_LINES    DrawFeatures, painted after the point layers: for line i of plv_line_tracker_last whose id is in the line
+ *                    database, colour ((i * 128) % 255, (i * 53) % 255, (i * 23) % 255): a thickness-2 segment with the end points
+ *                    (int)((double)v + 0.5), then a ring 49 .. 81 around every point of the last feed on that line (ascending point
+ *                    id: plv_line_tracker_last_points; ids that are not among the last points are skipped)
+ *   PLV_VIZ_MASK     the mask of the last feed, when there was one
+ * The overlay text of the reference ("init", "CAM:0") is the caller's to draw. */
+enum { PLV_VIZ_HISTORY = 1, PLV_VIZ_ACTIVE = 2, PLV_VIZ_LINES = 4, PLV_VIZ_MASK = 8 };
+typedef struct plv_track_image_options {
+  int layers;              /* PLV_VIZ_* bits */
+  int r1, g1, b1;          /* get_track_img passes 255, 255, 0 ... */
+  int r2, g2, b2;          /* ... and 255, 255, 255 */
+  int max_tracks;          /* 50 (REF: TrackBase.cpp:172) */
+  int n_highlighted;
+  const uint64_t *highlighted; /* [n_highlighted] ids drawn with the green box (the in-state landmarks) */
+  int n_flagged;
+  const uint64_t *flagged;     /* [n_flagged] ids whose history takes the Chi_test == false colours; may be NULL */
+} plv_track_image_options;
+/* get_track_img's colours, 50 tracks, the history layer, no lists. */
+void plv_track_image_options_default(plv_track_image_options *opt);
+/* The layers of `opt` over level 0 of the newest pyramid (what plv_pyramid_download(PLV_PYR_CUR, 0) returns), read where it lies: rgb
+ * is 3 W x H bytes, rows rgb_stride >= 3 W apart.  Before the first feed: the code plv_pyramid_download returns then.  The kernel goes
+ * on the context's stream behind the launch that writes that image and the call waits on an event of its own behind the result copy;
+ * it does not wait for work on the context's side streams (the detection started ahead, the prior factor), and it joins the line
+ * tracker's worker only when PLV_VIZ_LINES is asked for.  Read-only: tracker, databases, covariance and everything in flight are as
+ * they were, on a failing exit too. */
+int plv_track_image(plv_ctx *ctx, const plv_track_image_options *opt, uint8_t *rgb, int rgb_stride);
+/* The primitive list plv_track_image would paint, without painting (diagnostic).  *n receives the count; cap too small:
+ * PLV_E_BADARG with *n set, nothing written. */
+int plv_track_image_primitives(plv_ctx *ctx, const plv_track_image_options *opt, plv_draw_prim *prims, int cap, int *n);
+/* The point-on-line relations of the last line feed as CSR: the points on line i of plv_line_tracker_last are
+ * rel_id[rel_ptr[i]] .. rel_id[rel_ptr[i + 1]), ascending.  rel_ptr holds cap_lines + 1 entries.  *n_lines receives the number of
+ * lines (rel_ptr == NULL only queries it).  cap_lines too small: PLV_E_CAPACITY, nothing written; cap_ids too small:
+ * PLV_E_CAPACITY with rel_ptr written (its last entry is the number of ids needed). */
+int plv_line_tracker_last_points(plv_ctx *ctx, int *rel_ptr, uint64_t *rel_id, int cap_lines, int cap_ids, int *n_lines);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement aids: bench.py and the tests read and switch these; a product caller has no use for them.

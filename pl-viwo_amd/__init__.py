@@ -53,6 +53,39 @@ class PlvConfig(C.Structure):
     ]
 
 
+class PlvDrawPrim(C.Structure):
+    """plv_draw_prim: one primitive of the track image (32 bytes)"""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "x0", "y0", "x1", "y1", "a", "b")] + [("rgb", C.c_uint8 * 3), ("pad", C.c_uint8)]
+
+
+# the same record as a numpy dtype: Context.draw_primitives takes and Context.track_image_primitives returns arrays of it
+DRAW_PRIM_DTYPE = np.dtype([("kind", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("a", "<i4"), ("b", "<i4"),
+                            ("rgb", "u1", (3,)), ("pad", "u1")])
+PLV_DRAW_RING, PLV_DRAW_BOX, PLV_DRAW_SEG = 0, 1, 2
+PLV_VIZ_HISTORY, PLV_VIZ_ACTIVE, PLV_VIZ_LINES, PLV_VIZ_MASK = 1, 2, 4, 8
+VIZ_LAYERS = {"history": PLV_VIZ_HISTORY, "active": PLV_VIZ_ACTIVE, "lines": PLV_VIZ_LINES, "mask": PLV_VIZ_MASK}
+
+
+class PlvTrackImageOptions(C.Structure):
+    _fields_ = [("layers", C.c_int), ("r1", C.c_int), ("g1", C.c_int), ("b1", C.c_int), ("r2", C.c_int), ("g2", C.c_int), ("b2", C.c_int),
+                ("max_tracks", C.c_int), ("n_highlighted", C.c_int), ("highlighted", C.POINTER(C.c_uint64)),
+                ("n_flagged", C.c_int), ("flagged", C.POINTER(C.c_uint64))]
+
+
+def viz_layers(layers):
+    """PLV_VIZ_* bits of an int, a name, a comma-separated string or a sequence of names ("history", "active", "lines", "mask")"""
+    if isinstance(layers, (int, np.integer)):
+        return int(layers)
+    names = layers.split(",") if isinstance(layers, str) else list(layers)
+    bits = 0
+    for n in names:
+        n = n.strip()
+        if n not in VIZ_LAYERS:
+            raise ValueError(f"unknown track-image layer {n!r}: {sorted(VIZ_LAYERS)}")
+        bits |= VIZ_LAYERS[n]
+    return bits
+
+
 class PlvError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"plv error {code}: {msg}")
@@ -237,6 +270,11 @@ def load_library():
         "plv_line_tracker_feed": (C.c_int, [vp, C.c_double, dp]),
         "plv_line_tracker_feed_points": (C.c_int, [vp, C.c_double, dp, C.c_int, fp, u64p]),
         "plv_line_tracker_last": (C.c_int, [vp, fp, u64p, C.c_int, ip]),
+        "plv_line_tracker_last_points": (C.c_int, [vp, ip, u64p, C.c_int, C.c_int, ip]),
+        "plv_draw_primitives": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_int, C.POINTER(PlvDrawPrim), C.c_int, u8p, C.c_int, u8p, C.c_int]),
+        "plv_track_image_options_default": (None, [C.POINTER(PlvTrackImageOptions)]),
+        "plv_track_image": (C.c_int, [vp, C.POINTER(PlvTrackImageOptions), u8p, C.c_int]),
+        "plv_track_image_primitives": (C.c_int, [vp, C.POINTER(PlvTrackImageOptions), C.POINTER(PlvDrawPrim), C.c_int, ip]),
         "plv_line_db_size": (C.c_int, [vp]),
         "plv_line_db_ids": (C.c_int, [vp, u64p, C.c_int, ip]),
         "plv_line_db_export_tracks": (C.c_int, [vp, u64p, C.c_int, ip, dp, fp, fp, C.c_int, ip, ip, ip, C.c_int]),
@@ -1765,6 +1803,68 @@ class Context:
         n = C.c_int()
         self._chk(self.lib.plv_line_tracker_last(self.h, _fp(lines), _u64p(ids), cap, C.byref(n)))
         return lines[:n.value].copy(), ids[:n.value].copy()
+
+    def line_tracker_last_points(self):
+        """plv_line_tracker_last_points: (rel_ptr [n_lines + 1], rel_id) — the point ids on every line of the last line feed"""
+        n = C.c_int()
+        self._chk(self.lib.plv_line_tracker_last_points(self.h, None, None, 0, 0, C.byref(n)))
+        rel_ptr = np.zeros(n.value + 1, dtype=np.int32)
+        self._chk(self.lib.plv_line_tracker_last_points(self.h, _ip(rel_ptr), None, n.value, 0, C.byref(n)), allow=(PLV_E_CAPACITY,))
+        rel_id = np.zeros(max(int(rel_ptr[-1]), 1), dtype=np.uint64)
+        self._chk(self.lib.plv_line_tracker_last_points(self.h, _ip(rel_ptr), _u64p(rel_id), n.value, int(rel_ptr[-1]), C.byref(n)))
+        return rel_ptr, rel_id[:rel_ptr[-1]].copy()
+
+    # ---- track image
+    def draw_primitives(self, grey, prims, mask=None, out=None):
+        """plv_draw_primitives: the primitives (DRAW_PRIM_DTYPE array) painted over a grey image of any size, [h, w, 3] u8.  grey, mask
+        and out may be strided row views (their last axis contiguous)."""
+        grey = np.asarray(grey, dtype=np.uint8)
+        h, w = grey.shape
+        if grey.strides[1] != 1:
+            grey = np.ascontiguousarray(grey)
+        prims = np.ascontiguousarray(prims, dtype=DRAW_PRIM_DTYPE)
+        if mask is not None:
+            mask = np.asarray(mask, dtype=np.uint8)
+            if mask.strides[1] != 1:
+                mask = np.ascontiguousarray(mask)
+        if out is None:
+            out = np.zeros((h, w, 3), dtype=np.uint8)
+        assert out.dtype == np.uint8 and out.shape == (h, w, 3) and out.strides[1:] == (3, 1)
+        self._chk(self.lib.plv_draw_primitives(self.h, _u8p(grey), grey.strides[0], w, h, prims.ctypes.data_as(C.POINTER(PlvDrawPrim)), len(prims),
+                                               _u8p(mask), mask.strides[0] if mask is not None else 0, _u8p(out), out.strides[0]))
+        return out
+
+    def _track_image_options(self, layers, colors, max_tracks, highlighted, flagged):
+        opt = PlvTrackImageOptions()
+        self.lib.plv_track_image_options_default(C.byref(opt))
+        opt.layers = viz_layers(layers)
+        if colors is not None:
+            opt.r1, opt.g1, opt.b1, opt.r2, opt.g2, opt.b2 = (int(v) for v in colors)
+        if max_tracks is not None:
+            opt.max_tracks = int(max_tracks)
+        keep = []
+        for name, ids in (("highlighted", highlighted), ("flagged", flagged)):
+            a = np.ascontiguousarray(ids if ids is not None else [], dtype=np.uint64)
+            keep.append(a)
+            setattr(opt, "n_" + name, len(a))
+            setattr(opt, name, _u64p(a) if len(a) else None)
+        return opt, keep
+
+    def track_image(self, layers=PLV_VIZ_HISTORY, highlighted=None, flagged=None, colors=None, max_tracks=None):
+        """plv_track_image: the chosen layers over the tracker's newest image, [H, W, 3] u8.  colors = (r1, g1, b1, r2, g2, b2)."""
+        opt, keep = self._track_image_options(layers, colors, max_tracks, highlighted, flagged)
+        out = np.zeros((self.cfg.height, self.cfg.width, 3), dtype=np.uint8)
+        self._chk(self.lib.plv_track_image(self.h, C.byref(opt), _u8p(out), 3 * self.cfg.width))
+        return out
+
+    def track_image_primitives(self, layers=PLV_VIZ_HISTORY, highlighted=None, flagged=None, colors=None, max_tracks=None):
+        """plv_track_image_primitives: the list track_image would paint (DRAW_PRIM_DTYPE array)"""
+        opt, keep = self._track_image_options(layers, colors, max_tracks, highlighted, flagged)
+        n = C.c_int()
+        self._chk(self.lib.plv_track_image_primitives(self.h, C.byref(opt), None, 0, C.byref(n)), allow=(PLV_E_BADARG,))
+        prims = np.zeros(max(n.value, 1), dtype=DRAW_PRIM_DTYPE)
+        self._chk(self.lib.plv_track_image_primitives(self.h, C.byref(opt), prims.ctypes.data_as(C.POINTER(PlvDrawPrim)), n.value, C.byref(n)))
+        return prims[:n.value].copy()
 
     def line_db_size(self):
         return self.lib.plv_line_db_size(self.h)

@@ -905,6 +905,23 @@ int plv_line_tracker_last(plv_ctx *ctx, float *lines, uint64_t *ids, int cap, in
   return PLV_OK;
 }
 
+// the point ids AssignPointToLines gave every line of the last feed (TrackLSD keeps them as point_on_lines_last, REF: TrackLSD.cpp:186)
+int plv_line_tracker_last_points(plv_ctx *ctx, int *rel_ptr, uint64_t *rel_id, int cap_lines, int cap_ids, int *n_lines) {
+  if (!ctx || !n_lines) return PLV_E_BADARG;
+  LineTracker *T = ltr(ctx);
+  std::lock_guard<std::mutex> lk(T->mtx);
+  const int nl = (int)T->ids_last.size();
+  *n_lines = nl;
+  if (!rel_ptr) return PLV_OK;
+  if (nl > cap_lines) return PLV_E_CAPACITY;
+  // (a feed that kept no line leaves the CSR at {0})
+  for (int i = 0; i <= nl; ++i) rel_ptr[i] = i < (int)T->rel_ptr_last.size() ? T->rel_ptr_last[i] : (T->rel_ptr_last.empty() ? 0 : T->rel_ptr_last.back());
+  const int nid = rel_ptr[nl];
+  if (nid > cap_ids || (nid > 0 && !rel_id)) return PLV_E_CAPACITY;
+  std::copy(T->rel_id_last.begin(), T->rel_id_last.begin() + nid, rel_id);
+  return PLV_OK;
+}
+
 int plv_line_db_size(plv_ctx *ctx) {
   if (!ctx) return 0;
   LineTracker *T = ltr(ctx);

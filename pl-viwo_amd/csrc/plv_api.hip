@@ -276,6 +276,7 @@ void plv_ctx_destroy(plv_ctx *ctx) {
   (void)plv::stream_sync(ctx->stream);
   plv_tracker_destroy(ctx);
   plv_line_tracker_destroy(ctx);
+  plv_draw_destroy(ctx);
   plv_frontend_destroy(ctx);
   ctx->prof.destroy();
   plv::DevBuf *bufs[] = {&ctx->d_P, &ctx->d_P2, &ctx->d_H, &ctx->d_res, &ctx->d_cols, &ctx->d_Rdiag, &ctx->d_dx, &ctx->d_flag,

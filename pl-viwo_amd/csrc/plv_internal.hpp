@@ -3,6 +3,7 @@
 // compile or link error (C linkage carries no types), and hidden from the shared library's export table (Makefile, plviwo.map).
 #pragma once
 #include <cstdint>
+#include <vector>
 
 #include "../../include/plviwo.h"
 
@@ -64,6 +65,12 @@ void plv_point_anchor_fill(plv_ctx *ctx, int Lp, const int *pt_ptr, const int *p
 void plv_point_used_cleanup(plv_ctx *ctx, double t_oldest);
 // the database hand-back a point update left behind; runs inside the line update's wait (a void (*)(void *) callback)
 void plv_tracker_run_deferred(void *ctx);
+// a copy of the mask of the last feed (W x H bytes; empty: that feed had none)
+void plv_tracker_mask_last(plv_ctx *ctx, std::vector<uint8_t> &out);
+
+// ---- draw_api.hip
+// plv_ctx_destroy: the buffers of the track image
+void plv_draw_destroy(plv_ctx *ctx);
 
 // ---- line_api.hip
 // plv_ctx_destroy: the ctx's line tracker and its worker

@@ -107,6 +107,11 @@ void plv_tracker_destroy(plv_ctx *ctx) {
     g_trk.erase(it);
   }
 }
+void plv_tracker_mask_last(plv_ctx *ctx, std::vector<uint8_t> &out) {
+  Tracker *T = trk(ctx);
+  std::lock_guard<std::mutex> lk(T->mtx);
+  out = T->mask_last;
+}
 }  // namespace plv
 
 using namespace plv;

@@ -212,8 +212,18 @@ class TrajectoryLogger:
         self.f.close()
 
 
-def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_obs=24, host_images=False, **system_kw):
-    """run_bag's main loop.  Returns (SystemManager statistics, times, poses [n][7] = p, q).  A dataset whose frames are not grey
+def write_ppm(path, rgb):
+    """an [H, W, 3] u8 image as a binary PPM (P6)"""
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (rgb.shape[1], rgb.shape[0]))
+        f.write(rgb.tobytes())
+
+
+def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_obs=24, host_images=False, after_camera=None, **system_kw):
+    """run_bag's main loop.  Returns (SystemManager statistics, times, poses [n][7] = p, q).  after_camera(sys, frame, t), when given,
+    is called behind every camera message (run_bag.cpp:287-296 publishes the track image there); its time is kept apart from the
+    camera side's (time_after_camera_s).  A dataset whose frames are not grey
     (Dataset.encoding, e.g. the Bayer mosaics of a KAIST directory) hands them over as they are read and the library converts them
     on the device; host_images: the dataset converts them on the host (Dataset.image), as a context without the conversion has to."""
     ds = dataset if dataset is not None else open_dataset(op.sys.path_bag, use_wheel=op.est.wheel.enabled, use_cam=op.est.cam.enabled)
@@ -230,6 +240,7 @@ def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_
     has_raw = hasattr(ds, "raw_image") and hasattr(ds, "to_grey")
     device_images = not host_images and encoding != "mono8" and has_raw and hasattr(sys.ctx, "image_stage_encoded")
     cam_wall, cam_frames = 0.0, 0       # wall time of the camera messages past the file read: conversion + feed + update
+    after_wall = 0.0
     for k, (t, kind, i) in enumerate(ds.msgs):
         if t > t_finish:
             break
@@ -250,6 +261,10 @@ def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_
             else:
                 sys.feed_measurement_camera(t, ds.to_grey(raw) if has_raw else ds.image(i), mask)
             cam_wall, cam_frames = cam_wall + time.perf_counter() - t0, cam_frames + 1
+            if after_camera is not None:
+                t0 = time.perf_counter()
+                after_camera(sys, cam_frames - 1, t)
+                after_wall += time.perf_counter() - t0
         else:
             r = ds.wheel[i]
             sys.feed_measurement_wheel(r[0], r[1], r[2])
@@ -261,6 +276,8 @@ def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_
     stats.update(distance_m=sys.distance, time_s={k: round(v, 4) for k, v in sys.tc.total.items()}, initialized=sys.state.initialized,
                  startup_time=sys.state.startup_time, end_time=sys.state.time, n_state=sys.state.n, clone_freq=op.est.clone_freq,
                  image_route="device" if device_images else "host", time_camera_s=round(cam_wall, 6), camera_messages=cam_frames)
+    if after_camera is not None:
+        stats["time_after_camera_s"] = round(after_wall, 6)
     sys.close()
     return stats, np.array(times), np.array(poses).reshape(-1, 7)
 

@@ -777,6 +777,14 @@ class SystemManager:
             self.tc.dong("CAM")
         self._join_lines()
 
+    def get_track_img(self, layers="history"):
+        """UpdaterCamera::get_track_img (REF: UpdaterCamera.cpp:486-500): the track picture of the newest camera image with the
+        in-state landmarks highlighted, drawn on the device (Context.track_image).  layers: PLV_VIZ_* bits or layer names ("history",
+        "active", "lines", "mask").  Returns (rgb [H, W, 3] u8, overlay): the overlay text ("init" until the filter is initialised, else
+        "": the reference then writes "CAM:0") is the caller's to draw.  Read-only, and called by nothing in the frame path."""
+        overlay = "" if self.state.initialized else "init"
+        return self.ctx.track_image(layers, highlighted=list(self.state.slam)), overlay
+
     def _join_lines(self):
         if self._lines_in_flight:
             self.ctx.line_tracker_feed_wait()

@@ -5,6 +5,8 @@
     python tools/replay.py --synthetic 12 [--out result.json]        # renders tests/synth_dataset.py first (CPU), then replays it
     python tools/replay.py CONFIG.yaml --dataset KAIST_DIR [--host-images]   # Bayer frames: converted on the device unless --host-images
     python tools/replay.py --synthetic 12 --max-slam 12 --feat-rep GLOBAL_FULL_INVERSE_DEPTH   # in-state landmarks, either representation
+    python tools/replay.py --synthetic 12 --track-images DIR [--track-image-every 5] [--track-image-layers history,lines,mask]
+                                                                     # the track picture of the chosen frames as DIR/<frame>.ppm
 """
 import argparse
 import importlib
@@ -36,7 +38,13 @@ def main():
     ap.add_argument("--feat-rep", choices=("GLOBAL_3D", "GLOBAL_FULL_INVERSE_DEPTH"), help="override cam.feat_rep")
     ap.add_argument("--host-images", action="store_true", help="frames that are not grey (a KAIST directory's Bayer mosaics) are converted on the "
                     "host by the dataset reader instead of on the device by the library (the comparison run)")
+    ap.add_argument("--track-images", metavar="DIR", help="write the track image (SystemManager.get_track_img) behind the chosen camera frames "
+                    "as binary PPM files DIR/<frame>.ppm")
+    ap.add_argument("--track-image-every", type=int, default=1, metavar="N", help="every N-th camera frame (default: every frame)")
+    ap.add_argument("--track-image-layers", default="history", help="comma-separated: history, active, lines, mask")
     a = ap.parse_args()
+    if a.track_image_every < 1:
+        ap.error("--track-image-every: a positive number")
     pkg = ge.load_pkg()
     options = importlib.import_module("plviwo_amd.options")
     rp = importlib.import_module("plviwo_amd.replay")
@@ -61,10 +69,23 @@ def main():
         op.est.cam.feat_rep = options.FEAT_REP[a.feat_rep]
     if not op.sys.save_trajectory:
         op.sys.save_trajectory, op.sys.path_trajectory = True, os.path.join(tempfile.mkdtemp(prefix="plv_out_"), "traj.txt")
+    written, after_camera = [], None
+    if a.track_images:
+        layers = pkg.viz_layers(a.track_image_layers)
+        os.makedirs(a.track_images, exist_ok=True)
+
+        def after_camera(system, frame, t):
+            if frame % a.track_image_every == 0:
+                rgb, _overlay = system.get_track_img(layers)
+                path = os.path.join(a.track_images, f"{frame:06d}.ppm")
+                rp.write_ppm(path, rgb)
+                written.append(path)
     t0 = time.time()
-    stats, times, poses = rp.replay(op, host_images=a.host_images, progress=lambda s, t: print(f"  t={t:8.3f}  clones {s.stats['clones']}  cam accepted "
+    stats, times, poses = rp.replay(op, host_images=a.host_images, after_camera=after_camera, progress=lambda s, t: print(f"  t={t:8.3f}  clones {s.stats['clones']}  cam accepted "
                                                                     f"{s.stats['cam_accepted']}/{s.stats['cam_features']}  wheel {s.stats['wheel_accepted']}  zupt {s.stats['zupt_updates']}", flush=True))
     res = dict(config=a.config, wall_s=round(time.time() - t0, 2), stats=stats, poses_logged=len(times), trajectory=op.sys.path_trajectory)
+    if a.track_images:
+        res["track_images_written"] = len(written)
     if a.gt and len(times) > 2:
         ctx = pkg.Context(pkg.default_config(752, 480))
         et, ep, co, cp = pkg.traj_load(op.sys.path_trajectory)
