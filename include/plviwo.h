@@ -685,8 +685,13 @@ typedef struct plv_update_options {
   int init_min_meas;    /* min(window_size * (int)cam_hz - 1, 10): track length that qualifies for SLAM initialisation (:685) */
   const plv_cpi_table *cpi; /* OptionsEstimator::use_imu_res: State::get_interpolated_pose = get_interpolated_pose_imu (REF:
                          * State.cpp:975-977): the pose of every observation (validity, triangulation, residual) comes from this
-                         * table through plv_cpi_poses; an observation it cannot serve goes back to the database as one without
-                         * bounding clones does (CamHelper.cpp:360-365).  NULL = polynomial poses.                               */
+                         * table, as plv_cpi_poses forms it; an observation it cannot serve goes back to the database as one without
+                         * bounding clones does (CamHelper.cpp:360-365).  Which observations it serves is decided on the host from
+                         * times alone; the poses are formed on the device, one per distinct observation time, by a launch on the
+                         * ctx stream in front of the one-submission update (same launches and synchronisations as with NULL, plus
+                         * that one; the line update forms them twice: on the state of plv_camera_get_line_features for the
+                         * triangulation, on the state of the call for the rows).  The table is read during the call only.
+                         * NULL = polynomial poses.                                                                               */
 } plv_update_options;
 
 typedef struct plv_update_result {

@@ -1586,10 +1586,11 @@ class Context:
                     status=res.status, ids=ids[:m].copy(), accepted=acc[:m].copy(), line_FinG=lg[:m].copy(), n_truncated=res.n_truncated)
 
     def _try_update_io(self, plus, n, max_msckf, max_obs, t_prev_frame, state_time, window_full=True, chi2_mult=1.0, min_dist=0.1, max_dist=60.0,
-                       max_cond=1e4, max_baseline=40.0, refine=True, init_min_meas=10, lines=True, cap=512):
+                       max_cond=1e4, max_baseline=40.0, refine=True, init_min_meas=10, lines=True, cap=512, cpi=None):
         """plv_try_update for the given options + a function that turns the filled structure into the result dicts.  The structures and
         the output arrays of a given set of options are laid out once per context; a call only writes the fields that change from frame
-        to frame (the two times, the window flag, the variable list).  The results are copies."""
+        to frame (the two times, the window flag, the variable list, the CPI table of use_imu_res — one table for both halves, as
+        the reference reads one State::cpis).  The results are copies."""
         key = (n, max_msckf, max_obs, chi2_mult, min_dist, max_dist, max_cond, max_baseline, bool(refine), init_min_meas, bool(lines), cap)
         cache = self.__dict__.setdefault("_io_sets", {}) if self is not None else None
         hit = cache.get(key) if cache is not None else None
@@ -1616,7 +1617,7 @@ class Context:
                 lns = dict(dx=dxl.copy(), n_pool=rl.n_pool, n_lines=m, n_accepted=rl.n_accepted, n_rows=rl.n_rows, n_returned=rl.n_returned,
                            status=rl.status, ids=lids[:m].copy(), accepted=lacc[:m].copy(), line_FinG=lg[:m].copy())
                 return pts, lns, io.line_db_size
-            hit = (op, ol, io, results, bufs, rp, rl, tri, [None])      # (everything io points to lives as long as the entry)
+            hit = (op, ol, io, results, bufs, rp, rl, tri, [None, None])      # (everything io points to lives as long as the entry)
             if cache is not None:
                 cache[key] = hit
         op, ol, io, results = hit[0], hit[1], hit[2], hit[3]
@@ -1625,6 +1626,8 @@ class Context:
         op.state_time = ol.state_time = state_time
         op.window_full = ol.window_full = wf
         hit[8][0] = plus                     # (the variable list must outlive the call)
+        hit[8][1] = cpi                      # (... and the CPI table: the options point into its arrays)
+        op.cpi = ol.cpi = C.pointer(cpi.c) if cpi is not None else None
         results.keep = hit                   # (... and so must everything io points to, also without a context to cache it in)
         io.n_var = plus.n if plus is not None else 0
         io.vars = C.addressof(plus.vars) if plus is not None else None
@@ -1653,7 +1656,9 @@ class Context:
         f = PlvCameraFrameIo(float(timestamp), -1 if slot is None else int(slot), img.ctypes.data if slot is None else None,
                              self.cfg.width, m.ctypes.data if m is not None else None, 1 if use_lines else 0,
                              C.addressof(io) if io is not None else None, 0)
-        return dict(st=st, st_ref=C.byref(st.c), f=f, f_ref=C.byref(f), io=io, results=results, keep=(img, m), rc=None, rc_sync=None)
+        # (keep: what the structures point to and the record alone owns — the CPI table of a prepared call must live until it has run)
+        return dict(st=st, st_ref=C.byref(st.c), f=f, f_ref=C.byref(f), io=io, results=results, keep=(img, m, (update or {}).get("cpi")), rc=None,
+                    rc_sync=None)
 
     def camera_frame_run(self, prep, sync=False):
         """plv_camera_frame (+ plv_ctx_synchronize): the C-ABI calls and nothing else (bench.py times exactly this)"""

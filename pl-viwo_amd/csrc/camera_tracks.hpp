@@ -203,53 +203,150 @@ void flatten_pool(const std::vector<PoolCand<TrackT>> &pool, std::vector<int> &p
   }
 }
 
-// use_imu_res: the pose of every pool observation from the CPI table (plv_update_options::cpi), in the order of the flattened pool
-// (flatten_pool): R 9 and p 3 per observation, with the table's covariances (noise) Q 36 and the clone index C as well
+// ---- use_imu_res (plv_update_options::cpi)
+// use_imu_res on the one-submission updates (plv_update_options::cpi): what the stagers of a Jacobian batch (jacobian_api.hip) add to
+// the packed block so that cpi_pose_kernel, on the stream ahead of the fused launch, forms the pose of every DISTINCT observation
+// time — host arrays, valid for the duration of the submitting call.  Every time is one the table serves (cpi_servable).
+struct CpiStage {
+  const plv_cpi_table *table;
+  int n_times;
+  const double *times;  // [n_times] distinct observation time + camera time offset
+  const int *pose_of;   // [observations of the batch] index into times
+  const double *Q;      // (use_imu_cov, else null) [n_times][36] plv_cpi_noise of the times
+  const int *clone;     // ... and [n_times] the clone each hangs on
+};
+// Whether the CPI table serves query time t, and from which records — the rule of cpi_pose_kernel's `ok` (jacobian_kernels.hip;
+// REF State.cpp:273-355 have_cpi's first two stages), which reads times only: a record stored at exactly t whose clone is in the
+// window (e >= 0), else two neighbouring records i0 / i1 of one clone that has not left the window; and that clone (clone: its index
+// in the window) with its own record in the table.  Nothing is launched.
+struct CpiHit {
+  bool ok = false;
+  int e = -1, i0 = -1, i1 = -1, clone = -1;
+};
+inline CpiHit cpi_servable(const plv_state_view &st, const plv_cpi_table &cpi, double t) {
+  CpiHit h;
+  const int n = cpi.n;
+  auto find_t = [&](double x) {
+    const double *e = std::lower_bound(cpi.t, cpi.t + n, x);
+    return (e != cpi.t + n && *e == x) ? (int)(e - cpi.t) : -1;
+  };
+  auto find_clone = [&](double x) {
+    for (int i = 0; i < st.n_clones; ++i)
+      if (st.clone_time[i] == x) return i;
+    return -1;
+  };
+  double clone_t;
+  const int e = n > 0 ? find_t(t) : -1;
+  if (e >= 0 && find_clone(cpi.clone_t[e]) >= 0) {  // REF State.cpp:275-277
+    h.e = e;
+    clone_t = cpi.clone_t[e];
+  } else {  // create_new_cpi_linear :286-355
+    if (n == 0 || t < cpi.t[0] || t > cpi.t[n - 1]) return h;
+    const int lo = (int)(std::lower_bound(cpi.t, cpi.t + n, t) - cpi.t);
+    const int i0 = (t == cpi.t[0]) ? 0 : lo - 1;
+    const int up = (int)(std::upper_bound(cpi.t, cpi.t + n, t) - cpi.t);
+    const int i1 = (t == cpi.t[n - 1]) ? n - 1 : up;
+    if (cpi.clone_t[i0] != cpi.clone_t[i1] || cpi.clone_t[i0] < st.clone_time[0]) return h;
+    h.i0 = i0, h.i1 = i1;
+    clone_t = cpi.clone_t[i0];
+  }
+  const int ci = find_clone(clone_t);
+  if (ci < 0 || find_t(clone_t) < 0) return h;  // clones.at / cpis.at would throw
+  h.clone = ci;
+  h.ok = true;
+  return h;
+}
+// what plv_cpi_poses refuses of a table
+inline bool cpi_table_usable(const plv_cpi_table *cpi) {
+  if (!cpi || cpi->n < 0) return false;
+  if (cpi->n > 0 && (!cpi->t || !cpi->clone_t || !cpi->dt || !cpi->R_I0toIk || !cpi->alpha || !cpi->v)) return false;
+  for (int i = 1; i < cpi->n; ++i)
+    if (!(cpi->t[i - 1] < cpi->t[i])) return false;
+  return true;
+}
+
+// The poses of the pool's observations from the CPI table, in the order of the flattened pool (flatten_pool).  One-submission route:
+// the distinct observation times (time + dt) and every observation's index into them — cpi_pose_kernel forms the poses on the stream
+// (plv::CpiStage), nothing of them reaches the host; noise: the table's covariances Qt 36 and the clone index Ct per time (host
+// arithmetic, plv_cpi_noise).  Two-step route (expand): R 9 and p 3 per observation on the host, with Q 36 and C.
 struct CpiPoses {
   bool on = false, noise = false;
+  std::vector<double> times, Qt;
+  std::vector<int> pose_of, Ct;
   std::vector<double> R, p, Q;
   std::vector<int> C;
+  CpiStage stage(const plv_cpi_table *table) const {
+    return CpiStage{table, (int)times.size(), times.data(), pose_of.data(), noise ? Qt.data() : nullptr, noise ? Ct.data() : nullptr};
+  }
 };
 
-// REF CamHelper.cpp get_imu_poses (:356-365): the poses for every observation of the pool (time + dt); an observation the table
-// cannot serve leaves its track for `unused`.  A failing call of the table returns its status with the pool as it was.
+// REF CamHelper.cpp get_imu_poses (:356-365): an observation whose time + dt the table cannot serve leaves its track for `unused`
+// (cpi_servable: decided on the host from times, no launch and no synchronisation); the others' distinct times are listed.  A table
+// plv_cpi_poses would refuse returns PLV_E_BADARG with the pool as it was.
 template <class TrackT>
-int cpi_attach(plv_ctx *ctx, const plv_state_view *st, const plv_cpi_table *cpi, bool noise, double dt, std::vector<PoolCand<TrackT>> &pool,
+int cpi_attach(const plv_state_view *st, const plv_cpi_table *cpi, bool noise, double dt, std::vector<PoolCand<TrackT>> &pool,
                TrackMap<TrackT> &unused, CpiPoses &out) {
-  std::vector<double> tq;
-  for (const PoolCand<TrackT> &c : pool)
-    for (double t : c.tr.t) tq.push_back(t + dt);
-  std::vector<double> Rq(9 * tq.size()), pq(3 * tq.size());
-  std::vector<uint8_t> okq(tq.size());
-  int rc = plv_cpi_poses(ctx, st, cpi, (int)tq.size(), tq.data(), Rq.data(), pq.data(), okq.data());
-  std::vector<double> Qq(noise ? 36 * tq.size() : 0);
-  std::vector<int> Cq(noise ? tq.size() : 0);
-  if (rc == PLV_OK && noise) {
-    std::vector<uint8_t> okn(tq.size());
-    rc = plv_cpi_noise(st, cpi, (int)tq.size(), tq.data(), Qq.data(), Cq.data(), okn.data());
-    for (size_t i = 0; i < tq.size(); ++i) okq[i] = okq[i] && okn[i];
-  }
-  if (rc != PLV_OK) return rc;
+  if (!cpi_table_usable(cpi) || st->n_clones < 1 || (noise && cpi->n > 0 && !cpi->Q)) return PLV_E_BADARG;
   out = CpiPoses();
   out.on = true, out.noise = noise;
-  size_t o = 0;
+  // (a window's observations carry the stamps of its last few frames: the memo of what was asked, servable or not)
+  std::vector<double> asked;
+  std::vector<int> answer;  // index into out.times, -1: not served
+  auto index_of = [&](double tq) {
+    for (size_t i = asked.size(); i-- > 0;)
+      if (asked[i] == tq) return answer[i];
+    const bool ok = cpi_servable(*st, *cpi, tq).ok;
+    asked.push_back(tq), answer.push_back(ok ? (int)out.times.size() : -1);
+    if (ok) out.times.push_back(tq);
+    return answer.back();
+  };
   for (PoolCand<TrackT> &c : pool) {
+    bool all = true;
+    for (double t : c.tr.t) all = (index_of(t + dt) >= 0) && all;
+    if (all) {
+      for (double t : c.tr.t) out.pose_of.push_back(index_of(t + dt));
+      continue;
+    }
     TrackT kept;
     copy_track_meta(kept, c.tr);
-    for (size_t i = 0; i < c.tr.t.size(); ++i, ++o) {
-      if (!okq[o]) {
+    for (size_t i = 0; i < c.tr.t.size(); ++i) {
+      const int q = index_of(c.tr.t[i] + dt);
+      if (q < 0) {
         give_back(unused, c.id, c.tr, i);
         continue;
       }
       append_obs(kept, c.tr, i);
-      out.R.insert(out.R.end(), &Rq[9 * o], &Rq[9 * o] + 9);
-      out.p.insert(out.p.end(), &pq[3 * o], &pq[3 * o] + 3);
-      if (noise) {
-        out.Q.insert(out.Q.end(), &Qq[36 * o], &Qq[36 * o] + 36);
-        out.C.push_back(Cq[o]);
-      }
+      out.pose_of.push_back(q);
     }
     c.tr = std::move(kept);
+  }
+  if (noise && !out.times.empty()) {
+    const size_t nt = out.times.size();
+    out.Qt.resize(36 * nt), out.Ct.resize(nt);
+    std::vector<uint8_t> okn(nt);
+    const int rc = plv_cpi_noise(st, cpi, (int)nt, out.times.data(), out.Qt.data(), out.Ct.data(), okn.data());
+    if (rc != PLV_OK) return rc;
+  }
+  return PLV_OK;
+}
+// the two-step route: the poses of the listed times come to the host (plv_cpi_poses: a launch and a synchronisation) and are laid
+// out per observation
+inline int cpi_expand(plv_ctx *ctx, const plv_state_view *st, const plv_cpi_table *cpi, CpiPoses &out) {
+  const size_t nt = out.times.size(), nobs = out.pose_of.size();
+  std::vector<double> Rt(9 * nt), pt(3 * nt);
+  std::vector<uint8_t> okt(nt);
+  const int rc = plv_cpi_poses(ctx, st, cpi, (int)nt, out.times.data(), Rt.data(), pt.data(), okt.data());
+  if (rc != PLV_OK) return rc;
+  out.R.resize(9 * nobs), out.p.resize(3 * nobs);
+  if (out.noise) out.Q.resize(36 * nobs), out.C.resize(nobs);
+  for (size_t o = 0; o < nobs; ++o) {
+    const size_t q = (size_t)out.pose_of[o];
+    std::copy(&Rt[9 * q], &Rt[9 * q] + 9, &out.R[9 * o]);
+    std::copy(&pt[3 * q], &pt[3 * q] + 3, &out.p[3 * o]);
+    if (out.noise) {
+      std::copy(&out.Qt[36 * q], &out.Qt[36 * q] + 36, &out.Q[36 * o]);
+      out.C[o] = out.Ct[q];
+    }
   }
   return PLV_OK;
 }

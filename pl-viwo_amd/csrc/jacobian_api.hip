@@ -94,6 +94,13 @@ struct StateStage {
   const int *col_to_state;
   StageBlock::Slot<double> time, R, p, Rf, pf, rR, rp, rQ;
   StageBlock::Slot<int> ccol, cols, rc;
+  // residual poses from the CPI table on the device (plv::CpiStage): the table, the batch's distinct observation times and every
+  // observation's index into them ride in the block; cpi_pose_kernel writes [n_times][9] + [n_times][3] into the staging's own
+  // buffer (a second set on the clone poses of the lines' triangulation state), and the batch reads them through res_pose_of
+  const CpiStage *cs = nullptr;
+  StageBlock::Slot<double> c_t, c_ct, c_dt, c_R, c_a, c_v, c_tq;
+  StageBlock::Slot<int> c_of;
+  const double *cpi_R[2] = {nullptr, nullptr}, *cpi_p[2] = {nullptr, nullptr};
   int col_of(int sid) const {
     if (sid < 0) return -1;
     for (int j = 0; j < k; ++j)
@@ -111,6 +118,35 @@ struct StateStage {
   int add_res_noise(const double *res_Q, const int *res_clone, size_t nobs) {
     if (res_Q && !res_clone) return PLV_E_BADARG;
     if (res_Q) rQ = B.add<36>(res_Q, nobs), rc = B.add(res_clone, nobs);
+    return PLV_OK;
+  }
+  int add_cpi(const CpiStage *c, size_t nobs) {
+    if (!c->table || c->table->n < 1 || c->n_times < 1 || !c->times || !c->pose_of || (c->Q && !c->clone)) return PLV_E_BADARG;
+    const plv_cpi_table &T = *c->table;
+    const size_t n = (size_t)T.n, nt = (size_t)c->n_times;
+    for (size_t o = 0; o < nobs; ++o)
+      if (c->pose_of[o] < 0 || c->pose_of[o] >= c->n_times) return PLV_E_BADARG;
+    cs = c;
+    c_t = B.add(T.t, n), c_ct = B.add(T.clone_t, n), c_dt = B.add(T.dt, n), c_R = B.add<9>(T.R_I0toIk, n), c_a = B.add<3>(T.alpha, n);
+    c_v = B.add<3>(T.v, n), c_tq = B.add(c->times, nt), c_of = B.add(c->pose_of, nobs);
+    if (c->Q) rQ = B.add<36>(c->Q, nt), rc = B.add(c->clone, nt);
+    return PLV_OK;
+  }
+  // behind the block's upload on the ctx stream; tri_R / tri_p: the clone poses (device) of a second state to form the poses on as well
+  int launch_cpi(plv_ctx *ctx, Staging &sg, const double *tri_R, const double *tri_p) {
+    const size_t nt = (size_t)cs->n_times, ok_room = StageBlock::padded(nt);
+    TRY(sg.cpi.reserve(2 * 12 * nt * sizeof(double) + 2 * ok_room));
+    for (int s = 0; s < (tri_R ? 2 : 1); ++s) {
+      CpiParams C{};
+      C.n = cs->table->n, C.n_clones = st->n_clones, C.n_q = cs->n_times;
+      C.t = B.dev(c_t), C.clone_t = B.dev(c_ct), C.dt = B.dev(c_dt), C.R = B.dev(c_R), C.alpha = B.dev(c_a), C.v = B.dev(c_v);
+      C.clone_time = B.dev(time), C.clone_R = s ? tri_R : B.dev(R), C.clone_p = s ? tri_p : B.dev(p);
+      std::copy(cs->table->gravity, cs->table->gravity + 3, C.gravity);
+      double *dR = sg.cpi.as<double>() + 12 * nt * (size_t)s, *dp = dR + 9 * nt;
+      unsigned char *dok = sg.cpi.as<unsigned char>() + 2 * 12 * nt * sizeof(double) + ok_room * (size_t)s;
+      TRY(launch_cpi_poses(ctx, C, B.dev(c_tq), dR, dp, dok));
+      cpi_R[s] = dR, cpi_p[s] = dp;
+    }
     return PLV_OK;
   }
   void add_cols() { cols = B.add(col_to_state, (size_t)k); }
@@ -140,6 +176,8 @@ struct StateStage {
     P.use_imu_cov = st->use_imu_cov && rQ ? 1 : 0;
     P.intr_err_mlt = st->intr_err_mlt;
     P.res_R = B.dev(rR), P.res_p = B.dev(rp), P.res_Q = B.dev(rQ), P.res_clone = B.dev(rc);
+    P.res_pose_of = nullptr;
+    if (cs) P.res_R = cpi_R[0], P.res_p = cpi_p[0], P.res_pose_of = B.dev(c_of);
     P.feat_rep = st->feat_rep;
     P.col_dt = col_of(st->dt_state_id);
     P.k = k;
@@ -181,14 +219,16 @@ int stage_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *s
   const auto ot = B.add(tr->obs_time, nobs);
   const auto uv = B.add<2>(tr->obs_uv, nobs);
   const auto pg = B.add<3>(tr->p_FinG, F), pgf = B.add<3>(tr->p_FinG_fej, F);
-  S.add_res_poses(tr->res_R, tr->res_p, nobs);
+  const CpiStage *cs = tr->res_R ? nullptr : ctx->cpi_stage;
+  if (cs) TRY(S.add_cpi(cs, (size_t)nobs));
+  else S.add_res_poses(tr->res_R, tr->res_p, nobs);
   S.add_cols();
   StageBlock::Slot<float> xuvn;
   StageBlock::Slot<uint8_t> xfl, sme, spv;
   StageBlock::Slot<int> sli, send;
   if (ex && ex->uvn) xuvn = B.add<2>(ex->uvn, nobs);
   if (ex && ex->flags) xfl = B.add(ex->flags, F);
-  TRY(S.add_res_noise(tr->res_Q, tr->res_clone, nobs));
+  if (!cs) TRY(S.add_res_noise(tr->res_Q, tr->res_clone, nobs));
   if (spec) {
     sli = B.add(ex->spec_li, F), sme = B.add(ex->spec_meta, F), spv = B.add(ex->spec_prevalid, F);
     send = B.add(tr->obs_ptr + 1, F);  // (overwritten by spec_select_kernel)
@@ -213,6 +253,7 @@ int stage_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *s
     PLV_HIP_CHECK(hipStreamWaitEvent(ctx->stream, us->spec_ev, 0));
   } else
     PLV_HIP_CHECK(plv::memcpy_async(sg.jin.p, sg.h_jin.p, B.total(), hipMemcpyHostToDevice, ctx->stream));
+  if (cs) TRY(S.launch_cpi(ctx, sg, nullptr, nullptr));
   S.fill(P, ctx, ld);
   P.col_ext = S.col_of(st->extrinsic_state_id);
   P.col_int = S.col_of(st->intrinsic_state_id);
@@ -685,8 +726,12 @@ int stage_line_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_vi
   if (lt->line_FinG) lg = B.add<6>(lt->line_FinG, L);
   if (lt->D) D = B.add(lt->D, L);
   if (lt->has_pt) ap = B.add<3>(lt->anchor_pt, L), hp = B.add(lt->has_pt, L);
-  S.add_res_poses(lt->res_R, lt->res_p, nobs);
-  TRY(S.add_res_noise(lt->res_Q, lt->res_clone, nobs));
+  const CpiStage *cs = lt->res_R ? nullptr : ctx->cpi_stage;
+  if (cs) TRY(S.add_cpi(cs, (size_t)nobs));
+  else {
+    S.add_res_poses(lt->res_R, lt->res_p, nobs);
+    TRY(S.add_res_noise(lt->res_Q, lt->res_clone, nobs));
+  }
   S.add_cols();
   if (ex && ex->flags) xfl = B.add(ex->flags, L);
   const bool two_states = st_tri && Pt && st_tri != st && st_tri->n_clones == N;
@@ -707,6 +752,8 @@ int stage_line_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_vi
   TRY(S.pack(sg));
   // (an upload by a kernel of the ctx stream instead of the copy command was measured, alternating frame by frame: no difference)
   PLV_HIP_CHECK(plv::memcpy_async(sg.jin.p, sg.h_jin.p, B.total(), hipMemcpyHostToDevice, ctx->stream));
+  // (CPI poses: the triangulation's on the clone poses of its own state, the rows' on st's — both from the one table)
+  if (cs) TRY(S.launch_cpi(ctx, sg, two_states ? B.dev(tR) : nullptr, two_states ? B.dev(tp) : nullptr));
   S.fill(P, ctx, ld);
   P.col_ext = P.col_int = -1;
   P.n_feat = L;
@@ -728,6 +775,7 @@ int stage_line_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_vi
     *Pt = P;
     if (two_states) {
       Pt->clone_R = B.dev(tR), Pt->clone_p = B.dev(tp);
+      if (cs) Pt->res_R = S.cpi_R[1], Pt->res_p = S.cpi_p[1];
       memcpy(Pt->R_ItoC, st_tri->R_ItoC, sizeof Pt->R_ItoC);
       memcpy(Pt->p_IinC, st_tri->p_IinC, sizeof Pt->p_IinC);
       Pt->cam_dt = st_tri->cam_dt;
@@ -910,47 +958,28 @@ int plv_triangulate_lines(plv_ctx *ctx, const plv_state_view *st, const plv_line
   return PLV_OK;
 }
 
-// The record behind a query time, as cpi_pose_kernel finds it, for its covariance (host arithmetic: a search and one blend).
+// The record behind a query time, as cpi_pose_kernel finds it (cpi_servable, camera_tracks.hpp), for its covariance (host arithmetic:
+// a search and one blend).
 int plv_cpi_noise(const plv_state_view *st, const plv_cpi_table *cpi, int n_q, const double *t_q, double *Q, int *clone_index, uint8_t *ok) {
   if (!st || !cpi || n_q < 0 || (n_q > 0 && (!t_q || !Q || !clone_index || !ok)) || st->n_clones < 1) return PLV_E_BADARG;
   if (cpi->n > 0 && (!cpi->t || !cpi->clone_t || !cpi->Q)) {
     set_last_error("plv_cpi_noise: the table carries no covariances (plv_cpi_table::Q)");
     return PLV_E_BADARG;
   }
-  const int n = cpi->n;
-  auto find_t = [&](double t) {
-    const double *e = std::lower_bound(cpi->t, cpi->t + n, t);
-    return (e != cpi->t + n && *e == t) ? (int)(e - cpi->t) : -1;
-  };
-  auto find_clone = [&](double t) {
-    for (int i = 0; i < st->n_clones; ++i)
-      if (st->clone_time[i] == t) return i;
-    return -1;
-  };
   for (int q = 0; q < n_q; ++q) {
     ok[q] = 0;
     clone_index[q] = -1;
-    std::fill(Q + 36 * (size_t)q, Q + 36 * (size_t)q + 36, 0.0);
-    const double t = t_q[q];
-    double clone_t;
-    const int e = find_t(t);
-    if (e >= 0 && find_clone(cpi->clone_t[e]) >= 0) {  // REF State.cpp:275-277
-      std::copy(cpi->Q + 36 * (size_t)e, cpi->Q + 36 * (size_t)e + 36, Q + 36 * (size_t)q);
-      clone_t = cpi->clone_t[e];
-    } else {  // create_new_cpi_linear :286-355
-      if (n == 0 || t < cpi->t[0] || t > cpi->t[n - 1]) continue;
-      const int lo = (int)(std::lower_bound(cpi->t, cpi->t + n, t) - cpi->t);
-      const int i0 = (t == cpi->t[0]) ? 0 : lo - 1;
-      const int up = (int)(std::upper_bound(cpi->t, cpi->t + n, t) - cpi->t);
-      const int i1 = (t == cpi->t[n - 1]) ? n - 1 : up;
-      if (cpi->clone_t[i0] != cpi->clone_t[i1] || cpi->clone_t[i0] < st->clone_time[0]) continue;
-      const double lambda = (t - cpi->t[i0]) / (cpi->t[i1] - cpi->t[i0]);
-      for (int j = 0; j < 36; ++j) Q[36 * (size_t)q + j] = (1 - lambda) * cpi->Q[36 * (size_t)i0 + j] + lambda * cpi->Q[36 * (size_t)i1 + j];
-      clone_t = cpi->clone_t[i0];
+    double *Qq = Q + 36 * (size_t)q;
+    std::fill(Qq, Qq + 36, 0.0);
+    const CpiHit h = cpi_servable(*st, *cpi, t_q[q]);
+    if (h.e >= 0) {  // REF State.cpp:275-277
+      std::copy(cpi->Q + 36 * (size_t)h.e, cpi->Q + 36 * (size_t)h.e + 36, Qq);
+    } else if (h.i0 >= 0) {  // create_new_cpi_linear :286-355
+      const double lambda = (t_q[q] - cpi->t[h.i0]) / (cpi->t[h.i1] - cpi->t[h.i0]);
+      for (int j = 0; j < 36; ++j) Qq[j] = (1 - lambda) * cpi->Q[36 * (size_t)h.i0 + j] + lambda * cpi->Q[36 * (size_t)h.i1 + j];
     }
-    const int ci = find_clone(clone_t);
-    if (ci < 0 || find_t(clone_t) < 0) continue;
-    clone_index[q] = ci;
+    if (!h.ok) continue;
+    clone_index[q] = h.clone;
     ok[q] = 1;
   }
   return PLV_OK;

@@ -313,11 +313,15 @@ struct PointTriStage {
   unsigned char *ok_out;  // [F]
   double *err_out;        // [F]
 };
+// where observation o's residual pose (res_R / res_p) and its covariance (res_Q / res_clone) sit: at o, or — poses per distinct
+// observation time, JacParams::res_pose_of — at the entry of its time
+__device__ __forceinline__ int res_index(const JacParams &P, int o) { return P.res_pose_of ? P.res_pose_of[o] : o; }
 // REF: CamHelper.cpp:217-224 (and LineHelper's twin): R += H_ Q H_^T * mlt with H_ = HI * blockdiag(I, R_clone_fej^T), HI the 2 x 6
 // Jacobian of the measurement in the interpolated pose, Q the CPI covariance of that pose.
 __device__ __forceinline__ void add_imu_cov(const JacParams &P, int o, const double *HI, double *Rn) {
-  const double *Q = P.res_Q + 36 * (size_t)o;
-  const double *Rc = P.clone_R_fej + 9 * (size_t)P.res_clone[o];  // Rot_fej of the clone, row-major; H_cpi(3:6,3:6) = its transpose
+  const int ro = res_index(P, o);
+  const double *Q = P.res_Q + 36 * (size_t)ro;
+  const double *Rc = P.clone_R_fej + 9 * (size_t)P.res_clone[ro];  // Rot_fej of the clone, row-major; H_cpi(3:6,3:6) = its transpose
   double Hc[12];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -356,8 +360,9 @@ __device__ void jacobian_rows(const JacParams &P, const WinTab *tab, int f, int 
   M3 R_GtoI;
   V3 p_IinG;
   if (P.res_R) {
-    R_GtoI = ldM(P.res_R + 9 * o);
-    p_IinG = ldV(P.res_p + 3 * o);
+    const int ro = res_index(P, o);
+    R_GtoI = ldM(P.res_R + 9 * ro);
+    p_IinG = ldV(P.res_p + 3 * ro);
   } else {
     Interp est;
     interpolate_tab(P, tab[2 * s0], s0, tm, false, est);
@@ -655,8 +660,9 @@ __device__ __forceinline__ int assign_row_slots(const JacParams &P, int o0, int 
 // estimate pose of observation o (CamHelper::get_imu_poses) from the window tables; the same values as campose_one's
 __device__ __forceinline__ void est_pose_tab(const JacParams &P, const WinTab &T, int o, int s0, double tm, M3 &R_GtoI, V3 &p_IinG) {
   if (P.res_R) {
-    R_GtoI = ldM(P.res_R + 9 * o);
-    p_IinG = ldV(P.res_p + 3 * o);
+    const int ro = res_index(P, o);
+    R_GtoI = ldM(P.res_R + 9 * ro);
+    p_IinG = ldV(P.res_p + 3 * ro);
   } else {
     Interp est;
     interpolate_tab(P, T, s0, tm, false, est);
@@ -957,8 +963,9 @@ __device__ __forceinline__ void campose_one(const JacParams &P, int o, double *_
   M3 R_GtoI;
   V3 p_IinG;
   if (P.res_R) {
-    R_GtoI = ldM(P.res_R + 9 * o);
-    p_IinG = ldV(P.res_p + 3 * o);
+    const int ro = res_index(P, o);
+    R_GtoI = ldM(P.res_R + 9 * ro);
+    p_IinG = ldV(P.res_p + 3 * ro);
   } else {
     Interp est;
     interpolate(P, s0, tm, false, false, est);
@@ -1577,8 +1584,9 @@ __device__ void line_rows(const JacParams &P, int l, int o, int s0, double tm, i
   M3 Re;
   V3 pe;
   if (P.res_R) {
-    Re = ldM(P.res_R + 9 * o);
-    pe = ldV(P.res_p + 3 * o);
+    const int ro = res_index(P, o);
+    Re = ldM(P.res_R + 9 * ro);
+    pe = ldV(P.res_p + 3 * ro);
   } else {
     Interp est;
     if (tab)

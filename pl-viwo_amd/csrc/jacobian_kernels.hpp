@@ -83,6 +83,9 @@ struct JacParams {
   double intr_err_mlt;
   const double *res_Q;
   const int *res_clone;
+  // (optional) [n_obs]: res_R / res_p / res_Q / res_clone hold one entry per distinct observation time and this is every
+  // observation's entry (plv::CpiStage: the poses came from cpi_pose_kernel on the stream).  null: one entry per observation.
+  const int *res_pose_of;
 };
 
 struct CpiParams {  // device pointers; State::cpis as a table sorted by time + the clone window

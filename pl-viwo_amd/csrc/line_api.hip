@@ -90,7 +90,7 @@ struct LinesJob {
     plv_line_tracks all{};
     all.n_lines = Lp, all.obs_ptr = ptr.data(), all.obs_time = ot.data(), all.seg_uv = uv.data(), all.seg_uvn = uvn.data();
     all.D = D.data(), all.anchor_pt = anchor.data(), all.has_pt = has.data();
-    if (cpi.on) all.res_R = cpi.R.data(), all.res_p = cpi.p.data();
+    if (cpi.on && !cpi.R.empty()) all.res_R = cpi.R.data(), all.res_p = cpi.p.data();  // (two-step route: cpi_expand)
     return all;
   }
 };
@@ -1187,7 +1187,7 @@ static int lines_first_half(plv_ctx *ctx, LineTracker *T, const plv_state_view *
   // ---- use_imu_res: poses from the CPI table (plv_update_options::cpi); views it cannot serve go back to the database
   const bool imu_cov = opt->cpi && opt->cpi->Q && st->use_imu_cov && !st->use_pol_cov;
   if (opt->cpi) {
-    const int rc0 = cpi_attach(ctx, st, opt->cpi, imu_cov, dt, pool, LP.unused, J.cpi);
+    const int rc0 = cpi_attach(st, opt->cpi, imu_cov, dt, pool, LP.unused, J.cpi);
     if (rc0 != PLV_OK) {
       J.stage = LinesJob::FAILED, J.rc = rc0;
       return PLV_OK;
@@ -1220,13 +1220,19 @@ static int lines_first_half(plv_ctx *ctx, LineTracker *T, const plv_state_view *
   J.most_valid = count_usable(pool, dt, start_of, J.valid_n);
   J.cols.resize(ctx->cfg.max_state_dim > 0 ? ctx->cfg.max_state_dim : 1024);
   // ---- one submission (see plv_camera_update_points): line triangulation, the selection below, Jacobians, null space, gate,
-  // compression and EKFUpdate back to back on the stream, one synchronisation.  CPI poses and over-long tracks take the two-step route.
-  const bool fused = !opt->cpi && J.most_valid <= opt->max_obs;
+  // compression and EKFUpdate back to back on the stream, one synchronisation.  CPI poses (use_imu_res) are formed by a launch in
+  // front, once on the clone poses of st_tri for the triangulation and once on st's for the rows.  Over-long tracks take the
+  // two-step route.
+  const bool fused = J.most_valid <= opt->max_obs;
   J.us_pool = since(U0);
   ph_p2.stop();
   ph_pool.stop();
   if (!fused) {
     J.stage = LinesJob::TWO_STEP;
+    if (J.cpi.on) {  // (the two-step route stages the poses per observation, from the host)
+      const int rc1 = cpi_expand(ctx, st, opt->cpi, J.cpi);
+      if (rc1 != PLV_OK) J.stage = LinesJob::FAILED, J.rc = rc1;
+    }
     return PLV_OK;
   }
   J.flags.resize(Lp);
@@ -1244,8 +1250,11 @@ static int lines_first_half(plv_ctx *ctx, LineTracker *T, const plv_state_view *
     plv::HostPhase ph_sub("update_lines: fused submit (gate prepare + stage + upload + launch)");
     ctx->gate_rows_hint = 2 * J.most_valid;
     ch.on = chained;
+    const CpiStage cpi_stage = J.cpi.stage(opt->cpi);
+    ctx->cpi_stage = J.cpi.on ? &cpi_stage : nullptr;
     rc = plv_lines_update_fused_submit(ctx, st, st_tri, &all, J.flags.data(), cap, J.k, J.cols.data(), 2 * opt->max_obs, st->sigma_pix * st->sigma_pix,
                                        opt->chi2_mult);
+    ctx->cpi_stage = nullptr;
     ch.on = false;
     launched = rc == PLV_OK;
   }

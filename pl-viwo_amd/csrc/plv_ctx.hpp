@@ -438,6 +438,7 @@ struct ProfScope {
   ~ProfScope() { p.end(s); }
 };
 
+struct CpiStage;  // camera_tracks.hpp
 }  // namespace plv
 
 struct plv_ctx {
@@ -554,6 +555,10 @@ struct plv_ctx {
   // its wait until it returns nonzero = done / nothing to do)
   int (*wait_poll)(void *) = nullptr;
   void *wait_poll_arg = nullptr;
+
+  // residual poses of the batch about to be staged come from the CPI table on the device (set around the one-submission calls by
+  // plv_camera_update_points / _lines; null: the tracks' own res_R / res_p, if any)
+  const plv::CpiStage *cpi_stage = nullptr;
 
   // ---- front-end (frontend_api.hip owns the object)
   void *fe_state = nullptr;

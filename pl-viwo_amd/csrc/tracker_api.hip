@@ -855,13 +855,14 @@ struct PointsUpdate {
   }
 
   // ---- the whole pool as one batch (the reference goes feature by feature until the cap; a feature it never reaches keeps its
-  // observations either way): CPI poses, the flattened arrays, the usable views of every candidate
+  // observations either way): what the CPI table serves, the flattened arrays, the usable views of every candidate
   int stage_pool() {
     if (pool.empty()) return finish_early(spec_done);
-    // ---- use_imu_res: poses from the CPI table; what it cannot serve leaves the track here (get_imu_poses, :356-365)
+    // ---- use_imu_res: poses from the CPI table; what it cannot serve leaves the track here (get_imu_poses, :356-365) — decided
+    // from times on the host; the poses themselves are formed on the stream in front of the fused launch (plv::CpiStage)
     const bool imu_cov = opt->cpi && opt->cpi->Q && st->use_imu_cov && !st->use_pol_cov;  // REF CamHelper.cpp:214-224
     if (opt->cpi) {
-      const int rc0 = cpi_attach(ctx, st, opt->cpi, imu_cov, dt, pool, unused, cpi);
+      const int rc0 = cpi_attach(st, opt->cpi, imu_cov, dt, pool, unused, cpi);
       if (rc0 != PLV_OK) return abandon(rc0);
     }
     const size_t Fp = pool.size();
@@ -871,7 +872,11 @@ struct PointsUpdate {
     if (ptr[Fp] == 0) return finish_early(spec_done);
     pf.resize(3 * Fp), err.resize(Fp), ok.resize(Fp), acc_all.resize(Fp, 0);  // (a used speculative batch has filled them)
     all.n_feat = (int)Fp, all.obs_ptr = ptr.data(), all.obs_time = ot.data(), all.obs_uv = ouv.data(), all.obs_uvn = ouvn.data();
-    if (cpi.on) all.res_R = cpi.R.data(), all.res_p = cpi.p.data();
+    if (cpi.on && !fused_route()) {  // (the two-step route selects on the host and stages the selected tracks' poses per observation)
+      const int rc1 = cpi_expand(ctx, st, opt->cpi, cpi);
+      if (rc1 != PLV_OK) return abandon(rc1);
+      all.res_R = cpi.R.data(), all.res_p = cpi.p.data();
+    }
     cols.resize(ctx->cfg.max_state_dim > 0 ? ctx->cfg.max_state_dim : 1024);
     return GO_ON;
   }
@@ -880,9 +885,10 @@ struct PointsUpdate {
   // (jacobian_nullspace_kernel: candidate_selected), Jacobians / gate / compression / EKFUpdate follow on the stream, and the host
   // reads triangulation results, gate decisions and dx after ONE synchronisation.  The batch then holds all candidates (the ones
   // the loop does not take are empty systems) and its column set is the union over all of them: a permutation / zero columns of the
-  // reference's, which changes neither dx nor P beyond rounding.  Poses from the CPI table, in-state landmarks and tracks longer
-  // than the batch rows take the two-step route (triangulate, select on the host, then build + update).
-  bool fused_route() const { return !opt->cpi && opt->max_slam == 0 && most_valid <= opt->max_obs; }
+  // reference's, which changes neither dx nor P beyond rounding.  Poses from the CPI table (use_imu_res) are formed by one more
+  // launch in front on the same stream, for triangulation and rows alike.  In-state landmarks and tracks longer than the batch
+  // rows take the two-step route (triangulate, select on the host, then build + update).
+  bool fused_route() const { return opt->max_slam == 0 && most_valid <= opt->max_obs; }
 
   // triangulation and gate results of the pool, by route: the speculative batch's, the fused call's, or (two-step) the triangulation alone
   int triangulate_and_gate() {
@@ -913,9 +919,12 @@ struct PointsUpdate {
         for (int f = 0; f < Fp; ++f)
           if (flags[f]) T->chain_index.emplace(pool[f].id, f);
       plv::frame_mark("@ update_points: columns done, fused call");
+      const CpiStage cpi_stage = cpi.stage(opt->cpi);
+      ctx->cpi_stage = cpi.on ? &cpi_stage : nullptr;
       rc_f = plv_points_update_fused(ctx, st, &all, &opt->tri, flags.data(), opt->max_msckf, k, cols.data(), 2 * opt->max_obs,
                                      st->sigma_pix * st->sigma_pix, opt->chi2_mult, 3.0, pf.data(), ok.data(), err.data(), acc_all.data(),
                                      &n_rows, dx, start_detection_ahead, ctx);
+      ctx->cpi_stage = nullptr;
       T->chain_ok = false;
       rc_f = ekf_returned_false(rc_f, &res->status, dx, ctx->cov_n);
       fused_ran = rc_f == PLV_OK;

@@ -79,8 +79,9 @@ struct plv_ctx_update_state {
   // of the two halves may share a buffer the host writes or reads.
   struct Staging {
     plv::DevBuf jin, tri;
+    plv::DevBuf cpi;  // plv::CpiStage: cpi_pose_kernel's poses of the batch's distinct observation times ([n][9], [n][3]; a second set for the lines' triangulation state; ok)
     plv::PinBuf h_jin, h_tri;
-    void release() { jin.release(), tri.release(), h_jin.release(), h_tri.release(); }
+    void release() { jin.release(), tri.release(), cpi.release(), h_jin.release(), h_tri.release(); }
   } stg[2];
   Staging &staging_of(int fdim) { return stg[fdim == 6 ? 1 : 0]; }
   plv::DevBuf eval;

@@ -670,7 +670,7 @@ class SystemManager:
         e, st = self.op.est, self.state
         if not e.cam.enabled:
             return None
-        if not (self.one_call_update and self.one_call_frame and e.cam.max_slam == 0 and not e.use_imu_res and not e.cam.downsample and not st.slam
+        if not (self.one_call_update and self.one_call_frame and e.cam.max_slam == 0 and not e.cam.downsample and not st.slam
                 and self.zupt_opt is None and hasattr(self.ctx, "camera_frame")):
             return None
         if not _bookkeeping_done:
@@ -887,7 +887,7 @@ class SystemManager:
             return
         pk, kw, max_msckf = args
         c = e.cam
-        if self.one_call_update and c.max_slam == 0 and "cpi" not in kw and hasattr(self.ctx, "camera_try_update"):
+        if self.one_call_update and c.max_slam == 0 and hasattr(self.ctx, "camera_try_update"):
             # the whole of try_update in one library call: point update, dx applied, line update on the updated state, dx applied
             label = "[Time-Cam] get features + MSCKF update + LINE update" if self.use_lines else "[Time-Cam] get features + MSCKF update"
             self.tc.ding(label)
