@@ -550,10 +550,25 @@ typedef struct plv_line_tracks {
  * the first view's end points is intersected with the plane of every later view and the Pluecker
  * results are averaged (:372-495, CompoutePlaneFromPoints :615-623, ComputeLineFramePlanes :625-650).
  * ok[l] = 0 when the reference returns false (fewer than two usable views, all plane pairs with
- * |cos| >= 0.99).  LineFeature::EndPoints is left to the caller (the reference stores an
- * uninitialised vector there, :489-493). */
+ * |cos| >= 0.99).  LineFeature::EndPoints (the reference stores an uninitialised vector there,
+ * :489-493) comes from plv_line_segments below. */
 int plv_triangulate_lines(plv_ctx *ctx, const plv_state_view *st, const plv_line_tracks *lt, double *line_FinG,
                           uint8_t *ok);
+
+/* The line map: the 3-D end points of triangulated lines (what LineFeature::EndPoints was meant to hold, REF:
+ * LineHelper.cpp:476-493 commented out; published by ROSPublisher::publish_cam_features, ROSPublisher.cpp:220-241).
+ * The definition is the library's own (DESIGN.md "The line map"): with v^ = v/|v| and p0 = v x n / |v|^2 of
+ * lt->line_FinG = [n; v], every observation that has bounding clones (pose formed as plv_triangulate_lines forms it)
+ * sends a ray through each of its two normalised end points (seg_uvn); the ray's closest approach to the line lies at
+ * s along v^ from p0.  An end point whose ray is within 1e-3 rad of parallel to the line, or that meets it behind the
+ * camera, is rejected; an observation counts when both of its end points are kept, with lo = min(s1, s2) and
+ * hi = max(s1, s2).  Of more than 64 usable observations the newest 64 are looked at.  Over the k counted ones lo* and
+ * hi* are the lower medians (sorted index (k - 1) / 2) of the lows and the highs: P1 = p0 + lo* v^, P2 = p0 + hi* v^,
+ * ok = 1, n_views = k.  k = 0, |v| = 0 or a non-finite line: ok = 0 and zeros.
+ * Argument checks and error codes as plv_triangulate_lines (lt->line_FinG is required); n_lines = 0 is PLV_OK.
+ * extent and n_views may be NULL. */
+int plv_line_segments(plv_ctx *ctx, const plv_state_view *st, const plv_line_tracks *lt, double *end_points /* [L][6] P1, P2 */,
+                      double *extent /* [L][2] lo*, hi* */, int *n_views /* [L] */, uint8_t *ok /* [L] */);
 
 /* Column order of the stacked line Jacobians: per observation the four interpolation clones, then the
  * time offset when it is calibrated, first-seen order (REF: LineHelper.cpp:757-788 with
@@ -766,6 +781,21 @@ int plv_camera_get_line_features(plv_ctx *ctx, const plv_state_view *st);
  * (capacity cap, may be NULL) list the lines of the update in batch order. */
 int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, double *dx,
                             plv_update_result *res, uint64_t *line_ids, uint8_t *accepted, double *line_FinG, int cap);
+
+/* The list behind UpdaterCamera::get_used_lines (REF: UpdaterCamera.cpp:477-484, filled by LineHelper::cleanup_lines,
+ * LineHelper.cpp:522-530, with every triangulated line of the pool, accepted by the gate or not).
+ * plv_line_map_mode: on = 1 makes plv_camera_update_lines (and so plv_camera_try_update / plv_camera_frame) keep the tracks of
+ * the lines of its batch when it ends; on = 0 (the default) keeps nothing and the update does exactly what it does without this
+ * call; on < 0 returns the mode.  A new update replaces what was kept; one that fails or is refused leaves nothing.
+ * plv_camera_used_lines returns the lines of the last line update in batch order: ids, accepted and line_FinG as that update
+ * returned them, and end_points [n][6] / ok [n] by plv_line_segments on `st`.  *n receives the count; cap too small:
+ * PLV_E_CAPACITY with *n set.  Mode off or no update yet: *n = 0.  It changes nothing: a second call returns the same.
+ * When that update ran with a CPI table (plv_update_options::cpi) the observation poses are the table's as the update formed them
+ * (kept with the record as res_R / res_p: the table is the caller's and need not outlive the update); `st` then supplies the
+ * window test, the extrinsics and the time offset.  Without a table the poses are the polynomial's on `st`. */
+int plv_line_map_mode(plv_ctx *ctx, int on);
+int plv_camera_used_lines(plv_ctx *ctx, const plv_state_view *st, int cap, int *n, uint64_t *ids, uint8_t *accepted, double *line_FinG,
+                          double *end_points, uint8_t *ok);
 
 /* x <- x [+] dx for every variable of the state in one call (REF: StateHelper::EKFUpdate, PL-VIWO/src/state/StateHelper.cpp:156-160,
  * which calls Type::update(dx.block(id, 0, size, 1)) variable by variable: ov_type::Vec adds, JPLQuat composes on the left, PoseJPL is

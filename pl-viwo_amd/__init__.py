@@ -280,6 +280,9 @@ def load_library():
         "plv_line_db_export_tracks": (C.c_int, [vp, u64p, C.c_int, ip, dp, fp, fp, C.c_int, ip, ip, ip, C.c_int]),
         "plv_line_db_remove": (C.c_int, [vp, u64p, C.c_int]),
         "plv_triangulate_lines": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvLineTracks), dp, u8p]),
+        "plv_line_segments": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvLineTracks), dp, dp, ip, u8p]),
+        "plv_line_map_mode": (C.c_int, [vp, C.c_int]),
+        "plv_camera_used_lines": (C.c_int, [vp, C.POINTER(PlvStateView), C.c_int, ip, u64p, u8p, dp, dp, u8p]),
         "plv_line_jacobian_columns": (C.c_int, [C.POINTER(PlvStateView), C.POINTER(PlvLineTracks), ip, C.c_int, ip]),
         "plv_build_line_jacobians": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvLineTracks), C.c_int, ip, C.c_int, ip,
                                                dp, dp, dp]),
@@ -1924,6 +1927,36 @@ class Context:
         out, ok = np.zeros((L, 6)), np.zeros(L, dtype=np.uint8)
         self._chk(self.lib.plv_triangulate_lines(self.h, C.byref(st.c), C.byref(lt.c), _dp(out), _u8p(ok)))
         return out, ok
+
+    # ---- the line map
+    def line_segments(self, st, lt):
+        """plv_line_segments: 3-D end points of the lines of lt (lt.line_FinG) -> end_points [L, 6] (P1, P2), extent [L, 2] (lo*, hi*
+        along the line's direction), n_views [L], ok [L]"""
+        L = lt.c.n_lines
+        ep, ext, nv, ok = np.zeros((L, 6)), np.zeros((L, 2)), np.zeros(L, dtype=np.int32), np.zeros(L, dtype=np.uint8)
+        self._chk(self.lib.plv_line_segments(self.h, C.byref(st.c), C.byref(lt.c), _dp(ep), _dp(ext), _ip(nv), _u8p(ok)))
+        return ep, ext, nv, ok
+
+    def line_map_mode(self, on=None):
+        """plv_line_map_mode: True / False switches the line update's record for camera_used_lines on / off; None returns the mode"""
+        if on is None:
+            return bool(self.lib.plv_line_map_mode(self.h, -1))
+        self._chk(self.lib.plv_line_map_mode(self.h, 1 if on else 0))
+
+    def camera_used_lines(self, st, cap=512):
+        """plv_camera_used_lines: the lines of the last line update in batch order (nothing while line_map_mode is off) with their end
+        points on st -> dict(ids, accepted, line_FinG [n, 6], end_points [n, 6], ok)"""
+        n = C.c_int()
+        while True:
+            ids, acc, ok = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype=np.uint8)
+            lg, ep = np.zeros((cap, 6)), np.zeros((cap, 6))
+            rc = self.lib.plv_camera_used_lines(self.h, C.byref(st.c), cap, C.byref(n), _u64p(ids), _u8p(acc), _dp(lg), _dp(ep), _u8p(ok))
+            if rc != PLV_E_CAPACITY:
+                break
+            cap = n.value
+        self._chk(rc)
+        m = n.value
+        return dict(ids=ids[:m].copy(), accepted=acc[:m].copy(), line_FinG=lg[:m].copy(), end_points=ep[:m].copy(), ok=ok[:m].copy())
 
     # ---- detection
     def perform_detection(self, which, pts, ids, currid, mask=None, cap=None):

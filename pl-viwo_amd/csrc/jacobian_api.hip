@@ -6,6 +6,7 @@
 
 #include <chrono>
 #include "jacobian_kernels.hpp"
+#include "line_map_kernels.hpp"
 #include "nullspace_core.hpp"
 #include "update_kernels.hpp"
 #include "update_state.hpp"
@@ -955,6 +956,37 @@ int plv_triangulate_lines(plv_ctx *ctx, const plv_state_view *st, const plv_line
   PLV_HIP_CHECK(plv::memcpy_async(ok, d + o_ok, (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
   PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
   ctx->prof.collect();
+  return PLV_OK;
+}
+
+// The line map's end points (DESIGN.md "The line map"): the tracks staged as plv_triangulate_lines stages them — the poses of the
+// observations are the ones that call forms —, one launch, one copy back.
+int plv_line_segments(plv_ctx *ctx, const plv_state_view *st, const plv_line_tracks *lt, double *end_points, double *extent, int *n_views,
+                      uint8_t *ok) {
+  if (!ctx || !end_points || !ok) return PLV_E_BADARG;
+  if (st && lt && lt->n_lines == 0) return PLV_OK;
+  (void)hipSetDevice(ctx->device);
+  auto *us = plv_update_state(ctx);
+  TRY(check_line_views(st, lt, true, true));
+  const int L = lt->n_lines;
+  int dummy_cols[1] = {-1};
+  JacParams P{};
+  TRY(stage_line_inputs(ctx, us, st, lt, 0, dummy_cols, 2, P));
+  const size_t o_seg = 0, o_views = (size_t)L * 64, o_ok = o_views + (size_t)L * 4, total = o_ok + L;
+  TRY(us->staging_of(3).tri.reserve(total + 16));
+  char *d = us->staging_of(3).tri.as<char>();
+  TRY(launch_line_segments(ctx, P, (double *)(d + o_seg), (int *)(d + o_views), (unsigned char *)(d + o_ok)));
+  std::vector<char> h(total);
+  PLV_HIP_CHECK(plv::memcpy_async(h.data(), d, total, hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
+  ctx->prof.collect();
+  const double *seg = (const double *)(h.data() + o_seg);
+  for (int l = 0; l < L; ++l) {
+    std::copy(seg + 8 * (size_t)l, seg + 8 * (size_t)l + 6, end_points + 6 * (size_t)l);
+    if (extent) extent[2 * l] = seg[8 * (size_t)l + 6], extent[2 * l + 1] = seg[8 * (size_t)l + 7];
+  }
+  if (n_views) memcpy(n_views, h.data() + o_views, (size_t)L * 4);
+  memcpy(ok, h.data() + o_ok, (size_t)L);
   return PLV_OK;
 }
 

@@ -128,6 +128,16 @@ struct LineTracker {
   // equalised form is not current yet) through its histogram
   std::vector<uint64_t> dec_ids;  // plv_decision_trace: the last line update's batch and its gate values (plv_last_line_decisions)
   std::vector<double> dec_vals;
+  // plv_line_map_mode: the batch of the last line update — ids, verdicts and lines as the update returned them, and the pool's flattened
+  // observations (the job's own arrays, handed over when the update ends) with the pool index of every line of the batch
+  struct LineMapRecord {
+    std::vector<uint64_t> ids;
+    std::vector<uint8_t> accepted;
+    std::vector<double> lines, res_R, res_p;
+    std::vector<int> sel, ptr;
+    std::vector<double> ot;
+    std::vector<float> uv, uvn;
+  } map_rec;
   const uint8_t *early_raw = nullptr;
   const unsigned *early_hist = nullptr;
   int early_w = 0, early_h = 0;
@@ -1466,6 +1476,27 @@ struct LinesUpdate {
     return PLV_OK;
   }
 
+  // plv_line_map_mode: the batch and the pool's flattened observations become the tracker's record (plv_camera_used_lines).  The job's
+  // arrays are not read again — they would be released with the job — so they are handed over; CPI poses the fused route formed on
+  // the device only are fetched per observation first (the two-step route has them already): with a CPI table the record carries the
+  // poses of the update as res_R / res_p, and plv_camera_used_lines computes its end points from those — the table is the caller's
+  // and gone by then — taking from its `st` the window test, the extrinsics and the time offset.  The record holds the flattened
+  // observations of the whole pool (LinesJob's arrays as they are), not only the batch's: bounded by the pool, a few dozen tracks of
+  // at most the window's frames; plv_camera_used_lines gathers the batch's part out of it on every call (cold path).
+  int keep_for_map(const Selection<LineTrack> &S) {
+    LineTracker::LineMapRecord &R = T->map_rec;
+    if (J.cpi.on && J.cpi.R.empty()) {
+      const int rc = cpi_expand(ctx, st, opt->cpi, J.cpi);
+      if (rc != PLV_OK) return finish(rc);
+    }
+    R.sel = S.sel, R.accepted = S.acc, R.lines = S.feat;
+    R.ids.resize(S.sel.size());
+    for (size_t q = 0; q < S.sel.size(); ++q) R.ids[q] = pool[S.sel[q]].id;
+    R.ptr = std::move(J.ptr), R.ot = std::move(J.ot), R.uv = std::move(J.uv), R.uvn = std::move(J.uvn);
+    if (J.cpi.on) R.res_R = std::move(J.cpi.R), R.res_p = std::move(J.cpi.p);
+    return PLV_OK;
+  }
+
   // REF UpdaterCamera.cpp:441-444 copy_to_db(lbd_unused, line) of a rejected line: every view usable and nothing of the line handed
   // back earlier — the usual case — makes the copy the reference builds view by view the track itself, returned whole by the
   // hand-back like the candidates the update never took
@@ -1479,6 +1510,7 @@ struct LinesUpdate {
 
 int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, double *dx,
                             plv_update_result *res, uint64_t *line_ids, uint8_t *accepted_out, double *lines_out, int cap) {
+  if (ctx && ctx->line_map) ltr(ctx, false)->map_rec = LineTracker::LineMapRecord();  // (whatever happens below: the old record is gone)
   if (!ctx || !st || !opt || !dx || !res || st->n_clones < 2 || opt->max_obs < 2) return PLV_E_BADARG;
   LineTracker *T = ltr(ctx);
   *res = plv_update_result{0, 0, 0, 0, 0, PLV_OK, 0, 0, 0};
@@ -1527,7 +1559,59 @@ int plv_camera_update_lines(plv_ctx *ctx, const plv_state_view *st, const plv_up
   if (ctx->decision_trace) TRY(U.record_decisions(S));
   plv::frame_mark("@ line arrays of the selected done");
   res->n_accepted = return_rejected(U.pool, S, U.dt, U.start_of, U.unused, accepted_out, [&U](int l) { return U.returns_whole(l); });
+  if (ctx->line_map) TRY(U.keep_for_map(S));
   return U.finish(PLV_OK);
+}
+
+// ------------------------------------------------------------------------------------------ the line map
+int plv_line_map_mode(plv_ctx *ctx, int on) {
+  if (!ctx) return PLV_E_BADARG;
+  if (on < 0) return ctx->line_map ? 1 : 0;
+  ctx->line_map = on != 0;
+  if (!ctx->line_map) ltr(ctx, false)->map_rec = LineTracker::LineMapRecord();
+  return PLV_OK;
+}
+
+// The record of the last line update (LineMapRecord) in batch order, its end points by plv_line_segments on st.  Reads only.
+int plv_camera_used_lines(plv_ctx *ctx, const plv_state_view *st, int cap, int *n, uint64_t *ids, uint8_t *accepted, double *line_FinG, double *end_points,
+                          uint8_t *ok) {
+  if (!ctx || !n || cap < 0) return PLV_E_BADARG;
+  *n = 0;
+  if (!ctx->line_map) return PLV_OK;
+  const LineTracker::LineMapRecord &R = ltr(ctx, false)->map_rec;
+  const int L = (int)R.sel.size();
+  *n = L;
+  if (L == 0) return PLV_OK;
+  if (cap < L) {
+    plv::set_last_error("plv_camera_used_lines: %d lines, room for %d", L, cap);
+    return PLV_E_CAPACITY;
+  }
+  if (!st || !ids || !accepted || !line_FinG || !end_points || !ok) return PLV_E_BADARG;
+  std::copy(R.ids.begin(), R.ids.end(), ids);
+  std::copy(R.accepted.begin(), R.accepted.end(), accepted);
+  std::copy(R.lines.begin(), R.lines.end(), line_FinG);
+  // the batch's observations out of the pool's
+  const bool res = !R.res_R.empty();
+  std::vector<int> ptr(1, 0);
+  std::vector<double> ot, rR, rp;
+  std::vector<float> uv, uvn;
+  for (int q = 0; q < L; ++q) {
+    const size_t a = (size_t)R.ptr[R.sel[q]], b = (size_t)R.ptr[R.sel[q] + 1];
+    ot.insert(ot.end(), R.ot.begin() + a, R.ot.begin() + b);
+    uv.insert(uv.end(), R.uv.begin() + 4 * a, R.uv.begin() + 4 * b);
+    uvn.insert(uvn.end(), R.uvn.begin() + 4 * a, R.uvn.begin() + 4 * b);
+    if (res) rR.insert(rR.end(), R.res_R.begin() + 9 * a, R.res_R.begin() + 9 * b), rp.insert(rp.end(), R.res_p.begin() + 3 * a, R.res_p.begin() + 3 * b);
+    ptr.push_back((int)ot.size());
+  }
+  if (ot.empty()) {  // (cannot be: a line of the batch has two usable views)
+    std::fill(end_points, end_points + 6 * (size_t)L, 0.0);
+    std::fill(ok, ok + L, (uint8_t)0);
+    return PLV_OK;
+  }
+  plv_line_tracks lt{};
+  lt.n_lines = L, lt.obs_ptr = ptr.data(), lt.obs_time = ot.data(), lt.seg_uv = uv.data(), lt.seg_uvn = uvn.data(), lt.line_FinG = line_FinG;
+  if (res) lt.res_R = rR.data(), lt.res_p = rp.data();
+  return plv_line_segments(ctx, st, &lt, end_points, nullptr, nullptr, ok);
 }
 
 }  // extern "C"

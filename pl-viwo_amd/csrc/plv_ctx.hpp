@@ -477,6 +477,8 @@ struct plv_ctx {
   void *after_edges_arg = nullptr;
   // plv_decision_trace: the values behind every verdict of the point update stay on the device until plv_last_point_decisions asks
   bool decision_trace = false;
+  // plv_line_map_mode: the line update keeps the tracks of its batch for plv_camera_used_lines (line_api.hip, LineMapRecord)
+  bool line_map = false;
   plv::DevBuf d_tri_dbg, d_gate_dec, d_gate_dec_l;  // (_l: the line update's gate)
   int dec_F_l = 0;        // entries of the last line batch whose gate values are in d_gate_dec_l (0: none)
   int dec_F = 0;          // entries of the last point batch whose values are in d_tri_dbg

@@ -62,6 +62,35 @@ __device__ __forceinline__ int wave_sum_i32_lane63(int v) {
   PLV_WAVE_REDUCE_BODY(dpp_mov_i32)
   return v;
 }
+// The value of lane (lane ^ MASK), all lanes active: inside a quad (1, 2) and across half a row (8 = row_ror:8) a DPP move, the other
+// distances go through the permute network (no LDS is allocated).
+template <int MASK> __device__ __forceinline__ double lane_xor_f64(double v) {
+  if constexpr (MASK == 1) return dpp_mov_f64<0xB1>(v);
+  else if constexpr (MASK == 2) return dpp_mov_f64<0x4E>(v);
+  else if constexpr (MASK == 8) return dpp_mov_f64<0x128>(v);
+  else return __hiloint2double(__shfl_xor(__double2hiint(v), MASK, 64), __shfl_xor(__double2loint(v), MASK, 64));
+}
+// One compare-exchange step of the bitonic network on two independent keys: lanes J apart, inside ascending / descending runs of K.
+template <int K, int J> __device__ __forceinline__ void bitonic_step2_f64(double &a, double &b, int lane) {
+  const double pa = lane_xor_f64<J>(a), pb = lane_xor_f64<J>(b);
+  const bool keep_min = ((lane & J) == 0) == ((lane & K) == 0);
+  a = keep_min ? (pa < a ? pa : a) : (pa > a ? pa : a);
+  b = keep_min ? (pb < b ? pb : b) : (pb > b ? pb : b);
+}
+template <int K, int J> __device__ __forceinline__ void bitonic_merge2_f64(double &a, double &b, int lane) {
+  bitonic_step2_f64<K, J>(a, b, lane);
+  if constexpr (J > 1) bitonic_merge2_f64<K, J / 2>(a, b, lane);
+}
+// Two keys per lane, each sorted ascending over the 64 lanes (lane 0 the smallest; +inf sorts last, no NaN may come in): 21
+// compare-exchange steps, all lanes must be active.
+__device__ __forceinline__ void wave_sort2_f64(double &a, double &b, int lane) {
+  bitonic_merge2_f64<2, 1>(a, b, lane);
+  bitonic_merge2_f64<4, 2>(a, b, lane);
+  bitonic_merge2_f64<8, 4>(a, b, lane);
+  bitonic_merge2_f64<16, 8>(a, b, lane);
+  bitonic_merge2_f64<32, 16>(a, b, lane);
+  bitonic_merge2_f64<64, 32>(a, b, lane);  // (lane & 64 == 0 everywhere: the last merge ascends)
+}
 // Sum over each aligned group of 4 lanes, result in all 4 lanes.
 __device__ __forceinline__ double quad_sum_f64(double v) {
   v += dpp_mov_f64<0xB1>(v);

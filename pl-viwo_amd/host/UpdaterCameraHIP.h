@@ -48,6 +48,28 @@ public:
     return cv::Mat(wh.at(1), wh.at(0), CV_8UC1, ptr, (size_t)stride);
   }
 
+  // ---- the map ROSPublisher::publish_cam_features publishes (REF: ROSPublisher.cpp:220-241).  Off by default: the updates then ask
+  // the library for nothing they do not ask today.  On: every update appends the accepted MSCKF points and the 3-D segments of the
+  // used lines (plv_line_map_mode + plv_camera_used_lines: LineFeature::EndPoints, which the reference leaves uninitialised).
+  void line_map(bool on) {
+    map_on = on && plv_line_map_mode(ctx, on ? 1 : 0) == PLV_OK;
+    if (!on) (void)plv_line_map_mode(ctx, 0), msckf_used.clear(), lines_used.clear();
+  }
+  // REF: UpdaterCamera.h:41 / UpdaterCamera.cpp:466-475 — the features used since the last call; clears
+  std::vector<Eigen::Vector3d> get_used_msckf() {
+    std::vector<Eigen::Vector3d> cp = msckf_used;
+    msckf_used.clear();
+    return cp;
+  }
+  // REF: UpdaterCamera.h:44 / UpdaterCamera.cpp:477-484 — [P1; P2] of every triangulated line of the batches since the last call,
+  // accepted by the gate or not, as LineHelper::cleanup_lines lists them (:522-530).  The reference's clear() is commented out and
+  // its list grows without bound; this one is cleared by the call, like the points.
+  std::vector<Eigen::Matrix<double, 6, 1>> get_used_lines() {
+    std::vector<Eigen::Matrix<double, 6, 1>> cp = lines_used;
+    lines_used.clear();
+    return cp;
+  }
+
   // the window as the kernels read it: clone times ascending, rotations row-major, first estimates, covariance ids
   struct View {
     std::vector<double> t, R, p, Rf, pf;
@@ -133,14 +155,20 @@ public:
     View w;
     bool ok = true;
     build_view(w);
-    if (plv_camera_update_points(ctx, &w.v, &o, dx.data(), &r, nullptr, nullptr, nullptr) != PLV_OK) return false;
+    MapOut mo(map_on ? o.max_msckf : 0);
+    if (plv_camera_update_points(ctx, &w.v, &o, dx.data(), &r, nullptr, mo.acc(), mo.p()) != PLV_OK) return false;
     if (r.status == PLV_OK && r.n_accepted > 0) StateHelperHIP::apply(ctx, state, dx);
     ok = ok && r.status == PLV_OK;
+    if (map_on) collect_points(mo, r);
     if (trackLSDS) {
       build_view(w);  // the clones moved
       if (plv_camera_update_lines(ctx, &w.v, &o, dx.data(), &r, nullptr, nullptr, nullptr, 0x7fffffff) != PLV_OK) return false;
       if (r.status == PLV_OK && r.n_accepted > 0) StateHelperHIP::apply(ctx, state, dx);
       ok = ok && r.status == PLV_OK;
+      if (map_on) {
+        build_view(w);
+        collect_lines(w.v);
+      }
     }
     return ok;
   }
@@ -243,14 +271,48 @@ private:
     plv_update_result rp{}, rl{};
     Mean m;
     build_mean(m);
+    MapOut mo(map_on && update ? o.max_msckf : 0);
     plv_try_update up{&o, trackLSDS ? &o : nullptr, (int)m.vars.size(), m.vars.data(), dx_p.data(), dx_l.data(), &rp, &rl,
-                      nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0x7fffffff, 0};
+                      nullptr, mo.acc(), mo.p(), nullptr, nullptr, nullptr, 0x7fffffff, 0};
     plv_camera_frame_io io{timestamp, slot, img, step, mask.empty() ? nullptr : mask.data, trackLSDS ? 1 : 0, update ? &up : nullptr, 0};
     if (plv_camera_frame(ctx, &m.w.v, &io) != PLV_OK) return false;
     if (update) write_back(m);
+    if (map_on && update) {
+      collect_points(mo, rp);
+      if (trackLSDS) collect_lines(m.w.v);  // (the view's arrays are the mean the call moved: the state after both updates)
+    }
     return rp.status == PLV_OK && rl.status == PLV_OK;
   }
 
+  // the outputs of the point update the map reads (none while the map is off: the library is handed null pointers, as before)
+  struct MapOut {
+    std::vector<uint8_t> accepted;
+    std::vector<double> p_FinG;
+    explicit MapOut(int cap) : accepted((size_t)(cap > 0 ? cap : 0)), p_FinG(3 * accepted.size()) {}
+    uint8_t *acc() { return accepted.empty() ? nullptr : accepted.data(); }
+    double *p() { return p_FinG.empty() ? nullptr : p_FinG.data(); }
+  };
+  void collect_points(const MapOut &mo, const plv_update_result &r) {  // REF: UpdaterCamera.cpp:266-292 (msckf_used)
+    if (r.status != PLV_OK) return;
+    for (int f = 0; f < r.n_msckf && f < (int)mo.accepted.size(); ++f)
+      if (mo.accepted[f]) msckf_used.push_back(Eigen::Map<const Eigen::Vector3d>(&mo.p_FinG[3 * (size_t)f]));
+  }
+  // REF: LineHelper.cpp:522-530 (lines_used): every triangulated line of the batch, whatever the gate or EKFUpdate made of it — the
+  // update's status is not looked at, as cleanup_lines does not look at it (the Python driver's accepted_only filter does)
+  void collect_lines(const plv_state_view &v) {
+    int n = 0;
+    if (plv_camera_used_lines(ctx, &v, 0, &n, nullptr, nullptr, nullptr, nullptr, nullptr) != PLV_E_CAPACITY || n <= 0) return;
+    std::vector<uint64_t> ids((size_t)n);
+    std::vector<uint8_t> acc((size_t)n), ok((size_t)n);
+    std::vector<double> lg(6 * (size_t)n), ep(6 * (size_t)n);
+    if (plv_camera_used_lines(ctx, &v, n, &n, ids.data(), acc.data(), lg.data(), ep.data(), ok.data()) != PLV_OK) return;
+    for (int l = 0; l < n; ++l)
+      if (ok[l]) lines_used.push_back(Eigen::Map<const Eigen::Matrix<double, 6, 1>>(&ep[6 * (size_t)l]));
+  }
+
+  bool map_on = false;
+  std::vector<Eigen::Vector3d> msckf_used;
+  std::vector<Eigen::Matrix<double, 6, 1>> lines_used;
   std::shared_ptr<State> state;
   plv_ctx *ctx;
   std::shared_ptr<ov_core::TrackKLT_HIP> trackFEATS;

@@ -220,6 +220,55 @@ def write_ppm(path, rgb):
         f.write(rgb.tobytes())
 
 
+class MapAccumulator:
+    """The map of a whole replay (SystemManager(line_map=True)): behind every camera message the MSCKF points and line segments the
+    updates used are taken over (get_used_msckf / get_used_lines clear their lists) and the in-state landmarks' latest positions are
+    noted by feature id.  `after_camera` has replay()'s callback signature."""
+    KINDS = {"msckf": 0, "slam": 1, "line": 2}
+
+    def __init__(self, accepted_only=True):
+        self.accepted_only = accepted_only
+        self.points, self.segments, self.landmarks = [], [], {}
+
+    def after_camera(self, system, frame, t):
+        self.points.append(system.get_used_msckf())
+        self.segments.append(system.get_used_lines(self.accepted_only))
+        for fid, lm in system.state.slam.items():
+            self.landmarks[int(fid)] = np.array(lm.p, dtype=float)
+
+    def arrays(self):
+        """-> (msckf points [n, 3], landmark positions [m, 3], segments [k, 6])"""
+        pts = np.concatenate(self.points) if self.points else np.zeros((0, 3))
+        seg = np.concatenate(self.segments) if self.segments else np.zeros((0, 6))
+        lms = np.array([self.landmarks[k] for k in sorted(self.landmarks)], dtype=float).reshape(-1, 3)
+        return pts, lms, seg
+
+    def stats(self):
+        pts, lms, seg = self.arrays()
+        length = np.linalg.norm(seg[:, 3:] - seg[:, :3], axis=1)
+        return dict(map_points=int(len(pts) + len(lms)), map_lines=int(len(seg)),
+                    map_line_length_p50=float(np.median(length)) if len(length) else 0.0)
+
+    def write_ply(self, path):
+        """ASCII PLY: a vertex per MSCKF point, landmark and segment end point (property `kind`: 0 / 1 / 2), an edge per segment"""
+        pts, lms, seg = self.arrays()
+        verts = [(p, self.KINDS["msckf"]) for p in pts] + [(p, self.KINDS["slam"]) for p in lms]
+        first = len(verts)
+        for s in seg:
+            verts += [(s[:3], self.KINDS["line"]), (s[3:], self.KINDS["line"])]
+        d = os.path.dirname(path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        with open(path, "w") as f:
+            f.write("ply\nformat ascii 1.0\ncomment kind: 0 MSCKF point, 1 in-state landmark, 2 line segment end point\n")
+            f.write(f"element vertex {len(verts)}\nproperty double x\nproperty double y\nproperty double z\nproperty uchar kind\n")
+            f.write(f"element edge {len(seg)}\nproperty int vertex1\nproperty int vertex2\nend_header\n")
+            for p, kind in verts:
+                f.write(f"{p[0]:.6f} {p[1]:.6f} {p[2]:.6f} {kind}\n")
+            for i in range(len(seg)):
+                f.write(f"{first + 2 * i} {first + 2 * i + 1}\n")
+
+
 def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_obs=24, host_images=False, after_camera=None, **system_kw):
     """run_bag's main loop.  Returns (SystemManager statistics, times, poses [n][7] = p, q).  after_camera(sys, frame, t), when given,
     is called behind every camera message (run_bag.cpp:287-296 publishes the track image there); its time is kept apart from the

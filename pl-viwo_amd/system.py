@@ -425,8 +425,11 @@ class SystemManager:
     one_call_update = True      # try_update through plv_camera_try_update (False: plv_camera_update_points / _lines with the dx applied here)
     slam_pass = True            # in-state landmarks through camera_update_slam / camera_init_slam where the context has them (False: one by one)
 
-    def __init__(self, op, device=0, max_obs=24, context_factory=None, iw_initializer_factory=None, decisions=None):
-        """context_factory / iw_initializer_factory: stand-ins with the interface of Context / IwInitializer (the tests run the same
+    def __init__(self, op, device=0, max_obs=24, context_factory=None, iw_initializer_factory=None, decisions=None, line_map=False):
+        """line_map: keep what ROSPublisher::publish_cam_features publishes after every camera update — the accepted MSCKF points and
+        the 3-D segments of the used lines (get_used_msckf / get_used_lines / get_slam_cloud); off, the driver makes exactly the calls
+        it makes without it.
+        context_factory / iw_initializer_factory: stand-ins with the interface of Context / IwInitializer (the tests run the same
         driver over the CPU oracle through them); the defaults are the HIP library.  decisions: a list that receives one record per
         camera update — (kind, frame, state time, pool size, ids that were triangulated, accepted flags, status, the values behind the verdicts
         where the context reports them, dx) — for the
@@ -469,6 +472,11 @@ class SystemManager:
         self.max_obs = max_obs
         if decisions is not None and hasattr(self.ctx, "decision_trace"):
             self.ctx.decision_trace(True)
+        # the map (REF: UpdaterCamera::get_used_msckf / get_used_lines, UpdaterCamera.cpp:466-484)
+        self.line_map = bool(line_map)
+        self._used_msckf, self._used_lines = [], []
+        if self.line_map:
+            self.ctx.line_map_mode(True)
         self.state = State(op, self.ctx)
         self.noise = imu_noise(e.imu.sigma_w, e.imu.sigma_wb, e.imu.sigma_a, e.imu.sigma_ab, tuple(e.gravity))
         # Propagator
@@ -951,6 +959,8 @@ class SystemManager:
         self._cov_probe("after the point update")
         self.stats["cam_features"] += out["n_msckf"]
         self.stats["cam_accepted"] += out["n_accepted"] if out["status"] == 0 else 0
+        if self.line_map and out["status"] == 0 and out["n_accepted"] > 0:
+            self._used_msckf.append(np.array(out["p_FinG"], dtype=float).reshape(-1, 3)[np.asarray(out["accepted"]) != 0])
 
     def _count_lines(self, lo):
         if self.decisions is not None:
@@ -966,6 +976,33 @@ class SystemManager:
         elif lo["n_accepted"] > 0:
             self.stats["line_updates"] += 1
             self.stats["lines_accepted"] += lo["n_accepted"]
+        if self.line_map and lo["n_lines"] > 0:
+            ul = self.ctx.camera_used_lines(self.state.view())       # (end points on the state the line update left)
+            keep = ul["ok"] != 0
+            acc = ul["accepted"][keep] if lo["status"] == 0 else np.zeros(int(keep.sum()), dtype=np.uint8)
+            self._used_lines.append((ul["end_points"][keep], acc))
+
+    # ---------------------------------------------------------------------------------------------- the map
+    def get_used_msckf(self):
+        """UpdaterCamera::get_used_msckf (REF: UpdaterCamera.cpp:466-475): p_FinG [n, 3] of the MSCKF features the updates since the
+        last call accepted; cleared by the call.  Empty without line_map."""
+        pts = np.concatenate(self._used_msckf) if self._used_msckf else np.zeros((0, 3))
+        self._used_msckf = []
+        return pts
+
+    def get_used_lines(self, accepted_only=True):
+        """UpdaterCamera::get_used_lines (REF: UpdaterCamera.cpp:477-484): the 3-D segments [n, 6] = (P1, P2) of the lines the updates
+        since the last call used (Context.camera_used_lines) — those the gate accepted, or with accepted_only=False every
+        triangulated line of the batches, which is what the reference lists; cleared by the call (the reference's clear() is commented
+        out and its list grows for ever).  Empty without line_map."""
+        segs = [ep if not accepted_only else ep[acc != 0] for ep, acc in self._used_lines]
+        self._used_lines = []
+        return np.concatenate(segs) if segs else np.zeros((0, 6))
+
+    def get_slam_cloud(self):
+        """positions [n, 3] of the in-state landmarks (State::_features_SLAM through landmark_xyz)"""
+        lms = list(self.state.slam.values())
+        return np.array([lm.p for lm in lms], dtype=float).reshape(-1, 3)
 
     def _landmark_system(self, t, uv, p, p_fej):
         """get_feature_jacobian_full for one feature: (rows, Hf [rows][3], Hx [rows][k], res, cols)."""

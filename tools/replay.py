@@ -7,6 +7,7 @@
     python tools/replay.py --synthetic 12 --max-slam 12 --feat-rep GLOBAL_FULL_INVERSE_DEPTH   # in-state landmarks, either representation
     python tools/replay.py --synthetic 12 --track-images DIR [--track-image-every 5] [--track-image-layers history,lines,mask]
                                                                      # the track picture of the chosen frames as DIR/<frame>.ppm
+    python tools/replay.py --synthetic 12 --map map.ply              # the map of the whole replay: MSCKF points, landmarks, 3-D line segments
 """
 import argparse
 import importlib
@@ -42,6 +43,10 @@ def main():
                     "as binary PPM files DIR/<frame>.ppm")
     ap.add_argument("--track-image-every", type=int, default=1, metavar="N", help="every N-th camera frame (default: every frame)")
     ap.add_argument("--track-image-layers", default="history", help="comma-separated: history, active, lines, mask")
+    ap.add_argument("--map", metavar="FILE.ply", help="write the map of the whole replay as an ASCII PLY: the accepted MSCKF points, the in-state "
+                    "landmarks and the end points of the used lines as vertices (property kind: 0 / 1 / 2), one edge per line segment")
+    ap.add_argument("--map-all-lines", action="store_true", help="every triangulated line of the updates' batches (the reference's list), not "
+                    "only those the gate accepted")
     a = ap.parse_args()
     if a.track_image_every < 1:
         ap.error("--track-image-every: a positive number")
@@ -80,12 +85,24 @@ def main():
                 path = os.path.join(a.track_images, f"{frame:06d}.ppm")
                 rp.write_ppm(path, rgb)
                 written.append(path)
+    the_map, system_kw = None, {}
+    if a.map:
+        the_map, system_kw, picture = rp.MapAccumulator(accepted_only=not a.map_all_lines), dict(line_map=True), after_camera
+
+        def after_camera(system, frame, t):
+            the_map.after_camera(system, frame, t)
+            if picture is not None:
+                picture(system, frame, t)
     t0 = time.time()
-    stats, times, poses = rp.replay(op, host_images=a.host_images, after_camera=after_camera, progress=lambda s, t: print(f"  t={t:8.3f}  clones {s.stats['clones']}  cam accepted "
+    stats, times, poses = rp.replay(op, host_images=a.host_images, after_camera=after_camera, **system_kw, progress=lambda s, t: print(f"  t={t:8.3f}  clones {s.stats['clones']}  cam accepted "
                                                                     f"{s.stats['cam_accepted']}/{s.stats['cam_features']}  wheel {s.stats['wheel_accepted']}  zupt {s.stats['zupt_updates']}", flush=True))
     res = dict(config=a.config, wall_s=round(time.time() - t0, 2), stats=stats, poses_logged=len(times), trajectory=op.sys.path_trajectory)
     if a.track_images:
         res["track_images_written"] = len(written)
+    if the_map is not None:
+        the_map.write_ply(a.map)
+        stats.update(the_map.stats())
+        res["map"] = a.map
     if a.gt and len(times) > 2:
         ctx = pkg.Context(pkg.default_config(752, 480))
         et, ep, co, cp = pkg.traj_load(op.sys.path_trajectory)
