@@ -238,8 +238,12 @@ def test_update_graph_replay_matches_eager(pkg, oracle):
 @pytest.mark.parametrize("k", [12, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 79, 95, 96, 97, 111, 112, 113, 127, 128, 129, 143, 144, 145,
                                159, 160, 161, 176, 191, 192])
 def test_msckf_update_tile_boundaries(ctx, oracle, k):
-    """Every 16-column tile boundary of the blocked factorisations (the kernels are instantiated for 2, 4, 7, 8, 10 and 12 tiles), with
-    fewer stacked rows than columns for the small ones (no compression) and more for the rest."""
+    """Widths around the 16-column tile boundaries, on two routes.  Even k and k <= 17 (F, M = 30, 8: more row slots than columns) take
+    the whitened route: prior factor and EKF solve of k x k, i.e. the full widths 16 t and, one below and one past a boundary, only
+    15 and 17.  Odd k >= 31 (F, M = 4, 4: at most 20 row slots, fewer than k) are not compressed: the EKF solve factors at most
+    20 x 20 (the two-tile instantiation) and no prior factor is taken, so what varies there is the number of columns, not the
+    factorisation.  The widths 16 t - 15, 16 t - 1 and 16 t on the whitened route, with the route asserted, at every instantiation
+    (2, 4, 7, 8, 10 and 12 tiles) and tile count: test_gpu_blocked_chol.py."""
     n = k + 15
     F, M = (4, 4) if k >= 31 and k % 2 else (30, 8)
     P = synth.spd_cov(n, seed=k)

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import synth
+from chol_cases import truth as _truth   # (the extended-precision restatement, shared with tests/test_gpu_blocked_chol.py)
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "replay_batches.npz")
@@ -95,44 +96,6 @@ def _conditioned(k, cond, seed):
     Q, _ = np.linalg.qr(rng.normal(size=(k, k)))
     s = np.logspace(0, -np.log10(cond), k)
     return (Q * s) @ Q.T
-
-
-def _truth(P, rows, Hf, Hx, res, cols, acc):
-    """information-form update in extended precision on the accepted, projected rows: P' = (P^-1 + H^T H)^-1, dx = P' H^T r"""
-    ld = np.longdouble
-    n = P.shape[0]
-    Hs, rs = [], []
-    for f in range(len(rows)):
-        if not acc[f]:
-            continue
-        m = int(rows[f])
-        q, _ = np.linalg.qr(Hf[f, :, :m].T, mode="complete")
-        N = q[:, Hf.shape[1]:]
-        Hs.append(N.T @ Hx[f, :, :m].T)
-        rs.append(N.T @ res[f, :m])
-    H = np.zeros((sum(h.shape[0] for h in Hs), n))
-    H[:, cols] = np.vstack(Hs)
-    r = np.concatenate(rs)
-    # K form in long double with a Cholesky solve written out (numpy's linalg has no extended precision)
-    Hl, Pl, rl = H.astype(ld), P.astype(ld), r.astype(ld)
-    S = Hl @ Pl @ Hl.T + np.eye(H.shape[0], dtype=ld)
-    L = np.zeros_like(S)
-    for i in range(S.shape[0]):
-        for j in range(i + 1):
-            v = S[i, j] - L[i, :j] @ L[j, :j]
-            L[i, j] = np.sqrt(v) if i == j else v / L[j, j]
-    M = Pl @ Hl.T
-
-    def solve(B):   # S^-1 B
-        Y = np.zeros_like(B)
-        for i in range(L.shape[0]):
-            Y[i] = (B[i] - L[i, :i] @ Y[:i]) / L[i, i]
-        X = np.zeros_like(B)
-        for i in range(L.shape[0] - 1, -1, -1):
-            X[i] = (Y[i] - L[i + 1:, i] @ X[i + 1:]) / L[i, i]
-        return X
-    KT = solve(M.T)
-    return (Pl - M @ KT).astype(np.float64), (KT.T @ rl).astype(np.float64)
 
 
 @pytest.mark.parametrize("mode,cond,tol", [(0, 1e2, 1e-9), (0, 1e4, 1e-9), (0, 1e6, 1e-9), (0, 1e8, 1e-9), (1, 1e4, 1e-9), (1, 1e8, 1e-9)])
