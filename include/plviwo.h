@@ -595,7 +595,12 @@ int plv_build_line_jacobians_resident(plv_ctx *ctx, const plv_state_view *st, co
  * update/cam/TrackLSD.cpp:194-235): half-resolution image, FastLineDetector(cfg.line_length_threshold,
  * cfg.line_distance_threshold, cfg.canny_th1, cfg.canny_th2, 3, no merge), x2, drop length^2 <=
  * cfg.line_min_length_px^2.  Works on the equalised image of the current (PLV_PYR_CUR) or previous
- * frame held by the ctx; lines = x1 y1 x2 y2 full-resolution pixels, in the detector's output order. */
+ * frame held by the ctx; lines = x1 y1 x2 y2 full-resolution pixels, in the detector's output order.
+ * The Canny thresholds may come in either order; with two different ones the edge map goes through hysteresis and FastLineDetector's
+ * two corners are cleared behind it.  Settings the detector cannot honour are refused with PLV_E_BADARG and a message that names the
+ * field, by this call, plv_line_detect_launch / _finish and the line tracker's feeds alike, before anything is launched:
+ * canny_aperture other than 3, line_length_threshold below 1, line_distance_threshold not finite or not positive,
+ * line_min_length_px negative or not finite, a negative Canny threshold. */
 int plv_detect_lines(plv_ctx *ctx, int which, float *lines, int cap, int *n_out);
 /* With the prefetch on, plv_tracker_feed / _staged / _downsampled run the line detector of the new image themselves: resize + Canny
  * go on the stream ahead of the point front-end, the host walks the edge chains and grows the segments while the device runs LK and

@@ -321,8 +321,39 @@ LineTracker *ltr(plv_ctx *ctx, bool run_deferred) {
   return T;
 }
 
+// The detector's settings as the kernels and the host stage take them.  What they cannot honour is refused here, in front of every
+// buffer and every launch: canny_kernel is the 3 x 3 Sobel (aperture 3) and nothing else; the length threshold is a divisor on the
+// device and on the host (slots per chain) and sizes their buffers; a distance threshold or a minimum length that is not a number
+// decides nothing.
+int fld_params_of(const plv_config &cfg, FldParams &fp) {
+  if (cfg.canny_aperture != 3) {
+    set_last_error("plv_detect_lines: canny_aperture %d is not supported (the edge kernel is the 3 x 3 Sobel: 3)", cfg.canny_aperture);
+    return PLV_E_BADARG;
+  }
+  if (cfg.line_length_threshold < 1) {
+    set_last_error("plv_detect_lines: line_length_threshold %d must be 1 or more", cfg.line_length_threshold);
+    return PLV_E_BADARG;
+  }
+  if (!std::isfinite(cfg.line_distance_threshold) || !(cfg.line_distance_threshold > 0.0f)) {
+    set_last_error("plv_detect_lines: line_distance_threshold %g must be finite and positive", (double)cfg.line_distance_threshold);
+    return PLV_E_BADARG;
+  }
+  if (!std::isfinite(cfg.line_min_length_px) || cfg.line_min_length_px < 0.0f) {
+    set_last_error("plv_detect_lines: line_min_length_px %g must be finite and not negative", (double)cfg.line_min_length_px);
+    return PLV_E_BADARG;
+  }
+  if (cfg.canny_th1 < 0 || cfg.canny_th2 < 0) {
+    set_last_error("plv_detect_lines: canny_th1 %d / canny_th2 %d must not be negative", cfg.canny_th1, cfg.canny_th2);
+    return PLV_E_BADARG;
+  }
+  fp = FldParams{cfg.line_length_threshold, (float)cfg.line_distance_threshold, cfg.canny_th1, cfg.canny_th2};
+  return PLV_OK;
+}
+
 // detection on the device + the host tail of perform_detection_monocular (x2, FilterShortLines)
 int detect(plv_ctx *ctx, LineTracker *T, int which, std::vector<float> &lines, bool launch_only = false) {
+  FldParams fp;
+  TRY(fld_params_of(ctx->cfg, fp));
   const bool prelaunched = !launch_only && !T->walk_on_device && T->pending_which == which && T->pending_fed == plv_front_fed_count(ctx);
   if (!launch_only) T->pending_which = -1;
   int W = 0, H = 0;
@@ -347,12 +378,11 @@ int detect(plv_ctx *ctx, LineTracker *T, int which, std::vector<float> &lines, b
   TRY(T->pts.reserve(npix * sizeof(int2)));
   TRY(T->chains.reserve(kChainCap * sizeof(FldChain)));
   TRY(T->counts.reserve(12 * sizeof(int)));  // (4 counts, then the 8 words of the component walk)
-  const size_t slot_cap = npix / (size_t)std::max(1, ctx->cfg.line_length_threshold) + kChainCap;
+  const size_t slot_cap = npix / (size_t)fp.length_threshold + kChainCap;
   TRY(T->segs.reserve(slot_cap * sizeof(float4)));
   TRY(T->seg_count.reserve(kChainCap * sizeof(int)));
   FldBuffers b{T->half.as<uint8_t>(), T->map.as<uint8_t>(), T->work.as<uint8_t>(), T->pts.as<int2>(), T->chains.as<FldChain>(),
                kChainCap,             T->counts.as<int>(),  T->segs.as<float4>(), T->seg_count.as<int>()};
-  FldParams fp{ctx->cfg.line_length_threshold, (float)ctx->cfg.line_distance_threshold, ctx->cfg.canny_th1, ctx->cfg.canny_th2};
   const size_t bytes = 16 + kChainCap * (sizeof(FldChain) + sizeof(int));
   const size_t lab_off = bytes + ((2 * npix + 63) & ~(size_t)63) + npix * sizeof(int2);  // (behind the host stage's chain points)
   // (behind the labels: the parts' pixel lists, ccl_flatten_kernel)

@@ -8,7 +8,8 @@
 //   half_kernel      exact 2x decimation, (a + b + c + d + 2) >> 2                      HBM-bound, elementwise
 //   canny_kernel     Sobel + |gx|+|gy| + non-maximum suppression + double threshold      HBM-bound stencil,
 //                    on a 16x16 tile with the 2-pixel halo staged in LDS                 one read of the image
-//   canny_hyst_kernel  hysteresis flood (only launched when low != high; the reference uses 50/50)
+//   canny_hyst_kernel  hysteresis flood, then FastLineDetector's two cleared corners (only launched when low != high; the
+//                    reference uses 50/50, where canny_kernel clears the corners itself)
 //   fld_walk_kernel  8-neighbour chain walking.  The walk consumes edge pixels in raster order and
 //                    every step depends on the previous one: it is the sequential core of the
 //                    detector.  One wave; the edge map lives in LDS (90 KB at 376x240) so a step costs
@@ -133,8 +134,10 @@ __global__ void __launch_bounds__(CN_T *CN_T) canny_kernel(const uint8_t *__rest
     }
     if (keep) out = m > high ? 2 : 0;
   }
-  // FastLineDetector clears the top-left 6x6 and the bottom-right 5x5 corner of the edge map
-  if ((x < 6 && y < 6) || (x >= w - 5 && y >= h - 5)) out = 1;
+  // FastLineDetector clears the top-left 6x6 and the bottom-right 5x5 corner of the edge map — of the FINISHED map: with hysteresis
+  // (low != high, uniform) a strong pixel inside a corner still promotes weak pixels outside it, and canny_hyst_kernel clears the
+  // corners behind its flood
+  if (low == high && ((x < 6 && y < 6) || (x >= w - 5 && y >= h - 5))) out = 1;
   if (inside) map[(size_t)y * w + x] = out;
   if (lab_init) {
     // component labels, first pass: union-find inside the tile, in LDS (W / NW / N / NE neighbours of the same tile); every edge pixel
@@ -310,6 +313,14 @@ __global__ void __launch_bounds__(1024) canny_hyst_kernel(uint8_t *__restrict__ 
     }
     __syncthreads();
   } while (changed);
+  // FastLineDetector's two cleared corners (canny_kernel leaves them to this kernel when it runs): top-left 6x6, bottom-right 5x5
+  if (threadIdx.x < 36) {
+    const int x = threadIdx.x % 6, y = threadIdx.x / 6;
+    if (x < w && y < h) map[(size_t)y * w + x] = 1;
+  } else if (threadIdx.x < 61) {
+    const int q = threadIdx.x - 36, x = w - 5 + q % 5, y = h - 5 + q / 5;
+    if (x >= 0 && y >= 0) map[(size_t)y * w + x] = 1;
+  }
 }
 
 // ------------------------------------------------------------------------------------------ chain walking

@@ -10,72 +10,17 @@ from scipy import ndimage
 
 import oracle_lib
 import synth
+from line_restatement import LEN_THR, edge_map, walk_chains      # the CPU references: the detector's edge map, the chain walk
 
 pytestmark = pytest.mark.gpu
 
-LEN_THR = 20          # FastLineDetector's length_threshold (plv_config default, the oracle's default)
 SEG_TOL = 2e-3        # the contract of the device fit in test_detect_lines_parity (float rounding of the fit's atan2 / cos / sin)
-_F = np.float32
-_NB = ((1, 1), (1, 0), (1, -1), (0, -1), (-1, -1), (-1, 0), (-1, 1), (0, 1))  # {row, col}: getPointChain's neighbour order
 _EIGHT = np.ones((3, 3), dtype=int)
 
 
 @pytest.fixture(scope="module")
 def lo():
     return oracle_lib.load_line()
-
-
-# ------------------------------------------------------------------------------------------------ the CPU references
-def edge_map(lo, eq):
-    """the detector's edge map: Canny of the half-resolution image, FastLineDetector's two cleared corners"""
-    e = lo.canny(lo.resize_half(eq)) != 0
-    e[:6, :6] = False
-    e[-5:, -5:] = False
-    return e
-
-
-def walk_chains(edges, length_threshold=LEN_THR):
-    """lineDetection's seed loop + getPointChain: the kept chains (length_threshold + 1 points or more) in the order of their seeds"""
-    h, w = edges.shape
-    alive = [list(map(bool, row)) for row in edges]
-    chains = []
-    for r in range(h):
-        row = alive[r]
-        for c in range(w):
-            if not row[c]:
-                continue
-            x, y = c, r
-            pts = [(x, y)]
-            row[c] = False
-            direction, step = _F(0), 0
-            while True:
-                best, best_dir, min_diff = None, 0, _F(7)
-                for i, (dr, dc) in enumerate(_NB):
-                    ci, ri = x + dc, y + dr
-                    if ri < 0 or ri == h or ci < 0 or ci == w or not alive[ri][ci]:
-                        continue
-                    curr = _F(i - 8 if i > 4 else i)
-                    if step == 0:
-                        best, direction = (ci, ri), curr
-                        break
-                    diff = abs(curr - direction)          # float32 - float32 -> float32
-                    if diff > _F(4):
-                        diff = _F(8) - diff
-                    if diff <= min_diff:                  # ties: the later neighbour wins
-                        min_diff, best, best_dir = diff, (ci, ri), (i - 8 if i > 4 else i)
-                if best is None:
-                    break
-                if step > 0:
-                    if not min_diff < _F(2):
-                        break
-                    direction = (direction * _F(step) + _F(best_dir)) / _F(step + 1)   # product, sum, quotient: each rounded to float32
-                x, y = best
-                pts.append(best)
-                alive[y][x] = False
-                step += 1
-            if len(pts) >= length_threshold + 1:
-                chains.append(np.array(pts, dtype=np.int32))
-    return chains
 
 
 # ------------------------------------------------------------------------------------------------ the drawings (320 x 240)

@@ -116,11 +116,16 @@ def test_line_tracker_stream_1280x720(pkg, lo):
     _line_tracker_stream(pkg, lo, fr, w, h, num_features=500)
 
 
-def _line_tracker_stream(pkg, lo, frames, W, H, num_features=None):
-    cfg = pkg.default_config(W, H)
+def _line_tracker_stream(pkg, lo, frames, W, H, num_features=None, cfg=None, detect_args=(), prefetch=False):
+    """cfg: the context's configuration when it is not the default one, with detect_args = its line settings as lo.detect_lines takes
+    them (length, dist, c1, c2, min_len); prefetch: the point tracker's feed detects the frame's lines ahead of the line tracker's"""
+    if cfg is None:
+        cfg = pkg.default_config(W, H)
     if num_features:
         cfg.num_features = num_features
     ctx = pkg.Context(cfg)
+    if prefetch:
+        ctx.line_prefetch_mode(True)
     K8 = np.array(list(cfg.intrinsics))
     vps = lo.vanishing_points(np.eye(3), K8)
     fo = oracle_lib.load_front()
@@ -134,7 +139,7 @@ def _line_tracker_stream(pkg, lo, frames, W, H, num_features=None):
         pts, pids = ctx.tracker_last()
         # oracle composition on the same equalised image and the same tracked points
         eq = ctx.pyramid_level(0, 0)
-        lines = lo.detect_lines(eq)
+        lines = lo.detect_lines(eq, *detect_args)
         ids = np.arange(currid + 1, currid + 1 + len(lines), dtype=np.uint64)
         currid += len(lines)
         a = lo.assign_points_to_lines(lines, pts, pids)
