@@ -764,7 +764,7 @@ int stage_line_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_vi
   if (chained) {
     P.chain_dx = us->result.as<double>();  // (dx leads the status block of the update launched last: the point update)
     P.chain_applied = us->applied_word;
-    P.chain_status = (const int *)(us->result.as<char>() + (size_t)ctx->cov_n * 8);
+    P.chain_status = ResultBlock(ctx->cov_n, 0).status((const void *)us->result.p);
     P.chain_q = B.dev(cq), P.chain_id = B.dev(cid);
     memcpy(P.chain_qe, ch.qe, sizeof P.chain_qe);
     P.anc_ptr = B.dev(aptr), P.anc_f = B.dev(af), P.anc_has_old = B.dev(aho), P.anc_old = B.dev(aold);

@@ -9,6 +9,7 @@
 
 #include "plv_ctx.hpp"
 #include "update_kernels.hpp"
+#include "update_route.hpp"
 #include "update_state.hpp"
 
 namespace plv {
@@ -112,7 +113,7 @@ unsigned long long plv_alloc_count(void) { return plv::alloc_epoch().load(); }
 // (measurement aid) line launches that plv_camera_try_update enqueued behind a point update still running (the chained line launch)
 unsigned long long plv_chain_count(void) { return plv::counters().chained.load(); }
 // (measurement aid) updates collected since the library was loaded, by the route they took (plv_update_compression_mode's last_route:
-// 0 no compression, 1 Gram + Cholesky, 2 Householder, 3 Gram then Householder, 4 whitened, 5 whitened rejected, then Householder)
+// update_route.hpp, UpdateRoute)
 void plv_route_counts(unsigned long long *out8) {
   if (!out8) return;
   for (int i = 0; i < 8; ++i) out8[i] = plv::counters().route[i].load();
@@ -422,19 +423,13 @@ int plv_cov_rollback(plv_ctx *ctx) {
 }
 
 // ------------------------------------------------------------------------------ EKF update
-static size_t result_rows_off(int n, int F) { return ((size_t)n * 8 + 16 + (size_t)F + 7) & ~(size_t)7; }
-static int result_buf(plv_ctx *ctx, plv_ctx_update_state *us, int n, int F, double **dx, int **flag, unsigned char **acc,
-                      int **acc_rows = nullptr, int fdim = 3) {
-  size_t bytes = result_rows_off(n, F) + (size_t)F * 4 + 16;
+// the device's result block of a measurement kind, large enough for `lay` (a block that moved starts out zeroed)
+static int result_buf(plv_ctx *ctx, plv_ctx_update_state *us, const ResultBlock &lay, int fdim, char **base) {
   plv::DevBuf &rb = us->result_of(fdim);
   const void *before = rb.p;
-  TRY(rb.reserve(bytes));
+  TRY(rb.reserve(lay.alloc_bytes()));
   if (rb.p != before) PLV_HIP_CHECK(hipMemsetAsync(rb.p, 0, rb.cap, ctx->stream));
-  char *b = rb.as<char>();
-  *dx = (double *)b;
-  *flag = (int *)(b + (size_t)n * 8);
-  *acc = (unsigned char *)(b + (size_t)n * 8 + 16);
-  if (acc_rows) *acc_rows = (int *)(b + result_rows_off(n, F));
+  *base = rb.as<char>();
   return PLV_OK;
 }
 
@@ -509,26 +504,26 @@ int plv_ekf_update(plv_ctx *ctx, double *P, int n, int ldp, const double *H, int
     TRY(h2d(ctx, ctx->d_Rdiag.p, Rdiag, (size_t)r * 8));
     dR = ctx->d_Rdiag.as<double>();
   }
-  double *d_dx;
-  int *d_flag;
-  unsigned char *d_acc;
-  TRY(result_buf(ctx, us, n, 0, &d_dx, &d_flag, &d_acc));
+  const ResultBlock lay(n, 0);
+  char *d_res;
+  TRY(result_buf(ctx, us, lay, 3, &d_res));
+  double *d_dx = lay.dx(d_res);
+  int *d_flag = lay.status(d_res);
   if (ekf_fast_fits(r))
     TRY(launch_ekf_fast(ctx, ctx->d_P.as<double>(), n, n, ctx->d_H.as<double>(), r, k, r, ctx->d_cols.as<int>(),
                         ctx->d_res.as<double>(), dR, d_dx, d_flag));
   else
     TRY(launch_ekf(ctx, ctx->d_P.as<double>(), n, n, ctx->d_H.as<double>(), r, k, r, ctx->d_cols.as<int>(),
                    ctx->d_res.as<double>(), dR, d_dx, d_flag));
-  size_t rb = (size_t)n * 8 + 16;
-  TRY(ctx->h_pin.reserve(rb));
-  TRY(d2h(ctx, ctx->h_pin.p, us->result.p, rb));
+  TRY(ctx->h_pin.reserve(lay.head_bytes()));
+  TRY(d2h(ctx, ctx->h_pin.p, us->result.p, lay.head_bytes()));
   TRY(sync(ctx));
-  int flag = *(int *)(ctx->h_pin.as<char>() + (size_t)n * 8);
+  const int flag = *lay.status((const void *)ctx->h_pin.p);
   if (flag != 0) {
-    set_last_error("EKFUpdate rejected: %s", (flag & 16) ? "speculative batch over the selection cap (run again by the caller)" : (flag & 2) ? "S not positive definite" : "negative covariance diagonal");
+    set_last_error("EKFUpdate rejected: %s", ekf_rejection_text(flag));
     return PLV_E_NOT_PSD;
   }
-  memcpy(dx, ctx->h_pin.p, (size_t)n * 8);
+  memcpy(dx, lay.dx((const void *)ctx->h_pin.p), (size_t)n * 8);
   if (P) {
     TRY(download_mat(ctx, P, ctx->d_P.as<double>(), n, n, ldp));
     TRY(sync(ctx));
@@ -680,42 +675,47 @@ int plv_feat_batch_upload(plv_ctx *ctx, int F, int fdim, int k, int ld, const in
   return sync(ctx);
 }
 
-static bool whitened_route(const plv_ctx_update_state *us, int Mtot, int k);
 }  // extern "C"
-namespace plv {
-// Called by the one-submission updates before they build their batch: fills plv_ctx::gate_stage so that the projected Jacobian
-// launch ends with the gate of every entry (gate_core.hpp) — verdicts, counter, stack — and plv_msckf_update_resident_launch starts
-// behind it.  The buffers are the ones that launch function reserves (same sizes: no reallocation in between).
-int plv_update_gate_prepare(plv_ctx *ctx, int F, int fdim, int k, int ld, double sigma2, double chi2_mult, double res_norm_gate, int probe) {
-  auto *us = ustate(ctx);
-  ctx->gate_stage = plv::GateStage{};
-  ctx->gate_stage_taken = false;
-  const int n = ctx->cov_n, mp_max = ld - fdim;
-  const int rows_most = ctx->gate_rows_hint > 0 ? std::min(ctx->gate_rows_hint, ld) : ld;
-  ctx->gate_rows_hint = 0;
-  if (plv::knob(plv::PLV_KNOB_GATE_SEPARATE) || us->graph_mode || n < 1 || F < 1 || mp_max < 1 || rows_most - fdim > GATE_MMAX || k > GATE_KMAX)
-    return PLV_OK;
-  const int nc = k + 1, Mtot = F * mp_max;
+
+namespace {
+
+// the most rows ekf_fast_fits() takes, as a number for the route plan (the limit itself stays with its kernels: dense_kernels.hip)
+int ekf_fast_rows() {
+  static const int rows = [] {
+    int r = 0;
+    while (r < (1 << 16) && ekf_fast_fits(r + 1)) ++r;
+    return r;
+  }();
+  return rows;
+}
+
+// The buffers that the gate inside a Jacobian launch (plv_update_gate_prepare) and the update launch behind it both address: reserved
+// by one function, so with the same sizes — nothing moves between the two.
+struct UpdateBuffers {
+  ResultBlock lay{0, 0};
+  char *dev = nullptr, *pin = nullptr;  // the result block on the device, and its mirror in pinned memory
+  double *d_dx() const { return lay.dx(dev); }
+  int *d_flag() const { return lay.status(dev); }
+  int *d_acc_rows() const { return lay.acc_rows(dev); }
+};
+int reserve_update_buffers(plv_ctx *ctx, plv_ctx_update_state *us, int n, int F, int fdim, int k, int mp_max, UpdateBuffers *b) {
   TRY(ctx->d_chi2.reserve((size_t)F * 8));
-  TRY(ctx->stack_of(fdim).reserve_units((size_t)F, (size_t)std::max(ctx->cfg.num_features, 64), (size_t)mp_max * nc * 8));
-  double *d_dx;
-  int *d_flag;
-  unsigned char *d_acc;
-  int *d_acc_rows;
-  TRY(result_buf(ctx, us, n, F, &d_dx, &d_flag, &d_acc, &d_acc_rows, fdim));
-  const size_t rb = result_rows_off(n, F) + (size_t)F * 4;
+  TRY(ctx->stack_of(fdim).reserve_units((size_t)F, (size_t)std::max(ctx->cfg.num_features, 64), (size_t)mp_max * (k + 1) * 8));
+  b->lay = ResultBlock(n, F);
+  TRY(result_buf(ctx, us, b->lay, fdim, &b->dev));
   plv::PinBuf &hpin = ctx->res_pin(fdim);
-  TRY(hpin.reserve(rb));
-  plv_ctx_update_state::AccWords &aw = us->acc_of(fdim);
-  aw.word = aw.word == 1 ? 2 : 1;  // the two counters alternate: this update counts in one and zeroes the other for the next
-  // the word must be zero when the launch starts: the gate of the update before in this block zeroed it — unless this is the first
-  // use, the block moved, cov_n changed (the words sit behind dx) or that launch declined the gate (ADVICE r3): then a memset does
-  if (!(aw.z_ptr == us->result_of(fdim).p && aw.z_n == n && aw.z_word == aw.word)) PLV_HIP_CHECK(hipMemsetAsync(d_flag + aw.word, 0, 4, ctx->stream));
-  aw.z_ptr = nullptr;  // (known again once a launch has taken the gate: plv_msckf_update_resident_launch)
-  plv::GateStage &g = ctx->gate_stage;
-  g.on = 1;
+  TRY(hpin.reserve(b->lay.bytes()));
+  b->pin = hpin.as<char>();
+  return PLV_OK;
+}
+
+// The gate's description, for the gate inside a Jacobian launch (GateStage) and for the gate launched on its own (Chi2Args): the two
+// kernel arguments spell these fields alike.  The counter words (n_acc, n_acc_next) and the probe's second block are the caller's.
+template <class G>
+int fill_gate(plv_ctx *ctx, plv_ctx_update_state *us, G &g, const UpdateBuffers &b, int F, int fdim, int mp_max, double sigma2, double chi2_mult,
+              double res_norm_gate, bool stack_accepted_only, bool probe) {
   g.P = ctx->d_P.as<double>();
-  g.ldp = n;
+  g.ldp = b.lay.n;
   g.sigma2 = sigma2, g.chi2_mult = chi2_mult, g.res_norm_gate = res_norm_gate;
   g.q95 = us->q95.as<double>();
   g.q95_n = Q95_N;
@@ -731,26 +731,53 @@ int plv_update_gate_prepare(plv_ctx *ctx, int F, int fdim, int k, int ld, double
     g.dec = ctx->d_gate_dec_l.as<double>();
     ctx->dec_F_l = F;
   }
-  g.accepted = d_acc;
-  g.acc_rows = d_acc_rows;
-  g.n_acc = d_flag + aw.word;
-  g.n_acc_next = d_flag + (3 - aw.word);
+  g.accepted = b.lay.accepted(b.dev);
+  g.acc_rows = b.lay.acc_rows(b.dev);
   g.stack = ctx->stack_of(fdim).as<double>();
-  g.lds = Mtot;
+  g.lds = F * mp_max;
   g.mp_max = mp_max;
-  g.stack_accepted_only = (Mtot > k && k <= 192 && whitened_route(us, Mtot, k)) ? 1 : 0;
-  if (probe) {  // the verdicts also go to pinned memory (the caller adds the second block: probe_src / probe_dst / strides)
-    char *hb = hpin.as<char>();
-    g.h_accepted = (unsigned char *)(hb + (size_t)n * 8 + 16);
-    g.h_acc_rows = (int *)(hb + result_rows_off(n, F));
+  g.stack_accepted_only = stack_accepted_only ? 1 : 0;
+  if (probe) {  // the verdicts also go to pinned memory
+    g.h_accepted = b.lay.accepted(b.pin);
+    g.h_acc_rows = b.lay.acc_rows(b.pin);
   }
   return PLV_OK;
 }
-}  // namespace plv
-extern "C" {
-static bool whitened_route(const plv_ctx_update_state *us, int Mtot, int k) {
-  return Mtot > k && k <= 192 && us->compress_mode == 0 && !us->graph_mode;
+
+}  // namespace
+
+namespace plv {
+// Called by the one-submission updates before they build their batch: fills plv_ctx::gate_stage so that the projected Jacobian
+// launch ends with the gate of every entry (gate_core.hpp) — verdicts, counter, stack — and plv_msckf_update_resident_launch starts
+// behind it.  The buffers are the ones that launch function reserves (reserve_update_buffers: no reallocation in between).
+int plv_update_gate_prepare(plv_ctx *ctx, int F, int fdim, int k, int ld, double sigma2, double chi2_mult, double res_norm_gate, int probe) {
+  auto *us = ustate(ctx);
+  ctx->gate_stage = plv::GateStage{};
+  ctx->gate_stage_taken = false;
+  const int n = ctx->cov_n, mp_max = ld - fdim;
+  const int rows_most = ctx->gate_rows_hint > 0 ? std::min(ctx->gate_rows_hint, ld) : ld;
+  ctx->gate_rows_hint = 0;
+  if (plv::knob(plv::PLV_KNOB_GATE_SEPARATE) || us->graph_mode || n < 1 || F < 1 || mp_max < 1 || rows_most - fdim > GATE_MMAX || k > GATE_KMAX)
+    return PLV_OK;
+  UpdateBuffers b;
+  TRY(reserve_update_buffers(ctx, us, n, F, fdim, k, mp_max, &b));
+  int *d_flag = b.d_flag();
+  plv_ctx_update_state::AccWords &aw = us->acc_of(fdim);
+  aw.word = aw.word == 1 ? 2 : 1;  // the two counters alternate: this update counts in one and zeroes the other for the next
+  // the word must be zero when the launch starts: the gate of the update before in this block zeroed it — unless this is the first
+  // use, the block moved, cov_n changed (the words sit behind dx) or that launch declined the gate (ADVICE r3): then a memset does
+  if (!(aw.z_ptr == b.dev && aw.z_n == n && aw.z_word == aw.word)) PLV_HIP_CHECK(hipMemsetAsync(d_flag + aw.word, 0, 4, ctx->stream));
+  aw.z_ptr = nullptr;  // (known again once a launch has taken the gate: plv_msckf_update_resident_launch)
+  plv::GateStage &g = ctx->gate_stage;
+  g.on = 1;
+  // (with probe the caller adds the second block: probe_src / probe_dst / strides)
+  TRY(fill_gate(ctx, us, g, b, F, fdim, mp_max, sigma2, chi2_mult, res_norm_gate, whitened_route(us->compress_mode, us->graph_mode, F * mp_max, k), probe != 0));
+  g.n_acc = d_flag + aw.word;
+  g.n_acc_next = d_flag + (3 - aw.word);
+  return PLV_OK;
 }
+}  // namespace plv
+
 // Side stream: behind everything the main stream held when prior_mark() was called (the previous update's commit, the upload that
 // carries d_cols), factor the prior block and form W0^T W0; aux_join is recorded behind them.  Two steps so that a caller can mark,
 // enqueue its own next launch on the main stream first (the host's enqueue time of the side work then overlaps that launch's run
@@ -777,7 +804,7 @@ static int prior_start(plv_ctx *ctx, const int *d_cols, int k) {
   PLV_HIP_CHECK(hipEventRecord(ctx->aux_join, ctx->aux_stream));
   return PLV_OK;
 }
-}  // extern "C"
+
 namespace plv {
 // Called by the one-submission updates (jacobian_api.hip) with the update's shape: phase 0 before anything of the update is on the main
 // stream (its upload included), phase 1 right after the Jacobian launch with the column map in memory the device can read NOW (the
@@ -785,7 +812,7 @@ namespace plv {
 // Jacobians and gate.
 int plv_prior_prefetch(plv_ctx *ctx, int phase, const int *d_cols, int k, int F, int mp_max) {
   auto *us = ustate(ctx);
-  if (plv::knob(plv::PLV_KNOB_PRIOR_LATE) || !whitened_route(us, F * mp_max, k) || ctx->cov_n < 1) return PLV_OK;
+  if (plv::knob(plv::PLV_KNOB_PRIOR_LATE) || !whitened_route(us->compress_mode, us->graph_mode, F * mp_max, k) || ctx->cov_n < 1) return PLV_OK;
   if (phase == 0) return prior_mark(ctx);
   TRY(prior_start(ctx, d_cols, k));
   ctx->prior_pending = true;
@@ -793,251 +820,247 @@ int plv_prior_prefetch(plv_ctx *ctx, int phase, const int *d_cols, int k, int F,
   return PLV_OK;
 }
 }  // namespace plv
-extern "C" {
 
-int plv_msckf_update_resident_launch(plv_ctx *ctx, double sigma2, double chi2_mult, double res_norm_gate) {
-  REQUIRE_CTX(ctx);
-  auto *us = ustate(ctx);
-  const int F_guard = us->bF;
-  us->pending_F = 0;
-  ctx->probe_done = false;  // (a launch that failed after setting it, or a wait that was skipped, must not short-cut this update's wait)
-  if (F_guard < 1 || ctx->cov_n < 1) {
-    set_last_error("plv_msckf_update_resident: no staged batch / covariance");
-    return PLV_E_BADARG;
-  }
-  const int F = us->bF, fdim = us->bfdim, k = us->bk, ld = us->bld, n = ctx->cov_n;
-  size_t nHf = (size_t)F * fdim * ld, nHx = (size_t)F * k * ld, nr = (size_t)F * ld;
-  TRY(ctx->d_chi2.reserve((size_t)F * 8));
-  double *wHf;
-  if (us->b_single_use) {
-    // the batch was just built on the device (plv_build_jacobians_resident): consume it in place
-    wHf = us->bHf.as<double>();
-    us->b_single_use = false;
-    us->bF = 0;
-  } else {
-    // working copy (the nullspace projection is in place): one D2D
-    TRY(us->bwork.reserve((nHf + nHx + nr) * 8));
-    PLV_HIP_CHECK(plv::memcpy_async(us->bwork.p, us->bHf.p, (nHf + nHx + nr) * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    wHf = us->bwork.as<double>();
-  }
-  double *wHx = wHf + nHf, *wres = wHx + nHx;
+namespace {
 
-  const int mp_max = (us->b_on_device_rows ? ld : us->bmaxrows) - fdim;
-  if (mp_max < 1) {
-    set_last_error("plv_msckf_update: no feature has more than fdim rows");
-    return PLV_E_BADARG;
-  }
-  const int nc = k + 1;
-  const int Mtot = F * mp_max;
-  TRY(ctx->stack_of(fdim).reserve_units((size_t)F, (size_t)std::max(ctx->cfg.num_features, 64), (size_t)mp_max * nc * 8));
-  size_t tmp_elems = (size_t)std::max(Mtot / (2 * nc) + 2, 16) * nc * nc;  // TSQR tree levels
-  {  // Gram path: per-chunk partial tiles (64-row chunks, upper 16x16 tiles) + the reduced matrix
-    const size_t nt = (size_t)(nc + 15) / 16, ntri = nt * (nt + 1) / 2;
-    tmp_elems = std::max(tmp_elems, (size_t)((Mtot + 63) / 64) * ntri * 256 + (size_t)nc * nc);
-  }
-  TRY(ctx->d_stack2.reserve(tmp_elems * 8));
+// The launch of one camera update on the staged batch (points or lines, speculative or not, behind a fused gate or with its own): what
+// its stages share.  The route is decided by update_route.hpp from `shape`; the stages below only carry it out.
+struct UpdateLaunch {
+  plv_ctx *ctx;
+  plv_ctx_update_state *us;
+  const double sigma2, chi2_mult, res_norm_gate;
+  UpdateShape shape;
+  UpdatePlan plan;
+  int n = 0;
+  double *wHf = nullptr, *wHx = nullptr, *wres = nullptr;  // the batch this update consumes
+  UpdateBuffers buf;
+  bool aux_open = false;  // side-stream work that reads the covariance and that the main stream has not joined yet
 
-  double *d_dx;
-  int *d_flag;
-  unsigned char *d_acc;
-  int *d_acc_rows;
-  TRY(result_buf(ctx, us, n, F, &d_dx, &d_flag, &d_acc, &d_acc_rows, fdim));
-  plv::DevBuf &resbuf = us->result_of(fdim);
+  ~UpdateLaunch() { ctx->skip_word = nullptr; }  // the word is only meaningful for the kernels of this update
 
-  // a batch from plv_build_jacobians_resident arrives projected, with the covariance gathers done on its launch: they stand as
-  // long as nothing has touched the covariance or the gathered blocks since (plv_ctx::gather_stamp)
-  const bool projected = us->b_projected;
-  const bool gathers_valid = projected && us->b_gather_token != 0 && us->b_gather_token == ctx->gather_stamp;
-  us->b_gather_token = 0;
-  // (the prefetched prior factor stands exactly as long as the gathers that rode on the same launch do)
-  const bool prior_was_pending = ctx->prior_pending;
-  const bool prefetched = prior_was_pending && ctx->prior_k == k && gathers_valid;
-  ctx->prior_pending = false;
-  const size_t rb = result_rows_off(n, F) + (size_t)F * 4;
-  plv::PinBuf &hpin = ctx->res_pin(fdim);
-  TRY(hpin.reserve(rb));
-  struct SkipGuard {  // the words are only meaningful for the kernels of this update
-    plv_ctx *c;
-    ~SkipGuard() { c->skip_word = nullptr; }
-  } skip_guard{ctx};
-  // Whitened route (mode 0, DESIGN.md "Whitened update").  Its prior factor only needs the covariance: the one-submission updates
-  // start it on the side stream before their Jacobian launch (plv_prior_prefetch); otherwise it starts here.
-  const bool whiten = whitened_route(us, Mtot, k);
-  bool aux_open = prior_was_pending;  // (a prefetch that is not taken after all is still joined: the main stream rewrites the covariance)
-  auto aux_join = [&]() -> int {  // the main stream goes on only when the side work is done (it reads the covariance)
+  double *P() const { return ctx->d_P.as<double>(); }
+  int *cols() const { return us->bcols_of(shape.fdim).as<int>(); }
+  double *stack() const { return ctx->stack_of(shape.fdim).as<double>(); }
+
+  int take_batch() {
+    UpdateShape &s = shape;
+    s.F = us->bF, s.fdim = us->bfdim, s.k = us->bk, s.ld = us->bld;
+    n = ctx->cov_n;
+    const size_t nHf = (size_t)s.F * s.fdim * s.ld, nHx = (size_t)s.F * s.k * s.ld, nr = (size_t)s.F * s.ld;
+    if (us->b_single_use) {
+      // the batch was just built on the device (plv_build_jacobians_resident): consume it in place
+      wHf = us->bHf.as<double>();
+      us->b_single_use = false;
+      us->bF = 0;
+    } else {
+      // working copy (the nullspace projection is in place): one D2D
+      TRY(us->bwork.reserve((nHf + nHx + nr) * 8));
+      PLV_HIP_CHECK(plv::memcpy_async(us->bwork.p, us->bHf.p, (nHf + nHx + nr) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+      wHf = us->bwork.as<double>();
+    }
+    wHx = wHf + nHf, wres = wHx + nHx;
+    s.mp_max = (us->b_on_device_rows ? s.ld : us->bmaxrows) - s.fdim;
+    if (s.mp_max < 1) {
+      set_last_error("plv_msckf_update: no feature has more than fdim rows");
+      return PLV_E_BADARG;
+    }
+    s.compress_mode = us->compress_mode, s.graph_mode = us->graph_mode;
+    // a batch from plv_build_jacobians_resident arrives projected, with the covariance gathers done on its launch: they stand as
+    // long as nothing has touched the covariance or the gathered blocks since (plv_ctx::gather_stamp)
+    s.projected = us->b_projected;
+    s.gathers_valid = s.projected && us->b_gather_token != 0 && us->b_gather_token == ctx->gather_stamp;
+    // (the prefetched prior factor stands exactly as long as the gathers that rode on the same launch do)
+    s.prefetched = ctx->prior_pending && ctx->prior_k == s.k && s.gathers_valid;
+    s.probing = ctx->probe;
+    s.force_factor_form = plv::knob(plv::PLV_KNOB_FORCE_FACTOR_FORM), s.tsqr_tree = plv::knob(plv::PLV_KNOB_TSQR_TREE);
+    s.ekf_fast_rows = ekf_fast_rows();
+    plan = plan_update(s);
+    return PLV_OK;
+  }
+
+  int reserve() {
+    TRY(reserve_update_buffers(ctx, us, n, shape.F, shape.fdim, shape.k, shape.mp_max, &buf));
+    TRY(ctx->d_stack2.reserve(plan.tmp_elems * 8));
+    us->b_gather_token = 0;
+    aux_open = ctx->prior_pending;  // (a prefetch that is not taken after all is still joined: the main stream rewrites the covariance)
+    ctx->prior_pending = false;
+    return PLV_OK;
+  }
+
+  // Whitened route: its prior factor only needs the covariance.  The one-submission updates start it on the side stream before their
+  // Jacobian launch (plv_prior_prefetch); otherwise it starts here.
+  int start_prior() {
+    TRY(join_prior());
+    TRY(prior_mark(ctx, true));  // (us->bcols is written by the Jacobian launch queued on the main stream)
+    TRY(prior_start(ctx, cols(), shape.k));
+    aux_open = true;
+    return PLV_OK;
+  }
+  int join_prior() {  // the main stream goes on only when the side work is done (it reads the covariance)
     if (!aux_open) return PLV_OK;
     aux_open = false;
     PLV_HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->aux_join, 0));
     return PLV_OK;
-  };
-  const bool probing = ctx->probe && !us->graph_mode;
-  auto start_prior = [&]() -> int {
-    TRY(aux_join());
-    TRY(prior_mark(ctx, true));  // (us->bcols is written by the Jacobian launch queued on the main stream)
-    TRY(prior_start(ctx, us->bcols_of(fdim).as<int>(), k));
-    aux_open = true;
-    return PLV_OK;
-  };
-  auto enqueue = [&]() -> int {
-  // (a probed update starts the factor once it knows that it takes the whitened route: few accepted rows go another way)
-  if (whiten && !prefetched && !probing) TRY(start_prior());
-  if (!projected) {
-    // (+ the covariance gathers the gate and the EKF step read: independent of the projection, same launch)
-    TRY(launch_nullspace(ctx, F, fdim, k, ld, us->brows.as<int>(), wHf, wHx, wres, ctx->d_P.as<double>(), n, n, us->bcols_of(fdim).as<int>()));
-  } else if (!gathers_valid) {
-    TRY(launch_gather_cov(ctx, ctx->d_P.as<double>(), n, n, us->bcols_of(fdim).as<int>(), k));
-  }
-  Chi2Args a{};
-  a.P = ctx->d_P.as<double>();
-  a.ldp = n;
-  a.k = k;
-  a.ld = ld;
-  a.fdim_off = fdim;
-  a.rows = us->brows.as<int>();
-  a.Hx = wHx;
-  a.res = wres;
-  a.cols = us->bcols_of(fdim).as<int>();
-  a.sigma2 = sigma2;
-  a.chi2 = ctx->d_chi2.as<double>();
-  a.dec = nullptr;
-  if (ctx->decision_trace && fdim == 3) {
-    TRY(ctx->d_gate_dec.reserve((size_t)F * 24));
-    a.dec = ctx->d_gate_dec.as<double>();
-    ctx->dec_gate = true;
-  } else if (ctx->decision_trace) {
-    TRY(ctx->d_gate_dec_l.reserve((size_t)F * 24));
-    a.dec = ctx->d_gate_dec_l.as<double>();
-    ctx->dec_F_l = F;
-  }
-  a.stack = ctx->stack_of(fdim).as<double>();
-  a.lds = Mtot;
-  a.mp_max = mp_max;
-  a.chi2_mult = chi2_mult;
-  a.res_norm_gate = res_norm_gate;
-  a.q95 = us->q95.as<double>();
-  a.q95_n = Q95_N;
-  a.min_rows = fdim == 3 ? 4 : 5;  // REF: UpdaterCamera.cpp:228 / :406
-  a.accepted = d_acc;
-  a.acc_rows = d_acc_rows;
-  a.n_acc = d_flag + 1;           // second word of the status block
-  // with more rows than columns the stack goes to gram_direct_kernel, which walks the accepted entries only (not in the modes that may
-  // hand the whole stack to the Householder route, nor beyond its 192-column capacity)
-  a.stack_accepted_only = (Mtot > k && k <= 192 && whiten) ? 1 : 0;
-  // read by every kernel enqueued from here on (cleared after enqueue()); only the blocked-Cholesky route honours it in all of
-  // its kernels, so the Householder / LDS-resident fallbacks (more than 192 columns) run unconditionally
-  ctx->skip_word = (Mtot > k ? k <= 192 : ekf_fast_fits(Mtot)) ? d_flag + 1 : nullptr;
-  const bool probe = ctx->probe && !us->graph_mode;
-  if (probe) {
-    char *hb = hpin.as<char>();
-    a.h_accepted = (unsigned char *)(hb + (size_t)n * 8 + 16);
-    a.h_acc_rows = (int *)(hb + result_rows_off(n, F));
-    a.probe_src = (const unsigned char *)ctx->probe_src;
-    a.probe_dst = (unsigned char *)ctx->probe_dst;
-    a.probe_stride_a = ctx->probe_stride_a, a.probe_off_b = ctx->probe_off_b, a.probe_stride_b = ctx->probe_stride_b;
-  }
-  // the gate already ran as the tail of the Jacobian launch (plv_update_gate_prepare): same buffers, its own counter word
-  const bool gated = ctx->gate_stage_taken && projected && ctx->gate_stage.stack == a.stack && ctx->gate_stage.lds == a.lds &&
-                     ctx->gate_stage.accepted == a.accepted && ctx->gate_stage.stack_accepted_only == a.stack_accepted_only;
-  if (ctx->gate_stage_taken && !gated) {  // (the launch that took the gate did not write the projected blocks a separate gate would read)
-    set_last_error("plv_msckf_update_resident: the batch was gated inside its Jacobian launch for other buffers than this update's");
-    return PLV_E_BADARG;
-  }
-  if (gated) {
-    ctx->skip_word = ctx->skip_word ? ctx->gate_stage.n_acc : nullptr;
-    plv_ctx_update_state::AccWords &aw = us->acc_of(fdim);
-    us->acc_word_used = aw.word;
-    aw.z_ptr = resbuf.p, aw.z_n = n, aw.z_word = 3 - aw.word;  // (workgroup 0 of the gated launch zeroed the other counter)
-  } else {
-    us->acc_word_used = 1;
-    TRY(launch_chi2(ctx, F, a, mp_max));
-  }
-  us->last_route = 0;  // (before the probe's early return: a line update that ends at the gate must not report the point update's route)
-  us->redo_w.armed = false;
-  if (probe) {
-    // the gate's verdicts are in pinned memory when its launch has finished: most line updates end here (three frames in four at
-    // BASELINE configs[2] accept no line), without the six launches that would find nothing to do
-    if (ctx->probe_hook) ctx->probe_hook(ctx->probe_hook_arg);
-    TRY(sync(ctx));
-    const unsigned char *hacc = (const unsigned char *)(hpin.as<char>() + (size_t)n * 8 + 16);
-    int any = 0;
-    for (int f = 0; f < F; ++f) any |= hacc[f];
-    if (!any) {
-      memset(hpin.p, 0, (size_t)n * 8 + 16);  // dx = 0, status = updated-with-nothing (as the skipped chain reports it)
-      ctx->probe_done = true;
-      return aux_join();
-    }
-    // (round 6) The host holds the gate's verdicts here.  With no more accepted rows than columns the reference does not compress at
-    // all (measurement_compress_inplace returns at once when H has no more rows than columns, StateHelper.cpp:604-606) and EKFUpdate
-    // factors S = H P H^T + R of the accepted rows' size — a line update accepts one or two lines, ~20 rows, where the whitened form
-    // factors a k x k matrix (k ~ 100: 34 us of blocked Cholesky against 6) behind an information matrix it has to form first.
-    // The accepted rows are gathered into a dense block and go through EKFUpdate as they are.
-    const int *hrows = (const int *)(hpin.as<char>() + result_rows_off(n, F));
-    int m_acc = 0;
-    for (int f = 0; f < F; ++f) m_acc += std::max(hrows[f], 0);
-    if (whiten && m_acc > 0 && m_acc <= k && ekf_fast_fits(m_acc) && !plv::knob(plv::PLV_KNOB_FORCE_FACTOR_FORM)) {
-      TRY(ctx->d_stackc.reserve((size_t)m_acc * nc * 8));
-      TRY(launch_stack_compact(ctx, ctx->stack_of(fdim).as<double>(), Mtot, nc, d_acc_rows, F, mp_max, ctx->d_stackc.as<double>(), m_acc, true));
-      TRY(aux_join());  // (a prior factor started ahead of time is not used, but it reads the covariance this update rewrites)
-      const double *Hc = ctx->d_stackc.as<double>();
-      TRY(launch_ekf_fast(ctx, ctx->d_P.as<double>(), n, n, Hc, m_acc, k, m_acc, us->bcols_of(fdim).as<int>(), Hc + (size_t)k * m_acc, nullptr, d_dx, d_flag,
-                          gathers_valid, resbuf.p, hpin.p, (rb + 3) & ~(size_t)3));
-      us->last_route = 0;
-      return PLV_OK;
-    }
-    if (whiten && !prefetched) TRY(start_prior());
   }
 
-  const double *dH, *dr;
-  int r, ldh;
-  if (whiten) {
-    // REF: measurement_compress_inplace + EKFUpdate as one whitened step: no triangular factor of the measurements is formed
-    TRY(launch_gram_information(ctx, ctx->stack_of(fdim).as<double>(), Mtot, nc, d_acc_rows, F, mp_max));
-    TRY(aux_join());
-    TRY(launch_ekf_whitened(ctx, ctx->d_P.as<double>(), n, n, k, us->bcols_of(fdim).as<int>(), d_dx, d_flag, resbuf.p, hpin.p, (rb + 3) & ~(size_t)3));
-    us->last_route = 4;
-    us->redo_w = plv_ctx_update_state::RedoW{!us->graph_mode, Mtot, k, n, F, mp_max, fdim, tmp_elems, rb, d_dx, d_flag, d_acc_rows};
+  int project_or_gather() {
+    const UpdateShape &s = shape;
+    if (plan.project == PROJECT_NULLSPACE_AND_GATHERS)
+      // (+ the covariance gathers the gate and the EKF step read: independent of the projection, same launch)
+      return launch_nullspace(ctx, s.F, s.fdim, s.k, s.ld, us->brows.as<int>(), wHf, wHx, wres, P(), n, n, cols());
+    if (plan.project == PROJECT_GATHERS_ONLY) return launch_gather_cov(ctx, P(), n, n, cols(), s.k);
     return PLV_OK;
   }
-  if (Mtot > k) {
-    // REF: measurement_compress_inplace — [R z] by Householder reflections on the stacked rows (TSQR): mode 1, and whatever the
-    // whitened update does not take (more than 192 columns, graph mode)
-    double *R;
-    int ldr;
-    if (projected && d_acc_rows && !plv::knob(plv::PLV_KNOB_TSQR_TREE)) {
+
+  // The gate already ran as the tail of the Jacobian launch (plv_update_gate_prepare: same buffers, its own counter word), or runs here
+  int gate() {
+    const UpdateShape &s = shape;
+    int *d_flag = buf.d_flag();
+    Chi2Args a{};
+    a.k = s.k;
+    a.ld = s.ld;
+    a.fdim_off = s.fdim;
+    a.rows = us->brows.as<int>();
+    a.Hx = wHx;
+    a.res = wres;
+    a.cols = cols();
+    TRY(fill_gate(ctx, us, a, buf, s.F, s.fdim, s.mp_max, sigma2, chi2_mult, res_norm_gate, plan.stack_accepted_only, plan.probing));
+    a.n_acc = d_flag + 1;  // second word of the status block
+    // read by every kernel enqueued from here on (cleared when the launch ends)
+    ctx->skip_word = plan.skip_word ? d_flag + 1 : nullptr;
+    if (plan.probing) {
+      a.probe_src = (const unsigned char *)ctx->probe_src;
+      a.probe_dst = (unsigned char *)ctx->probe_dst;
+      a.probe_stride_a = ctx->probe_stride_a, a.probe_off_b = ctx->probe_off_b, a.probe_stride_b = ctx->probe_stride_b;
+    }
+    const plv::GateStage &g = ctx->gate_stage;
+    const bool gated = ctx->gate_stage_taken && s.projected && g.stack == a.stack && g.lds == a.lds && g.accepted == a.accepted &&
+                       g.stack_accepted_only == a.stack_accepted_only;
+    if (ctx->gate_stage_taken && !gated) {  // (the launch that took the gate did not write the projected blocks a separate gate would read)
+      set_last_error("plv_msckf_update_resident: the batch was gated inside its Jacobian launch for other buffers than this update's");
+      return PLV_E_BADARG;
+    }
+    if (gated) {
+      ctx->skip_word = ctx->skip_word ? g.n_acc : nullptr;
+      plv_ctx_update_state::AccWords &aw = us->acc_of(s.fdim);
+      us->acc_word_used = aw.word;
+      aw.z_ptr = buf.dev, aw.z_n = n, aw.z_word = 3 - aw.word;  // (workgroup 0 of the gated launch zeroed the other counter)
+      return PLV_OK;
+    }
+    us->acc_word_used = 1;
+    return launch_chi2(ctx, s.F, a, s.mp_max);
+  }
+
+  // The gate's verdicts are in pinned memory when its launch has finished: most line updates end here (three frames in four at
+  // BASELINE configs[2] accept no line), without the six launches that would find nothing to do.  *done: the update needs no chain.
+  int probe(bool *done) {
+    const UpdateShape &s = shape;
+    *done = true;
+    if (ctx->probe_hook) ctx->probe_hook(ctx->probe_hook_arg);
+    TRY(sync(ctx));
+    const unsigned char *hacc = buf.lay.accepted((const void *)buf.pin);
+    const int *hrows = buf.lay.acc_rows((const void *)buf.pin);
+    int any = 0, m_acc = 0;
+    for (int f = 0; f < s.F; ++f) any |= hacc[f];
+    if (any)
+      for (int f = 0; f < s.F; ++f) m_acc += std::max(hrows[f], 0);
+    const TailPlan t = plan_tail(plan, any != 0, m_acc);
+    if (t.kind == TAIL_ENDED_AT_GATE) {
+      memset(buf.pin, 0, buf.lay.head_bytes());  // dx = 0, status = updated-with-nothing (as the skipped chain reports it)
+      ctx->probe_done = true;
+      return join_prior();
+    }
+    if (t.kind == TAIL_DIRECT) {
+      // (round 6) With no more accepted rows than columns the reference does not compress at all (measurement_compress_inplace returns
+      // at once when H has no more rows than columns, StateHelper.cpp:604-606) and EKFUpdate factors S = H P H^T + R of the accepted
+      // rows' size — a line update accepts one or two lines, ~20 rows, where the whitened form factors a k x k matrix (k ~ 100: 34 us
+      // of blocked Cholesky against 6) behind an information matrix it has to form first.  The accepted rows are gathered into a dense
+      // block and go through EKFUpdate as they are.
+      TRY(ctx->d_stackc.reserve((size_t)m_acc * s.nc() * 8));
+      TRY(launch_stack_compact(ctx, stack(), s.Mtot(), s.nc(), buf.d_acc_rows(), s.F, s.mp_max, ctx->d_stackc.as<double>(), m_acc, true));
+      TRY(join_prior());  // (a prior factor started ahead of time is not used, but it reads the covariance this update rewrites)
+      const double *Hc = ctx->d_stackc.as<double>();
+      TRY(launch_ekf_fast(ctx, P(), n, n, Hc, m_acc, s.k, m_acc, cols(), Hc + (size_t)s.k * m_acc, nullptr, buf.d_dx(), buf.d_flag(), s.gathers_valid, buf.dev,
+                          buf.pin, buf.lay.mirror_bytes()));
+      us->last_route = ROUTE_DIRECT;
+      return PLV_OK;
+    }
+    if (t.start_prior_now) TRY(start_prior());
+    *done = false;
+    return PLV_OK;
+  }
+
+  // REF: measurement_compress_inplace + EKFUpdate as one whitened step: no triangular factor of the measurements is formed
+  int tail_whitened(const ChainPlan &c) {
+    const UpdateShape &s = shape;
+    TRY(launch_gram_information(ctx, stack(), s.Mtot(), s.nc(), buf.d_acc_rows(), s.F, s.mp_max));
+    TRY(join_prior());
+    TRY(launch_ekf_whitened(ctx, P(), n, n, s.k, cols(), buf.d_dx(), buf.d_flag(), buf.dev, buf.pin, buf.lay.mirror_bytes()));
+    us->last_route = c.route;
+    us->redo_w = plv_ctx_update_state::RedoW{true, s.Mtot(), s.k, n, s.F, s.mp_max, s.fdim, plan.tmp_elems, buf.lay.bytes(), buf.d_dx(), buf.d_flag(), buf.d_acc_rows()};
+    return PLV_OK;
+  }
+
+  // REF: measurement_compress_inplace — [R z] by Householder reflections on the stacked rows (TSQR): mode 1, and whatever the
+  // whitened update does not take (more than 192 columns, graph mode)
+  int tail_householder(const ChainPlan &c, double **R, int *ldr) {
+    const UpdateShape &s = shape;
+    const int Mtot = s.Mtot(), nc = s.nc();
+    if (c.tail == CHAIN_HOUSEHOLDER_GATHERED) {
       // (round 6b) the stack is F slots of mp_max rows, the accepted rows a fraction of them and the rest zeros: gathered first (the
       // count stays on the device: hqr_kernel reads it), 2.3 ms of six tree levels over 2100 rows became ~0.8 at workload C
       TRY(ctx->d_stackc.reserve((size_t)Mtot * nc * 8));
       TRY(ctx->d_count_words.reserve(64));
       int *m_dev = ctx->d_count_words.as<int>();
-      TRY(launch_stack_compact(ctx, ctx->stack_of(fdim).as<double>(), Mtot, nc, d_acc_rows, F, mp_max, ctx->d_stackc.as<double>(), Mtot, false, m_dev));
-      TRY(launch_tsqr(ctx, ctx->d_stackc.as<double>(), Mtot, Mtot, nc, ctx->d_stack2.as<double>(), tmp_elems, &R, &ldr, m_dev));
+      TRY(launch_stack_compact(ctx, stack(), Mtot, nc, buf.d_acc_rows(), s.F, s.mp_max, ctx->d_stackc.as<double>(), Mtot, false, m_dev));
+      TRY(launch_tsqr(ctx, ctx->d_stackc.as<double>(), Mtot, Mtot, nc, ctx->d_stack2.as<double>(), plan.tmp_elems, R, ldr, m_dev));
     } else {
-      TRY(launch_tsqr(ctx, ctx->stack_of(fdim).as<double>(), Mtot, Mtot, nc, ctx->d_stack2.as<double>(), tmp_elems, &R, &ldr));
+      TRY(launch_tsqr(ctx, stack(), Mtot, Mtot, nc, ctx->d_stack2.as<double>(), plan.tmp_elems, R, ldr));
     }
-    dH = R;
-    dr = R + (size_t)k * ldr;
-    r = k;
-    ldh = ldr;
-    us->last_route = 2;
-  } else {
-    dH = ctx->stack_of(fdim).as<double>();
-    dr = dH + (size_t)k * Mtot;
-    r = Mtot;
-    ldh = Mtot;
-  }
-  if (ekf_fast_fits(r)) {  // (its last kernel mirrors the result block into h_pin: no copy command after the chain)
-    TRY(launch_ekf_fast(ctx, ctx->d_P.as<double>(), n, n, dH, r, k, ldh, us->bcols_of(fdim).as<int>(), dr, nullptr, d_dx, d_flag, true,
-                        resbuf.p, hpin.p, (rb + 3) & ~(size_t)3));
+    us->last_route = c.route;
     return PLV_OK;
   }
-  TRY(launch_ekf(ctx, ctx->d_P.as<double>(), n, n, dH, r, k, ldh, us->bcols_of(fdim).as<int>(), dr, nullptr, d_dx, d_flag, true));
-  TRY(d2h(ctx, hpin.p, resbuf.p, rb));
-    return PLV_OK;
-  };
-  if (us->graph_mode && !ctx->prof.on) {
-    // (the skip word is chosen inside enqueue() from Mtot, k and d_flag: all functions of the key's own fields and of `result`)
-    plv_ctx_update_state::GraphKey key{ctx->d_P.p, wHf, us->brows.p, us->bcols_of(fdim).p, resbuf.p, hpin.p, ctx->mirror2_src, ctx->mirror2_dst,
-                                       (const void *)(d_flag + 1), ctx->mirror2_bytes, F, fdim + 16 * (projected ? 1 : 0) + 32 * (gathers_valid ? 1 : 0), k, ld, n, mp_max,
+
+  // EKFUpdate on c.r rows [H | res] (col-major, ldh)
+  int ekf_step(const ChainPlan &c, const double *dH, const double *dr, int ldh) {
+    if (c.ekf == EKF_FAST)  // (its last kernel mirrors the result block into pinned memory: no copy command after the chain)
+      return launch_ekf_fast(ctx, P(), n, n, dH, c.r, shape.k, ldh, cols(), dr, nullptr, buf.d_dx(), buf.d_flag(), true, buf.dev, buf.pin, buf.lay.mirror_bytes());
+    TRY(launch_ekf(ctx, P(), n, n, dH, c.r, shape.k, ldh, cols(), dr, nullptr, buf.d_dx(), buf.d_flag(), true));
+    return d2h(ctx, buf.pin, buf.dev, buf.lay.bytes());
+  }
+
+  int enqueue() {
+    if (plan.prior_before_gate) TRY(start_prior());
+    TRY(project_or_gather());
+    TRY(gate());
+    us->last_route = ROUTE_DIRECT;  // (before the probe's early return: a line update that ends at the gate must not report the point update's route)
+    us->redo_w.armed = false;
+    if (plan.probing) {
+      bool done;
+      TRY(probe(&done));
+      if (done) return PLV_OK;
+    }
+    const ChainPlan c = plan_chain(plan);
+    if (c.tail == CHAIN_WHITENED) return tail_whitened(c);
+    if (c.tail == CHAIN_STACK_AS_IS) return ekf_step(c, stack(), stack() + (size_t)shape.k * shape.Mtot(), shape.Mtot());
+    double *R;
+    int ldr;
+    TRY(tail_householder(c, &R, &ldr));
+    return ekf_step(c, R, R + (size_t)shape.k * ldr, ldr);
+  }
+
+  // Eagerly, or — plv_update_graph_mode — through a hipGraph of the same sequence: the first sight of a key runs eagerly (sizes every
+  // buffer), the second captures, later ones replay
+  int run_or_replay() {
+    if (!us->graph_mode || ctx->prof.on) {
+      const int erc = enqueue();
+      const int jrc = join_prior();  // (also on an error path: what follows on the main stream may rewrite the covariance)
+      return erc ? erc : jrc;
+    }
+    const UpdateShape &s = shape;
+    // (the skip word is chosen by the plan from Mtot, k and the status block: all functions of the key's own fields and of `result`)
+    plv_ctx_update_state::GraphKey key{ctx->d_P.p, wHf, us->brows.p, us->bcols_of(s.fdim).p, buf.dev, buf.pin, ctx->mirror2_src, ctx->mirror2_dst,
+                                       (const void *)(buf.d_flag() + 1), ctx->mirror2_bytes, s.F, s.fdim + 16 * (s.projected ? 1 : 0) + 32 * (s.gathers_valid ? 1 : 0), s.k, s.ld, n, s.mp_max,
                                        sigma2, chi2_mult, res_norm_gate, plv::alloc_epoch().load()};
     if (us->gexec && key == us->gkey) {
       PLV_HIP_CHECK(hipGraphLaunch(us->gexec, ctx->stream));
@@ -1075,16 +1098,61 @@ int plv_msckf_update_resident_launch(plv_ctx *ctx, double sigma2, double chi2_mu
       us->gkey_seen.epoch = plv::alloc_epoch().load();  // the eager run may have grown buffers
       us->gseen = true;
     }
-  } else {
-    const int erc = enqueue();
-    const int jrc = aux_join();  // (also on an error path: what follows on the main stream may rewrite the covariance)
-    if (erc) return erc;
-    if (jrc) return jrc;
+    return PLV_OK;
   }
+};
+
+// The whitened update came back rejected (update_state.hpp, RedoW): nothing was committed.  The stacked rows are run again the
+// reference's way — compression, then S = R P R^T + I — with the compression by Householder reflections on the rows themselves
+// (on the KAIST-layout drive with stamps of 1.5e9 s, where this happens to the first update after the initialisation, the Gram +
+// Cholesky compression ended 5.6 cm from this one; and the updates the factor form hands over on the bench drive — the car at rest,
+// a prior block of rank 50 of 110, lambda above 1e4 — all have 5 .. 70 pivots the Gram + Cholesky compression cannot tell from zero,
+// so trying that compression first would only add its 0.1 ms to the 2 ms of this one).  Its verdict is the update's.
+int redo_by_householder(plv_ctx *ctx, plv_ctx_update_state *us, int fdim, void *hpin, const int *hrows) {
+  const plv_ctx_update_state::RedoW rd = us->redo_w;
+  us->redo_w.armed = false;
+  const int nc = rd.k + 1;
+  ctx->skip_word = nullptr;
+  double *R;
+  int ldr;
+  // (the accepted rows gathered into a dense matrix first: the stack is F x mp_max slots, most of them empty, and the tree of
+  // Householder reductions costs 0.4 ms per level of 224 rows)
+  int m_acc = 0;
+  for (int f = 0; f < rd.F; ++f) m_acc += std::max(hrows[f], 0);
+  const int m_c = std::max(m_acc, 2 * nc);
+  TRY(ctx->d_stackc.reserve((size_t)m_c * nc * 8));
+  TRY(launch_stack_compact(ctx, ctx->stack_of(fdim).as<double>(), rd.Mtot, nc, rd.d_acc_rows, rd.F, rd.mp_max, ctx->d_stackc.as<double>(), m_c));
+  TRY(launch_tsqr(ctx, ctx->d_stackc.as<double>(), m_c, m_c, nc, ctx->d_stack2.as<double>(), rd.tmp_elems, &R, &ldr));
+  TRY(launch_ekf_fast(ctx, ctx->d_P.as<double>(), rd.n, rd.n, R, rd.k, rd.k, ldr, us->bcols_of(fdim).as<int>(), R + (size_t)rd.k * ldr, nullptr, rd.d_dx, rd.d_flag,
+                      true, us->result_of(rd.fdim).p, hpin, ResultBlock(rd.n, rd.F).head_mirror_bytes()));
+  TRY(sync(ctx));
+  us->last_route = ROUTE_WHITENED_REDONE;
+  ++ctx->gather_stamp;
+  ctx->cov_host_synced = ctx->gather_stamp;
+  return PLV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int plv_msckf_update_resident_launch(plv_ctx *ctx, double sigma2, double chi2_mult, double res_norm_gate) {
+  REQUIRE_CTX(ctx);
+  auto *us = ustate(ctx);
+  us->pending_F = 0;
+  ctx->probe_done = false;  // (a launch that failed after setting it, or a wait that was skipped, must not short-cut this update's wait)
+  if (us->bF < 1 || ctx->cov_n < 1) {
+    set_last_error("plv_msckf_update_resident: no staged batch / covariance");
+    return PLV_E_BADARG;
+  }
+  UpdateLaunch u{ctx, us, sigma2, chi2_mult, res_norm_gate};
+  TRY(u.take_batch());
+  TRY(u.reserve());
+  TRY(u.run_or_replay());
   ctx->gate_stage.on = 0, ctx->gate_stage_taken = false;
   ++ctx->gather_stamp;  // the update rewrites the covariance
-  us->pending_fdim = fdim;
-  us->pending_F = F;  // stream-ordered: the result block lands in h_pin; plv_msckf_update_resident_wait reads it
+  us->pending_fdim = u.shape.fdim;
+  us->pending_F = u.shape.F;  // stream-ordered: the result block lands in pinned memory; plv_msckf_update_resident_wait reads it
   if (!us->done_ev) PLV_HIP_CHECK(hipEventCreateWithFlags(&us->done_ev, hipEventDisableTiming));
   PLV_HIP_CHECK(hipEventRecord(us->done_ev, ctx->stream));
   us->done_stamp = ctx->gather_stamp;
@@ -1139,43 +1207,17 @@ int plv_msckf_update_resident_wait(plv_ctx *ctx, uint8_t *accepted, int *n_accep
     PLV_HIP_CHECK(plv::event_sync(us->done_ev));
     if (us->done_stamp > ctx->cov_host_synced) ctx->cov_host_synced = us->done_stamp;
   }
-  const char *hb = hpin.as<char>();
-  const int *hrows = (const int *)(hb + result_rows_off(n, F));
+  const ResultBlock lay(n, F);
+  const void *hb = hpin.p;
+  const int *status = lay.status(hb), *hrows = lay.acc_rows(hb);
   us->last_ambiguous = 0;
-  if (us->redo_w.armed && us->last_route == 4 && *(const int *)(hb + (size_t)n * 8) != 0 && !(*(const int *)(hb + (size_t)n * 8) & 16) &&
-      ((const int *)(hb + (size_t)n * 8))[us->acc_word_used] > 0) {  // (bit 16: not a rejection — a speculative batch the selection loop's cap would have cut, ekf_commit_kernel)
-    // The whitened update came back rejected (update_state.hpp, RedoW): nothing was committed.  The stacked rows are run again the
-    // reference's way — compression, then S = R P R^T + I — with the compression by Householder reflections on the rows themselves
-    // (on the KAIST-layout drive with stamps of 1.5e9 s, where this happens to the first update after the initialisation, the Gram +
-    // Cholesky compression ended 5.6 cm from this one; and the updates the factor form hands over on the bench drive — the car at rest,
-    // a prior block of rank 50 of 110, lambda above 1e4 — all have 5 .. 70 pivots the Gram + Cholesky compression cannot tell from zero,
-    // so trying that compression first would only add its 0.1 ms to the 2 ms of this one).  Its verdict is the update's.
-    const plv_ctx_update_state::RedoW rd = us->redo_w;
-    us->redo_w.armed = false;
-    const int nc = rd.k + 1;
-    const size_t mb = ((size_t)rd.n * 8 + 16 + 3) & ~(size_t)3;
-    ctx->skip_word = nullptr;
-    double *R;
-    int ldr;
-    // (the accepted rows gathered into a dense matrix first: the stack is F x mp_max slots, most of them empty, and the tree of
-    // Householder reductions costs 0.4 ms per level of 224 rows)
-    int m_acc = 0;
-    for (int f = 0; f < rd.F; ++f) m_acc += std::max(hrows[f], 0);
-    const int m_c = std::max(m_acc, 2 * nc);
-    TRY(ctx->d_stackc.reserve((size_t)m_c * nc * 8));
-    TRY(launch_stack_compact(ctx, ctx->stack_of(wfdim).as<double>(), rd.Mtot, nc, rd.d_acc_rows, rd.F, rd.mp_max, ctx->d_stackc.as<double>(), m_c));
-    TRY(launch_tsqr(ctx, ctx->d_stackc.as<double>(), m_c, m_c, nc, ctx->d_stack2.as<double>(), rd.tmp_elems, &R, &ldr));
-    TRY(launch_ekf_fast(ctx, ctx->d_P.as<double>(), rd.n, rd.n, R, rd.k, rd.k, ldr, us->bcols_of(wfdim).as<int>(), R + (size_t)rd.k * ldr, nullptr, rd.d_dx, rd.d_flag,
-                        true, us->result_of(rd.fdim).p, hpin.p, mb));
-    TRY(sync(ctx));
-    us->last_route = 5;
-    ++ctx->gather_stamp;
-    ctx->cov_host_synced = ctx->gather_stamp;
-  }
+  // (STATUS_SPEC_OVER_CAP: not a rejection — a speculative batch the selection loop's cap would have cut, ekf_commit_kernel)
+  if (us->redo_w.armed && us->last_route == ROUTE_WHITENED && status[0] != 0 && !(status[0] & STATUS_SPEC_OVER_CAP) && status[us->acc_word_used] > 0)
+    TRY(redo_by_householder(ctx, us, wfdim, hpin.p, hrows));
   us->redo_w.armed = false;
   ++plv::counters().route[us->last_route & 7];
-  int flag = *(const int *)(hb + (size_t)n * 8);
-  const unsigned char *hacc = (const unsigned char *)(hb + (size_t)n * 8 + 16);
+  const int flag = status[0];
+  const unsigned char *hacc = lay.accepted(hb);
   int nrows = 0, overflow = 0;
   for (int f = 0; f < F; ++f) {
     if (accepted) accepted[f] = hacc[f];
@@ -1188,10 +1230,10 @@ int plv_msckf_update_resident_wait(plv_ctx *ctx, uint8_t *accepted, int *n_accep
     return PLV_E_CAPACITY;
   }
   if (flag != 0) {
-    set_last_error("EKFUpdate rejected: %s", (flag & 16) ? "speculative batch over the selection cap (run again by the caller)" : (flag & 2) ? "S not positive definite" : "negative covariance diagonal");
+    set_last_error("EKFUpdate rejected: %s", ekf_rejection_text(flag));
     return PLV_E_NOT_PSD;
   }
-  memcpy(dx, hb, (size_t)n * 8);
+  memcpy(dx, lay.dx(hb), (size_t)n * 8);
   return PLV_OK;
 }
 

@@ -228,14 +228,16 @@ struct Pass {
     d_block = S.sys.as<double>();
     char *w = S.sys.as<char>() + blk;
     d_rows = (int *)w, d_initflag = (int *)(w + 16), d_skip = (int *)(w + 32), d_out = (double *)(w + 64);
-    res_bytes = (size_t)n_cap * 8 + 16 + 8 + 8;
+    // (the shared head of plv::ResultBlock — dx, status words, accepted — and a tail of its own: one verdict padded to 8, its rows)
+    const ResultBlock head(n_cap, 0);
+    res_bytes = head.head_bytes() + 8 + 8;
     const void *before = S.res.p;
     TRY(S.res.reserve(res_bytes));
     if (S.res.p != before) PLV_HIP_CHECK(hipMemsetAsync(S.res.p, 0, S.res.cap, ctx->stream));
     TRY(S.h_res.reserve(res_bytes + 64));
     char *r = S.res.as<char>();
-    d_dx = (double *)r, d_flag = (int *)(r + (size_t)n_cap * 8), d_acc = (unsigned char *)(r + (size_t)n_cap * 8 + 16);
-    d_acc_rows = (int *)(r + (size_t)n_cap * 8 + 24);
+    d_dx = head.dx(r), d_flag = head.status(r), d_acc = head.accepted(r);
+    d_acc_rows = (int *)(r + head.head_bytes() + 8);
     TRY(ctx->d_chi2.reserve(64));
     TRY(ctx->d_stack.reserve((size_t)(kmax + 4) * ld * 8));
     return PLV_OK;
@@ -410,7 +412,8 @@ int plv_camera_update_slam(plv_ctx *ctx, const plv_state_view *st, const plv_upd
     return PLV_OK;
   }
   TRY(W.stage_static(n));
-  const size_t rb = (size_t)n * 8 + 16 + 8;
+  const ResultBlock head(n, 0);
+  const size_t rb = head.head_bytes() + 8;  // (+ the verdict)
   char *hres = W.us->slam.h_res.as<char>();
   for (int f = 0; f < F; ++f) {
     const Entry &e = W.ent[f];
@@ -447,14 +450,14 @@ int plv_camera_update_slam(plv_ctx *ctx, const plv_state_view *st, const plv_upd
     PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
     ctx->cov_host_synced = stamp;
     ctx->prof.collect();
-    const int flag = *(const int *)(hres + (size_t)n * 8);
-    const bool passed = *(const unsigned char *)(hres + (size_t)n * 8 + 16) != 0;
+    const int flag = *head.status(hres);
+    const bool passed = *head.accepted(hres) != 0;
     if (!passed) {
       verdict[f] = 2;
     } else if (flag != 0) {
       verdict[f] = 3;  // (the commit kernel left covariance and dx alone)
     } else {
-      const double *dx = (const double *)hres;
+      const double *dx = head.dx(hres);
       TRY(W.apply(n_var, vars, n_lm, lms, dx, n));
       if (dx_each) std::copy(dx, dx + n, dx_each + (size_t)f * n);
       verdict[f] = 1;
@@ -548,12 +551,13 @@ int plv_camera_init_slam(plv_ctx *ctx, const plv_state_view *st, const plv_updat
     const int rc_e = launch_ekf_fast(ctx, ctx->d_P2.as<double>(), n2, n2, dHx + 3, mup, k, W.ld, d_cols, dres + 3, nullptr, W.d_dx, W.d_flag);
     ctx->skip_word = nullptr;
     TRY(rc_e);
-    const size_t rb = (size_t)n_cap * 8 + 16;
+    const ResultBlock head(n_cap, 0);
+    const size_t rb = head.head_bytes();
     PLV_HIP_CHECK(plv::memcpy_async(hres, W.us->slam.res.p, rb, hipMemcpyDeviceToHost, ctx->stream));
     PLV_HIP_CHECK(plv::memcpy_async(hres + rb, W.d_initflag, 16 + 32 + 24, hipMemcpyDeviceToHost, ctx->stream));  // flag .. skip .. v
     PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
     ctx->prof.collect();
-    const int rejected = *(const int *)(hres + rb), flag = *(const int *)(hres + (size_t)n_cap * 8);
+    const int rejected = *(const int *)(hres + rb), flag = *head.status(hres);
     if (rejected || flag != 0) {  // :572-587 / the update failed: the initialisation is reverted (:430-435) — nothing was swapped in
       verdict[f] = rejected ? 2 : 3;
       TRY(W.give_back(e));
@@ -564,7 +568,7 @@ int plv_camera_init_slam(plv_ctx *ctx, const plv_state_view *st, const plv_updat
     ctx->cov_n = n2;
     ++ctx->gather_stamp;
     ctx->cov_host_synced = ctx->gather_stamp;
-    const double *dx = (const double *)hres, *v = (const double *)(hres + rb + 48);
+    const double *dx = head.dx(hres), *v = (const double *)(hres + rb + 48);
     plv_landmark &lm = lms[*n_lm_io];
     lm.featid = e.id, lm.id = n, lm.rep = st->feat_rep;
     plv_landmark_from_xyz(lm.rep, e.p, lm.fej);  // create_landmark: value = fej (CamHelper.cpp create_landmark)

@@ -1238,10 +1238,10 @@ int plv_camera_try_update(plv_ctx *ctx, const plv_state_view *st, plv_try_update
   T->defer_db = false;
   T->early_st = nullptr, T->early_lines = nullptr;
   bool chained = io->opt_lines && plv_camera_lines_job_pending(ctx);
-  if (chained && (plv_update_state(ctx)->last_route >= 5 || io->res_points->status != PLV_OK)) {
+  if (chained && (plv_update_state(ctx)->last_route == plv::ROUTE_WHITENED_REDONE || io->res_points->status != PLV_OK)) {
     // the point update came back rejected — and was perhaps run again on the host's verdict (update_state.hpp, RedoW): the chained
     // line launch saw the rejection and ended without touching anything (JacParams::chain_status).  The line half goes the unchained way.
-    if (plv_update_state(ctx)->last_route >= 5) ++plv::counters().route[6];  // (plv_route_counts[6]: re-runs next to a chained line launch)
+    if (plv_update_state(ctx)->last_route == plv::ROUTE_WHITENED_REDONE) ++plv::counters().route[6];  // (plv_route_counts[6]: re-runs next to a chained line launch)
     plv_camera_lines_job_abort2(ctx, rc == PLV_OK ? 1 : 0);  // (the frame goes on: its line pool stays formed)
     chained = false;
   }

@@ -5,10 +5,11 @@
 
 #include "plv_ctx.hpp"
 #include "plv_internal.hpp"
+#include "update_route.hpp"
 
 struct plv_ctx_update_state {
   plv::DevBuf q95;
-  plv::DevBuf result;   // [dx: max_n doubles][flag: int + pad][accepted: bytes]
+  plv::DevBuf result;   // plv::ResultBlock (update_route.hpp)
   plv::DevBuf covck;    // covariance checkpoint
   int covck_n = 0;      // dimension of the checkpointed covariance (a rollback restores it together with the data)
   plv::DevBuf bHf, bHx, bres, brows, bcols, bwork;  // staged feature batch ([Hf|Hx|res] in bHf) + working copy
@@ -21,12 +22,10 @@ struct plv_ctx_update_state {
   unsigned long long b_gather_token = 0;  // plv_ctx::gather_stamp right after the gathers that rode on the batch's launch (0: none)
   std::vector<int> brows_host;
   // measurement compression (plv_update_compression_mode): 0 = whitened update (information matrix + factor of the prior block; no
-  // factor of the measurements), 1 = Householder TSQR on the stacked rows, 2 = Gram + Cholesky first, redone through the Householder
-  // route when its factorisation reports pivots it could not resolve, 3 = Gram matrix + blocked Cholesky (the round-2 default)
+  // factor of the measurements), 1 = Householder TSQR on the stacked rows; anything else is refused
   int compress_mode = 0;
-  int last_route = 0;       // of the last update: 0 none / not compressed, 1 Gram + Cholesky, 2 Householder, 3 Gram vetoed and redone by Householder, 4 whitened,
-                            // 5 whitened came back rejected / withheld and was run again by Householder reflections (redo_w)
-  int last_ambiguous = 0;   // pivots the last Gram factorisation could not tell from zero
+  int last_route = 0;       // of the last update: plv::UpdateRoute (update_route.hpp)
+  int last_ambiguous = 0;   // always 0 (no route is left that counts unresolved pivots); still reported by plv_update_compression_mode
   // Status block of a LINE update (round 4): the chained line launch reads the point update's dx from `result` while its own gate
   // writes verdicts — and a larger line batch may make its block grow — so the two measurement kinds keep separate blocks, each with
   // its own pair of alternating accepted-entry counters.
@@ -42,7 +41,7 @@ struct plv_ctx_update_state {
   // A whitened update that comes back rejected (negative diagonal of P', B not positive definite) is not final: its formulas are
   // not the reference's and lose digits elsewhere (dense_kernels.hip "whitened update": eps x how much better than the prior the
   // measurements know a direction — large for the first update after an initialisation).  The stacked rows are still on the device
-  // and the update is run again through a Householder compression and the EKF step on R (last_route 5) before the verdict is reported.
+  // and the update is run again through a Householder compression and the EKF step on R (ROUTE_WHITENED_REDONE) before the verdict is reported.
   struct RedoW {
     bool armed = false;
     int Mtot = 0, k = 0, n = 0, F = 0, mp_max = 0, fdim = 3;

@@ -173,6 +173,27 @@ def test_msckf_update_parity(ctx, oracle, F, M, n, k, fdim, gate):
     assert np.array_equal(P1, P1.T)
 
 
+@pytest.mark.parametrize("F,k,route", [(30, 200, 2), (25, 204, 0)])
+def test_msckf_update_beyond_the_fast_ekf_step_is_refused(ctx, pkg, F, k, route):
+    """More than 192 rows for the EKF step, F features of 11 rows (fdim 3: eight row slots each) built as test_msckf_update_parity
+    builds its batches — behind the Householder compression with k = 200 columns (240 row slots, r = k), and as the uncompressed
+    stack of 200 row slots under k = 204 columns.  The fast step does not take them, and the general one holds its factor in LDS,
+    r (r | 1) 8 B <= 160 KB, i.e. r <= 143: the route behind ekf_fast (update_route.hpp: EKF_THEN_COPY, and no skip word) refuses every
+    update that reaches it, with PLV_E_CAPACITY and before anything has touched the covariance; the route it got as far as is
+    reported.  (Every other branch of the route plan is reached by the tests of this file and of test_gpu_update_hard /
+    _update_frame / _fused_launches / _kaist_replay / _jacobian.)"""
+    n, M = 210, 6
+    P = synth.spd_cov(n, seed=F)
+    cols = synth.col_map(n, k, seed=M, skip=min(15, n - k))
+    rows, Hf, Hx, res = synth.msckf_batch(F=F, M=M, k=k, fdim=3, seed=F + M)
+    rows = np.minimum(rows, 11).astype(np.int32)
+    with pytest.raises(pkg.PlvError) as e:
+        ctx.msckf_update(P, rows, Hf, Hx, res, cols, 2.25, 1.0, 3.0)
+    assert e.value.code == pkg.PLV_E_CAPACITY and "LDS-resident Cholesky capacity" in str(e.value)
+    assert ctx.update_compression_mode()[1] == route
+    assert np.array_equal(ctx.cov_download(n), P)
+
+
 def test_msckf_update_golden(ctx):
     import os
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "update_small.npz"))

@@ -101,6 +101,26 @@ def test_batch_tail_conserves_observations_under_sanitizers(tmp_path):
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
 
 
+def test_update_route_plan_and_result_layout_under_sanitizers(tmp_path):
+    """pl-viwo_amd/csrc/update_route.hpp, the device-free part of the update launch, under AddressSanitizer + UBSan: every quantity of
+    the result block's layout equals the offset arithmetic it replaced, the regions lie apart and aligned, and every field is written
+    through the views into a heap block of exactly the allocated size; the route plan (plan_update / plan_tail / plan_chain) equals the
+    conditions the launch spelled out before, over the full product of modes, flags, knobs and (Mtot, k, accepted rows) on both sides
+    of every threshold."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "update_route_check")
+    src = os.path.join(ROOT, "tests", "host_sanitize", "update_route_check.cpp")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", src, "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"), timeout=120)
+    import re
+    m = re.search(r"ok: update routes, (\d+) combinations", r.stdout)
+    assert r.returncode == 0 and m and int(m.group(1)) > 0, (r.stdout[-3000:], r.stderr[-4000:])
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+
+
 def test_helper_threads_are_clamped_to_the_allowed_cpus(tmp_path):
     """the default number of polling helper threads of the line detector's host stage is min(7, allowed CPUs - 2),
     at most two below six CPUs, none below three — the caller's thread and the line worker keep a CPU each."""
