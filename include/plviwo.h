@@ -410,6 +410,38 @@ int plv_db_export_tracks(plv_ctx *ctx, const uint64_t *ids, int n, int *obs_ptr,
 int plv_db_cleanup_measurements(plv_ctx *ctx, double t); /* REF: FeatureDatabase.cpp:286-323 */
 int plv_db_remove(plv_ctx *ctx, const uint64_t *ids, int n);
 
+/* ================================================================ stereo point tracker
+ *
+ * TrackKLT::feed_stereo and perform_detection_stereo (REF: open_vins/ov_core/src/track/TrackKLT.cpp:202-393, 530-827) for a
+ * synchronised pair: camera 0 (left) is the context's camera (cfg.intrinsics, plv_set_camera_intrinsics, plv_set_camera_model),
+ * camera 1 (right) gets its own eight intrinsic values and model here; both have the context's width x height.  The stereo tracker
+ * is a second tracker beside the monocular one, with its own pyramids, last points, id counter and a database whose features keep
+ * their observations per camera (ov_core::Feature).  A context takes images through one of the two: once plv_tracker_feed_stereo
+ * has taken a pair, plv_tracker_feed* and plv_camera_frame return PLV_E_BADARG, and the reverse.  The updates
+ * (plv_camera_update_*, plv_camera_try_update) read the monocular database only.
+ * Every call below returns PLV_E_BADARG with a plv_last_error text for an argument it refuses and then leaves the stereo tracker,
+ * both cameras' pyramids and the database as they were. */
+int plv_stereo_configure(plv_ctx *ctx, const double *K8_right, int model_right);
+/* the intrinsics camera `cam` (0, 1) tracks with from the next pair on (the reference tracks with the state's estimate when it
+ * calibrates them: an adapter refreshes both per frame); cam 0 is plv_set_camera_intrinsics */
+int plv_stereo_set_intrinsics(plv_ctx *ctx, int cam, const double *K8);
+/* One pair.  `encoding`: PLV_ENC_* of both images (rows of width * bytes-per-pixel bytes at least: stride_left / stride_right); a
+ * Bayer or colour image is converted per image on the device, as by plv_tracker_feed_encoded.  Masks are width x height bytes
+ * (> 127: no feature there) or NULL (nothing masked). */
+int plv_tracker_feed_stereo(plv_ctx *ctx, double timestamp, const uint8_t *left, int stride_left, const uint8_t *right, int stride_right,
+                            int encoding, const uint8_t *mask_left, const uint8_t *mask_right);
+/* pts_last / ids_last of camera `cam` (a feature seen by both cameras has the same id in both lists) */
+int plv_stereo_last(plv_ctx *ctx, int cam, float *pts, uint64_t *ids, int cap, int *n);
+/* The stereo database: features (by id), each with the observations of camera 0 and of camera 1. */
+int plv_stereo_db_size(plv_ctx *ctx);
+int plv_stereo_db_ids(plv_ctx *ctx, uint64_t *ids, int cap, int *n); /* ascending */
+/* plv_db_export_tracks for the observations of camera `cam`; a feature without any in that camera gets an empty range */
+int plv_stereo_db_export_tracks(plv_ctx *ctx, const uint64_t *ids, int n, int cam, int *obs_ptr, double *obs_time, float *obs_uv,
+                                float *obs_uvn, int cap_obs);
+/* FeatureDatabase::cleanup_measurements(t) over both cameras: a feature left without observations goes */
+int plv_stereo_db_cleanup_measurements(plv_ctx *ctx, double t);
+int plv_stereo_db_remove(plv_ctx *ctx, const uint64_t *ids, int n);
+
 /* ================================================================ per-feature Jacobians (K10)
  *
  * Flat views of what CamHelper::get_feature_jacobian_full (REF: PL-VIWO/src/update/cam/

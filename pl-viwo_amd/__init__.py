@@ -172,6 +172,15 @@ def load_library():
         "plv_db_export_tracks": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int, ip, dp, fp, fp, C.c_int]),
         "plv_db_cleanup_measurements": (C.c_int, [vp, C.c_double]),
         "plv_db_remove": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int]),
+        "plv_stereo_configure": (C.c_int, [vp, dp, C.c_int]),
+        "plv_stereo_set_intrinsics": (C.c_int, [vp, C.c_int, dp]),
+        "plv_tracker_feed_stereo": (C.c_int, [vp, C.c_double, u8p, C.c_int, u8p, C.c_int, C.c_int, u8p, u8p]),
+        "plv_stereo_last": (C.c_int, [vp, C.c_int, fp, u64p, C.c_int, ip]),
+        "plv_stereo_db_size": (C.c_int, [vp]),
+        "plv_stereo_db_ids": (C.c_int, [vp, u64p, C.c_int, ip]),
+        "plv_stereo_db_export_tracks": (C.c_int, [vp, u64p, C.c_int, C.c_int, ip, dp, fp, fp, C.c_int]),
+        "plv_stereo_db_cleanup_measurements": (C.c_int, [vp, C.c_double]),
+        "plv_stereo_db_remove": (C.c_int, [vp, u64p, C.c_int]),
         "plv_cpi_noise": (C.c_int, [C.POINTER(PlvStateView), C.POINTER(PlvCpiTable), C.c_int, dp, dp, ip, u8p]),
         "plv_triangulate": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvTracks), C.POINTER(PlvTriOptions), dp, u8p, dp]),
         "plv_jacobian_columns": (C.c_int, [C.POINTER(PlvStateView), C.POINTER(PlvTracks), ip, C.c_int, ip]),
@@ -2043,6 +2052,59 @@ class Context:
     def db_remove(self, ids):
         ids = np.ascontiguousarray(ids, dtype=np.uint64)
         self._chk(self.lib.plv_db_remove(self.h, ids.ctypes.data_as(C.POINTER(C.c_uint64)), len(ids)))
+
+    # ---- stereo point tracker (camera 0: the context's camera, camera 1: configured here) + its per-camera database
+    def stereo_configure(self, K8_right, model_right=0):
+        K = np.ascontiguousarray(K8_right, dtype=np.float64)
+        self._chk(self.lib.plv_stereo_configure(self.h, _dp(K), int(model_right)))
+
+    def stereo_set_intrinsics(self, cam, K8):
+        K = np.ascontiguousarray(K8, dtype=np.float64)
+        self._chk(self.lib.plv_stereo_set_intrinsics(self.h, int(cam), _dp(K)))
+
+    def tracker_feed_stereo(self, timestamp, left, right, encoding="mono8", mask_left=None, mask_right=None):
+        """plv_tracker_feed_stereo: one pair (TrackKLT::feed_stereo); both images in `encoding` (name or PLV_ENC_* value)"""
+        shape = (self.cfg.height, self.cfg.width)
+        a, sa, e = self._encoded_rows(left, encoding, shape)
+        b, sb, _ = self._encoded_rows(right, encoding, shape)
+        ml = np.ascontiguousarray(mask_left, dtype=np.uint8) if mask_left is not None else None
+        mr = np.ascontiguousarray(mask_right, dtype=np.uint8) if mask_right is not None else None
+        self._chk(self.lib.plv_tracker_feed_stereo(self.h, float(timestamp), _u8p(a), sa, _u8p(b), sb, e, _u8p(ml), _u8p(mr)))
+
+    def stereo_last(self, cam, cap=8192):
+        pts = np.zeros((cap, 2), dtype=np.float32)
+        ids = np.zeros(cap, dtype=np.uint64)
+        n = C.c_int()
+        self._chk(self.lib.plv_stereo_last(self.h, int(cam), _fp(pts), ids.ctypes.data_as(C.POINTER(C.c_uint64)), cap, C.byref(n)))
+        return pts[:n.value].copy(), ids[:n.value].copy()
+
+    def stereo_db_size(self):
+        return self.lib.plv_stereo_db_size(self.h)
+
+    def stereo_db_ids(self, cap=65536):
+        ids = np.zeros(cap, dtype=np.uint64)
+        n = C.c_int()
+        self._chk(self.lib.plv_stereo_db_ids(self.h, ids.ctypes.data_as(C.POINTER(C.c_uint64)), cap, C.byref(n)))
+        return ids[:n.value].copy()
+
+    def stereo_db_export(self, ids, cam, cap_obs=1 << 20):
+        """(obs_ptr, times, uv, uvn) of camera `cam`'s observations of the features `ids`, in plv_tracks layout"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64)
+        ptr = np.zeros(len(ids) + 1, dtype=np.int32)
+        t = np.zeros(cap_obs)
+        uv = np.zeros((cap_obs, 2), dtype=np.float32)
+        uvn = np.zeros((cap_obs, 2), dtype=np.float32)
+        self._chk(self.lib.plv_stereo_db_export_tracks(self.h, ids.ctypes.data_as(C.POINTER(C.c_uint64)), len(ids), int(cam), _ip(ptr),
+                                                       _dp(t), _fp(uv), _fp(uvn), cap_obs))
+        n = ptr[-1]
+        return ptr, t[:n].copy(), uv[:n].copy(), uvn[:n].copy()
+
+    def stereo_db_cleanup_measurements(self, t):
+        self._chk(self.lib.plv_stereo_db_cleanup_measurements(self.h, float(t)))
+
+    def stereo_db_remove(self, ids):
+        ids = np.ascontiguousarray(ids, dtype=np.uint64)
+        self._chk(self.lib.plv_stereo_db_remove(self.h, ids.ctypes.data_as(C.POINTER(C.c_uint64)), len(ids)))
 
     def triangulate(self, st, tr, min_dist=0.1, max_dist=60.0, max_cond=1e4, max_baseline=40.0, refine=True):
         opt = PlvTriOptions(min_dist, max_dist, max_cond, max_baseline, 1 if refine else 0)

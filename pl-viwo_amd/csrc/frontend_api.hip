@@ -5,6 +5,7 @@
 
 #include "detect_kernels.hpp"
 #include "encoding_kernels.hpp"
+#include "front_parts.hpp"
 #include "frontend_kernels.hpp"
 #include "line_kernels.hpp"
 #include "plv_internal.hpp"
@@ -13,22 +14,7 @@ using namespace plv;
 
 namespace {
 
-struct DetJob {  // one top-up detection between its host stages (plv_perform_detection / _ahead)
-  std::vector<uint8_t> close;        // occupancy grid of the kept points (min_px_dist cells)
-  std::vector<int> boxes, cells;
-  std::vector<float> pts;            // kept points
-  std::vector<uint64_t> ids;
-  int cw = 0, ch = 0, nfg = 0, sxp = 0, syp = 0, n_cells = 0, n_slots = 0;
-  char *h_out = nullptr;             // pinned: [xy n_slots x 2 f32][resp n_slots f32][valid n_slots u8][over n_cells u8]
-  // what an ahead-of-time job was started from
-  bool active = false, has_mask = false;
-  int fed = 0, n_in = 0;
-  std::vector<float> in_pts;
-  std::vector<uint64_t> in_ids;
-  std::vector<uint8_t> in_mask;
-};
-
-struct FrontState {
+struct FrontState : DetScratch {
   int W = 0, H = 0;
   PyrDesc pyr[2];          // ping-pong pyramids
   DevBuf pyr_mem[2];
@@ -42,8 +28,6 @@ struct FrontState {
   DevBuf ds_src, ds_dst;   // full-resolution staging of plv_downsample / plv_feed_image_downsampled
   // per-call point buffers
   DevBuf pts0, pts1, n0, n1, status, iters, mask, counts, info, io, models;
-  DevBuf det_in, det_out, det_mask, subpix_tab, det_cand, det_cand_n;  // detection staging
-  PinBuf det_pin;
   PinBuf img_pin[6];       // host images on their way to the device (plv_feed_image_enqueue): the caller's buffer is free at return
   int img_pin_next = 0;
   // images in their sensor encoding (plv_image_stage_encoded ...): nothing here is allocated before the first of them arrives
@@ -64,6 +48,8 @@ struct FrontState {
     if (_rc != PLV_OK) return _rc; \
   } while (0)
 
+}  // namespace
+namespace plv {
 int level_geometry(int W, int H, int win, int max_level, PyrDesc &p) {
   p.levels = 0;
   unsigned off = 0;
@@ -83,8 +69,7 @@ int level_geometry(int W, int H, int win, int max_level, PyrDesc &p) {
   }
   return (int)off;
 }
-
-}  // namespace
+}  // namespace plv
 extern "C" int plv_set_lk_window(plv_ctx *ctx, int win) {
   if (!ctx || win < 3 || win > 21 || (win & 1) == 0) {
     set_last_error("plv_set_lk_window: odd window sizes 3 .. 21");
@@ -149,33 +134,36 @@ int sync(plv_ctx *ctx) {
 int feed_device(plv_ctx *ctx, FrontState *s, const uint8_t *d_img, const uint8_t *h_src = nullptr) {
   plv::HostPhase ph("feed image (enqueue hist + pyramid)");
   const int next = s->fed == 0 ? s->cur : 1 - s->cur;
-  PyrDesc &p = s->pyr[next];
-  const int npix = s->W * s->H;
+  TRY(front_feed_pyramid(ctx, s->W, s->H, d_img, h_src, s->pyr[next], s->hist, s->clahe_lut));
+  s->cur = next;
+  s->fed++;
+  return PLV_OK;
+}
+}  // namespace
+
+int plv::front_feed_pyramid(plv_ctx *ctx, int W, int H, const uint8_t *d_img, const uint8_t *h_src, const PyrDesc &p, DevBuf &hist,
+                            DevBuf &clahe_lut) {
+  const int npix = W * H;
   switch (ctx->cfg.histogram_method) {
     case PLV_HIST_HISTOGRAM:  // (the equalisation rides on the first pyramid launch)
-      TRY(launch_equalize_pyramid(ctx, d_img, p, s->hist.as<unsigned>(), h_src));
-      s->cur = next;
-      s->fed++;
-      return PLV_OK;
+      return launch_equalize_pyramid(ctx, d_img, p, hist.as<unsigned>(), h_src);
     case PLV_HIST_NONE:
       if (h_src) PLV_HIP_CHECK(plv::memcpy_async((void *)d_img, h_src, (size_t)npix, hipMemcpyHostToDevice, ctx->stream));
       PLV_HIP_CHECK(plv::memcpy_async(p.base + p.off[0], d_img, (size_t)npix, hipMemcpyDeviceToDevice, ctx->stream));
       break;
     case PLV_HIST_CLAHE:  // REF: TrackKLT.cpp:60-64 — clip 10.0, 8x8 tiles
       if (h_src) PLV_HIP_CHECK(plv::memcpy_async((void *)d_img, h_src, (size_t)npix, hipMemcpyHostToDevice, ctx->stream));
-      TRY(s->clahe_lut.reserve(64 * 256));
-      TRY(launch_clahe(ctx, d_img, p.base + p.off[0], s->W, s->H, 10.0, 8, s->clahe_lut.as<uint8_t>()));
+      TRY(clahe_lut.reserve(64 * 256));
+      TRY(launch_clahe(ctx, d_img, p.base + p.off[0], W, H, 10.0, 8, clahe_lut.as<uint8_t>()));
       break;
     default:
       set_last_error("front-end: unknown histogram method %d", ctx->cfg.histogram_method);
       return PLV_E_BADARG;
   }
-  TRY(launch_pyramid(ctx, p));
-  s->cur = next;
-  s->fed++;
-  return PLV_OK;
+  return launch_pyramid(ctx, p);
 }
 
+namespace {
 int upload_image(plv_ctx *ctx, FrontState *s, void *dst, const uint8_t *img, int stride) {
   if (!img || stride < s->W) {
     set_last_error("front-end: null image or stride %d < width %d", stride, s->W);
@@ -186,8 +174,10 @@ int upload_image(plv_ctx *ctx, FrontState *s, void *dst, const uint8_t *img, int
   return PLV_OK;
 }
 
+}  // namespace
+
 // ---- images in their sensor encoding
-int check_encoded(const char *who, const uint8_t *data, int stride, int encoding, int w) {
+int plv::check_encoded(const char *who, const uint8_t *data, int stride, int encoding, int w) {
   const int bpp = encoding_bpp(encoding);
   if (bpp == 0) {
     set_last_error("%s: %d is no PLV_ENC_* encoding", who, encoding);
@@ -204,6 +194,7 @@ int check_encoded(const char *who, const uint8_t *data, int stride, int encoding
   return PLV_OK;
 }
 
+namespace {
 // Where the conversion kernel reads a W x H image from: `data` itself when it lies (packed) in one of the library's page-locked raw
 // blocks, else one of the library's own two blocks, into which the image is copied here.  *own: that block's index, or -1.
 int encoded_source(FrontState *s, const uint8_t *data, int stride, int bpp, const uint8_t **h_src, int *own) {
@@ -263,11 +254,10 @@ void plv_frontend_destroy(plv_ctx *ctx) {
   s->cv_src.release();
   s->cv_dst.release();
   DevBuf *bufs[] = {&s->pyr_mem[0], &s->pyr_mem[1], &s->raw, &s->hist, &s->clahe_lut, &s->ds_src, &s->ds_dst, &s->pts0, &s->pts1, &s->n0, &s->n1,
-                    &s->status, &s->iters, &s->mask, &s->counts, &s->info, &s->io, &s->models, &s->det_in, &s->det_out,
-                    &s->det_mask, &s->subpix_tab, &s->det_cand, &s->det_cand_n};
+                    &s->status, &s->iters, &s->mask, &s->counts, &s->info, &s->io, &s->models};
   for (auto *b : bufs) b->release();
   for (auto &b : s->slots) b.release();
-  s->det_pin.release();
+  s->release_detection();
   delete s;
   ctx->fe_state = nullptr;
 }
@@ -710,9 +700,10 @@ int plv_perform_matching(plv_ctx *ctx, int n, const float *pts0, float *pts1, ui
 // near existing points, ids in extraction order).  plv_perform_detection runs them back to back; plv_perform_detection_ahead runs
 // the first two on a side stream as soon as a frame's points are known, so that the top-up the NEXT frame starts with (it works on
 // the then-last image with these very points, TrackKLT.cpp:127-131) is waiting for it instead of sitting on its critical path.
-namespace {
-int det_pre(plv_ctx *ctx, FrontState *s, const uint8_t *mask, const float *pts_in, const uint64_t *ids_in, int n_in, DetJob &J) {
-  const int w = s->W, h = s->H;
+}  // extern "C"
+namespace plv {
+int det_pre(plv_ctx *ctx, int w, int h, const uint8_t *mask, const float *pts_in, const uint64_t *ids_in, int n_in, DetJob &J,
+            const DetStereoRules *stereo) {
   const plv_config &c = ctx->cfg;
   const int min_px = c.min_px_dist, grid_x = c.grid_x, grid_y = c.grid_y, num_features = c.num_features;
   if (min_px < 1 || grid_x < 1 || grid_y < 1) return PLV_E_BADARG;
@@ -733,7 +724,9 @@ int det_pre(plv_ctx *ctx, FrontState *s, const uint8_t *mask, const float *pts_i
     if (xc < 0 || xc >= J.cw || yc < 0 || yc >= J.ch) continue;
     const int xg = (int)std::floor(fx / size_x), yg = (int)std::floor(fy / size_y);
     if (xg < 0 || xg >= grid_x || yg < 0 || yg >= grid_y) continue;
-    if (J.close[(size_t)yc * J.cw + xc] > 127) continue;
+    if (J.close[(size_t)yc * J.cw + xc] > 127 &&
+        !(stereo && std::find(stereo->spared, stereo->spared + stereo->n_spared, ids_in[i]) != stereo->spared + stereo->n_spared))
+      continue;
     if (mask && mask[(size_t)y * w + x] > 127) continue;
     J.close[(size_t)yc * J.cw + xc] = 255;
     if (grid[(size_t)yg * grid_x + xg] < 255) grid[(size_t)yg * grid_x + xg] += 1;
@@ -750,7 +743,8 @@ int det_pre(plv_ctx *ctx, FrontState *s, const uint8_t *mask, const float *pts_i
   // ---- REF :466-471
   const double min_feat_percent = 0.50;
   const int n = (int)J.ids.size();
-  if (num_features - n < std::min(20, (int)(min_feat_percent * num_features))) return PLV_OK;
+  const int needed = num_features - n, least = std::min(20, (int)(min_feat_percent * num_features));
+  if (stereo && stereo->strict_need ? needed <= least : needed < least) return PLV_OK;
   // ---- REF :478-492 cells that still need features and are not fully masked
   const int nfg_req = std::max(1, (int)(min_feat_percent * ((int)((double)num_features / (double)(grid_x * grid_y)) + 1)));
   // REF Grider_GRID.h:88-98 grid actually used for extraction
@@ -781,8 +775,8 @@ int det_pre(plv_ctx *ctx, FrontState *s, const uint8_t *mask, const float *pts_i
 }
 
 // FAST per cell + sub-pixel refinement of every kept slot + the copy of the slots to pinned memory, all on `stream`
-int det_launch(plv_ctx *ctx, FrontState *s, const PyrDesc &pyr, const uint8_t *mask, DetJob &J, hipStream_t stream) {
-  const int w = s->W, h = s->H;
+int det_launch(plv_ctx *ctx, DetScratch &scratch, int w, int h, const PyrDesc &pyr, const uint8_t *mask, DetJob &J, hipStream_t stream) {
+  DetScratch *s = &scratch;
   const plv_config &c = ctx->cfg;
   const int n_cells = J.n_cells, n_slots = J.n_slots;
   const size_t o_cells = 0, o_boxes = ((size_t)n_cells * 8 + 15) & ~(size_t)15, in_total = o_boxes + ((J.boxes.size() * 4 + 15) & ~(size_t)15);
@@ -867,36 +861,51 @@ int det_check(const DetJob &J) {
   return PLV_OK;
 }
 
-// ---- REF :497-527 reject near existing points, assign ids in extraction order
+// ---- REF :497-527 reject near existing points: take(x, y) for every corner that stays, in extraction order, while room() holds
+template <class Room, class Take> static void accept_corners(plv_ctx *ctx, const DetJob &J, Room room, Take take) {
+  if (J.n_slots <= 0) return;
+  const int min_px = ctx->cfg.min_px_dist;
+  std::vector<uint8_t> close = J.close;
+  const float *oxy = (const float *)(J.h_out);
+  const uint8_t *oval = (const uint8_t *)(J.h_out + (size_t)J.n_slots * 12);
+  for (int sl = 0; sl < J.n_slots && room(); ++sl) {
+    if (!oval[sl]) continue;
+    const float px = oxy[2 * sl], py = oxy[2 * sl + 1];
+    const int xg = (int)(px / (float)min_px), yg = (int)(py / (float)min_px);
+    if (xg < 0 || xg >= J.cw || yg < 0 || yg >= J.ch) continue;
+    if (close[(size_t)yg * J.cw + xg] > 127) continue;
+    close[(size_t)yg * J.cw + xg] = 255;
+    take(px, py);
+  }
+}
+
+// ... and ids in extraction order
 void det_post(plv_ctx *ctx, const DetJob &J, float *pts, uint64_t *ids, int cap, uint64_t *currid, int *n_out) {
   int n = (int)J.ids.size();
   std::copy(J.pts.begin(), J.pts.end(), pts);
   std::copy(J.ids.begin(), J.ids.end(), ids);
-  if (J.n_slots > 0) {
-    const int min_px = ctx->cfg.min_px_dist;
-    std::vector<uint8_t> close = J.close;
-    const float *oxy = (const float *)(J.h_out);
-    const uint8_t *oval = (const uint8_t *)(J.h_out + (size_t)J.n_slots * 12);
-    for (int sl = 0; sl < J.n_slots && n < cap; ++sl) {
-      if (!oval[sl]) continue;
-      const float px = oxy[2 * sl], py = oxy[2 * sl + 1];
-      const int xg = (int)(px / (float)min_px), yg = (int)(py / (float)min_px);
-      if (xg < 0 || xg >= J.cw || yg < 0 || yg >= J.ch) continue;
-      if (close[(size_t)yg * J.cw + xg] > 127) continue;
-      close[(size_t)yg * J.cw + xg] = 255;
-      pts[2 * n] = px;
-      pts[2 * n + 1] = py;
-      ids[n] = ++*currid;
-      ++n;
-    }
-  }
+  accept_corners(ctx, J, [&] { return n < cap; }, [&](float px, float py) {
+    pts[2 * n] = px;
+    pts[2 * n + 1] = py;
+    ids[n] = ++*currid;
+    ++n;
+  });
   *n_out = n;
 }
 
+void det_new_points(plv_ctx *ctx, const DetJob &J, std::vector<float> &out) {
+  out.clear();
+  accept_corners(ctx, J, [] { return true; }, [&](float px, float py) {
+    out.push_back(px);
+    out.push_back(py);
+  });
+}
+}  // namespace plv
+
+namespace {
 // a detection that was started ahead of time and has not been collected: wait for it so that its buffers can be reused
 void det_drop_pending(FrontState *s);
 }  // namespace
-}  // extern "C"
 namespace plv {
 // plv_ctx_synchronize: the side stream's work belongs to the frame that started it — wait for it too (the job stays collectable)
 int plv_front_quiesce(plv_ctx *ctx) {
@@ -942,9 +951,9 @@ int plv_perform_detection(plv_ctx *ctx, int which, const uint8_t *mask, float *p
   }
   const PyrDesc &pyr = s->pyr[which == PLV_PYR_LAST ? 1 - s->cur : s->cur];
   DetJob J;
-  TRY(det_pre(ctx, s, mask, pts, ids, n_in, J));
+  TRY(det_pre(ctx, s->W, s->H, mask, pts, ids, n_in, J));
   if (J.n_slots > 0) {
-    TRY(det_launch(ctx, s, pyr, mask, J, ctx->stream));
+    TRY(det_launch(ctx, *s, s->W, s->H, pyr, mask, J, ctx->stream));
     TRY(sync(ctx));
     TRY(det_check(J));
   }
@@ -966,7 +975,7 @@ int plv_perform_detection_ahead(plv_ctx *ctx, const uint8_t *mask, const float *
   if (s->fed < 1) return PLV_OK;
   det_drop_pending(s);
   DetJob &A = s->det_pending;
-  TRY(det_pre(ctx, s, mask, pts, ids, n_in, A));
+  TRY(det_pre(ctx, s->W, s->H, mask, pts, ids, n_in, A));
   A.fed = s->fed;
   A.n_in = n_in;
   A.has_mask = mask != nullptr;
@@ -980,7 +989,7 @@ int plv_perform_detection_ahead(plv_ctx *ctx, const uint8_t *mask, const float *
     PLV_HIP_CHECK(hipStreamCreateWithFlags(&s->det_stream, hipStreamNonBlocking));
     PLV_HIP_CHECK(hipEventCreateWithFlags(&s->det_done, hipEventDisableTiming));
   }
-  if (A.n_slots > 0) TRY(det_launch(ctx, s, s->pyr[s->cur], mask ? A.in_mask.data() : nullptr, A, s->det_stream));  // (the job's own copy of the mask)
+  if (A.n_slots > 0) TRY(det_launch(ctx, *s, s->W, s->H, s->pyr[s->cur], mask ? A.in_mask.data() : nullptr, A, s->det_stream));  // (the job's own copy of the mask)
   PLV_HIP_CHECK(hipEventRecord(s->det_done, s->det_stream));
   A.active = true;
   return PLV_OK;

@@ -314,19 +314,18 @@ typedef unsigned __attribute__((aligned(2))) lk_u32a2;  // a 32-bit LDS read at 
 // a division sequence — 73.8 us against 72.7 with the run-time window at workload C: the launch is bound by the dependent operations of
 // its slowest point's iterations, not by the set-up's instruction count.  Nor was a schedule that fetches every level's template tile up
 // front and the next level's search tile during the current level's iterations: same bits, 74.8 against 72.7 us, profiles/HISTORY.md.)
-__global__ void __launch_bounds__(64 * LK4_WAVES) lk_kernel(PyrDesc prev, PyrDesc cur, int n, const float *__restrict__ pts0,
-                                                            const float *__restrict__ pts1_init, float *__restrict__ pts1,
-                                                            uint8_t *__restrict__ status,
-                                                            int *__restrict__ iters_out, int win, int max_iters, float eps, CamK K,
-                                                            float *__restrict__ n0, float *__restrict__ n1) {
+// (The body is one workgroup's work on point `pt` of one job: lk_kernel runs it on the launch's only job, lk_pair_kernel on the job
+// the workgroup's index falls into.)
+__device__ __forceinline__ void lk_point(const PyrDesc &prev, const PyrDesc &cur, const int pt, const float *__restrict__ pts0,
+                                         const float *__restrict__ pts1_init, float *__restrict__ pts1, uint8_t *__restrict__ status,
+                                         int *__restrict__ iters_out, const int win, const int max_iters, const float eps, const CamK &K,
+                                         float *__restrict__ n0, float *__restrict__ n1) {
   __shared__ uint8_t ttile[LK_TT][LK_TT + 2];
   __shared__ short tdx[LK_TT - 2][LK_TT - 2], tdy[LK_TT - 2][LK_TT - 2];
   __shared__ uint8_t jtile[LK_JT][LK_JT];
   __shared__ unsigned short jt16[LK_JT][LK_JT];  // (lean iteration: the search tile as 16-bit pixels, two of them per 32-bit read)
   __shared__ int part[2][LK4_WAVES][2], part2[2][LK4_WAVES][2];
   __shared__ int partA[LK4_WAVES][3], partA2[LK4_WAVES][3];
-  const int pt = blockIdx.x;
-  if (pt >= n) return;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int W_BITS = 14;
   const float FLT_SCALE = 1.f / (1 << 20);
@@ -615,6 +614,28 @@ __global__ void __launch_bounds__(64 * LK4_WAVES) lk_kernel(PyrDesc prev, PyrDes
     dst[2 * pt] = xn;
     dst[2 * pt + 1] = yn;
   }
+}
+
+__global__ void __launch_bounds__(64 * LK4_WAVES) lk_kernel(PyrDesc prev, PyrDesc cur, int n, const float *__restrict__ pts0,
+                                                            const float *__restrict__ pts1_init, float *__restrict__ pts1,
+                                                            uint8_t *__restrict__ status,
+                                                            int *__restrict__ iters_out, int win, int max_iters, float eps, CamK K,
+                                                            float *__restrict__ n0, float *__restrict__ n1) {
+  const int pt = blockIdx.x;
+  if (pt >= n) return;
+  lk_point(prev, cur, pt, pts0, pts1_init, pts1, status, iters_out, win, max_iters, eps, K, n0, n1);
+}
+
+// The two temporal matchings of a stereo frame in one launch: workgroups [0, n of job 0) track the left camera's points over its
+// (last, current) pyramids, the rest the right camera's over its own, each undistorted with its own camera.  The job is chosen by
+// an index into the kernel's argument block (uniform for the workgroup): no select between two structs, nothing goes to scratch.
+__global__ void __launch_bounds__(64 * LK4_WAVES) lk_pair_kernel(LkPair P, int win, int max_iters, float eps) {
+  const int first = P.job[0].n;
+  const int c = (int)blockIdx.x >= first ? 1 : 0;
+  const int pt = (int)blockIdx.x - (c ? first : 0);
+  const LkJob &J = P.job[c];
+  if (pt >= J.n) return;
+  lk_point(J.prev, J.cur, pt, J.pts0, J.pts1_init, J.pts1, J.status, J.iters, win, max_iters, eps, J.K, J.n0, J.n1);
 }
 
 // ------------------------------------------------------------------------------------------ K6
@@ -1321,6 +1342,19 @@ int launch_lk(plv_ctx *ctx, const PyrDesc &prev, const PyrDesc &cur, int n, cons
   CamK none{};
   hipLaunchKernelGGL(lk_kernel, dim3(n), dim3(64 * LK4_WAVES), 0, ctx->stream, prev, cur, n, d_pts0, pts1_init ? pts1_init : d_pts1, d_pts1,
                      d_status, d_iters, win, max_iters, eps, K ? *K : none, K ? d_n0 : nullptr, K ? d_n1 : nullptr);
+  PLV_HIP_CHECK(hipGetLastError());
+  return PLV_OK;
+}
+
+int launch_lk_pair(plv_ctx *ctx, const LkPair &jobs, int win, int max_iters, float eps) {
+  if (win > LK_MAXWIN || win < 3 || (win & 1) == 0) {
+    set_last_error("lk: window %d unsupported (odd, <= %d)", win, LK_MAXWIN);
+    return PLV_E_CAPACITY;
+  }
+  const int n = jobs.job[0].n + jobs.job[1].n;
+  if (jobs.job[0].n < 0 || jobs.job[1].n < 0 || n < 1) return PLV_E_BADARG;
+  ProfScope ps(ctx->prof, "lk_pair_kernel", ctx->stream);
+  hipLaunchKernelGGL(lk_pair_kernel, dim3(n), dim3(64 * LK4_WAVES), 0, ctx->stream, jobs, win, max_iters, eps);
   PLV_HIP_CHECK(hipGetLastError());
   return PLV_OK;
 }

@@ -29,6 +29,22 @@ int launch_lk(plv_ctx *ctx, const PyrDesc &prev, const PyrDesc &cur, int n, cons
               uint8_t *d_status, int *d_iters, int win, int max_iters, float eps,
               const CamK *K = nullptr, float *d_n0 = nullptr, float *d_n1 = nullptr,
               const float *pts1_init = nullptr /* initial guesses when they are not in d_pts1 (e.g. pinned host memory) */);
+// one camera's share of launch_lk_pair: n points of `prev` tracked into `cur` (the arguments of launch_lk, K always given)
+struct LkJob {
+  PyrDesc prev, cur;
+  int n;
+  const float *pts0, *pts1_init;
+  float *pts1;
+  uint8_t *status;
+  int *iters;
+  CamK K;
+  float *n0, *n1;
+};
+struct LkPair {
+  LkJob job[2];
+};
+// both jobs in one launch (a job may be empty, not both): same values per point as launch_lk on each job
+int launch_lk_pair(plv_ctx *ctx, const LkPair &jobs, int win, int max_iters, float eps);
 int launch_undistort(plv_ctx *ctx, const CamK &K, int n, const float *d_uv, float *d_xy);
 int launch_undistort2(plv_ctx *ctx, const CamK &K, int n, const float *d_uv0, const float *d_uv1, float *d_xy0,
                       float *d_xy1);

@@ -276,6 +276,7 @@ void plv_ctx_destroy(plv_ctx *ctx) {
   (void)hipSetDevice(ctx->device);
   (void)plv::stream_sync(ctx->stream);
   plv_tracker_destroy(ctx);
+  plv_stereo_destroy(ctx);
   plv_line_tracker_destroy(ctx);
   plv_draw_destroy(ctx);
   plv_frontend_destroy(ctx);

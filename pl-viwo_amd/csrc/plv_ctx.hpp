@@ -564,4 +564,8 @@ struct plv_ctx {
 
   // ---- front-end (frontend_api.hip owns the object)
   void *fe_state = nullptr;
+  // ---- the stereo point tracker (stereo_api.hip owns the object), and which of the two trackers has taken an image on this
+  // context (PLV_TRACKER_*: they never share one)
+  void *stereo_state = nullptr;
+  int tracker_kind = 0;
 };

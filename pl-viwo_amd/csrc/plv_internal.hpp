@@ -68,6 +68,13 @@ void plv_tracker_run_deferred(void *ctx);
 // a copy of the mask of the last feed (W x H bytes; empty: that feed had none)
 void plv_tracker_mask_last(plv_ctx *ctx, std::vector<uint8_t> &out);
 
+// ---- stereo_api.hip
+// plv_ctx_destroy: the ctx's stereo tracker, its pyramids and its database
+void plv_stereo_destroy(plv_ctx *ctx);
+// plv_ctx::tracker_kind: PLV_OK unless the other tracker has taken an image on this context (then PLV_E_BADARG, with the error text)
+enum { PLV_TRACKER_NONE = 0, PLV_TRACKER_MONO = 1, PLV_TRACKER_STEREO = 2 };
+int plv_tracker_kind_check(plv_ctx *ctx, int kind, const char *who);
+
 // ---- draw_api.hip
 // plv_ctx_destroy: the buffers of the track image
 void plv_draw_destroy(plv_ctx *ctx);

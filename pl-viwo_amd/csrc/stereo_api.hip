@@ -1,0 +1,559 @@
+// stereo_api.hip — the stereo point tracker behind plv_stereo_* / plv_tracker_feed_stereo: host mirror of
+//   TrackKLT::feed_new_camera (two images) / feed_stereo   REF: open_vins/ov_core/src/track/TrackKLT.cpp:34-94, 202-393
+//   TrackKLT::perform_detection_stereo                     REF: TrackKLT.cpp:530-827
+//   FeatureDatabase with ov_core::Feature's per-camera observations
+// A second tracker beside the monocular one of tracker_api.hip: its own ping-pong pyramids per camera, last masks, last points, one
+// id counter, one database.  The bookkeeping is the reference's, on the host; the image and point work goes through the launchers
+// the monocular path uses (front_parts.hpp, frontend_kernels.hpp), with the two temporal matchings of a frame in one LK launch
+// (launch_lk_pair) and one wait.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <unordered_map>
+#include <vector>
+
+#include "camera_tracks.hpp"
+#include "encoding_kernels.hpp"
+#include "front_parts.hpp"
+#include "plv_internal.hpp"
+
+using namespace plv;
+
+namespace {
+
+struct StereoCam {
+  PyrDesc pyr[2];  // ping-pong pyramids
+  DevBuf pyr_mem[2];
+  DevBuf raw, hist, clahe_lut;
+  PinBuf img_pin;  // the host image on its way to the device (packed, in its encoding): the caller's buffer is free at return
+  DetScratch det;
+  DevBuf io, counts, models, info;  // the temporal matching: [pts0 | pts1 | n0 | n1 | iters | mask | status] and RANSAC's scratch
+  PinBuf flow_pin;                  // ... its host twin (points in, results out)
+  std::vector<float> pts_last;      // 2 per point
+  std::vector<uint64_t> ids_last;
+  std::vector<uint8_t> mask_last;   // W*H or empty
+  double K[8] = {};                 // camera 1 only: camera 0 is the context's (cfg.intrinsics, plv_ctx::cam_model)
+  int model = PLV_CAM_RADTAN;
+};
+
+struct StereoFeature {  // ov_core::Feature: the observations of one id, per camera
+  Track cam[2];
+};
+
+struct Stereo {
+  bool configured = false;
+  int W = 0, H = 0;
+  StereoCam cam[2];
+  int cur = 0;  // index of the current pyramids (both cameras are fed in step); last = 1 - cur
+  int fed = 0;
+  uint64_t currid = 0;  // REF: TrackBase::currid, shared by both cameras
+  std::unordered_map<uint64_t, StereoFeature> db;
+  DevBuf lr_dev;  // left-to-right LK of new left corners: [pts1 | status | iters]
+  PinBuf lr_pin;  // ... [pts0 | pts1 | status]
+  bool unsynced = false;  // kernels that read img_pin may still be on the stream
+  std::mutex mtx;
+};
+
+#define TRY(expr)                  \
+  do {                             \
+    int _rc = (expr);              \
+    if (_rc != PLV_OK) return _rc; \
+  } while (0)
+
+std::mutex g_mtx;
+Stereo *stereo_of(plv_ctx *ctx, bool create) {
+  std::lock_guard<std::mutex> lk(g_mtx);
+  if (!ctx->stereo_state && create) ctx->stereo_state = new Stereo();
+  return (Stereo *)ctx->stereo_state;
+}
+
+int sync(plv_ctx *ctx, Stereo *S) {
+  const unsigned long long stamp = ctx->gather_stamp;
+  PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
+  ctx->cov_host_synced = stamp;
+  ctx->prof.collect();
+  S->unsynced = false;
+  return PLV_OK;
+}
+
+CamK cam_k(plv_ctx *ctx, const Stereo *S, int c) {
+  CamK K;
+  for (int i = 0; i < 8; ++i) K.v[i] = c == 0 ? ctx->cfg.intrinsics[i] : S->cam[1].K[i];
+  K.model = c == 0 ? ctx->cam_model : S->cam[1].model;
+  return K;
+}
+
+bool bad_cam(int cam, const char *who) {
+  if (cam == 0 || cam == 1) return false;
+  set_last_error("%s: camera %d, a stereo pair has cameras 0 and 1", who, cam);
+  return true;
+}
+
+// one image of the pair: into the camera's pinned block, [conversion,] equalisation and pyramid into pyramid `next` — all enqueued
+int enqueue_image(plv_ctx *ctx, Stereo *S, int c, int next, const uint8_t *img, int stride, int encoding) {
+  StereoCam &C = S->cam[c];
+  const size_t row = (size_t)S->W * encoding_bpp(encoding);
+  TRY(C.img_pin.reserve(row * S->H));
+  uint8_t *pin = C.img_pin.as<uint8_t>();
+  if ((size_t)stride == row)
+    memcpy(pin, img, row * S->H);
+  else
+    for (int y = 0; y < S->H; ++y) memcpy(pin + (size_t)y * row, img + (size_t)y * stride, row);
+  S->unsynced = true;
+  if (encoding == PLV_ENC_MONO8)  // (the histogram kernel reads the pinned block and leaves the image in C.raw)
+    return front_feed_pyramid(ctx, S->W, S->H, C.raw.as<uint8_t>(), pin, C.pyr[next], C.hist, C.clahe_lut);
+  TRY(launch_grey_from_encoded(ctx, pin, true, C.raw.as<uint8_t>(), S->W, S->H, encoding));
+  return front_feed_pyramid(ctx, S->W, S->H, C.raw.as<uint8_t>(), nullptr, C.pyr[next], C.hist, C.clahe_lut);
+}
+
+// cv::calcOpticalFlowPyrLK(left pyramid, right pyramid of the same time, p, p, USE_INITIAL_FLOW)   REF :661-672
+int track_left_to_right(plv_ctx *ctx, Stereo *S, int which, const std::vector<float> &p0, std::vector<float> &p1, std::vector<uint8_t> &status) {
+  const size_t n = p0.size() / 2;
+  TRY(S->lr_pin.reserve(n * 17));
+  TRY(S->lr_dev.reserve(n * 13 + 16));
+  char *hp = S->lr_pin.as<char>(), *dp = S->lr_dev.as<char>();
+  memcpy(hp, p0.data(), n * 8);
+  float *d_p1 = (float *)dp;
+  int *d_it = (int *)(dp + n * 8);
+  uint8_t *d_st = (uint8_t *)(dp + n * 12);
+  // (both cameras have the context's width x height and one window: the two pyramids have the same level geometry, which is all
+  // lk_kernel asks of its (prev, cur) pair)
+  TRY(launch_lk(ctx, S->cam[0].pyr[which], S->cam[1].pyr[which], (int)n, (const float *)hp, d_p1, d_st, d_it, ctx->cfg.win_size,
+                ctx->cfg.lk_max_iters, ctx->cfg.lk_eps, nullptr, nullptr, nullptr, (const float *)hp));
+  PLV_HIP_CHECK(plv::memcpy_async(hp + n * 8, d_p1, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(hp + n * 16, d_st, n, hipMemcpyDeviceToHost, ctx->stream));
+  TRY(sync(ctx, S));
+  p1.assign((const float *)(hp + n * 8), (const float *)(hp + n * 8) + 2 * n);
+  status.assign((const uint8_t *)(hp + n * 16), (const uint8_t *)(hp + n * 16) + n);
+  return PLV_OK;
+}
+
+// the corners one camera's top-up extracts and keeps: FAST per cell + sub-pixel on level 0 of pyramid `which`, rejection near the
+// kept points (J); mask_dev is what the corners are tested against
+int extract_corners(plv_ctx *ctx, Stereo *S, int c, int which, const uint8_t *mask_dev, DetJob &J, std::vector<float> &fresh) {
+  fresh.clear();
+  if (J.n_slots <= 0) return PLV_OK;
+  TRY(det_launch(ctx, S->cam[c].det, S->W, S->H, S->cam[c].pyr[which], mask_dev, J, ctx->stream));
+  TRY(sync(ctx, S));
+  TRY(det_check(J));
+  det_new_points(ctx, J, fresh);
+  return PLV_OK;
+}
+
+// TrackKLT::perform_detection_stereo on pyramids `which` of both cameras; the four lists are pruned and topped up in place
+int detection_stereo(plv_ctx *ctx, Stereo *S, int which, const uint8_t *mask0, const uint8_t *mask1, std::vector<float> &pts0,
+                     std::vector<uint64_t> &ids0, std::vector<float> &pts1, std::vector<uint64_t> &ids1) {
+  plv::HostPhase ph("stereo feed: perform_detection_stereo");
+  const int W = S->W, H = S->H;
+  auto in_image = [W, H](float x, float y) { return !((int)x < 0 || (int)x >= W || (int)y < 0 || (int)y >= H); };
+  // ---- LEFT  :537-710
+  DetStereoRules left;
+  DetJob J0;
+  TRY(det_pre(ctx, W, H, mask0, pts0.data(), ids0.data(), (int)ids0.size(), J0, &left));
+  pts0 = J0.pts, ids0 = J0.ids;
+  std::vector<float> fresh, tracked;
+  std::vector<uint8_t> status;
+  TRY(extract_corners(ctx, S, 0, which, mask0, J0, fresh));
+  if (!fresh.empty()) {
+    TRY(track_left_to_right(ctx, S, which, fresh, tracked, status));
+    for (size_t i = 0; i < status.size(); ++i) {  // :675-708
+      const bool oob_left = !in_image(fresh[2 * i], fresh[2 * i + 1]), oob_right = !in_image(tracked[2 * i], tracked[2 * i + 1]);
+      if (oob_left) continue;  // (no id is spent)
+      const uint64_t id = ++S->currid;
+      pts0.insert(pts0.end(), {fresh[2 * i], fresh[2 * i + 1]});
+      ids0.push_back(id);
+      if (!oob_right && status[i] == 1) {
+        pts1.insert(pts1.end(), {tracked[2 * i], tracked[2 * i + 1]});
+        ids1.push_back(id);
+      }
+    }
+  }
+  // ---- RIGHT  :715-826.  A point whose id the left list holds survives an occupied cell (:754-759); the mask the corners are
+  // tested against is cloned from mask0 (:721) while the points and the grid cells are tested against mask1 (:762, :794).
+  DetStereoRules right;
+  right.spared = ids0.data(), right.n_spared = (int)ids0.size();
+  DetJob J1;
+  TRY(det_pre(ctx, W, H, mask1, pts1.data(), ids1.data(), (int)ids1.size(), J1, &right));
+  pts1 = J1.pts, ids1 = J1.ids;
+  TRY(extract_corners(ctx, S, 1, which, mask0, J1, fresh));
+  for (size_t i = 0; i < fresh.size() / 2; ++i) {
+    pts1.insert(pts1.end(), {fresh[2 * i], fresh[2 * i + 1]});
+    ids1.push_back(++S->currid);
+  }
+  return PLV_OK;
+}
+
+// what one camera's temporal matching works on and returns
+struct Matching {
+  int n = 0;
+  bool ran = false;                // n >= 10: LK + RANSAC on the device
+  std::vector<float> p_new, n_new;  // positions in the current image and their normalised coordinates (n_new: only where ran)
+  std::vector<uint8_t> mask;        // empty for n == 0, all zero for n < 10 (REF :836-852)
+};
+
+// both cameras' perform_matching (REF :260-268, :829-886): one LK launch over both point sets (each camera's own pyramids and
+// intrinsics), the two RANSACs behind it, one wait
+int matching_pair(plv_ctx *ctx, Stereo *S, const std::vector<float> *pts_old[2], Matching M[2]) {
+  plv::HostPhase ph("stereo feed: perform_matching x 2");
+  const int mi = std::max(1, ctx->cfg.ransac_max_iters);
+  LkPair jobs{};
+  for (int c = 0; c < 2; ++c) {
+    Matching &m = M[c];
+    m.n = (int)pts_old[c]->size() / 2;
+    m.p_new = *pts_old[c];  // (the initial flow; fewer than 10 points stay where they were)
+    m.mask.assign((size_t)m.n, 0);
+    m.ran = m.n >= 10;
+    jobs.job[c].n = 0;
+    if (!m.ran) continue;
+    StereoCam &C = S->cam[c];
+    const size_t nn = (size_t)m.n;
+    TRY(C.io.reserve(nn * 38));
+    TRY(C.flow_pin.reserve(nn * 38));
+    TRY(C.counts.reserve((size_t)mi * 3 * 4));
+    TRY(C.models.reserve((size_t)mi * 28 * 8));
+    TRY(C.info.reserve(16));
+    char *hp = C.flow_pin.as<char>(), *dp = C.io.as<char>();
+    memcpy(hp, pts_old[c]->data(), nn * 8);
+    memcpy(hp + nn * 8, pts_old[c]->data(), nn * 8);
+    LkJob &j = jobs.job[c];
+    j.prev = C.pyr[1 - S->cur], j.cur = C.pyr[S->cur], j.n = m.n;
+    j.pts0 = (const float *)hp, j.pts1_init = (const float *)(hp + nn * 8);  // (read from the pinned block, once)
+    j.pts1 = (float *)(dp + nn * 8), j.n0 = (float *)(dp + nn * 16), j.n1 = (float *)(dp + nn * 24);
+    j.iters = (int *)(dp + nn * 32), j.status = (uint8_t *)(dp + nn * 37);
+    j.K = cam_k(ctx, S, c);
+  }
+  if (!M[0].ran && !M[1].ran) return PLV_OK;
+  TRY(launch_lk_pair(ctx, jobs, ctx->cfg.win_size, ctx->cfg.lk_max_iters, ctx->cfg.lk_eps));
+  for (int c = 0; c < 2; ++c) {
+    if (!M[c].ran) continue;
+    StereoCam &C = S->cam[c];
+    const LkJob &j = jobs.job[c];
+    const size_t nn = (size_t)M[c].n, o_p1 = nn * 8, o_mk = nn * 36;
+    char *hp = C.flow_pin.as<char>(), *dp = C.io.as<char>();
+    // each RANSAC is a findFundamentalMat call of its own in the reference: the seed of a fresh call, this camera's focal length
+    const double fmax = std::max(j.K.v[0], j.K.v[1]);
+    bool mirrored = false;
+    TRY(launch_ransac(ctx, j.n0, j.n1, M[c].n, ctx->cfg.ransac_thr_px / fmax, ctx->cfg.ransac_conf, mi, 0u, C.counts.as<int>(), j.status,
+                      (uint8_t *)(dp + o_mk), C.info.as<int>(), C.models.as<double>(), dp + o_p1, hp + o_p1, o_mk - o_p1, (uint8_t *)(hp + o_mk),
+                      &mirrored));
+    if (!mirrored) PLV_HIP_CHECK(plv::memcpy_async(hp + o_p1, dp + o_p1, nn * 37 - o_p1, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  {
+    plv::NsScope ns_wait(plv::counters().flow_wait_ns);
+    TRY(sync(ctx, S));
+  }
+  for (int c = 0; c < 2; ++c) {
+    if (!M[c].ran) continue;
+    const size_t nn = (size_t)M[c].n;
+    const char *hp = S->cam[c].flow_pin.as<char>();
+    M[c].p_new.assign((const float *)(hp + nn * 8), (const float *)(hp + nn * 8) + 2 * nn);
+    M[c].n_new.assign((const float *)(hp + nn * 24), (const float *)(hp + nn * 24) + 2 * nn);
+    M[c].mask.assign((const uint8_t *)(hp + nn * 36), (const uint8_t *)(hp + nn * 36) + nn);
+    const int *it = (const int *)(hp + nn * 32);
+    unsigned long long t = 0;
+    for (size_t i = 0; i < nn; ++i) t += (unsigned long long)it[i];
+    plv::counters().lk_iters += t;
+  }
+  return PLV_OK;
+}
+
+// the rest of TrackKLT::feed_stereo once both images are equalised and their pyramids built
+int feed_fed(plv_ctx *ctx, Stereo *S, double timestamp, const uint8_t *mask_l, const uint8_t *mask_r) {
+  const int W = S->W, H = S->H;
+  StereoCam &L = S->cam[0], &R = S->cam[1];
+  auto move_forward = [&](std::vector<float> &pl, std::vector<uint64_t> &il, std::vector<float> &pr, std::vector<uint64_t> &ir) {
+    L.pts_last.swap(pl), L.ids_last.swap(il), R.pts_last.swap(pr), R.ids_last.swap(ir);
+    const uint8_t *m[2] = {mask_l, mask_r};
+    for (int c = 0; c < 2; ++c)
+      if (m[c])
+        S->cam[c].mask_last.assign(m[c], m[c] + (size_t)W * H);
+      else
+        S->cam[c].mask_last.clear();
+    return S->unsynced ? sync(ctx, S) : PLV_OK;  // (the pinned image blocks are written again by the next pair)
+  };
+  std::vector<float> pl, pr;
+  std::vector<uint64_t> il, ir;
+  if (L.pts_last.empty() && R.pts_last.empty()) {  // :221-240 first pair / lost everything: detect on the current pair
+    TRY(detection_stereo(ctx, S, S->cur, mask_l, mask_r, pl, il, pr, ir));
+    return move_forward(pl, il, pr, ir);
+  }
+  // :244-251 top-up on the LAST pair, with the last masks
+  pl = L.pts_last, il = L.ids_last, pr = R.pts_last, ir = R.ids_last;
+  TRY(detection_stereo(ctx, S, 1 - S->cur, L.mask_last.empty() ? nullptr : L.mask_last.data(),
+                       R.mask_last.empty() ? nullptr : R.mask_last.data(), pl, il, pr, ir));
+  // :254-268 temporal KLT per camera, the old positions as the initial flow
+  Matching M[2];
+  const std::vector<float> *old[2] = {&pl, &pr};
+  TRY(matching_pair(ctx, S, old, M));
+  std::vector<float> good_l, good_r;
+  std::vector<uint64_t> gid_l, gid_r;
+  if (M[0].mask.empty() && M[1].mask.empty())  // :285-299 nothing to match in either camera: reset
+    return move_forward(good_l, gid_l, good_r, gid_r);
+  plv::HostPhase ph_db("stereo feed: pairing + database update");
+  std::vector<int> src_l, src_r;  // where in the matched lists a good point came from (its normalised coordinates)
+  // :306-338 left points, with their partner in the right list when both were tracked
+  for (int i = 0; i < M[0].n; ++i) {
+    const float x = M[0].p_new[2 * i], y = M[0].p_new[2 * i + 1];
+    if (x < 0 || y < 0 || (int)x > W || (int)y > H) continue;  // (:308-309: `>`, unlike the right side's `>=`)
+    const auto it = std::find(ir.begin(), ir.end(), il[i]);
+    const int k = it == ir.end() ? -1 : (int)(it - ir.begin());
+    if (M[0].mask[i] && k >= 0 && M[1].mask[k]) {
+      const float xr = M[1].p_new[2 * k], yr = M[1].p_new[2 * k + 1];
+      if (xr < 0 || yr < 0 || (int)xr >= W || (int)yr >= H) continue;  // :325-327 dropped from both lists
+      good_l.insert(good_l.end(), {x, y}), gid_l.push_back(il[i]), src_l.push_back(i);
+      good_r.insert(good_r.end(), {xr, yr}), gid_r.push_back(ir[k]), src_r.push_back(k);
+    } else if (M[0].mask[i]) {
+      good_l.insert(good_l.end(), {x, y}), gid_l.push_back(il[i]), src_l.push_back(i);
+    }
+  }
+  // :341-354 right points that were not added with their partner
+  for (int i = 0; i < M[1].n; ++i) {
+    const float x = M[1].p_new[2 * i], y = M[1].p_new[2 * i + 1];
+    if (x < 0 || y < 0 || (int)x >= W || (int)y >= H) continue;
+    if (!M[1].mask[i] || std::find(gid_r.begin(), gid_r.end(), ir[i]) != gid_r.end()) continue;
+    good_r.insert(good_r.end(), {x, y}), gid_r.push_back(ir[i]), src_r.push_back(i);
+  }
+  // :357-366 database: the left list under camera 0, then the right list under camera 1 (a good point passed its camera's matching,
+  // whose launch undistorted it with that camera's intrinsics: undistort_cv of the same point)
+  const std::vector<float> *good[2] = {&good_l, &good_r};
+  const std::vector<uint64_t> *gid[2] = {&gid_l, &gid_r};
+  const std::vector<int> *src[2] = {&src_l, &src_r};
+  for (int c = 0; c < 2; ++c)
+    for (size_t i = 0; i < gid[c]->size(); ++i) {
+      Track &tr = S->db[(*gid[c])[i]].cam[c];
+      const int k = (*src[c])[i];
+      tr.t.push_back(timestamp);
+      tr.uv.push_back((*good[c])[2 * i]), tr.uv.push_back((*good[c])[2 * i + 1]);
+      tr.uvn.push_back(M[c].n_new[2 * k]), tr.uvn.push_back(M[c].n_new[2 * k + 1]);
+    }
+  return move_forward(good_l, gid_l, good_r, gid_r);  // :369-381
+}
+
+// a configured stereo tracker, or null with the error text
+Stereo *configured(plv_ctx *ctx, const char *who) {
+  Stereo *S = stereo_of(ctx, false);
+  if (S && S->configured) return S;
+  set_last_error("%s: no stereo pair on this context (plv_stereo_configure comes first)", who);
+  return nullptr;
+}
+
+}  // namespace
+
+namespace plv {
+void plv_stereo_destroy(plv_ctx *ctx) {
+  Stereo *S = (Stereo *)ctx->stereo_state;
+  if (!S) return;
+  for (StereoCam &C : S->cam) {
+    DevBuf *bufs[] = {&C.pyr_mem[0], &C.pyr_mem[1], &C.raw, &C.hist, &C.clahe_lut, &C.io, &C.counts, &C.models, &C.info};
+    for (auto *b : bufs) b->release();
+    C.img_pin.release();
+    C.flow_pin.release();
+    C.det.release_detection();
+  }
+  S->lr_dev.release();
+  S->lr_pin.release();
+  delete S;
+  ctx->stereo_state = nullptr;
+}
+
+int plv_tracker_kind_check(plv_ctx *ctx, int kind, const char *who) {
+  if (ctx->tracker_kind == PLV_TRACKER_NONE || ctx->tracker_kind == kind) return PLV_OK;
+  set_last_error("%s: this context has been fed through the %s tracker; the two trackers do not share a context", who,
+                 ctx->tracker_kind == PLV_TRACKER_STEREO ? "stereo" : "monocular");
+  return PLV_E_BADARG;
+}
+}  // namespace plv
+
+extern "C" {
+
+int plv_stereo_configure(plv_ctx *ctx, const double *K8_right, int model_right) {
+  if (!ctx || !K8_right || (model_right != PLV_CAM_RADTAN && model_right != PLV_CAM_EQUIDISTANT)) {
+    set_last_error("plv_stereo_configure: no context, no intrinsics or camera model %d unknown", model_right);
+    return PLV_E_BADARG;
+  }
+  for (int i = 0; i < 8; ++i)
+    if (!std::isfinite(K8_right[i])) {
+      set_last_error("plv_stereo_configure: intrinsic value %d of the right camera is not finite", i);
+      return PLV_E_BADARG;
+    }
+  const int W = ctx->cfg.width, H = ctx->cfg.height;
+  if (W < 16 || H < 16) {
+    set_last_error("plv_stereo_configure: image %dx%d too small", W, H);
+    return PLV_E_BADARG;
+  }
+  (void)hipSetDevice(ctx->device);
+  Stereo *S = stereo_of(ctx, true);
+  std::lock_guard<std::mutex> lk(S->mtx);
+  if (!S->configured) {
+    S->W = W, S->H = H;
+    for (StereoCam &C : S->cam) {
+      for (int i = 0; i < 2; ++i) {
+        const int bytes = level_geometry(W, H, ctx->cfg.win_size, ctx->cfg.pyr_levels, C.pyr[i]);
+        TRY(C.pyr_mem[i].reserve((size_t)bytes));
+        C.pyr[i].base = C.pyr_mem[i].as<uint8_t>();
+      }
+      TRY(C.hist.reserve(257 * sizeof(unsigned)));  // 256 bins + arrival counter; the pyramid launch leaves it zero for the next image
+      PLV_HIP_CHECK(hipMemsetAsync(C.hist.p, 0, 257 * sizeof(unsigned), ctx->stream));
+      TRY(C.raw.reserve((size_t)W * H));
+      TRY(C.img_pin.reserve((size_t)W * H));
+    }
+  }
+  std::copy(K8_right, K8_right + 8, S->cam[1].K);
+  S->cam[1].model = model_right;
+  S->configured = true;
+  return PLV_OK;
+}
+
+int plv_stereo_set_intrinsics(plv_ctx *ctx, int cam, const double *K8) {
+  if (!ctx || !K8) {
+    set_last_error("plv_stereo_set_intrinsics: no context or no intrinsics");
+    return PLV_E_BADARG;
+  }
+  if (bad_cam(cam, "plv_stereo_set_intrinsics")) return PLV_E_BADARG;
+  Stereo *S = configured(ctx, "plv_stereo_set_intrinsics");
+  if (!S) return PLV_E_BADARG;
+  for (int i = 0; i < 8; ++i)
+    if (!std::isfinite(K8[i])) {
+      set_last_error("plv_stereo_set_intrinsics: intrinsic value %d is not finite", i);
+      return PLV_E_BADARG;
+    }
+  if (cam == 0) return plv_set_camera_intrinsics(ctx, K8);
+  std::lock_guard<std::mutex> lk(S->mtx);
+  std::copy(K8, K8 + 8, S->cam[1].K);
+  return PLV_OK;
+}
+
+int plv_tracker_feed_stereo(plv_ctx *ctx, double timestamp, const uint8_t *left, int stride_left, const uint8_t *right, int stride_right,
+                            int encoding, const uint8_t *mask_left, const uint8_t *mask_right) {
+  if (!ctx) {
+    set_last_error("plv_tracker_feed_stereo: no context");
+    return PLV_E_BADARG;
+  }
+  // every refusal comes before anything is enqueued or written
+  TRY(plv_tracker_kind_check(ctx, PLV_TRACKER_STEREO, "plv_tracker_feed_stereo"));
+  Stereo *S = configured(ctx, "plv_tracker_feed_stereo");
+  if (!S) return PLV_E_BADARG;
+  TRY(check_encoded("plv_tracker_feed_stereo (left)", left, stride_left, encoding, S->W));
+  TRY(check_encoded("plv_tracker_feed_stereo (right)", right, stride_right, encoding, S->W));
+  std::lock_guard<std::mutex> lk(S->mtx);  // REF: mtx_feeds of both cameras, TrackKLT.cpp:207-208
+  {
+    PyrDesc want{};
+    (void)level_geometry(S->W, S->H, ctx->cfg.win_size, ctx->cfg.pyr_levels, want);
+    if (want.levels != S->cam[0].pyr[0].levels) {
+      set_last_error("plv_tracker_feed_stereo: a %d x %d window gives %d pyramid levels, the stereo pyramids have %d", ctx->cfg.win_size,
+                     ctx->cfg.win_size, want.levels, S->cam[0].pyr[0].levels);
+      return PLV_E_BADARG;
+    }
+    if (ctx->cfg.histogram_method == PLV_HIST_CLAHE && (S->W % 8 != 0 || S->H % 8 != 0)) {
+      set_last_error("plv_tracker_feed_stereo: CLAHE needs a width and height divisible into 8 x 8 tiles, not %dx%d", S->W, S->H);
+      return PLV_E_BADARG;
+    }
+    if (ctx->cfg.histogram_method != PLV_HIST_HISTOGRAM && ctx->cfg.histogram_method != PLV_HIST_NONE && ctx->cfg.histogram_method != PLV_HIST_CLAHE) {
+      set_last_error("plv_tracker_feed_stereo: unknown histogram method %d", ctx->cfg.histogram_method);
+      return PLV_E_BADARG;
+    }
+  }
+  (void)hipSetDevice(ctx->device);
+  ctx->tracker_kind = PLV_TRACKER_STEREO;
+  // :50-76 equalisation and pyramid per image, back to back on the stream (no wait between them)
+  const int next = S->fed == 0 ? S->cur : 1 - S->cur;
+  {
+    plv::HostPhase ph("stereo feed: two images enqueued");
+    TRY(enqueue_image(ctx, S, 0, next, left, stride_left, encoding));
+    TRY(enqueue_image(ctx, S, 1, next, right, stride_right, encoding));
+  }
+  S->cur = next;
+  S->fed++;
+  return feed_fed(ctx, S, timestamp, mask_left, mask_right);
+}
+
+// TrackBase::get_last_obs / get_last_ids of one camera
+int plv_stereo_last(plv_ctx *ctx, int cam, float *pts, uint64_t *ids, int cap, int *n) {
+  if (!ctx || !n) {
+    set_last_error("plv_stereo_last: no context or no count");
+    return PLV_E_BADARG;
+  }
+  if (bad_cam(cam, "plv_stereo_last")) return PLV_E_BADARG;
+  Stereo *S = configured(ctx, "plv_stereo_last");
+  if (!S) return PLV_E_BADARG;
+  std::lock_guard<std::mutex> lk(S->mtx);
+  const StereoCam &C = S->cam[cam];
+  *n = (int)C.ids_last.size();
+  if (*n > cap) return PLV_E_CAPACITY;
+  if (pts) std::copy(C.pts_last.begin(), C.pts_last.end(), pts);
+  if (ids) std::copy(C.ids_last.begin(), C.ids_last.end(), ids);
+  return PLV_OK;
+}
+
+int plv_stereo_db_size(plv_ctx *ctx) {
+  Stereo *S = ctx ? stereo_of(ctx, false) : nullptr;
+  if (!S) return 0;
+  std::lock_guard<std::mutex> lk(S->mtx);
+  return (int)S->db.size();
+}
+
+int plv_stereo_db_ids(plv_ctx *ctx, uint64_t *ids, int cap, int *n) {
+  if (!ctx || !n) return PLV_E_BADARG;
+  Stereo *S = configured(ctx, "plv_stereo_db_ids");
+  if (!S) return PLV_E_BADARG;
+  std::lock_guard<std::mutex> lk(S->mtx);
+  std::vector<uint64_t> out;
+  out.reserve(S->db.size());
+  for (const auto &kv : S->db) out.push_back(kv.first);
+  std::sort(out.begin(), out.end());
+  *n = (int)out.size();
+  if (*n > cap) return PLV_E_CAPACITY;
+  if (ids) std::copy(out.begin(), out.end(), ids);
+  return PLV_OK;
+}
+
+int plv_stereo_db_export_tracks(plv_ctx *ctx, const uint64_t *ids, int n, int cam, int *obs_ptr, double *obs_time, float *obs_uv,
+                                float *obs_uvn, int cap_obs) {
+  if (!ctx || n < 0 || (n > 0 && !ids) || !obs_ptr) return PLV_E_BADARG;
+  if (bad_cam(cam, "plv_stereo_db_export_tracks")) return PLV_E_BADARG;
+  Stereo *S = configured(ctx, "plv_stereo_db_export_tracks");
+  if (!S) return PLV_E_BADARG;
+  std::lock_guard<std::mutex> lk(S->mtx);
+  int at = 0;
+  obs_ptr[0] = 0;
+  for (int f = 0; f < n; ++f) {
+    const auto it = S->db.find(ids[f]);
+    if (it != S->db.end()) {
+      const Track &tr = it->second.cam[cam];
+      const int m = (int)tr.t.size();
+      if (at + m > cap_obs) return PLV_E_CAPACITY;
+      if (obs_time) std::copy(tr.t.begin(), tr.t.end(), obs_time + at);
+      if (obs_uv) std::copy(tr.uv.begin(), tr.uv.end(), obs_uv + 2 * (size_t)at);
+      if (obs_uvn) std::copy(tr.uvn.begin(), tr.uvn.end(), obs_uvn + 2 * (size_t)at);
+      at += m;
+    }
+    obs_ptr[f + 1] = at;
+  }
+  return PLV_OK;
+}
+
+// FeatureDatabase::cleanup_measurements(t) (REF: FeatureDatabase.cpp:286-323): Feature::clean_older_measurements over every
+// camera, the feature erased when nothing is left
+int plv_stereo_db_cleanup_measurements(plv_ctx *ctx, double t) {
+  if (!ctx) return PLV_E_BADARG;
+  Stereo *S = configured(ctx, "plv_stereo_db_cleanup_measurements");
+  if (!S) return PLV_E_BADARG;
+  std::lock_guard<std::mutex> lk(S->mtx);
+  for (auto it = S->db.begin(); it != S->db.end();) {
+    const size_t left = drop_before(it->second.cam[0], t) + drop_before(it->second.cam[1], t);
+    it = left == 0 ? S->db.erase(it) : std::next(it);
+  }
+  return PLV_OK;
+}
+
+int plv_stereo_db_remove(plv_ctx *ctx, const uint64_t *ids, int n) {
+  if (!ctx || n < 0 || (n > 0 && !ids)) return PLV_E_BADARG;
+  Stereo *S = configured(ctx, "plv_stereo_db_remove");
+  if (!S) return PLV_E_BADARG;
+  std::lock_guard<std::mutex> lk(S->mtx);
+  for (int i = 0; i < n; ++i) S->db.erase(ids[i]);
+  return PLV_OK;
+}
+
+}  // extern "C"

@@ -132,6 +132,7 @@ static int feed_with_early_edges(plv_ctx *ctx, const std::function<int()> &feed)
 
 int plv_tracker_feed(plv_ctx *ctx, double timestamp, const uint8_t *img, int stride, const uint8_t *mask) {
   if (!ctx || !img) return PLV_E_BADARG;
+  TRY(plv_tracker_kind_check(ctx, PLV_TRACKER_MONO, "plv_tracker_feed"));
   Tracker *T = trk(ctx);
   std::lock_guard<std::mutex> lk(T->mtx);  // REF: mtx_feeds.at(cam_id), TrackKLT.cpp:54,100
   // :59 equalizeHist, :71 buildOpticalFlowPyramid (enqueued; the feed below waits for its flow)
@@ -141,6 +142,7 @@ int plv_tracker_feed(plv_ctx *ctx, double timestamp, const uint8_t *img, int str
 
 int plv_tracker_feed_staged(plv_ctx *ctx, double timestamp, int slot, const uint8_t *mask) {
   if (!ctx) return PLV_E_BADARG;
+  TRY(plv_tracker_kind_check(ctx, PLV_TRACKER_MONO, "plv_tracker_feed_staged"));
   Tracker *T = trk(ctx);
   std::lock_guard<std::mutex> lk(T->mtx);
   TRY(feed_with_early_edges(ctx, [&] { return plv_feed_staged(ctx, slot); }));  // the image is already in HBM (plv_image_stage)
@@ -152,6 +154,7 @@ int plv_tracker_feed_encoded(plv_ctx *ctx, double timestamp, const uint8_t *data
     set_last_error("plv_tracker_feed_encoded: no context or null image");
     return PLV_E_BADARG;
   }
+  TRY(plv_tracker_kind_check(ctx, PLV_TRACKER_MONO, "plv_tracker_feed_encoded"));
   Tracker *T = trk(ctx);
   std::lock_guard<std::mutex> lk(T->mtx);
   // the conversion in front of the feed, on the same stream (a refused argument returns before anything is enqueued)
@@ -162,6 +165,7 @@ int plv_tracker_feed_encoded(plv_ctx *ctx, double timestamp, const uint8_t *data
 int plv_tracker_feed_downsampled(plv_ctx *ctx, double timestamp, const uint8_t *img, int stride, int src_w, int src_h,
                                  const uint8_t *mask, int mask_stride) {
   if (!ctx || !img) return PLV_E_BADARG;
+  TRY(plv_tracker_kind_check(ctx, PLV_TRACKER_MONO, "plv_tracker_feed_downsampled"));
   Tracker *T = trk(ctx);
   std::lock_guard<std::mutex> lk(T->mtx);
   const int W = ctx->cfg.width, H = ctx->cfg.height;
@@ -353,6 +357,7 @@ static void spec_submit(plv_ctx *ctx, Tracker *T, double t_now, int n_flow, cons
 // the rest of TrackKLT::feed_monocular once the image is equalised and its pyramid built
 static int tracker_feed_fed(plv_ctx *ctx, Tracker *T, double timestamp, const uint8_t *mask) {
   const int W = ctx->cfg.width, H = ctx->cfg.height;
+  ctx->tracker_kind = PLV_TRACKER_MONO;  // (the image was taken: from here on the context is the monocular tracker's)
   ++T->feed_seq;
   if (T->frame_t.empty() || timestamp > T->frame_t.back()) {
     T->frame_t.push_back(timestamp);
@@ -1276,6 +1281,7 @@ int plv_camera_try_update(plv_ctx *ctx, const plv_state_view *st, plv_try_update
 // UpdaterCamera::feed_measurement followed by try_update (REF: UpdaterCamera.cpp:77-116, 139-195), one call per camera frame.
 int plv_camera_frame(plv_ctx *ctx, const plv_state_view *st, plv_camera_frame_io *io) {
   if (!ctx || !st || !io || (io->slot < 0 && !io->img)) return PLV_E_BADARG;
+  TRY(plv_tracker_kind_check(ctx, PLV_TRACKER_MONO, "plv_camera_frame"));
   // update arguments plv_camera_try_update would refuse: the frame is fed as one without an update, and the call returns the refusal
   // (nothing enqueued for an update that cannot be used)
   const int rc_args = io->update ? try_update_args(ctx, st, io->update) : PLV_OK;

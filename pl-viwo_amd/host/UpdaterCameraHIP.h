@@ -26,6 +26,10 @@ public:
   // reference's own constructor arguments (:41,44; TrackKLT_HIP creates and owns the plv_ctx)
   explicit UpdaterCameraHIP(std::shared_ptr<State> state_) : state(state_), ctx(nullptr), max_obs(24) {
     const std::shared_ptr<OptionsCamera> op = state->op->cam;
+    if (op->use_stereo) {  // the updates on the device read the monocular track store; a stereo pair is tracked by TrackKLT_HIP alone
+      PRINT_ERROR(RED "[UpdaterCameraHIP]: the update on the device takes one camera (use_stereo: false)\n" RESET);
+      std::exit(EXIT_FAILURE);
+    }
     trackFEATS = std::make_shared<ov_core::TrackKLT_HIP>(state->cam_intrinsic_model, op->n_pts, 0, op->use_stereo, op->histogram, op->fast, op->grid_x,
                                                          op->grid_y, op->min_px_dist);
     trackFEATS->mirror_database(false);  // (this class reads the library's track store)
