@@ -5,6 +5,8 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <iterator>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -138,6 +140,74 @@ template <class TrackT, class Keep> size_t trim_track(TrackT &tr, Keep keep) {
 // cleanup_measurements on one track (REF FeatureDatabase.cpp:286-323): observations older than t go; returns how many stay
 template <class TrackT> size_t drop_before(TrackT &tr, double t) {
   return trim_track(tr, [&tr, t](size_t i) { return !(tr.t[i] < t); });
+}
+
+// ---- what the point, stereo and line databases answer their accessors with (plv_db_* / plv_stereo_db_* / plv_line_db_*): the entry
+// points keep their own argument checks and locks.  A database is any map from id to feature; where a feature is not itself a
+// track (the stereo pair's two cameras), the caller says how to get at one.
+
+// the ids in ascending order (the reference iterates an unordered_map), as many as `cap` holds: *n is set either way
+template <class Map> int export_sorted_ids(const Map &db, uint64_t *ids, int cap, int *n) {
+  std::vector<uint64_t> out;
+  out.reserve(db.size());
+  for (const auto &kv : db) out.push_back(kv.first);
+  std::sort(out.begin(), out.end());
+  *n = (int)out.size();
+  if (*n > cap) return PLV_E_CAPACITY;
+  if (ids) std::copy(out.begin(), out.end(), ids);
+  return PLV_OK;
+}
+
+// CSR export of the tracks of ids [n] in the layout of plv_tracks / plv_line_tracks: obs_ptr [n + 1], and (each may be null) times,
+// uv and uvn with TrackT::W floats per observation.  track_of(id): the track or null — a missing id gets no observations.  A
+// track that does not fit cap_obs ends the export with PLV_E_CAPACITY before anything of it is written (obs_ptr of it neither).
+// extra(f, track or null) runs per id behind the observations and may end the export with a code of its own.
+template <class TrackOf, class Extra>
+int export_tracks(const uint64_t *ids, int n, TrackOf track_of, int *obs_ptr, double *obs_time, float *obs_uv, float *obs_uvn, int cap_obs,
+                  Extra extra) {
+  int at = 0;
+  obs_ptr[0] = 0;
+  for (int f = 0; f < n; ++f) {
+    const auto *tr = track_of(ids[f]);
+    if (tr) {
+      constexpr size_t W = std::remove_pointer_t<decltype(tr)>::W;
+      const int m = (int)tr->t.size();
+      if (at + m > cap_obs) return PLV_E_CAPACITY;
+      if (obs_time) std::copy(tr->t.begin(), tr->t.end(), obs_time + at);
+      if (obs_uv) std::copy(tr->uv.begin(), tr->uv.end(), obs_uv + W * (size_t)at);
+      if (obs_uvn) std::copy(tr->uvn.begin(), tr->uvn.end(), obs_uvn + W * (size_t)at);
+      at += m;
+    }
+    const int rc = extra(f, tr);
+    if (rc != PLV_OK) return rc;
+    obs_ptr[f + 1] = at;
+  }
+  return PLV_OK;
+}
+template <class TrackOf>
+int export_tracks(const uint64_t *ids, int n, TrackOf track_of, int *obs_ptr, double *obs_time, float *obs_uv, float *obs_uvn, int cap_obs) {
+  return export_tracks(ids, n, track_of, obs_ptr, obs_time, obs_uv, obs_uvn, cap_obs, [](int, const void *) { return (int)PLV_OK; });
+}
+// ... of a database whose features are tracks
+template <class TrackT> auto track_in(const TrackMap<TrackT> &db) {
+  return [&db](uint64_t id) -> const TrackT * {
+    const auto it = db.find(id);
+    return it == db.end() ? nullptr : &it->second;
+  };
+}
+
+// the features of ids [n] leave the database (an id it does not hold: nothing happens)
+template <class Map> void erase_ids(Map &db, const uint64_t *ids, int n) {
+  for (int i = 0; i < n; ++i) db.erase(ids[i]);
+}
+
+// FeatureDatabase::cleanup_measurements(t) (REF FeatureDatabase.cpp:286-323): observations older than t go, a feature with none
+// left is erased.  drop(feature, t): how many the feature keeps, over all its cameras.
+template <class Map, class Drop> void cleanup_measurements(Map &db, double t, Drop drop) {
+  for (auto it = db.begin(); it != db.end();) it = drop(it->second, t) == 0 ? db.erase(it) : std::next(it);
+}
+template <class TrackT> void cleanup_measurements(TrackMap<TrackT> &db, double t) {
+  cleanup_measurements(db, t, [](TrackT &tr, double t_) { return drop_before(tr, t_); });
 }
 
 // remove_unusable_measurements on one track (REF CamHelper.cpp:740-775): with tm = time + dt, observations with tm > t_new go back

@@ -38,12 +38,6 @@ DrawState *ds(plv_ctx *ctx) {
   return s;
 }
 
-#define TRY(expr)                  \
-  do {                             \
-    int _rc = (expr);              \
-    if (_rc != PLV_OK) return _rc; \
-  } while (0)
-
 constexpr int COORD_MAX = 1 << 24;        // plv_draw_primitives refuses anything beyond
 constexpr float FLOAT_COORD_MAX = 1048576.f;  // 2^20: a layer drops the primitive
 

@@ -14,20 +14,14 @@ using namespace plv;
 
 namespace {
 
-struct FrontState : DetScratch {
-  int W = 0, H = 0;
-  PyrDesc pyr[2];          // ping-pong pyramids
-  DevBuf pyr_mem[2];
-  int cur = 0;             // index of the current pyramid; last = 1 - cur
-  int fed = 0;             // number of images fed so far (last is valid when fed >= 2)
+struct FrontState : CamFront {  // the context's one camera, and what only the monocular path has
   int pending_n = -1;      // plv_perform_matching_launch .. _wait
   bool pending_ran = false;
-  DevBuf raw;              // incoming raw image (packed)
   DevBuf slots[8];
-  DevBuf hist, clahe_lut;
   DevBuf ds_src, ds_dst;   // full-resolution staging of plv_downsample / plv_feed_image_downsampled
   // per-call point buffers
-  DevBuf pts0, pts1, n0, n1, status, iters, mask, counts, info, io, models;
+  DevBuf pts0, pts1, n0, n1, status, iters, mask, io;
+  RansacScratch ransac;
   PinBuf img_pin[6];       // host images on their way to the device (plv_feed_image_enqueue): the caller's buffer is free at return
   int img_pin_next = 0;
   // images in their sensor encoding (plv_image_stage_encoded ...): nothing here is allocated before the first of them arrives
@@ -41,12 +35,6 @@ struct FrontState : DetScratch {
   unsigned long long flow_done_stamp = 0;  // plv_ctx::gather_stamp when flow_done was recorded
   hipEvent_t flow_done = nullptr;  // behind the result copy of plv_perform_matching_launch: the wait does not cover what is enqueued after it
 };
-
-#define TRY(expr)                  \
-  do {                             \
-    int _rc = (expr);              \
-    if (_rc != PLV_OK) return _rc; \
-  } while (0)
 
 }  // namespace
 namespace plv {
@@ -77,13 +65,10 @@ extern "C" int plv_set_lk_window(plv_ctx *ctx, int win) {
   }
   if (ctx->fe_state) {
     FrontState *s = (FrontState *)ctx->fe_state;
-    if (s->pyr_mem[0].p) {
-      PyrDesc want{};
-      (void)level_geometry(s->W, s->H, win, ctx->cfg.pyr_levels, want);
-      if (want.levels != s->pyr[0].levels) {
-        set_last_error("plv_set_lk_window: a %d x %d window gives %d pyramid levels, the pyramids of this context have %d", win, win, want.levels, s->pyr[0].levels);
-        return PLV_E_BADARG;
-      }
+    if (s->prepared() && s->levels_for(ctx, win) != s->pyr[0].levels) {
+      set_last_error("plv_set_lk_window: a %d x %d window gives %d pyramid levels, the pyramids of this context have %d", win, win,
+                     s->levels_for(ctx, win), s->pyr[0].levels);
+      return PLV_E_BADARG;
     }
   }
   ctx->cfg.win_size = win;
@@ -101,42 +86,19 @@ FrontState *fe(plv_ctx *ctx) {
 }
 
 int ensure_pyramids(plv_ctx *ctx, FrontState *s) {
-  if (s->pyr_mem[0].p) return PLV_OK;
-  if (s->W < 16 || s->H < 16) {
-    set_last_error("front-end: image %dx%d too small", s->W, s->H);
-    return PLV_E_BADARG;
-  }
-  for (int i = 0; i < 2; ++i) {
-    int bytes = level_geometry(s->W, s->H, ctx->cfg.win_size, ctx->cfg.pyr_levels, s->pyr[i]);
-    TRY(s->pyr_mem[i].reserve((size_t)bytes));
-    s->pyr[i].base = s->pyr_mem[i].as<uint8_t>();
-  }
-  if (!s->hist.p) {  // 256 bins + arrival counter; equalize_kernel leaves it zero for the next frame
-    TRY(s->hist.reserve(257 * sizeof(unsigned)));
-    PLV_HIP_CHECK(hipMemsetAsync(s->hist.p, 0, 257 * sizeof(unsigned), ctx->stream));
-  }
-  TRY(s->raw.reserve((size_t)s->W * s->H));
+  if (s->prepared()) return PLV_OK;
+  TRY(s->prepare(ctx, "front-end"));
   TRY(s->img_pin[0].reserve((size_t)s->W * s->H));  // (pinned blocks of plv_feed_image_enqueue: not allocated inside a frame)
-  TRY(s->img_pin[1].reserve((size_t)s->W * s->H));
-  return PLV_OK;
-}
-
-int sync(plv_ctx *ctx) {
-  const unsigned long long stamp = ctx->gather_stamp;
-  PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
-  ctx->cov_host_synced = stamp;
-  ctx->prof.collect();
-  return PLV_OK;
+  return s->img_pin[1].reserve((size_t)s->W * s->H);
 }
 
 // equalize + pyramid of the packed device image d_img into the next "current" pyramid
 // h_src != null: d_img is still empty and the image sits in pinned host memory at h_src (the first kernel that reads it brings it in)
 int feed_device(plv_ctx *ctx, FrontState *s, const uint8_t *d_img, const uint8_t *h_src = nullptr) {
   plv::HostPhase ph("feed image (enqueue hist + pyramid)");
-  const int next = s->fed == 0 ? s->cur : 1 - s->cur;
+  const int next = s->next();
   TRY(front_feed_pyramid(ctx, s->W, s->H, d_img, h_src, s->pyr[next], s->hist, s->clahe_lut));
-  s->cur = next;
-  s->fed++;
+  s->commit(next);
   return PLV_OK;
 }
 }  // namespace
@@ -214,11 +176,7 @@ int encoded_source(FrontState *s, const uint8_t *data, int stride, int bpp, cons
   // the conversion that read this block two images ago: normally long finished
   if (s->raw_done[i] && hipEventQuery(s->raw_done[i]) == hipErrorNotReady) PLV_HIP_CHECK(plv::event_sync(s->raw_done[i]));
   uint8_t *dst = s->raw_pin[i].as<uint8_t>();
-  if ((size_t)stride == row) {
-    memcpy(dst, data, bytes);
-  } else {
-    for (int y = 0; y < s->H; ++y) memcpy(dst + (size_t)y * row, data + (size_t)y * stride, row);
-  }
+  pack_rows(dst, data, (size_t)stride, row, s->H);
   *h_src = dst;
   *own = i;
   return PLV_OK;
@@ -253,11 +211,11 @@ void plv_frontend_destroy(plv_ctx *ctx) {
     if (e) (void)hipEventDestroy(e);
   s->cv_src.release();
   s->cv_dst.release();
-  DevBuf *bufs[] = {&s->pyr_mem[0], &s->pyr_mem[1], &s->raw, &s->hist, &s->clahe_lut, &s->ds_src, &s->ds_dst, &s->pts0, &s->pts1, &s->n0, &s->n1,
-                    &s->status, &s->iters, &s->mask, &s->counts, &s->info, &s->io, &s->models};
+  DevBuf *bufs[] = {&s->ds_src, &s->ds_dst, &s->pts0, &s->pts1, &s->n0, &s->n1, &s->status, &s->iters, &s->mask, &s->io};
   for (auto *b : bufs) b->release();
   for (auto &b : s->slots) b.release();
-  s->release_detection();
+  s->ransac.release();
+  s->release();
   delete s;
   ctx->fe_state = nullptr;
 }
@@ -285,11 +243,7 @@ int plv_feed_image_enqueue(plv_ctx *ctx, const uint8_t *img, int stride) {
     PinBuf &pin = s->img_pin[s->img_pin_next];
     s->img_pin_next ^= 1;
     TRY(pin.reserve(bytes));
-    if (stride == s->W) {
-      memcpy(pin.p, img, bytes);
-    } else {
-      for (int y = 0; y < s->H; ++y) memcpy(pin.as<uint8_t>() + (size_t)y * s->W, img + (size_t)y * stride, s->W);
-    }
+    pack_rows(pin.p, img, (size_t)stride, (size_t)s->W, s->H);
     h_src = pin.as<uint8_t>();  // (a block is reused two images later: the wait for that image's flow lies in between)
   }
   // no copy command: the histogram kernel reads the pinned block over PCIe (16 bytes per lane) and leaves the image in s->raw
@@ -359,7 +313,7 @@ int plv_image_convert(plv_ctx *ctx, const uint8_t *data, int stride, int encodin
   PLV_HIP_CHECK(hipMemcpy2DAsync(s->cv_src.p, row, data, (size_t)stride, row, (size_t)h, hipMemcpyHostToDevice, ctx->stream));
   TRY(launch_grey_from_encoded(ctx, s->cv_src.as<uint8_t>(), false, s->cv_dst.as<uint8_t>(), w, h, encoding));
   PLV_HIP_CHECK(hipMemcpy2DAsync(grey, (size_t)grey_stride, s->cv_dst.p, (size_t)w, (size_t)w, (size_t)h, hipMemcpyDeviceToHost, ctx->stream));
-  return sync(ctx);
+  return stream_wait(ctx);
 }
 
 // A pinned host block of the library for the caller to write the next image into (a camera driver's DMA target, cv_bridge's copy
@@ -383,7 +337,7 @@ int plv_feed_image(plv_ctx *ctx, const uint8_t *img, int stride) {
   TRY(ensure_pyramids(ctx, s));
   TRY(upload_image(ctx, s, s->raw.p, img, stride));
   TRY(feed_device(ctx, s, s->raw.as<uint8_t>()));
-  return sync(ctx);
+  return stream_wait(ctx);
 }
 
 // cv::pyrDown(img, out, Size(cols / 2.0, rows / 2.0)) on the device: the Size_<int> constructor truncates, so an
@@ -408,7 +362,7 @@ int plv_downsample(plv_ctx *ctx, const uint8_t *src, int stride, int src_w, int 
   TRY(downsample_to(ctx, s, src, stride, src_w, src_h, s->ds_dst.as<uint8_t>()));
   PLV_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)dstride, s->ds_dst.p, (size_t)dw, (size_t)dw, (size_t)dh, hipMemcpyDeviceToHost,
                                  ctx->stream));
-  return sync(ctx);
+  return stream_wait(ctx);
 }
 
 int plv_feed_image_downsampled(plv_ctx *ctx, const uint8_t *img, int stride, int src_w, int src_h) {
@@ -423,7 +377,7 @@ int plv_feed_image_downsampled(plv_ctx *ctx, const uint8_t *img, int stride, int
   }
   TRY(downsample_to(ctx, s, img, stride, src_w, src_h, s->raw.as<uint8_t>()));
   TRY(feed_device(ctx, s, s->raw.as<uint8_t>()));
-  return sync(ctx);
+  return stream_wait(ctx);
 }
 
 int plv_image_stage(plv_ctx *ctx, int slot, const uint8_t *img, int stride) {
@@ -433,7 +387,7 @@ int plv_image_stage(plv_ctx *ctx, int slot, const uint8_t *img, int stride) {
   TRY(ensure_pyramids(ctx, s));
   TRY(s->slots[slot].reserve((size_t)s->W * s->H));
   TRY(upload_image(ctx, s, s->slots[slot].p, img, stride));
-  return sync(ctx);
+  return stream_wait(ctx);
 }
 
 int plv_feed_staged(plv_ctx *ctx, int slot) {
@@ -457,9 +411,8 @@ int plv_front_match_device(plv_ctx *ctx, const float **d_p1, const float **d_n1,
   if (!ctx || !ctx->fe_state) return PLV_E_BADARG;
   FrontState *s = fe(ctx);
   if (s->pending_n < 10 || !s->pending_ran || !s->io.p) return PLV_E_BADARG;
-  const size_t nn = (size_t)s->pending_n;
-  const char *dp_ = s->io.as<char>();
-  *d_p1 = (const float *)(dp_ + nn * 8), *d_n1 = (const float *)(dp_ + nn * 24), *d_mask = (const uint8_t *)(dp_ + nn * 36), *n = s->pending_n;
+  const MatchBlock dev((size_t)s->pending_n, s->io.p);
+  *d_p1 = dev.pts1(), *d_n1 = dev.n1(), *d_mask = dev.mask(), *n = s->pending_n;
   return PLV_OK;
 }
 const uint8_t *plv_front_level0(plv_ctx *ctx, int which, int *w, int *h) {
@@ -493,7 +446,7 @@ int plv_pyramid_download(plv_ctx *ctx, int which, int level, int *w, int *h, uin
   if (out) {
     PLV_HIP_CHECK(plv::memcpy_async(out, p.base + p.off[level], (size_t)p.w[level] * p.h[level], hipMemcpyDeviceToHost,
                                  ctx->stream));
-    return sync(ctx);
+    return stream_wait(ctx);
   }
   return PLV_OK;
 }
@@ -516,10 +469,7 @@ static int reserve_points(FrontState *s, int n, int ransac_iters) {
   TRY(s->status.reserve(nn));
   TRY(s->mask.reserve(nn));
   TRY(s->iters.reserve(nn * 4));
-  TRY(s->counts.reserve((size_t)std::max(ransac_iters, 1) * 3 * 4));
-  TRY(s->models.reserve((size_t)std::max(ransac_iters, 1) * 28 * 8));
-  TRY(s->info.reserve(16));
-  return PLV_OK;
+  return s->ransac.reserve(ransac_iters);
 }
 
 int plv_lk_track(plv_ctx *ctx, int n, const float *pts0, float *pts1, uint8_t *status, int *iters) {
@@ -536,7 +486,7 @@ int plv_lk_track(plv_ctx *ctx, int n, const float *pts0, float *pts1, uint8_t *s
   PLV_HIP_CHECK(plv::memcpy_async(pts1, s->pts1.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
   PLV_HIP_CHECK(plv::memcpy_async(status, s->status.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   if (iters) PLV_HIP_CHECK(plv::memcpy_async(iters, s->iters.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  return sync(ctx);
+  return stream_wait(ctx);
 }
 
 static CamK cam_of(plv_ctx *ctx) {
@@ -555,7 +505,7 @@ int plv_undistort(plv_ctx *ctx, int n, const float *uv, float *xy) {
   PLV_HIP_CHECK(plv::memcpy_async(s->pts0.p, uv, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
   TRY(launch_undistort(ctx, cam_of(ctx), n, s->pts0.as<float>(), s->n0.as<float>()));
   PLV_HIP_CHECK(plv::memcpy_async(xy, s->n0.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  return sync(ctx);
+  return stream_wait(ctx);
 }
 
 int plv_ransac_fundamental(plv_ctx *ctx, int n, const float *m1, const float *m2, double thr, uint32_t seed,
@@ -570,12 +520,12 @@ int plv_ransac_fundamental(plv_ctx *ctx, int n, const float *m1, const float *m2
   TRY(reserve_points(s, n, mi));
   PLV_HIP_CHECK(plv::memcpy_async(s->n0.p, m1, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
   PLV_HIP_CHECK(plv::memcpy_async(s->n1.p, m2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-  TRY(launch_ransac(ctx, s->n0.as<float>(), s->n1.as<float>(), n, thr, ctx->cfg.ransac_conf, mi, seed, s->counts.as<int>(),
-                    nullptr, s->mask.as<uint8_t>(), s->info.as<int>(), s->models.as<double>()));
+  TRY(launch_ransac(ctx, s->n0.as<float>(), s->n1.as<float>(), n, thr, ctx->cfg.ransac_conf, mi, seed, s->ransac.counts.as<int>(),
+                    nullptr, s->mask.as<uint8_t>(), s->ransac.info.as<int>(), s->ransac.models.as<double>()));
   int info[2] = {0, 0};
   PLV_HIP_CHECK(plv::memcpy_async(mask, s->mask.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  PLV_HIP_CHECK(plv::memcpy_async(info, s->info.p, sizeof(info), hipMemcpyDeviceToHost, ctx->stream));
-  TRY(sync(ctx));
+  PLV_HIP_CHECK(plv::memcpy_async(info, s->ransac.info.p, sizeof(info), hipMemcpyDeviceToHost, ctx->stream));
+  TRY(stream_wait(ctx));
   if (n_inliers) *n_inliers = info[0];
   if (iters_used) *iters_used = info[1];
   return PLV_OK;
@@ -589,10 +539,10 @@ int plv_ransac_hypotheses(plv_ctx *ctx, int n, const float *m1, const float *m2,
   TRY(reserve_points(s, n, nhyp));
   PLV_HIP_CHECK(plv::memcpy_async(s->n0.p, m1, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
   PLV_HIP_CHECK(plv::memcpy_async(s->n1.p, m2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-  TRY(launch_ransac_hyp(ctx, s->n0.as<float>(), s->n1.as<float>(), n, thr, seed, nhyp, s->counts.as<int>(), s->models.as<double>()));
-  PLV_HIP_CHECK(plv::memcpy_async(models, s->models.p, (size_t)nhyp * 28 * 8, hipMemcpyDeviceToHost, ctx->stream));
-  PLV_HIP_CHECK(plv::memcpy_async(counts, s->counts.p, (size_t)nhyp * 3 * 4, hipMemcpyDeviceToHost, ctx->stream));
-  return sync(ctx);
+  TRY(launch_ransac_hyp(ctx, s->n0.as<float>(), s->n1.as<float>(), n, thr, seed, nhyp, s->ransac.counts.as<int>(), s->ransac.models.as<double>()));
+  PLV_HIP_CHECK(plv::memcpy_async(models, s->ransac.models.p, (size_t)nhyp * 28 * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(counts, s->ransac.counts.p, (size_t)nhyp * 3 * 4, hipMemcpyDeviceToHost, ctx->stream));
+  return stream_wait(ctx);
 }
 
 int plv_perform_matching_launch(plv_ctx *ctx, int n, const float *pts0, const float *pts1_init) {
@@ -607,33 +557,21 @@ int plv_perform_matching_launch(plv_ctx *ctx, int n, const float *pts0, const fl
   (void)hipSetDevice(ctx->device);
   FrontState *s = s0;
   TRY(need_two(ctx, s, "plv_perform_matching"));
-  const int mi = std::max(1, ctx->cfg.ransac_max_iters);
-  TRY(reserve_points(s, n, mi));
-  // one device block  [pts0 | pts1 | n0 | n1 | iters | mask | status]  -> one H2D (first two
-  // fields) and one D2H (pts1 .. mask) per call
-  const size_t nn = (size_t)n;
-  const size_t o_p0 = 0, o_p1 = nn * 8, o_n0 = nn * 16, o_n1 = nn * 24, o_it = nn * 32, o_mk = nn * 36, o_st = nn * 37,
-               total = nn * 38;
+  TRY(reserve_points(s, n, ctx->cfg.ransac_max_iters));
+  // one device block (MatchBlock) and its pinned twin: no H2D and one D2H (pts1 .. mask) per call at the most
+  const size_t total = MatchBlock((size_t)n).total();
   TRY(s->io.reserve(total));
   TRY(ctx->h_pin_flow.reserve(total));
-  char *hp = ctx->h_pin_flow.as<char>();
-  char *dp_ = s->io.as<char>();
+  const MatchBlock dev((size_t)n, s->io.p), pin((size_t)n, ctx->h_pin_flow.p);
   // No copy commands around the two kernels: lk_kernel reads the points and the initial guesses straight from the pinned buffer
   // (16 B per point, once) and the last kernel of the call copies the results back into it (ransac_select_kernel).
-  memcpy(hp + o_p0, pts0, nn * 8);
-  memcpy(hp + o_p1, pts1_init, nn * 8);
-  float *d_p1 = (float *)(dp_ + o_p1), *d_n0 = (float *)(dp_ + o_n0), *d_n1 = (float *)(dp_ + o_n1);
-  int *d_it = (int *)(dp_ + o_it);
-  uint8_t *d_mk = (uint8_t *)(dp_ + o_mk), *d_st = (uint8_t *)(dp_ + o_st);
+  memcpy(pin.pts0(), pts0, (size_t)n * 8);
+  memcpy(pin.pts1(), pts1_init, (size_t)n * 8);
   const CamK camk = cam_of(ctx);
-  TRY(launch_lk(ctx, s->pyr[1 - s->cur], s->pyr[s->cur], n, (const float *)(hp + o_p0), d_p1, d_st, d_it, ctx->cfg.win_size,
-                ctx->cfg.lk_max_iters, ctx->cfg.lk_eps, &camk, d_n0, d_n1,
-                (const float *)(hp + o_p1)));  // (+ the undistortion of both point sets on the same launch)
-  const double fmax = std::max(ctx->cfg.intrinsics[0], ctx->cfg.intrinsics[1]);
-  bool mirrored = false;
-  TRY(launch_ransac(ctx, d_n0, d_n1, n, ctx->cfg.ransac_thr_px / fmax, ctx->cfg.ransac_conf, mi, 0u, s->counts.as<int>(), d_st,
-                    d_mk, s->info.as<int>(), s->models.as<double>(), dp_ + o_p1, hp + o_p1, o_mk - o_p1, (uint8_t *)(hp + o_mk), &mirrored));
-  if (!mirrored) PLV_HIP_CHECK(plv::memcpy_async(hp + o_p1, dp_ + o_p1, o_st - o_p1, hipMemcpyDeviceToHost, ctx->stream));
+  TRY(launch_lk(ctx, s->pyr[1 - s->cur], s->pyr[s->cur], n, pin.pts0(), dev.pts1(), dev.status(), dev.iters(), ctx->cfg.win_size,
+                ctx->cfg.lk_max_iters, ctx->cfg.lk_eps, &camk, dev.n0(), dev.n1(),
+                pin.pts1()));  // (+ the undistortion of both point sets on the same launch)
+  TRY(match_ransac_tail(ctx, camk, dev, pin, s->ransac));
   if (!s->flow_done) PLV_HIP_CHECK(hipEventCreateWithFlags(&s->flow_done, hipEventDisableTiming));
   PLV_HIP_CHECK(hipEventRecord(s->flow_done, ctx->stream));
   s->flow_done_stamp = ctx->gather_stamp;
@@ -660,24 +598,14 @@ int plv_perform_matching_wait(plv_ctx *ctx, float *pts1, uint8_t *mask_out, floa
   }
   (void)hipSetDevice(ctx->device);
   if (ctx->prof.on)
-    TRY(sync(ctx));  // (the per-kernel timer reads every event recorded so far)
+    TRY(stream_wait(ctx));  // (the per-kernel timer reads every event recorded so far)
   else
   {
     // not the whole stream: the caller may have enqueued more behind the flow
     PLV_HIP_CHECK(plv::event_sync(s->flow_done));
     if (s->flow_done_stamp > ctx->cov_host_synced) ctx->cov_host_synced = s->flow_done_stamp;
   }
-  const size_t nn = (size_t)n;
-  const size_t o_p1 = nn * 8, o_n0 = nn * 16, o_n1 = nn * 24, o_it = nn * 32, o_mk = nn * 36;
-  const char *hp = ctx->h_pin_flow.as<char>();
-  memcpy(pts1, hp + o_p1, nn * 8);
-  if (n0) memcpy(n0, hp + o_n0, nn * 8);
-  if (n1) memcpy(n1, hp + o_n1, nn * 8);
-  memcpy(mask_out, hp + o_mk, nn);
-  long long t = 0;
-  const int *it = (const int *)(hp + o_it);
-  for (int i = 0; i < n; ++i) t += it[i];
-  plv::counters().lk_iters += (unsigned long long)t;
+  const long long t = match_read_back(MatchBlock((size_t)n, ctx->h_pin_flow.p), pts1, mask_out, n0, n1);
   if (lk_iters) *lk_iters = t;
   return PLV_OK;
 }
@@ -953,8 +881,8 @@ int plv_perform_detection(plv_ctx *ctx, int which, const uint8_t *mask, float *p
   DetJob J;
   TRY(det_pre(ctx, s->W, s->H, mask, pts, ids, n_in, J));
   if (J.n_slots > 0) {
-    TRY(det_launch(ctx, *s, s->W, s->H, pyr, mask, J, ctx->stream));
-    TRY(sync(ctx));
+    TRY(det_launch(ctx, s->det, s->W, s->H, pyr, mask, J, ctx->stream));
+    TRY(stream_wait(ctx));
     TRY(det_check(J));
   }
   det_post(ctx, J, pts, ids, cap, currid, n_out);
@@ -989,7 +917,7 @@ int plv_perform_detection_ahead(plv_ctx *ctx, const uint8_t *mask, const float *
     PLV_HIP_CHECK(hipStreamCreateWithFlags(&s->det_stream, hipStreamNonBlocking));
     PLV_HIP_CHECK(hipEventCreateWithFlags(&s->det_done, hipEventDisableTiming));
   }
-  if (A.n_slots > 0) TRY(det_launch(ctx, *s, s->W, s->H, s->pyr[s->cur], mask ? A.in_mask.data() : nullptr, A, s->det_stream));  // (the job's own copy of the mask)
+  if (A.n_slots > 0) TRY(det_launch(ctx, s->det, s->W, s->H, s->pyr[s->cur], mask ? A.in_mask.data() : nullptr, A, s->det_stream));  // (the job's own copy of the mask)
   PLV_HIP_CHECK(hipEventRecord(s->det_done, s->det_stream));
   A.active = true;
   return PLV_OK;

@@ -38,12 +38,6 @@ using namespace plv::linehost;
 int plv_tracker_last(plv_ctx *ctx, float *pts, uint64_t *ids, int cap, int *n);
 namespace {
 
-#define TRY(expr)                  \
-  do {                             \
-    int _rc = (expr);              \
-    if (_rc != PLV_OK) return _rc; \
-  } while (0)
-
 // The pool of LineHelper::get_line_features (REF: linefeat/LineHelper.cpp:33-44: features_containing_older + features_not_containing_newer,
 // remove_unusable_measurements, sort) taken out of the database.  It reads times only, so plv_camera_try_update forms it while the
 // point update is still running on the device (form_line_pool below); plv_camera_update_lines consumes it.
@@ -973,13 +967,7 @@ int plv_line_db_ids(plv_ctx *ctx, uint64_t *ids, int cap, int *n) {
   if (!ctx || !n) return PLV_E_BADARG;
   LineTracker *T = ltr(ctx);
   std::lock_guard<std::mutex> lk(T->mtx);
-  std::vector<uint64_t> v;
-  for (const auto &kv : T->db) v.push_back(kv.first);
-  std::sort(v.begin(), v.end());
-  *n = (int)v.size();
-  if (*n > cap) return PLV_E_CAPACITY;
-  if (ids) std::copy(v.begin(), v.end(), ids);
-  return PLV_OK;
+  return export_sorted_ids(T->db, ids, cap, n);
 }
 
 // CSR export of the chosen line tracks in the layout of plv_line_tracks (+ the assigned point ids)
@@ -988,39 +976,27 @@ int plv_line_db_export_tracks(plv_ctx *ctx, const uint64_t *ids, int n_ids, int 
   if (!ctx || !ids || !obs_ptr) return PLV_E_BADARG;
   LineTracker *T = ltr(ctx);
   std::lock_guard<std::mutex> lk(T->mtx);
-  int no = 0, npt = 0;
-  obs_ptr[0] = 0;
+  int npt = 0;
   if (pts_ptr) pts_ptr[0] = 0;
-  for (int i = 0; i < n_ids; ++i) {
-    auto it = T->db.find(ids[i]);
-    if (it != T->db.end()) {
-      const LineTrack &tr = it->second;
-      const int m = (int)tr.t.size();
-      if (no + m > obs_cap) return PLV_E_CAPACITY;
-      if (obs_time) std::copy(tr.t.begin(), tr.t.end(), obs_time + no);
-      if (seg_uv) std::copy(tr.uv.begin(), tr.uv.end(), seg_uv + 4 * (size_t)no);
-      if (seg_uvn) std::copy(tr.uvn.begin(), tr.uvn.end(), seg_uvn + 4 * (size_t)no);
-      no += m;
-      if (D) D[i] = tr.D;
-      if (pts_ptr) {
-        if (npt + (int)tr.points.size() > pts_cap) return PLV_E_CAPACITY;
-        if (pt_ids) std::copy(tr.points.begin(), tr.points.end(), pt_ids + npt);
-        npt += (int)tr.points.size();
-      }
-    } else if (D) {
-      D[i] = 0;
+  // behind a line's observations: its direction class (0 for a missing id) and the CSR of its point ids
+  auto extras = [&](int i, const LineTrack *tr) {
+    if (D) D[i] = tr ? tr->D : 0;
+    if (tr && pts_ptr) {
+      if (npt + (int)tr->points.size() > pts_cap) return (int)PLV_E_CAPACITY;
+      if (pt_ids) std::copy(tr->points.begin(), tr->points.end(), pt_ids + npt);
+      npt += (int)tr->points.size();
     }
-    obs_ptr[i + 1] = no;
     if (pts_ptr) pts_ptr[i + 1] = npt;
-  }
-  return PLV_OK;
+    return (int)PLV_OK;
+  };
+  return export_tracks(ids, n_ids, track_in(T->db), obs_ptr, obs_time, seg_uv, seg_uvn, obs_cap, extras);
 }
 
 int plv_line_db_remove(plv_ctx *ctx, const uint64_t *ids, int n_ids) {
   if (!ctx || (n_ids > 0 && !ids)) return PLV_E_BADARG;
   LineTracker *T = ltr(ctx);
   std::lock_guard<std::mutex> lk(T->mtx);
-  for (int i = 0; i < n_ids; ++i) T->db.erase(ids[i]);
+  erase_ids(T->db, ids, n_ids);
   return PLV_OK;
 }
 
@@ -1399,7 +1375,7 @@ struct LinesUpdate {
   void scan_db_early() {
     if (!opt->window_full || db_scanned_early) return;
     std::lock_guard<std::mutex> lk(T->mtx);
-    for (auto it = T->db.begin(); it != T->db.end();) it = drop_before(it->second, t_oldest) == 0 ? T->db.erase(it) : std::next(it);
+    cleanup_measurements(T->db, t_oldest);
     db_scanned_early = true;
   }
 
@@ -1429,7 +1405,7 @@ struct LinesUpdate {
         }
       for (auto &kv : un) put(kv.first, kv.second);
       if (window_full && !scanned)
-        for (auto it = T->db.begin(); it != T->db.end();) it = drop_before(it->second, t_oldest) == 0 ? T->db.erase(it) : std::next(it);
+        cleanup_measurements(T->db, t_oldest);
     };
     // (point_used->cleanup_measurements is not deferred: it takes the point tracker's lock, which a feed in progress holds)
     if (window_full) plv_point_used_cleanup(ctx, t_oldest);

@@ -46,14 +46,13 @@ static int d2h(plv_ctx *ctx, void *dst, const void *src, size_t bytes) {
   PLV_HIP_CHECK(plv::memcpy_async(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
   return PLV_OK;
 }
-static int sync(plv_ctx *ctx) {
+int stream_wait(plv_ctx *ctx) {
   const unsigned long long stamp = ctx->gather_stamp;
   PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
   ctx->cov_host_synced = stamp;
   ctx->prof.collect();
   return PLV_OK;
-}
-// upload a col-major matrix with arbitrary ld into a dense (ld = rows) device matrix
+}// upload a col-major matrix with arbitrary ld into a dense (ld = rows) device matrix
 static int upload_mat(plv_ctx *ctx, double *dst, const double *src, int rows, int cols, int ld) {
   if (ld == rows) return h2d(ctx, dst, src, (size_t)rows * cols * 8);
   PLV_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)rows * 8, src, (size_t)ld * 8, (size_t)rows * 8, cols,
@@ -79,12 +78,6 @@ using namespace plv;
     }                                        \
     (void)hipSetDevice((ctx)->device);       \
   } while (0)
-#define TRY(expr)              \
-  do {                         \
-    int _rc = (expr);          \
-    if (_rc != PLV_OK) return _rc; \
-  } while (0)
-
 static std::mutex g_state_mtx;
 static std::vector<std::pair<plv_ctx *, plv_ctx_update_state *>> g_states;
 plv_ctx_update_state *plv::plv_update_state(plv_ctx *ctx) {
@@ -336,20 +329,20 @@ int plv_ctx_synchronize(plv_ctx *ctx) {
     (void)plv_line_tracker_feed_wait(ctx);
   }
   plv::HostPhase ph("ctx_synchronize: ctx stream");
-  TRY(sync(ctx));
+  TRY(stream_wait(ctx));
   ctx->prof.collect();
   return PLV_OK;
 }
 
 int plv_prof_enable(plv_ctx *ctx, int on) {
   REQUIRE_CTX(ctx);
-  TRY(sync(ctx));
+  TRY(stream_wait(ctx));
   ctx->prof.on = on != 0;
   return PLV_OK;
 }
 int plv_prof_reset(plv_ctx *ctx) {
   REQUIRE_CTX(ctx);
-  TRY(sync(ctx));
+  TRY(stream_wait(ctx));
   ctx->prof.reset();
   return PLV_OK;
 }
@@ -379,7 +372,7 @@ int plv_cov_upload(plv_ctx *ctx, const double *P, int n, int ldp) {
   TRY(upload_mat(ctx, ctx->d_P.as<double>(), P, n, n, ldp));
   ctx->cov_n = n;
   ++ctx->gather_stamp;
-  return sync(ctx);
+  return stream_wait(ctx);
 }
 int plv_cov_download(plv_ctx *ctx, double *P, int n, int ldp) {
   REQUIRE_CTX(ctx);
@@ -388,7 +381,7 @@ int plv_cov_download(plv_ctx *ctx, double *P, int n, int ldp) {
     return PLV_E_BADARG;
   }
   TRY(download_mat(ctx, P, ctx->d_P.as<double>(), n, n, ldp));
-  return sync(ctx);
+  return stream_wait(ctx);
 }
 void plv_counters(unsigned long long *out) {
   plv::Counters &c = plv::counters();
@@ -403,7 +396,7 @@ int plv_cov_checkpoint(plv_ctx *ctx) {
   TRY(us->covck.reserve(bytes));
   PLV_HIP_CHECK(plv::memcpy_async(us->covck.p, ctx->d_P.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
   us->covck_n = ctx->cov_n;
-  return sync(ctx);
+  return stream_wait(ctx);
 }
 int plv_cov_rollback(plv_ctx *ctx) {
   REQUIRE_CTX(ctx);
@@ -483,13 +476,13 @@ int plv_ekf_update(plv_ctx *ctx, double *P, int n, int ldp, const double *H, int
     }
     if (rc != PLV_OK) {
       PLV_HIP_CHECK(plv::memcpy_async(ctx->d_P.p, ctx->d_P2.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-      TRY(sync(ctx));
+      TRY(stream_wait(ctx));
       return rc;
     }
     std::copy(dx_tot.begin(), dx_tot.end(), dx);
     if (P) {
       TRY(download_mat(ctx, P, ctx->d_P.as<double>(), n, n, ldp));
-      TRY(sync(ctx));
+      TRY(stream_wait(ctx));
     }
     return PLV_OK;
   }
@@ -518,7 +511,7 @@ int plv_ekf_update(plv_ctx *ctx, double *P, int n, int ldp, const double *H, int
                    ctx->d_res.as<double>(), dR, d_dx, d_flag));
   TRY(ctx->h_pin.reserve(lay.head_bytes()));
   TRY(d2h(ctx, ctx->h_pin.p, us->result.p, lay.head_bytes()));
-  TRY(sync(ctx));
+  TRY(stream_wait(ctx));
   const int flag = *lay.status((const void *)ctx->h_pin.p);
   if (flag != 0) {
     set_last_error("EKFUpdate rejected: %s", ekf_rejection_text(flag));
@@ -527,7 +520,7 @@ int plv_ekf_update(plv_ctx *ctx, double *P, int n, int ldp, const double *H, int
   memcpy(dx, lay.dx((const void *)ctx->h_pin.p), (size_t)n * 8);
   if (P) {
     TRY(download_mat(ctx, P, ctx->d_P.as<double>(), n, n, ldp));
-    TRY(sync(ctx));
+    TRY(stream_wait(ctx));
   }
   return PLV_OK;
 }
@@ -557,7 +550,7 @@ int plv_compress(plv_ctx *ctx, double *H, int m, int k, int ldh, double *res, in
   PLV_HIP_CHECK(hipMemcpy2DAsync(H, (size_t)ldh * 8, R, (size_t)ldr * 8, (size_t)k * 8, k, hipMemcpyDeviceToHost,
                                  ctx->stream));
   TRY(d2h(ctx, res, R + (size_t)k * ldr, (size_t)k * 8));
-  TRY(sync(ctx));
+  TRY(stream_wait(ctx));
   *m_out = k;
   return PLV_OK;
 }
@@ -595,7 +588,7 @@ int plv_nullspace_batch(plv_ctx *ctx, int F, int fdim, int k, int ld, const int 
   TRY(d2h(ctx, Hf, ctx->d_fHf.p, nHf * 8));
   TRY(d2h(ctx, Hx, ctx->d_fHx.p, nHx * 8));
   TRY(d2h(ctx, res, ctx->d_fres.p, nr * 8));
-  return sync(ctx);
+  return stream_wait(ctx);
 }
 
 int plv_chi2_batch(plv_ctx *ctx, const double *P, int n, int ldp, int F, int k, int ld, const int *rows,
@@ -643,7 +636,7 @@ int plv_chi2_batch(plv_ctx *ctx, const double *P, int n, int ldp, int F, int k, 
   TRY(launch_gather_cov(ctx, ctx->d_P.as<double>(), n, n, ctx->d_cols.as<int>(), k));
   TRY(launch_chi2(ctx, F, a, max_mp));
   TRY(d2h(ctx, chi2, ctx->d_chi2.p, (size_t)F * 8));
-  return sync(ctx);
+  return stream_wait(ctx);
 }
 
 int plv_feat_batch_upload(plv_ctx *ctx, int F, int fdim, int k, int ld, const int *rows, const double *Hf,
@@ -673,7 +666,7 @@ int plv_feat_batch_upload(plv_ctx *ctx, int F, int fdim, int k, int ld, const in
   us->b_single_use = false;
   us->b_projected = false;
   us->b_gather_token = 0;
-  return sync(ctx);
+  return stream_wait(ctx);
 }
 
 }  // extern "C"
@@ -958,7 +951,7 @@ struct UpdateLaunch {
     const UpdateShape &s = shape;
     *done = true;
     if (ctx->probe_hook) ctx->probe_hook(ctx->probe_hook_arg);
-    TRY(sync(ctx));
+    TRY(stream_wait(ctx));
     const unsigned char *hacc = buf.lay.accepted((const void *)buf.pin);
     const int *hrows = buf.lay.acc_rows((const void *)buf.pin);
     int any = 0, m_acc = 0;
@@ -1126,7 +1119,7 @@ int redo_by_householder(plv_ctx *ctx, plv_ctx_update_state *us, int fdim, void *
   TRY(launch_tsqr(ctx, ctx->d_stackc.as<double>(), m_c, m_c, nc, ctx->d_stack2.as<double>(), rd.tmp_elems, &R, &ldr));
   TRY(launch_ekf_fast(ctx, ctx->d_P.as<double>(), rd.n, rd.n, R, rd.k, rd.k, ldr, us->bcols_of(fdim).as<int>(), R + (size_t)rd.k * ldr, nullptr, rd.d_dx, rd.d_flag,
                       true, us->result_of(rd.fdim).p, hpin, ResultBlock(rd.n, rd.F).head_mirror_bytes()));
-  TRY(sync(ctx));
+  TRY(stream_wait(ctx));
   us->last_route = ROUTE_WHITENED_REDONE;
   ++ctx->gather_stamp;
   ctx->cov_host_synced = ctx->gather_stamp;
@@ -1201,7 +1194,7 @@ int plv_msckf_update_resident_wait(plv_ctx *ctx, uint8_t *accepted, int *n_accep
   if (ctx->probe_done)
     ctx->probe_done = false;  // (ended at the gate: already synchronised, the result block in h_pin is complete)
   else if (ctx->prof.on || !us->done_ev)
-    TRY(sync(ctx));
+    TRY(stream_wait(ctx));
   else
   {
     // (not the whole stream: the caller may have enqueued more behind the update)

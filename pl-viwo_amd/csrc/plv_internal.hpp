@@ -20,9 +20,19 @@ struct plv_points_spec {
   const uint8_t *d_flow_mask;
 };
 
+// a PLV_* code other than PLV_OK leaves the calling function as it is
+#define TRY(expr)                  \
+  do {                             \
+    int _rc = (expr);              \
+    if (_rc != PLV_OK) return _rc; \
+  } while (0)
+
 namespace plv {
 
 // ---- plv_api.hip
+// the host waits for everything on the ctx's stream: plv_ctx::cov_host_synced moves up to the stamp of the moment the wait began,
+// and the per-kernel timer reads its events
+int stream_wait(plv_ctx *ctx);
 // the ctx's update-side state (update_state.hpp); null for a ctx plv_ctx_create did not make
 plv_ctx_update_state *plv_update_state(plv_ctx *ctx);
 // fills plv_ctx::gate_stage so that the projected Jacobian launch ends with the gate of every entry (the one-submission updates)

@@ -25,12 +25,6 @@
 namespace plv {
 namespace {
 
-#define TRY(expr)                  \
-  do {                             \
-    int _rc = (expr);              \
-    if (_rc != PLV_OK) return _rc; \
-  } while (0)
-
 // LDS image of plv_imu_state: q4 p3 v3 bg3 ba3 qf4 pf3 vf3
 enum { IQ = 0, IP = 4, IV = 7, IBG = 10, IBA = 13, IQF = 16, IPF = 20, IVF = 23, IMU_N = 26 };
 

@@ -15,12 +15,6 @@
 
 using namespace plv;
 
-#define TRY(expr)                  \
-  do {                             \
-    int _rc = (expr);              \
-    if (_rc != PLV_OK) return _rc; \
-  } while (0)
-
 namespace {
 
 struct Inv3 {

@@ -20,12 +20,6 @@
 
 using namespace plv;
 
-#define TRY(expr)                  \
-  do {                             \
-    int _rc = (expr);              \
-    if (_rc != PLV_OK) return _rc; \
-  } while (0)
-
 namespace {
 
 const int Q95_ENTRIES = 1024;  // plv_ctx_update_state::q95 (plv_ctx_create)
@@ -446,10 +440,7 @@ int plv_camera_update_slam(plv_ctx *ctx, const plv_state_view *st, const plv_upd
     ctx->skip_word = nullptr;
     TRY(rc_e);
     PLV_HIP_CHECK(plv::memcpy_async(hres, W.us->slam.res.p, rb, hipMemcpyDeviceToHost, ctx->stream));
-    const unsigned long long stamp = ctx->gather_stamp;
-    PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
-    ctx->cov_host_synced = stamp;
-    ctx->prof.collect();
+    TRY(plv::stream_wait(ctx));
     const int flag = *head.status(hres);
     const bool passed = *head.accepted(hres) != 0;
     if (!passed) {

@@ -22,13 +22,10 @@ using namespace plv;
 
 namespace {
 
-struct StereoCam {
-  PyrDesc pyr[2];  // ping-pong pyramids
-  DevBuf pyr_mem[2];
-  DevBuf raw, hist, clahe_lut;
+struct StereoCam : CamFront {  // (cur and fed move in step in both cameras)
   PinBuf img_pin;  // the host image on its way to the device (packed, in its encoding): the caller's buffer is free at return
-  DetScratch det;
-  DevBuf io, counts, models, info;  // the temporal matching: [pts0 | pts1 | n0 | n1 | iters | mask | status] and RANSAC's scratch
+  DevBuf io;                        // the temporal matching's block (MatchBlock)
+  RansacScratch ransac;
   PinBuf flow_pin;                  // ... its host twin (points in, results out)
   std::vector<float> pts_last;      // 2 per point
   std::vector<uint64_t> ids_last;
@@ -45,8 +42,7 @@ struct Stereo {
   bool configured = false;
   int W = 0, H = 0;
   StereoCam cam[2];
-  int cur = 0;  // index of the current pyramids (both cameras are fed in step); last = 1 - cur
-  int fed = 0;
+  int cur() const { return cam[0].cur; }  // index of the current pyramids (both cameras are fed in step); last = 1 - cur
   uint64_t currid = 0;  // REF: TrackBase::currid, shared by both cameras
   std::unordered_map<uint64_t, StereoFeature> db;
   DevBuf lr_dev;  // left-to-right LK of new left corners: [pts1 | status | iters]
@@ -54,12 +50,6 @@ struct Stereo {
   bool unsynced = false;  // kernels that read img_pin may still be on the stream
   std::mutex mtx;
 };
-
-#define TRY(expr)                  \
-  do {                             \
-    int _rc = (expr);              \
-    if (_rc != PLV_OK) return _rc; \
-  } while (0)
 
 std::mutex g_mtx;
 Stereo *stereo_of(plv_ctx *ctx, bool create) {
@@ -69,10 +59,7 @@ Stereo *stereo_of(plv_ctx *ctx, bool create) {
 }
 
 int sync(plv_ctx *ctx, Stereo *S) {
-  const unsigned long long stamp = ctx->gather_stamp;
-  PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
-  ctx->cov_host_synced = stamp;
-  ctx->prof.collect();
+  TRY(stream_wait(ctx));
   S->unsynced = false;
   return PLV_OK;
 }
@@ -96,10 +83,7 @@ int enqueue_image(plv_ctx *ctx, Stereo *S, int c, int next, const uint8_t *img, 
   const size_t row = (size_t)S->W * encoding_bpp(encoding);
   TRY(C.img_pin.reserve(row * S->H));
   uint8_t *pin = C.img_pin.as<uint8_t>();
-  if ((size_t)stride == row)
-    memcpy(pin, img, row * S->H);
-  else
-    for (int y = 0; y < S->H; ++y) memcpy(pin + (size_t)y * row, img + (size_t)y * stride, row);
+  pack_rows(pin, img, (size_t)stride, row, S->H);
   S->unsynced = true;
   if (encoding == PLV_ENC_MONO8)  // (the histogram kernel reads the pinned block and leaves the image in C.raw)
     return front_feed_pyramid(ctx, S->W, S->H, C.raw.as<uint8_t>(), pin, C.pyr[next], C.hist, C.clahe_lut);
@@ -196,7 +180,6 @@ struct Matching {
 // intrinsics), the two RANSACs behind it, one wait
 int matching_pair(plv_ctx *ctx, Stereo *S, const std::vector<float> *pts_old[2], Matching M[2]) {
   plv::HostPhase ph("stereo feed: perform_matching x 2");
-  const int mi = std::max(1, ctx->cfg.ransac_max_iters);
   LkPair jobs{};
   for (int c = 0; c < 2; ++c) {
     Matching &m = M[c];
@@ -207,20 +190,18 @@ int matching_pair(plv_ctx *ctx, Stereo *S, const std::vector<float> *pts_old[2],
     jobs.job[c].n = 0;
     if (!m.ran) continue;
     StereoCam &C = S->cam[c];
-    const size_t nn = (size_t)m.n;
-    TRY(C.io.reserve(nn * 38));
-    TRY(C.flow_pin.reserve(nn * 38));
-    TRY(C.counts.reserve((size_t)mi * 3 * 4));
-    TRY(C.models.reserve((size_t)mi * 28 * 8));
-    TRY(C.info.reserve(16));
-    char *hp = C.flow_pin.as<char>(), *dp = C.io.as<char>();
-    memcpy(hp, pts_old[c]->data(), nn * 8);
-    memcpy(hp + nn * 8, pts_old[c]->data(), nn * 8);
+    const size_t total = MatchBlock((size_t)m.n).total();
+    TRY(C.io.reserve(total));
+    TRY(C.flow_pin.reserve(total));
+    TRY(C.ransac.reserve(ctx->cfg.ransac_max_iters));
+    const MatchBlock dev((size_t)m.n, C.io.p), pin((size_t)m.n, C.flow_pin.p);
+    memcpy(pin.pts0(), pts_old[c]->data(), (size_t)m.n * 8);
+    memcpy(pin.pts1(), pts_old[c]->data(), (size_t)m.n * 8);
     LkJob &j = jobs.job[c];
-    j.prev = C.pyr[1 - S->cur], j.cur = C.pyr[S->cur], j.n = m.n;
-    j.pts0 = (const float *)hp, j.pts1_init = (const float *)(hp + nn * 8);  // (read from the pinned block, once)
-    j.pts1 = (float *)(dp + nn * 8), j.n0 = (float *)(dp + nn * 16), j.n1 = (float *)(dp + nn * 24);
-    j.iters = (int *)(dp + nn * 32), j.status = (uint8_t *)(dp + nn * 37);
+    j.prev = C.pyr[1 - C.cur], j.cur = C.pyr[C.cur], j.n = m.n;
+    j.pts0 = pin.pts0(), j.pts1_init = pin.pts1();  // (read from the pinned block, once)
+    j.pts1 = dev.pts1(), j.n0 = dev.n0(), j.n1 = dev.n1();
+    j.iters = dev.iters(), j.status = dev.status();
     j.K = cam_k(ctx, S, c);
   }
   if (!M[0].ran && !M[1].ran) return PLV_OK;
@@ -228,16 +209,7 @@ int matching_pair(plv_ctx *ctx, Stereo *S, const std::vector<float> *pts_old[2],
   for (int c = 0; c < 2; ++c) {
     if (!M[c].ran) continue;
     StereoCam &C = S->cam[c];
-    const LkJob &j = jobs.job[c];
-    const size_t nn = (size_t)M[c].n, o_p1 = nn * 8, o_mk = nn * 36;
-    char *hp = C.flow_pin.as<char>(), *dp = C.io.as<char>();
-    // each RANSAC is a findFundamentalMat call of its own in the reference: the seed of a fresh call, this camera's focal length
-    const double fmax = std::max(j.K.v[0], j.K.v[1]);
-    bool mirrored = false;
-    TRY(launch_ransac(ctx, j.n0, j.n1, M[c].n, ctx->cfg.ransac_thr_px / fmax, ctx->cfg.ransac_conf, mi, 0u, C.counts.as<int>(), j.status,
-                      (uint8_t *)(dp + o_mk), C.info.as<int>(), C.models.as<double>(), dp + o_p1, hp + o_p1, o_mk - o_p1, (uint8_t *)(hp + o_mk),
-                      &mirrored));
-    if (!mirrored) PLV_HIP_CHECK(plv::memcpy_async(hp + o_p1, dp + o_p1, nn * 37 - o_p1, hipMemcpyDeviceToHost, ctx->stream));
+    TRY(match_ransac_tail(ctx, jobs.job[c].K, MatchBlock((size_t)M[c].n, C.io.p), MatchBlock((size_t)M[c].n, C.flow_pin.p), C.ransac));
   }
   {
     plv::NsScope ns_wait(plv::counters().flow_wait_ns);
@@ -245,15 +217,8 @@ int matching_pair(plv_ctx *ctx, Stereo *S, const std::vector<float> *pts_old[2],
   }
   for (int c = 0; c < 2; ++c) {
     if (!M[c].ran) continue;
-    const size_t nn = (size_t)M[c].n;
-    const char *hp = S->cam[c].flow_pin.as<char>();
-    M[c].p_new.assign((const float *)(hp + nn * 8), (const float *)(hp + nn * 8) + 2 * nn);
-    M[c].n_new.assign((const float *)(hp + nn * 24), (const float *)(hp + nn * 24) + 2 * nn);
-    M[c].mask.assign((const uint8_t *)(hp + nn * 36), (const uint8_t *)(hp + nn * 36) + nn);
-    const int *it = (const int *)(hp + nn * 32);
-    unsigned long long t = 0;
-    for (size_t i = 0; i < nn; ++i) t += (unsigned long long)it[i];
-    plv::counters().lk_iters += t;
+    M[c].n_new.resize(2 * (size_t)M[c].n);  // (p_new and mask have their sizes)
+    (void)match_read_back(MatchBlock((size_t)M[c].n, S->cam[c].flow_pin.p), M[c].p_new.data(), M[c].mask.data(), nullptr, M[c].n_new.data());
   }
   return PLV_OK;
 }
@@ -275,12 +240,12 @@ int feed_fed(plv_ctx *ctx, Stereo *S, double timestamp, const uint8_t *mask_l, c
   std::vector<float> pl, pr;
   std::vector<uint64_t> il, ir;
   if (L.pts_last.empty() && R.pts_last.empty()) {  // :221-240 first pair / lost everything: detect on the current pair
-    TRY(detection_stereo(ctx, S, S->cur, mask_l, mask_r, pl, il, pr, ir));
+    TRY(detection_stereo(ctx, S, S->cur(), mask_l, mask_r, pl, il, pr, ir));
     return move_forward(pl, il, pr, ir);
   }
   // :244-251 top-up on the LAST pair, with the last masks
   pl = L.pts_last, il = L.ids_last, pr = R.pts_last, ir = R.ids_last;
-  TRY(detection_stereo(ctx, S, 1 - S->cur, L.mask_last.empty() ? nullptr : L.mask_last.data(),
+  TRY(detection_stereo(ctx, S, 1 - S->cur(), L.mask_last.empty() ? nullptr : L.mask_last.data(),
                        R.mask_last.empty() ? nullptr : R.mask_last.data(), pl, il, pr, ir));
   // :254-268 temporal KLT per camera, the old positions as the initial flow
   Matching M[2];
@@ -345,11 +310,11 @@ void plv_stereo_destroy(plv_ctx *ctx) {
   Stereo *S = (Stereo *)ctx->stereo_state;
   if (!S) return;
   for (StereoCam &C : S->cam) {
-    DevBuf *bufs[] = {&C.pyr_mem[0], &C.pyr_mem[1], &C.raw, &C.hist, &C.clahe_lut, &C.io, &C.counts, &C.models, &C.info};
-    for (auto *b : bufs) b->release();
+    C.release();
+    C.io.release();
+    C.ransac.release();
     C.img_pin.release();
     C.flow_pin.release();
-    C.det.release_detection();
   }
   S->lr_dev.release();
   S->lr_pin.release();
@@ -377,26 +342,15 @@ int plv_stereo_configure(plv_ctx *ctx, const double *K8_right, int model_right) 
       set_last_error("plv_stereo_configure: intrinsic value %d of the right camera is not finite", i);
       return PLV_E_BADARG;
     }
-  const int W = ctx->cfg.width, H = ctx->cfg.height;
-  if (W < 16 || H < 16) {
-    set_last_error("plv_stereo_configure: image %dx%d too small", W, H);
-    return PLV_E_BADARG;
-  }
   (void)hipSetDevice(ctx->device);
   Stereo *S = stereo_of(ctx, true);
   std::lock_guard<std::mutex> lk(S->mtx);
   if (!S->configured) {
-    S->W = W, S->H = H;
+    S->W = ctx->cfg.width, S->H = ctx->cfg.height;
     for (StereoCam &C : S->cam) {
-      for (int i = 0; i < 2; ++i) {
-        const int bytes = level_geometry(W, H, ctx->cfg.win_size, ctx->cfg.pyr_levels, C.pyr[i]);
-        TRY(C.pyr_mem[i].reserve((size_t)bytes));
-        C.pyr[i].base = C.pyr_mem[i].as<uint8_t>();
-      }
-      TRY(C.hist.reserve(257 * sizeof(unsigned)));  // 256 bins + arrival counter; the pyramid launch leaves it zero for the next image
-      PLV_HIP_CHECK(hipMemsetAsync(C.hist.p, 0, 257 * sizeof(unsigned), ctx->stream));
-      TRY(C.raw.reserve((size_t)W * H));
-      TRY(C.img_pin.reserve((size_t)W * H));
+      C.W = S->W, C.H = S->H;
+      TRY(C.prepare(ctx, "plv_stereo_configure"));
+      TRY(C.img_pin.reserve((size_t)S->W * S->H));
     }
   }
   std::copy(K8_right, K8_right + 8, S->cam[1].K);
@@ -438,11 +392,10 @@ int plv_tracker_feed_stereo(plv_ctx *ctx, double timestamp, const uint8_t *left,
   TRY(check_encoded("plv_tracker_feed_stereo (right)", right, stride_right, encoding, S->W));
   std::lock_guard<std::mutex> lk(S->mtx);  // REF: mtx_feeds of both cameras, TrackKLT.cpp:207-208
   {
-    PyrDesc want{};
-    (void)level_geometry(S->W, S->H, ctx->cfg.win_size, ctx->cfg.pyr_levels, want);
-    if (want.levels != S->cam[0].pyr[0].levels) {
+    const int want = S->cam[0].levels_for(ctx, ctx->cfg.win_size);
+    if (want != S->cam[0].pyr[0].levels) {
       set_last_error("plv_tracker_feed_stereo: a %d x %d window gives %d pyramid levels, the stereo pyramids have %d", ctx->cfg.win_size,
-                     ctx->cfg.win_size, want.levels, S->cam[0].pyr[0].levels);
+                     ctx->cfg.win_size, want, S->cam[0].pyr[0].levels);
       return PLV_E_BADARG;
     }
     if (ctx->cfg.histogram_method == PLV_HIST_CLAHE && (S->W % 8 != 0 || S->H % 8 != 0)) {
@@ -457,14 +410,13 @@ int plv_tracker_feed_stereo(plv_ctx *ctx, double timestamp, const uint8_t *left,
   (void)hipSetDevice(ctx->device);
   ctx->tracker_kind = PLV_TRACKER_STEREO;
   // :50-76 equalisation and pyramid per image, back to back on the stream (no wait between them)
-  const int next = S->fed == 0 ? S->cur : 1 - S->cur;
+  const int next = S->cam[0].next();
   {
     plv::HostPhase ph("stereo feed: two images enqueued");
     TRY(enqueue_image(ctx, S, 0, next, left, stride_left, encoding));
     TRY(enqueue_image(ctx, S, 1, next, right, stride_right, encoding));
   }
-  S->cur = next;
-  S->fed++;
+  for (StereoCam &C : S->cam) C.commit(next);  // (only now: a pair of which one image was refused leaves both cameras where they were)
   return feed_fed(ctx, S, timestamp, mask_left, mask_right);
 }
 
@@ -498,14 +450,7 @@ int plv_stereo_db_ids(plv_ctx *ctx, uint64_t *ids, int cap, int *n) {
   Stereo *S = configured(ctx, "plv_stereo_db_ids");
   if (!S) return PLV_E_BADARG;
   std::lock_guard<std::mutex> lk(S->mtx);
-  std::vector<uint64_t> out;
-  out.reserve(S->db.size());
-  for (const auto &kv : S->db) out.push_back(kv.first);
-  std::sort(out.begin(), out.end());
-  *n = (int)out.size();
-  if (*n > cap) return PLV_E_CAPACITY;
-  if (ids) std::copy(out.begin(), out.end(), ids);
-  return PLV_OK;
+  return export_sorted_ids(S->db, ids, cap, n);
 }
 
 int plv_stereo_db_export_tracks(plv_ctx *ctx, const uint64_t *ids, int n, int cam, int *obs_ptr, double *obs_time, float *obs_uv,
@@ -515,22 +460,11 @@ int plv_stereo_db_export_tracks(plv_ctx *ctx, const uint64_t *ids, int n, int ca
   Stereo *S = configured(ctx, "plv_stereo_db_export_tracks");
   if (!S) return PLV_E_BADARG;
   std::lock_guard<std::mutex> lk(S->mtx);
-  int at = 0;
-  obs_ptr[0] = 0;
-  for (int f = 0; f < n; ++f) {
-    const auto it = S->db.find(ids[f]);
-    if (it != S->db.end()) {
-      const Track &tr = it->second.cam[cam];
-      const int m = (int)tr.t.size();
-      if (at + m > cap_obs) return PLV_E_CAPACITY;
-      if (obs_time) std::copy(tr.t.begin(), tr.t.end(), obs_time + at);
-      if (obs_uv) std::copy(tr.uv.begin(), tr.uv.end(), obs_uv + 2 * (size_t)at);
-      if (obs_uvn) std::copy(tr.uvn.begin(), tr.uvn.end(), obs_uvn + 2 * (size_t)at);
-      at += m;
-    }
-    obs_ptr[f + 1] = at;
-  }
-  return PLV_OK;
+  auto track_of = [S, cam](uint64_t id) -> const Track * {
+    const auto it = S->db.find(id);
+    return it == S->db.end() ? nullptr : &it->second.cam[cam];
+  };
+  return export_tracks(ids, n, track_of, obs_ptr, obs_time, obs_uv, obs_uvn, cap_obs);
 }
 
 // FeatureDatabase::cleanup_measurements(t) (REF: FeatureDatabase.cpp:286-323): Feature::clean_older_measurements over every
@@ -540,10 +474,7 @@ int plv_stereo_db_cleanup_measurements(plv_ctx *ctx, double t) {
   Stereo *S = configured(ctx, "plv_stereo_db_cleanup_measurements");
   if (!S) return PLV_E_BADARG;
   std::lock_guard<std::mutex> lk(S->mtx);
-  for (auto it = S->db.begin(); it != S->db.end();) {
-    const size_t left = drop_before(it->second.cam[0], t) + drop_before(it->second.cam[1], t);
-    it = left == 0 ? S->db.erase(it) : std::next(it);
-  }
+  cleanup_measurements(S->db, t, [](StereoFeature &f, double t_) { return drop_before(f.cam[0], t_) + drop_before(f.cam[1], t_); });
   return PLV_OK;
 }
 
@@ -552,7 +483,7 @@ int plv_stereo_db_remove(plv_ctx *ctx, const uint64_t *ids, int n) {
   Stereo *S = configured(ctx, "plv_stereo_db_remove");
   if (!S) return PLV_E_BADARG;
   std::lock_guard<std::mutex> lk(S->mtx);
-  for (int i = 0; i < n; ++i) S->db.erase(ids[i]);
+  erase_ids(S->db, ids, n);
   return PLV_OK;
 }
 

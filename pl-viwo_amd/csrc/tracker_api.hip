@@ -90,12 +90,6 @@ Tracker *trk(plv_ctx *ctx) {
   return t;
 }
 
-#define TRY(expr)                  \
-  do {                             \
-    int _rc = (expr);              \
-    if (_rc != PLV_OK) return _rc; \
-  } while (0)
-
 }  // namespace
 
 namespace plv {
@@ -602,24 +596,7 @@ int plv_db_export_tracks(plv_ctx *ctx, const uint64_t *ids, int n, int *obs_ptr,
   if (!ctx || !ids || !obs_ptr) return PLV_E_BADARG;
   Tracker *T = trk(ctx);
   std::lock_guard<std::mutex> lk(T->mtx);
-  int at = 0;
-  obs_ptr[0] = 0;
-  for (int f = 0; f < n; ++f) {
-    auto it = T->db.find(ids[f]);
-    if (it != T->db.end()) {
-      const Track &tr = it->second;
-      const int m = (int)tr.t.size();
-      if (at + m > cap_obs) return PLV_E_CAPACITY;
-      for (int i = 0; i < m; ++i) {
-        if (obs_time) obs_time[at + i] = tr.t[i];
-        if (obs_uv) obs_uv[2 * (at + i)] = tr.uv[2 * i], obs_uv[2 * (at + i) + 1] = tr.uv[2 * i + 1];
-        if (obs_uvn) obs_uvn[2 * (at + i)] = tr.uvn[2 * i], obs_uvn[2 * (at + i) + 1] = tr.uvn[2 * i + 1];
-      }
-      at += m;
-    }
-    obs_ptr[f + 1] = at;
-  }
-  return PLV_OK;
+  return export_tracks(ids, n, track_in(T->db), obs_ptr, obs_time, obs_uv, obs_uvn, cap_obs);
 }
 
 // FeatureDatabase::cleanup_measurements(t): drop observations older than t (REF: FeatureDatabase.cpp:286-323)
@@ -627,7 +604,7 @@ int plv_db_cleanup_measurements(plv_ctx *ctx, double t) {
   if (!ctx) return PLV_E_BADARG;
   Tracker *T = trk(ctx);
   std::lock_guard<std::mutex> lk(T->mtx);
-  for (auto it = T->db.begin(); it != T->db.end();) it = drop_before(it->second, t) == 0 ? T->db.erase(it) : std::next(it);
+  cleanup_measurements(T->db, t);
   return PLV_OK;
 }
 
@@ -636,7 +613,7 @@ int plv_db_remove(plv_ctx *ctx, const uint64_t *ids, int n) {
   if (!ctx || (n > 0 && !ids)) return PLV_E_BADARG;
   Tracker *T = trk(ctx);
   std::lock_guard<std::mutex> lk(T->mtx);
-  for (int i = 0; i < n; ++i) T->db.erase(ids[i]);
+  erase_ids(T->db, ids, n);
   return PLV_OK;
 }
 

@@ -28,12 +28,6 @@
 namespace plv {
 namespace {
 
-#define TRY(expr)                  \
-  do {                             \
-    int _rc = (expr);              \
-    if (_rc != PLV_OK) return _rc; \
-  } while (0)
-
 struct WheelArgs {
   plv_wheel_options op;
   plv_wheel_state st;

@@ -34,12 +34,6 @@
 namespace plv {
 namespace {
 
-#define TRY(expr)                  \
-  do {                             \
-    int _rc = (expr);              \
-    if (_rc != PLV_OK) return _rc; \
-  } while (0)
-
 constexpr int kRows = 9, kCols = 12;
 
 struct ZuptArgs {

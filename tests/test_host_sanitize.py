@@ -121,6 +121,46 @@ def test_update_route_plan_and_result_layout_under_sanitizers(tmp_path):
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
 
 
+def test_matching_block_layout_and_row_packing_under_sanitizers(tmp_path):
+    """pl-viwo_amd/csrc/match_block.hpp, the device-free header of the two point front ends, compiled by plain g++ with no HIP header in
+    reach, under AddressSanitizer + UBSan: for every n in 0 .. 4096 and a few up to 2^20 the offsets, the total and the two extents of
+    the temporal matching's block equal the literal expressions the four functions used before (8n, 16n, 24n, 32n, 36n, 37n, 38n;
+    36n - 8n mirrored, 37n - 8n copied), the regions lie apart in the documented order, every field is written and read back through
+    the views in a heap block of exactly `total` bytes; pack_rows for 1 .. 4 bytes per pixel, packed and stride = row + 5, 1 and 7 rows,
+    from a source that ends at the last row's last byte into a destination of exactly row * h bytes."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "front_layout_check")
+    src = os.path.join(ROOT, "tests", "host_sanitize", "front_layout_check.cpp")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", src, "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"), timeout=120)
+    assert r.returncode == 0 and "ok: matching block and pack_rows, 16 row copies" in r.stdout, (r.stdout[-3000:], r.stderr[-4000:])
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+
+
+def test_database_accessors_under_sanitizers(tmp_path):
+    """pl-viwo_amd/csrc/camera_tracks.hpp, the accessors the point, stereo and line databases share (sorted ids, CSR export, erase by id
+    list, cleanup_measurements) under AddressSanitizer + UBSan: hand-made point and line databases and a two-camera feature map; exports
+    with present and missing ids, each nullable output absent in turn, capacities exactly sufficient and one short (the capacity code,
+    and nothing written that the loops they replace did not write), erasure of absent ids, a cleanup that empties one camera of a
+    feature and one that empties both — each against a plain restatement in the check."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "track_db_check")
+    src = os.path.join(ROOT, "tests", "host_sanitize", "track_db_check.cpp")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+           "-I" + os.path.join(ROOT, "include"), src, "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"), timeout=120)
+    import re
+    m = re.search(r"ok: database accessors, (\d+) exports", r.stdout)
+    assert r.returncode == 0 and m and int(m.group(1)) > 100, (r.stdout[-3000:], r.stderr[-4000:])
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+
+
 def test_helper_threads_are_clamped_to_the_allowed_cpus(tmp_path):
     """the default number of polling helper threads of the line detector's host stage is min(7, allowed CPUs - 2),
     at most two below six CPUs, none below three — the caller's thread and the line worker keep a CPU each."""
