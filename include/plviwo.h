@@ -418,7 +418,8 @@ int plv_db_remove(plv_ctx *ctx, const uint64_t *ids, int n);
  * is a second tracker beside the monocular one, with its own pyramids, last points, id counter and a database whose features keep
  * their observations per camera (ov_core::Feature).  A context takes images through one of the two: once plv_tracker_feed_stereo
  * has taken a pair, plv_tracker_feed* and plv_camera_frame return PLV_E_BADARG, and the reverse.  The updates
- * (plv_camera_update_*, plv_camera_try_update) read the monocular database only.
+ * (plv_camera_update_*, plv_camera_try_update) read the monocular database only; the stereo database is consumed by
+ * plv_stereo_update_points ("The stereo point update" below).
  * Every call below returns PLV_E_BADARG with a plv_last_error text for an argument it refuses and then leaves the stereo tracker,
  * both cameras' pyramids and the database as they were. */
 int plv_stereo_configure(plv_ctx *ctx, const double *K8_right, int model_right);
@@ -787,6 +788,84 @@ int plv_camera_update_list(plv_ctx *ctx, int which, int cap_feat, int cap_obs, i
  * landmark's feature is no longer in the tracker database or update_fail_count[i] > 1 (nullable = all 0).  The
  * caller then removes flagged landmarks with plv_cov_marginalize (StateHelper::marginalize_slam). */
 int plv_slam_marg_flags(plv_ctx *ctx, int n_slam, const uint64_t *slam_ids, const int *update_fail_count, uint8_t *should_marg);
+
+/* ---------------------------------------------------------------------------------------------
+ * The stereo point update: both cameras of a track in one MSCKF update.
+ *
+ * The reference has no separate stereo update: CamHelper::get_features / get_imu_poses / get_cam_poses / feature_triangulation /
+ * moving_consistency / get_feature_jacobian_full loop over Feature::timestamps, a map from camera id to that camera's observations,
+ * and read cam_extrinsic / cam_intrinsic / cam_intrinsic_model by camera id (REF: PL-VIWO/src/update/cam/CamHelper.cpp:70-75,
+ * 137-143, 345-347, 378-380, 436-441).  The calls below do that for the pair of the stereo tracker: camera 0 is the
+ * plv_state_view's camera (R_ItoC, p_IinC, intrinsics, extrinsic_state_id, intrinsic_state_id) with the context's model
+ * (plv_set_camera_model); camera 1 comes as a plv_camera_side.  The time offset is one object for a stereo pair (REF: State.cpp:
+ * 102-103): the view's cam_dt / dt_state_id serve both cameras.
+ *
+ * Order and anchor.  Feature::timestamps is a std::unordered_map<size_t, ...> that feed_stereo fills with key 0, then key 1; with
+ * libstdc++ such a map iterates 1, then 0 (a map holding one key iterates that key).  Hence, everywhere below:
+ *   - the observations of a feature seen by both cameras are listed camera 1 first (oldest to newest), then camera 0;
+ *   - the triangulation anchor is the last observation of the camera with strictly more observations, camera 1 on a tie — the
+ *     first one iterated (REF: open_vins/ov_core/src/feat/FeatureInitializer.cpp:36-46); plv_triangulate_stereo counts the
+ *     observations that have bounding clones (the others never reach the reference's triangulation, CamHelper.cpp:649-661);
+ *   - the Jacobian rows follow the same order.
+ * The row order moves results by rounding only; the anchor decides the depth and baseline tests.
+ * plv_stereo_tracks with another order (a camera-0 observation in front of a camera-1 observation of the same feature), or an
+ * obs_cam value above 1, is refused with PLV_E_BADARG before anything is launched.
+ *
+ * Not built for a stereo context (PLV_E_BADARG where a call could be asked for it): use_imu_res / use_imu_cov at the update level
+ * (plv_update_options::cpi, plv_state_view::use_imu_cov; the low-level calls still honour res_R / res_p of the tracks), in-state
+ * landmarks (max_slam), the line update and its point_used list, plv_camera_try_update / plv_camera_frame, plv_decision_trace. */
+typedef struct plv_camera_side { /* camera 1 of the pair on the update side */
+  double R_ItoC[9], p_IinC[3]; /* State::cam_extrinsic.at(1): Rot() row-major, pos()                   */
+  double intrinsics[8];        /* State::cam_intrinsic.at(1) value                                      */
+  int model;                   /* PLV_CAM_* (State::cam_intrinsic_model.at(1))                           */
+  int extrinsic_state_id;      /* covariance index, -1: not estimated                                    */
+  int intrinsic_state_id;      /* ... -1: not estimated                                                  */
+} plv_camera_side;
+
+typedef struct plv_stereo_tracks {
+  plv_tracks tracks;     /* both cameras' observations of every feature, in the order defined above     */
+  const uint8_t *obs_cam; /* [n_obs] camera of each observation: 0 or 1                                  */
+} plv_stereo_tracks;
+
+/* FeatureDatabase::append_new_measurements for one camera of one feature of the stereo database (the twin of
+ * plv_db_append_measurements; plv_stereo_configure comes first).  For callers with their own tracker, and the tests. */
+int plv_stereo_db_append_measurements(plv_ctx *ctx, uint64_t id, int cam, int n, const double *t, const float *uv, const float *uvn);
+
+/* Column order of the stacked stereo Jacobians: [ext0 6][int0 8][dt 1][ext1 6][int1 8], each block present only when its state id
+ * is >= 0, then every clone an observation interpolates over, in first-seen order over the batch.  Host integer logic.  A state
+ * id of `right` that equals one of camera 0's (or the time offset's) is refused. */
+int plv_stereo_jacobian_columns(const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *tracks, int *col_to_state,
+                                int cap, int *k_out);
+
+/* plv_triangulate over both cameras: get_cam_poses with each observation's own extrinsics, single_triangulation + single_gaussnewton
+ * over all observations (anchor as defined above), and moving_consistency's error as the reference forms it: the mean pixel error
+ * per camera (each with its own intrinsics and model), then the mean of those over the cameras that have observations (REF:
+ * CamHelper.cpp:469-477) — not the mean over all observations.  res_R / res_p of the embedded tracks are honoured. */
+int plv_triangulate_stereo(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *tracks,
+                           const plv_tri_options *opt, double *p_FinG, uint8_t *ok, double *reproj_err);
+
+/* plv_build_jacobians with every observation's own extrinsics, intrinsics, distortion model and calibration columns
+ * (get_feature_jacobian_full).  Output layout as plv_build_jacobians; the _resident twin leaves the batch staged for
+ * plv_msckf_update_resident. */
+int plv_build_jacobians_stereo(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *tracks, int k,
+                               const int *col_to_state, int ld, int *rows, double *Hf, double *Hx, double *res);
+int plv_build_jacobians_stereo_resident(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right,
+                                        const plv_stereo_tracks *tracks, int k, const int *col_to_state, int ld);
+
+/* plv_camera_update_points over the stereo database.  Pool: features_containing_older(2nd-oldest clone) +
+ * features_not_containing_newer(t_prev_frame), tested over the observations of both cameras; remove_unusable_measurements per camera
+ * with the shared dt; sort by total observation count, ties by ascending id; the loop of CamHelper.cpp:649-700 (observations
+ * without bounding clones go back, a feature with fewer than 2 left goes back, triangulation, the 3 px consistency test, the cap
+ * max_msckf); msckf_update on the resident covariance; cleanup_features (what the gate rejected and whatever was left over
+ * returns to the stereo database, per camera; observations older than the oldest clone are dropped when window_full).
+ * Route: one triangulation launch over the pool, the selection on the host, one Jacobian launch into the resident batch, the
+ * resident update tail (DESIGN.md "The stereo point update").  A feature with more than max_obs usable observations is not
+ * truncated here: it is refused with PLV_E_CAPACITY and the pool returns to the database.
+ * PLV_E_BADARG with a plv_last_error text, the database, the covariance and a staged batch as they were: opt->max_slam != 0,
+ * opt->cpi != NULL, st->use_imu_cov, a context whose stereo tracker is not configured, right == NULL, a state id of `right` that
+ * collides with camera 0's, plv_decision_trace on.  plv_update_result as by plv_camera_update_points; n_slam and n_init are 0. */
+int plv_stereo_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_update_options *opt, double *dx,
+                             plv_update_result *res, uint64_t *msckf_ids, uint8_t *accepted, double *p_FinG);
 
 /* ---------------------------------------------------------------------------------------------
  * UpdaterCamera::try_update, line half, as one call (a15/a16, a27-a29, a31).  Call after the caller has

@@ -181,6 +181,17 @@ def load_library():
         "plv_stereo_db_export_tracks": (C.c_int, [vp, u64p, C.c_int, C.c_int, ip, dp, fp, fp, C.c_int]),
         "plv_stereo_db_cleanup_measurements": (C.c_int, [vp, C.c_double]),
         "plv_stereo_db_remove": (C.c_int, [vp, u64p, C.c_int]),
+        "plv_stereo_db_append_measurements": (C.c_int, [vp, C.c_uint64, C.c_int, C.c_int, dp, fp, fp]),
+        "plv_stereo_jacobian_columns": (C.c_int, [C.POINTER(PlvStateView), C.POINTER(PlvCameraSide), C.POINTER(PlvStereoTracks), ip,
+                                                  C.c_int, ip]),
+        "plv_triangulate_stereo": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvCameraSide), C.POINTER(PlvStereoTracks),
+                                             C.POINTER(PlvTriOptions), dp, u8p, dp]),
+        "plv_build_jacobians_stereo": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvCameraSide), C.POINTER(PlvStereoTracks),
+                                                 C.c_int, ip, C.c_int, ip, dp, dp, dp]),
+        "plv_build_jacobians_stereo_resident": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvCameraSide),
+                                                          C.POINTER(PlvStereoTracks), C.c_int, ip, C.c_int]),
+        "plv_stereo_update_points": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvCameraSide), C.POINTER(PlvUpdateOptions), dp,
+                                               C.POINTER(PlvUpdateResult), u64p, u8p, dp]),
         "plv_cpi_noise": (C.c_int, [C.POINTER(PlvStateView), C.POINTER(PlvCpiTable), C.c_int, dp, dp, ip, u8p]),
         "plv_triangulate": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvTracks), C.POINTER(PlvTriOptions), dp, u8p, dp]),
         "plv_jacobian_columns": (C.c_int, [C.POINTER(PlvStateView), C.POINTER(PlvTracks), ip, C.c_int, ip]),
@@ -373,6 +384,15 @@ class PlvTracks(C.Structure):
         ("obs_uvn", C.POINTER(C.c_float)),
         ("res_Q", C.POINTER(C.c_double)), ("res_clone", C.POINTER(C.c_int)),
     ]
+
+
+class PlvCameraSide(C.Structure):
+    _fields_ = [("R_ItoC", C.c_double * 9), ("p_IinC", C.c_double * 3), ("intrinsics", C.c_double * 8), ("model", C.c_int),
+                ("extrinsic_state_id", C.c_int), ("intrinsic_state_id", C.c_int)]
+
+
+class PlvStereoTracks(C.Structure):
+    _fields_ = [("tracks", PlvTracks), ("obs_cam", C.POINTER(C.c_uint8))]
 
 
 class PlvLineTracks(C.Structure):
@@ -834,6 +854,30 @@ class Tracks:
         self.rQ = np.ascontiguousarray(res_Q, dtype=np.float64).reshape(-1, 36) if res_Q is not None else None
         self.rc = np.ascontiguousarray(res_clone, dtype=np.int32) if res_clone is not None else None
         v.res_Q, v.res_clone = _dp(self.rQ), _ip(self.rc)
+        self.c = v
+
+
+class CameraSide:
+    """plv_camera_side: camera 1 of a stereo pair on the update side (camera 0 is the StateView's)."""
+
+    def __init__(self, R_ItoC, p_IinC, intrinsics, model=PLV_CAM_RADTAN, extrinsic_state_id=-1, intrinsic_state_id=-1):
+        v = PlvCameraSide()
+        v.R_ItoC = (C.c_double * 9)(*np.asarray(R_ItoC, dtype=np.float64).ravel())
+        v.p_IinC = (C.c_double * 3)(*np.asarray(p_IinC, dtype=np.float64).ravel())
+        v.intrinsics = (C.c_double * 8)(*np.asarray(intrinsics, dtype=np.float64).ravel())
+        v.model, v.extrinsic_state_id, v.intrinsic_state_id = int(model), int(extrinsic_state_id), int(intrinsic_state_id)
+        self.c = v
+
+
+class StereoTracks:
+    """plv_stereo_tracks: a Tracks plus the camera (0 / 1) of every observation; within a feature camera 1's observations come first."""
+
+    def __init__(self, obs_ptr, obs_time, obs_uv, obs_cam, p_FinG, **kw):
+        self.tracks = Tracks(obs_ptr, obs_time, obs_uv, p_FinG, **kw)
+        self.cam = np.ascontiguousarray(obs_cam, dtype=np.uint8)
+        v = PlvStereoTracks()
+        v.tracks = self.tracks.c
+        v.obs_cam = _u8p(self.cam)
         self.c = v
 
 
@@ -2105,6 +2149,60 @@ class Context:
     def stereo_db_remove(self, ids):
         ids = np.ascontiguousarray(ids, dtype=np.uint64)
         self._chk(self.lib.plv_stereo_db_remove(self.h, ids.ctypes.data_as(C.POINTER(C.c_uint64)), len(ids)))
+
+    # ---- the stereo point update: both cameras of a track in one MSCKF update (camera 1: a CameraSide)
+    def stereo_db_append_measurements(self, fid, cam, t, uv, uvn):
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+        uvn = np.ascontiguousarray(uvn, dtype=np.float32).reshape(-1, 2)
+        self._chk(self.lib.plv_stereo_db_append_measurements(self.h, int(fid), int(cam), len(t), _dp(t), _fp(uv), _fp(uvn)))
+
+    def stereo_jacobian_columns(self, st, right, tr, cap=1024):
+        cols = np.zeros(cap, dtype=np.int32)
+        k = C.c_int()
+        self._chk(self.lib.plv_stereo_jacobian_columns(C.byref(st.c), C.byref(right.c) if right is not None else None, C.byref(tr.c),
+                                                       _ip(cols), cap, C.byref(k)))
+        return cols[:k.value].copy()
+
+    def triangulate_stereo(self, st, right, tr, min_dist=0.1, max_dist=60.0, max_cond=1e4, max_baseline=40.0, refine=True):
+        opt = PlvTriOptions(min_dist, max_dist, max_cond, max_baseline, 1 if refine else 0)
+        F = tr.c.tracks.n_feat
+        p, ok, err = np.zeros((F, 3)), np.zeros(F, dtype=np.uint8), np.zeros(F)
+        self._chk(self.lib.plv_triangulate_stereo(self.h, C.byref(st.c), C.byref(right.c) if right is not None else None, C.byref(tr.c),
+                                                  C.byref(opt), _dp(p), _u8p(ok), _dp(err)))
+        return p, ok, err
+
+    def build_jacobians_stereo(self, st, right, tr, cols, ld):
+        F, k = tr.c.tracks.n_feat, len(cols)
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        rows = np.zeros(F, dtype=np.int32)
+        Hf, Hx, res = np.zeros((F, 3, ld)), np.zeros((F, k, ld)), np.zeros((F, ld))
+        self._chk(self.lib.plv_build_jacobians_stereo(self.h, C.byref(st.c), C.byref(right.c) if right is not None else None,
+                                                      C.byref(tr.c), k, _ip(cols), ld, _ip(rows), _dp(Hf), _dp(Hx), _dp(res)))
+        return rows, Hf, Hx, res
+
+    def build_jacobians_stereo_resident(self, st, right, tr, cols, ld):
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        self._chk(self.lib.plv_build_jacobians_stereo_resident(self.h, C.byref(st.c), C.byref(right.c) if right is not None else None,
+                                                               C.byref(tr.c), len(cols), _ip(cols), ld))
+
+    def stereo_update_points(self, st, right, n, max_msckf, max_obs, t_prev_frame, state_time, window_full=True, chi2_mult=1.0,
+                             min_dist=0.1, max_dist=60.0, max_cond=1e4, max_baseline=40.0, refine=True, max_slam=0, cpi=None):
+        """plv_stereo_update_points: the dict camera_update_points returns"""
+        opt = PlvUpdateOptions(max_msckf, max_obs, chi2_mult, PlvTriOptions(min_dist, max_dist, max_cond, max_baseline, 1 if refine else 0),
+                               t_prev_frame, state_time, 1 if window_full else 0, max_slam, 0, None, 10,
+                               C.pointer(cpi.c) if cpi is not None else None)
+        res = PlvUpdateResult()
+        dx = np.zeros(n)
+        ids = np.zeros(max_msckf, dtype=np.uint64)
+        acc = np.zeros(max_msckf, dtype=np.uint8)
+        p = np.zeros((max_msckf, 3))
+        self._chk(self.lib.plv_stereo_update_points(self.h, C.byref(st.c), C.byref(right.c) if right is not None else None, C.byref(opt),
+                                                    _dp(dx), C.byref(res), _u64p(ids), _u8p(acc), _dp(p)))
+        m = res.n_msckf
+        return dict(dx=dx, n_pool=res.n_pool, n_msckf=m, n_accepted=res.n_accepted, n_rows=res.n_rows, n_returned=res.n_returned,
+                    status=res.status, ids=ids[:m].copy(), accepted=acc[:m].copy(), p_FinG=p[:m].copy(), n_slam=res.n_slam,
+                    n_init=res.n_init, n_truncated=res.n_truncated)
 
     def triangulate(self, st, tr, min_dist=0.1, max_dist=60.0, max_cond=1e4, max_baseline=40.0, refine=True):
         opt = PlvTriOptions(min_dist, max_dist, max_cond, max_baseline, 1 if refine else 0)

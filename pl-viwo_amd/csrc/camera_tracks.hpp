@@ -77,6 +77,21 @@ struct LineTrack {  // LineFeature, one camera   REF: linefeat/LineFeature.h:22-
   int D = 0;
 };
 
+struct StereoFeature {  // ov_core::Feature of a stereo pair: the observations of one id, per camera
+  Track cam[2];
+};
+
+// the observation times of a feature, over all its cameras, and how many there are (feat_sort's track length, REF CamHelper.cpp:777-787)
+template <class TrackT, class Fn> void each_time(const TrackT &tr, Fn fn) {
+  for (double t : tr.t) fn(t);
+}
+template <class Fn> void each_time(const StereoFeature &f, Fn fn) {
+  each_time(f.cam[0], fn);
+  each_time(f.cam[1], fn);
+}
+template <class TrackT> size_t n_meas(const TrackT &tr) { return tr.t.size(); }
+inline size_t n_meas(const StereoFeature &f) { return f.cam[0].t.size() + f.cam[1].t.size(); }
+
 // what a track that starts from another one's observations takes along besides them: nothing for a point; a line's direction class
 // and point list (copy_to_db copies the feature's point list)
 inline void copy_track_meta(Track &, const Track &) {}
@@ -233,10 +248,10 @@ template <class TrackT> void take_pool(TrackMap<TrackT> &db, double t_old, doubl
   take.clear();
   for (auto it = db.begin(); it != db.end(); ++it) {
     bool older = false, newer = false;
-    for (double t : it->second.t) {
+    each_time(it->second, [&](double t) {
       older = older || t < t_old;
       newer = newer || t > t_new;
-    }
+    });
     if (older || !newer) take.emplace_back(it->first, it);
   }
   std::sort(take.begin(), take.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
@@ -249,7 +264,7 @@ template <class TrackT> void take_pool(TrackMap<TrackT> &db, double t_old, doubl
 template <class TrackT> void sort_long_first(std::vector<PoolCand<TrackT>> &pool) {
   static thread_local std::vector<std::pair<int, int>> ord;
   ord.clear();
-  for (size_t i = 0; i < pool.size(); ++i) ord.emplace_back(-(int)pool[i].tr.t.size(), (int)i);
+  for (size_t i = 0; i < pool.size(); ++i) ord.emplace_back(-(int)n_meas(pool[i].tr), (int)i);
   std::sort(ord.begin(), ord.end());
   std::vector<PoolCand<TrackT>> sorted;
   sorted.reserve(pool.size());
@@ -522,6 +537,12 @@ int return_rejected(const std::vector<PoolCand<TrackT>> &pool, const Selection<T
   return n_accepted;
 }
 
+// tr's observations behind d's
+template <class TrackT> void append_track(TrackT &d, const TrackT &tr) {
+  d.t.insert(d.t.end(), tr.t.begin(), tr.t.end());
+  d.uv.insert(d.uv.end(), tr.uv.begin(), tr.uv.end());
+  d.uvn.insert(d.uvn.end(), tr.uvn.begin(), tr.uvn.end());
+}
 // append_new_measurements (REF FeatureDatabase.cpp): tr's observations appended to the database's track of id — tr itself when the
 // database has none.  The caller holds the database's lock.
 template <class TrackT> typename TrackMap<TrackT>::iterator put_track(TrackMap<TrackT> &db, uint64_t id, TrackT &tr) {
@@ -530,9 +551,7 @@ template <class TrackT> typename TrackMap<TrackT>::iterator put_track(TrackMap<T
   if (ins.second) {
     d = std::move(tr);
   } else {
-    d.t.insert(d.t.end(), tr.t.begin(), tr.t.end());
-    d.uv.insert(d.uv.end(), tr.uv.begin(), tr.uv.end());
-    d.uvn.insert(d.uvn.end(), tr.uvn.begin(), tr.uvn.end());
+    append_track(d, tr);
   }
   return ins.first;
 }

@@ -43,7 +43,7 @@ int check_views(const plv_state_view *st, const plv_tracks *tr) {
 // Column order of a batch: every clone an observation interpolates over, in first-seen order.  Points (lines = false) put the
 // calibration blocks in front, lines the time offset behind each new window.
 int jacobian_columns(const plv_state_view *st, int n, const int *obs_ptr, const double *obs_time, bool lines, int *col_to_state, int cap,
-                     int *k_out) {
+                     int *k_out, const plv_camera_side *right = nullptr) {
   int k = 0;
   auto push = [&](int id, int size) {
     if (id < 0) return true;
@@ -55,6 +55,8 @@ int jacobian_columns(const plv_state_view *st, int n, const int *obs_ptr, const 
   };
   // REF: CamHelper.cpp:74-95 calibration blocks first, then :98-110 interpolation poses in first-seen order
   if (!lines && (!push(st->extrinsic_state_id, 6) || !push(st->intrinsic_state_id, 8) || !push(st->dt_state_id, 1))) return PLV_E_CAPACITY;
+  // a stereo pair (plv_stereo_jacobian_columns): camera 1's calibration blocks behind camera 0's and the shared time offset
+  if (right && (!push(right->extrinsic_state_id, 6) || !push(right->intrinsic_state_id, 8))) return PLV_E_CAPACITY;
   // (a window start that has been seen adds nothing: 700 observations meet ~14 distinct windows, and the search through the
   // column list per pose was 29 us of the caller's thread in front of the point launch at configs[2])
   std::vector<uint8_t> seen_s0((size_t)std::max(st->n_clones, 1), 0);
@@ -198,6 +200,11 @@ struct StageExtra {  // optional riders of the packed block (one-submission upda
   const uint8_t *d_spec_meta = nullptr, *d_spec_prevalid = nullptr;
   int *d_obs_end = nullptr;
   float *d_obs_uv = nullptr;
+  // a stereo pair (plv_stereo_tracks): the two cameras' table and every observation's camera
+  const CamSide *cams = nullptr;
+  const uint8_t *obs_cam = nullptr;
+  const CamSide *d_cams = nullptr;
+  const uint8_t *d_obs_cam = nullptr;
 };
 int stage_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *st, const plv_tracks *tr, int k,
                  const int *col_to_state, int ld, JacParams &P, StageExtra *ex = nullptr) {
@@ -224,6 +231,9 @@ int stage_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *s
   if (ex && ex->uvn) xuvn = B.add<2>(ex->uvn, nobs);
   if (ex && ex->flags) xfl = B.add(ex->flags, F);
   if (!cs) TRY(S.add_res_noise(tr->res_Q, tr->res_clone, nobs));
+  StageBlock::Slot<CamSide> xcam;
+  StageBlock::Slot<uint8_t> xoc;
+  if (ex && ex->cams) xcam = B.add(ex->cams, 2), xoc = B.add(ex->obs_cam, nobs);
   if (spec) {
     sli = B.add(ex->spec_li, F), sme = B.add(ex->spec_meta, F), spv = B.add(ex->spec_prevalid, F);
     send = B.add(tr->obs_ptr + 1, F);  // (overwritten by spec_select_kernel)
@@ -261,6 +271,7 @@ int stage_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *s
   if (spec) P.in_bytes = (int)B.offset(of);
   if (ex) {
     ex->d_uvn = B.dev(xuvn), ex->d_flags = B.dev(xfl);
+    ex->d_cams = B.dev(xcam), ex->d_obs_cam = B.dev(xoc);
     if (spec) {
       ex->d_spec_li = B.dev(sli), ex->d_spec_meta = B.dev(sme), ex->d_spec_prevalid = B.dev(spv);
       ex->d_obs_end = const_cast<int *>(B.dev(send)), ex->d_obs_uv = const_cast<float *>(B.dev(uv));
@@ -673,6 +684,207 @@ int plv_triangulate(plv_ctx *ctx, const plv_state_view *st, const plv_tracks *tr
   PLV_HIP_CHECK(plv::memcpy_async(d + o_uvn, tr->obs_uvn, (size_t)nobs * 8, hipMemcpyHostToDevice, ctx->stream));
   TRY(launch_triangulate(ctx, P, (double *)(d + o_pose), (unsigned char *)(d + o_valid), (const float *)(d + o_uvn), *opt,
                          (double *)(d + o_p), (unsigned char *)(d + o_ok), (double *)(d + o_err), max_obs(tr->obs_ptr, F)));
+  PLV_HIP_CHECK(plv::memcpy_async(p_FinG, d + o_p, (size_t)F * 24, hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::memcpy_async(ok, d + o_ok, (size_t)F, hipMemcpyDeviceToHost, ctx->stream));
+  if (reproj_err) PLV_HIP_CHECK(plv::memcpy_async(reproj_err, d + o_err, (size_t)F * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
+  ctx->prof.collect();
+  return PLV_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ stereo pair (plv_stereo_tracks)
+namespace {
+
+bool ids_overlap(int a, int na, int b, int nb) { return a >= 0 && b >= 0 && a < b + nb && b < a + na; }
+
+}  // namespace
+namespace plv {
+int plv_stereo_side_check(const char *what, const plv_state_view *st, const plv_camera_side *right) {
+  if (!st || !right) {
+    set_last_error("%s: no state view or no plv_camera_side for camera 1", what);
+    return PLV_E_BADARG;
+  }
+  if (right->model != PLV_CAM_RADTAN && right->model != PLV_CAM_EQUIDISTANT) {
+    set_last_error("%s: camera model %d of camera 1 unknown", what, right->model);
+    return PLV_E_BADARG;
+  }
+  const int e1 = right->extrinsic_state_id, i1 = right->intrinsic_state_id;
+  if (ids_overlap(e1, 6, i1, 8) || ids_overlap(e1, 6, st->extrinsic_state_id, 6) || ids_overlap(e1, 6, st->intrinsic_state_id, 8) ||
+      ids_overlap(e1, 6, st->dt_state_id, 1) || ids_overlap(i1, 8, st->extrinsic_state_id, 6) || ids_overlap(i1, 8, st->intrinsic_state_id, 8) ||
+      ids_overlap(i1, 8, st->dt_state_id, 1)) {
+    set_last_error("%s: a state id of camera 1 (extrinsics %d, intrinsics %d) collides with camera 0's or the time offset's", what, e1, i1);
+    return PLV_E_BADARG;
+  }
+  return PLV_OK;
+}
+}  // namespace plv
+namespace {
+// ... and of the tracks, before anything is staged: an observation camera above 1, a camera-0 observation in front of a camera-1 one
+int check_stereo(const char *what, const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *s) {
+  TRY(plv_stereo_side_check(what, st, right));
+  if (!s || !s->obs_cam) {
+    set_last_error("%s: no tracks or no obs_cam", what);
+    return PLV_E_BADARG;
+  }
+  const plv_tracks &t = s->tracks;
+  if (t.n_feat < 1 || !t.obs_ptr) {
+    set_last_error("%s: no features", what);
+    return PLV_E_BADARG;
+  }
+  for (int f = 0; f < t.n_feat; ++f) {
+    if (t.obs_ptr[f + 1] < t.obs_ptr[f]) return PLV_E_BADARG;
+    for (int o = t.obs_ptr[f]; o < t.obs_ptr[f + 1]; ++o) {
+      if (s->obs_cam[o] > 1) {
+        set_last_error("%s: observation %d is of camera %d, a stereo pair has cameras 0 and 1", what, o, (int)s->obs_cam[o]);
+        return PLV_E_BADARG;
+      }
+      if (o > t.obs_ptr[f] && s->obs_cam[o] > s->obs_cam[o - 1]) {
+        set_last_error("%s: feature %d lists a camera-0 observation in front of a camera-1 observation (camera 1 comes first)", what, f);
+        return PLV_E_BADARG;
+      }
+    }
+  }
+  return PLV_OK;
+}
+
+void fill_cam_sides(const plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, int k, const int *col_to_state, CamSide *cams) {
+  auto col_of = [&](int sid) {
+    for (int j = 0; sid >= 0 && j < k; ++j)
+      if (col_to_state[j] == sid) return j;
+    return -1;
+  };
+  memset(cams, 0, 2 * sizeof(CamSide));
+  memcpy(cams[0].R_ItoC, st->R_ItoC, sizeof cams[0].R_ItoC), memcpy(cams[1].R_ItoC, right->R_ItoC, sizeof cams[1].R_ItoC);
+  memcpy(cams[0].p_IinC, st->p_IinC, sizeof cams[0].p_IinC), memcpy(cams[1].p_IinC, right->p_IinC, sizeof cams[1].p_IinC);
+  memcpy(cams[0].K, st->intrinsics, sizeof cams[0].K), memcpy(cams[1].K, right->intrinsics, sizeof cams[1].K);
+  cams[0].cam_model = ctx->cam_model, cams[1].cam_model = right->model;
+  cams[0].col_ext = col_of(st->extrinsic_state_id), cams[1].col_ext = col_of(right->extrinsic_state_id);
+  cams[0].col_int = col_of(st->intrinsic_state_id), cams[1].col_int = col_of(right->intrinsic_state_id);
+}
+
+int build_stereo_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *st, const plv_camera_side *right,
+                           const plv_stereo_tracks *s, int k, const int *col_to_state, int ld) {
+  TRY(check_stereo("stereo jacobians", st, right, s));
+  TRY(check_views(st, &s->tracks));
+  if (k < 1 || ld < 2 || !col_to_state) return PLV_E_BADARG;
+  const int F = s->tracks.n_feat;
+  TRY(reserve_batch(ctx, us, F, 3, k, ld));
+  CamSide cams[2];
+  fill_cam_sides(ctx, st, right, k, col_to_state, cams);
+  StageExtra ex;
+  ex.cams = cams, ex.obs_cam = s->obs_cam;
+  JacParams P{};
+  TRY(stage_inputs(ctx, us, st, &s->tracks, k, col_to_state, ld, P, &ex));
+  return launch_batch(
+      ctx, us, P, F, 3, k, col_to_state, ld, false, false, nullptr, nullptr, [](const GatherArgs *, int) { return (int)PLV_E_BADARG; },
+      [&] {
+        P.cols_out = us->bcols.as<int>();
+        return launch_jacobians_stereo(ctx, P, ex.d_cams, ex.d_obs_cam);
+      });
+}
+
+}  // namespace
+
+extern "C" {
+
+int plv_stereo_jacobian_columns(const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *s, int *col_to_state, int cap,
+                                int *k_out) {
+  if (!col_to_state || !k_out) return PLV_E_BADARG;
+  TRY(check_stereo("plv_stereo_jacobian_columns", st, right, s));
+  plv_tracks t2 = s->tracks;  // (the columns read times only)
+  if (!t2.p_FinG) t2.p_FinG = t2.p_FinG_fej = st->clone_p;
+  if (!t2.p_FinG_fej) t2.p_FinG_fej = t2.p_FinG;
+  TRY(check_views(st, &t2));
+  return jacobian_columns(st, t2.n_feat, t2.obs_ptr, t2.obs_time, false, col_to_state, cap, k_out, right);
+}
+
+int plv_build_jacobians_stereo_resident(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *s,
+                                        int k, const int *col_to_state, int ld) {
+  if (!ctx) return PLV_E_BADARG;
+  (void)hipSetDevice(ctx->device);
+  auto *us = plv_update_state(ctx);
+  TRY(build_stereo_on_device(ctx, us, st, right, s, k, col_to_state, ld));
+  us->b_single_use = true;  // consumed in place by the next plv_msckf_update_resident (which projects it first)
+  return PLV_OK;            // stream-ordered; no host synchronisation
+}
+
+int plv_build_jacobians_stereo(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *s, int k,
+                               const int *col_to_state, int ld, int *rows, double *Hf, double *Hx, double *res) {
+  if (!ctx || !rows || !Hf || !Hx || !res) return PLV_E_BADARG;
+  (void)hipSetDevice(ctx->device);
+  auto *us = plv_update_state(ctx);
+  TRY(build_stereo_on_device(ctx, us, st, right, s, k, col_to_state, ld));
+  us->b_single_use = false;
+  return download_batch(ctx, us, s->tracks.n_feat, 3, k, ld, rows, Hf, Hx, res);
+}
+
+int plv_triangulate_stereo(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *s,
+                           const plv_tri_options *opt, double *p_FinG, uint8_t *ok, double *reproj_err) {
+  if (!ctx || !opt || !p_FinG || !ok) return PLV_E_BADARG;
+  TRY(check_stereo("plv_triangulate_stereo", st, right, s));
+  (void)hipSetDevice(ctx->device);
+  auto *us = plv_update_state(ctx);
+  plv_tracks t2 = s->tracks;  // p_FinG of the view is an OUTPUT here, as in plv_triangulate
+  if (!t2.p_FinG) t2.p_FinG = p_FinG;
+  if (!t2.p_FinG_fej) t2.p_FinG_fej = t2.p_FinG;
+  TRY(check_views(st, &t2));
+  if (!t2.obs_uvn) {
+    set_last_error("plv_triangulate_stereo: plv_tracks.obs_uvn is required");
+    return PLV_E_BADARG;
+  }
+  const int F = t2.n_feat, nobs = t2.obs_ptr[F];
+  // The kernel anchors on a feature's last observation with bounding clones.  The reference's anchor is the last observation of the
+  // camera with strictly more of them, camera 1 on a tie (FeatureInitializer.cpp:36-46): where that is camera 1, the feature's two
+  // blocks change places in the staged copy — camera 0's observations, then camera 1's.  The sums over the observations then run in
+  // that order: a difference by rounding.
+  std::vector<int> src((size_t)nobs);
+  BoundingMemo start_of(*st);
+  for (int f = 0; f < F; ++f) {
+    const int a = t2.obs_ptr[f], b = t2.obs_ptr[f + 1];
+    int m = a, n_valid[2] = {0, 0};
+    while (m < b && s->obs_cam[m] == 1) ++m;  // [a, m) camera 1, [m, b) camera 0
+    for (int o = a; o < b; ++o) n_valid[s->obs_cam[o]] += start_of(t2.obs_time[o] + st->cam_dt) >= 0;
+    const bool anchor_right = n_valid[1] >= n_valid[0];
+    int at = a;
+    if (anchor_right) {
+      for (int o = m; o < b; ++o) src[at++] = o;
+      for (int o = a; o < m; ++o) src[at++] = o;
+    } else {
+      for (int o = a; o < b; ++o) src[at++] = o;
+    }
+  }
+  std::vector<double> ot((size_t)nobs), rR, rp;
+  std::vector<float> uv(2 * (size_t)nobs), uvn(2 * (size_t)nobs);
+  std::vector<uint8_t> oc((size_t)nobs);
+  if (t2.res_R) rR.resize(9 * (size_t)nobs), rp.resize(3 * (size_t)nobs);
+  for (int o = 0; o < nobs; ++o) {
+    const int q = src[o];
+    ot[o] = t2.obs_time[q], oc[o] = s->obs_cam[q];
+    std::copy(t2.obs_uv + 2 * (size_t)q, t2.obs_uv + 2 * (size_t)q + 2, &uv[2 * (size_t)o]);
+    std::copy(t2.obs_uvn + 2 * (size_t)q, t2.obs_uvn + 2 * (size_t)q + 2, &uvn[2 * (size_t)o]);
+    if (t2.res_R) {
+      std::copy(t2.res_R + 9 * (size_t)q, t2.res_R + 9 * (size_t)q + 9, &rR[9 * (size_t)o]);
+      std::copy(t2.res_p + 3 * (size_t)q, t2.res_p + 3 * (size_t)q + 3, &rp[3 * (size_t)o]);
+    }
+  }
+  t2.obs_time = ot.data(), t2.obs_uv = uv.data(), t2.obs_uvn = uvn.data();
+  if (t2.res_R) t2.res_R = rR.data(), t2.res_p = rp.data();
+  t2.res_Q = nullptr, t2.res_clone = nullptr;  // (the triangulation reads no noise)
+  CamSide cams[2];
+  int dummy_cols[1] = {-1};
+  fill_cam_sides(ctx, st, right, 0, dummy_cols, cams);
+  StageExtra ex;
+  ex.cams = cams, ex.obs_cam = oc.data(), ex.uvn = uvn.data();
+  JacParams P{};
+  TRY(stage_inputs(ctx, us, st, &t2, 0, dummy_cols, 2, P, &ex));
+  const size_t o_pose = 0, o_valid = (size_t)nobs * 96, o_p = (o_valid + nobs + 15) & ~(size_t)15, o_err = o_p + (size_t)F * 24,
+               o_ok = o_err + (size_t)F * 8, total = o_ok + F + 16;
+  TRY(us->staging_of(3).tri.reserve(total));
+  char *d = us->staging_of(3).tri.as<char>();
+  TRY(launch_triangulate_stereo(ctx, P, ex.d_cams, ex.d_obs_cam, (double *)(d + o_pose), (unsigned char *)(d + o_valid), ex.d_uvn, *opt,
+                                (double *)(d + o_p), (unsigned char *)(d + o_ok), (double *)(d + o_err), max_obs(t2.obs_ptr, F)));
   PLV_HIP_CHECK(plv::memcpy_async(p_FinG, d + o_p, (size_t)F * 24, hipMemcpyDeviceToHost, ctx->stream));
   PLV_HIP_CHECK(plv::memcpy_async(ok, d + o_ok, (size_t)F, hipMemcpyDeviceToHost, ctx->stream));
   if (reproj_err) PLV_HIP_CHECK(plv::memcpy_async(reproj_err, d + o_err, (size_t)F * 8, hipMemcpyDeviceToHost, ctx->stream));

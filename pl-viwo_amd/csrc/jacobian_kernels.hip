@@ -1304,6 +1304,130 @@ __global__ void __launch_bounds__(64) triangulate_kernel(JacParams P, double *po
                       tot);
 }
 
+// ------------------------------------------------------------------------------------------ stereo pair
+// The reference's helpers loop over Feature::timestamps, a map from camera id to that camera's observations, and read extrinsics,
+// intrinsics and the distortion model by camera id (REF: CamHelper.cpp:70-75, 137-143, 345-347, 378-380, 436-441).  Here a
+// feature's observations of both cameras lie in one range and obs_cam says whose each is.  Both kernels go through the two cameras
+// one after the other (a wave-uniform loop): the launch's parameters with camera `side` of the table in place of their camera
+// fields, handed to the monocular device functions by the lanes whose observation is that camera's — the same expressions, and no
+// per-lane choice between two parameter structs.
+__device__ __forceinline__ JacParams with_camera(const JacParams &P, const CamSide *cams, int side) {
+  JacParams Q = P;
+  const CamSide &c = cams[side];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) Q.R_ItoC[i] = c.R_ItoC[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) Q.p_IinC[i] = c.p_IinC[i];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) Q.K[i] = c.K[i];
+  Q.cam_model = c.cam_model, Q.col_ext = c.col_ext, Q.col_int = c.col_int;
+  return Q;
+}
+
+// jacobian_kernel for plv_stereo_tracks: one workgroup per feature, one lane per observation, ballot-prefix row slots over the
+// observations of both cameras in the order they are listed, the 64-observation chunk loop; the slice is zero-filled here.
+__global__ void __launch_bounds__(128) stereo_jacobian_kernel(JacParams P, const CamSide *__restrict__ cams, const unsigned char *__restrict__ obs_cam) {
+  __shared__ WinTab tab[JAC_MAX_WIN];
+  const int f = blockIdx.x;
+  const int ld = P.ld, k = P.k;
+  double *hf = P.Hf + (size_t)f * 3 * ld, *hx = P.Hx + (size_t)f * k * ld, *rs = P.res + (size_t)f * ld;
+  for (int i = threadIdx.x; i < 3 * ld; i += blockDim.x) hf[i] = 0.0;
+  for (int i = threadIdx.x; i < k * ld; i += blockDim.x) hx[i] = 0.0;
+  for (int i = threadIdx.x; i < ld; i += blockDim.x) rs[i] = 0.0;
+  if (f == 0 && P.cols_out)
+    for (int i = threadIdx.x; i < k; i += blockDim.x) P.cols_out[i] = P.cols_in[i];
+  build_window_tables(P, tab);  // (ends with a barrier: also orders the zero fill before the row writes)
+  if (threadIdx.x >= 64) return;  // observation lanes = wave 0
+  const int o0 = P.obs_ptr[f], o1 = P.obs_ptr[f + 1];
+  int base = 0;
+  for (int ob = o0; ob < o1; ob += 64) {
+    const int o = ob + threadIdx.x;
+    const bool have = o < o1;
+    const double tm = (have ? P.obs_time[o] : 0.0) + P.cam_dt;
+    const int s0 = have ? bounding_start(P, tm) : -1;
+    const unsigned long long vmask = __ballot(s0 >= 0);
+    const int c = base + __popcll(vmask & ((1ull << threadIdx.x) - 1ull));
+    base += __popcll(vmask);
+    const bool writes = s0 >= 0 && 2 * c + 2 <= ld;
+    const int cam = have ? (int)obs_cam[o] : -1;
+    for (int side = 0; side < 2; ++side) {
+      if (!__ballot(writes && cam == side)) continue;  // (uniform) none of this chunk's rows is this camera's
+      const JacParams Q = with_camera(P, cams, side);
+      if (writes && cam == side) jacobian_rows(Q, tab, f, o, s0, tm, c, hf, hx, rs, ld, 1);
+    }
+  }
+  if (threadIdx.x == 0) P.rows[f] = 2 * base;
+}
+
+// pixel error of one observation of the triangulated point (CamHelper.cpp:441-466: distort_d's float round trip included) — the
+// expressions of triangulate_feature's own error pass, with the observation's camera
+__device__ __forceinline__ double stereo_reproj_px(const CamSide &C, const double *pose /* R_GtoC, p_CinG */, const V3 &pg, const float *uv) {
+  const double *K = C.K;
+  const V3 pC = mv(ldM(pose), vsub(pg, ldV(pose + 9)));
+  double x1, y1;
+  if (C.cam_model == PLV_CAM_EQUIDISTANT) {
+    distort_equidistant_f(K, (float)(pC[0] / pC[2]), (float)(pC[1] / pC[2]), x1, y1);
+  } else {
+    const double x = (double)(float)(pC[0] / pC[2]), y = (double)(float)(pC[1] / pC[2]);
+    const double r = sqrt(x * x + y * y), r_2 = r * r, r_4 = r_2 * r_2;
+    x1 = x * (1 + K[4] * r_2 + K[5] * r_4) + 2 * K[6] * x * y + K[7] * (r_2 + 2 * x * x);
+    y1 = y * (1 + K[4] * r_2 + K[5] * r_4) + K[6] * (r_2 + 2 * y * y) + 2 * K[7] * x * y;
+  }
+  const double r0 = (double)uv[0] - (double)(float)(K[0] * x1 + K[2]);
+  const double r1 = (double)uv[1] - (double)(float)(K[1] * y1 + K[3]);
+  return sqrt(r0 * r0 + r1 * r1);
+}
+
+// triangulate_kernel for plv_stereo_tracks, one wave per feature: camera poses from each observation's own extrinsics
+// (get_cam_poses), then triangulate_feature on them — linear solve, condition number, Levenberg-Marquardt and the depth / baseline
+// tests are its own; it anchors on the last observation with bounding clones, which the caller's ordering of the two cameras'
+// blocks makes the reference's anchor —, then moving_consistency's error: the mean per camera, each summed in observation order,
+// and the mean of those over the cameras that have observations (REF CamHelper.cpp:469-477).
+__global__ void __launch_bounds__(64) stereo_triangulate_kernel(JacParams P, const CamSide *__restrict__ cams, const unsigned char *__restrict__ obs_cam,
+                                                                double *poses, unsigned char *valid, const float *__restrict__ uvn,
+                                                                plv_tri_options opt, double *__restrict__ p_out, unsigned char *__restrict__ ok_out,
+                                                                double *__restrict__ err_out, int max_obs) {
+  extern __shared__ double tri_smem[];
+  __shared__ double tot[32];
+  __shared__ double res_l[5];
+  const int f = blockIdx.x, lane = threadIdx.x;
+  const int o0 = P.obs_ptr[f], o1 = P.obs_ptr[f + 1];
+  for (int side = 0; side < 2; ++side) {
+    const JacParams Q = with_camera(P, cams, side);
+    for (int o = o0 + lane; o < o1; o += 64)
+      if ((int)obs_cam[o] == side) campose_one(Q, o, poses, valid, nullptr);
+  }
+  __threadfence_block();
+  tri_wave_sync();
+  triangulate_feature(P, f, o0, o1, poses, valid, uvn, P.obs_uv, opt, p_out, ok_out, nullptr, max_obs, tri_smem, tot, true, res_l);
+  tri_wave_sync();
+  if (!err_out) return;
+  const bool ok = res_l[3] != 0.0;  // (uniform)
+  if (!ok) {
+    if (lane == 0) err_out[f] = 0;
+    return;
+  }
+  const V3 pg{{res_l[0], res_l[1], res_l[2]}};
+  double *e_l = tri_smem;  // [o1 - o0] <= max_obs: the triangulation's scratch is dead
+  for (int o = o0 + lane; o < o1; o += 64)
+    if (valid[o]) e_l[o - o0] = stereo_reproj_px(cams[obs_cam[o] ? 1 : 0], poses + 12 * (size_t)o, pg, P.obs_uv + 2 * (size_t)o);
+  tri_wave_sync();
+  if (lane == 0) {
+    double sum[2] = {0, 0};
+    int cnt[2] = {0, 0};
+    for (int o = o0; o < o1; ++o)
+      if (valid[o]) {
+        if (obs_cam[o]) sum[1] += e_l[o - o0], ++cnt[1];
+        else sum[0] += e_l[o - o0], ++cnt[0];
+      }
+    double avg = 0;
+    int ncam = 0;
+    if (cnt[1]) avg += sum[1] / cnt[1], ++ncam;  // (camera 1 first: the reference's iteration order)
+    if (cnt[0]) avg += sum[0] / cnt[0], ++ncam;
+    err_out[f] = avg / ncam;
+  }
+}
+
 
 // ------------------------------------------------------------------------------------------ lines
 // a28: LineHelper::get_line_feature_jacobian_full   REF: PL-VIWO/src/update/cam/linefeat/LineHelper.cpp:733-1024
@@ -2209,6 +2333,33 @@ int launch_jacobians(plv_ctx *ctx, const JacParams &P) {
     return PLV_E_CAPACITY;
   }
   hipLaunchKernelGGL(jacobian_kernel, dim3(P.n_feat), dim3(128), 0, ctx->stream, P);
+  PLV_HIP_CHECK(hipGetLastError());
+  return PLV_OK;
+}
+
+int launch_jacobians_stereo(plv_ctx *ctx, const JacParams &P, const CamSide *d_cams, const unsigned char *d_obs_cam) {
+  ProfScope ps(ctx->prof, "stereo_jacobian_kernel", ctx->stream);
+  if (2 * (P.n_clones - 3) > JAC_MAX_WIN) {
+    set_last_error("stereo jacobians: %d clones exceed the window table (%d)", P.n_clones, JAC_MAX_WIN / 2 + 3);
+    return PLV_E_CAPACITY;
+  }
+  hipLaunchKernelGGL(stereo_jacobian_kernel, dim3(P.n_feat), dim3(128), 0, ctx->stream, P, d_cams, d_obs_cam);
+  PLV_HIP_CHECK(hipGetLastError());
+  return PLV_OK;
+}
+
+int launch_triangulate_stereo(plv_ctx *ctx, const JacParams &P, const CamSide *d_cams, const unsigned char *d_obs_cam, double *d_poses,
+                              unsigned char *d_valid, const float *d_uvn, const plv_tri_options &opt, double *d_p, unsigned char *d_ok,
+                              double *d_err, int max_obs) {
+  ProfScope ps(ctx->prof, "stereo_triangulate_kernel", ctx->stream);
+  const size_t shm = (size_t)std::max(max_obs, 1) * (sizeof(TriObs) + TRI_TERMS * 8 + 4) + 16;
+  if (shm > 150 * 1024) {
+    set_last_error("stereo triangulation: a track of %d observations exceeds LDS", max_obs);
+    return PLV_E_CAPACITY;
+  }
+  PLV_HIP_CHECK(ensure_dyn_smem((const void *)stereo_triangulate_kernel, (int)shm));
+  hipLaunchKernelGGL(stereo_triangulate_kernel, dim3(P.n_feat), dim3(64), shm, ctx->stream, P, d_cams, d_obs_cam, d_poses, d_valid, d_uvn, opt,
+                     d_p, d_ok, d_err, std::max(max_obs, 1));
   PLV_HIP_CHECK(hipGetLastError());
   return PLV_OK;
 }

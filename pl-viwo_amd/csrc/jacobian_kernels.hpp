@@ -162,4 +162,19 @@ int launch_triangulate_lines(plv_ctx *ctx, const JacParams &P, double *d_poses, 
 int launch_triangulate(plv_ctx *ctx, const JacParams &P, double *d_poses, unsigned char *d_valid, const float *d_uvn,
                        const plv_tri_options &opt, double *d_p, unsigned char *d_ok, double *d_err, int max_obs);
 
+// ---- stereo pair (plv_stereo_tracks): what JacParams holds once per launch, per camera.  The stereo kernels read a two-entry table
+// of these in global memory, indexed by the observation's camera (obs_cam [n_obs], 0 / 1); P's own camera fields are not read.
+struct CamSide {
+  double R_ItoC[9], p_IinC[3], K[8];
+  int cam_model, col_ext, col_int, pad;
+};
+// stereo_jacobian_kernel: jacobian_kernel's batch, every observation with its own camera's extrinsics, intrinsics, model and columns
+int launch_jacobians_stereo(plv_ctx *ctx, const JacParams &P, const CamSide *d_cams, const unsigned char *d_obs_cam);
+// stereo_triangulate_kernel: triangulate_kernel over both cameras' observations.  The anchor is the LAST observation with bounding
+// clones of each feature (the caller orders the two cameras' blocks accordingly); d_err: mean pixel error per camera, then the mean
+// over the cameras that have observations (REF CamHelper.cpp:469-477)
+int launch_triangulate_stereo(plv_ctx *ctx, const JacParams &P, const CamSide *d_cams, const unsigned char *d_obs_cam, double *d_poses,
+                              unsigned char *d_valid, const float *d_uvn, const plv_tri_options &opt, double *d_p, unsigned char *d_ok,
+                              double *d_err, int max_obs);
+
 }  // namespace plv

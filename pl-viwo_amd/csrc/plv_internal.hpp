@@ -40,6 +40,11 @@ int plv_update_gate_prepare(plv_ctx *ctx, int F, int fdim, int k, int ld, double
 // the prior factor of the update on the side stream, next to triangulation, Jacobians and gate (phase 0 / 1)
 int plv_prior_prefetch(plv_ctx *ctx, int phase, const int *d_cols, int k, int F, int mp_max);
 
+// ---- jacobian_api.hip
+// what every stereo call refuses of the pair's camera 1: no side, an unknown model, a state id that collides with camera 0's or the
+// time offset's.  Host logic; `what` leads the error text.
+int plv_stereo_side_check(const char *what, const plv_state_view *st, const plv_camera_side *right);
+
 // ---- init_api.cpp
 // the test plv_state_boxplus makes of a variable list, made before anything is enqueued (plv_camera_try_update / plv_camera_frame)
 int plv_state_vars_check(int n_var, const plv_state_var *vars, int n_dx);

@@ -17,6 +17,7 @@
 #include "encoding_kernels.hpp"
 #include "front_parts.hpp"
 #include "plv_internal.hpp"
+#include "update_tail.hpp"
 
 using namespace plv;
 
@@ -32,10 +33,6 @@ struct StereoCam : CamFront {  // (cur and fed move in step in both cameras)
   std::vector<uint8_t> mask_last;   // W*H or empty
   double K[8] = {};                 // camera 1 only: camera 0 is the context's (cfg.intrinsics, plv_ctx::cam_model)
   int model = PLV_CAM_RADTAN;
-};
-
-struct StereoFeature {  // ov_core::Feature: the observations of one id, per camera
-  Track cam[2];
 };
 
 struct Stereo {
@@ -485,6 +482,235 @@ int plv_stereo_db_remove(plv_ctx *ctx, const uint64_t *ids, int n) {
   std::lock_guard<std::mutex> lk(S->mtx);
   erase_ids(S->db, ids, n);
   return PLV_OK;
+}
+
+int plv_stereo_db_append_measurements(plv_ctx *ctx, uint64_t id, int cam, int n, const double *t, const float *uv, const float *uvn) {
+  if (!ctx || n < 0 || (n > 0 && (!t || !uv || !uvn))) {
+    set_last_error("plv_stereo_db_append_measurements: no context, a negative count or a missing array");
+    return PLV_E_BADARG;
+  }
+  if (bad_cam(cam, "plv_stereo_db_append_measurements")) return PLV_E_BADARG;
+  Stereo *S = configured(ctx, "plv_stereo_db_append_measurements");
+  if (!S) return PLV_E_BADARG;
+  std::lock_guard<std::mutex> lk(S->mtx);
+  Track &tr = S->db[id].cam[cam];
+  tr.t.insert(tr.t.end(), t, t + n);
+  tr.uv.insert(tr.uv.end(), uv, uv + 2 * (size_t)n);
+  tr.uvn.insert(tr.uvn.end(), uvn, uvn + 2 * (size_t)n);
+  return PLV_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------ the stereo point update
+namespace {
+typedef PoolCand<StereoFeature> StereoCand;
+
+// One plv_stereo_update_points call.  The pool mechanics are camera_tracks.hpp's: a candidate holds the two cameras' tracks, and what
+// goes back to the database (db_unused) is kept per camera, so that every per-track template serves one camera of a feature.
+struct StereoPointsUpdate {
+  plv_ctx *ctx;
+  Stereo *S;
+  const plv_state_view *st;
+  const plv_camera_side *right;
+  const plv_update_options *opt;
+  double *dx;
+  plv_update_result *res;
+  const double dt = st->cam_dt, t_oldest = st->clone_time[0], t_oldest2 = st->clone_time[1];  // one time offset for the pair (REF State.cpp:102-103)
+  BoundingMemo start_of{*st};
+  std::vector<StereoCand> pool;
+  TrackMap<Track> unused[2];
+  std::vector<int> valid_n;
+
+  // REF CamHelper.cpp:702-703 / :709-738: db_unused returns to the tracker's database; cleanup_features runs on every call
+  int finish(int rc) {
+    std::lock_guard<std::mutex> lk(S->mtx);
+    res->n_returned = (int)unused[0].size();
+    for (const auto &kv : unused[1]) res->n_returned += unused[0].find(kv.first) == unused[0].end();
+    for (int c = 0; c < 2; ++c)
+      for (auto &kv : unused[c]) append_track(S->db[kv.first].cam[c], kv.second);
+    if (opt->window_full)
+      cleanup_measurements(S->db, t_oldest, [](StereoFeature &f, double t_) { return drop_before(f.cam[0], t_) + drop_before(f.cam[1], t_); });
+    return rc;
+  }
+  int finish_early() {
+    std::fill(dx, dx + ctx->cov_n, 0.0);
+    return finish(PLV_OK);
+  }
+  void back_all(StereoCand &c) {
+    for (int q = 0; q < 2; ++q) {
+      if (c.tr.cam[q].t.empty()) continue;
+      PoolCand<Track> one{c.id, std::move(c.tr.cam[q])};
+      give_back_all(unused[q], one);
+      c.tr.cam[q] = Track{};
+    }
+  }
+  int abandon(int rc) {
+    for (StereoCand &c : pool) back_all(c);
+    return finish(rc);
+  }
+  // observations with bounding clones (get_imu_poses, REF :327-372), over both cameras
+  int usable(const StereoCand &c) { return usable_views(c.tr.cam[0], dt, start_of) + usable_views(c.tr.cam[1], dt, start_of); }
+
+  void take_pool_of_window() {
+    {
+      std::lock_guard<std::mutex> lk(S->mtx);
+      take_pool(S->db, t_oldest2 - dt, opt->t_prev_frame - dt, pool);  // REF :631-637, over the observations of both cameras
+    }
+    res->n_pool = (int)pool.size();
+    size_t kept = 0;
+    for (size_t ci = 0; ci < pool.size(); ++ci) {  // REF :740-775 remove_unusable_measurements, per camera
+      StereoCand &c = pool[ci];
+      size_t keep = 0;
+      for (int q = 0; q < 2; ++q) keep += trim_to_window(unused[q], c.id, c.tr.cam[q], dt, opt->state_time + st->dt_exp, t_oldest - st->dt_exp);
+      if (keep < 2) continue;  // REF :766-771
+      if (kept != ci) pool[kept] = std::move(c);
+      ++kept;
+    }
+    pool.resize(kept);
+    sort_long_first(pool);  // REF :640, by the observations of both cameras; ties by ascending id
+  }
+
+  // candidates [sel] in the layout of plv_stereo_tracks: camera 1's observations, then camera 0's (the reference's iteration order);
+  // valid_only: without the observations that have no bounding clones
+  struct Flat {
+    std::vector<int> ptr;
+    std::vector<double> t;
+    std::vector<float> uv, uvn;
+    std::vector<uint8_t> cam;
+  };
+  void flatten(const std::vector<int> &sel, bool valid_only, Flat &F) {
+    F.ptr.assign(1, 0);
+    for (int f : sel) {
+      for (int q = 1; q >= 0; --q) {
+        const Track &tr = pool[f].tr.cam[q];
+        for (size_t i = 0; i < tr.t.size(); ++i) {
+          if (valid_only && start_of(tr.t[i] + dt) < 0) continue;
+          F.t.push_back(tr.t[i]);
+          F.uv.insert(F.uv.end(), tr.uv.begin() + 2 * i, tr.uv.begin() + 2 * i + 2);
+          F.uvn.insert(F.uvn.end(), tr.uvn.begin() + 2 * i, tr.uvn.begin() + 2 * i + 2);
+          F.cam.push_back((uint8_t)q);
+        }
+      }
+      F.ptr.push_back((int)F.t.size());
+    }
+  }
+  static plv_stereo_tracks view(const Flat &F, const double *p) {
+    plv_stereo_tracks v{};
+    v.tracks.n_feat = (int)F.ptr.size() - 1, v.tracks.obs_ptr = F.ptr.data(), v.tracks.obs_time = F.t.data(), v.tracks.obs_uv = F.uv.data();
+    v.tracks.obs_uvn = F.uvn.data(), v.tracks.p_FinG = v.tracks.p_FinG_fej = p;
+    v.obs_cam = F.cam.data();
+    return v;
+  }
+};
+}  // namespace
+
+extern "C" {
+
+int plv_stereo_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_update_options *opt, double *dx,
+                             plv_update_result *res, uint64_t *msckf_ids, uint8_t *accepted_out, double *p_out) {
+  const char *who = "plv_stereo_update_points";
+  if (!ctx || !st || !opt || !dx || !res || st->n_clones < 2 || !st->clone_time || opt->max_msckf < 1 || opt->max_obs < 2) {
+    set_last_error("%s: a missing argument, fewer than 2 clones, max_msckf < 1 or max_obs < 2", who);
+    return PLV_E_BADARG;
+  }
+  // ---- every refusal comes before the database, the covariance or the staged batch is touched
+  auto refuse = [who](const char *why) {
+    set_last_error("%s: %s", who, why);
+    return (int)PLV_E_BADARG;
+  };
+  if (opt->max_slam != 0) return refuse("in-state landmarks (max_slam != 0) are not built for the stereo update");
+  if (opt->cpi) return refuse("use_imu_res (plv_update_options::cpi) is not built for the stereo update");
+  if (st->use_imu_cov) return refuse("use_imu_cov is not built for the stereo update");
+  if (ctx->decision_trace) return refuse("the decision trace does not cover the stereo update (plv_decision_trace off first)");
+  Stereo *S = configured(ctx, who);
+  if (!S) return PLV_E_BADARG;
+  TRY(plv_stereo_side_check(who, st, right));
+  *res = plv_update_result{0, 0, 0, 0, 0, PLV_OK, 0, 0, 0};
+  (void)hipSetDevice(ctx->device);
+  StereoPointsUpdate U{ctx, S, st, right, opt, dx, res};
+  U.take_pool_of_window();
+  const int Fp = (int)U.pool.size();
+  if (Fp == 0) return U.finish_early();
+  U.valid_n.resize(Fp);
+  bool any = false;
+  for (int f = 0; f < Fp; ++f) {
+    U.valid_n[f] = U.usable(U.pool[f]);
+    any = any || U.valid_n[f] >= 2;
+    if (U.valid_n[f] > opt->max_obs) {
+      set_last_error("%s: feature %llu has %d usable observations over both cameras, the batch holds max_obs = %d", who,
+                     (unsigned long long)U.pool[f].id, U.valid_n[f], opt->max_obs);
+      return U.abandon(PLV_E_CAPACITY);
+    }
+  }
+  // ---- launch 1: every pool candidate triangulated (the reference goes feature by feature until the cap; a feature it never
+  // reaches keeps its observations either way)
+  std::vector<double> pf(3 * (size_t)Fp, 0.0), err(Fp, 0.0);
+  std::vector<uint8_t> ok(Fp, 0);
+  if (any) {
+    std::vector<int> everyone(Fp);
+    for (int f = 0; f < Fp; ++f) everyone[f] = f;
+    StereoPointsUpdate::Flat A;
+    U.flatten(everyone, false, A);
+    const plv_stereo_tracks all = StereoPointsUpdate::view(A, nullptr);
+    const int rc_t = plv_triangulate_stereo(ctx, st, right, &all, &opt->tri, pf.data(), ok.data(), err.data());
+    if (rc_t != PLV_OK) return U.abandon(rc_t);
+  }
+  // ---- REF :648-699 the selection loop, on the host
+  std::vector<int> sel;
+  for (int f = 0; f < Fp; ++f) {
+    StereoCand &c = U.pool[f];
+    if ((int)sel.size() >= opt->max_msckf || U.valid_n[f] < 2 || !ok[f] || !(err[f] < 3.0)) {
+      U.back_all(c);
+      continue;
+    }
+    sel.push_back(f);
+  }
+  res->n_msckf = (int)sel.size();
+  if (sel.empty()) return U.finish_early();
+  // ---- launch 2 + the resident tail: UpdaterCamera::msckf_update on the selected features
+  std::vector<double> feat(3 * sel.size());
+  for (size_t q = 0; q < sel.size(); ++q) {
+    std::copy(pf.begin() + 3 * (size_t)sel[q], pf.begin() + 3 * (size_t)sel[q] + 3, feat.begin() + 3 * q);
+    if (msckf_ids) msckf_ids[q] = U.pool[sel[q]].id;
+    for (int cq = 0; cq < 2; ++cq) {  // observations without bounding clones go back (get_imu_poses)
+      const Track &tr = U.pool[sel[q]].tr.cam[cq];
+      for (size_t i = 0; i < tr.t.size(); ++i)
+        if (U.start_of(tr.t[i] + U.dt) < 0) give_back(U.unused[cq], U.pool[sel[q]].id, tr, i);
+    }
+  }
+  if (p_out) std::copy(feat.begin(), feat.end(), p_out);
+  StereoPointsUpdate::Flat B;
+  U.flatten(sel, true, B);
+  const plv_stereo_tracks chosen = StereoPointsUpdate::view(B, feat.data());
+  std::vector<int> cols(ctx->cfg.max_state_dim > 0 ? ctx->cfg.max_state_dim : 1024);
+  std::vector<uint8_t> acc(sel.size(), 0);
+  int k = 0, n_rows = 0;
+  int rc = plv_stereo_jacobian_columns(st, right, &chosen, cols.data(), (int)cols.size(), &k);
+  if (rc == PLV_OK) rc = plv_build_jacobians_stereo_resident(ctx, st, right, &chosen, k, cols.data(), 2 * opt->max_obs);
+  if (rc == PLV_OK) {
+    rc = plv_msckf_update_resident(ctx, st->sigma_pix * st->sigma_pix, opt->chi2_mult, 3.0, acc.data(), &n_rows, dx);
+    rc = ekf_returned_false(rc, &res->status, dx, ctx->cov_n);
+  }
+  auto back_valid = [&](int f) {
+    for (int cq = 0; cq < 2; ++cq) {
+      const Track &tr = U.pool[f].tr.cam[cq];
+      for (size_t i = 0; i < tr.t.size(); ++i)
+        if (U.start_of(tr.t[i] + U.dt) >= 0) give_back(U.unused[cq], U.pool[f].id, tr, i);
+    }
+  };
+  if (rc != PLV_OK) {  // a failing update returns the selected tracks
+    for (int f : sel) back_valid(f);
+    return U.finish(rc);
+  }
+  res->n_rows = n_rows;
+  // REF UpdaterCamera.cpp:266-268: only what the gate rejected goes back
+  for (size_t q = 0; q < sel.size(); ++q) {
+    res->n_accepted += acc[q];
+    if (accepted_out) accepted_out[q] = acc[q];
+    if (!acc[q]) back_valid(sel[q]);
+  }
+  return U.finish(PLV_OK);
 }
 
 }  // extern "C"
