@@ -201,7 +201,7 @@ __global__ void __launch_bounds__(64 * (NT + 1)) bchol_ekf_kernel(const double *
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 
-int launch_bchol_ekf(plv_ctx *ctx, const double *d_S, int lds_, int r, const double *d_Mt, int ldm, int n,
+int launch_bchol_ekf(plv_ctx *ctx, const EkfRiders &rd, const double *d_S, int lds_, int r, const double *d_Mt, int ldm, int n,
                      const double *d_res, double *d_W, int ldw, int *d_flag, const WhitenC1Args *wc) {
   if (r > 192) return PLV_E_CAPACITY;
   const int strips = cdiv(n + 1, 16);  // one border strip per workgroup; every workgroup factors S itself
@@ -213,22 +213,22 @@ int launch_bchol_ekf(plv_ctx *ctx, const double *d_S, int lds_, int r, const dou
   ProfScope ps(ctx->prof, "bchol_ekf_kernel", ctx->stream);
   if (r <= 32)
     hipLaunchKernelGGL(bchol_ekf_kernel<2>, dim3(groups), dim3(64 * 3), 0, ctx->stream, d_S, lds_, r, d_Mt, ldm, n, d_res, d_W,
-                       ldw, d_flag, ctx->skip_word, c1);
+                       ldw, d_flag, rd.skip_word, c1);
   else if (r <= 64)
     hipLaunchKernelGGL(bchol_ekf_kernel<4>, dim3(groups), dim3(64 * 5), 0, ctx->stream, d_S, lds_, r, d_Mt, ldm, n, d_res, d_W,
-                       ldw, d_flag, ctx->skip_word, c1);
+                       ldw, d_flag, rd.skip_word, c1);
   else if (r <= 112)
     hipLaunchKernelGGL(bchol_ekf_kernel<7>, dim3(groups), dim3(64 * 8), 0, ctx->stream, d_S, lds_, r, d_Mt, ldm, n, d_res, d_W,
-                       ldw, d_flag, ctx->skip_word, c1);
+                       ldw, d_flag, rd.skip_word, c1);
   else if (r <= 128)
     hipLaunchKernelGGL(bchol_ekf_kernel<8>, dim3(groups), dim3(64 * 9), 0, ctx->stream, d_S, lds_, r, d_Mt, ldm, n, d_res, d_W,
-                       ldw, d_flag, ctx->skip_word, c1);
+                       ldw, d_flag, rd.skip_word, c1);
   else if (r <= 160)
     hipLaunchKernelGGL(bchol_ekf_kernel<10>, dim3(groups), dim3(64 * 11), 0, ctx->stream, d_S, lds_, r, d_Mt, ldm, n, d_res, d_W,
-                       ldw, d_flag, ctx->skip_word, c1);
+                       ldw, d_flag, rd.skip_word, c1);
   else
     hipLaunchKernelGGL(bchol_ekf_kernel<12>, dim3(groups), dim3(64 * 13), 0, ctx->stream, d_S, lds_, r, d_Mt, ldm, n, d_res, d_W,
-                       ldw, d_flag, ctx->skip_word, c1);
+                       ldw, d_flag, rd.skip_word, c1);
   PLV_HIP_CHECK(hipGetLastError());
   return PLV_OK;
 }

@@ -147,7 +147,7 @@ __global__ void __launch_bounds__(256) ekf_commit_kernel(double *__restrict__ P,
   // applied_out: "this update changed the state" — StateHelper::EKFUpdate reached its mean update (:156-168): read by a launch that is
   // enqueued behind the update before the host has seen its result and applies dx to its own copy of the state (the chained line launch)
   if (applied_out && blockIdx.x == 0 && threadIdx.x == 0) *applied_out = (skipped || capped || *flag != 0) ? 0 : 1;
-  // save (a speculative point batch, plv_ctx::cov_save): both halves of what the commit overwrites, and save_seq in save_word when it
+  // save (a speculative point batch, CovSave): both halves of what the commit overwrites, and save_seq in save_word when it
   // did — the host restores them when nobody uses the update (plv_points_spec_undo; (P - dC) + dC would not be P again)
   if (save_word && blockIdx.x == 0 && threadIdx.x == 0) *save_word = (skipped || capped || *flag != 0) ? 0u : save_seq;
   if (blockIdx.x == 0) {
@@ -176,11 +176,11 @@ __global__ void __launch_bounds__(256) ekf_commit_kernel(double *__restrict__ P,
 
 // ========================================================================================== launchers
 bool ekf_fast_fits(int r) { return r <= 192; }
-static int launch_ekf_commit(plv_ctx *ctx, double *d_P, int n, int ldp, const double *dC, double *d_dx, int *d_flag, const void *mirror_src,
+static int launch_ekf_commit(plv_ctx *ctx, const EkfRiders &rd, double *d_P, int n, int ldp, const double *dC, double *d_dx, int *d_flag, const void *mirror_src,
                              void *mirror_dst, size_t mirror_bytes);
 
 // EKF update with the identity-border Cholesky.  Requires ekf_fast_fits(r).
-int launch_ekf_fast(plv_ctx *ctx, double *d_P, int n, int ldp, const double *d_H, int r, int k, int ldh, const int *d_cols,
+int launch_ekf_fast(plv_ctx *ctx, const EkfRiders &rd, double *d_P, int n, int ldp, const double *d_H, int r, int k, int ldh, const int *d_cols,
                     const double *d_res, const double *d_Rdiag, double *d_dx, int *d_flag, bool gathered, const void *mirror_src,
                     void *mirror_dst, size_t mirror_bytes) {
   int rc;
@@ -189,29 +189,27 @@ int launch_ekf_fast(plv_ctx *ctx, double *d_P, int n, int ldp, const double *d_H
       (rc = ctx->d_W.reserve((size_t)r * (n + 1) * 8)) || (rc = ctx->d_y.reserve((size_t)n * n * 8)))
     return rc;
   double *Mt = ctx->d_Mt.as<double>(), *S = ctx->d_S.as<double>(), *W = ctx->d_W.as<double>(), *dC = ctx->d_y.as<double>();
-  launch_ekf_ms(ctx, d_P, n, ldp, d_H, r, k, ldh, d_cols, d_Rdiag, Mt, ldm, S, gathered, d_flag);
-  if ((rc = launch_bchol_ekf(ctx, S, r, r, Mt, ldm, n, d_res, W, ldw, d_flag))) return rc;
+  launch_ekf_ms(ctx, rd, d_P, n, ldp, d_H, r, k, ldh, d_cols, d_Rdiag, Mt, ldm, S, gathered, d_flag);
+  if ((rc = launch_bchol_ekf(ctx, rd, S, r, r, Mt, ldm, n, d_res, W, ldw, d_flag))) return rc;
   {
     ProfScope ps(ctx->prof, "ekf_dc_kernel", ctx->stream);
     int tn = cdiv(n + 1, 16);
     int waves = tn * (tn + 1) / 2;
-    hipLaunchKernelGGL(ekf_dc_kernel, dim3(cdiv(waves, 4)), dim3(256), 0, ctx->stream, W, ldw, r, n, dC, n, d_dx, d_P, ldp, d_flag, ctx->skip_word,
+    hipLaunchKernelGGL(ekf_dc_kernel, dim3(cdiv(waves, 4)), dim3(256), 0, ctx->stream, W, ldw, r, n, dC, n, d_dx, d_P, ldp, d_flag, rd.skip_word,
                        (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, (const int *)nullptr);
   }
-  return launch_ekf_commit(ctx, d_P, n, ldp, dC, d_dx, d_flag, mirror_src, mirror_dst, mirror_bytes);
+  return launch_ekf_commit(ctx, rd, d_P, n, ldp, dC, d_dx, d_flag, mirror_src, mirror_dst, mirror_bytes);
 }
 
-static int launch_ekf_commit(plv_ctx *ctx, double *d_P, int n, int ldp, const double *dC, double *d_dx, int *d_flag, const void *mirror_src,
+static int launch_ekf_commit(plv_ctx *ctx, const EkfRiders &rd, double *d_P, int n, int ldp, const double *dC, double *d_dx, int *d_flag, const void *mirror_src,
                              void *mirror_dst, size_t mirror_bytes) {
   {
     ProfScope ps(ctx->prof, "ekf_commit_kernel", ctx->stream);
     hipLaunchKernelGGL(ekf_commit_kernel, dim3(std::min(64, cdiv(n * n, 256))), dim3(256), 0, ctx->stream, d_P, ldp, n, dC, n,
-                       d_flag, (const unsigned *)mirror_src, (unsigned *)mirror_dst, (int)(mirror_bytes / 4), ctx->skip_word, d_dx,
-                       (const unsigned *)(mirror_dst ? ctx->mirror2_src : nullptr), (unsigned *)(mirror_dst ? ctx->mirror2_dst : nullptr),
-                       (int)((ctx->mirror2_bytes + 3) / 4), mirror_dst ? ctx->applied_word : nullptr,
-                       mirror_dst ? ctx->cap_words : nullptr, ctx->cap, ctx->cov_save, ctx->cov_save_word, ctx->cov_save_seq);
-    if (mirror_dst && ctx->applied_word) ctx->applied_used = true;
-    if (mirror_dst && ctx->mirror2_dst) ctx->mirror2_taken = true;
+                       d_flag, (const unsigned *)mirror_src, (unsigned *)mirror_dst, (int)(mirror_bytes / 4), rd.skip_word, d_dx,
+                       (const unsigned *)(mirror_dst ? rd.mirror2_src : nullptr), (unsigned *)(mirror_dst ? rd.mirror2_dst : nullptr),
+                       (int)((rd.mirror2_bytes + 3) / 4), mirror_dst ? rd.applied_word : nullptr,
+                       mirror_dst ? rd.cap_words : nullptr, rd.cap, rd.save.buf, rd.save.word, rd.save.seq);
   }
   PLV_HIP_CHECK(hipGetLastError());
   return PLV_OK;
@@ -359,19 +357,19 @@ int launch_prior_factor(plv_ctx *ctx, hipStream_t st, const double *d_P, int n, 
 }
 
 // Information matrix of the accepted rows of the stack (d_Gs k x k, d_gv k), on the main stream.
-int launch_gram_information(plv_ctx *ctx, const double *d_A, int lda, int nc, const int *d_acc_rows, int F, int mp_max) {
+int launch_gram_information(plv_ctx *ctx, const EkfRiders &rd, const double *d_A, int lda, int nc, const int *d_acc_rows, int F, int mp_max) {
   const int k = nc - 1, nt = cdiv(nc, 16), ntri = nt * (nt + 1) / 2;
   int rc;
   if ((rc = ctx->d_Gs.reserve(((size_t)k * k + k) * 8))) return rc;
   ProfScope ps(ctx->prof, "gram_direct_kernel", ctx->stream);
   hipLaunchKernelGGL(gram_direct_kernel, dim3(ntri), dim3(256), 0, ctx->stream, d_A, lda, nc, d_acc_rows, F, mp_max, (double *)nullptr,
-                     ctx->skip_word, ctx->d_Gs.as<double>(), ctx->d_Gs.as<double>() + (size_t)k * k);
+                     rd.skip_word, ctx->d_Gs.as<double>(), ctx->d_Gs.as<double>() + (size_t)k * k);
   PLV_HIP_CHECK(hipGetLastError());
   return PLV_OK;
 }
 
 // The main-stream part after launch_gram_information; the caller has made the stream wait for launch_prior_factor's end.
-int launch_ekf_whitened(plv_ctx *ctx, double *d_P, int n, int ldp, int k, const int *d_cols, double *d_dx, int *d_flag, const void *mirror_src,
+int launch_ekf_whitened(plv_ctx *ctx, const EkfRiders &rd, double *d_P, int n, int ldp, int k, const int *d_cols, double *d_dx, int *d_flag, const void *mirror_src,
                         void *mirror_dst, size_t mirror_bytes) {
   int rc;
   if ((rc = ctx->d_Mt.reserve((size_t)k * 8)) || (rc = ctx->d_S.reserve((size_t)k * k * 8)) || (rc = ctx->d_W.reserve((size_t)k * (n + 1) * 8)) ||
@@ -387,16 +385,16 @@ int launch_ekf_whitened(plv_ctx *ctx, double *d_P, int n, int ldp, int k, const 
     static const int one[2] = {1, 0};
     PLV_HIP_CHECK(hipMemcpyAsync(ctx->d_prior_near.p, one, 8, hipMemcpyHostToDevice, ctx->stream));
   }
-  launch_whiten_b(ctx, ctx->d_Lt.as<double>(), k, Gs, gv, cv, B, d_flag, d_P, ldp, n, d_cols, Y0, GP, d0, use_m);
+  launch_whiten_b(ctx, rd, ctx->d_Lt.as<double>(), k, Gs, gv, cv, B, d_flag, d_P, ldp, n, d_cols, Y0, GP, d0, use_m);
   const WhitenC1Args wc{d_P, ldp, d_cols, GP, C1, Y0, use_m};
-  if ((rc = launch_bchol_ekf(ctx, B, k, k, ctx->d_W0.as<double>(), k, n, cv, V, k, d_flag, &wc))) return rc;
+  if ((rc = launch_bchol_ekf(ctx, rd, B, k, k, ctx->d_W0.as<double>(), k, n, cv, V, k, d_flag, &wc))) return rc;
   {
     ProfScope ps(ctx->prof, "ekf_dc_kernel", ctx->stream);
     const int tn = cdiv(n + 1, 16), waves = tn * (tn + 1) / 2;
-    hipLaunchKernelGGL(ekf_dc_kernel, dim3(cdiv(waves, 4)), dim3(256), 0, ctx->stream, V, k, k, n, dC, n, d_dx, d_P, ldp, d_flag, ctx->skip_word,
+    hipLaunchKernelGGL(ekf_dc_kernel, dim3(cdiv(waves, 4)), dim3(256), 0, ctx->stream, V, k, k, n, dC, n, d_dx, d_P, ldp, d_flag, rd.skip_word,
                        ctx->d_dW.as<double>(), C1, d0, use_m);
   }
-  return launch_ekf_commit(ctx, d_P, n, ldp, dC, d_dx, d_flag, mirror_src, mirror_dst, mirror_bytes);
+  return launch_ekf_commit(ctx, rd, d_P, n, ldp, dC, d_dx, d_flag, mirror_src, mirror_dst, mirror_bytes);
 }
 
 }  // namespace plv

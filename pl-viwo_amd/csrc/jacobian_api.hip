@@ -205,6 +205,8 @@ struct StageExtra {  // optional riders of the packed block (one-submission upda
   const uint8_t *obs_cam = nullptr;
   const CamSide *d_cams = nullptr;
   const uint8_t *d_obs_cam = nullptr;
+  // residual poses of the batch come from the CPI table on the device (null: the tracks' own res_R / res_p, if any)
+  const CpiStage *cpi = nullptr;
 };
 int stage_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *st, const plv_tracks *tr, int k,
                  const int *col_to_state, int ld, JacParams &P, StageExtra *ex = nullptr) {
@@ -221,7 +223,7 @@ int stage_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *s
   const auto ot = B.add(tr->obs_time, nobs);
   const auto uv = B.add<2>(tr->obs_uv, nobs);
   const auto pg = B.add<3>(tr->p_FinG, F), pgf = B.add<3>(tr->p_FinG_fej, F);
-  const CpiStage *cs = tr->res_R ? nullptr : ctx->cpi_stage;
+  const CpiStage *cs = tr->res_R || !ex ? nullptr : ex->cpi;
   if (cs) TRY(S.add_cpi(cs, (size_t)nobs));
   else S.add_res_poses(tr->res_R, tr->res_p, nobs);
   S.add_cols();
@@ -296,18 +298,20 @@ int reserve_batch(plv_ctx *ctx, plv_ctx_update_state *us, int n, int fdim, int k
   return us->bcols_of(fdim).reserve((size_t)k * 4);
 }
 // Launches the staged batch and books it in us->b*.  project (resident update path): build + null-space projection in one launch,
-// launch_projected(gather, gblocks) — the column map is published by its workgroup 0, and when a covariance of matching size is
+// launch_projected(gather, gblocks, gate) — `gate` (plv_update_gate_prepare; off: none) rides on it and is booked with the batch when
+// the launch took it; the column map is published by its workgroup 0, and when a covariance of matching size is
 // resident its gathers ride along; prior_ahead: the prior factor's second phase follows on the side stream.  Else launch_plain().
 // ph_launch / ph_prior: labels of the two host phases (null: not timed).
 template <class Projected, class Plain>
 int launch_batch(plv_ctx *ctx, plv_ctx_update_state *us, JacParams &P, int n, int fdim, int k, const int *col_to_state, int ld, bool project,
-                 bool prior_ahead, const char *ph_launch, const char *ph_prior, Projected launch_projected, Plain launch_plain) {
+                 bool prior_ahead, GateStage gate, const char *ph_launch, const char *ph_prior, Projected launch_projected, Plain launch_plain) {
   P.rows = us->brows.as<int>();
   P.Hf = us->bHf.as<double>();
   P.Hx = P.Hf + (size_t)n * fdim * ld;
   P.res = P.Hx + (size_t)n * k * ld;
   us->b_projected = false;
   us->b_gather_token = 0;
+  us->b_gate.on = 0;
   if (project) {
     P.cols_out = us->bcols_of(fdim).as<int>();
     bool can_gather = ctx->cov_n > 0;
@@ -320,13 +324,14 @@ int launch_batch(plv_ctx *ctx, plv_ctx_update_state *us, JacParams &P, int n, in
       TRY(gather_args(ctx, ctx->d_P.as<double>(), cn, cn, P.cols_in, k, g));
       gblocks = (std::max(k * cn, std::max(k * k, cn)) + 255) / 256;
     }
-    TRY(launch_projected(can_gather ? &g : nullptr, gblocks));
+    TRY(launch_projected(can_gather ? &g : nullptr, gblocks, gate));
     ph_l.stop();
     plv::HostPhase ph_p1(ph_prior);
     if (can_gather && prior_ahead) TRY(plv_prior_prefetch(ctx, 1, host_copy_of(us, P.cols_in, fdim), k, n, ld - fdim));
     ph_p1.stop();
     us->b_projected = true;
     us->b_gather_token = can_gather ? ctx->gather_stamp : 0;
+    us->b_gate = gate;
   } else {
     TRY(launch_plain());
   }
@@ -360,6 +365,8 @@ struct FusedTri {  // triangulate on the device first and let the Jacobian launc
   const plv_points_spec *spec = nullptr;  // speculative submission: the candidates' membership is decided on the device (spec_select_kernel)
   size_t o_member = 0, o_words = 0;       // out (spec): member [F] and the words (SpecSelectArgs) behind ok, part of the mirrored result block
   const int *d_words = nullptr;           // out (spec): the words on the device
+  GateStage gate{};                       // the gate the Jacobian launch is to end with (plv_update_gate_prepare)
+  const CpiStage *cpi = nullptr;          // StageExtra::cpi
 };
 int build_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *st, const plv_tracks *tr, int k,
                     const int *col_to_state, int ld, bool project, FusedTri *ft = nullptr) {
@@ -384,6 +391,7 @@ int build_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view
     StageExtra ex;
     ex.uvn = ft->uvn;
     ex.flags = ft->flags;
+    ex.cpi = ft->cpi;
     if (ft->spec) ex.spec_li = ft->spec->li, ex.spec_meta = ft->spec->meta, ex.spec_prevalid = ft->spec->prevalid;
     TRY(stage_inputs(ctx, us, st, tr, k, col_to_state, ld, P, &ex));
     const int nobs = tr->obs_ptr[F];
@@ -408,14 +416,14 @@ int build_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view
       A.flow_p1 = ft->spec->d_flow_p1, A.flow_n1 = ft->spec->d_flow_n1, A.flow_mask = ft->spec->d_flow_mask;
       A.obs_uv = ex.d_obs_uv, A.obs_uvn = const_cast<float *>(ex.d_uvn), A.obs_end = ex.d_obs_end;
       A.sel_flags = const_cast<unsigned char *>(ex.d_flags), A.member = (unsigned char *)(d + o_member), A.words = (int *)(d + o_words);
-      if (!ctx->gate_stage.on) {
+      if (!ft->gate.on) {
         set_last_error("speculative point submission needs the gate inside the Jacobian launch");
         return PLV_E_BADARG;
       }
       A.order = (int *)(d + o_order), A.rows_out = us->brows.as<int>();
       A.tri_p = (double *)(d + o_p), A.tri_err = (double *)(d + o_err), A.tri_ok = (unsigned char *)(d + o_ok);
-      A.chi2 = ctx->gate_stage.chi2, A.accepted = ctx->gate_stage.accepted, A.acc_rows = ctx->gate_stage.acc_rows;
-      A.zero_word = ctx->gate_stage.n_acc_next, A.cols_out = us->bcols.as<int>(), A.cols_in = P.cols_in, A.k = k;
+      A.chi2 = ft->gate.chi2, A.accepted = ft->gate.accepted, A.acc_rows = ft->gate.acc_rows;
+      A.zero_word = ft->gate.n_acc_next, A.cols_out = us->bcols.as<int>(), A.cols_in = P.cols_in, A.k = k;
       TRY(launch_spec_select(ctx, A));
       P.spec_order = A.order, P.spec_count = A.words + 2, P.spec_pass = A.words + 4;
       ft->d_words = A.words;
@@ -440,12 +448,12 @@ int build_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view
   }
   ph_stage.stop();
   return launch_batch(
-      ctx, us, P, F, 3, k, col_to_state, ld, project, prior_ahead, "build: gather arguments + Jacobian launch",
+      ctx, us, P, F, 3, k, col_to_state, ld, project, prior_ahead, ft ? ft->gate : GateStage{}, "build: gather arguments + Jacobian launch",
       "build: prior prefetch, phase 1 (side stream)",
-      [&](const GatherArgs *g, int gblocks) {
+      [&](const GatherArgs *g, int gblocks, GateStage &gt) {
         if (fuse_tri)
-          return launch_jacobians_projected(ctx, P, g, gblocks, tri_opt, tri_poses, tri_valid, tri_uvn, tri_p, tri_ok, tri_err, tri_max_obs);
-        return launch_jacobians_projected(ctx, P, g, gblocks, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tri_max_obs);
+          return launch_jacobians_projected(ctx, P, g, gblocks, gt, tri_opt, tri_poses, tri_valid, tri_uvn, tri_p, tri_ok, tri_err, tri_max_obs);
+        return launch_jacobians_projected(ctx, P, g, gblocks, gt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tri_max_obs);
       },
       [&] {
         P.cols_out = us->bcols.as<int>();
@@ -472,17 +480,11 @@ namespace plv {
 // in both cases.
 typedef plv_ctx_update_state::PointJob PointJob;
 static PointJob &point_job(plv_ctx *ctx) { return plv_update_state(ctx)->point_job; }
-// the commits of a speculative point batch (its launch, and a re-run inside the wait) save the covariance they overwrite
-static void spec_save_arm(plv_ctx *ctx, plv_ctx_update_state *us, bool on) {
-  ctx->cov_save = on ? us->spec_save.as<double>() : nullptr;
-  ctx->cov_save_word = on ? us->chain_words.as<unsigned>() + 1 : nullptr;
-  ctx->cov_save_seq = on ? us->spec_save_seq : 0;
-}
 static hipEvent_t g_ce[3] = {nullptr, nullptr, nullptr};
 
 int plv_points_update_submit(plv_ctx *ctx, const plv_state_view *st, const plv_tracks *all, const plv_tri_options *tri, const uint8_t *flags,
                              int max_sel, int k, const int *col_to_state, int ld, double sigma2, double chi2_mult, double res_norm_gate,
-                             const plv_points_spec *spec) {
+                             const plv_points_spec *spec, int rows_hint, const CpiStage *cpi) {
   if (!ctx || !all || !tri || !flags || !all->obs_uvn) return PLV_E_BADARG;
   (void)hipSetDevice(ctx->device);
   auto *us = plv_update_state(ctx);
@@ -494,6 +496,7 @@ int plv_points_update_submit(plv_ctx *ctx, const plv_state_view *st, const plv_t
   t2.p_FinG = t2.p_FinG_fej = p_dummy.data();  // (outputs of the triangulation: the staged copy is never read)
   FusedTri ft{tri, all->obs_uvn, flags, max_sel, 0, 0, 0};
   ft.spec = spec;
+  ft.cpi = cpi;
   // PLV_KNOB_CHAIN_EVENTS (with PLV_KNOB_HOST_TIMING): three timed events on the stream — at entry (the stream is idle: stamped at once),
   // behind the Jacobian launch, behind the update's last kernel — to set the device's view of the chain against the host's phases
   J.chain_events = plv::knob(plv::PLV_KNOB_CHAIN_EVENTS) && plv::host_phases().on;
@@ -504,7 +507,7 @@ int plv_points_update_submit(plv_ctx *ctx, const plv_state_view *st, const plv_t
     (void)hipEventRecord(g_ce[0], ctx->stream);
   }
   plv::HostPhase ph_a("points fused: stage + triangulate + jacobians enqueued");
-  TRY(plv_update_gate_prepare(ctx, all->n_feat, 3, k, ld, sigma2, chi2_mult, res_norm_gate, 0));
+  TRY(plv_update_gate_prepare(ctx, all->n_feat, 3, k, ld, sigma2, chi2_mult, res_norm_gate, 0, rows_hint, &ft.gate));
   TRY(build_on_device(ctx, us, st, &t2, k, col_to_state, ld, true, &ft));
   ph_a.stop();
   plv::frame_mark("@ point Jacobian launch enqueued");
@@ -516,28 +519,28 @@ int plv_points_update_submit(plv_ctx *ctx, const plv_state_view *st, const plv_t
   plv::HostPhase ph_b("points fused: gate .. EKF enqueued");
   // the triangulation results reach the host with the update's result block (copied by its last kernel), or by a copy command when
   // the chain ended another way; either lands before the wait below returns
-  ctx->mirror2_src = sg.tri.as<char>() + ft.o_p, ctx->mirror2_dst = sg.h_tri.p, ctx->mirror2_bytes = mirror_bytes, ctx->mirror2_taken = false;
+  UpdateRiders riders;
+  EkfRiders &ekf = riders.ekf;
+  ekf.mirror2_src = sg.tri.as<char>() + ft.o_p, ekf.mirror2_dst = sg.h_tri.p, ekf.mirror2_bytes = mirror_bytes;
   // (for a line launch chained behind this update, plv_camera_try_update: the commit kernel leaves "state changed" in a device word)
   TRY(us->chain_words.reserve(64));
   us->applied_word = us->chain_words.as<int>();
-  ctx->applied_word = us->applied_word, ctx->applied_used = false;
-  ctx->cap_words = spec ? ft.d_words + 3 : nullptr, ctx->cap = max_sel;
+  ekf.applied_word = us->applied_word;
+  ekf.cap_words = spec ? ft.d_words + 3 : nullptr, ekf.cap = max_sel;
   us->spec_save_seq = 0;
   if (spec) {  // (the commit saves what it overwrites: plv_points_spec_undo)
     TRY(us->spec_save.reserve((size_t)ctx->cov_n * ctx->cov_n * 8));
     if (++us->spec_save_count == 0) ++us->spec_save_count;  // (0: no batch)
     us->spec_save_seq = us->spec_save_count;
     us->spec_save_n = ctx->cov_n;
-    spec_save_arm(ctx, us, true);
+    // (its launch's commit, and that of a re-run inside the wait, save the covariance they overwrite)
+    J.save = CovSave{us->spec_save.as<double>(), us->chain_words.as<unsigned>() + 1, us->spec_save_seq};
   }
-  int rc = plv_msckf_update_resident_launch(ctx, sigma2, chi2_mult, res_norm_gate);
-  ctx->cap_words = nullptr;
-  spec_save_arm(ctx, us, false);
-  us->applied_armed = rc == PLV_OK && ctx->applied_used;
-  ctx->applied_word = nullptr, ctx->applied_used = false;
+  ekf.save = J.save;
+  int rc = update_resident_launch(ctx, sigma2, chi2_mult, res_norm_gate, riders);
+  us->applied_armed = rc == PLV_OK && riders.applied_used;
   us->pt_tri_p = (const double *)(sg.tri.as<char>() + ft.o_p), us->pt_tri_ok = (const unsigned char *)(sg.tri.as<char>() + ft.o_ok), us->pt_tri_F = F;
-  const bool mirrored = ctx->mirror2_taken;
-  ctx->mirror2_src = nullptr, ctx->mirror2_dst = nullptr, ctx->mirror2_bytes = 0, ctx->mirror2_taken = false;
+  const bool mirrored = riders.mirror2_taken;
   if (!mirrored)
     PLV_HIP_CHECK(plv::memcpy_async(sg.h_tri.p, sg.tri.as<char>() + ft.o_p, mirror_bytes, hipMemcpyDeviceToHost, ctx->stream));
   ph_b.stop();
@@ -549,7 +552,8 @@ int plv_points_update_submit(plv_ctx *ctx, const plv_state_view *st, const plv_t
 }
 
 int plv_points_update_collect(plv_ctx *ctx, double *p_out, uint8_t *ok_out, double *err_out, uint8_t *accepted, int *n_rows, double *dx,
-                              void (*before_wait)(void *), void *before_wait_arg, uint8_t *member, int *spec_count, int *spec_over) {
+                              void (*before_wait)(void *), void *before_wait_arg, int (*wait_poll)(void *), void *wait_poll_arg, uint8_t *member,
+                              int *spec_count, int *spec_over) {
   if (!ctx || !p_out || !ok_out || !err_out || !accepted || !dx) return PLV_E_BADARG;
   auto *us = plv_update_state(ctx);
   PointJob &J = point_job(ctx);
@@ -564,9 +568,9 @@ int plv_points_update_collect(plv_ctx *ctx, double *p_out, uint8_t *ok_out, doub
   if (before_wait) before_wait(before_wait_arg);  // host work of the caller that fits into the wait
   // ... and work that becomes possible DURING the wait (the line pool, once the line worker has finished the frame's feed): the
   // caller's poll function is tried until it reports that nothing is left, or the update is done
-  if (rc == PLV_OK && ctx->wait_poll && us->done_ev) {
+  if (rc == PLV_OK && wait_poll && us->done_ev) {
     while (hipEventQuery(us->done_ev) == hipErrorNotReady || plv::knob(plv::PLV_KNOB_CHAIN_ALWAYS)) {
-      if (ctx->wait_poll(ctx->wait_poll_arg)) break;
+      if (wait_poll(wait_poll_arg)) break;
       for (int i = 0; i < 32; ++i) __builtin_ia32_pause();
     }
   }
@@ -574,9 +578,7 @@ int plv_points_update_collect(plv_ctx *ctx, double *p_out, uint8_t *ok_out, doub
   plv::frame_mark("@ host work inside the point wait done");
   plv::NsScope ns_pw(plv::counters().points_wait_ns);
   plv::HostPhase ph_d("points fused: wait");
-  if (J.spec && us->spec_save_seq) spec_save_arm(ctx, us, true);
-  if (rc == PLV_OK) rc = plv_msckf_update_resident_wait(ctx, accepted, n_rows, dx);  // (ends at the update's last kernel)
-  spec_save_arm(ctx, us, false);
+  if (rc == PLV_OK) rc = update_resident_wait(ctx, accepted, n_rows, dx, J.save);  // (ends at the update's last kernel)
   if (rc != PLV_OK || !J.mirrored) PLV_HIP_CHECK(plv::stream_sync(ctx->stream));    // (the copy command enqueued behind it)
   ph_d.stop();
   plv::frame_mark("@ point update collected");
@@ -625,15 +627,6 @@ int plv_points_spec_undo(plv_ctx *ctx) {
   ++ctx->gather_stamp;
   ctx->cov_host_synced = ctx->gather_stamp;
   return PLV_OK;
-}
-
-int plv_points_update_fused(plv_ctx *ctx, const plv_state_view *st, const plv_tracks *all, const plv_tri_options *tri,
-                            const uint8_t *flags, int max_sel, int k, const int *col_to_state, int ld, double sigma2, double chi2_mult,
-                            double res_norm_gate, double *p_out, uint8_t *ok_out, double *err_out, uint8_t *accepted, int *n_rows,
-                            double *dx, void (*before_wait)(void *), void *before_wait_arg) {
-  if (!ctx || !all || !tri || !flags || !p_out || !ok_out || !err_out || !accepted || !dx || !all->obs_uvn) return PLV_E_BADARG;
-  TRY(plv_points_update_submit(ctx, st, all, tri, flags, max_sel, k, col_to_state, ld, sigma2, chi2_mult, res_norm_gate, nullptr));
-  return plv_points_update_collect(ctx, p_out, ok_out, err_out, accepted, n_rows, dx, before_wait, before_wait_arg, nullptr, nullptr, nullptr);
 }
 }  // namespace plv
 extern "C" {
@@ -778,7 +771,8 @@ int build_stereo_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_sta
   JacParams P{};
   TRY(stage_inputs(ctx, us, st, &s->tracks, k, col_to_state, ld, P, &ex));
   return launch_batch(
-      ctx, us, P, F, 3, k, col_to_state, ld, false, false, nullptr, nullptr, [](const GatherArgs *, int) { return (int)PLV_E_BADARG; },
+      ctx, us, P, F, 3, k, col_to_state, ld, false, false, GateStage{}, nullptr, nullptr,
+      [](const GatherArgs *, int, GateStage &) { return (int)PLV_E_BADARG; },
       [&] {
         P.cols_out = us->bcols.as<int>();
         return launch_jacobians_stereo(ctx, P, ex.d_cams, ex.d_obs_cam);
@@ -933,7 +927,7 @@ int stage_line_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_vi
   if (lt->line_FinG) lg = B.add<6>(lt->line_FinG, L);
   if (lt->D) D = B.add(lt->D, L);
   if (lt->has_pt) ap = B.add<3>(lt->anchor_pt, L), hp = B.add(lt->has_pt, L);
-  const CpiStage *cs = lt->res_R ? nullptr : ctx->cpi_stage;
+  const CpiStage *cs = lt->res_R || !ex ? nullptr : ex->cpi;
   if (cs) TRY(S.add_cpi(cs, (size_t)nobs));
   else {
     S.add_res_poses(lt->res_R, lt->res_p, nobs);
@@ -996,6 +990,8 @@ struct FusedLineTri {
   int max_sel;
   size_t o_lines, o_ok;  // out: results in the line staging's tri (lines [L][6], ok [L])
   const plv_state_view *st_tri = nullptr;  // the state of the triangulation when it is not the one of the Jacobians
+  GateStage gate{};                        // the gate the Jacobian launch is to end with (plv_update_gate_prepare)
+  const CpiStage *cpi = nullptr;           // StageExtra::cpi
 };
 int build_lines_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *st, const plv_line_tracks *lt, int k,
                           const int *col_to_state, int ld, bool project, FusedLineTri *ft = nullptr) {
@@ -1007,14 +1003,15 @@ int build_lines_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_stat
   // accepts a line or two, fewer rows than columns, and then goes through EKFUpdate on the rows themselves (plv_api.hip, round 6); the
   // four enqueue calls were 8-10 us of the caller's thread in front of the line launch, the factor 50 us of side-stream work per frame
   // that nothing read.  (A probed update that does accept more rows than columns starts the factor when it knows.)
-  const bool prior_ahead = project && ctx->cov_n > 0 && !(ctx->gate_stage.on && ctx->gate_stage.probe_dst);
+  GateStage gate = ft ? ft->gate : GateStage{};
+  const bool prior_ahead = project && ctx->cov_n > 0 && !(gate.on && gate.probe_dst);
   if (prior_ahead) TRY(plv_prior_prefetch(ctx, 0, nullptr, k, L, ld - 6));  // (before the upload goes onto the stream)
   JacParams P{}, Pt{};
   bool fuse_tri = false;
   double *tri_cam = nullptr, *tri_imu = nullptr, *tri_lines = nullptr;
   unsigned char *tri_valid = nullptr, *tri_ok = nullptr;
   StageExtra ex;
-  if (ft) ex.flags = ft->flags;
+  if (ft) ex.flags = ft->flags, ex.cpi = ft->cpi;
   {
     plv::HostPhase ph_stage("build lines: inputs staged + upload enqueued");
     TRY(stage_line_inputs(ctx, us, st, lt, k, col_to_state, ld, P, &ex, ft ? ft->st_tri : nullptr, &Pt));
@@ -1038,17 +1035,17 @@ int build_lines_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_stat
     P.tri_err = nullptr;
     P.max_sel = ft->max_sel;
     ft->o_lines = o_lines, ft->o_ok = o_ok;
-    if (ctx->gate_stage.on && ctx->gate_stage.probe_dst) {  // the gate inside the launch also carries the triangulated lines to the host
-      ctx->gate_stage.probe_src = (const unsigned char *)(d + o_lines);
-      ctx->gate_stage.probe_stride_a = 48, ctx->gate_stage.probe_off_b = L * 48, ctx->gate_stage.probe_stride_b = 1;
+    if (gate.on && gate.probe_dst) {  // the gate inside the launch also carries the triangulated lines to the host
+      gate.probe_src = (const unsigned char *)(d + o_lines);
+      gate.probe_stride_a = 48, gate.probe_off_b = L * 48, gate.probe_stride_b = 1;
     }
   }
   return launch_batch(
-      ctx, us, P, L, 6, k, col_to_state, ld, project, prior_ahead, nullptr, nullptr,
-      [&](const GatherArgs *g, int gblocks) {
+      ctx, us, P, L, 6, k, col_to_state, ld, project, prior_ahead, gate, nullptr, nullptr,
+      [&](const GatherArgs *g, int gblocks, GateStage &gt) {
         const int line_max_obs = max_obs(lt->obs_ptr, L);
-        if (fuse_tri) return launch_line_jacobians_projected(ctx, P, g, gblocks, &Pt, tri_cam, tri_imu, tri_valid, tri_lines, tri_ok, line_max_obs);
-        return launch_line_jacobians_projected(ctx, P, g, gblocks, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, line_max_obs);
+        if (fuse_tri) return launch_line_jacobians_projected(ctx, P, g, gblocks, gt, &Pt, tri_cam, tri_imu, tri_valid, tri_lines, tri_ok, line_max_obs);
+        return launch_line_jacobians_projected(ctx, P, g, gblocks, gt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, line_max_obs);
       },
       [&]() -> int {  // (nothing publishes the column map on this route)
         PLV_HIP_CHECK(plv::memcpy_async(us->bcols_l.p, col_to_state, (size_t)k * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1067,16 +1064,18 @@ namespace plv {
 // compression + EKFUpdate only when something was accepted, and collects.  plv_camera_try_update calls `submit` while the point
 // update of the frame is still running (plv_ctx::chain.on: the launch then forms the corrected state itself, JacParams::chain_dx).
 int plv_lines_update_fused_submit(plv_ctx *ctx, const plv_state_view *st, const plv_state_view *st_tri, const plv_line_tracks *all,
-                                  const uint8_t *flags, int max_sel, int k, const int *col_to_state, int ld, double sigma2, double chi2_mult) {
+                                  const uint8_t *flags, int max_sel, int k, const int *col_to_state, int ld, double sigma2, double chi2_mult,
+                                  int rows_hint, const CpiStage *cpi) {
   if (!ctx || !all || !flags) return PLV_E_BADARG;
   (void)hipSetDevice(ctx->device);
   auto *us = plv_update_state(ctx);
   auto &sg = us->staging_of(6);
   FusedLineTri ft{flags, max_sel, 0, 0, st_tri};
+  ft.cpi = cpi;
   const int L = all->n_lines;
   TRY(sg.h_tri.reserve((size_t)L * 49 + 16));
-  TRY(plv_update_gate_prepare(ctx, L, 6, k, ld, sigma2, chi2_mult, 0.0, 1));
-  ctx->gate_stage.probe_dst = (unsigned char *)sg.h_tri.p;  // (probe_src and the strides: build_lines_on_device, where the results' place is decided)
+  TRY(plv_update_gate_prepare(ctx, L, 6, k, ld, sigma2, chi2_mult, 0.0, 1, rows_hint, &ft.gate));
+  ft.gate.probe_dst = (unsigned char *)sg.h_tri.p;  // (probe_src and the strides: build_lines_on_device, where the results' place is decided)
   TRY(build_lines_on_device(ctx, us, st, all, k, col_to_state, ld, true, &ft));
   us->b_single_use = true;
   us->lt_o_lines = ft.o_lines, us->lt_L = L;
@@ -1090,27 +1089,19 @@ int plv_lines_update_fused_finish(plv_ctx *ctx, double sigma2, double chi2_mult,
   auto &sg = us->staging_of(6);
   const int L = us->lt_L;
   // the gate's workgroups leave their verdicts and the triangulated lines in pinned memory and the launch function looks at them
-  // before it enqueues compression + EKF (plv_ctx::probe): a line update in which nothing passes the gate ends there
-  ctx->probe = true, ctx->probe_done = false;
-  ctx->probe_src = sg.tri.as<char>() + us->lt_o_lines, ctx->probe_dst = sg.h_tri.p;
-  ctx->probe_stride_a = 48, ctx->probe_off_b = L * 48, ctx->probe_stride_b = 1;
-  ctx->probe_hook = before_wait, ctx->probe_hook_arg = before_wait_arg;
-  int rc = plv_msckf_update_resident_launch(ctx, sigma2, chi2_mult, 0.0);
-  ctx->probe = false, ctx->probe_src = nullptr, ctx->probe_dst = nullptr, ctx->probe_hook = nullptr, ctx->probe_hook_arg = nullptr;
+  // before it enqueues compression + EKF (UpdateRiders::probe): a line update in which nothing passes the gate ends there
+  UpdateRiders riders;
+  riders.probe = true;
+  riders.probe_src = sg.tri.as<char>() + us->lt_o_lines, riders.probe_dst = sg.h_tri.p;
+  riders.probe_stride_a = 48, riders.probe_off_b = L * 48, riders.probe_stride_b = 1;
+  riders.probe_hook = before_wait, riders.probe_hook_arg = before_wait_arg;
+  int rc = update_resident_launch(ctx, sigma2, chi2_mult, 0.0, riders);
   if (rc == PLV_OK) rc = plv_msckf_update_resident_wait(ctx, accepted, n_rows, dx);
   else PLV_HIP_CHECK(plv::stream_sync(ctx->stream));
   const char *h = sg.h_tri.as<char>();
   memcpy(lines_out, h, (size_t)L * 48);
   memcpy(ok_out, h + (size_t)L * 48, (size_t)L);
   return rc;
-}
-int plv_lines_update_fused(plv_ctx *ctx, const plv_state_view *st, const plv_state_view *st_tri, const plv_line_tracks *all,
-                           const uint8_t *flags, int max_sel, int k, const int *col_to_state, int ld, double sigma2, double chi2_mult,
-                           double *lines_out, uint8_t *ok_out, uint8_t *accepted, int *n_rows, double *dx, void (*before_wait)(void *),
-                           void *before_wait_arg) {
-  if (!ctx || !all || !flags || !lines_out || !ok_out || !accepted || !dx) return PLV_E_BADARG;
-  TRY(plv_lines_update_fused_submit(ctx, st, st_tri, all, flags, max_sel, k, col_to_state, ld, sigma2, chi2_mult));
-  return plv_lines_update_fused_finish(ctx, sigma2, chi2_mult, lines_out, ok_out, accepted, n_rows, dx, before_wait, before_wait_arg);
 }
 }  // namespace plv
 

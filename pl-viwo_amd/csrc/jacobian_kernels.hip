@@ -2096,8 +2096,8 @@ int launch_line_jacobians(plv_ctx *ctx, const JacParams &P) {
   return PLV_OK;
 }
 
-int launch_line_jacobians_projected(plv_ctx *ctx, const JacParams &P, const GatherArgs *g, int gather_blocks, const JacParams *Pt, double *d_cam,
-                                    double *d_imu, unsigned char *d_valid, double *d_lines, unsigned char *d_ok, int max_obs) {
+int launch_line_jacobians_projected(plv_ctx *ctx, const JacParams &P, const GatherArgs *g, int gather_blocks, GateStage &gate, const JacParams *Pt,
+                                    double *d_cam, double *d_imu, unsigned char *d_valid, double *d_lines, unsigned char *d_ok, int max_obs) {
   ProfScope ps(ctx->prof, Pt ? "line_tri_jacobian_nullspace_kernel" : "line_jacobian_nullspace_kernel", ctx->stream);
   if (2 * (P.n_clones - 3) > JAC_MAX_WIN) {
     set_last_error("line jacobians: %d clones exceed the window table (%d)", P.n_clones, JAC_MAX_WIN / 2 + 3);
@@ -2113,8 +2113,6 @@ int launch_line_jacobians_projected(plv_ctx *ctx, const JacParams &P, const Gath
   }
   GatherArgs none{};
   LineTriStage tri{Pt ? 1 : 0, max_obs, d_cam, d_imu, d_valid, d_lines, d_ok};
-  GateStage gate = ctx->gate_stage;
-  ctx->gate_stage.on = 0;  // (one launch takes it)
   const size_t gate_off = ((size_t)lay.tab * sizeof(double) + 63) & ~(size_t)63;  // (overlays tables and slots: fused_lds_layout)
   const size_t t_off = (gate_off + sizeof(GateLds) + 63) & ~(size_t)63;
   const size_t ps_off = (std::max(shm, t_off + (size_t)GATE_MMAX * GATE_TLD * sizeof(double)) + 63) & ~(size_t)63;
@@ -2124,7 +2122,6 @@ int launch_line_jacobians_projected(plv_ctx *ctx, const JacParams &P, const Gath
     gate.lds_off = (int)gate_off, gate.ps_off = (int)ps_off, gate.t_off = (int)t_off;
     shm = gate_end;
   }
-  ctx->gate_stage_taken = gate.on != 0;
   PLV_HIP_CHECK(ensure_dyn_smem((const void *)line_jacobian_nullspace_kernel, (int)shm));
   if (jac_stamps().on) TRY_STAMP(jac_stamps().arm(ctx->stream, P.n_feat));
   hipLaunchKernelGGL(line_jacobian_nullspace_kernel, dim3(P.n_feat + (g ? gather_blocks : 0)), dim3(256), shm, ctx->stream, P, P.n_feat,
@@ -2161,8 +2158,8 @@ int launch_triangulate(plv_ctx *ctx, const JacParams &P, double *d_poses, unsign
   return PLV_OK;
 }
 
-int launch_jacobians_projected(plv_ctx *ctx, const JacParams &P, const GatherArgs *g, int gather_blocks, const plv_tri_options *tri_opt,
-                               double *d_poses, unsigned char *d_valid, const float *d_uvn, double *d_p, unsigned char *d_ok, double *d_err, int max_obs) {
+int launch_jacobians_projected(plv_ctx *ctx, const JacParams &P, const GatherArgs *g, int gather_blocks, GateStage &gate,
+                               const plv_tri_options *tri_opt, double *d_poses, unsigned char *d_valid, const float *d_uvn, double *d_p, unsigned char *d_ok, double *d_err, int max_obs) {
   ProfScope ps(ctx->prof, tri_opt ? "tri_jacobian_nullspace_kernel" : "jacobian_nullspace_kernel", ctx->stream);
   if (2 * (P.n_clones - 3) > JAC_MAX_WIN) {
     set_last_error("jacobians: %d clones exceed the window table (%d)", P.n_clones, JAC_MAX_WIN / 2 + 3);
@@ -2180,8 +2177,6 @@ int launch_jacobians_projected(plv_ctx *ctx, const JacParams &P, const GatherArg
   PointTriStage tri{};
   tri.max_obs = max_obs;
   if (tri_opt) tri = PointTriStage{1, max_obs, d_poses, d_valid, d_uvn, *tri_opt, d_p, d_ok, d_err};
-  GateStage gate = ctx->gate_stage;
-  ctx->gate_stage.on = 0;  // (one launch takes it)
   // the gate's LDS block overlays tables, scratch and slots (fused_lds_layout): taken where it fits behind the entry's block
   const size_t gate_off = ((size_t)lay.tab * sizeof(double) + 63) & ~(size_t)63;
   // (GateLds and T overlay tables, scratch and slots: dead when the gate starts; the prior block, staged early, sits behind them)
@@ -2193,7 +2188,6 @@ int launch_jacobians_projected(plv_ctx *ctx, const JacParams &P, const GatherArg
     gate.lds_off = (int)gate_off, gate.ps_off = (int)ps_off, gate.t_off = (int)t_off;
     shm = gate_end;
   }
-  ctx->gate_stage_taken = gate.on != 0;
   PLV_HIP_CHECK(ensure_dyn_smem((const void *)jacobian_nullspace_kernel, (int)shm));
   if (jac_stamps().on) TRY_STAMP(jac_stamps().arm(ctx->stream, P.n_feat));
   // (a speculative batch: one workgroup per pool entry, at most spec_grid(max_sel) of them — spec_select_kernel's list — not one per candidate)

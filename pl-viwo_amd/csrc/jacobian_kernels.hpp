@@ -1,5 +1,6 @@
 // jacobian_kernels.hpp — device-side view of plv_state_view / plv_tracks for jacobian_kernel.
 #pragma once
+#include "gate_stage.hpp"
 #include "plv_ctx.hpp"
 
 namespace plv {
@@ -76,7 +77,7 @@ struct JacParams {
   const int *spec_order, *spec_count;
   // ... and counts the candidates its workgroups selected (own verdict) in *spec_pass: a pool larger than max_sel is worked on as long
   // as it fits the launch (SpecSelectArgs::grid); whether the selection loop's cap would have cut it is known when all of them are
-  // done — the update's commit kernel reads the count and leaves the state alone when it reached max_sel (plv_ctx::cap_words)
+  // done — the update's commit kernel reads the count and leaves the state alone when it reached max_sel (EkfRiders::cap_words)
   int *spec_pass;
   // use_imu_cov: CPI covariance (6 x 6 row-major) of the pose each observation was made at and the clone it hangs on
   int use_imu_cov;
@@ -149,12 +150,13 @@ int launch_landmark_system(plv_ctx *ctx, const JacParams &P, const LandmarkSys &
 struct GatherArgs;
 // the batch built AND null-space projected in one launch (resident update path); g != null: the covariance gathers ride along
 // tri_opt != null: every workgroup first triangulates its feature (arguments as launch_triangulate takes them)
-int launch_jacobians_projected(plv_ctx *ctx, const JacParams &P, const GatherArgs *g, int gather_blocks, const plv_tri_options *tri_opt = nullptr,
+// gate: the gate the launch ends with (plv_update_gate_prepare; off: none); off on return when the launch did not take it (no room)
+int launch_jacobians_projected(plv_ctx *ctx, const JacParams &P, const GatherArgs *g, int gather_blocks, GateStage &gate, const plv_tri_options *tri_opt = nullptr,
                                double *d_poses = nullptr, unsigned char *d_valid = nullptr, const float *d_uvn = nullptr, double *d_p = nullptr,
                                unsigned char *d_ok = nullptr, double *d_err = nullptr, int max_obs = 0);
 int launch_line_jacobians(plv_ctx *ctx, const JacParams &P);
 // Pt != null: every workgroup first triangulates its line on the state Pt (scratch and results as launch_triangulate_lines takes them)
-int launch_line_jacobians_projected(plv_ctx *ctx, const JacParams &P, const GatherArgs *g, int gather_blocks, const JacParams *Pt = nullptr,
+int launch_line_jacobians_projected(plv_ctx *ctx, const JacParams &P, const GatherArgs *g, int gather_blocks, GateStage &gate, const JacParams *Pt = nullptr,
                                     double *d_cam = nullptr, double *d_imu = nullptr, unsigned char *d_valid = nullptr, double *d_lines = nullptr,
                                     unsigned char *d_ok = nullptr, int max_obs = 0);
 int launch_triangulate_lines(plv_ctx *ctx, const JacParams &P, double *d_poses, double *d_imu, unsigned char *d_valid,

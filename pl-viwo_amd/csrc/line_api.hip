@@ -1264,13 +1264,10 @@ static int lines_first_half(plv_ctx *ctx, LineTracker *T, const plv_state_view *
   bool launched = false;
   if (rc == PLV_OK && J.k > 0) {
     plv::HostPhase ph_sub("update_lines: fused submit (gate prepare + stage + upload + launch)");
-    ctx->gate_rows_hint = 2 * J.most_valid;
     ch.on = chained;
     const CpiStage cpi_stage = J.cpi.stage(opt->cpi);
-    ctx->cpi_stage = J.cpi.on ? &cpi_stage : nullptr;
     rc = plv_lines_update_fused_submit(ctx, st, st_tri, &all, J.flags.data(), cap, J.k, J.cols.data(), 2 * opt->max_obs, st->sigma_pix * st->sigma_pix,
-                                       opt->chi2_mult);
-    ctx->cpi_stage = nullptr;
+                                       opt->chi2_mult, 2 * J.most_valid, J.cpi.on ? &cpi_stage : nullptr);
     ch.on = false;
     launched = rc == PLV_OK;
   }
@@ -1313,7 +1310,6 @@ void plv_camera_lines_job_abort2(plv_ctx *ctx, int keep_pool) {
   LineTracker *T = ltr(ctx, false);
   if (!T->ujob.pending) return;
   (void)plv::stream_sync(ctx->stream);
-  ctx->gate_stage.on = 0, ctx->gate_stage_taken = false;
   T->pool_prep = std::move(T->ujob.LP);
   T->pool_prep.valid = true;
   if (!keep_pool) discard_line_pool(T);

@@ -504,10 +504,10 @@ int plv_ekf_update(plv_ctx *ctx, double *P, int n, int ldp, const double *H, int
   double *d_dx = lay.dx(d_res);
   int *d_flag = lay.status(d_res);
   if (ekf_fast_fits(r))
-    TRY(launch_ekf_fast(ctx, ctx->d_P.as<double>(), n, n, ctx->d_H.as<double>(), r, k, r, ctx->d_cols.as<int>(),
+    TRY(launch_ekf_fast(ctx, EkfRiders{}, ctx->d_P.as<double>(), n, n, ctx->d_H.as<double>(), r, k, r, ctx->d_cols.as<int>(),
                         ctx->d_res.as<double>(), dR, d_dx, d_flag));
   else
-    TRY(launch_ekf(ctx, ctx->d_P.as<double>(), n, n, ctx->d_H.as<double>(), r, k, r, ctx->d_cols.as<int>(),
+    TRY(launch_ekf(ctx, EkfRiders{}, ctx->d_P.as<double>(), n, n, ctx->d_H.as<double>(), r, k, r, ctx->d_cols.as<int>(),
                    ctx->d_res.as<double>(), dR, d_dx, d_flag));
   TRY(ctx->h_pin.reserve(lay.head_bytes()));
   TRY(d2h(ctx, ctx->h_pin.p, us->result.p, lay.head_bytes()));
@@ -666,6 +666,7 @@ int plv_feat_batch_upload(plv_ctx *ctx, int F, int fdim, int k, int ld, const in
   us->b_single_use = false;
   us->b_projected = false;
   us->b_gather_token = 0;
+  us->b_gate.on = 0;
   return stream_wait(ctx);
 }
 
@@ -741,16 +742,15 @@ int fill_gate(plv_ctx *ctx, plv_ctx_update_state *us, G &g, const UpdateBuffers 
 }  // namespace
 
 namespace plv {
-// Called by the one-submission updates before they build their batch: fills plv_ctx::gate_stage so that the projected Jacobian
-// launch ends with the gate of every entry (gate_core.hpp) — verdicts, counter, stack — and plv_msckf_update_resident_launch starts
-// behind it.  The buffers are the ones that launch function reserves (reserve_update_buffers: no reallocation in between).
-int plv_update_gate_prepare(plv_ctx *ctx, int F, int fdim, int k, int ld, double sigma2, double chi2_mult, double res_norm_gate, int probe) {
+// Called by the one-submission updates before they build their batch: fills *gate so that the projected Jacobian launch ends with
+// the gate of every entry (gate_core.hpp) — verdicts, counter, stack — and the update launch starts behind it.  The buffers are the
+// ones that launch function reserves (reserve_update_buffers: no reallocation in between).
+int plv_update_gate_prepare(plv_ctx *ctx, int F, int fdim, int k, int ld, double sigma2, double chi2_mult, double res_norm_gate, int probe,
+                            int rows_hint, GateStage *gate) {
   auto *us = ustate(ctx);
-  ctx->gate_stage = plv::GateStage{};
-  ctx->gate_stage_taken = false;
+  *gate = plv::GateStage{};
   const int n = ctx->cov_n, mp_max = ld - fdim;
-  const int rows_most = ctx->gate_rows_hint > 0 ? std::min(ctx->gate_rows_hint, ld) : ld;
-  ctx->gate_rows_hint = 0;
+  const int rows_most = rows_hint > 0 ? std::min(rows_hint, ld) : ld;
   if (plv::knob(plv::PLV_KNOB_GATE_SEPARATE) || us->graph_mode || n < 1 || F < 1 || mp_max < 1 || rows_most - fdim > GATE_MMAX || k > GATE_KMAX)
     return PLV_OK;
   UpdateBuffers b;
@@ -762,12 +762,13 @@ int plv_update_gate_prepare(plv_ctx *ctx, int F, int fdim, int k, int ld, double
   // use, the block moved, cov_n changed (the words sit behind dx) or that launch declined the gate: then a memset does
   if (!(aw.z_ptr == b.dev && aw.z_n == n && aw.z_word == aw.word)) PLV_HIP_CHECK(hipMemsetAsync(d_flag + aw.word, 0, 4, ctx->stream));
   aw.z_ptr = nullptr;  // (known again once a launch has taken the gate: plv_msckf_update_resident_launch)
-  plv::GateStage &g = ctx->gate_stage;
+  plv::GateStage g{};
   g.on = 1;
   // (with probe the caller adds the second block: probe_src / probe_dst / strides)
   TRY(fill_gate(ctx, us, g, b, F, fdim, mp_max, sigma2, chi2_mult, res_norm_gate, whitened_route(us->compress_mode, us->graph_mode, F * mp_max, k), probe != 0));
   g.n_acc = d_flag + aw.word;
   g.n_acc_next = d_flag + (3 - aw.word);
+  *gate = g;  // (whole, or off: a failing exit above hands nothing on)
   return PLV_OK;
 }
 }  // namespace plv
@@ -822,6 +823,8 @@ namespace {
 struct UpdateLaunch {
   plv_ctx *ctx;
   plv_ctx_update_state *us;
+  UpdateRiders &riders;
+  EkfRiders ekf;  // riders.ekf + the skip word this update chose (gate())
   const double sigma2, chi2_mult, res_norm_gate;
   UpdateShape shape;
   UpdatePlan plan;
@@ -829,8 +832,7 @@ struct UpdateLaunch {
   double *wHf = nullptr, *wHx = nullptr, *wres = nullptr;  // the batch this update consumes
   UpdateBuffers buf;
   bool aux_open = false;  // side-stream work that reads the covariance and that the main stream has not joined yet
-
-  ~UpdateLaunch() { ctx->skip_word = nullptr; }  // the word is only meaningful for the kernels of this update
+  plv::GateStage batch_gate{};  // the gate that ran inside the batch's Jacobian launch (on), taken over from the batch
 
   double *P() const { return ctx->d_P.as<double>(); }
   int *cols() const { return us->bcols_of(shape.fdim).as<int>(); }
@@ -839,6 +841,8 @@ struct UpdateLaunch {
   int take_batch() {
     UpdateShape &s = shape;
     s.F = us->bF, s.fdim = us->bfdim, s.k = us->bk, s.ld = us->bld;
+    batch_gate = us->b_gate;
+    us->b_gate.on = 0;  // (one update starts behind it)
     n = ctx->cov_n;
     const size_t nHf = (size_t)s.F * s.fdim * s.ld, nHx = (size_t)s.F * s.k * s.ld, nr = (size_t)s.F * s.ld;
     if (us->b_single_use) {
@@ -865,7 +869,7 @@ struct UpdateLaunch {
     s.gathers_valid = s.projected && us->b_gather_token != 0 && us->b_gather_token == ctx->gather_stamp;
     // (the prefetched prior factor stands exactly as long as the gathers that rode on the same launch do)
     s.prefetched = ctx->prior_pending && ctx->prior_k == s.k && s.gathers_valid;
-    s.probing = ctx->probe;
+    s.probing = riders.probe;
     s.force_factor_form = plv::knob(plv::PLV_KNOB_FORCE_FACTOR_FORM), s.tsqr_tree = plv::knob(plv::PLV_KNOB_TSQR_TREE);
     s.ekf_fast_rows = ekf_fast_rows();
     plan = plan_update(s);
@@ -920,22 +924,22 @@ struct UpdateLaunch {
     a.cols = cols();
     TRY(fill_gate(ctx, us, a, buf, s.F, s.fdim, s.mp_max, sigma2, chi2_mult, res_norm_gate, plan.stack_accepted_only, plan.probing));
     a.n_acc = d_flag + 1;  // second word of the status block
-    // read by every kernel enqueued from here on (cleared when the launch ends)
-    ctx->skip_word = plan.skip_word ? d_flag + 1 : nullptr;
+    // handed to every EKF launcher called from here on
+    ekf.skip_word = plan.skip_word ? d_flag + 1 : nullptr;
     if (plan.probing) {
-      a.probe_src = (const unsigned char *)ctx->probe_src;
-      a.probe_dst = (unsigned char *)ctx->probe_dst;
-      a.probe_stride_a = ctx->probe_stride_a, a.probe_off_b = ctx->probe_off_b, a.probe_stride_b = ctx->probe_stride_b;
+      a.probe_src = (const unsigned char *)riders.probe_src;
+      a.probe_dst = (unsigned char *)riders.probe_dst;
+      a.probe_stride_a = riders.probe_stride_a, a.probe_off_b = riders.probe_off_b, a.probe_stride_b = riders.probe_stride_b;
     }
-    const plv::GateStage &g = ctx->gate_stage;
-    const bool gated = ctx->gate_stage_taken && s.projected && g.stack == a.stack && g.lds == a.lds && g.accepted == a.accepted &&
+    const plv::GateStage &g = batch_gate;
+    const bool gated = g.on && s.projected && g.stack == a.stack && g.lds == a.lds && g.accepted == a.accepted &&
                        g.stack_accepted_only == a.stack_accepted_only;
-    if (ctx->gate_stage_taken && !gated) {  // (the launch that took the gate did not write the projected blocks a separate gate would read)
+    if (g.on && !gated) {  // (the launch that took the gate did not write the projected blocks a separate gate would read)
       set_last_error("plv_msckf_update_resident: the batch was gated inside its Jacobian launch for other buffers than this update's");
       return PLV_E_BADARG;
     }
     if (gated) {
-      ctx->skip_word = ctx->skip_word ? g.n_acc : nullptr;
+      ekf.skip_word = ekf.skip_word ? g.n_acc : nullptr;
       plv_ctx_update_state::AccWords &aw = us->acc_of(s.fdim);
       us->acc_word_used = aw.word;
       aw.z_ptr = buf.dev, aw.z_n = n, aw.z_word = 3 - aw.word;  // (workgroup 0 of the gated launch zeroed the other counter)
@@ -950,7 +954,7 @@ struct UpdateLaunch {
   int probe(bool *done) {
     const UpdateShape &s = shape;
     *done = true;
-    if (ctx->probe_hook) ctx->probe_hook(ctx->probe_hook_arg);
+    if (riders.probe_hook) riders.probe_hook(riders.probe_hook_arg);
     TRY(stream_wait(ctx));
     const unsigned char *hacc = buf.lay.accepted((const void *)buf.pin);
     const int *hrows = buf.lay.acc_rows((const void *)buf.pin);
@@ -961,7 +965,7 @@ struct UpdateLaunch {
     const TailPlan t = plan_tail(plan, any != 0, m_acc);
     if (t.kind == TAIL_ENDED_AT_GATE) {
       memset(buf.pin, 0, buf.lay.head_bytes());  // dx = 0, status = updated-with-nothing (as the skipped chain reports it)
-      ctx->probe_done = true;
+      riders.ended_at_gate = true;
       return join_prior();
     }
     if (t.kind == TAIL_DIRECT) {
@@ -974,8 +978,8 @@ struct UpdateLaunch {
       TRY(launch_stack_compact(ctx, stack(), s.Mtot(), s.nc(), buf.d_acc_rows(), s.F, s.mp_max, ctx->d_stackc.as<double>(), m_acc, true));
       TRY(join_prior());  // (a prior factor started ahead of time is not used, but it reads the covariance this update rewrites)
       const double *Hc = ctx->d_stackc.as<double>();
-      TRY(launch_ekf_fast(ctx, P(), n, n, Hc, m_acc, s.k, m_acc, cols(), Hc + (size_t)s.k * m_acc, nullptr, buf.d_dx(), buf.d_flag(), s.gathers_valid, buf.dev,
-                          buf.pin, buf.lay.mirror_bytes()));
+      TRY(mirrored(launch_ekf_fast(ctx, ekf, P(), n, n, Hc, m_acc, s.k, m_acc, cols(), Hc + (size_t)s.k * m_acc, nullptr, buf.d_dx(), buf.d_flag(), s.gathers_valid,
+                                   buf.dev, buf.pin, buf.lay.mirror_bytes())));
       us->last_route = ROUTE_DIRECT;
       return PLV_OK;
     }
@@ -987,9 +991,9 @@ struct UpdateLaunch {
   // REF: measurement_compress_inplace + EKFUpdate as one whitened step: no triangular factor of the measurements is formed
   int tail_whitened(const ChainPlan &c) {
     const UpdateShape &s = shape;
-    TRY(launch_gram_information(ctx, stack(), s.Mtot(), s.nc(), buf.d_acc_rows(), s.F, s.mp_max));
+    TRY(launch_gram_information(ctx, ekf, stack(), s.Mtot(), s.nc(), buf.d_acc_rows(), s.F, s.mp_max));
     TRY(join_prior());
-    TRY(launch_ekf_whitened(ctx, P(), n, n, s.k, cols(), buf.d_dx(), buf.d_flag(), buf.dev, buf.pin, buf.lay.mirror_bytes()));
+    TRY(mirrored(launch_ekf_whitened(ctx, ekf, P(), n, n, s.k, cols(), buf.d_dx(), buf.d_flag(), buf.dev, buf.pin, buf.lay.mirror_bytes())));
     us->last_route = c.route;
     us->redo_w = plv_ctx_update_state::RedoW{true, s.Mtot(), s.k, n, s.F, s.mp_max, s.fdim, plan.tmp_elems, buf.lay.bytes(), buf.d_dx(), buf.d_flag(), buf.d_acc_rows()};
     return PLV_OK;
@@ -1015,11 +1019,17 @@ struct UpdateLaunch {
     return PLV_OK;
   }
 
+  // rc of a chain that ends in ekf_commit_kernel with the result block's mirror: the kernel took the second mirror and the applied word too
+  int mirrored(int rc) {
+    if (rc == PLV_OK) riders.mirror2_taken = ekf.mirror2_dst != nullptr, riders.applied_used = ekf.applied_word != nullptr;
+    return rc;
+  }
+
   // EKFUpdate on c.r rows [H | res] (col-major, ldh)
   int ekf_step(const ChainPlan &c, const double *dH, const double *dr, int ldh) {
     if (c.ekf == EKF_FAST)  // (its last kernel mirrors the result block into pinned memory: no copy command after the chain)
-      return launch_ekf_fast(ctx, P(), n, n, dH, c.r, shape.k, ldh, cols(), dr, nullptr, buf.d_dx(), buf.d_flag(), true, buf.dev, buf.pin, buf.lay.mirror_bytes());
-    TRY(launch_ekf(ctx, P(), n, n, dH, c.r, shape.k, ldh, cols(), dr, nullptr, buf.d_dx(), buf.d_flag(), true));
+      return mirrored(launch_ekf_fast(ctx, ekf, P(), n, n, dH, c.r, shape.k, ldh, cols(), dr, nullptr, buf.d_dx(), buf.d_flag(), true, buf.dev, buf.pin, buf.lay.mirror_bytes()));
+    TRY(launch_ekf(ctx, ekf, P(), n, n, dH, c.r, shape.k, ldh, cols(), dr, nullptr, buf.d_dx(), buf.d_flag(), true));
     return d2h(ctx, buf.pin, buf.dev, buf.lay.bytes());
   }
 
@@ -1053,8 +1063,8 @@ struct UpdateLaunch {
     }
     const UpdateShape &s = shape;
     // (the skip word is chosen by the plan from Mtot, k and the status block: all functions of the key's own fields and of `result`)
-    plv_ctx_update_state::GraphKey key{ctx->d_P.p, wHf, us->brows.p, us->bcols_of(s.fdim).p, buf.dev, buf.pin, ctx->mirror2_src, ctx->mirror2_dst,
-                                       (const void *)(buf.d_flag() + 1), ctx->mirror2_bytes, s.F, s.fdim + 16 * (s.projected ? 1 : 0) + 32 * (s.gathers_valid ? 1 : 0), s.k, s.ld, n, s.mp_max,
+    plv_ctx_update_state::GraphKey key{ctx->d_P.p, wHf, us->brows.p, us->bcols_of(s.fdim).p, buf.dev, buf.pin, ekf.mirror2_src, ekf.mirror2_dst,
+                                       (const void *)(buf.d_flag() + 1), ekf.mirror2_bytes, s.F, s.fdim + 16 * (s.projected ? 1 : 0) + 32 * (s.gathers_valid ? 1 : 0), s.k, s.ld, n, s.mp_max,
                                        sigma2, chi2_mult, res_norm_gate, plv::alloc_epoch().load()};
     if (us->gexec && key == us->gkey) {
       PLV_HIP_CHECK(hipGraphLaunch(us->gexec, ctx->stream));
@@ -1102,11 +1112,12 @@ struct UpdateLaunch {
 // Cholesky compression ended 5.6 cm from this one; and the updates the factor form hands over on the bench drive — the car at rest,
 // a prior block of rank 50 of 110, lambda above 1e4 — all have 5 .. 70 pivots the Gram + Cholesky compression cannot tell from zero,
 // so trying that compression first would only add its 0.1 ms to the 2 ms of this one).  Its verdict is the update's.
-int redo_by_householder(plv_ctx *ctx, plv_ctx_update_state *us, int fdim, void *hpin, const int *hrows) {
+int redo_by_householder(plv_ctx *ctx, plv_ctx_update_state *us, int fdim, void *hpin, const int *hrows, const CovSave &save) {
   const plv_ctx_update_state::RedoW rd = us->redo_w;
   us->redo_w.armed = false;
   const int nc = rd.k + 1;
-  ctx->skip_word = nullptr;
+  EkfRiders ekf;  // (the update's own riders went with its launch; a speculative batch's commit saves the covariance here too)
+  ekf.save = save;
   double *R;
   int ldr;
   // (the accepted rows gathered into a dense matrix first: the stack is F x mp_max slots, most of them empty, and the tree of
@@ -1117,7 +1128,7 @@ int redo_by_householder(plv_ctx *ctx, plv_ctx_update_state *us, int fdim, void *
   TRY(ctx->d_stackc.reserve((size_t)m_c * nc * 8));
   TRY(launch_stack_compact(ctx, ctx->stack_of(fdim).as<double>(), rd.Mtot, nc, rd.d_acc_rows, rd.F, rd.mp_max, ctx->d_stackc.as<double>(), m_c));
   TRY(launch_tsqr(ctx, ctx->d_stackc.as<double>(), m_c, m_c, nc, ctx->d_stack2.as<double>(), rd.tmp_elems, &R, &ldr));
-  TRY(launch_ekf_fast(ctx, ctx->d_P.as<double>(), rd.n, rd.n, R, rd.k, rd.k, ldr, us->bcols_of(fdim).as<int>(), R + (size_t)rd.k * ldr, nullptr, rd.d_dx, rd.d_flag,
+  TRY(launch_ekf_fast(ctx, ekf, ctx->d_P.as<double>(), rd.n, rd.n, R, rd.k, rd.k, ldr, us->bcols_of(fdim).as<int>(), R + (size_t)rd.k * ldr, nullptr, rd.d_dx, rd.d_flag,
                       true, us->result_of(rd.fdim).p, hpin, ResultBlock(rd.n, rd.F).head_mirror_bytes()));
   TRY(stream_wait(ctx));
   us->last_route = ROUTE_WHITENED_REDONE;
@@ -1128,29 +1139,87 @@ int redo_by_householder(plv_ctx *ctx, plv_ctx_update_state *us, int fdim, void *
 
 }  // namespace
 
-extern "C" {
-
-int plv_msckf_update_resident_launch(plv_ctx *ctx, double sigma2, double chi2_mult, double res_norm_gate) {
+namespace plv {
+int update_resident_launch(plv_ctx *ctx, double sigma2, double chi2_mult, double res_norm_gate, UpdateRiders &riders) {
   REQUIRE_CTX(ctx);
   auto *us = ustate(ctx);
   us->pending_F = 0;
-  ctx->probe_done = false;  // (a launch that failed after setting it, or a wait that was skipped, must not short-cut this update's wait)
+  us->pending_at_gate = false;
   if (us->bF < 1 || ctx->cov_n < 1) {
     set_last_error("plv_msckf_update_resident: no staged batch / covariance");
     return PLV_E_BADARG;
   }
-  UpdateLaunch u{ctx, us, sigma2, chi2_mult, res_norm_gate};
+  UpdateLaunch u{ctx, us, riders, riders.ekf, sigma2, chi2_mult, res_norm_gate};
   TRY(u.take_batch());
   TRY(u.reserve());
   TRY(u.run_or_replay());
-  ctx->gate_stage.on = 0, ctx->gate_stage_taken = false;
   ++ctx->gather_stamp;  // the update rewrites the covariance
   us->pending_fdim = u.shape.fdim;
   us->pending_F = u.shape.F;  // stream-ordered: the result block lands in pinned memory; plv_msckf_update_resident_wait reads it
+  us->pending_at_gate = riders.ended_at_gate;
   if (!us->done_ev) PLV_HIP_CHECK(hipEventCreateWithFlags(&us->done_ev, hipEventDisableTiming));
   PLV_HIP_CHECK(hipEventRecord(us->done_ev, ctx->stream));
   us->done_stamp = ctx->gather_stamp;
   return PLV_OK;
+}
+
+// save: handed to the commit of a re-run (redo_by_householder)
+int update_resident_wait(plv_ctx *ctx, uint8_t *accepted, int *n_accepted_rows, double *dx, const CovSave &save) {
+  REQUIRE_CTX(ctx);
+  auto *us = ustate(ctx);
+  const int F = us->pending_F, n = ctx->cov_n, wfdim = us->pending_fdim;
+  plv::PinBuf &hpin = ctx->res_pin(us->pending_fdim);
+  if (F < 1 || !dx) {
+    set_last_error("plv_msckf_update_resident_wait: nothing was launched");
+    return PLV_E_BADARG;
+  }
+  us->pending_F = 0;
+  if (us->pending_at_gate)
+    us->pending_at_gate = false;  // (ended at the gate: already synchronised, the result block in h_pin is complete)
+  else if (ctx->prof.on || !us->done_ev)
+    TRY(stream_wait(ctx));
+  else
+  {
+    // (not the whole stream: the caller may have enqueued more behind the update)
+    PLV_HIP_CHECK(plv::event_sync(us->done_ev));
+    if (us->done_stamp > ctx->cov_host_synced) ctx->cov_host_synced = us->done_stamp;
+  }
+  const ResultBlock lay(n, F);
+  const void *hb = hpin.p;
+  const int *status = lay.status(hb), *hrows = lay.acc_rows(hb);
+  us->last_ambiguous = 0;
+  // (STATUS_SPEC_OVER_CAP: not a rejection — a speculative batch the selection loop's cap would have cut, ekf_commit_kernel)
+  if (us->redo_w.armed && us->last_route == ROUTE_WHITENED && status[0] != 0 && !(status[0] & STATUS_SPEC_OVER_CAP) && status[us->acc_word_used] > 0)
+    TRY(redo_by_householder(ctx, us, wfdim, hpin.p, hrows, save));
+  us->redo_w.armed = false;
+  ++plv::counters().route[us->last_route & 7];
+  const int flag = status[0];
+  const unsigned char *hacc = lay.accepted(hb);
+  int nrows = 0, overflow = 0;
+  for (int f = 0; f < F; ++f) {
+    if (accepted) accepted[f] = hacc[f];
+    if (hrows[f] < 0) ++overflow;  // (gate_core.hpp: an entry with more rows than the gate inside the Jacobian launch holds)
+    else nrows += hrows[f];
+  }
+  if (n_accepted_rows) *n_accepted_rows = nrows;
+  if (overflow) {
+    set_last_error("update: %d batch entries had more projected rows than the gate inside the Jacobian launch holds (%d): they were left out", overflow, GATE_MMAX);
+    return PLV_E_CAPACITY;
+  }
+  if (flag != 0) {
+    set_last_error("EKFUpdate rejected: %s", ekf_rejection_text(flag));
+    return PLV_E_NOT_PSD;
+  }
+  memcpy(dx, lay.dx(hb), (size_t)n * 8);
+  return PLV_OK;
+}
+}  // namespace plv
+
+extern "C" {
+
+int plv_msckf_update_resident_launch(plv_ctx *ctx, double sigma2, double chi2_mult, double res_norm_gate) {
+  plv::UpdateRiders none;
+  return plv::update_resident_launch(ctx, sigma2, chi2_mult, res_norm_gate, none);
 }
 
 int plv_update_compression_mode(plv_ctx *ctx, int mode, int *last_route, int *last_ambiguous) {
@@ -1182,53 +1251,7 @@ int plv_update_graph_mode(plv_ctx *ctx, int on, int *captures, int *replays) {
 }
 
 int plv_msckf_update_resident_wait(plv_ctx *ctx, uint8_t *accepted, int *n_accepted_rows, double *dx) {
-  REQUIRE_CTX(ctx);
-  auto *us = ustate(ctx);
-  const int F = us->pending_F, n = ctx->cov_n, wfdim = us->pending_fdim;
-  plv::PinBuf &hpin = ctx->res_pin(us->pending_fdim);
-  if (F < 1 || !dx) {
-    set_last_error("plv_msckf_update_resident_wait: nothing was launched");
-    return PLV_E_BADARG;
-  }
-  us->pending_F = 0;
-  if (ctx->probe_done)
-    ctx->probe_done = false;  // (ended at the gate: already synchronised, the result block in h_pin is complete)
-  else if (ctx->prof.on || !us->done_ev)
-    TRY(stream_wait(ctx));
-  else
-  {
-    // (not the whole stream: the caller may have enqueued more behind the update)
-    PLV_HIP_CHECK(plv::event_sync(us->done_ev));
-    if (us->done_stamp > ctx->cov_host_synced) ctx->cov_host_synced = us->done_stamp;
-  }
-  const ResultBlock lay(n, F);
-  const void *hb = hpin.p;
-  const int *status = lay.status(hb), *hrows = lay.acc_rows(hb);
-  us->last_ambiguous = 0;
-  // (STATUS_SPEC_OVER_CAP: not a rejection — a speculative batch the selection loop's cap would have cut, ekf_commit_kernel)
-  if (us->redo_w.armed && us->last_route == ROUTE_WHITENED && status[0] != 0 && !(status[0] & STATUS_SPEC_OVER_CAP) && status[us->acc_word_used] > 0)
-    TRY(redo_by_householder(ctx, us, wfdim, hpin.p, hrows));
-  us->redo_w.armed = false;
-  ++plv::counters().route[us->last_route & 7];
-  const int flag = status[0];
-  const unsigned char *hacc = lay.accepted(hb);
-  int nrows = 0, overflow = 0;
-  for (int f = 0; f < F; ++f) {
-    if (accepted) accepted[f] = hacc[f];
-    if (hrows[f] < 0) ++overflow;  // (gate_core.hpp: an entry with more rows than the gate inside the Jacobian launch holds)
-    else nrows += hrows[f];
-  }
-  if (n_accepted_rows) *n_accepted_rows = nrows;
-  if (overflow) {
-    set_last_error("update: %d batch entries had more projected rows than the gate inside the Jacobian launch holds (%d): they were left out", overflow, GATE_MMAX);
-    return PLV_E_CAPACITY;
-  }
-  if (flag != 0) {
-    set_last_error("EKFUpdate rejected: %s", ekf_rejection_text(flag));
-    return PLV_E_NOT_PSD;
-  }
-  memcpy(dx, lay.dx(hb), (size_t)n * 8);
-  return PLV_OK;
+  return plv::update_resident_wait(ctx, accepted, n_accepted_rows, dx, plv::CovSave{});
 }
 
 int plv_msckf_update_resident(plv_ctx *ctx, double sigma2, double chi2_mult, double res_norm_gate, uint8_t *accepted,

@@ -4,7 +4,6 @@
 #include <hip/hip_runtime.h>
 #include <sys/resource.h>
 
-#include "gate_stage.hpp"
 #include <cstdint>
 #include <cstdio>
 #include <execinfo.h>
@@ -438,7 +437,6 @@ struct ProfScope {
   ~ProfScope() { p.end(s); }
 };
 
-struct CpiStage;  // camera_tracks.hpp
 }  // namespace plv
 
 struct plv_ctx {
@@ -515,52 +513,6 @@ struct plv_ctx {
     std::vector<unsigned char> anc_has_old;
     std::vector<double> anc_old;
   } chain;
-  int *applied_word = nullptr;  // set by the caller of a launch that may end in ekf_commit_kernel: the kernel stores "state changed" there
-  bool applied_used = false;
-  // set by the caller of a speculative point update (plv_points_update_submit) around its launch: ekf_commit_kernel's cap test
-  const int *cap_words = nullptr;
-  int cap = 0;
-  // set around the launch of a speculative point update and its re-run (RedoW): ekf_commit_kernel saves the covariance it overwrites in
-  // cov_save (n x n) and stores cov_save_seq in cov_save_word — what plv_points_spec_undo restores when nobody uses the update
-  double *cov_save = nullptr;
-  unsigned *cov_save_word = nullptr;
-  unsigned cov_save_seq = 0;
-  // Device word holding the number of features the gate accepted in the update being enqueued (null outside
-  // plv_msckf_update_resident_launch): the compression and EKF kernels return at once when it is zero — an update in which the gate
-  // took nothing (most line updates) costs their launches, not their pivot chains; ekf_commit_kernel then reports dx = 0.
-  const int *skip_word = nullptr;
-  // a second block the update's last kernel copies to pinned host memory next to its result block (the triangulation results of the
-  // one-submission updates): set by the caller before plv_msckf_update_resident_launch, cleared (taken = true) when the chain ended in
-  // the kernel that does it — else the caller enqueues a copy command as before
-  const void *mirror2_src = nullptr;
-  void *mirror2_dst = nullptr;
-  size_t mirror2_bytes = 0;
-  bool mirror2_taken = false;
-  // gate probe of the one-submission line update: plv_msckf_update_resident_launch waits for the gate, reads its verdicts from
-  // pinned memory and enqueues compression + EKF only when something was accepted (probe_* describe the second block the gate's
-  // workgroups copy, update_kernels.hpp; probe_hook runs right before that wait).  probe_done: the update ended at the gate.
-  bool probe = false, probe_done = false;
-  const void *probe_src = nullptr;
-  void *probe_dst = nullptr;
-  int probe_stride_a = 0, probe_off_b = 0, probe_stride_b = 0;
-  void (*probe_hook)(void *) = nullptr;
-  void *probe_hook_arg = nullptr;
-
-  // the gate as the tail of the next projected Jacobian launch (gate_core.hpp): filled by plv_update_gate_prepare for the update the
-  // one-submission entry points are about to build; the launcher takes it (gate_stage_taken) when the batch fits, and
-  // plv_msckf_update_resident_launch then starts behind the gate
-  plv::GateStage gate_stage{};
-  bool gate_stage_taken = false;
-  int gate_rows_hint = 0;  // most rows any entry of the batch about to be built can have (0: unknown, the batch's row capacity counts)
-
-  // host work of the caller that becomes possible while a point update runs on the device (plv_points_update_fused polls it inside
-  // its wait until it returns nonzero = done / nothing to do)
-  int (*wait_poll)(void *) = nullptr;
-  void *wait_poll_arg = nullptr;
-
-  // residual poses of the batch about to be staged come from the CPI table on the device (set around the one-submission calls by
-  // plv_camera_update_points / _lines; null: the tracks' own res_R / res_p, if any)
-  const plv::CpiStage *cpi_stage = nullptr;
 
   // ---- front-end (frontend_api.hip owns the object)
   void *fe_state = nullptr;

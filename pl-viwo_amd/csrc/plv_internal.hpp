@@ -8,6 +8,9 @@
 #include "../../include/plviwo.h"
 
 struct plv_ctx_update_state;  // update_state.hpp
+namespace plv {  // update_state.hpp, update_kernels.hpp, gate_stage.hpp, camera_tracks.hpp
+struct UpdateRiders; struct CovSave; struct GateStage; struct CpiStage;
+}
 
 // Speculative submission of the point update (round 6): host arrays per candidate + where the flow leaves its results on the device
 // (SpecSelectArgs, jacobian_kernels.hpp).  The candidates' observation ranges end with a slot for the frame's own observation when
@@ -35,8 +38,13 @@ namespace plv {
 int stream_wait(plv_ctx *ctx);
 // the ctx's update-side state (update_state.hpp); null for a ctx plv_ctx_create did not make
 plv_ctx_update_state *plv_update_state(plv_ctx *ctx);
-// fills plv_ctx::gate_stage so that the projected Jacobian launch ends with the gate of every entry (the one-submission updates)
-int plv_update_gate_prepare(plv_ctx *ctx, int F, int fdim, int k, int ld, double sigma2, double chi2_mult, double res_norm_gate, int probe);
+// fills *gate so that the projected Jacobian launch ends with the gate of every entry (the one-submission updates; off: the update
+// launch runs its own).  rows_hint: most rows any entry of the batch can have (0: unknown, the batch's row capacity counts)
+int plv_update_gate_prepare(plv_ctx *ctx, int F, int fdim, int k, int ld, double sigma2, double chi2_mult, double res_norm_gate, int probe,
+                            int rows_hint, GateStage *gate);
+// plv_msckf_update_resident_launch / _wait with what internal callers hand them (the public functions: empty riders, no save)
+int update_resident_launch(plv_ctx *ctx, double sigma2, double chi2_mult, double res_norm_gate, UpdateRiders &riders);
+int update_resident_wait(plv_ctx *ctx, uint8_t *accepted, int *n_accepted_rows, double *dx, const CovSave &save);
 // the prior factor of the update on the side stream, next to triangulation, Jacobians and gate (phase 0 / 1)
 int plv_prior_prefetch(plv_ctx *ctx, int phase, const int *d_cols, int k, int F, int mp_max);
 
@@ -123,32 +131,28 @@ void plv_camera_lines_job_abort2(plv_ctx *ctx, int keep_pool);
 void plv_camera_lines_job_abort(plv_ctx *ctx);
 
 // ---- jacobian_api.hip: the one-call camera updates (tracker_api.hip, line_api.hip)
-// plv_points_update_fused = plv_points_update_submit (everything enqueued: upload, [spec_select,] triangulation + Jacobians + null space +
+// The point update = plv_points_update_submit (everything enqueued: upload, [spec_select,] triangulation + Jacobians + null space +
 // gate, compression, EKFUpdate) + plv_points_update_collect (host work inside the wait, the wait, results).  With `spec` the batch is
 // the speculative one; collect then also returns the device's membership (member [F], may be null) and *spec_over (1: the pool exceeded
 // max_sel and every candidate was left empty — nothing was updated, the caller runs the update the long way).
+// rows_hint: as plv_update_gate_prepare takes it.  cpi: the batch's residual poses come from the CPI table on the device (null: the tracks'
+// own, if any).  wait_poll: host work that becomes possible while the update runs, polled inside the wait until it returns nonzero.
 // plv_cpi_poses with the poses left on the device (*d_R [n_q][9], *d_p [n_q][3]: valid until the ctx's next point update or
 // triangulation); ok [n_q] comes back
 int plv_cpi_poses_resident(plv_ctx *ctx, const plv_state_view *st, const plv_cpi_table *cpi, int n_q, const double *t_q, uint8_t *ok,
                            const double **d_R, const double **d_p);
 int plv_points_update_submit(plv_ctx *ctx, const plv_state_view *st, const plv_tracks *all, const plv_tri_options *tri,
                              const uint8_t *flags, int max_sel, int k, const int *col_to_state, int ld, double sigma2,
-                             double chi2_mult, double res_norm_gate, const plv_points_spec *spec);
+                             double chi2_mult, double res_norm_gate, const plv_points_spec *spec, int rows_hint, const CpiStage *cpi);
 int plv_points_update_collect(plv_ctx *ctx, double *p_out, uint8_t *ok_out, double *err_out, uint8_t *accepted, int *n_rows, double *dx,
-                              void (*before_wait)(void *), void *before_wait_arg, uint8_t *member, int *spec_count, int *spec_over);
+                              void (*before_wait)(void *), void *before_wait_arg, int (*wait_poll)(void *), void *wait_poll_arg, uint8_t *member,
+                              int *spec_count, int *spec_over);
 // a collected speculative batch whose update nobody uses: the covariance as it found it (a chained line launch aborted first)
 int plv_points_spec_undo(plv_ctx *ctx);
-int plv_points_update_fused(plv_ctx *ctx, const plv_state_view *st, const plv_tracks *all, const plv_tri_options *tri,
-                            const uint8_t *flags, int max_sel, int k, const int *col_to_state, int ld, double sigma2,
-                            double chi2_mult, double res_norm_gate, double *p_out, uint8_t *ok_out, double *err_out,
-                            uint8_t *accepted, int *n_rows, double *dx, void (*before_wait)(void *), void *before_wait_arg);
 // the line update in two halves: `submit` enqueues up to the gate, `finish` waits for it, updates and collects
-int plv_lines_update_fused(plv_ctx *ctx, const plv_state_view *st, const plv_state_view *st_tri, const plv_line_tracks *all,
-                           const uint8_t *flags, int max_sel, int k, const int *col_to_state, int ld, double sigma2,
-                           double chi2_mult, double *lines_out, uint8_t *ok_out, uint8_t *accepted, int *n_rows, double *dx,
-                           void (*before_wait)(void *), void *before_wait_arg);
 int plv_lines_update_fused_submit(plv_ctx *ctx, const plv_state_view *st, const plv_state_view *st_tri, const plv_line_tracks *all,
-                                  const uint8_t *flags, int max_sel, int k, const int *col_to_state, int ld, double sigma2, double chi2_mult);
+                                  const uint8_t *flags, int max_sel, int k, const int *col_to_state, int ld, double sigma2, double chi2_mult,
+                                  int rows_hint, const CpiStage *cpi);
 int plv_lines_update_fused_finish(plv_ctx *ctx, double sigma2, double chi2_mult, double *lines_out, uint8_t *ok_out, uint8_t *accepted,
                                   int *n_rows, double *dx, void (*before_wait)(void *), void *before_wait_arg);
 

@@ -6,7 +6,7 @@
 // each of them.  A pass therefore stages once what no landmark changes (clone times and first estimates, every entry's observations,
 // poses of the CPI table, column maps) and per landmark only what the previous correction moved (clone poses, the landmark itself);
 // landmark_system_kernel writes the rows where the gate and the EKF step read them, the gate's verdict stays on the device (the EKF
-// kernels return at once behind a rejection: plv_ctx::skip_word), and one small block — dx, status, verdict — comes back.
+// kernels return at once behind a rejection: EkfRiders::skip_word), and one small block — dx, status, verdict — comes back.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -26,7 +26,7 @@ const int Q95_ENTRIES = 1024;  // plv_ctx_update_state::q95 (plv_ctx_create)
 const int GATE_MAX_ROWS = 63;  // chi2_gate_kernel's S tile
 const double NO_TIME = -1e300;  // observation time no clone window holds
 
-// cov_init_invertible_kernel reports 1 = rejected; the EKF kernels behind it skip on 0 (plv_ctx::skip_word)
+// cov_init_invertible_kernel reports 1 = rejected; the EKF kernels behind it skip on 0 (EkfRiders::skip_word)
 __global__ void init_skip_word_kernel(const int *__restrict__ rejected, int *__restrict__ skip) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *skip = *rejected ? 0 : 1;
 }
@@ -435,10 +435,7 @@ int plv_camera_update_slam(plv_ctx *ctx, const plv_state_view *st, const plv_upd
     a.q95 = W.us->q95.as<double>(), a.q95_n = Q95_ENTRIES, a.min_rows = 2;
     a.accepted = W.d_acc, a.acc_rows = W.d_acc_rows, a.n_acc = W.d_flag + 1;
     TRY(launch_chi2(ctx, 1, a, r));
-    ctx->skip_word = W.d_flag + 1;
-    const int rc_e = launch_ekf_fast(ctx, d_P, n, n, W.d_block, r, kx, W.ld, d_cols, a.res, nullptr, W.d_dx, W.d_flag, /*gathered*/ true);
-    ctx->skip_word = nullptr;
-    TRY(rc_e);
+    TRY(launch_ekf_fast(ctx, EkfRiders{W.d_flag + 1}, d_P, n, n, W.d_block, r, kx, W.ld, d_cols, a.res, nullptr, W.d_dx, W.d_flag, /*gathered*/ true));
     PLV_HIP_CHECK(plv::memcpy_async(hres, W.us->slam.res.p, rb, hipMemcpyDeviceToHost, ctx->stream));
     TRY(plv::stream_wait(ctx));
     const int flag = *head.status(hres);
@@ -538,10 +535,7 @@ int plv_camera_init_slam(plv_ctx *ctx, const plv_state_view *st, const plv_updat
     ++counters().launches;
     hipLaunchKernelGGL(init_skip_word_kernel, dim3(1), dim3(64), 0, ctx->stream, W.d_initflag, W.d_skip);
     PLV_HIP_CHECK(hipGetLastError());
-    ctx->skip_word = W.d_skip;
-    const int rc_e = launch_ekf_fast(ctx, ctx->d_P2.as<double>(), n2, n2, dHx + 3, mup, k, W.ld, d_cols, dres + 3, nullptr, W.d_dx, W.d_flag);
-    ctx->skip_word = nullptr;
-    TRY(rc_e);
+    TRY(launch_ekf_fast(ctx, EkfRiders{W.d_skip}, ctx->d_P2.as<double>(), n2, n2, dHx + 3, mup, k, W.ld, d_cols, dres + 3, nullptr, W.d_dx, W.d_flag));
     const ResultBlock head(n_cap, 0);
     const size_t rb = head.head_bytes();
     PLV_HIP_CHECK(plv::memcpy_async(hres, W.us->slam.res.p, rb, hipMemcpyDeviceToHost, ctx->stream));

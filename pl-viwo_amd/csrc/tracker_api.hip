@@ -334,9 +334,8 @@ static void spec_submit(plv_ctx *ctx, Tracker *T, double t_now, int n_flow, cons
   int n_dev = 0;
   if (plv::plv_front_match_device(ctx, &sp.d_flow_p1, &sp.d_flow_n1, &sp.d_flow_mask, &n_dev) != PLV_OK || n_dev != n_flow) return;
   (void)flow_ids;
-  ctx->gate_rows_hint = 2 * most_valid;
   if (plv_points_update_submit(ctx, st, &all, &opt->tri, S.flags.data(), opt->max_msckf, k, S.cols.data(), 2 * opt->max_obs,
-                               st->sigma_pix * st->sigma_pix, opt->chi2_mult, 3.0, &sp) != PLV_OK) {
+                               st->sigma_pix * st->sigma_pix, opt->chi2_mult, 3.0, &sp, 2 * most_valid, nullptr) != PLV_OK) {
     // (nothing usable was enqueued: whatever the failed call left on the stream works on empty or stale candidates and commits nothing
     //  it was not told to; the long way follows)
     plv_update_state(ctx)->point_job.pending = false;
@@ -497,7 +496,7 @@ static void start_detection_ahead(void *arg) {
   }
 }
 // LineHelper::get_line_features' pool (times only: nothing the point update changes) while the device is busy with that update;
-// polled inside the update's wait (plv_ctx::wait_poll) until the line worker has finished the frame's feed
+// polled inside the update's wait (plv_points_update_collect's wait_poll) until the line worker has finished the frame's feed
 static int poll_line_pool(void *arg) {
   plv_ctx *ctx = (plv_ctx *)arg;
   Tracker *T = trk(ctx);
@@ -671,6 +670,7 @@ struct PointsUpdate {
   const plv_update_options *opt;
   double *dx;
   plv_update_result *res;
+  int (*wait_poll)(void *);  // (arg: the ctx) host work polled inside the update's wait (plv_points_update_collect); null: none
   const double dt = st->cam_dt, t_oldest = st->clone_time[0], t_oldest2 = st->clone_time[1];  // no keyframes on this path
   BoundingMemo start_of{*st};
   std::vector<Cand> pool;
@@ -793,7 +793,7 @@ struct PointsUpdate {
     {
       plv::RoctxRange rx_upd("[Time-Cam] MSCKF update");
       plv::HostPhase ph_dev("update_points: device submission + wait");
-      rc_s = plv_points_update_collect(ctx, cp.data(), cok.data(), ce.data(), cacc.data(), &nrows, dx, start_detection_ahead, ctx, cmem.data(), &count, &over);
+      rc_s = plv_points_update_collect(ctx, cp.data(), cok.data(), ce.data(), cacc.data(), &nrows, dx, start_detection_ahead, ctx, wait_poll, ctx, cmem.data(), &count, &over);
     }
     T->chain_ok = false;
     // (an exit that does not use the batch's update: the covariance goes back to what the batch found, plv_points_spec_undo)
@@ -894,7 +894,6 @@ struct PointsUpdate {
     all.p_FinG = all.p_FinG_fej = pf.data();
     int rc_f = plv_jacobian_columns(st, &all, cols.data(), (int)cols.size(), &k);
     if (rc_f == PLV_OK && k > 0) {
-      ctx->gate_rows_hint = 2 * most_valid;
       T->chain_index.clear();
       T->chain_ok = Fp <= opt->max_msckf;  // (the selection loop cannot reach its cap: a candidate is taken on its own verdict)
       if (T->chain_ok && T->early_lines)
@@ -902,11 +901,11 @@ struct PointsUpdate {
           if (flags[f]) T->chain_index.emplace(pool[f].id, f);
       plv::frame_mark("@ update_points: columns done, fused call");
       const CpiStage cpi_stage = cpi.stage(opt->cpi);
-      ctx->cpi_stage = cpi.on ? &cpi_stage : nullptr;
-      rc_f = plv_points_update_fused(ctx, st, &all, &opt->tri, flags.data(), opt->max_msckf, k, cols.data(), 2 * opt->max_obs,
-                                     st->sigma_pix * st->sigma_pix, opt->chi2_mult, 3.0, pf.data(), ok.data(), err.data(), acc_all.data(),
-                                     &n_rows, dx, start_detection_ahead, ctx);
-      ctx->cpi_stage = nullptr;
+      rc_f = plv_points_update_submit(ctx, st, &all, &opt->tri, flags.data(), opt->max_msckf, k, cols.data(), 2 * opt->max_obs,
+                                      st->sigma_pix * st->sigma_pix, opt->chi2_mult, 3.0, nullptr, 2 * most_valid, cpi.on ? &cpi_stage : nullptr);
+      if (rc_f == PLV_OK)
+        rc_f = plv_points_update_collect(ctx, pf.data(), ok.data(), err.data(), acc_all.data(), &n_rows, dx, start_detection_ahead, ctx, wait_poll, ctx,
+                                         nullptr, nullptr, nullptr);
       T->chain_ok = false;
       rc_f = ekf_returned_false(rc_f, &res->status, dx, ctx->cov_n);
       fused_ran = rc_f == PLV_OK;
@@ -978,8 +977,9 @@ struct PointsUpdate {
 };
 }  // namespace
 
-int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, double *dx,
-                             plv_update_result *res, uint64_t *msckf_ids, uint8_t *accepted_out, double *p_out) {
+// plv_camera_update_points, with plv_camera_try_update's poll function (PointsUpdate::wait_poll)
+static int update_points(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, double *dx, plv_update_result *res,
+                         uint64_t *msckf_ids, uint8_t *accepted_out, double *p_out, int (*wait_poll)(void *)) {
   if (!ctx || !st || !opt || !dx || !res || st->n_clones < 2 || opt->max_msckf < 1 || opt->max_obs < 2) return PLV_E_BADARG;
   Tracker *T = trk(ctx);
   *res = plv_update_result{0, 0, 0, 0, 0, PLV_OK, 0, 0, 0};
@@ -987,7 +987,7 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
   plv::HostPhase ph_all("update_points: whole call");
   plv::HostPhase ph_pool("update_points: pool + staging");
   plv::RoctxRange rx_get("[Time-Cam] get features");
-  PointsUpdate U{ctx, T, st, opt, dx, res};
+  PointsUpdate U{ctx, T, st, opt, dx, res, wait_poll};
   T->last_slam.clear();
   T->last_init.clear();
   if (opt->n_slam > 0 && !opt->slam_ids) return PLV_E_BADARG;
@@ -1023,6 +1023,10 @@ int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_u
   res->n_rows = U.n_rows;
   res->n_accepted = return_rejected(U.pool, S, U.dt, U.start_of, U.unused, accepted_out, [](int) { return false; });
   return U.finish(PLV_OK);
+}
+int plv_camera_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_update_options *opt, double *dx,
+                             plv_update_result *res, uint64_t *msckf_ids, uint8_t *accepted_out, double *p_out) {
+  return update_points(ctx, st, opt, dx, res, msckf_ids, accepted_out, p_out, nullptr);
 }
 
 int plv_camera_update_list(plv_ctx *ctx, int which, int cap_feat, int cap_obs, int *n_feat, uint64_t *ids, int *obs_ptr,
@@ -1212,10 +1216,8 @@ int plv_camera_try_update(plv_ctx *ctx, const plv_state_view *st, plv_try_update
     ch.ready = okc;
   }
   plv::frame_mark("@ try_update: chain state ready");
-  ctx->wait_poll = io->opt_lines ? poll_line_pool : nullptr;
-  ctx->wait_poll_arg = ctx;
-  int rc = plv_camera_update_points(ctx, st, io->opt_points, io->dx_points, io->res_points, io->msckf_ids, io->msckf_accepted, io->p_FinG);
-  ctx->wait_poll = nullptr;
+  int rc = update_points(ctx, st, io->opt_points, io->dx_points, io->res_points, io->msckf_ids, io->msckf_accepted, io->p_FinG,
+                         io->opt_lines ? poll_line_pool : nullptr);
   ch.ready = false;
   T->defer_db = false;
   T->early_st = nullptr, T->early_lines = nullptr;
@@ -1297,7 +1299,7 @@ int plv_camera_frame(plv_ctx *ctx, const plv_state_view *st, plv_camera_frame_io
       std::vector<double> p(3 * (size_t)F), e(F), dx((size_t)std::max(n, 1));
       std::vector<uint8_t> ok(F), acc(F);
       int rows = 0;
-      (void)plv_points_update_collect(c, p.data(), ok.data(), e.data(), acc.data(), &rows, dx.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+      (void)plv_points_update_collect(c, p.data(), ok.data(), e.data(), acc.data(), &rows, dx.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
       (void)plv_points_spec_undo(c);
     }
   } spec_guard{ctx, Tf};

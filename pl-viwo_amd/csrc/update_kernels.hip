@@ -1108,36 +1108,36 @@ int launch_tsqr(plv_ctx *ctx, double *d_A, int lda, int m, int nc, double *d_tmp
 }
 
 // Mt = H P[cols,:] and S = Mt[:,cols] H^T + R in one launch (S: tiles on and above the diagonal).
-void launch_ekf_ms(plv_ctx *ctx, const double *d_P, int n, int ldp, const double *d_H, int r, int k, int ldh,
+void launch_ekf_ms(plv_ctx *ctx, const EkfRiders &rd, const double *d_P, int n, int ldp, const double *d_H, int r, int k, int ldh,
                    const int *d_cols, const double *d_Rdiag, double *Mt, int ldm, double *S, bool gathered, int *d_flag) {
   if (!gathered) (void)launch_gather_cov(ctx, d_P, n, ldp, d_cols, k);
   ProfScope ps(ctx->prof, "ekf_ms_kernel", ctx->stream);
   const int mt_blocks = cdiv(cdiv(r, 16) * cdiv(n, 16), 4);
   if (k > 192) {  // (the strip buffer of the fused kernel; launch_ekf's callers stay below: PLV_E_CAPACITY earlier)
     hipLaunchKernelGGL(ekf_mt_kernel, dim3(mt_blocks), dim3(256), 0, ctx->stream, d_H, ldh, r, k, ctx->d_inv.as<int>(),
-                       ctx->d_Pc.as<double>(), n, n, Mt, ldm, d_flag, ctx->skip_word);
+                       ctx->d_Pc.as<double>(), n, n, Mt, ldm, d_flag, rd.skip_word);
     hipLaunchKernelGGL(ekf_s_kernel, dim3(cdiv(cdiv(r, 16) * cdiv(r, 16), 4)), dim3(256), 0, ctx->stream, Mt + (size_t)(n + 1) * ldm, ldm,
-                       d_H, ldh, r, k, d_cols, d_Rdiag, S, r, ctx->skip_word);
+                       d_H, ldh, r, k, d_cols, d_Rdiag, S, r, rd.skip_word);
     return;
   }
   hipLaunchKernelGGL(ekf_ms_kernel, dim3(mt_blocks + cdiv(r, 16)), dim3(256), 0, ctx->stream, d_H, ldh, r, k, ctx->d_Pc.as<double>(), n, n,
-                     ctx->d_Ps.as<double>(), Mt, ldm, d_Rdiag, S, r, mt_blocks, d_flag, ctx->skip_word, 0, WhitenPanels{nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, -1});
+                     ctx->d_Ps.as<double>(), Mt, ldm, d_Rdiag, S, r, mt_blocks, d_flag, rd.skip_word, 0, WhitenPanels{nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, -1});
 }
 
 // Whitened route: B = M^T G M + I (k x k, upper tiles) and c = M^T g — ekf_ms_kernel with H := M^T (Lt), "Ps" := G (full
 // symmetric) and "Pc" := g as a k x 1 block — and, in further workgroups of the same launch, the products with the covariance
 // columns (WhitenPanels): GP = G P[cols, :], Y0 = M^T GP, d0 = P[:, cols] g.
-void launch_whiten_b(plv_ctx *ctx, const double *Lt, int k, const double *Gs, const double *gv, double *cv, double *B, int *d_flag,
+void launch_whiten_b(plv_ctx *ctx, const EkfRiders &rd, const double *Lt, int k, const double *Gs, const double *gv, double *cv, double *B, int *d_flag,
                      const double *d_P, int ldp, int n, const int *d_cols, double *Y0, double *GP, double *d0, const int *use_m) {
   ProfScope ps(ctx->prof, "ekf_ms_kernel", ctx->stream);
   const int mt_blocks = cdiv(cdiv(k, 16), 8), first = mt_blocks + cdiv(k, 16);  // eight waves a workgroup: one round of tiles per phase up to k = 128
   hipLaunchKernelGGL(ekf_ms_kernel, dim3(first + cdiv(n, 16)), dim3(512), 0, ctx->stream, Lt, k, k, k, gv, 1, 1, Gs, cv, k,
-                     (const double *)nullptr, B, k, mt_blocks, d_flag, ctx->skip_word, 1, WhitenPanels{d_P, ldp, n, d_cols, gv, Y0, GP, d0, use_m, first});
+                     (const double *)nullptr, B, k, mt_blocks, d_flag, rd.skip_word, 1, WhitenPanels{d_P, ldp, n, d_cols, gv, Y0, GP, d0, use_m, first});
 }
 
 // The EKF kernels on device-resident operands.  d_P is n x n (ldp).  On return *d_flag holds
 // 0 (updated), bit0 (negative diagonal), bit1 (S not positive definite).
-int launch_ekf(plv_ctx *ctx, double *d_P, int n, int ldp, const double *d_H, int r, int k, int ldh, const int *d_cols,
+int launch_ekf(plv_ctx *ctx, const EkfRiders &rd, double *d_P, int n, int ldp, const double *d_H, int r, int k, int ldh, const int *d_cols,
                const double *d_res, const double *d_Rdiag, double *d_dx, int *d_flag, bool gathered) {
   int rc;
   const int ldm = r, ldw = r;
@@ -1150,7 +1150,7 @@ int launch_ekf(plv_ctx *ctx, double *d_P, int n, int ldp, const double *d_H, int
     set_last_error("ekf: r=%d exceeds the LDS-resident Cholesky capacity", r);
     return PLV_E_CAPACITY;
   }
-  launch_ekf_ms(ctx, d_P, n, ldp, d_H, r, k, ldh, d_cols, d_Rdiag, Mt, ldm, S, gathered, d_flag);
+  launch_ekf_ms(ctx, rd, d_P, n, ldp, d_H, r, k, ldh, d_cols, d_Rdiag, Mt, ldm, S, gathered, d_flag);
   PLV_HIP_CHECK(ensure_dyn_smem((const void *)ekf_chol_kernel, (int)shm));
   PLV_HIP_CHECK(ensure_dyn_smem((const void *)ekf_trsm_kernel, (int)shm));
   {

@@ -3,9 +3,29 @@
 #include <chrono>
 #include <vector>
 
+#include "gate_stage.hpp"
 #include "plv_ctx.hpp"
 #include "plv_internal.hpp"
+#include "update_kernels.hpp"
 #include "update_route.hpp"
+
+namespace plv {
+// What the caller of one update launch (update_resident_launch) hands it beyond the staged batch, and what the launch reports back: a
+// local of the caller.  probe: the one-submission line update — the launch waits for the gate, reads its verdicts from pinned memory and
+// enqueues compression + EKF only when something was accepted; probe_src .. probe_stride_b: the second block the gate's workgroups copy
+// (update_kernels.hpp); probe_hook runs right before that wait.
+struct UpdateRiders {
+  EkfRiders ekf;  // the chain's share (the skip word is the launch's own choice)
+  bool probe = false;
+  const void *probe_src = nullptr;
+  void *probe_dst = nullptr;
+  int probe_stride_a = 0, probe_off_b = 0, probe_stride_b = 0;
+  void (*probe_hook)(void *) = nullptr;
+  void *probe_hook_arg = nullptr;
+  // out: ekf_commit_kernel took the second mirror (else the caller enqueues a copy command) / the applied word; the update ended at the gate
+  bool mirror2_taken = false, applied_used = false, ended_at_gate = false;
+};
+}  // namespace plv
 
 struct plv_ctx_update_state {
   plv::DevBuf q95;
@@ -20,6 +40,7 @@ struct plv_ctx_update_state {
   bool b_single_use = false;      // batch is rebuilt every frame: consume it in place, no working copy
   bool b_projected = false;       // the batch is already null-space projected (jacobian_nullspace_kernel)
   unsigned long long b_gather_token = 0;  // plv_ctx::gather_stamp right after the gathers that rode on the batch's launch (0: none)
+  plv::GateStage b_gate{};        // on: the batch's Jacobian launch ended with this gate (plv_update_gate_prepare); the update launch starts behind it
   std::vector<int> brows_host;
   // measurement compression (plv_update_compression_mode): 0 = whitened update (information matrix + factor of the prior block; no
   // factor of the measurements), 1 = Householder TSQR on the stacked rows; anything else is refused
@@ -50,6 +71,7 @@ struct plv_ctx_update_state {
     int *d_flag = nullptr, *d_acc_rows = nullptr;
   } redo_w;
   int pending_F = 0;  // features of a launched, not yet collected plv_msckf_update_resident_launch
+  bool pending_at_gate = false;  // ... which ended at the gate (UpdateRiders::probe): already synchronised, its result block is complete
   unsigned long long done_stamp = 0;  // plv_ctx::gather_stamp when done_ev was recorded
   hipEvent_t done_ev = nullptr;  // behind the update's last command: the wait does not cover what the caller enqueues after the launch
   // optional hipGraph replay of the update launch sequence (plv_update_graph_mode): key = every pointer / size / scalar a
@@ -99,7 +121,7 @@ struct plv_ctx_update_state {
   const unsigned char *pt_tri_ok = nullptr;
   int pt_tri_F = 0;
   plv::DevBuf chain_words;      // home of applied_word [0] and of the speculative batch's save word [1]
-  // the covariance as the last speculative point batch found it (ekf_commit_kernel, plv_ctx::cov_save), valid when the save word holds
+  // the covariance as the last speculative point batch found it (ekf_commit_kernel, plv::CovSave), valid when the save word holds
   // spec_save_seq; spec_save_seq = 0: no batch is waiting to be used or undone
   plv::DevBuf spec_save;
   unsigned spec_save_seq = 0, spec_save_count = 0;
@@ -113,6 +135,7 @@ struct plv_ctx_update_state {
     bool pending = false, mirrored = false, chain_events = false, spec = false;
     int rc = 0, F = 0, max_sel = 0;
     size_t o_p = 0, o_member = 0, o_words = 0;
+    plv::CovSave save;  // a speculative batch: what its launch's commit was handed, and a re-run inside the wait is handed again
     std::chrono::steady_clock::time_point t_entry;
   } point_job;
 };
