@@ -2,7 +2,8 @@
 // segment growth along the chains on the library's fitter threads (fld_fit_core.hpp), and TrackLSD's point-line assignment, line
 // matching and classification (REF: PL-VIWO/src/update/cam/TrackLSD.cpp:318-407,744-830; OpenCV contract of
 // ximgproc::FastLineDetector).  line_api.hip builds the tracker around it; tests/host_sanitize/ compiles this
-// header alone with -fsanitize=thread / address and drives the thread protocol with recorded edge maps.
+// header alone with -fsanitize=thread / address and drives the thread protocol with recorded edge maps.  The polling condition wait
+// of these threads (wait_polling, spin_budget_us) lives in job_slots.hpp, next to the line worker's job slots.
 #pragma once
 #include <sched.h>
 #include <algorithm>
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "fld_fit_core.hpp"
+#include "job_slots.hpp"
 #include "line_kernels.hpp"
 
 namespace plv {
@@ -135,16 +137,6 @@ struct HostStage {  // what the host stage keeps between detections
 
 const int kChainCap = 4096;
 
-// Condition wait that polls first: the library's threads hand each other work several times per frame and a thread that blocked
-// pays tens of microseconds (sometimes a millisecond) to be woken.  Polls for up to spin_us (the lock is released between probes),
-// then blocks as usual — at camera rates the threads sleep between frames, back to back frames keep them awake.
-// How long a waiting library thread polls before it blocks: process-wide, PLV_LINE_SPIN_US (default 300: the hand-overs inside one
-// frame follow each other within that time, between frames the threads sleep; 0 = block at once, measured +10..25 us per frame) or
-// plv_line_worker_config.
-inline std::atomic<int> &spin_budget_us() {
-  static std::atomic<int> v{getenv("PLV_LINE_SPIN_US") ? atoi(getenv("PLV_LINE_SPIN_US")) : 300};
-  return v;
-}
 // The most fitter threads the segment growth uses next to the walking thread (0 .. Fit::kThreads; 0 = the walk's own thread fits
 // afterwards).  host_extract takes one of them for a small map and both for a large one (see there).  Whole runs at workload C: 0.56 ms
 // per frame with one or two, 0.70 ms with none (without a fitter the worker finishes after the point update and the caller waits for it).
@@ -165,25 +157,6 @@ inline int default_fit_threads() {
 inline std::atomic<int> &fit_threads() {
   static std::atomic<int> v{getenv("PLV_LINE_FIT_THREADS") ? std::max(0, std::min((int)Fit::kThreads, atoi(getenv("PLV_LINE_FIT_THREADS")))) : default_fit_threads()};
   return v;
-}
-template <class Pred>
-inline void wait_polling(std::unique_lock<std::mutex> &lk, std::condition_variable &cv, Pred pred, int spin_us = -1) {
-  // `pred` reads atomics only (they are written under the mutex): the polling phase runs WITHOUT the mutex — round 5: eight threads
-  // polling by locking and unlocking it kept the thread that wanted to post a job out of it for tens of microseconds
-  if (pred()) return;
-  if (spin_us < 0) spin_us = spin_budget_us().load(std::memory_order_relaxed);
-  if (spin_us > 0) {
-    lk.unlock();
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-      for (int i = 0; i < 16; ++i) __builtin_ia32_pause();
-      if (pred()) break;
-      if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(spin_us)) break;
-    }
-    lk.lock();
-    if (pred()) return;
-  }
-  cv.wait(lk, pred);
 }
 
 inline float point_line_distance(const float *line, float x0, float y0) {

@@ -65,6 +65,31 @@ def test_line_host_stage_under_sanitizers(maps, tmp_path, san):
     assert "WARNING: ThreadSanitizer" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
 
 
+@pytest.mark.parametrize("san", ["thread", "address,undefined"])
+def test_line_worker_job_slots_under_sanitizers(tmp_path, san):
+    """pl-viwo_amd/csrc/job_slots.hpp, the line worker's protocol (three slots served by one thread: the update's database hand-back, the
+    detector's host stage, the asynchronous feed), compiled by plain g++ with no HIP header in reach and driven by bodies that write
+    plain words: join and probe of an idle slot, the joiner reading the body's result, service in the order hand-back, detect, feed
+    with all three posted behind a held worker, post / join rounds with naps on either side, drain_and_quit on a loaded and an idle
+    worker — all of it on two independent instances at once, with every wait blocking (spin budget 0) and polling (the default)."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / ("job_slots_check_" + san.replace(",", "_")))
+    src = os.path.join(ROOT, "tests", "host_sanitize", "job_slots_check.cpp")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", f"-fsanitize={san}", "-fno-omit-frame-pointer", src, "-o", exe, "-lpthread"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1", ASAN_OPTIONS="detect_leaks=0")
+    run = [exe]
+    if "thread" in san and shutil.which("setarch"):
+        run = ["setarch", os.uname().machine, "-R"] + run  # (as above: gcc 11's ThreadSanitizer and 28-bit mmap randomisation)
+    r = subprocess.run(run, capture_output=True, text=True, env=env, timeout=600)
+    import re
+    m = re.search(r"ok: job slots, (\d+) post / join rounds", r.stdout)
+    assert r.returncode == 0 and m and int(m.group(1)) > 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert "WARNING: ThreadSanitizer" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+
+
 def test_stage_block_packer_under_sanitizers(tmp_path):
     """pl-viwo_amd/csrc/stage_block.hpp, the packer of the Jacobian batches' one upload, under AddressSanitizer + UBSan: a point and a
     line batch in the stagers' order, every optional array present and absent, in a heap block of exactly the reported size — each
