@@ -27,11 +27,11 @@ class Settings:
         self.min_px_dist, self.fast_threshold = min_px_dist, fast_threshold
 
 
-def _pts(a):
+def points_array(a):
     return np.asarray(a, dtype=F32).reshape(-1, 2)
 
 
-def _ids(a):
+def ids_array(a):
     return np.asarray(a, dtype=np.uint64).reshape(-1)
 
 
@@ -96,7 +96,7 @@ class Detection:
         c = self.cfg
         h, w = img.shape
         if not valid:
-            return _pts([])
+            return points_array([])
         gx, gy = c.grid_x, c.grid_y
         if c.num_features < gx * gy:
             ratio = gx / gy
@@ -118,8 +118,8 @@ class Detection:
                     continue
                 ext.append((px, py))
         if not ext:
-            return _pts([])
-        return self.do.corner_subpix(img, _pts(ext))
+            return points_array([])
+        return self.do.corner_subpix(img, points_array(ext))
 
     def top_up(self, img, mask_cells, mask_corners, close, grid, boxes):
         """the extraction and the rejection near existing points (:478-512 / :617-650 / :793-825): accepted corners in order;
@@ -140,7 +140,7 @@ class Detection:
                 continue
             close[yg, xg] = 255
             out.append((px, py))
-        return _pts(out)
+        return points_array(out)
 
     def least(self):
         return min(20, int(0.5 * self.cfg.num_features))
@@ -148,7 +148,7 @@ class Detection:
     def monocular(self, img, mask, pts, ids, currid):
         """perform_detection_monocular (:395-528), for the comparison with DetectOracle.perform_detection"""
         h, w = img.shape
-        pts, ids = _pts(pts), _ids(ids)
+        pts, ids = points_array(pts), ids_array(ids)
         keep, close, grid, boxes, _ = self.prune(w, h, mask, pts, ids)
         pts, ids = pts[keep], ids[keep]
         if self.cfg.num_features - len(ids) < self.least():
@@ -163,8 +163,8 @@ class StereoRef:
         self.cfg, self.K8 = cfg, (np.asarray(K8_left, dtype=np.float64), np.asarray(K8_right, dtype=np.float64))
         self.fo = oracle_lib.load_front()
         self.det = Detection(cfg)
-        self.pts = [_pts([]), _pts([])]
-        self.ids = [_ids([]), _ids([])]
+        self.pts = [points_array([]), points_array([])]
+        self.ids = [ids_array([]), ids_array([])]
         self.currid = 0
         self.prev = None  # ((eq, pyramid, mask) left, (...) right) of the last pair
         self.db = {}      # id -> ([(t, u, v, un, vn) ...] camera 0, [...] camera 1)
@@ -176,7 +176,7 @@ class StereoRef:
         (eq0, pyr0, mask0), (eq1, pyr1, mask1) = left, right
         h, w = eq0.shape
         nf = self.cfg.num_features
-        pts0, ids0, pts1, ids1 = _pts(pts0), _ids(ids0), _pts(pts1), _ids(ids1)
+        pts0, ids0, pts1, ids1 = points_array(pts0), ids_array(ids0), points_array(pts1), ids_array(ids1)
         keep, close, grid, boxes, _ = self.det.prune(w, h, mask0, pts0, ids0)
         pts0, ids0 = pts0[keep], ids0[keep]
         if nf - len(ids0) > self.det.least():  # :609
@@ -196,8 +196,8 @@ class StereoRef:
                         self.stats["new stereo features"] += 1
                     else:
                         self.stats["new left-only features"] += 1
-                pts0, ids0 = np.vstack([pts0, _pts(add0)]), np.concatenate([ids0, _ids(id0)])
-                pts1, ids1 = np.vstack([pts1, _pts(add1)]), np.concatenate([ids1, _ids(id1)])
+                pts0, ids0 = np.vstack([pts0, points_array(add0)]), np.concatenate([ids0, ids_array(id0)])
+                pts1, ids1 = np.vstack([pts1, points_array(add1)]), np.concatenate([ids1, ids_array(id1)])
         keep, close, grid, boxes, spared = self.det.prune(w, h, mask1, pts1, ids1, spared={int(i) for i in ids0})  # :724-780
         self.stats["right points kept by the is_stereo exception"] += spared
         pts1, ids1 = pts1[keep], ids1[keep]
@@ -245,7 +245,7 @@ class StereoRef:
             events.add("fewer than 10 points")
         if m0 is None and m1 is None:  # :285-299
             events.add("reset")
-            self.pts, self.ids, self.prev = [_pts([]), _pts([])], [_ids([]), _ids([])], cur
+            self.pts, self.ids, self.prev = [points_array([]), points_array([])], [ids_array([]), ids_array([])], cur
             return
         good = ([], [])   # (point, id, normalised point) per camera
         right_index = {}
@@ -278,13 +278,13 @@ class StereoRef:
         for cam in (0, 1):  # :357-366
             for p, fid, un in good[cam]:
                 self.db.setdefault(int(fid), ([], []))[cam].append((t, p[0], p[1], un[0], un[1]))
-        self.pts = [_pts([g[0] for g in good[cam]]) for cam in (0, 1)]
-        self.ids = [_ids([g[1] for g in good[cam]]) for cam in (0, 1)]
+        self.pts = [points_array([g[0] for g in good[cam]]) for cam in (0, 1)]
+        self.ids = [ids_array([g[1] for g in good[cam]]) for cam in (0, 1)]
         self.prev = cur
 
 
 # ---- the streams the GPU test feeds (and the CPU test checks the coverage of)
-def _K(w, h, f):
+def intrinsics(w, h, f):
     return np.array([f, f * 1.01, w / 2.0 - 0.5, h / 2.0 + 0.25, -0.28, 0.07, 2e-4, -1e-4])
 
 
@@ -316,8 +316,8 @@ def streams():
     band[:, 80:112] = 255  # (between the grid cells' sample points at x = 0, 64, 128, ...: no cell is skipped for it)
     # a jump of the right view alone (frame 3) starves the right list, a jump of both (frame 5) the left one
     offs = [(0, 0, 0, 0), (2, 1, 0, 0), (4, 1, 0, 0), (5, 2, 40, 25), (6, 2, 40, 25), (60, 45, 40, 25), (61, 46, 40, 25), (63, 46, 40, 25)]
-    out.append(Stream("band", w, h, cfg, 6.0, offs, _K(w, h, 230.0), _K(w, h, 230.0), mask_right=band))
-    out.append(Stream("two cameras", w, h, cfg, 6.0, offs[:6], _K(w, h, 230.0), _K(w, h, 150.0) + np.array([0, 0, 3, -2, 0.1, 0, 0, 0])))
+    out.append(Stream("band", w, h, cfg, 6.0, offs, intrinsics(w, h, 230.0), intrinsics(w, h, 230.0), mask_right=band))
+    out.append(Stream("two cameras", w, h, cfg, 6.0, offs[:6], intrinsics(w, h, 230.0), intrinsics(w, h, 150.0) + np.array([0, 0, 3, -2, 0.1, 0, 0, 0])))
     w, h = 256, 192
     cfg = Settings(40, 4, 3, 8)
     nearly_all = np.full((h, w), 255, np.uint8)
@@ -325,7 +325,7 @@ def streams():
     offs = [(0, 0, 0, 0), (1, 1, 0, 0), (2, 1, 0, 0), (3, 2, 0, 0), (4, 2, 0, 0), (5, 3, 0, 0), (6, 3, 0, 0), (7, 3, 0, 0)]
     # frame 2's mask leaves a handful of points to frame 3's matching (fewer than 10: all-zero masks, empty lists), frame 4 detects
     # anew; frame 5's mask leaves none to frame 6 (both masks empty: the reset), frame 7 detects anew
-    out.append(Stream("cut", w, h, cfg, 4.0, offs, _K(w, h, 190.0), _K(w, h, 190.0), cut={2: nearly_all, 5: np.full((h, w), 255, np.uint8)}))
+    out.append(Stream("cut", w, h, cfg, 4.0, offs, intrinsics(w, h, 190.0), intrinsics(w, h, 190.0), cut={2: nearly_all, 5: np.full((h, w), 255, np.uint8)}))
     return out
 
 

@@ -19,7 +19,7 @@ W, H, PAD = 256, 192, 5
 @pytest.fixture(scope="module")
 def stream():
     offs = [(0, 0, 0, 0), (1, 1, 0, 0), (2, 1, 0, 0)]
-    K = stereo_ref._K(W, H, 190.0)
+    K = stereo_ref.intrinsics(W, H, 190.0)
     s = stereo_ref.Stream("strided", W, H, stereo_ref.Settings(40, 4, 3, 8), 4.0, offs, K, K)
     return s, [(t, left, right) for t, left, right, _, _ in s.frames()]
 
