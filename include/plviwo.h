@@ -637,7 +637,8 @@ int plv_build_line_jacobians_resident(plv_ctx *ctx, const plv_state_view *st, co
 int plv_detect_lines(plv_ctx *ctx, int which, float *lines, int cap, int *n_out);
 /* With the prefetch on, plv_tracker_feed / _staged / _downsampled run the line detector of the new image themselves: resize + Canny
  * go on the stream ahead of the point front-end, the host walks the edge chains and grows the segments while the device runs LK and
- * RANSAC, and the following plv_line_tracker_feed of the same frame takes the finished detection (same segments as without). */
+ * RANSAC, and the following plv_line_tracker_feed of the same frame takes the finished detection (same segments as without).
+ * No effect on a stereo context: plv_tracker_feed_stereo starts no detection ahead of time, the line feed detects when it is called. */
 int plv_line_prefetch_mode(plv_ctx *ctx, int on);
 /* The library's own threads (process-wide).  With the prefetch on the line detector's host stage runs on ONE worker thread per
  * context plus up to two segment-fitter threads (default: at most 2, one of them used below 150 000 half-resolution pixels); a thread that waits for work polls for spin_us microseconds before it blocks
@@ -701,7 +702,12 @@ int plv_vanishing_points(const double *R_ItoC, const double *K8, double *vps);
 
 /* TrackLSD::feed_monocular (REF :70-192) for the image currently held by the ctx — call after
  * plv_tracker_feed (the point tracker's current observations are the ones lines are attached to).
- * Updates lines_last / ids_last and the line track store (LineFeatureDatabase::update_feature). */
+ * Updates lines_last / ids_last and the line track store (LineFeatureDatabase::update_feature).
+ * On a context fed through plv_tracker_feed_stereo the lines are tracked on camera 0, as TrackLSD::feed_new_camera does with two
+ * images (REF :54-57): the image is camera 0's current one, the points are plv_stereo_last(ctx, 0, ...), the intrinsics and model
+ * the ctx's own (camera 0's).  The same holds for plv_detect_lines, plv_line_tracker_feed_async / _points, plv_line_walk_mode,
+ * plv_line_db_*, plv_camera_get_line_features and plv_camera_update_lines.  Before the first pair: PLV_E_BADARG, "no image has
+ * been fed". */
 int plv_line_tracker_feed(plv_ctx *ctx, double timestamp, const double *vps);
 /* The same with the caller's point observations of this frame (pts [n][2] pixels, ids [n]) in place of the ctx's own point
  * tracker: what an adapter that keeps the reference's TrackKLT object hands to TrackLSD (REF: TrackLSD.cpp:106-107 reads
@@ -811,9 +817,10 @@ int plv_slam_marg_flags(plv_ctx *ctx, int n_slam, const uint64_t *slam_ids, cons
  * plv_stereo_tracks with another order (a camera-0 observation in front of a camera-1 observation of the same feature), or an
  * obs_cam value above 1, is refused with PLV_E_BADARG before anything is launched.
  *
- * Not built for a stereo context (PLV_E_BADARG where a call could be asked for it): use_imu_res / use_imu_cov at the update level
- * (plv_update_options::cpi, plv_state_view::use_imu_cov; the low-level calls still honour res_R / res_p of the tracks), in-state
- * landmarks (max_slam), the line update and its point_used list, plv_camera_try_update / plv_camera_frame, plv_decision_trace. */
+ * Not built for a stereo context (PLV_E_BADARG where a call could be asked for it): use_imu_cov (plv_state_view::use_imu_cov),
+ * in-state landmarks (max_slam), plv_camera_try_update / plv_camera_frame (the pair's try_update is plv_stereo_try_update),
+ * plv_decision_trace.  plv_stereo_update_points takes no CPI table (use_imu_res) and records nothing in point_used;
+ * plv_stereo_try_update does both. */
 typedef struct plv_camera_side { /* camera 1 of the pair on the update side */
   double R_ItoC[9], p_IinC[3]; /* State::cam_extrinsic.at(1): Rot() row-major, pos()                   */
   double intrinsics[8];        /* State::cam_intrinsic.at(1) value                                      */
@@ -881,6 +888,9 @@ int plv_line_db_append_measurements(plv_ctx *ctx, uint64_t id, int n, const doub
  * UpdaterCamera.h / CamHelper.cpp:671-695): plv_camera_update_points records every triangulated feature it
  * examined; this entry point lets a caller with its own point pipeline do the same. */
 int plv_point_used_insert(plv_ctx *ctx, uint64_t id, const double *p_FinG, double newest_obs_time);
+/* What that list holds, in ascending id order: ids [cap], p_FinG [cap][3], newest_obs_time [cap] (each nullable).  *n receives the
+ * count; cap too small: PLV_E_CAPACITY with *n set and nothing written.  It changes nothing. */
+int plv_point_used_list(plv_ctx *ctx, int cap, int *n, uint64_t *ids, double *p_FinG, double *newest_obs_time);
 
 /* LineHelper::get_line_features' place in try_update (REF: UpdaterCamera.cpp:148-152): the reference forms and triangulates the
  * line pool after get_features and BEFORE msckf_update's correction reaches the state; lines_update then linearises on the
@@ -958,6 +968,27 @@ typedef struct plv_try_update {
   int line_db_size;                      /* out */
 } plv_try_update;
 int plv_camera_try_update(plv_ctx *ctx, const plv_state_view *st, plv_try_update *io);
+/* plv_camera_try_update for a stereo pair, on a context fed through plv_tracker_feed_stereo (same plv_try_update block, same failure
+ * contract).  The published reference cannot take a pair through try_update (UpdaterCamera's constructor makes the line tracker in
+ * its monocular branch only, try_update asks for it unconditionally); what it intends is built: points on both cameras, lines on
+ * camera 0 (TrackLSD::feed_new_camera, TrackLSD.cpp:54-57), everything else per cam_id = sensor_ids.at(0).
+ * Point half: plv_stereo_update_points, and
+ *   - opt_points->cpi (use_imu_res) is honoured: an observation whose time + dt the table cannot serve returns to its own camera's
+ *     track (CamHelper.cpp:356-365); the distinct served times of both cameras are listed once (the pair shares dt: a left and a
+ *     right observation of one frame share one pose) and cpi_pose_kernel forms their poses on the ctx stream in front of the stereo
+ *     triangulation; the Jacobian launch of the selected features reads the same poses.  No pose reaches the host, and there are
+ *     no more synchronisations than without a table;
+ *   - every feature the reference copies to point_used (CamHelper.cpp:648-699: triangulated, consistent or not, until max_msckf
+ *     ends the loop) is recorded as by plv_point_used_insert, under the id both cameras share.
+ * When the update was accepted its dx is applied with plv_state_boxplus over io->vars and the tracker is told calibrated intrinsics
+ * (plv_set_camera_intrinsics for camera 0, plv_stereo_set_intrinsics(ctx, 1, ...) for camera 1).  `right` is not const: like st's
+ * calibration fields, its extrinsics and intrinsics are `mirror`s of the variables and are current for the line half.
+ * Line half (opt_lines != NULL), on camera 0's calibration: plv_camera_get_line_features on the state before the point dx is
+ * applied, plv_camera_update_lines on the updated state (it cleans point_used when the window is full), its dx applied.
+ * Refused with PLV_E_BADARG before anything is touched: max_slam != 0, st->use_imu_cov, plv_decision_trace on, a context whose
+ * stereo tracker is not configured, right == NULL, a state id of `right` that collides with camera 0's or the time offset's, a
+ * CPI table plv_cpi_poses would refuse, whatever plv_state_boxplus refuses of vars. */
+int plv_stereo_try_update(plv_ctx *ctx, const plv_state_view *st, plv_camera_side *right, plv_try_update *io);
 /* One camera frame as one call: UpdaterCamera::feed_measurement (REF: UpdaterCamera.cpp:77-116: TrackKLT::feed_new_camera, then
  * LineHelper::Vanishing_Points + TrackLSD::feed_new_camera when lines are on) followed by try_update (:139-195) through
  * plv_camera_try_update.  The image comes from HBM slot `slot` (plv_image_stage; slot >= 0) or from the host (img, stride).

@@ -203,6 +203,7 @@ def load_library():
                                                C.POINTER(PlvUpdateResult), u64p, u8p, dp]),
         "plv_line_db_append_measurements": (C.c_int, [vp, C.c_uint64, C.c_int, dp, fp, fp, C.c_int, ip, C.c_int]),
         "plv_point_used_insert": (C.c_int, [vp, C.c_uint64, dp, C.c_double]),
+        "plv_point_used_list": (C.c_int, [vp, C.c_int, ip, C.POINTER(C.c_uint64), dp, dp]),
         "plv_select_imu_readings": (C.c_int, [C.c_int, dp, dp, dp, C.c_double, C.c_double, C.c_int, dp, dp, dp, ip, ip]),
         "plv_reset_cpi": (None, [C.POINTER(PlvCpiAccum), C.POINTER(PlvImuState), C.c_double]),
         "plv_propagate": (C.c_int, [vp, C.POINTER(PlvImuState), C.POINTER(PlvImuNoise), C.c_int, dp, dp, dp, C.POINTER(PlvCpiAccum),
@@ -276,6 +277,7 @@ def load_library():
         "plv_jpl_left_update": (None, [C.c_int, dp, dp, dp]),
         "plv_state_boxplus": (C.c_int, [C.c_int, C.POINTER(PlvStateVar), dp, C.c_int]),
         "plv_camera_try_update": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvTryUpdate)]),
+        "plv_stereo_try_update": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvCameraSide), C.POINTER(PlvTryUpdate)]),
         "plv_camera_frame": (C.c_int, [vp, C.POINTER(PlvStateView), C.POINTER(PlvCameraFrameIo)]),
         "plv_line_walk_mode": (C.c_int, [vp, C.c_int]),
         "plv_line_walk_info": (C.c_int, [vp, ip, ip, ip, ip, ip]),
@@ -1624,6 +1626,14 @@ class Context:
         p = np.ascontiguousarray(p, dtype=np.float64)
         self._chk(self.lib.plv_point_used_insert(self.h, int(fid), _dp(p), float(newest)))
 
+    def point_used_list(self):
+        """plv_point_used_list: (ids, p_FinG [n][3], newest observation time [n]) of the point_used list, ascending ids"""
+        n = C.c_int()
+        self._chk(self.lib.plv_point_used_list(self.h, 0, C.byref(n), None, None, None), allow=(PLV_E_CAPACITY,))
+        ids, p, newest = np.zeros(max(n.value, 1), dtype=np.uint64), np.zeros((max(n.value, 1), 3)), np.zeros(max(n.value, 1))
+        self._chk(self.lib.plv_point_used_list(self.h, n.value, C.byref(n), _u64p(ids), _dp(p), _dp(newest)))
+        return ids[:n.value].copy(), p[:n.value].copy(), newest[:n.value].copy()
+
     def camera_get_line_features(self, st, n=None, max_obs=None, **kw):
         """plv_camera_get_line_features: records the state (before the point update's dx is applied) the next camera_update_lines
         triangulates its pool on, as the reference's try_update orders it"""
@@ -2203,6 +2213,14 @@ class Context:
         return dict(dx=dx, n_pool=res.n_pool, n_msckf=m, n_accepted=res.n_accepted, n_rows=res.n_rows, n_returned=res.n_returned,
                     status=res.status, ids=ids[:m].copy(), accepted=acc[:m].copy(), p_FinG=p[:m].copy(), n_slam=res.n_slam,
                     n_init=res.n_init, n_truncated=res.n_truncated)
+
+    def stereo_try_update(self, st, right, plus, n, max_msckf, max_obs, t_prev_frame, state_time, **kw):
+        """plv_stereo_try_update: camera_try_update for a pair — the point update over both cameras (with `cpi`: poses from the CPI
+        table), its dx applied through `plus` (a BoxPlus whose arrays back `st` and mirror into `right`, a CameraSide), then the line
+        update on camera 0 and its dx applied.  Returns what camera_try_update returns."""
+        io, results = self._try_update_io(plus, n, max_msckf, max_obs, t_prev_frame, state_time, **kw)
+        self._chk(self.lib.plv_stereo_try_update(self.h, C.byref(st.c), C.byref(right.c) if right is not None else None, C.byref(io)))
+        return results()
 
     def triangulate(self, st, tr, min_dist=0.1, max_dist=60.0, max_cond=1e4, max_baseline=40.0, refine=True):
         opt = PlvTriOptions(min_dist, max_dist, max_cond, max_baseline, 1 if refine else 0)

@@ -365,8 +365,47 @@ struct CpiPoses {
   }
 };
 
-// REF CamHelper.cpp get_imu_poses (:356-365): an observation whose time + dt the table cannot serve leaves its track for `unused`
-// (cpi_servable: decided on the host from times, no launch and no synchronisation); the others' distinct times are listed.  A table
+// Which query times the table serves and where each served one stands in `times`, the list of the DISTINCT served times
+// (cpi_servable: decided on the host from times, no launch and no synchronisation).  A window's observations carry the stamps of
+// its last few frames: the memo of what was asked, servable or not.
+struct CpiTimes {
+  const plv_state_view &st;
+  const plv_cpi_table &cpi;
+  std::vector<double> &times;
+  std::vector<double> asked;
+  std::vector<int> answer;  // index into times, -1: not served
+  int index_of(double tq) {
+    for (size_t i = asked.size(); i-- > 0;)
+      if (asked[i] == tq) return answer[i];
+    const bool ok = cpi_servable(st, cpi, tq).ok;
+    asked.push_back(tq), answer.push_back(ok ? (int)times.size() : -1);
+    if (ok) times.push_back(tq);
+    return answer.back();
+  }
+};
+// REF CamHelper.cpp get_imu_poses (:356-365) on one track: an observation whose time + dt the table cannot serve leaves the track
+// for `unused`; the pose index of every observation that stays is appended to pose_of
+template <class TrackT> void cpi_attach_track(CpiTimes &M, double dt, uint64_t id, TrackT &tr, TrackMap<TrackT> &unused, std::vector<int> &pose_of) {
+  bool all = true;
+  for (double t : tr.t) all = (M.index_of(t + dt) >= 0) && all;
+  if (all) {
+    for (double t : tr.t) pose_of.push_back(M.index_of(t + dt));
+    return;
+  }
+  TrackT kept;
+  copy_track_meta(kept, tr);
+  for (size_t i = 0; i < tr.t.size(); ++i) {
+    const int q = M.index_of(tr.t[i] + dt);
+    if (q < 0) {
+      give_back(unused, id, tr, i);
+      continue;
+    }
+    append_obs(kept, tr, i);
+    pose_of.push_back(q);
+  }
+  tr = std::move(kept);
+}
+// ... on a pool: the others' distinct times are listed, the pose indices stand in the order of the flattened pool.  A table
 // plv_cpi_poses would refuse returns PLV_E_BADARG with the pool as it was.
 template <class TrackT>
 int cpi_attach(const plv_state_view *st, const plv_cpi_table *cpi, bool noise, double dt, std::vector<PoolCand<TrackT>> &pool,
@@ -374,37 +413,8 @@ int cpi_attach(const plv_state_view *st, const plv_cpi_table *cpi, bool noise, d
   if (!cpi_table_usable(cpi) || st->n_clones < 1 || (noise && cpi->n > 0 && !cpi->Q)) return PLV_E_BADARG;
   out = CpiPoses();
   out.on = true, out.noise = noise;
-  // (a window's observations carry the stamps of its last few frames: the memo of what was asked, servable or not)
-  std::vector<double> asked;
-  std::vector<int> answer;  // index into out.times, -1: not served
-  auto index_of = [&](double tq) {
-    for (size_t i = asked.size(); i-- > 0;)
-      if (asked[i] == tq) return answer[i];
-    const bool ok = cpi_servable(*st, *cpi, tq).ok;
-    asked.push_back(tq), answer.push_back(ok ? (int)out.times.size() : -1);
-    if (ok) out.times.push_back(tq);
-    return answer.back();
-  };
-  for (PoolCand<TrackT> &c : pool) {
-    bool all = true;
-    for (double t : c.tr.t) all = (index_of(t + dt) >= 0) && all;
-    if (all) {
-      for (double t : c.tr.t) out.pose_of.push_back(index_of(t + dt));
-      continue;
-    }
-    TrackT kept;
-    copy_track_meta(kept, c.tr);
-    for (size_t i = 0; i < c.tr.t.size(); ++i) {
-      const int q = index_of(c.tr.t[i] + dt);
-      if (q < 0) {
-        give_back(unused, c.id, c.tr, i);
-        continue;
-      }
-      append_obs(kept, c.tr, i);
-      out.pose_of.push_back(q);
-    }
-    c.tr = std::move(kept);
-  }
+  CpiTimes M{*st, *cpi, out.times};
+  for (PoolCand<TrackT> &c : pool) cpi_attach_track(M, dt, c.id, c.tr, unused, out.pose_of);
   if (noise && !out.times.empty()) {
     const size_t nt = out.times.size();
     out.Qt.resize(36 * nt), out.Ct.resize(nt);

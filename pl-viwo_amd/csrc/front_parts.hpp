@@ -80,6 +80,14 @@ struct CamFront {  // one camera's images on the device
   // the pyramid the next image goes into; commit() once everything of that image is enqueued
   int next() const { return fed == 0 ? cur : 1 - cur; }
   void commit(int next) { cur = next, ++fed; }
+  // equalised level-0 image of the current (which = PLV_PYR_CUR) or previous (PLV_PYR_LAST) frame; null before it has been fed
+  const uint8_t *level0(int which, int *w, int *h) const {
+    if (fed < (which == PLV_PYR_LAST ? 2 : 1)) return nullptr;
+    const PyrDesc &p = pyr[which == PLV_PYR_LAST ? 1 - cur : cur];
+    if (w) *w = p.w[0];
+    if (h) *h = p.h[0];
+    return p.base + p.off[0];
+  }
 };
 
 struct RansacScratch {  // launch_ransac's device scratch

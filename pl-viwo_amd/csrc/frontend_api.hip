@@ -404,7 +404,22 @@ int plv_feed_staged(plv_ctx *ctx, int slot) {
 
 }  // extern "C"
 namespace plv {
-int plv_front_fed_count(plv_ctx *ctx) { return (ctx && ctx->fe_state) ? fe(ctx)->fed : 0; }
+// The images the line code works on: the context's one camera, or camera 0 of the pair once the stereo tracker has taken the
+// context (plv_ctx::tracker_kind).  Both are a CamFront; null while nothing has been fed.
+static const CamFront *front_of(plv_ctx *ctx) {
+  if (!ctx) return nullptr;
+  if (ctx->tracker_kind == PLV_TRACKER_STEREO) return plv_stereo_front0(ctx);
+  return ctx->fe_state ? fe(ctx) : nullptr;
+}
+int plv_front_fed_count(plv_ctx *ctx) {
+  const CamFront *s = front_of(ctx);
+  return s ? s->fed : 0;
+}
+// TrackBase::get_last_obs / get_last_ids of the camera the lines are tracked on
+int plv_front_last_points(plv_ctx *ctx, float *pts, uint64_t *ids, int cap, int *n) {
+  if (ctx && ctx->tracker_kind == PLV_TRACKER_STEREO) return plv_stereo_last(ctx, 0, pts, ids, cap, n);
+  return plv_tracker_last(ctx, pts, ids, cap, n);
+}
 // where the flow launched last (plv_perform_matching_launch, not waited for yet) leaves its results on the device: tracked positions
 // and their normalised coordinates [n][2], the inlier mask [n] (LK status and RANSAC)
 int plv_front_match_device(plv_ctx *ctx, const float **d_p1, const float **d_n1, const uint8_t **d_mask, int *n) {
@@ -416,13 +431,8 @@ int plv_front_match_device(plv_ctx *ctx, const float **d_p1, const float **d_n1,
   return PLV_OK;
 }
 const uint8_t *plv_front_level0(plv_ctx *ctx, int which, int *w, int *h) {
-  if (!ctx || !ctx->fe_state) return nullptr;
-  FrontState *s = fe(ctx);
-  if (s->fed < (which == PLV_PYR_LAST ? 2 : 1)) return nullptr;
-  const PyrDesc &p = s->pyr[which == PLV_PYR_LAST ? 1 - s->cur : s->cur];
-  if (w) *w = p.w[0];
-  if (h) *h = p.h[0];
-  return p.base + p.off[0];
+  const CamFront *s = front_of(ctx);
+  return s ? s->level0(which, w, h) : nullptr;
 }
 }  // namespace plv
 extern "C" {

@@ -129,6 +129,17 @@ struct StateStage {
     if (c->Q) rQ = B.add<36>(c->Q, nt), rc = B.add(c->clone, nt);
     return PLV_OK;
   }
+  // The poses of c's times stand in the staging's buffer already — formed by launch_cpi for an earlier batch of the same update, of
+  // which this one is a part (the stereo update's selection out of its triangulated pool): only the pose index rides in the block.
+  int add_cpi_formed(const CpiStage *c, size_t nobs, Staging &sg) {
+    if (c->n_times < 1 || !c->pose_of || c->Q || sg.cpi.cap < 2 * 12 * (size_t)c->n_times * sizeof(double)) return PLV_E_BADARG;
+    for (size_t o = 0; o < nobs; ++o)
+      if (c->pose_of[o] < 0 || c->pose_of[o] >= c->n_times) return PLV_E_BADARG;
+    cs = c;
+    c_of = B.add(c->pose_of, nobs);
+    cpi_R[0] = sg.cpi.as<double>(), cpi_p[0] = cpi_R[0] + 9 * (size_t)c->n_times;  // (launch_cpi's layout)
+    return PLV_OK;
+  }
   // behind the block's upload on the ctx stream; tri_R / tri_p: the clone poses (device) of a second state to form the poses on as well
   int launch_cpi(plv_ctx *ctx, Staging &sg, const double *tri_R, const double *tri_p) {
     const size_t nt = (size_t)cs->n_times, ok_room = StageBlock::padded(nt);
@@ -205,8 +216,10 @@ struct StageExtra {  // optional riders of the packed block (one-submission upda
   const uint8_t *obs_cam = nullptr;
   const CamSide *d_cams = nullptr;
   const uint8_t *d_obs_cam = nullptr;
-  // residual poses of the batch come from the CPI table on the device (null: the tracks' own res_R / res_p, if any)
+  // residual poses of the batch come from the CPI table on the device (null: the tracks' own res_R / res_p, if any);
+  // cpi_formed: they are the ones the previous staging formed (StateStage::add_cpi_formed), nothing is launched
   const CpiStage *cpi = nullptr;
+  bool cpi_formed = false;
 };
 int stage_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *st, const plv_tracks *tr, int k,
                  const int *col_to_state, int ld, JacParams &P, StageExtra *ex = nullptr) {
@@ -224,7 +237,9 @@ int stage_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *s
   const auto uv = B.add<2>(tr->obs_uv, nobs);
   const auto pg = B.add<3>(tr->p_FinG, F), pgf = B.add<3>(tr->p_FinG_fej, F);
   const CpiStage *cs = tr->res_R || !ex ? nullptr : ex->cpi;
-  if (cs) TRY(S.add_cpi(cs, (size_t)nobs));
+  const bool formed = cs && ex->cpi_formed;
+  if (formed) TRY(S.add_cpi_formed(cs, (size_t)nobs, us->staging_of(3)));
+  else if (cs) TRY(S.add_cpi(cs, (size_t)nobs));
   else S.add_res_poses(tr->res_R, tr->res_p, nobs);
   S.add_cols();
   StageBlock::Slot<float> xuvn;
@@ -260,7 +275,7 @@ int stage_inputs(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *s
     PLV_HIP_CHECK(hipStreamWaitEvent(ctx->stream, us->spec_ev, 0));
   } else
     PLV_HIP_CHECK(plv::memcpy_async(sg.jin.p, sg.h_jin.p, B.total(), hipMemcpyHostToDevice, ctx->stream));
-  if (cs) TRY(S.launch_cpi(ctx, sg, nullptr, nullptr));
+  if (cs && !formed) TRY(S.launch_cpi(ctx, sg, nullptr, nullptr));
   S.fill(P, ctx, ld);
   P.col_ext = S.col_of(st->extrinsic_state_id);
   P.col_int = S.col_of(st->intrinsic_state_id);
@@ -757,8 +772,10 @@ void fill_cam_sides(const plv_ctx *ctx, const plv_state_view *st, const plv_came
   cams[0].col_int = col_of(st->intrinsic_state_id), cams[1].col_int = col_of(right->intrinsic_state_id);
 }
 
+// cpi (optional): the batch's residual poses are the ones the update's triangulation formed from the CPI table (cpi->pose_of: every
+// observation's index into them)
 int build_stereo_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_state_view *st, const plv_camera_side *right,
-                           const plv_stereo_tracks *s, int k, const int *col_to_state, int ld) {
+                           const plv_stereo_tracks *s, int k, const int *col_to_state, int ld, const CpiStage *cpi = nullptr) {
   TRY(check_stereo("stereo jacobians", st, right, s));
   TRY(check_views(st, &s->tracks));
   if (k < 1 || ld < 2 || !col_to_state) return PLV_E_BADARG;
@@ -768,6 +785,7 @@ int build_stereo_on_device(plv_ctx *ctx, plv_ctx_update_state *us, const plv_sta
   fill_cam_sides(ctx, st, right, k, col_to_state, cams);
   StageExtra ex;
   ex.cams = cams, ex.obs_cam = s->obs_cam;
+  ex.cpi = cpi, ex.cpi_formed = cpi != nullptr;
   JacParams P{};
   TRY(stage_inputs(ctx, us, st, &s->tracks, k, col_to_state, ld, P, &ex));
   return launch_batch(
@@ -796,12 +814,7 @@ int plv_stereo_jacobian_columns(const plv_state_view *st, const plv_camera_side 
 
 int plv_build_jacobians_stereo_resident(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *s,
                                         int k, const int *col_to_state, int ld) {
-  if (!ctx) return PLV_E_BADARG;
-  (void)hipSetDevice(ctx->device);
-  auto *us = plv_update_state(ctx);
-  TRY(build_stereo_on_device(ctx, us, st, right, s, k, col_to_state, ld));
-  us->b_single_use = true;  // consumed in place by the next plv_msckf_update_resident (which projects it first)
-  return PLV_OK;            // stream-ordered; no host synchronisation
+  return plv::stereo_jacobians_resident(ctx, st, right, s, k, col_to_state, ld, nullptr);
 }
 
 int plv_build_jacobians_stereo(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *s, int k,
@@ -816,6 +829,24 @@ int plv_build_jacobians_stereo(plv_ctx *ctx, const plv_state_view *st, const plv
 
 int plv_triangulate_stereo(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *s,
                            const plv_tri_options *opt, double *p_FinG, uint8_t *ok, double *reproj_err) {
+  return plv::stereo_triangulate(ctx, st, right, s, opt, nullptr, p_FinG, ok, reproj_err);
+}
+
+}  // extern "C"
+namespace plv {
+
+int stereo_jacobians_resident(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *s, int k,
+                              const int *col_to_state, int ld, const CpiStage *cpi) {
+  if (!ctx) return PLV_E_BADARG;
+  (void)hipSetDevice(ctx->device);
+  auto *us = plv_update_state(ctx);
+  TRY(build_stereo_on_device(ctx, us, st, right, s, k, col_to_state, ld, cpi));
+  us->b_single_use = true;  // consumed in place by the next plv_msckf_update_resident (which projects it first)
+  return PLV_OK;            // stream-ordered; no host synchronisation
+}
+
+int stereo_triangulate(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *s,
+                       const plv_tri_options *opt, const CpiStage *cpi, double *p_FinG, uint8_t *ok, double *reproj_err) {
   if (!ctx || !opt || !p_FinG || !ok) return PLV_E_BADARG;
   TRY(check_stereo("plv_triangulate_stereo", st, right, s));
   (void)hipSetDevice(ctx->device);
@@ -852,10 +883,12 @@ int plv_triangulate_stereo(plv_ctx *ctx, const plv_state_view *st, const plv_cam
   std::vector<double> ot((size_t)nobs), rR, rp;
   std::vector<float> uv(2 * (size_t)nobs), uvn(2 * (size_t)nobs);
   std::vector<uint8_t> oc((size_t)nobs);
+  std::vector<int> pose_of(cpi ? (size_t)nobs : 0);  // (the CPI poses' indices move with their observations)
   if (t2.res_R) rR.resize(9 * (size_t)nobs), rp.resize(3 * (size_t)nobs);
   for (int o = 0; o < nobs; ++o) {
     const int q = src[o];
     ot[o] = t2.obs_time[q], oc[o] = s->obs_cam[q];
+    if (cpi) pose_of[o] = cpi->pose_of[q];
     std::copy(t2.obs_uv + 2 * (size_t)q, t2.obs_uv + 2 * (size_t)q + 2, &uv[2 * (size_t)o]);
     std::copy(t2.obs_uvn + 2 * (size_t)q, t2.obs_uvn + 2 * (size_t)q + 2, &uvn[2 * (size_t)o]);
     if (t2.res_R) {
@@ -871,6 +904,8 @@ int plv_triangulate_stereo(plv_ctx *ctx, const plv_state_view *st, const plv_cam
   fill_cam_sides(ctx, st, right, 0, dummy_cols, cams);
   StageExtra ex;
   ex.cams = cams, ex.obs_cam = oc.data(), ex.uvn = uvn.data();
+  CpiStage moved{};
+  if (cpi) moved = *cpi, moved.pose_of = pose_of.data(), ex.cpi = &moved;
   JacParams P{};
   TRY(stage_inputs(ctx, us, st, &t2, 0, dummy_cols, 2, P, &ex));
   const size_t o_pose = 0, o_valid = (size_t)nobs * 96, o_p = (o_valid + nobs + 15) & ~(size_t)15, o_err = o_p + (size_t)F * 24,
@@ -887,7 +922,7 @@ int plv_triangulate_stereo(plv_ctx *ctx, const plv_state_view *st, const plv_cam
   return PLV_OK;
 }
 
-}  // extern "C"
+}  // namespace plv
 
 namespace {
 

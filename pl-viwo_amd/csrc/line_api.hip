@@ -34,7 +34,6 @@
 using namespace plv;
 using namespace plv::linehost;
 
-int plv_tracker_last(plv_ctx *ctx, float *pts, uint64_t *ids, int cap, int *n);
 namespace {
 
 // The pool of LineHelper::get_line_features (REF: linefeat/LineHelper.cpp:33-44: features_containing_older + features_not_containing_newer,
@@ -1281,12 +1280,12 @@ int plv_line_detect_finish(plv_ctx *ctx, int which) {
 // which also is where the reference's second equalizeHist comes from: same input, same result).
 int plv_line_tracker_feed(plv_ctx *ctx, double timestamp, const double *vps) {
   if (!ctx || !vps) return PLV_E_BADARG;
-  // the point tracker's current observations (REF :106-107, :131-134)
+  // the point tracker's current observations (REF :106-107, :131-134); of camera 0 on a stereo context
   int np = 0;
-  TRY(plv_tracker_last(ctx, nullptr, nullptr, 1 << 30, &np));
+  TRY(plv_front_last_points(ctx, nullptr, nullptr, 1 << 30, &np));
   std::vector<float> pts(2 * (size_t)std::max(np, 1));
   std::vector<uint64_t> pids((size_t)std::max(np, 1));
-  TRY(plv_tracker_last(ctx, pts.data(), pids.data(), np, &np));
+  TRY(plv_front_last_points(ctx, pts.data(), pids.data(), np, &np));
   return plv_line_tracker_feed_points(ctx, timestamp, vps, np, pts.data(), pids.data());
 }
 
@@ -1301,10 +1300,10 @@ int plv_line_tracker_feed_points(plv_ctx *ctx, double timestamp, const double *v
 int plv_line_tracker_feed_async(plv_ctx *ctx, double timestamp, const double *vps) {
   if (!ctx || !vps) return PLV_E_BADARG;
   int np = 0;
-  TRY(plv_tracker_last(ctx, nullptr, nullptr, 1 << 30, &np));
+  TRY(plv_front_last_points(ctx, nullptr, nullptr, 1 << 30, &np));
   std::vector<float> pts(2 * (size_t)std::max(np, 1));
   std::vector<uint64_t> pids((size_t)std::max(np, 1));
-  TRY(plv_tracker_last(ctx, pts.data(), pids.data(), np, &np));
+  TRY(plv_front_last_points(ctx, pts.data(), pids.data(), np, &np));
   return plv_line_tracker_feed_async_points(ctx, timestamp, vps, np, pts.data(), pids.data());
 }
 

@@ -9,7 +9,7 @@
 
 struct plv_ctx_update_state;  // update_state.hpp
 namespace plv {  // update_state.hpp, update_kernels.hpp, gate_stage.hpp, camera_tracks.hpp
-struct UpdateRiders; struct CovSave; struct GateStage; struct CpiStage;
+struct UpdateRiders; struct CovSave; struct GateStage; struct CpiStage; struct CamFront;  // (front_parts.hpp)
 }
 
 // Speculative submission of the point update (round 6): host arrays per candidate + where the flow leaves its results on the device
@@ -52,6 +52,14 @@ int plv_prior_prefetch(plv_ctx *ctx, int phase, const int *d_cols, int k, int F,
 // what every stereo call refuses of the pair's camera 1: no side, an unknown model, a state id that collides with camera 0's or the
 // time offset's.  Host logic; `what` leads the error text.
 int plv_stereo_side_check(const char *what, const plv_state_view *st, const plv_camera_side *right);
+// plv_triangulate_stereo / plv_build_jacobians_stereo_resident with the residual poses from a CPI table (cpi; null: as the public
+// calls).  The triangulation stages the table and forms the pose of every distinct time on the stream in front of its kernel
+// (cpi_pose_kernel); the Jacobian batch that follows is a part of the triangulated pool and reads the same poses: its cpi->pose_of
+// points into them, nothing is formed again and no pose reaches the host.
+int stereo_triangulate(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *tracks,
+                       const plv_tri_options *opt, const CpiStage *cpi, double *p_FinG, uint8_t *ok, double *reproj_err);
+int stereo_jacobians_resident(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_stereo_tracks *tracks, int k,
+                              const int *col_to_state, int ld, const CpiStage *cpi);
 
 // ---- init_api.cpp
 // the test plv_state_boxplus makes of a variable list, made before anything is enqueued (plv_camera_try_update / plv_camera_frame)
@@ -64,8 +72,12 @@ void plv_frontend_destroy(plv_ctx *ctx);
 int plv_feed_image_enqueue(plv_ctx *ctx, const uint8_t *img, int stride);
 // plv_tracker_feed_encoded's image feed: conversion of the encoded host image into the frame's raw image + the device feed, enqueued
 int plv_feed_encoded_enqueue(plv_ctx *ctx, const uint8_t *data, int stride, int encoding);
+// The next three answer for whichever tracker owns the context (plv_ctx::tracker_kind): the context's one camera, or camera 0 of
+// a stereo pair — the camera the lines are tracked on (REF: TrackLSD.cpp:54-57).
 // images fed so far: identifies the frame a cached detection belongs to
 int plv_front_fed_count(plv_ctx *ctx);
+// the point tracker's current observations and their ids (plv_tracker_last / plv_stereo_last of camera 0)
+int plv_front_last_points(plv_ctx *ctx, float *pts, uint64_t *ids, int cap, int *n);
 // where the flow launched last leaves its results on the device: positions, normalised coordinates [n][2], inlier mask [n]
 int plv_front_match_device(plv_ctx *ctx, const float **d_p1, const float **d_n1, const uint8_t **d_mask, int *n);
 // equalised level-0 image of the current (which = 0) or previous (1) frame
@@ -94,6 +106,8 @@ void plv_tracker_mask_last(plv_ctx *ctx, std::vector<uint8_t> &out);
 // ---- stereo_api.hip
 // plv_ctx_destroy: the ctx's stereo tracker, its pyramids and its database
 void plv_stereo_destroy(plv_ctx *ctx);
+// camera 0's images of a configured stereo tracker (null: none on this context)
+const CamFront *plv_stereo_front0(plv_ctx *ctx);
 // plv_ctx::tracker_kind: PLV_OK unless the other tracker has taken an image on this context (then PLV_E_BADARG, with the error text)
 enum { PLV_TRACKER_NONE = 0, PLV_TRACKER_MONO = 1, PLV_TRACKER_STEREO = 2 };
 int plv_tracker_kind_check(plv_ctx *ctx, int kind, const char *who);

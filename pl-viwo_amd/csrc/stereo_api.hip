@@ -7,6 +7,7 @@
 // the monocular path uses (front_parts.hpp, frontend_kernels.hpp), with the two temporal matchings of a frame in one LK launch
 // (launch_lk_pair) and one wait.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -319,6 +320,11 @@ void plv_stereo_destroy(plv_ctx *ctx) {
   ctx->stereo_state = nullptr;
 }
 
+const CamFront *plv_stereo_front0(plv_ctx *ctx) {
+  Stereo *S = stereo_of(ctx, false);
+  return S && S->configured ? &S->cam[0] : nullptr;
+}
+
 int plv_tracker_kind_check(plv_ctx *ctx, int kind, const char *who) {
   if (ctx->tracker_kind == PLV_TRACKER_NONE || ctx->tracker_kind == kind) return PLV_OK;
   set_last_error("%s: this context has been fed through the %s tracker; the two trackers do not share a context", who,
@@ -506,7 +512,7 @@ int plv_stereo_db_append_measurements(plv_ctx *ctx, uint64_t id, int cam, int n,
 namespace {
 typedef PoolCand<StereoFeature> StereoCand;
 
-// One plv_stereo_update_points call.  The pool mechanics are camera_tracks.hpp's: a candidate holds the two cameras' tracks, and what
+// One plv_stereo_update_points / plv_stereo_try_update call (stereo_points_run).  The pool mechanics are camera_tracks.hpp's: a candidate holds the two cameras' tracks, and what
 // goes back to the database (db_unused) is kept per camera, so that every per-track template serves one camera of a feature.
 struct StereoPointsUpdate {
   plv_ctx *ctx;
@@ -521,6 +527,11 @@ struct StereoPointsUpdate {
   std::vector<StereoCand> pool;
   TrackMap<Track> unused[2];
   std::vector<int> valid_n;
+  // use_imu_res (opt->cpi, plv_stereo_try_update): the distinct times the table serves, listed once for both cameras — the pair shares
+  // dt, a left and a right observation of one frame share one pose — and per pool candidate and camera every observation's index
+  bool cpi_on = false;
+  std::vector<double> cpi_times;
+  std::vector<std::array<std::vector<int>, 2>> pose_idx;
 
   // REF CamHelper.cpp:702-703 / :709-738: db_unused returns to the tracker's database; cleanup_features runs on every call
   int finish(int rc) {
@@ -571,6 +582,15 @@ struct StereoPointsUpdate {
     sort_long_first(pool);  // REF :640, by the observations of both cameras; ties by ascending id
   }
 
+  // REF CamHelper.cpp get_imu_poses (:356-365), per camera: what the table cannot serve returns to its own camera's track
+  void attach_cpi() {
+    cpi_on = true;
+    pose_idx.resize(pool.size());
+    CpiTimes M{*st, *opt->cpi, cpi_times};
+    for (size_t f = 0; f < pool.size(); ++f)
+      for (int q = 1; q >= 0; --q) cpi_attach_track(M, dt, pool[f].id, pool[f].tr.cam[q], unused[q], pose_idx[f][q]);
+  }
+
   // candidates [sel] in the layout of plv_stereo_tracks: camera 1's observations, then camera 0's (the reference's iteration order);
   // valid_only: without the observations that have no bounding clones
   struct Flat {
@@ -578,7 +598,9 @@ struct StereoPointsUpdate {
     std::vector<double> t;
     std::vector<float> uv, uvn;
     std::vector<uint8_t> cam;
+    std::vector<int> pose_of;  // (cpi_on) index into cpi_times
   };
+  CpiStage cpi_stage(const Flat &F) const { return CpiStage{opt->cpi, (int)cpi_times.size(), cpi_times.data(), F.pose_of.data(), nullptr, nullptr}; }
   void flatten(const std::vector<int> &sel, bool valid_only, Flat &F) {
     F.ptr.assign(1, 0);
     for (int f : sel) {
@@ -590,6 +612,7 @@ struct StereoPointsUpdate {
           F.uv.insert(F.uv.end(), tr.uv.begin() + 2 * i, tr.uv.begin() + 2 * i + 2);
           F.uvn.insert(F.uvn.end(), tr.uvn.begin() + 2 * i, tr.uvn.begin() + 2 * i + 2);
           F.cam.push_back((uint8_t)q);
+          if (cpi_on) F.pose_of.push_back(pose_idx[f][q][i]);
         }
       }
       F.ptr.push_back((int)F.t.size());
@@ -605,31 +628,16 @@ struct StereoPointsUpdate {
 };
 }  // namespace
 
-extern "C" {
-
-int plv_stereo_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_update_options *opt, double *dx,
-                             plv_update_result *res, uint64_t *msckf_ids, uint8_t *accepted_out, double *p_out) {
-  const char *who = "plv_stereo_update_points";
-  if (!ctx || !st || !opt || !dx || !res || st->n_clones < 2 || !st->clone_time || opt->max_msckf < 1 || opt->max_obs < 2) {
-    set_last_error("%s: a missing argument, fewer than 2 clones, max_msckf < 1 or max_obs < 2", who);
-    return PLV_E_BADARG;
-  }
-  // ---- every refusal comes before the database, the covariance or the staged batch is touched
-  auto refuse = [who](const char *why) {
-    set_last_error("%s: %s", who, why);
-    return (int)PLV_E_BADARG;
-  };
-  if (opt->max_slam != 0) return refuse("in-state landmarks (max_slam != 0) are not built for the stereo update");
-  if (opt->cpi) return refuse("use_imu_res (plv_update_options::cpi) is not built for the stereo update");
-  if (st->use_imu_cov) return refuse("use_imu_cov is not built for the stereo update");
-  if (ctx->decision_trace) return refuse("the decision trace does not cover the stereo update (plv_decision_trace off first)");
-  Stereo *S = configured(ctx, who);
-  if (!S) return PLV_E_BADARG;
-  TRY(plv_stereo_side_check(who, st, right));
+namespace {
+// plv_stereo_update_points behind its refusals.  try_update (plv_stereo_try_update): opt->cpi is honoured and every feature the
+// reference copies to point_used is recorded (REF CamHelper.cpp:648-699: triangulated, dynamic or not, until the cap ends the loop).
+int stereo_points_run(const char *who, plv_ctx *ctx, Stereo *S, const plv_state_view *st, const plv_camera_side *right, const plv_update_options *opt,
+                      double *dx, plv_update_result *res, uint64_t *msckf_ids, uint8_t *accepted_out, double *p_out, bool try_update) {
   *res = plv_update_result{0, 0, 0, 0, 0, PLV_OK, 0, 0, 0};
   (void)hipSetDevice(ctx->device);
   StereoPointsUpdate U{ctx, S, st, right, opt, dx, res};
   U.take_pool_of_window();
+  if (try_update && opt->cpi) U.attach_cpi();
   const int Fp = (int)U.pool.size();
   if (Fp == 0) return U.finish_early();
   U.valid_n.resize(Fp);
@@ -644,7 +652,7 @@ int plv_stereo_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_c
     }
   }
   // ---- launch 1: every pool candidate triangulated (the reference goes feature by feature until the cap; a feature it never
-  // reaches keeps its observations either way)
+  // reaches keeps its observations either way).  With a CPI table cpi_pose_kernel runs in front of it on the stream.
   std::vector<double> pf(3 * (size_t)Fp, 0.0), err(Fp, 0.0);
   std::vector<uint8_t> ok(Fp, 0);
   if (any) {
@@ -653,14 +661,25 @@ int plv_stereo_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_c
     StereoPointsUpdate::Flat A;
     U.flatten(everyone, false, A);
     const plv_stereo_tracks all = StereoPointsUpdate::view(A, nullptr);
-    const int rc_t = plv_triangulate_stereo(ctx, st, right, &all, &opt->tri, pf.data(), ok.data(), err.data());
+    const CpiStage cs = U.cpi_stage(A);
+    const int rc_t = stereo_triangulate(ctx, st, right, &all, &opt->tri, U.cpi_on ? &cs : nullptr, pf.data(), ok.data(), err.data());
     if (rc_t != PLV_OK) return U.abandon(rc_t);
   }
   // ---- REF :648-699 the selection loop, on the host
   std::vector<int> sel;
   for (int f = 0; f < Fp; ++f) {
     StereoCand &c = U.pool[f];
-    if ((int)sel.size() >= opt->max_msckf || U.valid_n[f] < 2 || !ok[f] || !(err[f] < 3.0)) {
+    if ((int)sel.size() >= opt->max_msckf) {
+      U.back_all(c);
+      continue;
+    }
+    if (try_update && U.valid_n[f] >= 2 && ok[f]) {  // copy_to_db(db_used, feat): dynamic (:677) and MSCKF (:697) features
+      double newest = 0;
+      for (const Track &tr : c.tr.cam)
+        if (!tr.t.empty()) newest = std::max(newest, tr.t.back());
+      (void)plv_point_used_insert(ctx, c.id, &pf[3 * (size_t)f], newest);
+    }
+    if (U.valid_n[f] < 2 || !ok[f] || !(err[f] < 3.0)) {
       U.back_all(c);
       continue;
     }
@@ -668,7 +687,8 @@ int plv_stereo_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_c
   }
   res->n_msckf = (int)sel.size();
   if (sel.empty()) return U.finish_early();
-  // ---- launch 2 + the resident tail: UpdaterCamera::msckf_update on the selected features
+  // ---- launch 2 + the resident tail: UpdaterCamera::msckf_update on the selected features (their CPI poses are the ones launch 1
+  // formed: the batch's index points into the same buffer)
   std::vector<double> feat(3 * sel.size());
   for (size_t q = 0; q < sel.size(); ++q) {
     std::copy(pf.begin() + 3 * (size_t)sel[q], pf.begin() + 3 * (size_t)sel[q] + 3, feat.begin() + 3 * q);
@@ -683,11 +703,12 @@ int plv_stereo_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_c
   StereoPointsUpdate::Flat B;
   U.flatten(sel, true, B);
   const plv_stereo_tracks chosen = StereoPointsUpdate::view(B, feat.data());
+  const CpiStage cs_b = U.cpi_stage(B);
   std::vector<int> cols(ctx->cfg.max_state_dim > 0 ? ctx->cfg.max_state_dim : 1024);
   std::vector<uint8_t> acc(sel.size(), 0);
   int k = 0, n_rows = 0;
   int rc = plv_stereo_jacobian_columns(st, right, &chosen, cols.data(), (int)cols.size(), &k);
-  if (rc == PLV_OK) rc = plv_build_jacobians_stereo_resident(ctx, st, right, &chosen, k, cols.data(), 2 * opt->max_obs);
+  if (rc == PLV_OK) rc = stereo_jacobians_resident(ctx, st, right, &chosen, k, cols.data(), 2 * opt->max_obs, U.cpi_on ? &cs_b : nullptr);
   if (rc == PLV_OK) {
     rc = plv_msckf_update_resident(ctx, st->sigma_pix * st->sigma_pix, opt->chi2_mult, 3.0, acc.data(), &n_rows, dx);
     rc = ekf_returned_false(rc, &res->status, dx, ctx->cov_n);
@@ -711,6 +732,84 @@ int plv_stereo_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_c
     if (!acc[q]) back_valid(sel[q]);
   }
   return U.finish(PLV_OK);
+}
+}  // namespace
+
+extern "C" {
+
+int plv_stereo_update_points(plv_ctx *ctx, const plv_state_view *st, const plv_camera_side *right, const plv_update_options *opt, double *dx,
+                             plv_update_result *res, uint64_t *msckf_ids, uint8_t *accepted_out, double *p_out) {
+  const char *who = "plv_stereo_update_points";
+  if (!ctx || !st || !opt || !dx || !res || st->n_clones < 2 || !st->clone_time || opt->max_msckf < 1 || opt->max_obs < 2) {
+    set_last_error("%s: a missing argument, fewer than 2 clones, max_msckf < 1 or max_obs < 2", who);
+    return PLV_E_BADARG;
+  }
+  // ---- every refusal comes before the database, the covariance or the staged batch is touched
+  auto refuse = [who](const char *why) {
+    set_last_error("%s: %s", who, why);
+    return (int)PLV_E_BADARG;
+  };
+  if (opt->max_slam != 0) return refuse("in-state landmarks (max_slam != 0) are not built for the stereo update");
+  if (opt->cpi) return refuse("use_imu_res (plv_update_options::cpi) is not built for the stereo update");
+  if (st->use_imu_cov) return refuse("use_imu_cov is not built for the stereo update");
+  if (ctx->decision_trace) return refuse("the decision trace does not cover the stereo update (plv_decision_trace off first)");
+  Stereo *S = configured(ctx, who);
+  if (!S) return PLV_E_BADARG;
+  TRY(plv_stereo_side_check(who, st, right));
+  return stereo_points_run(who, ctx, S, st, right, opt, dx, res, msckf_ids, accepted_out, p_out, false);
+}
+
+// UpdaterCamera::try_update for the pair (REF UpdaterCamera.cpp:139-195 with cam_id = sensor_ids.at(0)): the point half over both
+// cameras, the line half on camera 0 — a composition of the calls a caller would make one after the other.
+int plv_stereo_try_update(plv_ctx *ctx, const plv_state_view *st, plv_camera_side *right, plv_try_update *io) {
+  const char *who = "plv_stereo_try_update";
+  if (!ctx || !st || !io || !io->opt_points || !io->dx_points || !io->res_points || (io->n_var > 0 && !io->vars) ||
+      (io->opt_lines && (!io->dx_lines || !io->res_lines)) || st->n_clones < 2 || !st->clone_time || io->opt_points->max_msckf < 1 ||
+      io->opt_points->max_obs < 2) {
+    set_last_error("%s: a missing argument, fewer than 2 clones, max_msckf < 1 or max_obs < 2", who);
+    return PLV_E_BADARG;
+  }
+  // ---- every refusal comes before the databases, the covariance, the variables or the staged batch are touched
+  auto refuse = [who](const char *why) {
+    set_last_error("%s: %s", who, why);
+    return (int)PLV_E_BADARG;
+  };
+  const plv_update_options *op = io->opt_points, *ol = io->opt_lines;
+  if (op->max_slam != 0 || (ol && ol->max_slam != 0)) return refuse("in-state landmarks (max_slam != 0) are not built for the stereo update");
+  if (st->use_imu_cov) return refuse("use_imu_cov is not built for the stereo update");
+  if (ctx->decision_trace) return refuse("the decision trace does not cover the stereo update (plv_decision_trace off first)");
+  Stereo *S = configured(ctx, who);
+  if (!S) return PLV_E_BADARG;
+  TRY(plv_stereo_side_check(who, st, right));
+  if ((op->cpi && !cpi_table_usable(op->cpi)) || (ol && ol->cpi && !cpi_table_usable(ol->cpi)))
+    return refuse("a CPI table (plv_update_options::cpi) with a missing array or times that do not ascend");
+  if (plv_state_vars_check(io->n_var, io->vars, ctx->cov_n) != PLV_OK) {  // (the test plv_state_boxplus makes when dx is applied)
+    set_last_error("%s: a variable of the list has an unknown kind, no values or an index beyond the covariance (%d)", who, ctx->cov_n);
+    return PLV_E_BADARG;
+  }
+  // StateHelper::EKFUpdate's mean update (:156-168); `right` and st's calibration fields are mirrors of the variables, the tracker
+  // undistorts the next pair with the calibrated intrinsics of both cameras
+  auto apply = [&](const plv_update_result &r, const double *dx) {
+    if (r.status != PLV_OK || r.n_accepted < 1 || io->n_var < 1) return (int)PLV_OK;
+    TRY(plv_state_boxplus(io->n_var, io->vars, dx, ctx->cov_n));
+    if (st->intrinsic_state_id >= 0) TRY(plv_set_camera_intrinsics(ctx, st->intrinsics));
+    if (right->intrinsic_state_id >= 0) TRY(plv_stereo_set_intrinsics(ctx, 1, right->intrinsics));
+    return (int)PLV_OK;
+  };
+  int rc = stereo_points_run(who, ctx, S, st, right, op, io->dx_points, io->res_points, io->msckf_ids, io->msckf_accepted, io->p_FinG, true);
+  // REF :148-152: the line pool is formed and triangulated on the state as it is before the point update's correction is applied
+  const int rc_lf = rc == PLV_OK && ol ? plv_camera_get_line_features(ctx, st) : PLV_OK;
+  if (rc == PLV_OK) rc = apply(*io->res_points, io->dx_points);  // (the covariance holds the point update: so does the state)
+  if (rc == PLV_OK) rc = rc_lf;
+  if (rc == PLV_OK && ol) {
+    rc = plv_line_tracker_feed_wait(ctx);
+    io->line_db_size = plv_line_db_size_after_feed(ctx);
+    // camera 0's calibration, on the updated state; point_used is cleaned in there when the window is full (:187-189)
+    if (rc == PLV_OK) rc = plv_camera_update_lines(ctx, st, ol, io->dx_lines, io->res_lines, io->line_ids, io->line_accepted, io->line_FinG, io->line_cap);
+    if (rc == PLV_OK) rc = apply(*io->res_lines, io->dx_lines);
+  }
+  if (rc != PLV_OK && ol) plv_line_pool_discard(ctx);
+  return rc;
 }
 
 }  // extern "C"

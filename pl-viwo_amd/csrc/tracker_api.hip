@@ -1076,6 +1076,25 @@ int plv_point_used_insert(plv_ctx *ctx, uint64_t id, const double *p_FinG, doubl
   return PLV_OK;
 }
 
+int plv_point_used_list(plv_ctx *ctx, int cap, int *n, uint64_t *ids, double *p_FinG, double *newest_obs_time) {
+  if (!ctx || !n || cap < 0) return PLV_E_BADARG;
+  Tracker *T = trk(ctx);
+  std::lock_guard<std::mutex> lk(T->mtx);
+  std::vector<uint64_t> order;
+  order.reserve(T->used.size());
+  for (const auto &kv : T->used) order.push_back(kv.first);
+  std::sort(order.begin(), order.end());
+  *n = (int)order.size();
+  if (*n > cap) return PLV_E_CAPACITY;
+  for (size_t i = 0; i < order.size(); ++i) {
+    const Tracker::UsedPoint &u = T->used[order[i]];
+    if (ids) ids[i] = order[i];
+    if (p_FinG) std::copy(u.p, u.p + 3, p_FinG + 3 * i);
+    if (newest_obs_time) newest_obs_time[i] = u.newest;
+  }
+  return PLV_OK;
+}
+
 }  // extern "C"
 namespace plv {
 // line_api.hip: FeatureDatabase::get_feature(id) on point_used (Triangulated features only)

@@ -6,6 +6,7 @@ sequences replay from the dataset's own file layout the moment it is mounted —
     <root>/sensor_data/encoder.csv       t [ns], left count, right count
     <root>/sensor_data/stereo_stamp.csv  t [ns] of every stereo pair (optional: else the file stems)
     <root>/image/stereo_left/<t>.png     1280 x 560, 8-bit Bayer (RGGB)
+    <root>/image/stereo_right/<t>.png    the right camera of the pair (optional): the frame of the same stamp is the partner
     <root>/calibration/EncoderParameter.txt   resolution, wheel diameters, wheel base (optional: defaults below)
 
 What the reference's subscribers do with the corresponding messages (REF: PL-VIWO/src/core/ROSHelper.cpp:151-216):
@@ -124,6 +125,13 @@ class KaistDataset:
                 path = os.path.join(idir, f"{s}.png")
                 if os.path.exists(path):
                     self.frames.append((s * 1e-9, path))
+        # the right camera: image/stereo_right/<t>.png beside stereo_left, matched by stamp (replay.pair_frames)
+        from .replay import pair_frames
+        self.right_dir = os.path.join(root, "image", "stereo_right")
+        right = []
+        if use_cam and os.path.isdir(self.right_dir):
+            right = [(int(os.path.splitext(n)[0]) * 1e-9, os.path.join(self.right_dir, n)) for n in sorted(os.listdir(self.right_dir)) if n.endswith(".png")]
+        pair_frames(self, right)
         msgs = [(t, IMU, i) for i, t in enumerate(self.imu[:, 0])] + [(t, WHEEL, i) for i, t in enumerate(self.wheel[:, 0])] + \
                [(t, CAM, i) for i, (t, _) in enumerate(self.frames)]
         msgs.sort(key=lambda m: (m[0], m[1]))
@@ -132,16 +140,15 @@ class KaistDataset:
     def t_begin(self):
         return self.msgs[0][0]
 
-    def image(self, i):
-        from .replay import read_image
-        return bayer_rg_to_grey(read_image(self.frames[i][1]))
+    def image(self, i, cam=0):
+        return bayer_rg_to_grey(self.raw_image(i, cam))
 
     encoding = "bayer_rggb8"    # what raw_image delivers, as a ROS encoding string (the library converts it on the device)
 
-    def raw_image(self, i):
-        """the mosaic as read: what the camera's sensor_msgs/Image carries"""
+    def raw_image(self, i, cam=0):
+        """the mosaic as read: what the camera's sensor_msgs/Image carries (cam = 1: frame i's partner of the right camera)"""
         from .replay import read_image
-        return read_image(self.frames[i][1])
+        return read_image(self.frames[i][1] if cam == 0 else self.right_of[i])
 
     to_grey = staticmethod(bayer_rg_to_grey)    # the host yardstick of that conversion: image(i) = to_grey(raw_image(i))
 

@@ -12,8 +12,11 @@ Dataset layout (`sys.path_bag` names the directory):
     wheel.csv            t, m1, m2                          (the two readings of the configured wheel type; optional)
     cam0/data.csv        t, file name                       (optional: without it the file stem is the time stamp)
     cam0/data/*          8-bit grey images: .pgm (P5), .png (grey / RGB, not interlaced) or .npy
-A directory in the EuRoC MAV (ASL) layout is read as it is: mav0/imu0/data.csv, mav0/cam0/data.csv + mav0/cam0/data/*.png; a KAIST
-Complex Urban raw directory (sensor_data/xsens_imu.csv, encoder.csv, image/stereo_left) through kaist.KaistDataset (open_dataset).
+    cam1/data.csv, cam1/data/*   the right camera of a stereo pair, laid out like cam0 (optional): a left and a right frame with one
+                         time stamp are a pair; a frame without its partner is skipped by a stereo replay and counted
+A directory in the EuRoC MAV (ASL) layout is read as it is: mav0/imu0/data.csv, mav0/cam0/data.csv + mav0/cam0/data/*.png (and
+mav0/cam1); a KAIST Complex Urban raw directory (sensor_data/xsens_imu.csv, encoder.csv, image/stereo_left, image/stereo_right)
+through kaist.KaistDataset (open_dataset).
 """
 import os
 import struct
@@ -23,6 +26,7 @@ import zlib
 import numpy as np
 
 from . import traj_format, traj_header
+from .options import OptionsError
 from .system import SystemManager
 
 IMU, WHEEL, CAM = 0, 1, 2
@@ -143,37 +147,44 @@ def _stamp(s):
 class Dataset:
     """The time-ordered message list of a dataset directory (the rosbag::View of run_bag.cpp)."""
 
-    def __init__(self, root, cam_dir="cam0", use_wheel=True, use_cam=True):
+    def __init__(self, root, cam_dir="cam0", use_wheel=True, use_cam=True, right_dir="cam1"):
         self.root = root
         imu_path = os.path.join(root, "imu.csv")
         if not os.path.exists(imu_path) and os.path.isdir(os.path.join(root, "mav0")):   # EuRoC MAV (ASL) layout
             imu_path = os.path.join(root, "mav0", "imu0", "data.csv")
-            cam_dir = os.path.join("mav0", cam_dir)
+            cam_dir, right_dir = os.path.join("mav0", cam_dir), os.path.join("mav0", right_dir)
         imu = _read_csv(imu_path, 7)
         self.imu = np.array([[_stamp(r[0])] + [float(x) for x in r[1:]] for r in imu])
         self.wheel = np.zeros((0, 3))
         wp = os.path.join(root, "wheel.csv")
         if use_wheel and os.path.exists(wp):
             self.wheel = np.array([[_stamp(r[0]), float(r[1]), float(r[2])] for r in _read_csv(wp, 3)])
-        self.frames = []
-        cdir = os.path.join(root, cam_dir)
-        if use_cam and os.path.isdir(cdir):
-            listing = os.path.join(cdir, "data.csv")
-            if os.path.exists(listing):
-                self.frames = [(_stamp(r[0]), os.path.join(cdir, "data", r[1])) for r in _read_csv(listing, 2)]
-            else:
-                for name in sorted(os.listdir(os.path.join(cdir, "data"))):
-                    self.frames.append((_stamp(os.path.splitext(name)[0]), os.path.join(cdir, "data", name)))
+        self.frames = self._frames_of(os.path.join(root, cam_dir)) if use_cam else []
+        # the right camera of a stereo pair, matched to the left frames by time stamp
+        self.right_dir = os.path.join(root, right_dir)
+        right = self._frames_of(self.right_dir) if use_cam else []
+        pair_frames(self, right)
         msgs = [(t, IMU, i) for i, t in enumerate(self.imu[:, 0])] + [(t, WHEEL, i) for i, t in enumerate(self.wheel[:, 0])] + \
                [(t, CAM, i) for i, (t, _) in enumerate(self.frames)]
         msgs.sort(key=lambda m: (m[0], m[1]))
         self.msgs = msgs
 
+    @staticmethod
+    def _frames_of(cdir):
+        """[(stamp, path)] of one camera directory (data.csv, or the file stems as stamps); empty without the directory"""
+        if not os.path.isdir(cdir):
+            return []
+        listing = os.path.join(cdir, "data.csv")
+        if os.path.exists(listing):
+            return [(_stamp(r[0]), os.path.join(cdir, "data", r[1])) for r in _read_csv(listing, 2)]
+        return [(_stamp(os.path.splitext(name)[0]), os.path.join(cdir, "data", name)) for name in sorted(os.listdir(os.path.join(cdir, "data")))]
+
     def t_begin(self):
         return self.msgs[0][0]
 
-    def image(self, i):
-        return read_image(self.frames[i][1])
+    def image(self, i, cam=0):
+        """frame i of the left camera (cam = 0), or its partner of the right camera (cam = 1)"""
+        return read_image(self.frames[i][1] if cam == 0 else self.right_of[i])
 
     encoding = "mono8"      # what raw_image delivers (a ROS encoding string): these layouts hold grey images
     raw_image = image
@@ -182,6 +193,16 @@ class Dataset:
     def to_grey(raw):
         """raw_image -> the grey image, on the host (image(i) = to_grey(raw_image(i)))"""
         return raw
+
+
+def pair_frames(ds, right):
+    """Matches the right camera's frames [(stamp, path)] to ds.frames by time stamp: ds.has_right (there is a right camera),
+    ds.right_of [len(frames)] (the partner's path or None), ds.right_unpaired (right frames no left frame has the stamp of)"""
+    by_stamp = {t: p for t, p in right}
+    ds.has_right = len(right) > 0
+    ds.right_of = [by_stamp.get(t) for t, _ in ds.frames]
+    left_stamps = {t for t, _ in ds.frames}
+    ds.right_unpaired = sum(1 for t, _ in right if t not in left_stamps)
 
 
 def open_dataset(root, use_wheel=True, use_cam=True):
@@ -276,6 +297,9 @@ def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_
     (Dataset.encoding, e.g. the Bayer mosaics of a KAIST directory) hands them over as they are read and the library converts them
     on the device; host_images: the dataset converts them on the host (Dataset.image), as a context without the conversion has to."""
     ds = dataset if dataset is not None else open_dataset(op.sys.path_bag, use_wheel=op.est.wheel.enabled, use_cam=op.est.cam.enabled)
+    stereo = bool(op.est.cam.enabled and op.est.cam.use_stereo and op.est.cam.max_n == 2)
+    if stereo and not getattr(ds, "has_right", False):
+        raise OptionsError(f"replay: the configuration has a stereo pair, the dataset has no right camera images ({getattr(ds, 'right_dir', 'cam1')})")
     sys = SystemManager(op, device=device, max_obs=max_obs, **system_kw)
     path = trajectory_path if trajectory_path is not None else (op.sys.path_trajectory if op.sys.save_trajectory else None)
     log = TrajectoryLogger(path) if path else None
@@ -284,6 +308,8 @@ def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_
     mask = None
     if op.est.cam.enabled and op.est.cam.use_mask.get(0):
         mask = read_image(op.est.cam.mask_path[0])
+    mask_right = read_image(op.est.cam.mask_path[1]) if stereo and op.est.cam.use_mask.get(1) else None
+    pairs_skipped = ds.right_unpaired if stereo else 0
     times, poses = [], []
     encoding = getattr(ds, "encoding", "mono8")
     has_raw = hasattr(ds, "raw_image") and hasattr(ds, "to_grey")
@@ -302,6 +328,21 @@ def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_
                 times.append(st.time), poses.append(np.concatenate([np.array(st.imu.p), np.array(st.imu.q)]))
                 if log:
                     log.save(sys)
+        elif kind == CAM and stereo:
+            if ds.right_of[i] is None:       # a frame without its partner
+                pairs_skipped += 1
+                continue
+            left, right = (ds.raw_image(i), ds.raw_image(i, 1)) if has_raw else (ds.image(i), ds.image(i, 1))
+            on_device = not host_images and encoding != "mono8" and has_raw        # (plv_tracker_feed_stereo converts the pair itself)
+            if has_raw and not on_device:
+                left, right = ds.to_grey(left), ds.to_grey(right)
+            t0 = time.perf_counter()
+            sys.feed_measurement_stereo(t, left, right, mask, mask_right, encoding=encoding if on_device else "mono8")
+            cam_wall, cam_frames = cam_wall + time.perf_counter() - t0, cam_frames + 1
+            if after_camera is not None:
+                t0 = time.perf_counter()
+                after_camera(sys, cam_frames - 1, t)
+                after_wall += time.perf_counter() - t0
         elif kind == CAM:
             raw = ds.raw_image(i) if has_raw else None       # (the file read is not the camera side's time)
             t0 = time.perf_counter()
@@ -324,7 +365,8 @@ def replay(op, dataset=None, trajectory_path=None, device=0, progress=None, max_
     stats = dict(sys.stats)
     stats.update(distance_m=sys.distance, time_s={k: round(v, 4) for k, v in sys.tc.total.items()}, initialized=sys.state.initialized,
                  startup_time=sys.state.startup_time, end_time=sys.state.time, n_state=sys.state.n, clone_freq=op.est.clone_freq,
-                 image_route="device" if device_images else "host", time_camera_s=round(cam_wall, 6), camera_messages=cam_frames)
+                 image_route="device" if device_images or (stereo and not host_images and encoding != "mono8" and has_raw) else "host",
+                 time_camera_s=round(cam_wall, 6), camera_messages=cam_frames, stereo=stereo, pairs_skipped=pairs_skipped)
     if after_camera is not None:
         stats["time_after_camera_s"] = round(after_wall, 6)
     sys.close()

@@ -8,9 +8,9 @@ REF: PL-VIWO/src/core/SystemManager.cpp:55-135 (feed_measurement_imu / _camera /
      PL-VIWO/src/update/cam/UpdaterCamera.cpp:77-195; PL-VIWO/src/update/wheel/UpdaterWheel.cpp:21-139.
 
 The camera path follows the intended flow feed_measurement -> try_update (as published, SystemManager.cpp:107-127 returns
-before try_update once the filter is initialised).  Scope of this driver: one camera (monocular), MSCKF points and lines
+before try_update once the filter is initialised).  Scope of this driver: one camera, or one stereo pair (points on both cameras, lines on camera 0: SystemManager), MSCKF points and lines
 (in-state SLAM landmarks in either representation the reference accepts when the context has the landmark passes, GLOBAL_3D otherwise;
-the shipped configuration has cam.max_slam: 0), wheel optional; `use_imu_res` takes the poses of the camera update from the CPI records of plv_propagate; GPS / LiDAR / stereo /
+the shipped configuration has cam.max_slam: 0), wheel optional; `use_imu_res` takes the poses of the camera update from the CPI records of plv_propagate; GPS / LiDAR /
 simulation are outside SURVEY §8.  With `est.zupt.enabled` a camera frame first asks the zero-velocity updater (REF: SystemManager.cpp:50-52,
 116-121; _zupt_try_update) and leaves its camera update out when that one applied.
 """
@@ -21,7 +21,7 @@ import time as _time
 
 import numpy as np
 
-from . import BoxPlus, Landmarks, PlvStateView, jpl_left_update, landmark_from_xyz, landmark_xyz
+from . import BoxPlus, CameraSide, Landmarks, PlvCameraSide, PlvStateView, jpl_left_update, landmark_from_xyz, landmark_xyz
 from . import (Context, CpiTable, IwInitializer, PlvError, PlvImuState, PlvWheelOptions, PlvWheelState, PlvZuptOptions, StateView, Tracks, WHEEL_TYPES, default_config,
                imu_noise, init_imu_static, next_clone_time, reset_cpi, select_imu_readings, select_wheel_data)
 from .options import OptionsError
@@ -173,24 +173,29 @@ class State:
         self.est_a, self.est_A = Stat(), Stat()
         cur = 15                    # State.cpp:27-32: the IMU first
         self.cam_ext = self.cam_intr = self.cam_dt = None
+        self.cam_ext1 = self.cam_intr1 = None      # camera 1 of a stereo pair; the pair has ONE time offset, cam_dt (State.cpp:102-103)
         prior = []                  # (id, values on the diagonal)
-        if e.cam.enabled:           # set_camera_state :58-112: extrinsic, intrinsic, time offset
+        if e.cam.enabled:           # set_camera_state :58-112: per camera extrinsic, intrinsic, time offset
             c = e.cam
-            self.cam_ext = Pose(c.extrinsics[0][:4], c.extrinsics[0][4:])
-            self.cam_intr, self.cam_dt = Vec(c.intrinsics[0]), Vec([c.dt[0]])
-            if c.do_calib_ext:
-                self.cam_ext.id = cur
-                prior.append((cur, [c.init_cov_ex_o] * 3 + [c.init_cov_ex_p] * 3))
-                cur += 6
-            if c.do_calib_int:
-                self.cam_intr.id = cur
-                r2 = (math.sqrt(c.init_cov_in_r) / 10.0) ** 2 if c.init_cov_in_r > 1e-5 else c.init_cov_in_r   # State.cpp:245-249
-                prior.append((cur, [c.init_cov_in_k] * 2 + [c.init_cov_in_c] * 2 + [c.init_cov_in_r] * 2 + [r2] * 2))
-                cur += 8
-            if c.do_calib_dt:
-                self.cam_dt.id = cur
-                prior.append((cur, [c.init_cov_dt]))
-                cur += 1
+            r2 = (math.sqrt(c.init_cov_in_r) / 10.0) ** 2 if c.init_cov_in_r > 1e-5 else c.init_cov_in_r   # State.cpp:245-249
+            for i in range(2 if c.max_n == 2 and c.use_stereo else 1):
+                ext, intr = Pose(c.extrinsics[i][:4], c.extrinsics[i][4:]), Vec(c.intrinsics[i])
+                if c.do_calib_ext:
+                    ext.id = cur
+                    prior.append((cur, [c.init_cov_ex_o] * 3 + [c.init_cov_ex_p] * 3))
+                    cur += 6
+                if c.do_calib_int:
+                    intr.id = cur
+                    prior.append((cur, [c.init_cov_in_k] * 2 + [c.init_cov_in_c] * 2 + [c.init_cov_in_r] * 2 + [r2] * 2))
+                    cur += 8
+                if i == 1:
+                    self.cam_ext1, self.cam_intr1 = ext, intr
+                    continue
+                self.cam_ext, self.cam_intr, self.cam_dt = ext, intr, Vec([c.dt[0]])
+                if c.do_calib_dt:
+                    self.cam_dt.id = cur
+                    prior.append((cur, [c.init_cov_dt]))
+                    cur += 1
         self.wheel_ext = self.wheel_intr = self.wheel_dt = None
         if e.wheel.enabled:         # set_wheel_state :151-190: time offset, extrinsic, intrinsic
             w = e.wheel
@@ -257,14 +262,21 @@ class State:
             m_R, m_p, m_K, m_dt = (base + getattr(PlvStateView, f).offset for f in ("R_ItoC", "p_IinC", "intrinsics", "cam_dt"))
         else:
             m_R = m_p = m_K = m_dt = None
+        m_R1 = m_p1 = m_K1 = None
+        if self.cam_ext1 is not None:      # camera 1 of the pair: a plv_camera_side whose fields are mirrors, like the view's
+            models = getattr(type(self.ctx), "CAMERA_MODELS", ("radtan", "equidistant"))
+            side = w["side"] = CameraSide(self.cam_ext1.Rot(), self.cam_ext1.p, self.cam_intr1.v, models.index(c.distortion_model[1]),
+                                          self.cam_ext1.id, self.cam_intr1.id)
+            base1 = ctypes.addressof(side.c)
+            m_R1, m_p1, m_K1 = (base1 + getattr(PlvCameraSide, f).offset for f in ("R_ItoC", "p_IinC", "intrinsics"))
         x = np.frombuffer(self.imu, dtype=np.float64)      # q (4), p, v, bg, ba (3 each), then the first estimates
         # (row n of the window arrays is the IMU pose when it closes the clone list, view(): kept current as well)
         ent = [("quat", 0, x[0:4], w["R"][n], None), ("vec", 3, x[4:7], None, w["p"][n]), ("vec", 6, x[7:16], None, None)]
-        for var, mr, mp in ((self.cam_ext, m_R, m_p), (self.wheel_ext, None, None)):
+        for var, mr, mp in ((self.cam_ext, m_R, m_p), (self.cam_ext1, m_R1, m_p1), (self.wheel_ext, None, None)):
             if var is not None and var.id >= 0:
                 var.Rot()
                 ent += [("quat", var.id, var.q, var._R.reshape(9), mr), ("vec", var.id + 3, var.p, None, mp)]
-        for var, mv in ((self.cam_intr, m_K), (self.cam_dt, m_dt), (self.wheel_dt, None), (self.wheel_intr, None)):
+        for var, mv in ((self.cam_intr, m_K), (self.cam_intr1, m_K1), (self.cam_dt, m_dt), (self.wheel_dt, None), (self.wheel_intr, None)):
             if var is not None and var.id >= 0:
                 ent.append(("vec", var.id, var.v, None, mv))
         for i in range(n):
@@ -314,6 +326,10 @@ class State:
         v.intr_ori_cov, v.intr_pos_cov = oc, pc        # (the calibration fields are kept current by apply())
         return sv
 
+    def side(self):
+        """The plv_camera_side of camera 1 (a stereo pair), current under apply() like the view"""
+        return self._window_arrays()["side"]
+
     def cpi_table(self):
         """State::cpis as the plv_cpi_table of plv_cpi_poses / plv_update_options::cpi."""
         ts = sorted(self.cpis)
@@ -332,6 +348,8 @@ class State:
             lm.value = lm.value + dx[lm.id:lm.id + 3]      # Landmark::update: in the representation's coordinates
         if self.cam_intr is not None and self.op.est.cam.do_calib_int:
             self.ctx.set_camera_intrinsics(self.cam_intr.v)     # StateHelper.cpp:163-168
+            if self.cam_intr1 is not None:
+                self.ctx.stereo_set_intrinsics(1, self.cam_intr1.v)
 
     # ---- StateHelper::augment_clone / marginalize_old_clone
     def augment_clone(self):
@@ -419,7 +437,14 @@ class TimeChecker:
 
 
 class SystemManager:
-    """viw::SystemManager for IMU + one camera (+ wheel)."""
+    """viw::SystemManager for IMU + one camera or one stereo pair (+ wheel).
+
+    A stereo pair (cam.max_n: 2, use_stereo: true, stereo_pair: [0, 1]) is fed through feed_measurement_stereo: points on both
+    cameras, lines on camera 0 (DESIGN.md "Stereo through the driver"), the whole of try_update through Context.stereo_try_update.
+    On a stereo configuration the constructor raises OptionsError for: more than one pair or cam.max_n: 2 without use_stereo
+    ("one stereo pair"), cam.max_slam > 0 ("max_slam"), cam.downsample ("downsample"), est.use_imu_cov ("use_imu_cov"), an enabled
+    zero-velocity updater ("zero-velocity"), decisions is not None ("decision trace"), line_map=True ("line map"), a context
+    factory without stereo_try_update ("stereo_try_update"); get_track_img raises it too ("track image")."""
 
     one_call_frame = os.environ.get("PLV_ONE_CALL", "2") == "2"
     one_call_update = True      # try_update through plv_camera_try_update (False: plv_camera_update_points / _lines with the dx applied here)
@@ -436,14 +461,30 @@ class SystemManager:
         comparison of two runs decision by decision (tests/decision_trace.py)."""
         self.decisions = decisions
         e = op.est
-        if e.cam.enabled and e.cam.max_n != 1:
-            raise OptionsError("replay driver: one camera (cam.max_n: 1, use_stereo: false)")
+        self.stereo = bool(e.cam.enabled and e.cam.max_n == 2 and e.cam.use_stereo and e.cam.stereo_pairs.get(0) == 1)
+        if e.cam.enabled and e.cam.max_n != 1 and not self.stereo:
+            raise OptionsError("replay driver: one camera (cam.max_n: 1) or one stereo pair (cam.max_n: 2, use_stereo: true, stereo_pair: [0, 1])")
+        if self.stereo:
+            refused = {"cam.max_slam > 0: in-state landmarks are not built for a stereo pair (max_slam: 0)": e.cam.max_slam > 0,
+                       "cam.downsample is not built for a stereo pair": bool(e.cam.downsample),
+                       "est.use_imu_cov is not built for a stereo pair": bool(e.use_imu_cov),
+                       "the zero-velocity updater (config_zupt, zupt.enabled) is not built for a stereo pair": bool(e.zupt.enabled),
+                       "the decision trace (decisions=) does not cover a stereo pair": decisions is not None,
+                       "the line map (line_map=True) is not built for a stereo pair": bool(line_map),
+                       "this context factory has no stereo_try_update": not hasattr(context_factory or Context, "stereo_try_update")}
+            for why, hit in refused.items():
+                if hit:
+                    raise OptionsError("replay driver, stereo: " + why)
+            if list(e.cam.wh[1]) != list(e.cam.wh[0]):
+                raise OptionsError(f"replay driver, stereo: both cameras of the pair have one resolution (cam0 {e.cam.wh[0]}, cam1 {e.cam.wh[1]})")
         if e.cam.enabled and e.cam.max_slam != 0 and e.cam.feat_rep != 0 and not (self.slam_pass and hasattr(context_factory or Context, "LANDMARK_REPS")):
             raise OptionsError("replay driver: in-state landmarks (cam.max_slam > 0) are driven in the GLOBAL_3D representation only")
         cam_model = e.cam.distortion_model[0] if e.cam.enabled else "radtan"
-        if cam_model != "radtan" and cam_model not in getattr(context_factory or Context, "CAMERA_MODELS", ()):
-            raise OptionsError(f"camera model {cam_model!r}: this context builds the radtan model only" if cam_model == "equidistant"
-                               else f"camera model {cam_model!r}: the models built are radtan and equidistant")
+        for cam_model in ([cam_model, e.cam.distortion_model[1]] if self.stereo else [cam_model]):
+            if cam_model != "radtan" and cam_model not in getattr(context_factory or Context, "CAMERA_MODELS", ()):
+                raise OptionsError(f"camera model {cam_model!r}: this context builds the radtan model only" if cam_model == "equidistant"
+                                   else f"camera model {cam_model!r}: the models built are radtan and equidistant")
+        cam_model = e.cam.distortion_model[0] if e.cam.enabled else "radtan"
         if e.use_imu_cov and not e.use_pol_cov and not e.use_imu_res:
             # CamHelper.cpp:217-224 reads state->cpis.at(tm + dt), a record that only get_interpolated_pose_imu creates (use_imu_res)
             raise OptionsError("est.use_imu_cov needs est.use_imu_res (the CPI records behind the observation poses)")
@@ -466,6 +507,9 @@ class SystemManager:
         self.ctx = (context_factory or Context)(cfg)
         if cam_model != "radtan":
             self.ctx.set_camera_model(cam_model)          # State.cpp:74-80 (CamEqui)
+        if self.stereo:      # camera 1's intrinsics and model (camera 0's are the context's)
+            models = getattr(type(self.ctx), "CAMERA_MODELS", ("radtan", "equidistant"))
+            self.ctx.stereo_configure(e.cam.intrinsics[1], models.index(e.cam.distortion_model[1]))
         import os
         if os.environ.get("PLV_AHEAD") and hasattr(self.ctx, "tracker_detect_ahead"):
             self.ctx.tracker_detect_ahead(int(os.environ["PLV_AHEAD"]))
@@ -485,7 +529,7 @@ class SystemManager:
         # UpdaterCamera
         self.cam_t_hist = []
         self.use_lines = bool(e.cam.enabled and e.cam.use_lines)
-        if self.use_lines and hasattr(self.ctx, "line_prefetch_mode"):
+        if self.use_lines and hasattr(self.ctx, "line_prefetch_mode") and not self.stereo:     # (the pair feed starts no detection ahead of time)
             self.ctx.line_prefetch_mode(True)     # the tracker feed detects the frame's lines while the device tracks the points
         # UpdaterWheel
         self.whl = SampleBuffer(3)   # t, m1, m2
@@ -544,7 +588,7 @@ class SystemManager:
         if self.op.est.cam.enabled and len(self.cam_t_hist) > 1:
             cam_hz = (len(self.cam_t_hist) - 1) / (self.cam_t_hist[-1] - self.cam_t_hist[0])
             if self.last_cam_delete_t + 100.0 / cam_hz < old:
-                self.ctx.db_cleanup_measurements(old)
+                (self.ctx.stereo_db_cleanup_measurements if self.stereo else self.ctx.db_cleanup_measurements)(old)
                 self.last_cam_delete_t = old
         if self.op.est.wheel.enabled:
             self.whl.drop_before(old)
@@ -785,11 +829,51 @@ class SystemManager:
             self.tc.dong("CAM")
         self._join_lines()
 
+    def feed_measurement_stereo(self, t, left, right, mask_left=None, mask_right=None, encoding="mono8"):
+        """UpdaterCamera::feed_measurement + try_update for a stereo pair (REF: UpdaterCamera.cpp:77-195 with two images; TrackKLT::
+        feed_stereo, TrackLSD::feed_monocular on image 0): the pair through the stereo tracker, vanishing points and the line feed from
+        camera 0, then the whole of try_update in one library call (Context.stereo_try_update) — with the CPI table under use_imu_res."""
+        e, st = self.op.est, self.state
+        if not e.cam.enabled:
+            return
+        if not self.stereo:
+            raise OptionsError("feed_measurement_stereo: the configuration has no stereo pair (cam.max_n: 2, use_stereo: true, stereo_pair: [0, 1])")
+        if st.initialized:
+            self.tc.ding("CAM")
+        if len(self.cam_t_hist) > 100:
+            self.cam_t_hist.pop(0)
+        self.cam_t_hist.append(float(t))
+        self.tc.ding("[Time-Cam] feed measurement: points")
+        self.ctx.tracker_feed_stereo(t, left, right, encoding=encoding, mask_left=mask_left, mask_right=mask_right)
+        self.tc.dong("[Time-Cam] feed measurement: points")
+        if self.use_lines:
+            self.tc.ding("[Time-Cam] feed measurement: lines")
+            self.ctx.line_tracker_feed(t, self.ctx.vanishing_points(st.cam_ext.Rot(), st.cam_intr.v))
+            self.stats["lines_tracked"] += self.ctx.line_db_size()
+            self.tc.dong("[Time-Cam] feed measurement: lines")
+        self.stats["frames"] += 1
+        if not st.initialized:
+            return
+        args = self._try_update_args()
+        if args is not None:
+            pk, kw, max_msckf = args
+            label = "[Time-Cam] get features + MSCKF update + LINE update" if self.use_lines else "[Time-Cam] get features + MSCKF update"
+            self.tc.ding(label)
+            sv = st.view()
+            out, lo, _ = self.ctx.stereo_try_update(sv, st.side(), st._window_arrays()["plus"], st.n, max_msckf, self.max_obs, lines=self.use_lines, **pk, **kw)
+            self.tc.dong(label)
+            self._count_points(out)
+            if lo is not None:
+                self._count_lines(lo)
+        self.tc.dong("CAM")
+
     def get_track_img(self, layers="history"):
         """UpdaterCamera::get_track_img (REF: UpdaterCamera.cpp:486-500): the track picture of the newest camera image with the
         in-state landmarks highlighted, drawn on the device (Context.track_image).  layers: PLV_VIZ_* bits or layer names ("history",
         "active", "lines", "mask").  Returns (rgb [H, W, 3] u8, overlay): the overlay text ("init" until the filter is initialised, else
         "": the reference then writes "CAM:0") is the caller's to draw.  Read-only, and called by nothing in the frame path."""
+        if self.stereo:
+            raise OptionsError("replay driver, stereo: the track image is not built for a stereo pair")
         overlay = "" if self.state.initialized else "init"
         return self.ctx.track_image(layers, highlighted=list(self.state.slam)), overlay
 

@@ -8,6 +8,7 @@
     python tools/replay.py --synthetic 12 --track-images DIR [--track-image-every 5] [--track-image-layers history,lines,mask]
                                                                      # the track picture of the chosen frames as DIR/<frame>.ppm
     python tools/replay.py --synthetic 12 --map map.ply              # the map of the whole replay: MSCKF points, landmarks, 3-D line segments
+    python tools/replay.py --synthetic 12 --stereo [--workers 8]     # renders a stereo pair (tests/synth_stereo_dataset.py) and replays it
 """
 import argparse
 import importlib
@@ -32,6 +33,9 @@ def main():
     ap.add_argument("--rpe", help="comma-separated segment lengths in metres: relative pose error per length (ov_eval's calculate_rpe)")
     ap.add_argument("--nees", action="store_true", help="NEES of the logged pose covariance against the ground truth (calculate_nees)")
     ap.add_argument("--synthetic", type=float, default=0.0, help="seconds of the synthetic dataset to render and replay")
+    ap.add_argument("--stereo", action="store_true", help="with --synthetic: a second camera 0.5 m to the right of the first, replayed as a stereo pair")
+    ap.add_argument("--workers", type=int, default=1, help="with --synthetic: processes that render the images")
+    ap.add_argument("--imu-res", action="store_true", help="override est.use_imu_res: observation poses from the preintegrated IMU records")
     ap.add_argument("--no-wheel", action="store_true")
     ap.add_argument("--no-lines", action="store_true")
     ap.add_argument("--keep", help="directory to keep the synthetic dataset in")
@@ -59,7 +63,9 @@ def main():
         import synth_dataset as sd
         tmp = a.keep or tempfile.mkdtemp(prefix="plv_synth_")
         t0 = time.time()
-        sd.make_dataset(tmp, a.synthetic, log=lambda s: print("  [render]", s, flush=True))
+        if a.stereo:
+            import synth_stereo_dataset as sd      # (the same generator for the left camera, the right one beside it)
+        sd.make_dataset(tmp, a.synthetic, workers=max(1, a.workers), log=lambda s: print("  [render]", s, flush=True))
         a.config = sd.write_config(os.path.join(tmp, "config"), tmp, os.path.join(tmp, "out", "traj.txt"), use_wheel=not a.no_wheel)
         a.gt = os.path.join(tmp, "gt.txt")
         print(f"synthetic dataset in {tmp} ({time.time() - t0:.1f} s)", flush=True)
@@ -68,6 +74,8 @@ def main():
         op.sys.path_bag = a.dataset
     if a.no_lines:
         op.est.cam.use_lines = False
+    if a.imu_res:
+        op.est.use_imu_res = True
     if a.max_slam is not None:
         op.est.cam.max_slam = a.max_slam
     if a.feat_rep:
@@ -93,10 +101,14 @@ def main():
             the_map.after_camera(system, frame, t)
             if picture is not None:
                 picture(system, frame, t)
-    t0 = time.time()
+    t0, c0 = time.time(), pkg.counters()
     stats, times, poses = rp.replay(op, host_images=a.host_images, after_camera=after_camera, **system_kw, progress=lambda s, t: print(f"  t={t:8.3f}  clones {s.stats['clones']}  cam accepted "
                                                                     f"{s.stats['cam_accepted']}/{s.stats['cam_features']}  wheel {s.stats['wheel_accepted']}  zupt {s.stats['zupt_updates']}", flush=True))
     res = dict(config=a.config, wall_s=round(time.time() - t0, 2), stats=stats, poses_logged=len(times), trajectory=op.sys.path_trajectory)
+    c1, frames = pkg.counters(), max(1, stats["camera_messages"])
+    # what the whole replay submitted (plv_counters), per camera message: propagation and wheel updates between the frames included
+    res["per_camera_message"] = dict(time_camera_s=stats["time_camera_s"] / frames, launches=(c1["launches"] - c0["launches"]) / frames,
+                                     synchronisations=(c1["syncs"] - c0["syncs"]) / frames, bytes_copied=(c1["copy_bytes"] - c0["copy_bytes"]) / frames)
     if a.track_images:
         res["track_images_written"] = len(written)
     if the_map is not None:
