@@ -421,7 +421,13 @@ int plv_db_remove(plv_ctx *ctx, const uint64_t *ids, int n);
  * (plv_camera_update_*, plv_camera_try_update) read the monocular database only; the stereo database is consumed by
  * plv_stereo_update_points ("The stereo point update" below).
  * Every call below returns PLV_E_BADARG with a plv_last_error text for an argument it refuses and then leaves the stereo tracker,
- * both cameras' pyramids and the database as they were. */
+ * both cameras' pyramids and the database as they were.
+ * Models.  Each camera has its own: camera 0's is plv_set_camera_model's (before or after this call), camera 1's is model_right
+ * (PLV_CAM_RADTAN or PLV_CAM_EQUIDISTANT; anything else is refused and the configured pair stays).  All four pairings (camera 0,
+ * camera 1) — radtan-radtan, radtan-equidistant, equidistant-radtan, equidistant-equidistant — are held: the feed by
+ * tests/test_gpu_stereo_tracker.py (lists, stamps and pixels to the restatement's bits, an equidistant camera's normalised
+ * coordinates to 1 ulp), the triangulation, the Jacobians and both updates by tests/test_gpu_stereo_update.py and
+ * tests/test_gpu_stereo_try_update.py, a drive with both cameras equidistant by tests/test_gpu_stereo_replay.py. */
 int plv_stereo_configure(plv_ctx *ctx, const double *K8_right, int model_right);
 /* the intrinsics camera `cam` (0, 1) tracks with from the next pair on (the reference tracks with the state's estimate when it
  * calibrates them: an adapter refreshes both per frame); cam 0 is plv_set_camera_intrinsics */

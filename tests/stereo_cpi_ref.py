@@ -47,13 +47,13 @@ def table(pkg, cp):
     return pkg.CpiTable(cp["t"], cp["clone_t"], cp["R"], cp["alpha"], cp["v"], gravity=cp["gravity"])
 
 
-def update_scene(pkg, undistort, model1=sr.RADTAN):
+def update_scene(pkg, undistort, model1=sr.RADTAN, model0=sr.RADTAN):
     """sr.update_scene with one more track and the cut CPI table of its window.  The added track ("two then one") has camera 0's
     observations at the two oldest clones and camera 1's fifteen behind the newest clone (no bounding clones; the table serves
     them): seventeen observations, so the loop reaches it before the cap, two of them usable — and one once the table does not serve
     the oldest frame."""
-    sc, pair, tracks, names, opt = sr.update_scene(pkg, undistort, model1=model1)
-    _, _, obs = sr.stereo_scene(pkg, undistort, model1=model1)        # (seeded: the observations update_scene cut its tracks from)
+    sc, pair, tracks, names, opt = sr.update_scene(pkg, undistort, model1=model1, model0=model0)
+    _, _, obs = sr.stereo_scene(pkg, undistort, model1=model1, model0=model0)        # (seeded: the observations update_scene cut its tracks from)
     f = names["one usable"] - 1
     fid = max(tracks) + 100
     tracks = dict(tracks)

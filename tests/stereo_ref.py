@@ -13,6 +13,7 @@ from collections import Counter
 
 import numpy as np
 
+import cam_equi
 import oracle_lib
 import synth
 
@@ -158,9 +159,20 @@ class Detection:
         return np.vstack([pts, new]), np.concatenate([ids, new_ids]), currid + len(new)
 
 
+MODELS = ("radtan", "equidistant")  # (the values of PLV_CAM_*)
+
+
 class StereoRef:
-    def __init__(self, cfg, K8_left, K8_right):
-        self.cfg, self.K8 = cfg, (np.asarray(K8_left, dtype=np.float64), np.asarray(K8_right, dtype=np.float64))
+    """models: the camera model of each camera; undistort(cam, uv) -> normalised float32 points: by default the CPU oracle's radtan
+    undistortion or cam_equi.undistort on the camera's present K8 (the device's is held to 1 ulp of the latter, so a test may hand in
+    the device's own).  jitter: a numpy Generator that moves every normalised coordinate by -1, 0 or +1 ulp before RANSAC reads it
+    (test_stereo_ref_cpu.py: a run none of whose decisions hangs on the last bit gives the same lists with it)."""
+
+    def __init__(self, cfg, K8_left, K8_right, models=("radtan", "radtan"), undistort=None, jitter=None):
+        self.cfg, self.K8 = cfg, [np.array(K8_left, dtype=np.float64), np.array(K8_right, dtype=np.float64)]
+        assert all(m in MODELS for m in models)
+        self.models, self.undistort, self.jitter = tuple(models), undistort or self.model_undistort, jitter
+        self.matchings = []  # per matching that ran: (feed, camera, points handed to RANSAC, its inliers, points kept)
         self.fo = oracle_lib.load_front()
         self.det = Detection(cfg)
         self.pts = [points_array([]), points_array([])]
@@ -212,8 +224,35 @@ class StereoRef:
             pts1, ids1 = np.vstack([pts1, new]), np.concatenate([ids1, new_ids])
         return pts0, ids0, pts1, ids1
 
-    # ---- perform_matching of one camera (:829-886)
+    def model_undistort(self, cam, uv):
+        if self.models[cam] == "equidistant":
+            return cam_equi.undistort(self.K8[cam], uv)
+        return self.fo.undistort(self.K8[cam], uv)
+
+    def _normalised(self, cam, uv):
+        un = np.ascontiguousarray(self.undistort(cam, uv), dtype=F32).reshape(-1, 2)
+        if self.jitter is not None:
+            step = self.jitter.integers(-1, 2, un.shape)
+            un = np.where(step == 0, un, np.nextafter(un, np.where(step > 0, F32(np.inf), F32(-np.inf)).astype(F32))).astype(F32)
+        return un
+
+    # ---- perform_matching of one camera (:829-886), composed as the oracle's orc_perform_matching is: LK with the old positions as
+    # the initial flow, the camera's undistortion of both lists, RANSAC at 2 px over max(fx, fy), mask = status & inlier
     def match(self, cam, prev_pyr, pyr, pts_old):
+        n = len(pts_old)
+        if n == 0:
+            return pts_old, None, None
+        if n < 10:
+            return pts_old.copy(), np.zeros(n, np.uint8), None
+        pts_new, status, _ = self.fo.lk_track(prev_pyr, pyr, pts_old, pts_old)
+        n0, n1 = self._normalised(cam, pts_old), self._normalised(cam, pts_new)
+        inlier, _, _ = self.fo.ransac(n0, n1, 2.0 / max(self.K8[cam][0], self.K8[cam][1]))
+        mask = ((status != 0) & (inlier != 0)).astype(np.uint8)
+        self.matchings.append((len(self.frames) - 1, cam, n, int((inlier != 0).sum()), int(mask.sum())))
+        return pts_new, mask, n1
+
+    def match_oracle(self, cam, prev_pyr, pyr, pts_old):
+        """the same through FrontOracle.perform_matching (radtan only): what the composition is held to"""
         n = len(pts_old)
         if n == 0:
             return pts_old, None, None
@@ -329,13 +368,60 @@ def streams():
     return out
 
 
-@functools.lru_cache(maxsize=None)
-def reference_run(name):
-    """the restatement over one of the streams, computed once: (stream, [(pts0, ids0, pts1, ids1) after every frame], StereoRef)"""
-    s = {x.name: x for x in streams()}[name]
-    ref = StereoRef(s.cfg, s.K_left, s.K_right)
+# ---- the model pairings (camera 0, camera 1) and the equidistant coefficient sets (MILD and STRONG of test_gpu_equidistant.py)
+PAIRINGS = {"RR": ("radtan", "radtan"), "RE": ("radtan", "equidistant"), "ER": ("equidistant", "radtan"), "EE": ("equidistant", "equidistant")}
+EQUI_SETS = {"mild": (3.2e-3, -1.1e-3, 2.4e-3, -6.0e-4), "strong": (-0.35, 0.12, -0.03, 0.004)}
+# what test_gpu_stereo_tracker.py feeds beside the three RR streams ("cut" keeps every point under any model: it stays RR)
+PAIRING_RUNS = [("two cameras", "RE", "strong"), ("two cameras", "ER", "strong"), ("two cameras", "EE", "strong"), ("band", "EE", "strong"),
+                ("two cameras", "EE", "mild")]
+
+
+def paired_intrinsics(s, pairing, coeffs):
+    """the stream's K8 per camera, an equidistant camera's K8[4:] replaced by the coefficient set (its fx fy cx cy stay)"""
+    out = []
+    for K, model in zip((s.K_left, s.K_right), PAIRINGS[pairing]):
+        K = np.array(K, dtype=np.float64)
+        if model == "equidistant":
+            K[4:] = EQUI_SETS[coeffs]
+        out.append(K)
+    return out
+
+
+def run_stream(s, ref, K8_at=None):
+    """feeds the stream to `ref`; K8_at: frame -> (camera, K8) set before that frame is fed.  Returns the lists after every frame."""
     after = []
-    for t, left, right, ml, mr in s.frames():
+    for f, (t, left, right, ml, mr) in enumerate(s.frames()):
+        if K8_at and f in K8_at:
+            cam, K = K8_at[f]
+            ref.K8[cam] = np.array(K, dtype=np.float64)
         ref.feed(t, left, right, ml, mr)
         after.append((ref.pts[0].copy(), ref.ids[0].copy(), ref.pts[1].copy(), ref.ids[1].copy()))
-    return s, after, ref
+    return after
+
+
+@functools.lru_cache(maxsize=None)
+def reference_run(name, pairing="RR", coeffs=None):
+    """the restatement over one of the streams under one model pairing, computed once:
+    (stream, [(pts0, ids0, pts1, ids1) after every frame], StereoRef); the intrinsics it ran with are the StereoRef's K8"""
+    s = {x.name: x for x in streams()}[name]
+    K8 = paired_intrinsics(s, pairing, coeffs)
+    ref = StereoRef(s.cfg, K8[0], K8[1], models=PAIRINGS[pairing])
+    return s, run_stream(s, ref), ref
+
+
+# ---- an intrinsics change between two pairs (plv_stereo_set_intrinsics): "two cameras" under EE strong, one camera's K8 replaced
+# before pair CHANGE_AT is fed
+CHANGE_AT = 3
+
+
+def changed_intrinsics(K8):
+    """a calibration step far larger than an update makes, so that the threshold 2 / max(fx, fy) and the undistortion both show"""
+    return np.array(K8, dtype=np.float64) * np.array([1.25, 1.25, 1.0, 1.0, 0.5, 0.5, 0.5, 0.5]) + np.array([0, 0, 4.0, -3.0, 0, 0, 0, 0])
+
+
+@functools.lru_cache(maxsize=None)
+def changed_run(cam):
+    s, _, plain = reference_run("two cameras", "EE", "strong")
+    K8 = paired_intrinsics(s, "EE", "strong")
+    ref = StereoRef(s.cfg, K8[0], K8[1], models=PAIRINGS["EE"])
+    return s, run_stream(s, ref, {CHANGE_AT: (cam, changed_intrinsics(K8[cam]))}), ref

@@ -21,6 +21,7 @@ import synth
 
 RADTAN, EQUI = 0, 1
 MILD_EQUI = np.array([458.654, 457.296, 367.215, 248.375, -0.013, 0.002, -0.0005, 0.0001])
+EQUI0_COEFFS = np.array([-0.35, 0.12, -0.03, 0.004])  # camera 0 when equidistant: STRONG of test_gpu_equidistant.py on the scene's fx fy cx cy
 TRI = dict(max_cond=1e7, max_dist=100.0, max_baseline=1e3, min_dist=0.1)
 
 
@@ -314,9 +315,10 @@ def _small_rot(w):
     return synth._exp_so3(np.array(w, float))
 
 
-def stereo_scene(pkg, undistort, model1=RADTAN, calib="all", dt=0.0, seed=31, F=40, noise_px=0.4, scene_kw=None, **kw):
+def stereo_scene(pkg, undistort, model1=RADTAN, calib="all", dt=0.0, seed=31, F=40, noise_px=0.4, scene_kw=None, model0=RADTAN, **kw):
     """synth.vio_scene (15 clones, F features) seen by a pair: camera 1 has a 0.1 m baseline, a slightly rotated R_ItoC and its own
-    intrinsics (radtan, or equidistant).  State layout: IMU 15 | int0 8 | clones | ext0 6 | dt 1 | ext1 6 | int1 8.
+    intrinsics (radtan, or equidistant).  Camera 0 is the scene's camera; with model0 equidistant it keeps the scene's fx fy cx cy,
+    carries EQUI0_COEFFS and its observations are rendered through cam_equi.distort, as camera 1's are.  State layout: IMU 15 | int0 8 | clones | ext0 6 | dt 1 | ext1 6 | int1 8.
     calib: "all", "cam0" (camera 1's blocks off), "cam1" (camera 0's off), "none"; returns (sc, pair, obs) with
     obs[f] = {cam: (t, uv, uvn)} holding every clone-time observation of feature f in both cameras (noise_px each)."""
     sc = synth.vio_scene(F=F, M=15, noise_px=noise_px, seed=seed, **(scene_kw or {}))
@@ -324,16 +326,27 @@ def stereo_scene(pkg, undistort, model1=RADTAN, calib="all", dt=0.0, seed=31, F=
     sc["n_state"] = n0 + 21
     on0, on1 = calib in ("all", "cam0"), calib in ("all", "cam1")
     K1 = MILD_EQUI.copy() if model1 == EQUI else sc["K8"] * np.array([1.01, 0.99, 1.02, 0.97, 0.9, 1.1, -1.0, 0.8])
-    cams = [Cam(sc["R_ItoC"], sc["p_IinC"], sc["K8"], RADTAN, n0 if on0 else -1, sc["intr_id"] if on0 else -1),
+    K0 = np.concatenate([sc["K8"][:4], EQUI0_COEFFS]) if model0 == EQUI else sc["K8"]
+    cams = [Cam(sc["R_ItoC"], sc["p_IinC"], K0, model0, n0 if on0 else -1, sc["intr_id"] if on0 else -1),
             Cam(_small_rot([0.004, 0.012, -0.006]) @ sc["R_ItoC"], sc["p_IinC"] + np.array([-0.1, 0.002, 0.001]), K1, model1,
                 n0 + 7 if on1 else -1, n0 + 13 if on1 else -1)]
     pair = Pair(pkg, sc, cams, dt=dt, dt_id=n0 + 6 if calib != "none" else -1, **kw)
     rng = np.random.default_rng(seed + 1)
+    rng0 = np.random.default_rng(seed + 2)  # (camera 0's pixel noise when it is rendered here: camera 1's draws stay what they were)
     obs = []
     for f in range(F):
         a, b = sc["obs_ptr"][f], sc["obs_ptr"][f + 1]
         tt = sc["obs_time"][a:b].copy()
-        ft = {0: (tt - dt, sc["obs_uv"][a:b].astype(np.float32), undistort(sc["K8"], sc["obs_uv"][a:b].astype(np.float32)))}
+        if model0 == EQUI:
+            un0 = []
+            for tm in tt:
+                R, p = sc["pose_fn"](tm)
+                pc = cams[0].R @ (R @ (sc["pts"][f] - p)) + cams[0].p
+                un0.append(pc[:2] / pc[2])
+            uv0 = (cam_equi.distort(K0, np.array(un0)) + rng0.normal(0, noise_px, (len(tt), 2))).astype(np.float32)
+            ft = {0: (tt - dt, uv0, cam_equi.undistort(K0, uv0))}
+        else:
+            ft = {0: (tt - dt, sc["obs_uv"][a:b].astype(np.float32), undistort(sc["K8"], sc["obs_uv"][a:b].astype(np.float32)))}
         uv1 = []
         for tm in tt:
             R, p = sc["pose_fn"](tm)
@@ -372,9 +385,21 @@ def with_noise(ft, undistort, pair, sig0, sig1, seed):
     return out
 
 
+PAIRINGS = {"radtan-radtan": (RADTAN, RADTAN), "radtan-equidistant": (RADTAN, EQUI), "equidistant-radtan": (EQUI, RADTAN),
+            "equidistant-equidistant": (EQUI, EQUI)}  # (model0, model1) by the names the tests give their cases
+
+
+def read_as_radtan(pair):
+    """the pair with camera 0 read as radtan on the same eight numbers (what a launch that took the wrong model for it computes)"""
+    c0 = pair.cams[0]
+    return Pair(pair.pkg, pair.sc, [Cam(c0.R, c0.p, c0.K8, RADTAN, c0.ext_id, c0.int_id), pair.cams[1]], dt=pair.dt, dt_id=pair.dt_id,
+                sigma_pix=pair.sigma, **pair.kw)
+
+
 def update_scene(pkg, undistort, model1=RADTAN, **kw):
     """The database of the update tests: {id: {cam: (t, uv, uvn)}} reaching every branch of the selection (see
-    tests/test_stereo_update_ref_cpu.py, which asserts them), with the pair and the options of the call."""
+    tests/test_stereo_update_ref_cpu.py, which asserts them), with the pair and the options of the call.  model0 (stereo_scene):
+    camera 0's model."""
     sc, pair, obs = stereo_scene(pkg, undistort, model1=model1, **kw)
     t = sc["t"]
     full = [f for f in range(len(obs)) if len(obs[f][0][0]) == 15]

@@ -101,3 +101,41 @@ def test_bayer_pair_through_the_kaist_layout(pkg, pair_dataset, tmp_path):
             assert a[key] == b[key], (key, a[key], b[key])
     assert a["frames"] >= 9 and a["cam_accepted"] > 0
     assert np.array_equal(runs["device"][1], runs["host"][1]) and np.array_equal(runs["device"][2], runs["host"][2])
+
+
+# ---- a pair of equidistant (fisheye) cameras: both `distortion_model: equidistant` in the YAML
+@pytest.fixture(scope="module")
+def fisheye_pair_dataset(tmp_path_factory):
+    import synth_fisheye as sf
+    return sf.make_stereo_dataset(str(tmp_path_factory.mktemp("fisheye_pair")), seconds=4.0, cam_hz=10.0)
+
+
+def test_fisheye_pair_replays_to_an_ate(pkg, fisheye_pair_dataset, tmp_path):
+    """tests/synth_fisheye.py's drive (4 s at 10 Hz) seen by two equidistant cameras 0.5 m apart, through the driver from its
+    Kalibr-style files: the rules of tests/test_gpu_equidistant.py::test_fisheye_drive_replays_to_an_ate — it initialises, updates,
+    tracks lines on camera 0 and stays under that test's ATE bound; the same data with both cameras read as radtan (same fx fy cx cy,
+    zero coefficients) is clearly worse.  Camera 0 alone on the same 4 s is replayed for the comparison DESIGN.md reports."""
+    import synth_fisheye as sf
+    options, rp = importlib.import_module("plviwo_amd.options"), importlib.import_module("plviwo_amd.replay")
+    gt = os.path.join(fisheye_pair_dataset, "gt.txt")
+
+    def run(name, write, model):
+        traj = str(tmp_path / f"traj_{name}.txt")
+        op = options.load_options(write(str(tmp_path / name), fisheye_pair_dataset, traj, model=model))
+        stats, times, poses = rp.replay(op)
+        frac = stats["cam_accepted"] / max(stats["cam_features"], 1)
+        ate = _ate(pkg, traj, gt) if stats["initialized"] and len(times) > 2 else float("inf")
+        print(f"{name}: ATE {ate:.4f} m over {len(times)} poses, accepted {stats['cam_accepted']} / {stats['cam_features']} ({frac:.3f}), "
+              f"{stats['cam_updates']} updates in {stats['frames']} frames, lines tracked {stats['lines_tracked']}, not_psd {stats['not_psd']}")
+        return stats, ate, frac, op
+
+    stats, ate, frac, op = run("pair equidistant", sf.write_stereo_config, "equidistant")
+    assert op.est.cam.use_stereo and dict(op.est.cam.distortion_model) == {0: "equidistant", 1: "equidistant"}
+    assert stats["stereo"] and stats["pairs_skipped"] == 0 and stats["frames"] == 40
+    assert stats["initialized"] and stats["not_psd"] == 0
+    assert stats["cam_updates"] > 0 and stats["cam_accepted"] > 0
+    assert stats["lines_tracked"] > 0
+    assert ate < 0.10
+    fstats, fate, ffrac, _ = run("pair read as radtan", sf.write_stereo_config, "radtan")
+    assert ffrac < frac - 0.05 or fate > 1.5 * ate
+    run("camera 0 alone, equidistant", sf.write_config, "equidistant")

@@ -29,17 +29,19 @@ def fo():
     return oracle_lib.load_front()
 
 
-def _ref(pkg, jo, fo, oracle, model1):
-    """(scene, pair, tracks, names, options, table records, P, the restatement's first update), once per model and left unchanged"""
-    if model1 not in _REF:
-        sc, pair, tracks, names, opt, cp = scr.update_scene(pkg, fo.undistort, model1=model1)
+def _ref(pkg, jo, fo, oracle, model1, model0=sr.RADTAN):
+    """(scene, pair, tracks, names, options, table records, P, the restatement's first update), once per pairing and left unchanged"""
+    if (model0, model1) not in _REF:
+        sc, pair, tracks, names, opt, cp = scr.update_scene(pkg, fo.undistort, model1=model1, model0=model0)
         P = synth.spd_cov(sc["n_state"], seed=4) * 1e-4
-        _REF[model1] = (sc, pair, tracks, names, opt, cp, P, scr.update_points(jo, oracle, pair, tracks, P, cp, scr.table(pkg, cp), **opt))
-    return _REF[model1]
+        _REF[model0, model1] = (sc, pair, tracks, names, opt, cp, P, scr.update_points(jo, oracle, pair, tracks, P, cp, scr.table(pkg, cp), **opt))
+    return _REF[model0, model1]
 
 
 def _stereo_ctx(pkg, pair, tracks=None, P=None):
     c = pkg.Context(pkg.default_config(W, H))
+    if pair.cams[0].model == sr.EQUI:
+        c.set_camera_model("equidistant")
     c.stereo_configure(pair.cams[1].K8, pair.cams[1].model)
     for fid, ft in (tracks or {}).items():
         for cam, o in ft.items():
@@ -158,9 +160,12 @@ def _check_state(pkg, mv, before, ref_dx, what):
     assert np.abs(got["K"][0] - before["K"][0]).max() > 0 and np.abs(got["K"][1] - before["K"][1]).max() > 0
 
 
-@pytest.mark.parametrize("model1", [sr.RADTAN, sr.EQUI], ids=["radtan-radtan", "radtan-equidistant"])
-def test_cpi_update_against_restatement(pkg, jo, fo, oracle, model1):
-    sc, pair, tracks, names, opt, cp, P, ref = _ref(pkg, jo, fo, oracle, model1)
+@pytest.mark.parametrize("pairing", list(sr.PAIRINGS))
+def test_cpi_update_against_restatement(pkg, jo, fo, oracle, pairing):
+    """the pairings (camera 0, camera 1); camera 0's model is the context's (tests/test_stereo_cpi_ref_cpu.py: read as radtan, a scene
+    with camera 0 equidistant gives another selection or other verdicts)"""
+    model0, model1 = sr.PAIRINGS[pairing]
+    sc, pair, tracks, names, opt, cp, P, ref = _ref(pkg, jo, fo, oracle, model1, model0)
     n = sc["n_state"]
     c = _stereo_ctx(pkg, pair, tracks, P)
     try:

@@ -1,12 +1,16 @@
 """The stereo point update on the device — plv_triangulate_stereo, plv_build_jacobians_stereo, plv_stereo_update_points — against the
 restatement composed of oracle pieces (tests/stereo_update_ref.py; tests/test_stereo_update_ref_cpu.py pins it and the scene).
 Tolerances are the monocular tests': positions 1e-9 x max(1, largest entry) and the reprojection error 1e-7 relative
-(tests/triangulation_cases.py point_tolerances; 1e-6 absolute where camera 1 is equidistant, as tests/test_gpu_equidistant.py holds
+(tests/triangulation_cases.py point_tolerances; 1e-6 absolute where a camera of the pair is equidistant, as tests/test_gpu_equidistant.py holds
 the monocular fisheye error: the restatement's arctan is numpy's), Jacobians 1e-9 x max(1, largest entry) per array
-(tests/test_gpu_jacobian.py), the update p 1e-6, dx 1e-7, P 1e-8 (tests/test_gpu_update_frame.py test_camera_update_points)."""
+(tests/test_gpu_jacobian.py), the update p 1e-6, dx 1e-7, P 1e-8 (tests/test_gpu_update_frame.py test_camera_update_points).
+The pairings (camera 0, camera 1): radtan-radtan, radtan-equidistant, equidistant-radtan, equidistant-equidistant.  Camera 0's model
+is the context's (plv_set_camera_model), camera 1's comes with its plv_camera_side; tests/test_stereo_update_ref_cpu.py shows that a
+scene with camera 0 equidistant, read with camera 0 as radtan, gives other verdicts."""
 import numpy as np
 import pytest
 
+import cam_equi
 import oracle_lib
 import stereo_update_ref as sr
 import synth
@@ -34,17 +38,32 @@ def dev(pkg):
     c.close()
 
 
-def _update_ref(pkg, jo, fo, oracle, model1):
-    """(scene, pair, tracks, names, options, P, the restatement's first update), computed once per model and left unchanged"""
-    if model1 not in _REF:
-        sc, pair, tracks, names, opt = sr.update_scene(pkg, fo.undistort, model1=model1)
+@pytest.fixture(scope="module")
+def dev_equi(pkg):
+    c = pkg.Context(pkg.default_config(W, H))
+    c.set_camera_model("equidistant")
+    yield c
+    c.close()
+
+
+def _dev_of(pair, dev, dev_equi):
+    """the context whose model is camera 0's"""
+    return dev_equi if pair.cams[0].model == sr.EQUI else dev
+
+
+def _update_ref(pkg, jo, fo, oracle, model1, model0=sr.RADTAN):
+    """(scene, pair, tracks, names, options, P, the restatement's first update), computed once per pairing and left unchanged"""
+    if (model0, model1) not in _REF:
+        sc, pair, tracks, names, opt = sr.update_scene(pkg, fo.undistort, model1=model1, model0=model0)
         P = synth.spd_cov(sc["n_state"], seed=4) * 1e-4
-        _REF[model1] = (sc, pair, tracks, names, opt, P, sr.update_points(jo, oracle, pair, tracks, P, **opt))
-    return _REF[model1]
+        _REF[model0, model1] = (sc, pair, tracks, names, opt, P, sr.update_points(jo, oracle, pair, tracks, P, **opt))
+    return _REF[model0, model1]
 
 
 def _stereo_ctx(pkg, pair):
     c = pkg.Context(pkg.default_config(W, H))
+    if pair.cams[0].model == sr.EQUI:
+        c.set_camera_model("equidistant")
     c.stereo_configure(pair.cams[1].K8, pair.cams[1].model)
     return c
 
@@ -68,10 +87,12 @@ def _db(c):
 
 
 # ------------------------------------------------------------------ 1. triangulation
-@pytest.mark.parametrize("case", ["radtan", "equidistant", "res-poses", "time-offset"])
-def test_triangulate_stereo(pkg, dev, jo, fo, case):
-    model1 = sr.EQUI if case == "equidistant" else sr.RADTAN
-    sc, pair, tracks, names, _ = sr.update_scene(pkg, fo.undistort, model1=model1, dt=0.003 if case == "time-offset" else 0.0)
+@pytest.mark.parametrize("case", ["radtan", "equidistant", "res-poses", "time-offset", "equi-radtan", "equi-equi"])
+def test_triangulate_stereo(pkg, dev, dev_equi, jo, fo, case):
+    model1 = sr.EQUI if case in ("equidistant", "equi-equi") else sr.RADTAN
+    model0 = sr.EQUI if case in ("equi-radtan", "equi-equi") else sr.RADTAN
+    sc, pair, tracks, names, _ = sr.update_scene(pkg, fo.undistort, model1=model1, model0=model0, dt=0.003 if case == "time-offset" else 0.0)
+    dev = _dev_of(pair, dev, dev_equi)
     ids = sorted(tracks)
     feats = [tracks[i] for i in ids]
     if case == "res-poses":
@@ -91,7 +112,7 @@ def test_triangulate_stereo(pkg, dev, jo, fo, case):
         de = np.abs(err[sel] - err_o[sel])
         print(f"{case:12s} {what:22s} {len(sel):2d} features | p {dp:.1e} (tolerance {tol_p:.1e}) | error {de.max():.1e}")
         assert dp <= tol_p, (what, dp)
-        assert (de <= 1e-6).all() if model1 == sr.EQUI else (de <= 1e-7 * err_o[sel]).all(), (what, de.max())
+        assert (de <= 1e-6).all() if sr.EQUI in (model0, model1) else (de <= 1e-7 * err_o[sel]).all(), (what, de.max())
 
     # the anchor: camera 1 on a tie, else the camera with more usable observations
     close([q for q in range(len(ids)) if nv[q][0] == nv[q][1] and anchors[q] == 1], "anchor: tie")
@@ -101,7 +122,7 @@ def test_triangulate_stereo(pkg, dev, jo, fo, case):
     close(range(len(ids)), "all")
     # the mean over the cameras, not over the observations
     q = ids.index(names["camera-averaged"])
-    assert abs(err[q] - err_o[q]) <= 1e-6 and (err[q] < 3.0 or case not in ("radtan", "equidistant"))
+    assert abs(err[q] - err_o[q]) <= 1e-6 and (err[q] < 3.0 or case not in ("radtan", "equidistant", "equi-radtan", "equi-equi"))
 
 
 # ------------------------------------------------------------------ 2. Jacobians
@@ -115,14 +136,21 @@ JAC_CASES = {
     "res-poses": dict(calib="all", res=True),
     "long-40+30": dict(calib="all", long=True),
     "over-ld": dict(calib="all", ld=40),
+    # camera 0 equidistant: the intrinsic columns of both cameras carry dzeta; res poses; the second 64-lane chunk and a camera
+    # change inside it
+    "equi-radtan": dict(calib="all", model0=sr.EQUI),
+    "equi-equi": dict(calib="all", model0=sr.EQUI, model1=sr.EQUI),
+    "equi-equi-res-poses": dict(calib="all", model0=sr.EQUI, model1=sr.EQUI, res=True),
+    "equi-equi-long-40+30": dict(calib="all", model0=sr.EQUI, model1=sr.EQUI, long=True),
 }
 
 
 @pytest.mark.parametrize("case", sorted(JAC_CASES))
-def test_build_jacobians_stereo(pkg, dev, jo, fo, case):
+def test_build_jacobians_stereo(pkg, dev, dev_equi, jo, fo, case):
     kw = dict(JAC_CASES[case])
     res, long, ld = kw.pop("res", False), kw.pop("long", False), kw.pop("ld", 62)
     sc, pair, obs = sr.stereo_scene(pkg, fo.undistort, F=12, **kw)
+    dev = _dev_of(pair, dev, dev_equi)
     n = sc["n_state"]
     feats = [obs[0], sr.cut(obs[1], None, ()), sr.cut(obs[2], (), None), sr.cut(obs[3], slice(0, 9), None), sr.cut(obs[5], None, slice(3, 15)), obs[6], obs[7]]
     pts = [sc["pts"][f] for f in (0, 1, 2, 3, 5, 6, 7)]
@@ -178,9 +206,10 @@ def _check_update(out, ref, P0, c, n, what):
     assert sr.db_equal(_db(c), ref["db"]), what
 
 
-@pytest.mark.parametrize("model1", [sr.RADTAN, sr.EQUI], ids=["radtan-radtan", "radtan-equidistant"])
-def test_stereo_update_points(pkg, jo, fo, oracle, model1):
-    sc, pair, tracks, names, opt, P, ref = _update_ref(pkg, jo, fo, oracle, model1)
+@pytest.mark.parametrize("pairing", list(sr.PAIRINGS))
+def test_stereo_update_points(pkg, jo, fo, oracle, pairing):
+    model0, model1 = sr.PAIRINGS[pairing]
+    sc, pair, tracks, names, opt, P, ref = _update_ref(pkg, jo, fo, oracle, model1, model0)
     n = sc["n_state"]
     c = _stereo_ctx(pkg, pair)
     try:
@@ -229,6 +258,52 @@ def test_one_camera_equals_the_monocular_update(pkg, fo):
         assert np.abs(a["p_FinG"] - b["p_FinG"]).max() < 1e-6
         assert np.abs(a["dx"] - b["dx"]).max() <= 1e-7 * max(1.0, np.abs(a["dx"]).max())
         assert np.abs(mono.cov_download(n) - ster.cov_download(n)).max() <= 1e-8 * np.abs(P).max()
+        assert set(int(i) for i in mono.db_select(1, 1e18)) == set(int(i) for i in ster.stereo_db_ids())
+    finally:
+        mono.close()
+        ster.close()
+
+
+def test_one_equidistant_camera_equals_the_monocular_update(pkg):
+    """the same with camera 0 equidistant: a stereo context whose tracks have camera-0 observations only gives the update of a monocular
+    equidistant context.  (Camera 1 is configured radtan and has no observation: its model must not reach camera 0's rows.)"""
+    sc = synth.vio_scene(F=60, M=15, noise_px=0.0, seed=9)
+    t, n = sc["t"], sc["n_state"]
+    K8 = np.concatenate([sc["K8"][:4], sr.EQUI0_COEFFS])
+    st = pkg.StateView(sc["t"], sc["R"], sc["p"], sc["ids"], sc["R_ItoC"], sc["p_IinC"], K8, clone_R_fej=sc["Rf"], clone_p_fej=sc["pf"],
+                       intrinsic_state_id=sc["intr_id"], sigma_pix=1.5)
+    side = pkg.CameraSide(sc["R_ItoC"], sc["p_IinC"], sc["K8"])
+    P = synth.spd_cov(n, seed=4) * 1e-4
+    rng = np.random.default_rng(10)
+    mono, ster = pkg.Context(pkg.default_config(W, H)), pkg.Context(pkg.default_config(W, H))
+    try:
+        for c in (mono, ster):
+            c.set_camera_model("equidistant")
+        ster.stereo_configure(sc["K8"], 0)
+        for f in range(60):
+            a, b = sc["obs_ptr"][f], sc["obs_ptr"][f + 1]
+            un = []
+            for tm in sc["obs_time"][a:b]:
+                R, p = sc["pose_fn"](tm)
+                pc = sc["R_ItoC"] @ (R @ (sc["pts"][f] - p)) + sc["p_IinC"]
+                un.append(pc[:2] / pc[2])
+            uv = (cam_equi.distort(K8, np.array(un)) + rng.normal(0, 0.4, (b - a, 2))).astype(np.float32)
+            uvn = cam_equi.undistort(K8, uv)
+            mono.db_append_measurements(f + 1, sc["obs_time"][a:b], uv, uvn)
+            ster.stereo_db_append_measurements(f + 1, 0, sc["obs_time"][a:b], uv, uvn)
+        mono.cov_upload(P)
+        ster.cov_upload(P)
+        kw = dict(t_prev_frame=t[-2], state_time=t[-1], window_full=True, **sr.TRI)
+        a = mono.camera_update_points(st, n, 30, 15, **kw)
+        b = ster.stereo_update_points(st, side, n, 30, 15, **kw)
+        assert a["status"] == b["status"] == 0 and a["n_pool"] == b["n_pool"] and len(a["ids"]) == 30
+        assert a["accepted"].sum() >= 15                                   # (the data are consistent under the equidistant model)
+        assert np.array_equal(a["ids"], b["ids"]) and np.array_equal(a["accepted"], b["accepted"]) and a["n_rows"] == b["n_rows"]
+        dp, ddx, dP = np.abs(a["p_FinG"] - b["p_FinG"]).max(), np.abs(a["dx"] - b["dx"]).max(), np.abs(mono.cov_download(n) - ster.cov_download(n)).max()
+        print(f"equidistant camera 0 alone: accepted {int(a['accepted'].sum())} of 30 | p {dp:.1e} (1e-6) dx {ddx:.1e} (|dx| {np.abs(a['dx']).max():.1e}) P {dP:.1e} (|P| {np.abs(P).max():.1e})")
+        assert dp < 1e-6
+        assert ddx <= 1e-7 * max(1.0, np.abs(a["dx"]).max())
+        assert dP <= 1e-8 * np.abs(P).max()
         assert set(int(i) for i in mono.db_select(1, 1e18)) == set(int(i) for i in ster.stereo_db_ids())
     finally:
         mono.close()

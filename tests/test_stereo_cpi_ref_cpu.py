@@ -39,9 +39,10 @@ def test_served_rule_is_the_oracles(pkg, jo):
     assert [scr.servable(sc["t"][3:], cp, x) for x in tq2] == [bool(v) for v in jo.cpi_poses(st2, tab, tq2)[2]] == [False, False, True, True]
 
 
-@pytest.mark.parametrize("model1", [sr.RADTAN, sr.EQUI], ids=["radtan-radtan", "radtan-equidistant"])
-def test_scene_reaches_every_branch(pkg, oracle, jo, fo, model1):
-    sc, pair, tracks, names, opt, cp = scr.update_scene(pkg, fo.undistort, model1=model1)
+@pytest.mark.parametrize("pairing", list(sr.PAIRINGS))
+def test_scene_reaches_every_branch(pkg, oracle, jo, fo, pairing):
+    model0, model1 = sr.PAIRINGS[pairing]
+    sc, pair, tracks, names, opt, cp = scr.update_scene(pkg, fo.undistort, model1=model1, model0=model0)
     P = synth.spd_cov(sc["n_state"], seed=4) * 1e-4
     out = scr.update_points(jo, oracle, pair, tracks, P, cp, scr.table(pkg, cp), **opt)
     plain = sr.update_points(jo, oracle, pair, tracks, P, **opt)
@@ -72,3 +73,6 @@ def test_scene_reaches_every_branch(pkg, oracle, jo, fo, model1):
     assert len(tr["ok"]) < len(tr["order"])
     # the table changes the update: other poses, fewer rows
     assert out["n_rows"] < plain["n_rows"] and np.abs(out["dx"] - plain["dx"]).max() > 1e-6
+    if model0 == sr.EQUI:  # camera 0 read as radtan: other verdicts (the argument of test_stereo_update_ref_cpu.py, with the table)
+        wrong = scr.update_points(jo, oracle, sr.read_as_radtan(pair), tracks, P, cp, scr.table(pkg, cp), **opt)
+        assert list(wrong["ids"]) != list(out["ids"]) or list(wrong["accepted"]) != list(out["accepted"])

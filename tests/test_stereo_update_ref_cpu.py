@@ -69,9 +69,11 @@ def test_one_camera_is_the_monocular_composition(pkg, oracle, jo, fo):
     assert set(out["db"]) == {fid for fid in tracks if fid not in used and fid != 501}
 
 
-@pytest.mark.parametrize("model1", [sr.RADTAN, sr.EQUI], ids=["radtan-radtan", "radtan-equidistant"])
-def test_scene_reaches_every_branch(pkg, oracle, jo, fo, model1):
-    sc, pair, tracks, names, opt = sr.update_scene(pkg, fo.undistort, model1=model1)
+@pytest.mark.parametrize("pairing", list(sr.PAIRINGS))
+def test_scene_reaches_every_branch(pkg, oracle, jo, fo, pairing):
+    model0, model1 = sr.PAIRINGS[pairing]
+    sc, pair, tracks, names, opt = sr.update_scene(pkg, fo.undistort, model1=model1, model0=model0)
+    assert (pair.cams[0].model, pair.cams[1].model) == (model0, model1)
     n = sc["n_state"]
     assert len(sc["t"]) == 15 and 38 <= len(tracks) <= 42
     assert np.linalg.norm(pair.cams[1].p - pair.cams[0].p) == pytest.approx(0.1, abs=0.01) and not np.allclose(pair.cams[1].K8, pair.cams[0].K8)
@@ -113,6 +115,33 @@ def test_scene_reaches_every_branch(pkg, oracle, jo, fo, model1):
     # whatever was accepted is gone, the rest is there
     gone = {int(i) for i, a in zip(out["ids"], out["accepted"]) if a} - {names["late in cam1"]}
     assert not gone & set(out["db"]) and set(tracks) - gone - {names["late in cam1"]} <= set(out["db"])
+
+
+@pytest.mark.parametrize("pairing", ["equidistant-radtan", "equidistant-equidistant"])
+def test_equidistant_camera_0_decides_the_scene(pkg, oracle, jo, fo, pairing):
+    """the scenes with camera 0 equidistant still accept and reject — in the triangulation and at the gate — and the same scene with
+    camera 0 read as radtan (its eight numbers as fx fy cx cy k1 k2 p1 p2) gives other verdicts: a launch that takes the wrong model
+    for camera 0 does not pass the GPU tests' comparison of `ok`, the selection and `accepted`"""
+    model0, model1 = sr.PAIRINGS[pairing]
+    sc, pair, tracks, names, opt = sr.update_scene(pkg, fo.undistort, model1=model1, model0=model0)
+    ids = sorted(tracks)
+    feats = [tracks[i] for i in ids]
+    p_o, ok_o, err_o, _, _, nv = sr.triangulate_batch(jo, pair, feats)
+    assert ok_o.sum() >= 25 and (ok_o == 0).any()
+    P = synth.spd_cov(sc["n_state"], seed=4) * 1e-4
+    out = sr.update_points(jo, oracle, pair, tracks, P, **opt)
+    assert out["status"] == 0 and out["accepted"].sum() >= 10 and (out["accepted"] == 0).any()
+    wrong = sr.read_as_radtan(pair)
+    p_w, ok_w, err_w, _, _, _ = sr.triangulate_batch(jo, wrong, feats)
+    both = (ok_o > 0) & (ok_w > 0) & np.array([n[0] > 0 for n in nv])
+    assert both.sum() >= 10
+    consistent = lambda ok, err: [bool(o) and e < 3.0 for o, e in zip(ok, err)]
+    assert consistent(ok_o, err_o) != consistent(ok_w, err_w)                       # the 3 px test of the selection
+    assert np.abs(err_w[both] - err_o[both]).min() > 1e-3                            # every error camera 0 has a part in
+    out_w = sr.update_points(jo, oracle, wrong, tracks, P, **opt)
+    assert list(out_w["ids"]) != list(out["ids"]) or list(out_w["accepted"]) != list(out["accepted"])
+    print(f"{pairing}: triangulated {int(ok_o.sum())} of {len(ids)}, accepted {int(out['accepted'].sum())} of {len(out['ids'])}; camera 0 read as "
+          f"radtan: consistent {sum(consistent(ok_w, err_w))} (was {sum(consistent(ok_o, err_o))}), selected {len(out_w['ids'])}, accepted {int(out_w['accepted'].sum())}")
 
 
 @pytest.mark.parametrize("calib", ["all", "cam0", "cam1", "none"])
